@@ -13,7 +13,10 @@ N = 1 workload: C3 = ShaderBall x16 + plane, 4 point lights, GGX PBR + normal ma
 configuration BASELINE.json's metric "4K PBR ShaderBall" and its >=100 Mpixels/s target are quoted on).
 N > 1: the same frame (C4) split into interleaved screen bands => "scaling": "strong".
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline figure needs: set-up, warm-up, the K timed
+steps.  `--full` adds everything else the line can carry -- the k_shade events and `roofline` (with the one-frame-in-flight,
+two-frames-in-flight and k_present passes), the sampled `clocks`, the 1080p figure `also`, the CPU baseline and the two parity
+checks against the oracle.  `--dump-outputs DIR` writes the frame of the last timed step as .npy files (see `dump_outputs`).
 """
 from __future__ import annotations
 
@@ -232,6 +235,36 @@ def device_pci_address(index):
     except OSError:
         pass
     return None
+
+
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: at most this much in all (64 MB)
+DUMP_SAMPLE_PIXELS = 1 << 20    # ... else this many pixels, the same seeded choice for every array of the run
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(directory, arrays):
+    """Write `arrays` (name -> [H, W, C] frame of the last timed step) to directory/<name>.npy as float32.  When the whole frames
+    would exceed DUMP_LIMIT_BYTES, a fixed sample of DUMP_SAMPLE_PIXELS pixels is written instead: <name>_sample.npy ([n, C]) and
+    sample_pixels.npy (their row-major pixel indices, float64, ascending), drawn from a generator seeded with DUMP_SEED -- the same
+    pixels for the same frame size, so two builds can be compared output for output.  Returns the names of the files written."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    written = []
+    if sum(a.size * 4 for a in arrays.values()) <= DUMP_LIMIT_BYTES:
+        for name, a in arrays.items():
+            np.save(os.path.join(directory, f"{name}.npy"), a.astype(np.float32))
+            written.append(f"{name}.npy")
+        return written
+    pixels = {a.shape[0] * a.shape[1] for a in arrays.values()}
+    assert len(pixels) == 1, "the frames of one run have one size"
+    n = pixels.pop()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SAMPLE_PIXELS), replace=False))
+    np.save(os.path.join(directory, "sample_pixels.npy"), idx.astype(np.float64))
+    written.append("sample_pixels.npy")
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}_sample.npy"), a.reshape(n, -1)[idx].astype(np.float32))
+        written.append(f"{name}_sample.npy")
+    return written
 
 
 def cpu_quota():
@@ -604,7 +637,7 @@ def supervise(args, argv):
     return 1
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -638,7 +671,7 @@ def main():
                     help="do not sample this GPU's sclk / mclk / socket power from sysfs during the run (`clocks` in the line)")
     ap.add_argument("--clock-period-ms", type=float, default=2.0, help="sampling period of the clock thread")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the 1080p figure the default C3 run adds to its line (`also.c2_1080p`): the counter passes of "
+                    help="skip the 1080p figure a --full C3 run adds to its line (`also.c2_1080p`): the counter passes of "
                          "tools/profile_round.sh average every launch of a kernel in the process")
     ap.add_argument("--worker", action="store_true",
                     help="(internal) this process is one rank of one attempt, started by the supervisor (see `supervise`)")
@@ -662,9 +695,24 @@ def main():
     ap.add_argument("--present", action="store_true",
                     help="every step also runs the presentation step (tone map + sRGB + RGBA8, SURVEY 8(f) rank 1); "
                          "for N > 1 the RGBA8 shards are gathered instead of the fp32 ones (a quarter of the payload)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: k_shade events and `roofline` (with its "
+                         "extra passes after the timed region), `clocks`, `also.c2_1080p`, the CPU baseline and the parity checks "
+                         "against the oracle.  Off: the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last of them computed (what a caller of the path reads "
+                         "back: the RGBA32F frame, and / or the presented RGBA8 frame with --present) to DIR/<name>.npy as "
+                         "float32; a seeded sample of pixels when the whole frames exceed 64 MB (see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.frames_in_flight is None:
         args.frames_in_flight = 4 if args.workload == "c2" else 3
+    return args
+
+
+def main():
+    args = parse_args()
 
     # N > 1: this process is a SUPERVISOR unless it was started as a worker (--worker).  It starts the ranks of one attempt
     # after the other as CHILD processes -- before it has imported torch or made any HIP call (a process that has touched
@@ -937,7 +985,7 @@ def main():
     gc.disable()
     # The clocks of this GPU, sampled from sysfs on a thread of its own from here to the end of the measurements
     clocks = None
-    if not args.no_clock_samples:
+    if args.full and not args.no_clock_samples:
         addr = device_pci_address(local_rank)
         clocks = ClockSampler(addr, args.clock_period_ms * 1e-3).start() if addr else None
     # a few dozen frames let every frame slot learn its item count (the shading launch of a slot is sized from the slot's
@@ -946,7 +994,7 @@ def main():
         step()
     fence()
     layout, layout_decided, layout_ms = r.stream_layout_state()
-    use_events = not args.no_timing_events
+    use_events = args.full and not args.no_timing_events
     # HIP events around k_shade on sampled steps of the timed region: ten samples of a long run, but never closer than every
     # fourth step (a pair on every step costs ~6 % of the rate it describes; the driver's 20-step run gets five samples)
     event_stride = max(1, min(args.event_stride, args.steps)) if args.event_stride > 0 else max(min(4, max(1, args.steps // 2)), args.steps // 10)
@@ -1039,6 +1087,18 @@ def main():
     mark("timed")
     if r.capacity_growths() != overflow_before:   # (overflows healed during the warm-up frames do not count)
         raise SystemExit("a capacity overflowed inside the timed region: the frames timed were incomplete")
+    if args.dump_outputs and rank == 0:
+        # the frame of the last timed step, before anything of --full renders again (fence() has drained every stream)
+        if dist_path:
+            last = (step_no[0] - 1) & 1
+            whole = r.read_whole_frame(form) if args.exchange == "native" else \
+                (frame8_t[last] if args.present else frame_t[last]).cpu().numpy()
+            outputs = {"presented" if args.present else "frame": whole}
+        else:
+            outputs = {} if args.present_fused else {"frame": r.read_framebuffer()}
+            if args.present:
+                outputs["presented"] = r.read_presented()
+        dump_outputs(args.dump_outputs, outputs)
     gc.enable()
     # The host's side of the timed region: if the host were the bottleneck it would never be blocked
     # on a frame slot; if the GPU is, the host spends what is left of every frame period blocked.
@@ -1225,7 +1285,8 @@ def main():
     # north_star asks for 1080p AND 4K figures: after the timed region of the default (C3) run, C2 -- ShaderBall, one point
     # light, 1920x1080 -- for a hundred steps with ITS four frames in flight, in a context of its own
     also = None
-    if args.workload == "c3" and not dist_path and not args.present and args.render_pass == "forward" and not args.opt and not args.no_also:
+    if (args.full and args.workload == "c3" and not dist_path and not args.present and args.render_pass == "forward" and not args.opt
+            and not args.no_also):
         cfg2 = configs.CONFIGS["c2"]
         r.synchronize()
         rb = Renderer(cfg2.width, cfg2.height, device=local_rank)
@@ -1306,7 +1367,7 @@ def main():
     # supervisor timed them out, and the ladder then repeated a failure that no other exchange could cure).
     failure = None
     try:
-        if rank == 0 and not args.no_cpu_baseline:   # (N > 1: on rank 0's host cores, while the other ranks wait at the final barrier)
+        if rank == 0 and args.full and not args.no_cpu_baseline:   # (N > 1: on rank 0's host cores, while the other ranks wait at the final barrier)
             cpu, oracle_frame = cpu_baseline(cfg, maps, args.cpu_budget)
             if cpu["n_shaded"] != n_shaded_total:
                 raise SystemExit(f"GPU shaded {n_shaded_total} pixels, oracle {cpu['n_shaded']}: parity broken")

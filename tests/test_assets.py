@@ -2,9 +2,10 @@
   * files written by the encoders in this test (every PNG colour type, bit depth, filter, Adam7, tRNS; a binary FBX
     with zlib arrays, Direct and IndexToDirect layers; an OBJ with negative indices and polygons),
   * the in-repo Python readers that minted the committed fixtures (tools/fbx_geometry.py, tools/obj_loader.py),
-  * and, where the reference is mounted (authoring container only), its real assets against the committed fixtures:
-    ShaderBall.fbx -> shaderball_vertices.npz, gizmo.obj -> gizmo.npz, every PNG -> the hash of what the reference's own
-    stb_image 2.25 decodes (tests/golden/reference_png_sha256.json).
+  * and the reference's real assets against the committed fixtures: ShaderBall.fbx -> shaderball_vertices.npz, gizmo.obj ->
+    gizmo.npz, PNGs -> the hash of what the reference's own stb_image 2.25 decodes (tests/golden/reference_png_sha256.json).
+    The meshes and the pinned PNGs of at most 300 KB are committed under tests/golden/assets (tools/make_fixtures.py
+    reference_assets); where the reference itself is mounted, every one of its PNGs is checked too.
 Host-only functions: no GPU needed."""
 import hashlib
 import json
@@ -20,6 +21,7 @@ from bibim_renderer_amd import assets
 
 REF = os.environ.get("BB_REFERENCE", "/root/reference")
 have_ref = os.path.isdir(os.path.join(REF, "resources"))
+ASSETS = os.path.join(GOLDEN, "assets")   # the reference's meshes and its smaller PNGs, as they are
 
 
 # ------------------------------------------------------------------------------------------------ PNG
@@ -175,18 +177,28 @@ def test_png_rejects_garbage():
         assets.decode_png(corrupt)
 
 
-@pytest.mark.skipif(not have_ref, reason="reference assets are only mounted in the authoring container")
 def test_png_every_reference_texture_decodes_like_the_references_stb_image():
     pins = json.load(open(os.path.join(GOLDEN, "reference_png_sha256.json")))
     assert len(pins) >= 40
-    for rel, pin in pins.items():
-        img = assets.load_png(os.path.join(REF, "resources", rel))
+    committed = {os.path.relpath(os.path.join(base, f), ASSETS).replace(os.sep, "/")
+                 for base, _dirs, files in os.walk(ASSETS) for f in files if f.endswith(".png")}
+    assert len(committed) >= 20 and committed <= set(pins)
+    roots = [(rel, os.path.join(ASSETS, rel)) for rel in sorted(committed)]
+    if have_ref:
+        roots += [(rel, os.path.join(REF, "resources", rel)) for rel in sorted(pins)]
+    kinds = set()
+    for rel, path in roots:
+        pin = pins[rel]
+        img = assets.load_png(path)
         assert img.shape == (pin["h"], pin["w"], 4), rel
         assert hashlib.sha256(img.tobytes()).hexdigest() == pin["sha256_rgba8"], rel
+        head = open(path, "rb").read(26)
+        kinds.add((head[24], head[25]))    # (bit depth, colour type) of the IHDR chunk
+    assert {(8, 0), (16, 0), (8, 2), (8, 6)} <= kinds   # grey 8 / 16 bit, RGB, RGBA: every kind the reference ships
     d = json.load(open(os.path.join(GOLDEN, "default_texels.json")))["maps"]
     for name, m in d.items():
         if m:
-            img = assets.load_png(os.path.join(REF, "resources", "pbr", "default", name + ".png"))
+            img = assets.load_png(os.path.join(ASSETS, "pbr", "default", name + ".png"))
             assert (img == np.array(m["texel"], np.uint8)).all()
 
 
@@ -331,9 +343,8 @@ def test_packaged_shaderball_mesh_is_the_pinned_conversion():
     assert hashlib.sha256(v.tobytes()).hexdigest() == info["sha256_f32le"]
 
 
-@pytest.mark.skipif(not have_ref, reason="reference assets are only mounted in the authoring container")
 def test_fbx_reader_on_shaderball_matches_the_committed_fixture():
-    v = assets.load_fbx_vertices(os.path.join(REF, "resources", "ShaderBall.fbx"))
+    v = assets.load_fbx_vertices(os.path.join(ASSETS, "ShaderBall.fbx"))
     want = np.load(os.path.join(ROOT, "bibim_renderer_amd", "data", "shaderball_vertices.npz"))["vertices"]   # package data, hash pinned below
     info = json.load(open(os.path.join(GOLDEN, "shaderball_vertices.json")))
     assert v.shape == (29328, 11) and np.array_equal(v.view(np.uint32), want.view(np.uint32))
@@ -372,9 +383,8 @@ def test_obj_reader(tmp_path):
         assets.load_obj_gizmo(str(tmp_path / "missing.obj"))
 
 
-@pytest.mark.skipif(not have_ref, reason="reference assets are only mounted in the authoring container")
 def test_obj_reader_on_the_gizmo_matches_the_committed_fixture():
-    v, idx = assets.load_obj_gizmo(os.path.join(REF, "resources", "gizmo.obj"))
+    v, idx = assets.load_obj_gizmo(os.path.join(ASSETS, "gizmo.obj"))
     g = np.load(os.path.join(GOLDEN, "gizmo.npz"))
     assert np.array_equal(v.view(np.uint32), np.asarray(g["vertices"], np.float32).view(np.uint32))
     assert np.array_equal(idx, g["indices"]) and idx.size == 594 * 3

@@ -5,6 +5,8 @@ import json
 import time
 import os
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -421,3 +423,40 @@ def test_cpu_quota_reads_the_cgroup(tmp_path, monkeypatch):
     monkeypatch.setattr(builtins, "open", fake({"/sys/fs/cgroup/cpu.max": None, "/sys/fs/cgroup/cpu/cpu.cfs_quota_us": str(q),
                                                 "/sys/fs/cgroup/cpu/cpu.cfs_period_us": str(per)}))
     assert bench.cpu_quota() == 2.5
+
+
+def test_plain_run_is_lean_and_full_is_asked_for():
+    """`bench.py --gpus 1 --steps N --warmup W` measures the headline figure only; everything else waits for --full"""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_within_the_budget(tmp_path):
+    """--dump-outputs: whole frames as float32 when they fit in 64 MB, else the same seeded sample of pixels of every frame"""
+    import bench
+    rng = np.random.default_rng(1)
+    small = rng.random((90, 160, 4), dtype=np.float32)
+    assert bench.dump_outputs(str(tmp_path / "s"), {"frame": small}) == ["frame.npy"]
+    got = np.load(tmp_path / "s" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    # the 1080p frame and its presented form: 66.4 MB of float32 together, just over the limit
+    c2 = rng.random((1080, 1920, 4), dtype=np.float32)
+    assert sorted(bench.dump_outputs(str(tmp_path / "p"), {"frame": c2, "presented": c2})) == \
+        ["frame_sample.npy", "presented_sample.npy", "sample_pixels.npy"]
+    h, w = 2160, 3840      # the headline frame: 127 MiB of RGBA32F
+    frame = np.arange(h * w * 4, dtype=np.float32).reshape(h, w, 4)
+    rgba8 = (np.arange(h * w * 4) % 251).astype(np.uint8).reshape(h, w, 4)
+    names = bench.dump_outputs(str(tmp_path / "b"), {"frame": frame, "presented": rgba8})
+    assert sorted(names) == ["frame_sample.npy", "presented_sample.npy", "sample_pixels.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / n) for n in names) <= 64e6
+    idx = np.load(tmp_path / "b" / "sample_pixels.npy")
+    assert idx.dtype == np.float64 and idx.size == bench.DUMP_SAMPLE_PIXELS and np.all(np.diff(idx) > 0) and idx[-1] < h * w
+    i = idx.astype(np.int64)
+    fs, ps = np.load(tmp_path / "b" / "frame_sample.npy"), np.load(tmp_path / "b" / "presented_sample.npy")
+    assert fs.dtype == ps.dtype == np.float32 and fs.shape == ps.shape == (idx.size, 4)
+    assert np.array_equal(fs, frame.reshape(-1, 4)[i]) and np.array_equal(ps, rgba8.reshape(-1, 4)[i].astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "c"), {"frame": frame})     # the same pixels from run to run
+    assert np.array_equal(np.load(tmp_path / "c" / "sample_pixels.npy"), idx)

@@ -47,7 +47,7 @@ def test_native_collective_with_one_rank(extra):
 def test_two_ranks_on_one_gpu(exchange, extra):
     env = dict(os.environ, BBR_BENCH_BACKEND="gloo", BBR_BENCH_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--exchange", exchange] + COMMON + extra
+           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--exchange", exchange, "--full"] + COMMON + extra
     out = _line(subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env))
     assert out["verified_against_unpartitioned_render"] is True and out["n_gpus"] == 2
     assert out["scaling"] == "strong"
@@ -111,12 +111,13 @@ def test_a_rank_that_stalls_behind_the_line_does_not_walk_the_ladder_alone():
 
 def test_bare_bench_command_with_two_gpus_launches_its_own_ranks():
     """`python3 bench.py --gpus 2 --steps 20 --warmup 5` with no launcher around it (what a driver that reuses its N = 1
-    command form would run): bench.py starts the two ranks itself and relays rank 0's line.  Rehearsed on the one GPU."""
+    command form would run): bench.py starts the two ranks itself and relays rank 0's line.  Rehearsed on the one GPU, with
+    --full for the per-rank figures."""
     env = dict(os.environ, BBR_BENCH_BACKEND="gloo", BBR_BENCH_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = _line(subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--workload", "c2",
-                                "--verify"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env))
+                                "--verify", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env))
     assert out["n_gpus"] == 2 and out["verified_against_unpartitioned_render"] is True
     assert out["exchange"]["ranks_in_communicator"] == 2 and out["exchange"]["bytes_per_rank_block"] > 0
     assert out["exchange"]["who"] == "torch" and out["exchange"]["attempts"] == []   # (gloo rehearsal: the ladder starts at torch)

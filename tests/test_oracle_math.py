@@ -1,6 +1,6 @@
 """Row A0: the oracle's restatement of vector_math.cpp / camera.cpp is bit-identical to the reference's own
-sources -- via the committed golden vectors (minted from oracle/_ref) and, when oracle/_ref is present
-(authoring container), live on random inputs."""
+sources -- via the committed golden vectors (minted from oracle/_ref), among them 200 seeded random inputs per function, and,
+when oracle/_ref is present, live on those inputs."""
 import ctypes as C
 import json
 import os
@@ -67,35 +67,43 @@ def test_survey_sample_values():
     assert m[0, 0] == np.float32(3.13916471e-09)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libbb_ref.so")),
-                    reason="oracle/_ref is only built where /root/reference exists")
 def test_oracle_matches_compiled_reference_live():
-    ref = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libbb_ref.so"))
+    """200 seeded random inputs per function against what the reference's own vector_math.cpp / camera.cpp returned for them
+    (tests/golden/math_random.npz, minted from oracle/_ref by tools/make_fixtures.py math_random) -- and, where oracle/_ref is
+    built, against the compiled reference itself on the same inputs."""
+    g = np.load(os.path.join(GOLDEN, "math_random.npz"))
+    lib_path = os.path.join(ROOT, "oracle", "_ref", "libbb_ref.so")
+    ref = C.CDLL(lib_path) if os.path.exists(lib_path) else None
     P, f = C.c_void_p, C.c_float
-    ref.ref_mat4_mul.argtypes = [P, P, P]; ref.ref_mat4_inverse.argtypes = [P, P]
-    ref.ref_mat4_perspective.argtypes = [f, f, f, f, P]; ref.ref_camera_view.argtypes = [P, f, f, P]
-    ref.ref_mat4_look_at.argtypes = [P, P, P, P]
-    for n in "xyz":
-        getattr(ref, f"ref_mat4_rotate_{n}").argtypes = [f, P]
-    rng = np.random.Generator(np.random.PCG64(99))
-    p = lambda a: a.ctypes.data_as(P)
-    for _ in range(200):
-        a = rng.standard_normal((4, 4)).astype(np.float32) * np.float32(10 ** rng.uniform(-2, 2))
-        b = rng.standard_normal((4, 4)).astype(np.float32)
-        o = np.zeros((4, 4), np.float32)
-        ref.ref_mat4_mul(p(a), p(b), p(o)); assert _bits(o) == _bits(bbo.mat_mul(a, b))
-        ref.ref_mat4_inverse(p(a), p(o)); assert _bits(o) == _bits(bbo.mat_inverse(a))
-        d = float(rng.uniform(-720, 720))
+    if ref is not None:
+        ref.ref_mat4_mul.argtypes = [P, P, P]; ref.ref_mat4_inverse.argtypes = [P, P]
+        ref.ref_mat4_perspective.argtypes = [f, f, f, f, P]; ref.ref_camera_view.argtypes = [P, f, f, P]
+        ref.ref_mat4_look_at.argtypes = [P, P, P, P]
         for n in "xyz":
-            getattr(ref, f"ref_mat4_rotate_{n}")(d, p(o)); assert _bits(o) == _bits(getattr(bbo, f"mat_rotate_{n}")(d))
-        fov, asp = float(rng.uniform(5, 170)), float(rng.uniform(0.2, 4))
-        ref.ref_mat4_perspective(fov, asp, 0.1, 1000.0, p(o)); assert _bits(o) == _bits(bbo.mat_perspective(fov, asp, 0.1, 1000.0))
-        pos = rng.standard_normal(3).astype(np.float32) * 5
-        yaw, pitch = float(rng.uniform(-180, 180)), float(rng.uniform(-89, 89))
-        ref.ref_camera_view(p(pos), yaw, pitch, p(o)); assert _bits(o) == _bits(bbo.camera_view(pos, yaw, pitch))
-        eye, tgt = rng.standard_normal(3).astype(np.float32), rng.standard_normal(3).astype(np.float32) * 4
-        up = np.array([0, 1, 0], np.float32)
-        ref.ref_mat4_look_at(p(eye), p(tgt), p(up), p(o)); assert _bits(o) == _bits(bbo.mat_look_at(eye, tgt, up))
+            getattr(ref, f"ref_mat4_rotate_{n}").argtypes = [f, P]
+    p = lambda a: a.ctypes.data_as(P)
+    up = np.array([0, 1, 0], np.float32)
+    assert g["in_a"].shape == (200, 4, 4)
+    for i in range(200):
+        a, b = np.ascontiguousarray(g["in_a"][i]), np.ascontiguousarray(g["in_b"][i])
+        d, fov, asp = float(g["in_deg"][i]), float(g["in_fov"][i]), float(g["in_aspect"][i])
+        pos, yaw, pitch = np.ascontiguousarray(g["in_pos"][i]), float(g["in_yaw"][i]), float(g["in_pitch"][i])
+        eye, tgt = np.ascontiguousarray(g["in_eye"][i]), np.ascontiguousarray(g["in_target"][i])
+        mine = {"mul": bbo.mat_mul(a, b), "inverse": bbo.mat_inverse(a), "perspective": bbo.mat_perspective(fov, asp, 0.1, 1000.0),
+                "camera_view": bbo.camera_view(pos, yaw, pitch), "look_at": bbo.mat_look_at(eye, tgt, up),
+                **{f"rotate_{n}": getattr(bbo, f"mat_rotate_{n}")(d) for n in "xyz"}}
+        for name, m in mine.items():
+            assert _bits(m) == _bits(g[f"out_{name}"][i]), (name, i)
+        if ref is None:
+            continue
+        o = np.zeros((4, 4), np.float32)
+        ref.ref_mat4_mul(p(a), p(b), p(o)); assert _bits(o) == _bits(mine["mul"])
+        ref.ref_mat4_inverse(p(a), p(o)); assert _bits(o) == _bits(mine["inverse"])
+        for n in "xyz":
+            getattr(ref, f"ref_mat4_rotate_{n}")(d, p(o)); assert _bits(o) == _bits(mine[f"rotate_{n}"])
+        ref.ref_mat4_perspective(fov, asp, 0.1, 1000.0, p(o)); assert _bits(o) == _bits(mine["perspective"])
+        ref.ref_camera_view(p(pos), yaw, pitch, p(o)); assert _bits(o) == _bits(mine["camera_view"])
+        ref.ref_mat4_look_at(p(eye), p(tgt), p(up), p(o)); assert _bits(o) == _bits(mine["look_at"])
 
 
 def test_layout_sizes():

@@ -5,10 +5,11 @@ metal (roughness 46/255, metallic 255, mean albedo (243, 215, 148)) -- the corne
 (1 / (pi a^2) with a = roughness^2 = 0.033: D up to ~300) and where the two evaluation orders of the light loop are furthest
 apart.  The seeded maps of the other tests never go below roughness 0.15.
 
-* CPU (authoring container only: the reference's PNGs cannot travel): the set is loaded with the product's own PNG decoder
-  and createPBRMaterialSet's rule for missing maps (src/render.cpp:1328-1336: the `default` material's map), C2 is rendered
-  by the oracle in contract and in literal form; BASELINE's tolerance and finiteness are asserted, and the statistics SURVEY
-  quotes are pinned.
+* CPU: the set as createPBRMaterialSet assembles it (src/render.cpp:1328-1336: the `default` material's map for each map it
+  lacks), C2 and C3 rendered by the oracle in contract and in literal form; BASELINE's tolerance and finiteness are asserted,
+  and the statistics SURVEY quotes are pinned.  The set travels as tests/golden/light_gold_512.npz (decoded by the product's
+  PNG reader and box-filtered from 2048^2: tools/make_fixtures.py light_gold); where the reference is mounted, its 2048^2 PNGs
+  go through the same checks, and the fixture is checked to be their box filter.
 * GPU (travels): a seeded stand-in with the same statistics at full C3 size, HIP frame against the literal form and bit for
   bit against the contract form.
 """
@@ -19,7 +20,7 @@ import pytest
 
 from bibim_renderer_amd import configs, textures
 from oracle import bbo, scenes
-from tests.conftest import REFERENCE, assert_frame_close
+from tests.conftest import GOLDEN, REFERENCE, assert_frame_close
 
 
 def assert_within_baseline(img, literal):
@@ -59,19 +60,33 @@ def light_gold_stand_in(size=2048, seed=0x601D):
             "metallic": rgba(255, 255, 255), "roughness": rgba(r8, r8, r8), "ao": rgba(255, 255, 255), "normal": m["normal"]}
 
 
-@pytest.mark.skipif(not os.path.isdir(LIGHT_GOLD), reason="/root/reference is not present (authoring container only)")
 def test_light_gold_through_the_oracle_in_both_forms():
-    from bibim_renderer_amd import assets
-    maps = {}
-    for name in ("albedo", "metallic", "roughness", "ao", "normal", "height"):
-        f = os.path.join(LIGHT_GOLD, name + ".png")
-        if not os.path.exists(f):                    # src/render.cpp:1328-1336: the default material's map
-            f = os.path.join(DEFAULT, name + ".png")
-        maps[name] = assets.load_png(f)
-    assert not os.path.exists(os.path.join(LIGHT_GOLD, "ao.png")) and maps["ao"].shape[:2] == (16, 16)
-    # the statistics SURVEY 8(d) quotes for this set
-    assert abs(float(maps["roughness"][..., 0].mean()) - 46.0) < 1.5 and int(maps["metallic"][..., 0].min()) == 255
-    assert np.allclose(maps["albedo"][..., :3].reshape(-1, 3).mean(0), (243, 215, 148), atol=1.5)
+    g = np.load(os.path.join(GOLDEN, "light_gold_512.npz"))
+    sets = [{name: g[name] for name in g.files}]
+    if os.path.isdir(LIGHT_GOLD):
+        from bibim_renderer_amd import assets
+        maps = {}
+        for name in ("albedo", "metallic", "roughness", "ao", "normal", "height"):
+            f = os.path.join(LIGHT_GOLD, name + ".png")
+            if not os.path.exists(f):                    # src/render.cpp:1328-1336: the default material's map
+                f = os.path.join(DEFAULT, name + ".png")
+            maps[name] = assets.load_png(f)
+        assert not os.path.exists(os.path.join(LIGHT_GOLD, "ao.png"))
+        for name, a in maps.items():                     # the fixture is the box filter of these maps
+            n = sets[0][name].shape[0]
+            k = a.shape[0] // n
+            want = np.rint(a.reshape(n, k, n, k, 4).astype(np.float64).mean((1, 3))).astype(np.uint8) if k > 1 else a
+            assert np.array_equal(sets[0][name], want), name
+        sets.append(maps)
+    for maps in sets:
+        assert maps["ao"].shape[:2] == (16, 16) and maps["albedo"].shape[0] >= 512
+        # the statistics SURVEY 8(d) quotes for this set
+        assert abs(float(maps["roughness"][..., 0].mean()) - 46.0) < 1.5 and int(maps["metallic"][..., 0].min()) == 255
+        assert np.allclose(maps["albedo"][..., :3].reshape(-1, 3).mean(0), (243, 215, 148), atol=1.5)
+        _both_forms(maps)
+
+
+def _both_forms(maps):
     for cfg, peak in ((configs.C2, 500.0), (configs.C3, 100.0)):   # (C3: the headline workload, 16 balls and 4 lights at 4K)
         sc = scenes.shaderball_scene(cfg, bbo.MaterialData(maps))
         contract, st_c = bbo.render_parallel(sc)

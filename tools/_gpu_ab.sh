@@ -10,9 +10,9 @@ for W in c3 c2; do
 done
 for lib in "$@"; do
   n=$(basename $lib .so)
-  BBR_LIB=$R/$lib timeout -k 10 200 python3 bench.py --no-cpu-baseline > $O/bench_c3_$n.json 2> $O/bench_c3_$n.err || exit 1
-  BBR_LIB=$R/$lib timeout -k 10 200 python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_c3drv_$n.json 2>> $O/bench_c3_$n.err || exit 1
-  BBR_LIB=$R/$lib timeout -k 10 200 python3 bench.py --no-cpu-baseline --workload c2 > $O/bench_c2_$n.json 2>> $O/bench_c3_$n.err || exit 1
+  BBR_LIB=$R/$lib timeout -k 10 200 python3 bench.py --full --no-cpu-baseline > $O/bench_c3_$n.json 2> $O/bench_c3_$n.err || exit 1
+  BBR_LIB=$R/$lib timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_c3drv_$n.json 2>> $O/bench_c3_$n.err || exit 1
+  BBR_LIB=$R/$lib timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --workload c2 > $O/bench_c2_$n.json 2>> $O/bench_c3_$n.err || exit 1
 done
 cat $O/alone_c3.txt $O/alone_c2.txt
 python3 - <<PY

@@ -10,9 +10,9 @@ for a in "$@"; do
   i=$((i+1))
   for W in c3 c2 c5; do
     S=""; [ $W = c5 ] && S="--steps 60"
-    timeout -k 10 200 python3 bench.py --no-cpu-baseline --workload $W $S $a > $O/m${i}_$W.json 2> $O/m${i}_$W.err || { tail -5 $O/m${i}_$W.err; exit 1; }
+    timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --workload $W $S $a > $O/m${i}_$W.json 2> $O/m${i}_$W.err || { tail -5 $O/m${i}_$W.err; exit 1; }
   done
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 $a > $O/m${i}_c3drv.json 2>> $O/m${i}_c3.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 5 $a > $O/m${i}_c3drv.json 2>> $O/m${i}_c3.err || exit 1
 done
 python3 - <<PY
 import json, glob, os

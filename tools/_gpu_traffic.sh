@@ -4,7 +4,7 @@ W=${1:-c3}
 R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/traffic_$W
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --workload $W --steps 40 --warmup 5 --no-cpu-baseline"
+B="python3 $R/bench.py --workload $W --steps 40 --warmup 5 --full --no-cpu-baseline"
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d ${O}_fetch --output-format csv -- $B > /dev/null 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d ${O}_write --output-format csv -- $B > /dev/null 2>&1
 cd $R && python3 tools/profile_summary.py hbm $W ${O}_fetch ${O}_write $O.json && python3 -c "

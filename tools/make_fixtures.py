@@ -2,6 +2,10 @@
 
   shaderball_vertices.npz  ShaderBall.fbx -> bb::Vertex[29328] (see tools/fbx_geometry.py)
   math_golden.json         outputs of the REFERENCE's vector_math.cpp / camera.cpp (oracle/_ref)
+  math_random.npz          the same on 200 seeded random inputs per function (oracle/_ref)
+  reference_citations.json line counts of the reference's files, and the lines of a few anchor identifiers of its shaders
+  assets/                  ShaderBall.fbx, gizmo.obj/.mtl and the pinned PNGs of at most 300 KB, copied as they are
+  light_gold_512.npz       the light_gold material, decoded and box-filtered to 512^2
   default_texels.json      resources/pbr/default/*.png decoded by the reference's stb_image 2.25
   gizmo.npz                gizmo.obj/.mtl expanded to bb::GizmoVertex[] + indices
   oracle_frames.npz, n_shaded.json, presented.npz   outputs of the oracle itself, frozen
@@ -294,6 +298,127 @@ def deferred():
     print("deferred", info)
 
 
+# the identifiers tests/test_citations.py expects at the cited lines of the three shader files the whole path rests on
+ANCHOR_TOKENS = {"brdf.glsl": ("distributionGGX", "geometrySchlickGGX", "geometrySmith", "fresnelSchlick", "pow(", "NdotH2", "a2 - 1",
+                               "PI * denom * denom"),
+                 "forward_brdf.frag": ("uNumLights", "innerCutOff", "0.001", "vec3(0.03)", "outColor", "light.type == 0",
+                                       "light.type == 2", "normalize(L + V)", "kD *= (1 - metallic)"),
+                 "forward_brdf.vert": ("aModel", "uProjMat", "uViewMat", "aInvModel", "cross(")}
+CITED_SUFFIXES = (".frag", ".vert", ".geom", ".glsl", ".cpp", ".h", ".inl", ".bff", ".toml")
+
+
+def reference_citations():
+    """reference_citations.json: the line count of every file of the reference a citation can name (outside external/), and
+    the line numbers at which a few anchor identifiers of the three shader files stand"""
+    counts = {}
+    for base, _dirs, files in os.walk(REF):
+        if os.sep + "external" in base:
+            continue
+        for f in files:
+            if f.endswith(CITED_SUFFIXES):
+                path = os.path.join(base, f)
+                counts[os.path.relpath(path, REF)] = sum(1 for _ in open(path, errors="replace"))
+    anchors = {}
+    for name, tokens in ANCHOR_TOKENS.items():
+        lines = open(os.path.join(REF, "src", "shaders", name), errors="replace").read().splitlines()
+        anchors[name] = {t: [i + 1 for i, l in enumerate(lines) if t in l] for t in tokens}
+    json.dump({"note": "line counts of the reference's files (paths relative to its root, external/ left out), and the lines "
+                       "holding a few anchor identifiers of src/shaders/*; minted by tools/make_fixtures.py reference_citations",
+               "line_counts": dict(sorted(counts.items())), "anchors": anchors},
+              open(os.path.join(GOLD, "reference_citations.json"), "w"), indent=1)
+    print("reference citations", len(counts), "files")
+
+
+def math_random():
+    """math_random.npz: the reference's own vector_math.cpp / camera.cpp (oracle/_ref) on 200 seeded random inputs of every
+    function the oracle restates -- inputs and float32 outputs, as tests/test_oracle_math.py draws them"""
+    ref = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libbb_ref.so"))
+    P, f = C.c_void_p, C.c_float
+    ref.ref_mat4_mul.argtypes = [P, P, P]; ref.ref_mat4_inverse.argtypes = [P, P]
+    ref.ref_mat4_perspective.argtypes = [f, f, f, f, P]; ref.ref_camera_view.argtypes = [P, f, f, P]
+    ref.ref_mat4_look_at.argtypes = [P, P, P, P]
+    for n in "xyz":
+        getattr(ref, f"ref_mat4_rotate_{n}").argtypes = [f, P]
+    rng = np.random.Generator(np.random.PCG64(99))
+    keys = ("a", "b", "deg", "fov", "aspect", "pos", "yaw", "pitch", "eye", "target")
+    draws = {key: [] for key in keys}
+    for _ in range(200):
+        a = rng.standard_normal((4, 4)).astype(np.float32) * np.float32(10 ** rng.uniform(-2, 2))
+        b = rng.standard_normal((4, 4)).astype(np.float32)
+        d = float(rng.uniform(-720, 720))
+        fov, asp = float(rng.uniform(5, 170)), float(rng.uniform(0.2, 4))
+        pos = rng.standard_normal(3).astype(np.float32) * 5
+        yaw, pitch = float(rng.uniform(-180, 180)), float(rng.uniform(-89, 89))
+        eye, tgt = rng.standard_normal(3).astype(np.float32), rng.standard_normal(3).astype(np.float32) * 4
+        for key, v in zip(keys, (a, b, d, fov, asp, pos, yaw, pitch, eye, tgt)):
+            draws[key].append(v)
+    # (the scalars go in as float32: the C functions take float)
+    inp = {key: np.ascontiguousarray(np.array(v, np.float32)) for key, v in draws.items()}
+    k = len(inp["a"])
+    out = {name: np.zeros((k, 4, 4), np.float32) for name in
+           ("mul", "inverse", "rotate_x", "rotate_y", "rotate_z", "perspective", "camera_view", "look_at")}
+    p = lambda a: a.ctypes.data_as(P)   # noqa: E731
+    up = np.array([0, 1, 0], np.float32)
+    for i in range(k):
+        o = np.zeros((4, 4), np.float32)
+        ref.ref_mat4_mul(p(inp["a"][i]), p(inp["b"][i]), p(o)); out["mul"][i] = o
+        ref.ref_mat4_inverse(p(inp["a"][i]), p(o)); out["inverse"][i] = o
+        for n in "xyz":
+            getattr(ref, f"ref_mat4_rotate_{n}")(float(inp["deg"][i]), p(o)); out[f"rotate_{n}"][i] = o
+        ref.ref_mat4_perspective(float(inp["fov"][i]), float(inp["aspect"][i]), 0.1, 1000.0, p(o)); out["perspective"][i] = o
+        ref.ref_camera_view(p(np.ascontiguousarray(inp["pos"][i])), float(inp["yaw"][i]), float(inp["pitch"][i]), p(o))
+        out["camera_view"][i] = o
+        ref.ref_mat4_look_at(p(np.ascontiguousarray(inp["eye"][i])), p(np.ascontiguousarray(inp["target"][i])), p(up), p(o))
+        out["look_at"][i] = o
+    np.savez_compressed(os.path.join(GOLD, "math_random.npz"), **{f"in_{k_}": v for k_, v in inp.items()},
+                        **{f"out_{k_}": v for k_, v in out.items()})
+    print("math random", k, "cases")
+
+
+PNG_SUBSET_MAX_BYTES = 300_000   # reference_assets: the pinned PNGs up to this size travel with the tests (21 files, 0.9 MB)
+
+
+def reference_assets():
+    """tests/golden/assets/: the reference's ShaderBall.fbx, gizmo.obj and gizmo.mtl as they are, and every pinned PNG (see
+    reference_pngs) of at most PNG_SUBSET_MAX_BYTES under its path below resources/ -- the readers' inputs, byte for byte"""
+    import shutil
+    dst = os.path.join(GOLD, "assets")
+    for name in ("ShaderBall.fbx", "gizmo.obj", "gizmo.mtl"):
+        os.makedirs(dst, exist_ok=True)
+        shutil.copyfile(os.path.join(REF, "resources", name), os.path.join(dst, name))
+    pins = json.load(open(os.path.join(GOLD, "reference_png_sha256.json")))
+    n = 0
+    for rel in sorted(pins):
+        src = os.path.join(REF, "resources", rel)
+        if os.path.getsize(src) <= PNG_SUBSET_MAX_BYTES:
+            os.makedirs(os.path.dirname(os.path.join(dst, rel)), exist_ok=True)
+            shutil.copyfile(src, os.path.join(dst, rel))
+            n += 1
+    print("reference assets: 3 meshes,", n, "PNGs")
+
+
+LIGHT_GOLD_SIZE = 512
+
+
+def light_gold():
+    """light_gold_512.npz: the reference's light_gold material (resources/pbr_backup/light_gold, with the default material's map
+    for each map the set lacks: src/render.cpp:1328-1336), decoded by the product's PNG reader and box-filtered from 2048^2 to
+    LIGHT_GOLD_SIZE^2 (means kept, rounded to uint8); the 16^2 default maps as they are"""
+    from bibim_renderer_amd import assets
+    maps = {}
+    for name in ("albedo", "metallic", "roughness", "ao", "normal", "height"):
+        f = os.path.join(REF, "resources", "pbr_backup", "light_gold", name + ".png")
+        if not os.path.exists(f):
+            f = os.path.join(REF, "resources", "pbr", "default", name + ".png")
+        a = assets.load_png(f)
+        if a.shape[0] > LIGHT_GOLD_SIZE:
+            k = a.shape[0] // LIGHT_GOLD_SIZE
+            a = np.rint(a.reshape(LIGHT_GOLD_SIZE, k, LIGHT_GOLD_SIZE, k, 4).astype(np.float64).mean((1, 3))).astype(np.uint8)
+        maps[name] = a
+    np.savez_compressed(os.path.join(GOLD, f"light_gold_{LIGHT_GOLD_SIZE}.npz"), **maps)
+    print("light_gold", {k: v.shape for k, v in maps.items()})
+
+
 def contract_manifest():
     """tests/golden/CONTRACT.json: which revision of the arithmetic contract (oracle/bb_oracle.h, BBO_CONTRACT_REVISION)
     minted the frozen frames, and their hashes -- a re-mint shows up as a diff of this file next to a new revision."""
@@ -319,7 +444,7 @@ def contract_manifest():
 
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
-    which = sys.argv[1:] or ["shaderball", "math_golden", "default_texels", "gizmo", "golden_frames", "n_shaded", "present", "deferred", "reference_pngs", "uv_sphere", "overlays"]
+    which = sys.argv[1:] or ["shaderball", "math_golden", "default_texels", "gizmo", "golden_frames", "n_shaded", "present", "deferred", "reference_pngs", "uv_sphere", "overlays", "math_random", "reference_citations", "reference_assets", "light_gold"]
     if sys.argv[1:] == ["contract_manifest"]:
         contract_manifest()
         sys.exit(0)

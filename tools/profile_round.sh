@@ -13,9 +13,9 @@ RAW=/tmp/bbr_prof_raw   # the raw rocprofv3 directories stay on the box (gpurun 
 mkdir -p $RAW $O
 cd /tmp && export TMPDIR=/tmp
 # (1) kernel trace + stats of the default bench command
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $RAW/${pre}_stats --output-format csv -- python3 $R/bench.py --workload $W --no-also > $O/${pre}_bench_under_rocprof.json 2> $O/${pre}_bench_under_rocprof.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $RAW/${pre}_stats --output-format csv -- python3 $R/bench.py --workload $W --full --no-also > $O/${pre}_bench_under_rocprof.json 2> $O/${pre}_bench_under_rocprof.err
 # (2) HBM traffic: separate passes
-B="python3 $R/bench.py --workload $W --steps 40 --warmup 5 --no-cpu-baseline --no-also"   # (one workload's launches only: the passes average per kernel)
+B="python3 $R/bench.py --workload $W --steps 40 --warmup 5 --full --no-cpu-baseline --no-also"   # (one workload's launches only: the passes average per kernel)
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $RAW/${pre}_pmc_fetch --output-format csv -- $B > /dev/null 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $RAW/${pre}_pmc_write --output-format csv -- $B > /dev/null 2>&1
 # (3) executed instructions by class, issue / wait breakdown
