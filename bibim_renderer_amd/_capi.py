@@ -82,6 +82,8 @@ SIGNATURES = {
     "bbr_read_gbuffer": (C.c_int, [_P, C.c_void_p]),
     "bbr_upload_gizmo": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "bbr_draw_overlays": (C.c_int, [_P, C.c_int32]),
+    "bbr_read_tbn_segments": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "bbr_selftest_lines": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "bbr_present": (C.c_int, [_P, C.c_void_p, C.c_int32]),
     "bbr_read_presented": (C.c_int, [_P, C.c_void_p]),
     "bbr_present_buffer": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),

@@ -9,6 +9,7 @@
 //   k_shade      forward_brdf.frag + brdf.glsl once per visible pixel (src/shaders/forward_brdf.frag:15-76,
 //                brdf.glsl:2-36): one wave per item; a TAIL instantiation loops over what the main launch's estimate missed
 //   k_present, k_tone_map, k_deferred_background, k_shade_overlay, k_pack_shard / k_unpack_*: the rows either side of the path
+//   k_tbn_segments, k_tbn_raster, k_tbn_colour: the TBN line overlay (option "tbn"; tbn.vert / tbn.geom)
 //
 // Arithmetic contract: every floating-point expression below has the same operand order and the same
 // explicit fmaf() placement as the CPU oracle; the file is compiled with -ffp-contract=off, IEEE
@@ -2606,6 +2607,306 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_overlay(
 #pragma unroll
   for (int k = 0; k < 3; ++k) px |= srgb8(col[k], *tables) << (8 * k);
   out_rgba8[(size_t)gy * (size_t)fp.width + (size_t)gx] = px;
+}
+
+// ------------------------------------------------------------------------------------------------
+// TBN line overlay (option "tbn"): tbn.vert:18-41 + tbn.geom:14-73 per triangle, then 1-pixel lines with
+// the diamond-exit rule, depth-tested against the scene, resolved in primitive order
+// ------------------------------------------------------------------------------------------------
+
+constexpr int kTbnTile = 32;          // k_tbn_raster: one 32 x 32 tile per workgroup (fixed, whatever tile_mode is)
+constexpr int kTbnThreads = 256;
+constexpr float kTbnGuard = 4.0f;     // |x|, |y| <= 4 w: snapped coordinates stay below 2^25, every product below 2^53
+constexpr float kTbnLength = 0.05f;   // tbn.geom:3
+
+struct TbnParams {
+  int32_t width, height, tiles_x, tiles_y;
+  uint32_t bin_cap;
+  float half_w, half_h;
+};
+
+// Everything specific to TBN is plain IEEE fp32 in the order written (the file is compiled with -ffp-contract=off);
+// nothing here goes through a helper that uses fmaf.
+BB_DEV f3 tbn_cross(f3 a, f3 b) { return f3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+BB_DEV f3 tbn_mean(f3 a, f3 b, f3 c) {
+  return f3{((a.x + b.x) + c.x) / 3.0f, ((a.y + b.y) + c.y) / 3.0f, ((a.z + b.z) + c.z) / 3.0f};
+}
+BB_DEV f3 tbn_normalize(f3 v) {
+  const float l = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
+  return f3{v.x / l, v.y / l, v.z / l};
+}
+// vCombined * (p, 1): the centroid's w is ((1 + 1) + 1) / 3 = 1 and the offsets carry w = 0
+BB_DEV void tbn_to_clip(const Mat4 &m, f3 p, float *c) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) c[i] = ((m.M[0][i] * p.x + m.M[1][i] * p.y) + m.M[2][i] * p.z) + m.M[3][i] * 1.0f;
+}
+
+BB_DEV float tbn_plane(const float *c, int k) {
+  switch (k) {
+    case 0: return c[3] - c[2];  // z <= w
+    case 1: return c[2];         // z >= 0
+    case 2: return kTbnGuard * c[3] + c[0];
+    case 3: return kTbnGuard * c[3] - c[0];
+    case 4: return kTbnGuard * c[3] + c[1];
+    default: return kTbnGuard * c[3] - c[1];
+  }
+}
+
+// Liang-Barsky in clip space, then project_vertex on both ends.  False: no segment (non-finite, outside, behind the
+// camera, or zero length once snapped).
+BB_DEV bool tbn_make_segment(const float *p0, const float *p1, const Viewport &vp, TbnSeg &r) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (!isfinite(p0[k]) || !isfinite(p1[k])) return false;
+  float t0 = 0.0f, t1 = 1.0f;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const float d0 = tbn_plane(p0, k), d1 = tbn_plane(p1, k);
+    if (d0 < 0.0f && d1 < 0.0f) return false;
+    if (d0 < 0.0f) t0 = fmaxf(t0, d0 / (d0 - d1));
+    else if (d1 < 0.0f) t1 = fminf(t1, d0 / (d0 - d1));
+  }
+  if (t0 > t1) return false;
+  float q0[4], q1[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    q0[k] = t0 > 0.0f ? p0[k] + t0 * (p1[k] - p0[k]) : p0[k];
+    q1[k] = t1 < 1.0f ? p0[k] + t1 * (p1[k] - p0[k]) : p1[k];
+  }
+  float rw;
+  if (!project_vertex(q0, vp, r.X0, r.Y0, rw, r.za) || !project_vertex(q1, vp, r.X1, r.Y1, rw, r.zb)) return false;
+  return r.X0 != r.X1 || r.Y0 != r.Y1;
+}
+
+// Reserve `has` lanes a slot in tile `tile`'s bin: lanes of the wave that name the same tile share ONE returning atomic
+// (neighbouring triangles of a wave land in the same few tiles; one atomic per lane on a far ball's tile counter
+// serialised the whole pass).  Called by every active lane of the wave.
+BB_DEV uint32_t tbn_wave_reserve(bool has, uint32_t tile, uint32_t *tile_count) {
+  const int lane = threadIdx.x & 63;
+  unsigned long long pending = __ballot(has);
+  int leader = lane;
+  uint32_t rank = 0, gsize = 0;
+  while (pending) {
+    const int l = __builtin_amdgcn_readfirstlane(__ffsll((long long)pending) - 1);
+    const uint32_t lt = (uint32_t)__builtin_amdgcn_readlane((int)tile, l);
+    const bool mine = has && tile == lt;
+    const unsigned long long m = __ballot(mine);
+    if (mine) {
+      leader = l;
+      rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      gsize = (uint32_t)__popcll(m);
+    }
+    pending &= ~m;
+  }
+  uint32_t base = 0;
+  if (has && lane == leader) base = atomicAdd(&tile_count[tile], gsize);
+  return (uint32_t)__shfl((int)base, leader) + rank;
+}
+
+// Bin a segment (valid) to every tile its pixel bounding box (one pixel of slack each side) meets inside the target; the
+// lanes of a wave walk their tile ranges in lock-step.  A full bin raises overflow bit 0 and reports the count it needed;
+// the host grows the bins and redoes the pass.  Called by every active lane of the wave.
+BB_DEV void tbn_bin(bool valid, const TbnSeg &s, uint32_t index, const TbnParams &tp, uint32_t *tile_count, uint32_t *bins,
+                    uint32_t *ctr) {
+  const int px0 = max((min(s.X0, s.X1) >> 8) - 1, 0), px1 = min((max(s.X0, s.X1) >> 8) + 1, tp.width - 1);
+  const int py0 = max((min(s.Y0, s.Y1) >> 8) - 1, 0), py1 = min((max(s.Y0, s.Y1) >> 8) + 1, tp.height - 1);
+  const int tx0 = px0 / kTbnTile, ty0 = py0 / kTbnTile, tw = px1 / kTbnTile - tx0 + 1;
+  const int nt = (valid && px0 <= px1 && py0 <= py1) ? tw * (py1 / kTbnTile - ty0 + 1) : 0;
+  for (int k = 0; __ballot(k < nt) != 0ull; ++k) {
+    const bool has = k < nt;
+    const uint32_t t = has ? (uint32_t)(ty0 + k / tw) * (uint32_t)tp.tiles_x + (uint32_t)(tx0 + k % tw) : 0u;
+    const uint32_t slot = tbn_wave_reserve(has, t, tile_count);
+    if (!has) continue;
+    if (slot < tp.bin_cap) {
+      bins[(size_t)t * tp.bin_cap + slot] = index;
+    } else {
+      atomicOr(&ctr[0], 1u);
+      atomicMax(&ctr[1], slot + 1u);
+    }
+  }
+}
+
+// One lane per triangle of the frame's draw list: the vertex stage's N, T, B and posWorld (the forward pass's own
+// expressions), the normal-map branch of tbn.vert, the face frame of tbn.geom, and the strip's eight segments clipped
+// and snapped into slot prim * 8 + s (kTbnNoSeg where segment s produced nothing).
+__global__ __launch_bounds__(256) void k_tbn_segments(const DrawDesc *__restrict__ draws, uint32_t n_draws, uint32_t n_prims,
+                                                      Mat4 pv, int32_t enable_normal_map,
+                                                      const MaterialDesc *__restrict__ materials, TbnParams tp,
+                                                      TbnSeg *__restrict__ segs, uint32_t *__restrict__ tile_count,
+                                                      uint32_t *__restrict__ bins, uint32_t *__restrict__ ctr) {
+  const uint32_t prim = blockIdx.x * blockDim.x + threadIdx.x;
+  if (prim >= n_prims) return;
+  uint32_t d = 0;
+  while (d + 1 < n_draws && prim >= draws[d + 1].first_prim) ++d;
+  const DrawDesc draw = draws[d];
+  const uint32_t local = prim - draw.first_prim;
+  const uint32_t inst = local / draw.tris_per_instance;
+  const uint32_t tri = local - inst * draw.tris_per_instance;
+  const InstanceBlock &ib = draw.instances[inst];
+  uint32_t vi[3] = {3u * tri, 3u * tri + 1u, 3u * tri + 2u};
+  if (draw.indices) {
+    vi[0] = draw.indices[3u * tri]; vi[1] = draw.indices[3u * tri + 1u]; vi[2] = draw.indices[3u * tri + 2u];
+  }
+  const f3 im0 = mk3(ib.inv_model.M[0][0], ib.inv_model.M[0][1], ib.inv_model.M[0][2]);
+  const f3 im1 = mk3(ib.inv_model.M[1][0], ib.inv_model.M[1][1], ib.inv_model.M[1][2]);
+  const f3 im2 = mk3(ib.inv_model.M[2][0], ib.inv_model.M[2][1], ib.inv_model.M[2][2]);
+  f3 P[3], T[3], B[3], N[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const Vertex &v = draw.vertices[vi[k]];
+    // tbn.vert:18-25 -- the same expressions as k_geometry's vertex stage (forward_brdf.vert:25,31-35)
+    const f4 w = mat4_mul(ib.model, f4{v.pos[0], v.pos[1], v.pos[2], 1.0f});
+    const f3 n = ld3(v.normal), tg = ld3(v.tangent);
+    f3 Nk = normalize3(mk3(dot3(im0, n), dot3(im1, n), dot3(im2, n)));
+    f3 Tk = normalize3(mk3(dot3(im0, tg), dot3(im1, tg), dot3(im2, tg)));
+    f3 Bk = cross3(Nk, Tk);
+    if (enable_normal_map != 0) {
+      // tbn.vert:27-42: a vertex-stage fetch with k_shade's sampler (bilinear, REPEAT, LOD 0), then the TBN product
+      const TexDesc td = materials[draw.material].maps[kMapNormal];
+      const BilinearTaps tp_ = bilinear_taps(v.uv[0], v.uv[1], td.w, td.h);
+      const uint32_t *tx32 = reinterpret_cast<const uint32_t *>(td.texels);
+      const uint32_t t00 = tx32[tp_.o00], t10 = tx32[tp_.o10], t01 = tx32[tp_.o01], t11 = tx32[tp_.o11];
+      const float sx = filter_channel(t00, t10, t01, t11, 0, tp_.fx, tp_.fy) * 2.0f - 1.0f;
+      const float sy = filter_channel(t00, t10, t01, t11, 8, tp_.fx, tp_.fy) * 2.0f - 1.0f;
+      const float sz = filter_channel(t00, t10, t01, t11, 16, tp_.fx, tp_.fy) * 2.0f - 1.0f;
+      const f3 nm = mk3((Tk.x * sx + Bk.x * sy) + Nk.x * sz, (Tk.y * sx + Bk.y * sy) + Nk.y * sz,
+                        (Tk.z * sx + Bk.z * sy) + Nk.z * sz);
+      f3 bn = mk3(1.0f, 0.0f, 0.0f);
+      if (nm.x == 1.0f && nm.y == 0.0f && nm.z == 0.0f) bn = mk3(0.0f, 0.0f, 1.0f);
+      const f3 tn = tbn_cross(nm, bn);
+      Bk = tbn_cross(nm, tn);
+      Tk = tn;
+      Nk = nm;
+    }
+    P[k] = mk3(w.x, w.y, w.z);
+    T[k] = Tk; B[k] = Bk; N[k] = Nk;
+  }
+  // tbn.geom:18-35
+  const f3 C = tbn_mean(P[0], P[1], P[2]);
+  const f3 e[3] = {scale3(tbn_normalize(tbn_mean(T[0], T[1], T[2])), kTbnLength),
+                   scale3(tbn_normalize(tbn_mean(B[0], B[1], B[2])), kTbnLength),
+                   scale3(tbn_normalize(tbn_mean(N[0], N[1], N[2])), kTbnLength)};
+  float strip[9][4];  // C,T,C, C,B,C, C,N,C (tbn.geom:39-71)
+  tbn_to_clip(pv, C, strip[0]);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    tbn_to_clip(pv, add3(C, e[j]), strip[3 * j + 1]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) strip[3 * j][k] = strip[3 * j + 2][k] = strip[0][k];
+  }
+  const Viewport vp = {tp.half_w, tp.half_h, tp.half_w, tp.half_h};
+#pragma unroll  // (static indices into strip: no scratch)
+  for (int s = 0; s < 8; ++s) {
+    TbnSeg r = {};
+    const uint32_t slot = prim * 8u + (uint32_t)s;
+    const bool valid = tbn_make_segment(strip[s], strip[s + 1], vp, r);
+    r.key = valid ? slot : kTbnNoSeg;
+    segs[slot] = r;
+    tbn_bin(valid, r, slot, tp, tile_count, bins, ctr);
+  }
+}
+
+// bbr_selftest_lines: bin segments the caller supplied (record i is bin entry i)
+__global__ __launch_bounds__(256) void k_tbn_bin(const TbnSeg *__restrict__ segs, uint32_t n, TbnParams tp,
+                                                 uint32_t *__restrict__ tile_count, uint32_t *__restrict__ bins,
+                                                 uint32_t *__restrict__ ctr) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  TbnSeg s = {};
+  if (i < n) s = segs[i];
+  tbn_bin(i < n && (s.X0 != s.X1 || s.Y0 != s.Y1), s, i, tp, tile_count, bins, ctr);
+}
+
+// OpenGL 4.6 §14.5.1 diamond-exit rule on 1/256-pixel integers, endpoints relative to the fragment centre, with the
+// spec's perturbation p' = p - (eps, eps^2).  A fragment is produced iff the perturbed segment meets the open diamond
+// |x| + |y| < 128 and its perturbed end point is not inside it.  After the perturbation nothing touches a boundary, so
+// separation along one of three axes decides: the diamond's two edge normals and the segment's normal.
+BB_DEV bool tbn_covers(long long ax, long long ay, long long bx, long long by) {
+  const long long eb = llabs(bx) + llabs(by);
+  if (eb < 128 || (eb == 128 && bx > 0)) return false;  // b - (eps, eps^2) inside the diamond
+  const long long au = ax + ay, bu = bx + by;           // axis (1, 1): shifted by -(eps + eps^2)
+  if (max(au, bu) <= -128 || min(au, bu) >= 129) return false;
+  const long long av = ax - ay, bv = bx - by;           // axis (1, -1): shifted by -eps + eps^2
+  if (max(av, bv) <= -128 || min(av, bv) >= 129) return false;
+  const long long dx = bx - ax, dy = by - ay;           // axis (-dy, dx): the segment is the point c + dy eps - dx eps^2
+  const long long c = dx * ay - dy * ax, h = 128 * max(llabs(dx), llabs(dy));
+  if (c > h || (c == h && (dy > 0 || (dy == 0 && dx < 0)))) return false;
+  if (c < -h || (c == -h && (dy < 0 || (dy == 0 && dx > 0)))) return false;
+  return true;
+}
+
+// Walk the segment's major axis through the tile: per column (row) of an x-major (y-major) segment only the four pixels
+// around the line's crossing of the pixel centre can hold a fragment; tbn_covers decides exactly.
+BB_DEV void tbn_raster_segment(const TbnSeg &s, int tx0, int ty0, const TbnParams &tp, const float *s_depth,
+                               uint32_t *s_key) {
+  const long long dx = (long long)s.X1 - s.X0, dy = (long long)s.Y1 - s.Y0;
+  if (dx == 0 && dy == 0) return;
+  const bool xmajor = llabs(dx) >= llabs(dy);
+  const int ma0 = xmajor ? s.X0 : s.Y0, ma1 = xmajor ? s.X1 : s.Y1, mi0 = xmajor ? s.Y0 : s.X0;
+  const long long dma = xmajor ? dx : dy, dmi = xmajor ? dy : dx;
+  const int tma = xmajor ? tx0 : ty0, tmi = xmajor ? ty0 : tx0;
+  const int lima = xmajor ? tp.width : tp.height, limi = xmajor ? tp.height : tp.width;
+  const int i0 = max(max((min(ma0, ma1) >> 8) - 1, tma), 0);
+  const int i1 = min(min((max(ma0, ma1) >> 8) + 1, tma + kTbnTile - 1), lima - 1);
+  const int jlo = max(tmi, 0), jhi = min(tmi + kTbnTile - 1, limi - 1);
+  const long long den = dx * dx + dy * dy;
+  for (int i = i0; i <= i1; ++i) {
+    const long long cm = 256ll * i + 128;
+    const double mc = (double)mi0 + (double)(cm - ma0) * (double)dmi / (double)dma;
+    const int j0 = (int)floor((mc - 128.0) / 256.0);
+    for (int j = max(j0 - 1, jlo); j <= min(j0 + 2, jhi); ++j) {
+      const int px = xmajor ? i : j, py = xmajor ? j : i;
+      const long long fx = 256ll * px + 128, fy = 256ll * py + 128;
+      if (!tbn_covers(s.X0 - fx, s.Y0 - fy, s.X1 - fx, s.Y1 - fy)) continue;
+      const long long num = (fx - s.X0) * dx + (fy - s.Y0) * dy;
+      const double t = (double)num / (double)den;
+      const float z = (float)((1.0 - t) * (double)s.za + t * (double)s.zb);
+      const int l = (py - ty0) * kTbnTile + (px - tx0);
+      if (z >= s_depth[l]) atomicMax(&s_key[l], s.key + 1u);
+    }
+  }
+}
+
+// One workgroup per 32 x 32 tile and slice of kTbnThreads bin entries (blockIdx.z; a slice strides by kTbnSplit slices,
+// so that a far ball's few tiles with thousands of segments each are spread over many CUs): the tile's scene depth and
+// its keys (ds_max_u32) in LDS, lanes walk the slice's segments, then every touched pixel folds its key into the frame's
+// key buffer with one atomicMax (per pixel and slice, lanes on consecutive pixels; never per fragment).
+constexpr int kTbnSplit = 16;
+__global__ __launch_bounds__(kTbnThreads) void k_tbn_raster(const TbnSeg *__restrict__ segs,
+                                                            const uint32_t *__restrict__ tile_count,
+                                                            const uint32_t *__restrict__ bins, TbnParams tp,
+                                                            const float *__restrict__ depth, uint32_t *__restrict__ keys) {
+  __shared__ uint32_t s_key[kTbnTile * kTbnTile];
+  __shared__ float s_depth[kTbnTile * kTbnTile];
+  const int tx0 = blockIdx.x * kTbnTile, ty0 = blockIdx.y * kTbnTile;
+  const uint32_t tile = blockIdx.y * (uint32_t)tp.tiles_x + blockIdx.x;
+  const uint32_t n = min(tile_count[tile], tp.bin_cap);
+  const uint32_t first = blockIdx.z * kTbnThreads;
+  if (first >= n) return;  // (workgroup-uniform)
+  for (int l = threadIdx.x; l < kTbnTile * kTbnTile; l += kTbnThreads) {
+    const int px = tx0 + (l & (kTbnTile - 1)), py = ty0 + l / kTbnTile;
+    s_key[l] = 0u;
+    s_depth[l] = (px < tp.width && py < tp.height) ? depth[(size_t)py * tp.width + px] : 0.0f;
+  }
+  __syncthreads();
+  for (uint32_t j = first + threadIdx.x; j < n; j += kTbnThreads * kTbnSplit)
+    tbn_raster_segment(segs[bins[(size_t)tile * tp.bin_cap + j]], tx0, ty0, tp, s_depth, s_key);
+  __syncthreads();
+  for (int l = threadIdx.x; l < kTbnTile * kTbnTile; l += kTbnThreads) {
+    const int px = tx0 + (l & (kTbnTile - 1)), py = ty0 + l / kTbnTile;
+    const uint32_t k = s_key[l];
+    if (k && px < tp.width && py < tp.height) atomicMax(&keys[(size_t)py * tp.width + px], k);
+  }
+}
+
+// The winning keys to the presented image: flat colour of segment s = (key - 1) & 7, red, green, blue for s / 3 = 0, 1, 2,
+// sRGB-encoded (tbn.frag:8-10); pixels without a key are not written.
+__global__ __launch_bounds__(256) void k_tbn_colour(const uint32_t *__restrict__ keys, uint32_t *__restrict__ present, size_t n) {
+  const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= n) return;
+  const uint32_t k = keys[o];
+  if (!k) return;
+  const uint32_t c = ((k - 1u) & 7u) / 3u;
+  present[o] = c == 0u ? 0xFF0000FFu : (c == 1u ? 0xFF00FF00u : 0xFFFF0000u);
 }
 
 }  // namespace bbr

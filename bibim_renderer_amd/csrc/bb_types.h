@@ -206,6 +206,16 @@ struct BlockStats {
   uint32_t raster_tris, clipped_prims, bin_refs;
 };
 
+// TBN line overlay (option "tbn"): one clipped, snapped line segment.  Same layout as the public bbr_tbn_segment.
+struct TbnSeg {
+  int32_t X0, Y0, X1, Y1;  // endpoints in 1/256 pixel (project_vertex), first = the strip's earlier vertex
+  float za, zb;            // z / w at the two endpoints (after clipping)
+  uint32_t key;            // global_prim * 8 + strip segment (0..7); kTbnNoSeg: the slot holds no segment
+  uint32_t pad;
+};
+static_assert(sizeof(TbnSeg) == 32, "TbnSeg");
+constexpr uint32_t kTbnNoSeg = 0xFFFFFFFFu;  // (never a key: primitives < 2^29)
+
 struct FrameParams {
   int32_t width, height;
   float half_w, half_h;

@@ -226,6 +226,21 @@ struct bbr_context {
   bool overlays = false;  // option "overlays": frames keep their depth so that bbr_draw_overlays can test against it
   Mesh marker_mesh, gizmo_mesh;  // generateUVSphereMesh(0.1, 16, 16) and the caller's gizmo, both as Vertex meshes
   FrameSlot ov;           // buffers of the overlay pass (its own little frame)
+  bool tbn = false;       // option "tbn": bbr_draw_overlays first draws the TBN lines of the last frame (tbn.vert/.geom/.frag)
+  struct TbnPass {
+    DeviceBuffer<uint8_t> d_staging;   // the frame's draw descriptors + instances
+    DeviceBuffer<TbnSeg> d_segs;       // eight slots per primitive (slot = key)
+    DeviceBuffer<uint32_t> d_tile_count, d_bins, d_ctr;
+    DeviceBuffer<uint32_t> d_keys;     // per pixel: key + 1 of the winning segment, 0 = none
+    uint32_t bin_cap = 1024;           // bin entries per 32 x 32 tile (grows on overflow)
+    uint32_t n_slots = 0;
+    bool valid = false;                // d_segs holds the records of the last TBN draw
+    void release() {
+      d_staging.release(); d_segs.release(); d_tile_count.release(); d_bins.release(); d_ctr.release(); d_keys.release();
+      n_slots = 0;
+      valid = false;
+    }
+  } tbn_pass;
   int gbuffer_view = -1;  // option "gbuffer_view": GBufferVisualizingOption (src/scene.h:27-35) while the deferred path runs
   bool deferred = false;  // option "render_pass": the reference's deferred path (its default) instead of the forward one
   bool dump_gbuffer = false;
@@ -903,6 +918,92 @@ inline void mat_vec(const Mat4 &m, const float *v, float *out) {
     out[i] = std::fmaf(m.M[3][i], v[3], std::fmaf(m.M[2][i], v[2], std::fmaf(m.M[1][i], v[1], m.M[0][i] * v[0])));
 }
 
+// TBN line overlay (option "tbn"): the last frame's draws through k_tbn_segments (clipped, snapped segment records,
+// binned to 32 x 32 tiles), then k_tbn_raster over the presented image.  Synchronous, like the rest of the overlay pass.
+int tbn_launch_params(bbr_context *c, int32_t w, int32_t h, TbnParams &tp) {
+  tp.width = w;
+  tp.height = h;
+  tp.tiles_x = (w + kTbnTile - 1) / kTbnTile;
+  tp.tiles_y = (h + kTbnTile - 1) / kTbnTile;
+  tp.bin_cap = c->tbn_pass.bin_cap;
+  tp.half_w = 0.5f * (float)w;
+  tp.half_h = 0.5f * (float)h;
+  auto &t = c->tbn_pass;
+  HIP_TRY(c, t.d_tile_count.ensure((size_t)tp.tiles_x * tp.tiles_y));
+  HIP_TRY(c, t.d_bins.ensure((size_t)tp.tiles_x * tp.tiles_y * tp.bin_cap));
+  HIP_TRY(c, t.d_ctr.ensure(2));
+  HIP_TRY(c, zero_fill_sync(t.d_tile_count.ptr, (size_t)tp.tiles_x * tp.tiles_y * sizeof(uint32_t)));
+  HIP_TRY(c, zero_fill_sync(t.d_ctr.ptr, 2 * sizeof(uint32_t)));
+  return BBR_OK;
+}
+
+// after a binning launch: 0 = the bins held everything, 1 = grown (redo the pass), < 0 = error
+int tbn_check_bins(bbr_context *c, hipStream_t st) {
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(st));
+  uint32_t h[2] = {0, 0};
+  HIP_TRY(c, hipMemcpy(h, c->tbn_pass.d_ctr.ptr, sizeof h, hipMemcpyDeviceToHost));
+  if (!h[0]) return 0;
+  uint32_t cap = c->tbn_pass.bin_cap;
+  while (cap < h[1]) cap *= 2;
+  c->tbn_pass.bin_cap = cap;
+  c->retries++;
+  return 1;
+}
+
+int draw_tbn(bbr_context *c, FrameSlot &fs) {
+  auto &t = c->tbn_pass;
+  t.valid = false;
+  const uint32_t n_prims = c->n_prims;
+  std::vector<DrawDesc> draws;
+  for (const RecordedDraw &rd : c->draws) {
+    const Mesh &m = c->meshes[rd.mesh];
+    DrawDesc d = {};
+    d.vertices = m.d_vertices;
+    d.indices = m.d_indices;
+    d.n_instances = rd.n_instances;
+    d.tris_per_instance = rd.tris_per_instance;
+    d.first_prim = rd.first_prim;
+    d.material = (uint32_t)rd.material;
+    draws.push_back(d);
+  }
+  const size_t draws_bytes = (draws.size() * sizeof(DrawDesc) + 255) / 256 * 256;
+  const size_t inst_bytes = c->host_instances.size() * sizeof(InstanceBlock);
+  HIP_TRY(c, t.d_staging.ensure(std::max<size_t>(draws_bytes + inst_bytes, 1)));
+  const InstanceBlock *d_inst = reinterpret_cast<const InstanceBlock *>(t.d_staging.ptr + draws_bytes);
+  for (size_t i = 0; i < draws.size(); ++i) draws[i].instances = d_inst + c->draws[i].first_instance;
+  if (!draws.empty()) HIP_TRY(c, upload_sync(t.d_staging.ptr, draws.data(), draws.size() * sizeof(DrawDesc)));
+  if (inst_bytes) HIP_TRY(c, upload_sync(t.d_staging.ptr + draws_bytes, c->host_instances.data(), inst_bytes));
+  HIP_TRY(c, t.d_segs.ensure(std::max<size_t>((size_t)n_prims * 8, 1)));
+  t.n_slots = n_prims * 8;
+  const Mat4 pv = proj_view(fs.view_u);  // vCombined = uProjMat * uViewMat (tbn.vert:21), both render passes
+  hipStream_t st = c->shade_stream();
+  for (int attempt = 0; attempt < 8; ++attempt) {
+    TbnParams tp;
+    int rc = tbn_launch_params(c, c->width, c->height, tp);
+    if (rc) return rc;
+    if (n_prims)
+      hipLaunchKernelGGL(k_tbn_segments, dim3((n_prims + 255) / 256), dim3(256), 0, st,
+                         reinterpret_cast<const DrawDesc *>(t.d_staging.ptr), (uint32_t)draws.size(), n_prims, pv,
+                         fs.view_u.enable_normal_map, c->d_materials.ptr, tp, t.d_segs.ptr, t.d_tile_count.ptr, t.d_bins.ptr,
+                         t.d_ctr.ptr);
+    rc = tbn_check_bins(c, st);
+    if (rc < 0) return rc;
+    if (rc == 1) continue;  // a bin overflowed: nothing was drawn yet, redo the pass with the grown bins
+    const size_t px = (size_t)c->width * c->height;
+    HIP_TRY(c, t.d_keys.ensure(px));
+    HIP_TRY(c, hipMemsetAsync(t.d_keys.ptr, 0, px * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_tbn_raster, dim3(tp.tiles_x, tp.tiles_y, kTbnSplit), dim3(kTbnThreads), 0, st, t.d_segs.ptr,
+                       t.d_tile_count.ptr, t.d_bins.ptr, tp, fs.d_depth.ptr, t.d_keys.ptr);
+    hipLaunchKernelGGL(k_tbn_colour, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, t.d_keys.ptr, fs.present.out, px);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    t.valid = true;
+    return BBR_OK;
+  }
+  return fail(c, BBR_ERR_CAPACITY, "draw_overlays: TBN bins still overflow after 8 growth steps");
+}
+
 }  // namespace
 
 extern "C" int bbr_upload_gizmo(bbr_context *c, const void *gizmo_vertices, uint32_t n_vertices, const uint32_t *indices,
@@ -944,6 +1045,10 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
   FrameSlot &fs = c->slots[c->last_slot];
   if (!fs.has_depth) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_overlays: the frame was rendered without option \"overlays\"");
   if (!fs.present.active) return fail(c, BBR_ERR_NOT_IN_FRAME, "draw_overlays: call bbr_present first (overlays go into the presented image)");
+  if (c->tbn) {  // the TBN lines first, then the markers and the gizmo over them (src/main.cpp:132-136)
+    rc = draw_tbn(c, fs);
+    if (rc) return rc;
+  }
   rc = ensure_marker_mesh(c);
   if (rc) return rc;
   rc = ensure_srgb_tables(c);
@@ -1111,6 +1216,7 @@ static void release_context(bbr_context *c) {
     if (m->d_indices) (void)hipFree(m->d_indices);
   }
   c->ov.release_all();
+  c->tbn_pass.release();
   if (c->ov.ev_geom_done) (void)hipEventDestroy(c->ov.ev_geom_done);
   if (c->ov.ev_raster_done) (void)hipEventDestroy(c->ov.ev_raster_done);
   if (c->ov.ev_shade_done) (void)hipEventDestroy(c->ov.ev_shade_done);
@@ -1543,6 +1649,7 @@ int bbr_resize(bbr_context *c, int32_t width, int32_t height) {
   };
   for (FrameSlot &s : c->slots) drop(s);
   drop(c->ov);
+  c->tbn_pass.release();  // (its records were snapped to the old extent)
   c->d_vis_prim.release();
   c->d_vis_depth.release();
   c->d_gbuffer.release();
@@ -1816,6 +1923,8 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
     c->present_fused = value != 0;
   } else if (n == "overlays") {
     c->overlays = value != 0;
+  } else if (n == "tbn") {
+    c->tbn = value != 0;
   } else if (n == "stream_layout") {
     if (value < 0 || value >= bbr_context::kLayouts) return fail(c, BBR_ERR_INVALID_ARGUMENT, "stream_layout: 0, 1 or 2");
     c->layout_mode = (int)value;
@@ -2380,6 +2489,87 @@ int bbr_selftest_rcp(bbr_context *c, uint32_t lo_bits, uint32_t hi_bits, uint64_
   (void)hipFree(d);
   HIP_TRY(c, e);
   *out_mismatches = h;
+  return BBR_OK;
+}
+
+static_assert(sizeof(bbr_tbn_segment) == sizeof(TbnSeg) && offsetof(bbr_tbn_segment, za) == offsetof(TbnSeg, za) &&
+                  offsetof(bbr_tbn_segment, key) == offsetof(TbnSeg, key), "bbr_tbn_segment");
+
+int bbr_read_tbn_segments(bbr_context *c, bbr_tbn_segment *out, uint32_t cap, uint32_t *out_count) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!out_count) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_tbn_segments: NULL count");
+  if (!c->tbn_pass.valid) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_tbn_segments: no TBN draw since the context was created or resized");
+  int rc = drain(c);
+  if (rc) return rc;
+  std::vector<TbnSeg> all(c->tbn_pass.n_slots);
+  if (!all.empty()) HIP_TRY(c, hipMemcpy(all.data(), c->tbn_pass.d_segs.ptr, all.size() * sizeof(TbnSeg), hipMemcpyDeviceToHost));
+  uint32_t n = 0;
+  for (const TbnSeg &s : all) {
+    if (s.key == kTbnNoSeg) continue;
+    if (out && n < cap) std::memcpy(out + n, &s, sizeof s);
+    ++n;
+  }
+  *out_count = n;
+  return BBR_OK;
+}
+
+int bbr_selftest_lines(bbr_context *c, const bbr_tbn_segment *segs, uint32_t n, int32_t width, int32_t height,
+                       const float *depth, uint32_t *out_keys) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if ((n && !segs) || !depth || !out_keys || width <= 0 || height <= 0 || width > 32768 || height > 32768)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "selftest_lines: bad arguments");
+  std::vector<TbnSeg> h(n);
+  if (n) std::memcpy(h.data(), segs, (size_t)n * sizeof(TbnSeg));
+  for (const TbnSeg &s : h) {
+    const int32_t lim = 1 << 25;  // (what the guard band guarantees for the pass's own segments)
+    if (s.key == kTbnNoSeg || std::abs(s.X0) > lim || std::abs(s.Y0) > lim || std::abs(s.X1) > lim || std::abs(s.Y1) > lim)
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, "selftest_lines: key 0xFFFFFFFF or a coordinate beyond 2^25");
+  }
+  int rc = drain(c);
+  if (rc) return rc;
+  const size_t px = (size_t)width * height;
+  TbnSeg *d_segs = nullptr;
+  float *d_depth = nullptr;
+  uint32_t *d_keys = nullptr;
+  auto cleanup = [&]() {
+    if (d_segs) (void)hipFree(d_segs);
+    if (d_depth) (void)hipFree(d_depth);
+    if (d_keys) (void)hipFree(d_keys);
+  };
+  hipError_t e = hipMalloc(&d_segs, std::max<size_t>(n, 1) * sizeof(TbnSeg));
+  if (e == hipSuccess) e = hipMalloc(&d_depth, px * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&d_keys, px * sizeof(uint32_t));
+  if (e == hipSuccess && n) e = upload_sync(d_segs, h.data(), (size_t)n * sizeof(TbnSeg));
+  if (e == hipSuccess) e = upload_sync(d_depth, depth, px * sizeof(float));
+  if (e != hipSuccess) {
+    cleanup();
+    HIP_TRY(c, e);
+  }
+  hipStream_t st = c->geom_stream();
+  rc = BBR_ERR_CAPACITY;
+  for (int attempt = 0; attempt < 8 && rc == BBR_ERR_CAPACITY; ++attempt) {
+    TbnParams tp;
+    int r = tbn_launch_params(c, width, height, tp);
+    if (r) { cleanup(); return r; }
+    if (n) hipLaunchKernelGGL(k_tbn_bin, dim3((n + 255) / 256), dim3(256), 0, st, d_segs, n, tp, c->tbn_pass.d_tile_count.ptr,
+                              c->tbn_pass.d_bins.ptr, c->tbn_pass.d_ctr.ptr);
+    r = tbn_check_bins(c, st);
+    if (r < 0) { cleanup(); return r; }
+    if (r == 1) continue;
+    e = hipMemsetAsync(d_keys, 0, px * sizeof(uint32_t), st);
+    if (e == hipSuccess)
+      hipLaunchKernelGGL(k_tbn_raster, dim3(tp.tiles_x, tp.tiles_y, kTbnSplit), dim3(kTbnThreads), 0, st, d_segs,
+                         c->tbn_pass.d_tile_count.ptr, c->tbn_pass.d_bins.ptr, tp, d_depth, d_keys);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(out_keys, d_keys, px * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    rc = BBR_OK;
+  }
+  cleanup();
+  HIP_TRY(c, e);
+  if (rc) return fail(c, rc, "selftest_lines: bins still overflow after 8 growth steps");
   return BBR_OK;
 }
 

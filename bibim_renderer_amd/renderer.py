@@ -11,6 +11,9 @@ from . import _capi
 from ._capi import BbrImage, BbrStats, BibimError, lib
 
 MAP_NAMES = ("albedo", "metallic", "roughness", "ao", "normal", "height")
+# bbr_tbn_segment (include/bibim_hip.h): endpoints in 1/256 pixel, z / w at both ends, key = primitive * 8 + segment
+TBN_SEGMENT_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("za", "<f4"), ("zb", "<f4"),
+                              ("key", "<u4"), ("pad", "<u4")])
 
 
 def _ptr(a):
@@ -170,6 +173,26 @@ class Renderer:
         self._check(self._L.bbr_draw_overlays(self._ctx, int(gizmo_extent)))
 
     # -- presentation (tone map + sRGB + UNORM8) --
+    # -- TBN line overlay (option "tbn": bbr_draw_overlays draws the tangent frames of the last frame first) --
+    def read_tbn_segments(self):
+        """segment records of the last TBN draw, in key order (numpy structured array of TBN_SEGMENT_DTYPE)"""
+        n = C.c_uint32()
+        self._check(self._L.bbr_read_tbn_segments(self._ctx, None, 0, C.byref(n)))
+        out = np.zeros(n.value, TBN_SEGMENT_DTYPE)
+        self._check(self._L.bbr_read_tbn_segments(self._ctx, _ptr(out), len(out), C.byref(n)))
+        assert n.value == len(out)
+        return out
+
+    def selftest_lines(self, segments, width, height, depth):
+        """the pass's raster + resolve on caller-supplied segments: [height, width] uint32 of key + 1 (0: nothing passed)"""
+        segs = np.ascontiguousarray(segments, TBN_SEGMENT_DTYPE)
+        depth = np.ascontiguousarray(depth, np.float32)
+        assert depth.shape == (height, width)
+        keys = np.zeros((height, width), np.uint32)
+        self._check(self._L.bbr_selftest_lines(self._ctx, _ptr(segs) if len(segs) else None, len(segs), int(width),
+                                               int(height), _ptr(depth), _ptr(keys)))
+        return keys
+
     def present(self, rgba8_device_ptr=None, hdr16=True):
         """queue k_present for the last frame; EnableToneMapping / Exposure come from its FrameUniformBlock"""
         self._check(self._L.bbr_present(self._ctx, C.c_void_p(rgba8_device_ptr) if rgba8_device_ptr else None, int(bool(hdr16))))

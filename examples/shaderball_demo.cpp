@@ -6,6 +6,7 @@
 //   ./demo --fbx resources/ShaderBall.fbx            (or --vertices-bin file: raw bb::Vertex records)
 //          [--size 1920 1080] [--grid 4] [--frames 100] [--frames-in-flight 2] [--deferred] [--tone-map 1.0] [--pbr-dir resources/pbr/bark1]
 //          [--gizmo resources/gizmo.obj] [--out frame.ppm]        (--gizmo also turns the light markers on)
+//          [--tbn]                                   (the TBN line overlay, "Enable TBN": src/main.cpp:1309-1310)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -23,7 +24,7 @@ static int die(const char *what, bbr_context *ctx = nullptr) {
 
 int main(int argc, char **argv) {
   int width = 1920, height = 1080, grid = 1, frames = 100, in_flight = 2;  // the reference keeps 2 (src/main.cpp:38)
-  bool deferred = false, tone = false;
+  bool deferred = false, tone = false, tbn = false;
   float exposure = 1.f;
   std::string fbx, vbin, out = "frame.ppm", pbr, gizmo;
   for (int i = 1; i < argc; ++i) {
@@ -35,6 +36,7 @@ int main(int argc, char **argv) {
     else if (a == "--frames" && i + 1 < argc) frames = std::atoi(argv[++i]);
     else if (a == "--frames-in-flight" && i + 1 < argc) in_flight = std::atoi(argv[++i]);
     else if (a == "--deferred") deferred = true;
+    else if (a == "--tbn") tbn = true;
     else if (a == "--tone-map" && i + 1 < argc) { tone = true; exposure = (float)std::atof(argv[++i]); }
     else if (a == "--pbr-dir" && i + 1 < argc) pbr = argv[++i];
     else if (a == "--gizmo" && i + 1 < argc) gizmo = argv[++i];
@@ -87,6 +89,8 @@ int main(int argc, char **argv) {
       bba_free(gv);
       bba_free(gi);
     }
+    if (tbn && (bbr_set_option(ctx, "overlays", 1) != BBR_OK || bbr_set_option(ctx, "tbn", 1) != BBR_OK))
+      return die("bbr_set_option tbn", ctx);
 
     bb::ShaderBallScene scene(ctx, ball.data(), (uint32_t)ball.size(), grid);
     scene.SceneRenderPassType = deferred ? bb::RenderPassType::Deferred : bb::RenderPassType::Forward;
@@ -117,7 +121,7 @@ int main(int argc, char **argv) {
     // --- present (tone map + sRGB + RGBA8) and write it out
     std::vector<uint8_t> rgba((size_t)width * height * 4);
     if (bbr_present(ctx, nullptr, 1) != BBR_OK) return die("bbr_present", ctx);
-    if (!gizmo.empty() && bbr_draw_overlays(ctx, 100) != BBR_OK) return die("bbr_draw_overlays", ctx);
+    if ((tbn || !gizmo.empty()) && bbr_draw_overlays(ctx, gizmo.empty() ? 0 : 100) != BBR_OK) return die("bbr_draw_overlays", ctx);
     if (bbr_read_presented(ctx, rgba.data()) != BBR_OK) return die("bbr_read_presented", ctx);
     FILE *f = std::fopen(out.c_str(), "wb");
     if (!f) { std::perror(out.c_str()); rc = 1; }

@@ -207,6 +207,7 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            encode fused into the raster / shade kernels): no fp32 frame, no k_present pass; bbr_present
  *                            then only marks (or copies to a caller buffer), bbr_read_framebuffer / bbr_read_shard fail
  *   "overlays" 0|1           keep every frame's resolved depth for bbr_draw_overlays (default 0)
+ *   "tbn" 0|1                bbr_draw_overlays first draws the TBN lines of the last frame (default 0; see below)
  *   "stream_layout" 0|1|2    how the kernels of the frames in flight are spread over HIP streams.  Same pixels in every
  *                            layout.  0: geometry + raster on one stream, shade on a second, present on a third.
  *                            1: as 0 with k_raster on a stream of its own (the geometry of frame N+1 overlaps the
@@ -259,6 +260,31 @@ int bbr_read_gbuffer(bbr_context *ctx, float *gbuffer_host);
 int bbr_upload_gizmo(bbr_context *ctx, const void *gizmo_vertices, uint32_t n_vertices, const uint32_t *indices,
                      uint32_t n_indices);
 int bbr_draw_overlays(bbr_context *ctx, int32_t gizmo_extent);
+
+/* ---- TBN line overlay ("Enable TBN", src/main.cpp:1309-1310; pipeline src/main.cpp:788-822) ----
+ * With option "tbn" = 1, bbr_draw_overlays first draws, for every triangle of the last frame's draws, the tangent frame
+ * of tbn.vert / tbn.geom (src/shaders/tbn.vert:18-41, src/shaders/tbn.geom:14-73): a 9-vertex line strip C,T,C, C,B,C,
+ * C,N,C from the centroid, 0.05 long, red / green / blue, depth-tested (>=) against the scene without writing depth,
+ * over the presented image; then the markers and the gizmo as above.  Same preconditions as bbr_draw_overlays; it also
+ * runs with no lights and gizmo_extent = 0.  The line rule: clip-space Liang-Barsky against
+ * 0 <= z <= w and |x|, |y| <= 4 w, snapped to 1/256 pixel like the triangles, diamond-exit fragments (OpenGL 4.6
+ * section 14.5.1) on those integers, at each pixel the passing fragment with the largest key wins.
+ * One segment record (32 bytes): */
+typedef struct bbr_tbn_segment {
+  int32_t x0, y0, x1, y1; /* endpoints in 1/256 pixel, pixel (px, py) has its centre at (256 px + 128, 256 py + 128) */
+  float za, zb;           /* z / w at the two endpoints */
+  uint32_t key;           /* global primitive index * 8 + strip segment s (0..7); colour s / 3 = red, green, blue */
+  uint32_t pad;
+} bbr_tbn_segment;
+/* The segment records of the last TBN draw, in key order (a strip segment that was clipped away, not finite or of zero
+ * length once snapped has none).  *out_count = their number; min(cap, count) are copied to out (out may be NULL).
+ * Synchronises.  BBR_ERR_NOT_IN_FRAME before the first TBN draw and after bbr_resize. */
+int bbr_read_tbn_segments(bbr_context *ctx, bbr_tbn_segment *out, uint32_t cap, uint32_t *out_count);
+/* Self-test of the line rule: the pass's own binning, raster and resolve kernels on n caller-supplied segments over a
+ * width x height depth buffer (row-major floats).  out_keys[width * height] receives key + 1 of the winning segment per
+ * pixel, 0 where no fragment passed.  Coordinates within +-2^25, key != 0xFFFFFFFF.  Synchronises. */
+int bbr_selftest_lines(bbr_context *ctx, const bbr_tbn_segment *segs, uint32_t n, int32_t width, int32_t height,
+                       const float *depth, uint32_t *out_keys);
 
 /* ---- presentation: the step after the path ----
  * Replaces the tone-map subpass + swapchain write (src/main.cpp:123-126, src/shaders/hdr_tone_mapping.frag:9-18,
