@@ -486,7 +486,6 @@ BB_DEV void clip_primitive_wave(ClipWork &w, int owner, const float (*clip)[4], 
   // -- arena slots (lane 0) and every-tile entries (lane 1) -- go out together afterwards: one memory round trip per clipped
   // primitive instead of two (the ground plane's two primitives are k_geometry's critical path at 1080p: in-kernel stamps).
   bool ok = false;
-  ClipSlot s;
   RasterTri tri = {};
   if (lane < n_slots) {
     const int i = lane + 1;
@@ -494,18 +493,9 @@ BB_DEV void clip_primitive_wave(ClipWork &w, int owner, const float (*clip)[4], 
     tri.X1 = w.X[i]; tri.Y1 = w.Y[i];
     tri.X2 = w.X[i + 1]; tri.Y2 = w.Y[i + 1];
     tri.rw0 = w.rw[0]; tri.rw1 = w.rw[i]; tri.rw2 = w.rw[i + 1];
-    const ClipVert v0 = w.poly[cur][0], v1 = w.poly[cur][i], v2 = w.poly[cur][i + 1];
-    for (int c = 0; c < 3; ++c) {
-      s.bary[0][c] = v0.b[c];
-      s.bary[1][c] = v1.b[c];
-      s.bary[2][c] = v2.b[c];
-    }
-    s.pad = 0;
     ok = setup_tri(tri, w.z[0], w.z[i], w.z[i + 1]);
     TileRange tr;
     ok = ok && tile_range<TILE_W, TILE_H>(tri, fp, tr);
-    s.valid = ok ? 1u : 0u;
-    s.h = PlaneHead{tri.X0, tri.Y0, tri.l1dx, tri.l1dy, tri.l2dx, tri.l2dy, tri.rw0, tri.rw1, tri.rw2};
   }
   const unsigned long long m = __ballot(ok);
   const int n_valid = (int)__popcll(m);
@@ -517,24 +507,131 @@ BB_DEV void clip_primitive_wave(ClipWork &w, int owner, const float (*clip)[4], 
   const bool list_fits = slot + (uint32_t)n_valid <= fp.broad_cap;
   if (!arena_fits && lane == 0) atomicOr(&ctr->overflow, 4u);
   if (n_valid && !list_fits && lane == 0) atomicOr(&ctr->overflow, 2u);
-  if (arena_fits && lane < n_slots) clip_arena[base + (uint32_t)lane] = s;
-  if (lane == owner && arena_fits) {
-    w.base = base;
-    w.n_slots = n_slots;
-  }
-  if (n_valid == 0 || !list_fits) return;  // (an overflowed list: the frame takes none of its entries, k_raster)
-  if (ok) {
+  const bool listed = n_valid != 0 && list_fits;  // (an overflowed list: the frame takes none of its entries, k_raster)
+  if (listed && ok) {
     // the run of entries is reserved and fits, so every one of them is written: a real entry, or -- when the arena had
     // no room for the sub-triangles, and the frame is rendered again anyway -- an entry no tile can touch (all zero)
-    BroadTri b = {};
+    BroadTri *const entry = broad_list + (slot + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)));
     if (arena_fits) {
+      BroadTri b;
       b.tri = tri;
       b.ref = (w.prim << 3) | (uint32_t)lane;  // the OWNER's primitive (prim is per lane)
       b.pad[0] = base + (uint32_t)lane + 1u;     // its clip-arena slot + 1: travels into the fragment word (k_raster)
+      b.pad[1] = b.pad[2] = 0;
+      *entry = b;
+    } else {
+      *entry = BroadTri{};
     }
-    broad_list[slot + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = b;
   }
-  if (lane == owner && arena_fits) w.n_valid = n_valid;
+  if (arena_fits && lane < n_slots) {
+    // (The slot is put together here -- behind the reservation and behind the list entry, when only the planes of the triangle
+    //  are still needed -- from the triangle and the polygon in LDS: built next to the binary64 setup, its twenty values were
+    //  this kernel's register peak.)
+    const int i = lane + 1;
+    ClipSlot s;
+    for (int c = 0; c < 3; ++c) {
+      s.bary[0][c] = w.poly[cur][0].b[c];
+      s.bary[1][c] = w.poly[cur][i].b[c];
+      s.bary[2][c] = w.poly[cur][i + 1].b[c];
+    }
+    s.pad = 0;
+    s.valid = ok ? 1u : 0u;
+    s.h = PlaneHead{tri.X0, tri.Y0, tri.l1dx, tri.l1dy, tri.l2dx, tri.l2dy, tri.rw0, tri.rw1, tri.rw2};
+    clip_arena[base + (uint32_t)lane] = s;
+  }
+  if (lane == owner && arena_fits) {
+    w.base = base;
+    w.n_slots = n_slots;
+    if (listed) w.n_valid = n_valid;
+  }
+}
+
+// ---- k_geometry's view of a primitive's inputs ----
+// (global, not flat, loads: through pointers the compiler knows to be global memory)
+typedef const Vertex __attribute__((address_space(1))) *GlobalVertex;
+typedef const uint32_t __attribute__((address_space(1))) *GlobalIndex;
+typedef const InstanceBlock __attribute__((address_space(1))) *GlobalInstance;
+
+// which draw: the first few draws' first_prim are kernel arguments (no load); more draws than that: the table
+BB_DEV uint32_t find_draw(const DrawDesc *__restrict__ draws, uint32_t n_draws, const FirstPrims &first_prims, uint32_t prim) {
+  uint32_t d = 0;
+#pragma unroll
+  for (int q = 0; q < kInlineFirstPrims; ++q) d += prim >= first_prims.v[q] ? 1u : 0u;
+  if (n_draws > (uint32_t)kInlineFirstPrims + 1u)
+    while (d + 1 < n_draws && prim >= draws[d + 1].first_prim) ++d;
+  return d;
+}
+
+// Where a primitive's three vertices and its instance block are.  (One shape of loads for indexed and non-indexed meshes --
+// three 44-byte vertices at three indices: left as an if / else of two copies into the same array the compiler merged them
+// into flat dword loads with selected addresses.)
+struct PrimSource {
+  GlobalVertex v[3];
+  GlobalInstance ib;
+};
+
+BB_DEV PrimSource prim_source(const DrawDesc &draw, uint32_t prim) {
+  const uint32_t local = prim - draw.first_prim;
+  const uint32_t inst = local / draw.tris_per_instance;
+  const uint32_t tri = local - inst * draw.tris_per_instance;
+  uint32_t vi[3] = {3u * tri, 3u * tri + 1u, 3u * tri + 2u};
+  if (draw.indices) {
+    const GlobalIndex ix = (GlobalIndex)draw.indices + 3u * tri;
+    vi[0] = ix[0]; vi[1] = ix[1]; vi[2] = ix[2];
+  }
+  PrimSource s;
+  const GlobalVertex gv = (GlobalVertex)draw.vertices;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) s.v[k] = gv + vi[k];
+  s.ib = (GlobalInstance)draw.instances + inst;
+  return s;
+}
+
+// Phase 1's loads: the three positions and the instance's model matrix, one batch.  The fence keeps the compiler from
+// sinking the loads to their first use (one round trip for the batch, not one per matrix column).
+BB_DEV void load_positions(const PrimSource &s, float (*pos)[3], Mat4 &model) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pos[k][c] = s.v[k]->pos[c];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc) model.M[r][cc] = s.ib->model.M[r][cc];
+  asm volatile("" :: "v"(pos[0][0]), "v"(pos[1][0]), "v"(pos[2][0]), "v"(model.M[0][0]),
+               "v"(model.M[0][1]), "v"(model.M[0][2]), "v"(model.M[0][3]), "v"(model.M[1][0]), "v"(model.M[1][1]), "v"(model.M[1][2]),
+               "v"(model.M[1][3]), "v"(model.M[2][0]), "v"(model.M[2][1]), "v"(model.M[2][2]), "v"(model.M[2][3]), "v"(model.M[3][0]),
+               "v"(model.M[3][1]), "v"(model.M[3][2]), "v"(model.M[3][3]) : "memory");
+}
+
+// gl_Position of one vertex (and posWorld of the main passes' vertex program).  k_geometry evaluates it for every primitive,
+// and once more for the few that go through the clipper: the same expressions on the same operands, hence the same bits.
+template <bool OVERLAY>
+BB_DEV f4 vertex_clip_pos(const Mat4 &model, const float *pos, const Mat4 &pv, const Mat4 &view, const FrameParams &fp, f3 &world) {
+  if (OVERLAY) {
+    // The host folds the matrices: ib.model = (P*V)*modelMat of the light (light.vert:11-14) or the gizmo's own
+    // projMat*viewMat (gizmo.vert:13-24)
+    world = mk3(0.0f, 0.0f, 0.0f);
+    return mat4_mul(model, f4{pos[0], pos[1], pos[2], 1.0f});
+  }
+  // forward_brdf.vert:25,27
+  const f4 w = mat4_mul(model, f4{pos[0], pos[1], pos[2], 1.0f});
+  world = mk3(w.x, w.y, w.z);
+  // forward_brdf.vert:27 multiplies (P*V) * posWorld (pv = P*V); gbuffer.vert:19-22 P * (V * posWorld) (pv = P)
+  return fp.deferred ? mat4_mul(pv, mat4_mul(view, w)) : mat4_mul(pv, w);
+}
+
+// Four dwords of a primitive record.  The record leaves k_geometry in 16-byte pieces as soon as their values exist --
+// never as one 56-register struct -- and the pieces are the same fourteen dwordx4 stores the struct assignment was.
+typedef uint32_t rec_u32x4_ __attribute__((ext_vector_type(4)));
+typedef rec_u32x4_ rec_u32x4 __attribute__((aligned(8)));  // (a record is 8-byte aligned: it holds a pointer)
+BB_DEV void rec_store4(ShadeRec *rec, int dword, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+  rec_u32x4 v;
+  v.x = a; v.y = b; v.z = c; v.w = d;
+  *reinterpret_cast<rec_u32x4 *>(reinterpret_cast<uint32_t *>(rec) + dword) = v;
+}
+BB_DEV void rec_store4(ShadeRec *rec, int dword, float a, float b, float c, float d) {
+  rec_store4(rec, dword, __float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d));
 }
 
 // One thread per primitive, all draw calls of the frame in one launch (API order = primitive index order).
@@ -566,7 +663,6 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
   //  workspace and leaves its own statistics record -- so a wave retires when ITS primitives are done.)
   const uint32_t prim = blockIdx.x * blockDim.x + threadIdx.x;
   bool needs_clip = false;
-  float clip[3][4];
   bool survives_out = false;  // this lane's primitive is rasterised unclipped (statistics)
   bool binned = false;  // this lane holds an unclipped, set-up triangle that goes to tile bins
   uint32_t cls = 0;     // raster class of the triangle: bin segment (kBinClasses per tile)
@@ -574,86 +670,31 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
   uint32_t clipped_raster = 0;  // wave-uniform: sub-triangles of this wave's clipped primitives that reached the every-tile list
   Viewport vp = {fp.half_w, fp.half_h, fp.half_w, fp.half_h};
   if (prim < n_prims) {
-    // which draw: the first few draws' first_prim are kernel arguments (no load); more draws than that: the table
-    uint32_t d = 0;
-#pragma unroll
-    for (int q = 0; q < kInlineFirstPrims; ++q) d += prim >= first_prims.v[q] ? 1u : 0u;
-    if (n_draws > (uint32_t)kInlineFirstPrims + 1u)
-      while (d + 1 < n_draws && prim >= draws[d + 1].first_prim) ++d;
-    const DrawDesc draw = draws[d];
-    const uint32_t local = prim - draw.first_prim;
-    const uint32_t inst = local / draw.tris_per_instance;
-    const uint32_t tri = local - inst * draw.tris_per_instance;
-
+    const DrawDesc draw = draws[find_draw(draws, n_draws, first_prims, prim)];
     BB_STAMP(1);
-    typedef const InstanceBlock __attribute__((address_space(1))) *GlobalInstance;  // (global, not flat, loads)
-    const auto &ib = ((GlobalInstance)draw.instances)[inst];
-    // The three 44-byte vertices as few, wide loads (a non-indexed triangle is 132 contiguous bytes: nine
-    // dwordx4/x3/x2 loads instead of 33 dword loads).  Lanes are 132 bytes apart, so every load instruction touches
-    // ~64 cache lines and the L1's tag rate, not HBM, bounds this phase: fewer instructions is what counts.
-    // (One shape of loads for indexed and non-indexed meshes -- three 44-byte vertices at three indices, through pointers the
-    //  compiler knows to be global memory: left as an if / else of two copies into the same array it merged them into 33
-    //  flat dword loads with 33 selected addresses.)
-    typedef const Vertex __attribute__((address_space(1))) *GlobalVertex;
-    typedef const uint32_t __attribute__((address_space(1))) *GlobalIndex;
-    uint32_t vi[3] = {3u * tri, 3u * tri + 1u, 3u * tri + 2u};
-    if (draw.indices) {
-      const GlobalIndex ix = (GlobalIndex)draw.indices + 3u * tri;
-      vi[0] = ix[0]; vi[1] = ix[1]; vi[2] = ix[2];
-    }
-    const GlobalVertex gv = (GlobalVertex)draw.vertices;
-    Vertex vtx[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const GlobalVertex q = gv + vi[k];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) { vtx[k].pos[c] = q->pos[c]; vtx[k].normal[c] = q->normal[c]; vtx[k].tangent[c] = q->tangent[c]; }
-      vtx[k].uv[0] = q->uv[0]; vtx[k].uv[1] = q->uv[1];
-    }
-    // The upper 3 x 3 of the instance's inverse model matrix (the survivors' normal matrix; the overlay programs' colour /
-    // view rows) is asked for in the SAME batch as the vertices and the model matrix: every lane of an instance reads the
-    // same 128 bytes (L1 hits), and asked for only behind the cull it was one more dependent round trip in a kernel that is
-    // nothing but a chain of them.  The fence keeps the compiler from sinking the loads back to their first use.
-    float im_[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int cc = 0; cc < 3; ++cc) im_[r][cc] = ib.inv_model.M[r][cc];
-    Mat4 model;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int cc = 0; cc < 4; ++cc) model.M[r][cc] = ib.model.M[r][cc];
-    asm volatile("" :: "v"(im_[0][0]), "v"(im_[0][1]), "v"(im_[0][2]), "v"(im_[1][0]), "v"(im_[1][1]), "v"(im_[1][2]), "v"(im_[2][0]),
-                 "v"(im_[2][1]), "v"(im_[2][2]), "v"(vtx[0].pos[0]), "v"(vtx[1].pos[0]), "v"(vtx[2].pos[0]), "v"(model.M[0][0]),
-                 "v"(model.M[0][1]), "v"(model.M[0][2]), "v"(model.M[0][3]), "v"(model.M[1][0]), "v"(model.M[1][1]), "v"(model.M[1][2]),
-                 "v"(model.M[1][3]), "v"(model.M[2][0]), "v"(model.M[2][1]), "v"(model.M[2][2]), "v"(model.M[2][3]), "v"(model.M[3][0]),
-                 "v"(model.M[3][1]), "v"(model.M[3][2]), "v"(model.M[3][3]) : "memory");
-#ifdef BB_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    BB_STAMP(6);
-#endif
-    // ---- positions first: gl_Position of the three vertices decides whether the primitive can touch a pixel at all.  Half
-    // of a closed mesh faces away from the camera and is culled below; only the survivors pay for the rest of the vertex
-    // stage (normal matrix, two normalisations and a cross product per vertex) and for their 224-byte record ----
+    const PrimSource src = prim_source(draw, prim);
+    ShadeRec *const rec = recs + prim;
+    // ---- phase 1, every lane: positions and the model matrix only.  gl_Position of the three vertices decides whether the
+    // primitive can touch a pixel at all; half of a closed mesh faces away from the camera and is culled below.  Normals,
+    // tangents, texture coordinates and the inverse model matrix are asked for behind the cull, by the survivors alone: carried
+    // through the cull and the binary64 setup they made this kernel the largest register holder of the pipelined frame ----
+    float clip[3][4];
     float pw[3][3];  // posWorld (main passes)
+    {
+      float pos[3][3];
+      Mat4 model;
+      load_positions(src, pos, model);
+#ifdef BB_STAMPS
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      BB_STAMP(6);
+#endif
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const Vertex &v = vtx[k];
-      f4 c;
-      if (OVERLAY) {
-        // The host folds the matrices: ib.model = (P*V)*modelMat of the light (light.vert:11-14) or the gizmo's own
-        // projMat*viewMat (gizmo.vert:13-24)
-        c = mat4_mul(model, f4{v.pos[0], v.pos[1], v.pos[2], 1.0f});
-        pw[k][0] = pw[k][1] = pw[k][2] = 0.0f;
-      } else {
-        // forward_brdf.vert:25,27
-        const f4 w = mat4_mul(model, f4{v.pos[0], v.pos[1], v.pos[2], 1.0f});
-        // forward_brdf.vert:27 multiplies (P*V) * posWorld (pv = P*V); gbuffer.vert:19-22 P * (V * posWorld) (pv = P)
-        c = fp.deferred ? mat4_mul(pv, mat4_mul(view, w)) : mat4_mul(pv, w);
+      for (int k = 0; k < 3; ++k) {
+        f3 w;
+        const f4 c = vertex_clip_pos<OVERLAY>(model, pos[k], pv, view, fp, w);
         pw[k][0] = w.x; pw[k][1] = w.y; pw[k][2] = w.z;
+        clip[k][0] = c.x; clip[k][1] = c.y; clip[k][2] = c.z; clip[k][3] = c.w;
       }
-      clip[k][0] = c.x; clip[k][1] = c.y; clip[k][2] = c.z; clip[k][3] = c.w;
     }
     if (OVERLAY && prim >= fp.ov_first_gizmo_prim) vp = Viewport{fp.ov_half, fp.ov_half, fp.ov_cx, fp.ov_cy};
     // trivial reject against the true frustum (cannot change any pixel)
@@ -693,67 +734,121 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
     BB_STAMP(7);
 #endif
     if (survives || needs_clip) {
-      // ---- the rest of the vertex stage and the primitive's record ----
-      ShadeRec pa;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const Vertex &v = vtx[k];
-        float o[kNumVary];
-        if (OVERLAY) {
-          // ib.inv_model row 0 = the light's colour, or the gizmo's viewMat whose upper 3x3 turns the normals
-          // (gizmo.vert:27).  draw.material is the program: 1 marker, 2 gizmo.
-#pragma unroll
-          for (int j = 0; j < kNumVary; ++j) o[j] = 0.0f;
-          if (draw.material == 1u) {
-            o[0] = im_[0][0]; o[1] = im_[0][1]; o[2] = im_[0][2];
-          } else {
-            f3 n = ld3(v.normal);
-            o[0] = v.tangent[0]; o[1] = v.tangent[1]; o[2] = v.tangent[2];  // the gizmo mesh keeps its colour there
-            o[3] = fmaf(im_[2][0], n.z, fmaf(im_[1][0], n.y, im_[0][0] * n.x));
-            o[4] = fmaf(im_[2][1], n.z, fmaf(im_[1][1], n.y, im_[0][1] * n.x));
-            o[5] = fmaf(im_[2][2], n.z, fmaf(im_[1][2], n.y, im_[0][2] * n.x));
-          }
-        } else {
-          // :31-36  normalMat = transpose(mat3(aInvModel))
-          f3 n = ld3(v.normal), tg = ld3(v.tangent);
-          const f3 im0 = mk3(im_[0][0], im_[0][1], im_[0][2]), im1 = mk3(im_[1][0], im_[1][1], im_[1][2]),
-                   im2 = mk3(im_[2][0], im_[2][1], im_[2][2]);
-          f3 N = normalize3(mk3(dot3(im0, n), dot3(im1, n), dot3(im2, n)));
-          f3 T = normalize3(mk3(dot3(im0, tg), dot3(im1, tg), dot3(im2, tg)));
-          f3 B = cross3(N, T);
-          o[0] = v.uv[0]; o[1] = v.uv[1];
-          o[2] = pw[k][0]; o[3] = pw[k][1]; o[4] = pw[k][2];
-          o[5] = N.x; o[6] = N.y; o[7] = N.z;
-          o[8] = T.x; o[9] = T.y; o[10] = T.z;
-          o[11] = B.x; o[12] = B.y; o[13] = B.z;
-        }
-        // varying j of vertex k: 0, 1 in the record's head (the texture coordinates), the rest in its body
-        pa.uv[k][0] = o[0]; pa.uv[k][1] = o[1];
-#pragma unroll
-        for (int j = 0; j < kNumBodyVary; ++j) pa.vary[j][k] = o[2 + j];
-      }
-      pa.material = draw.material;  // (overlay pass: the overlay program, not an index into the material table)
-      pa.packed = nullptr;
-      pa.packed_dims = 0u;
-      if (!OVERLAY) {
-        // (the material's packed form travels in the draw descriptor: no load of the material table here)
-        pa.packed = draw.packed;
-        pa.packed_dims = draw.packed ? draw.packed_dims : 0u;
-      }
-      pa.clip_base = kNotClipped;  // (a clipped primitive's is patched in once the clipper has its arena slots, below)
-      // planes of the unclipped triangle; zero for a primitive that goes through the clipper (its sub-triangles have their own)
-      pa.h = PlaneHead{t.X0, t.Y0, t.l1dx, t.l1dy, t.l2dx, t.l2dy, t.rw0, t.rw1, t.rw2};
-      if (needs_clip) pa.h = PlaneHead{0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-      if (!BB_ABLATE(64u)) {
-        recs[prim] = pa;
+      // ---- phase 2, survivors: ask for the attributes and the upper 3 x 3 of the instance's inverse model matrix (the normal
+      // matrix; the overlay programs' colour / view rows) -- one batch, one more dependent round trip, closed by a fence like
+      // phase 1's -- and, while they travel, send off everything phase 1 already knows: the triangle, the record's planes and
+      // posWorld.  Only two values of phase 1 (rw2, posWorld.z of vertex 2: the first dwords of 16-byte pieces that the
+      // attributes complete) and the tile range wait for the loads with the lane. ----
+      const bool keep = !BB_ABLATE(64u);
+      if (keep) {
         if (survives) tris[prim] = t;
+        // planes of the unclipped triangle; zero for a primitive that goes through the clipper (its sub-triangles have their
+        // own): t is written in the unclipped branch only, so there it still holds the zeros it was initialised with
+        rec_store4(rec, 0, (uint32_t)t.X0, (uint32_t)t.Y0, __float_as_uint(t.l1dx), __float_as_uint(t.l1dy));
+        rec_store4(rec, 4, t.l2dx, t.l2dy, t.rw0, t.rw1);
+        if (!OVERLAY) {
+          // varyings 2..4 (posWorld), varying-major: vary[j][k] = pw[k][j], dwords 20..28
+          rec_store4(rec, 20, pw[0][0], pw[1][0], pw[2][0], pw[0][1]);
+          rec_store4(rec, 24, pw[1][1], pw[2][1], pw[0][2], pw[1][2]);
+        }
       }
+      const float rw2 = t.rw2, pwz2 = pw[2][2];
       survives_out = survives;
       if (survives) {
         uint32_t ntiles = (uint32_t)(tr.tx1 - tr.tx0 + 1) * (uint32_t)(tr.ty1 - tr.ty0 + 1);
         if (ntiles > fp.broad_threshold) broad_insert(t, prim << 3, fp, ctr, broad_list);
         else binned = true;
         cls = raster_class(t, fp);
+      }
+      float nrm[3][3], tng[3][3], uv[3][2], im_[3][3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        uv[k][0] = src.v[k]->uv[0]; uv[k][1] = src.v[k]->uv[1];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { nrm[k][c] = src.v[k]->normal[c]; tng[k][c] = src.v[k]->tangent[c]; }
+      }
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int cc = 0; cc < 3; ++cc) im_[r][cc] = src.ib->inv_model.M[r][cc];
+      asm volatile("" :: "v"(im_[0][0]), "v"(im_[0][1]), "v"(im_[0][2]), "v"(im_[1][0]), "v"(im_[1][1]), "v"(im_[1][2]), "v"(im_[2][0]),
+                   "v"(im_[2][1]), "v"(im_[2][2]), "v"(nrm[0][0]), "v"(nrm[1][0]), "v"(nrm[2][0]), "v"(tng[0][0]), "v"(tng[1][0]),
+                   "v"(tng[2][0]), "v"(uv[0][0]), "v"(uv[1][0]), "v"(uv[2][0]) : "memory");
+      // the rest of the head: dwords 8..19 = rw2, uv[3][2], packed_dims, packed, material, clip_base
+      uint32_t material = draw.material;  // (overlay pass: the overlay program, not an index into the material table)
+      const uint8_t *packed = nullptr;
+      uint32_t packed_dims = 0u;
+      if (!OVERLAY) {
+        // (the material's packed form travels in the draw descriptor: no load of the material table here)
+        packed = draw.packed;
+        packed_dims = draw.packed ? draw.packed_dims : 0u;
+      }
+      const unsigned long long packed_bits = (unsigned long long)reinterpret_cast<uintptr_t>(packed);
+      if (OVERLAY) {
+        // ib.inv_model row 0 = the light's colour, or the gizmo's viewMat whose upper 3x3 turns the normals
+        // (gizmo.vert:27).  draw.material is the program: 1 marker, 2 gizmo.  Varyings 0, 1 sit in the head, 2..5 in the body.
+        float o[3][6];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#pragma unroll
+          for (int j = 0; j < 6; ++j) o[k][j] = 0.0f;
+          if (draw.material == 1u) {
+            o[k][0] = im_[0][0]; o[k][1] = im_[0][1]; o[k][2] = im_[0][2];
+          } else {
+            f3 n = ld3(nrm[k]);
+            o[k][0] = tng[k][0]; o[k][1] = tng[k][1]; o[k][2] = tng[k][2];  // the gizmo mesh keeps its colour there
+            o[k][3] = fmaf(im_[2][0], n.z, fmaf(im_[1][0], n.y, im_[0][0] * n.x));
+            o[k][4] = fmaf(im_[2][1], n.z, fmaf(im_[1][1], n.y, im_[0][1] * n.x));
+            o[k][5] = fmaf(im_[2][2], n.z, fmaf(im_[1][2], n.y, im_[0][2] * n.x));
+          }
+        }
+        if (keep) {
+          rec_store4(rec, 8, rw2, o[0][0], o[0][1], o[1][0]);
+          rec_store4(rec, 12, __float_as_uint(o[1][1]), __float_as_uint(o[2][0]), __float_as_uint(o[2][1]), packed_dims);
+          rec_store4(rec, 16, (uint32_t)packed_bits, (uint32_t)(packed_bits >> 32), material, kNotClipped);
+          rec_store4(rec, 20, o[0][2], o[1][2], o[2][2], o[0][3]);
+          rec_store4(rec, 24, o[1][3], o[2][3], o[0][4], o[1][4]);
+          rec_store4(rec, 28, o[2][4], o[0][5], o[1][5], o[2][5]);
+#pragma unroll
+          for (int q = 32; q < kShadeRecDwords; q += 4) rec_store4(rec, q, 0.0f, 0.0f, 0.0f, 0.0f);
+        }
+      } else {
+        if (keep) {
+          rec_store4(rec, 8, rw2, uv[0][0], uv[0][1], uv[1][0]);
+          rec_store4(rec, 12, __float_as_uint(uv[1][1]), __float_as_uint(uv[2][0]), __float_as_uint(uv[2][1]), packed_dims);
+          // (a clipped primitive's clip_base is patched in once the clipper has its arena slots, below)
+          rec_store4(rec, 16, (uint32_t)packed_bits, (uint32_t)(packed_bits >> 32), material, kNotClipped);
+        }
+        // :31-36  normalMat = transpose(mat3(aInvModel)).  Varying-major like the record's body: N of the three vertices, then
+        // T, then B, each 16-byte piece stored when its last value exists.
+        const f3 im0 = mk3(im_[0][0], im_[0][1], im_[0][2]), im1 = mk3(im_[1][0], im_[1][1], im_[1][2]),
+                 im2 = mk3(im_[2][0], im_[2][1], im_[2][2]);
+        f3 N[3], T[3], B[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const f3 n = ld3(nrm[k]);
+          N[k] = normalize3(mk3(dot3(im0, n), dot3(im1, n), dot3(im2, n)));
+        }
+        if (keep) {
+          rec_store4(rec, 28, pwz2, N[0].x, N[1].x, N[2].x);
+          rec_store4(rec, 32, N[0].y, N[1].y, N[2].y, N[0].z);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const f3 tg = ld3(tng[k]);
+          T[k] = normalize3(mk3(dot3(im0, tg), dot3(im1, tg), dot3(im2, tg)));
+        }
+        if (keep) {
+          rec_store4(rec, 36, N[1].z, N[2].z, T[0].x, T[1].x);
+          rec_store4(rec, 40, T[2].x, T[0].y, T[1].y, T[2].y);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) B[k] = cross3(N[k], T[k]);
+        if (keep) {
+          rec_store4(rec, 44, T[0].z, T[1].z, T[2].z, B[0].x);
+          rec_store4(rec, 48, B[1].x, B[2].x, B[0].y, B[1].y);
+          rec_store4(rec, 52, B[2].y, B[0].z, B[1].z, B[2].z);
+        }
       }
     }
   }
@@ -788,12 +883,22 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
   for (unsigned long long cm = __ballot(needs_clip); cm; cm &= cm - 1ull) {
     const int owner = __builtin_amdgcn_readfirstlane(__ffsll((long long)cm) - 1);
     ClipWork &w = s_clip[threadIdx.x >> 6];
-    // the owner's clip-space vertices and primitive index are the wave's input
-    float cv[3][4];
+    // The owner's clip-space vertices and primitive index are the wave's input.  The vertices are not kept from phase 1
+    // (twelve registers in every lane, through the bin loop, for a handful of primitives per frame): the lanes that clip
+    // evaluate them again here from their positions -- vertex_clip_pos, the same bits.
+    float cv[3][4] = {};
+    if (needs_clip) {
+      const DrawDesc cdraw = draws[find_draw(draws, n_draws, first_prims, prim)];
+      float pos[3][3];
+      Mat4 model;
+      load_positions(prim_source(cdraw, prim), pos, model);
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) cv[i][k] = clip[i][k];
+      for (int i = 0; i < 3; ++i) {
+        f3 unused;
+        const f4 c = vertex_clip_pos<OVERLAY>(model, pos[i], pv, view, fp, unused);
+        cv[i][0] = c.x; cv[i][1] = c.y; cv[i][2] = c.z; cv[i][3] = c.w;
+      }
+    }
     Viewport ovp = vp;  // the owner's viewport for the whole wave
     if (OVERLAY) {
       ovp.half_w = __shfl(vp.half_w, owner); ovp.half_h = __shfl(vp.half_h, owner);

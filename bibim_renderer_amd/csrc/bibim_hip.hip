@@ -1311,11 +1311,20 @@ int bbr_upload_mesh(bbr_context *c, const void *vertices, uint32_t n_vertices, c
   Mesh m;
   m.n_vertices = n_vertices;
   m.n_indices = indices ? n_indices : 0;
-  HIP_TRY(c, hipMalloc(&m.d_vertices, (size_t)n_vertices * sizeof(Vertex)));
-  HIP_TRY(c, upload_sync(m.d_vertices, vertices, (size_t)n_vertices * sizeof(Vertex)));
-  if (m.n_indices) {
-    HIP_TRY(c, hipMalloc(&m.d_indices, (size_t)n_indices * sizeof(uint32_t)));
-    HIP_TRY(c, upload_sync(m.d_indices, indices, (size_t)n_indices * sizeof(uint32_t)));
+  // (a failure half way gives back what the mesh already owns: the handle never comes to exist, so nobody else could)
+  const int rc = [&]() -> int {
+    HIP_TRY(c, hipMalloc(&m.d_vertices, (size_t)n_vertices * sizeof(Vertex)));
+    HIP_TRY(c, upload_sync(m.d_vertices, vertices, (size_t)n_vertices * sizeof(Vertex)));
+    if (m.n_indices) {
+      HIP_TRY(c, hipMalloc(&m.d_indices, (size_t)n_indices * sizeof(uint32_t)));
+      HIP_TRY(c, upload_sync(m.d_indices, indices, (size_t)n_indices * sizeof(uint32_t)));
+    }
+    return BBR_OK;
+  }();
+  if (rc != BBR_OK) {
+    if (m.d_vertices) (void)hipFree(m.d_vertices);
+    if (m.d_indices) (void)hipFree(m.d_indices);
+    return rc;
   }
   m.alive = true;
   c->meshes.push_back(m);

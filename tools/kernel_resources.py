@@ -5,7 +5,8 @@ import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "bibim_renderer_amd", "csrc")
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
-       "-fPIC", "-I" + os.path.join(ROOT, "include"), "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(src, "bibim_hip.hip"),
+       "-fPIC", "-I" + os.path.join(ROOT, "include"), "-mllvm", "-amdgpu-kernarg-preload-count=16",  # (the Makefile's flags)
+        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(src, "bibim_hip.hip"),
        "-o", "/dev/null"] + sys.argv[1:]
 err = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
