@@ -199,7 +199,8 @@ def test_depth_greater_or_equal_and_api_order_ties():
 
 
 def test_top_left_rule_shared_edges_cover_once():
-    # a fan of triangles around a vertex on a pixel centre: every pixel inside the quad is hit exactly once
+    # one screen-filling quad of two triangles: every pixel, those on the shared diagonal included, is hit exactly once
+    # (the fan of triangles around a vertex on a pixel centre is in test_raster_reference.py's exact layer)
     sc = quad_scene(32, 32, 3.0, 3.0, "a")
     _, prim, _, st = bbo.render(sc)
     assert st["n_fragments"] == 32 * 32 and st["n_shaded"] == 32 * 32 and (prim != bbo.NO_PRIM).all()
