@@ -2502,19 +2502,6 @@ __global__ void k_selftest_rcp(unsigned long long *__restrict__ mismatches, uint
   if (bad) atomicAdd(mismatches, bad);
 }
 
-// [world][shard_rows][width] float4 -> row-major frame (screen-band un-interleave after the all-gather)
-__global__ void k_unpack_gathered(const float4 *__restrict__ gathered, float4 *__restrict__ frame, int width, int height,
-                                  int world, int band_rows, int shard_rows) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t n = (size_t)width * (size_t)height;
-  if (i >= n) return;
-  int y = (int)(i / (size_t)width), x = (int)(i - (size_t)y * width);
-  int band = y / band_rows, r = y - band * band_rows;
-  int rank = band % world, lb = band / world;
-  size_t src = ((size_t)rank * shard_rows + (size_t)lb * band_rows + r) * (size_t)width + x;
-  frame[i] = gathered[src];
-}
-
 // ------------------------------------------------------------------------------------------------
 // presentation: HDR attachment (binary16) -> hdr_tone_mapping.frag:9-18 -> sRGB UNORM8.
 // Same fixed sequences as the CPU oracle (binary16 rounding, exp, threshold table): byte-exact.
@@ -2560,10 +2547,54 @@ __global__ __launch_bounds__(kPresentThreads) void k_present(const float4 *__res
   }
 }
 
-// Lossless 12.1-byte form of a shard for the all-gather (a quarter less than RGBA32F over links that are the bottleneck
-// at N > 1): alpha is 1.0 where geometry was shaded and 0.0 on cleared pixels (forward_brdf.frag:75 writes 1, the clear
-// colour is 0, src/main.cpp:84; the deferred path writes 1 everywhere), so it travels as one bit.
-//   packed block of a rank = rgb[n][3] float, then (8-byte aligned) one 64-bit mask per 64 pixels, n = shard_rows * width
+// ------------------------------------------------------------------------------------------------
+// The wire forms of the exchange (include/bibim_hip.h, BBR_SHARD_*): what a rank's shard of n = shard_rows * width pixels
+// looks like while it travels.  One struct per form: Whole = pixel of the whole frame it unpacks to, block_bytes(n) = size
+// of one rank's block, load(block, j, n) = pixel j of a block.  How a block is made from the shard: bibim_hip.hip, kWireForms.
+// ------------------------------------------------------------------------------------------------
+
+// the shard as it is, [shard_rows][width] pixels: the fp32 one, or the presented RGBA8 one
+template <class Pixel>
+struct WirePlain {
+  using Whole = Pixel;
+  static constexpr __host__ __device__ size_t block_bytes(size_t n) { return n * sizeof(Pixel); }
+  static __device__ Whole load(const uint8_t *block, size_t j, size_t) { return reinterpret_cast<const Pixel *>(block)[j]; }
+};
+using WireRgba32f = WirePlain<float4>;
+using WireRgba8 = WirePlain<uint32_t>;
+
+// Lossless 12.1-byte form (a quarter less than RGBA32F over links that are the bottleneck at N > 1): alpha is 1.0 where
+// geometry was shaded and 0.0 on cleared pixels (forward_brdf.frag:75 writes 1, the clear colour is 0, src/main.cpp:84;
+// the deferred path writes 1 everywhere), so it travels as one bit.
+//   block = rgb[n][3] float, padding to 8 bytes, one 64-bit mask per 64 pixels (bit k of word w = pixel 64 w + k), padding
+//   to 16 bytes
+struct WirePacked {
+  using Whole = float4;
+  static constexpr __host__ __device__ size_t mask_offset(size_t n) { return (n * 12 + 7) & ~(size_t)7; }
+  static constexpr __host__ __device__ size_t block_bytes(size_t n) { return (mask_offset(n) + ((n + 63) / 64) * 8 + 15) & ~(size_t)15; }
+  static __device__ Whole load(const uint8_t *block, size_t j, size_t n) {
+    const float *rgb = reinterpret_cast<const float *>(block) + 3 * j;
+    const unsigned long long m = reinterpret_cast<const unsigned long long *>(block + mask_offset(n))[j >> 6];
+    return make_float4(rgb[0], rgb[1], rgb[2], ((m >> (j & 63)) & 1ull) ? 1.0f : 0.0f);
+  }
+};
+
+// The reference's own HDR attachment format (R16G16B16A16_SFLOAT, src/render.h:94, src/main.cpp:463-472): 8 bytes per
+// pixel, half of the fp32 shard.  Lossy -- every channel is rounded to the nearest binary16 value (ties to even, the
+// rounding an attachment write performs: bb_half_round) -- and therefore a separate output, never the default.  The whole
+// frame is widened back to RGBA32F (every binary16 value is a binary32 value).
+struct WireRgba16f {
+  using Whole = float4;
+  static constexpr __host__ __device__ size_t block_bytes(size_t n) { return n * 8; }
+  static __device__ Whole load(const uint8_t *block, size_t j, size_t) {
+    const uint2 w = reinterpret_cast<const uint2 *>(block)[j];
+    _Float16 h[4];
+    __builtin_memcpy(h, &w, 8);
+    return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+  }
+};
+
+// fp32 shard -> WirePacked block (`mask` = block + mask_offset(n))
 __global__ void k_pack_shard(const float4 *__restrict__ shard, float *__restrict__ rgb, unsigned long long *__restrict__ mask,
                              size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2579,25 +2610,7 @@ __global__ void k_pack_shard(const float4 *__restrict__ shard, float *__restrict
   if ((threadIdx.x & 63) == 0 && live) mask[i >> 6] = m;
 }
 
-// [world] packed blocks -> row-major RGBA32F frame (the un-interleave of k_unpack_gathered on the packed form)
-__global__ void k_unpack_gathered_packed(const uint8_t *__restrict__ gathered, float4 *__restrict__ frame, int width, int height,
-                                         int world, int band_rows, int shard_rows, size_t block_bytes, size_t mask_offset) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t n = (size_t)width * (size_t)height;
-  if (i >= n) return;
-  int y = (int)(i / (size_t)width), x = (int)(i - (size_t)y * width);
-  int band = y / band_rows, r = y - band * band_rows;
-  int rank = band % world, lb = band / world;
-  const size_t j = ((size_t)lb * band_rows + r) * (size_t)width + x;
-  const uint8_t *block = gathered + (size_t)rank * block_bytes;
-  const float *rgb = reinterpret_cast<const float *>(block) + 3 * j;
-  const unsigned long long m = reinterpret_cast<const unsigned long long *>(block + mask_offset)[j >> 6];
-  frame[i] = make_float4(rgb[0], rgb[1], rgb[2], ((m >> (j & 63)) & 1ull) ? 1.0f : 0.0f);
-}
-
-// The reference's own HDR attachment format as a wire form (R16G16B16A16_SFLOAT, src/render.h:94, src/main.cpp:463-472):
-// 8 bytes per pixel, half of the fp32 shard.  Lossy -- every channel is rounded to the nearest binary16 value (ties to even,
-// the rounding an attachment write performs: bb_half_round) -- and therefore a separate output, never the default.
+// fp32 shard -> WireRgba16f block
 __global__ void k_pack_shard_half(const float4 *__restrict__ shard, uint2 *__restrict__ out, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -2608,31 +2621,24 @@ __global__ void k_pack_shard_half(const float4 *__restrict__ shard, uint2 *__res
   out[i] = w;
 }
 
-// [world][shard_rows][width] RGBA16F -> row-major frame, widened to RGBA32F (every binary16 value is a binary32 value)
-__global__ void k_unpack_gathered_half(const uint2 *__restrict__ gathered, float4 *__restrict__ frame, int width, int height,
-                                       int world, int band_rows, int shard_rows) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t n = (size_t)width * (size_t)height;
-  if (i >= n) return;
-  int y = (int)(i / (size_t)width), x = (int)(i - (size_t)y * width);
-  int band = y / band_rows, r = y - band * band_rows;
-  int rank = band % world, lb = band / world;
-  const uint2 w = gathered[((size_t)rank * shard_rows + (size_t)lb * band_rows + r) * (size_t)width + x];
-  _Float16 h[4];
-  __builtin_memcpy(h, &w, 8);
-  frame[i] = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+// The screen-band un-interleave: pixel i of the row-major frame -> the rank whose shard holds it, and its index there
+// (band b = band_rows framebuffer rows belongs to rank b % world; a shard is its rank's bands stacked in order).
+__device__ __forceinline__ size_t shard_index(size_t i, int width, int world, int band_rows, int &rank) {
+  const int y = (int)(i / (size_t)width), x = (int)(i - (size_t)y * width);
+  const int band = y / band_rows, r = y - band * band_rows;
+  rank = band % world;
+  return ((size_t)(band / world) * band_rows + r) * (size_t)width + x;
 }
 
-// [world][shard_rows][width] RGBA8 -> row-major presented frame (same un-interleave as k_unpack_gathered)
-__global__ void k_unpack_gathered_rgba8(const uint32_t *__restrict__ gathered, uint32_t *__restrict__ frame, int width,
-                                        int height, int world, int band_rows, int shard_rows) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t n = (size_t)width * (size_t)height;
-  if (i >= n) return;
-  int y = (int)(i / (size_t)width), x = (int)(i - (size_t)y * width);
-  int band = y / band_rows, r = y - band * band_rows;
-  int rank = band % world, lb = band / world;
-  frame[i] = gathered[((size_t)rank * shard_rows + (size_t)lb * band_rows + r) * (size_t)width + x];
+// [world] blocks of `shard_pixels` pixels each, back to back (what the all-gather leaves) -> the row-major whole frame
+template <class Form>
+__global__ void k_unpack_gathered(const uint8_t *__restrict__ gathered, typename Form::Whole *__restrict__ frame, int width,
+                                  int height, int world, int band_rows, size_t shard_pixels) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)width * (size_t)height) return;
+  int rank;
+  const size_t j = shard_index(i, width, world, band_rows, rank);
+  frame[i] = Form::load(gathered + (size_t)rank * Form::block_bytes(shard_pixels), j, shard_pixels);
 }
 
 // The peer form of the exchange as ONE kernel (bbr_push_shard, option "push_mode" 1): a workgroup loads a piece of this

@@ -318,6 +318,7 @@ struct bbr_context {
   int n_bands() const { return (height + eff_band_rows() - 1) / eff_band_rows(); }
   int local_bands() const { return world > 1 ? (n_bands() - rank + world - 1) / world : n_bands(); }
   int shard_rows() const { return world > 1 ? ((n_bands() + world - 1) / world) * eff_band_rows() : height; }
+  size_t shard_pixels() const { return (size_t)width * shard_rows(); }  // pixels of this rank's output (world 1: the frame)
 };
 
 namespace {
@@ -779,7 +780,7 @@ int ensure_srgb_tables(bbr_context *c) {
 int queue_present(bbr_context *c, FrameSlot &s) {
   int rc_tables = ensure_srgb_tables(c);
   if (rc_tables) return rc_tables;
-  const size_t n = (size_t)c->width * (c->world > 1 ? c->shard_rows() : c->height);
+  const size_t n = c->shard_pixels();
   // layout 2: on the slot's own stream, behind its k_shade (the other slots' streams keep the GPU busy meanwhile)
   hipStream_t ps = (c->pipelined() && s.stream_used && s.stream_used != c->shade_stream()) ? s.stream_used : c->present_stream();
   if (ps != s.stream_used) HIP_TRY(c, hipStreamWaitEvent(ps, s.ev_shade_done, 0));  // behind the frame's k_shade
@@ -830,7 +831,7 @@ int resubmit_last_frame(bbr_context *c) {
     rc = queue_present(c, s);
     if (rc) return rc;
   } else if (s.fused && present.copy_to) {  // fused: the re-rendered frame is the image; redo the caller's copy
-    const size_t n = (size_t)c->width * (c->world > 1 ? c->shard_rows() : c->height);
+    const size_t n = c->shard_pixels();
     s.present.copy_to = present.copy_to;
     HIP_TRY(c, hipStreamWaitEvent(c->present_stream(), s.ev_shade_done, 0));
     HIP_TRY(c, hipMemcpyAsync(present.copy_to, s.d_present.ptr, n * 4, hipMemcpyDeviceToDevice, c->present_stream()));
@@ -1547,7 +1548,7 @@ int bbr_read_shard(bbr_context *c, float *host) {
     return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shard: the frame was rendered with option present_fused (no fp32 frame); use bbr_read_presented");
   int rc = sync_and_fix(c, nullptr);
   if (rc) return rc;
-  HIP_TRY(c, hipMemcpy(host, last_output(c), (size_t)c->width * c->shard_rows() * 16, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(host, last_output(c), c->shard_pixels() * 16, hipMemcpyDeviceToHost));
   return BBR_OK;
 }
 
@@ -1566,7 +1567,7 @@ int bbr_set_output_device_ptr(bbr_context *c, void *device_ptr, uint64_t bytes) 
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (device_ptr) {
-    uint64_t need = (uint64_t)c->width * (c->world > 1 ? c->shard_rows() : c->height) * 16;
+    uint64_t need = (uint64_t)c->shard_pixels() * 16;
     if (bytes < need) return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_output_device_ptr: buffer too small");
     if ((uintptr_t)device_ptr & 15u) return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_output_device_ptr: need 16-byte alignment");
   }
@@ -1622,7 +1623,7 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
   c->exchange_slot = -1;  // (block sizes change with the partition)
   c->exchange_whole = nullptr;
   if (c->ext_out) {
-    uint64_t need = (uint64_t)c->width * (world > 1 ? c->shard_rows() : c->height) * 16;
+    uint64_t need = (uint64_t)c->shard_pixels() * 16;
     if (c->ext_out_bytes < need) {
       c->ext_out = nullptr;
       c->ext_out_bytes = 0;
@@ -1684,18 +1685,6 @@ int bbr_stream_layout_state(const bbr_context *c, int32_t *out_layout, int32_t *
 int bbr_shard_rows(const bbr_context *c, int32_t *out_rows) {
   if (!c || !out_rows) return BBR_ERR_INVALID_ARGUMENT;
   *out_rows = c->shard_rows();
-  return BBR_OK;
-}
-
-int bbr_unpack_gathered(bbr_context *c, const void *gathered, void *frame, void *stream) {
-  if (!c) return BBR_ERR_INVALID_ARGUMENT;
-  BBR_ON_DEVICE(c);
-  if (!gathered || !frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "unpack_gathered: NULL");
-  size_t n = (size_t)c->width * c->height;
-  hipStream_t st = stream ? (hipStream_t)stream : c->shade_stream();
-  hipLaunchKernelGGL(k_unpack_gathered, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)gathered,
-                     (float4 *)frame, c->width, c->height, c->world, c->eff_band_rows(), c->shard_rows());
-  HIP_TRY(c, hipGetLastError());
   return BBR_OK;
 }
 
@@ -1991,7 +1980,7 @@ int bbr_present(bbr_context *c, void *rgba8_device, int32_t hdr16) {
   BBR_ON_DEVICE(c);
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "present: nothing rendered");
   FrameSlot &s = c->slots[c->last_slot];
-  const size_t n = (size_t)c->width * (c->world > 1 ? c->shard_rows() : c->height);
+  const size_t n = c->shard_pixels();
   if (c->present_fused && s.present.active && s.present.out == s.d_present.ptr) {
     // the frame was rendered as presented pixels already (binary16 stage included); a caller buffer gets a copy
     if (!hdr16) return fail(c, BBR_ERR_INVALID_ARGUMENT, "present: option present_fused always applies the binary16 stage");
@@ -2036,7 +2025,7 @@ int bbr_read_presented(bbr_context *c, uint8_t *host) {
     return fail(c, BBR_ERR_NOT_IN_FRAME, "read_presented: bbr_present was not called for the last frame");
   int rc = sync_and_fix(c, nullptr);
   if (rc) return rc;
-  const size_t n = (size_t)c->width * (c->world > 1 ? c->shard_rows() : c->height);
+  const size_t n = c->shard_pixels();
   HIP_TRY(c, hipMemcpy(host, c->slots[c->last_slot].present.out, n * 4, hipMemcpyDeviceToHost));
   return BBR_OK;
 }
@@ -2048,65 +2037,11 @@ int bbr_presented_device_ptr(bbr_context *c, void **out_ptr, uint64_t *out_bytes
   if (!c->have_frame || c->last_slot < 0 || !c->slots[c->last_slot].present.active)
     return fail(c, BBR_ERR_NOT_IN_FRAME, "presented_device_ptr: bbr_present was not called for the last frame");
   *out_ptr = c->slots[c->last_slot].present.out;
-  if (out_bytes) *out_bytes = (uint64_t)c->width * (c->world > 1 ? c->shard_rows() : c->height) * 4;
+  if (out_bytes) *out_bytes = (uint64_t)c->shard_pixels() * 4;
   return BBR_OK;
 }
 
-int bbr_unpack_gathered_rgba8(bbr_context *c, const void *gathered, void *frame, void *stream) {
-  if (!c) return BBR_ERR_INVALID_ARGUMENT;
-  BBR_ON_DEVICE(c);
-  if (!gathered || !frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "unpack_gathered_rgba8: NULL");
-  size_t n = (size_t)c->width * c->height;
-  hipStream_t st = stream ? (hipStream_t)stream : c->shade_stream();
-  hipLaunchKernelGGL(k_unpack_gathered_rgba8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                     (const uint32_t *)gathered, (uint32_t *)frame, c->width, c->height, c->world, c->eff_band_rows(),
-                     c->shard_rows());
-  HIP_TRY(c, hipGetLastError());
-  return BBR_OK;
-}
-
-namespace {
-// packed shard: rgb[n][3] float, padding to 8 bytes, one 64-bit alpha mask per 64 pixels, padding to 16 bytes
-size_t packed_mask_offset(const bbr_context *c) { return (((size_t)c->width * c->shard_rows() * 12) + 7) & ~(size_t)7; }
-size_t packed_block_bytes(const bbr_context *c) {
-  const size_t n = (size_t)c->width * c->shard_rows();
-  return (packed_mask_offset(c) + ((n + 63) / 64) * 8 + 15) & ~(size_t)15;
-}
-}  // namespace
-
-int bbr_packed_shard_bytes(const bbr_context *c, uint64_t *out_bytes) {
-  if (!c || !out_bytes) return BBR_ERR_INVALID_ARGUMENT;
-  *out_bytes = packed_block_bytes(c);
-  return BBR_OK;
-}
-
-int bbr_pack_shard(bbr_context *c, void *packed, void *stream) {
-  if (!c) return BBR_ERR_INVALID_ARGUMENT;
-  BBR_ON_DEVICE(c);
-  if (!packed) return fail(c, BBR_ERR_INVALID_ARGUMENT, "pack_shard: NULL");
-  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "pack_shard: nothing rendered");
-  const FrameSlot &s = c->slots[c->last_slot];
-  if (s.fused) return fail(c, BBR_ERR_INVALID_ARGUMENT, "pack_shard: no fp32 frame with option present_fused");
-  const size_t n = (size_t)c->width * c->shard_rows();
-  hipStream_t st = stream ? (hipStream_t)stream : s.stream_used;  // a caller's stream must already wait for the frame
-  hipLaunchKernelGGL(k_pack_shard, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)s.out_used,
-                     (float *)packed, (unsigned long long *)((uint8_t *)packed + packed_mask_offset(c)), n);
-  HIP_TRY(c, hipGetLastError());
-  return BBR_OK;
-}
-
-int bbr_unpack_gathered_packed(bbr_context *c, const void *gathered, void *frame, void *stream) {
-  if (!c) return BBR_ERR_INVALID_ARGUMENT;
-  BBR_ON_DEVICE(c);
-  if (!gathered || !frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "unpack_gathered_packed: NULL");
-  size_t n = (size_t)c->width * c->height;
-  hipStream_t st = stream ? (hipStream_t)stream : c->shade_stream();
-  hipLaunchKernelGGL(k_unpack_gathered_packed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)gathered,
-                     (float4 *)frame, c->width, c->height, c->world, c->eff_band_rows(), c->shard_rows(),
-                     packed_block_bytes(c), packed_mask_offset(c));
-  HIP_TRY(c, hipGetLastError());
-  return BBR_OK;
-}
+}  // extern "C" (the exchange's internals are templates over the wire forms)
 
 // ================================================================================================
 // native exchange (BASELINE config #4): the step in which every rank gets the whole frame
@@ -2121,12 +2056,38 @@ int bbr_unpack_gathered_packed(bbr_context *c, const void *gathered, void *frame
 // ================================================================================================
 namespace {
 
-size_t exchange_block_bytes(const bbr_context *c, int form) {
-  const size_t n = (size_t)c->width * c->shard_rows();
-  return form == BBR_SHARD_RGBA32F ? n * 16 : (form == BBR_SHARD_PACKED ? packed_block_bytes(c) : (form == BBR_SHARD_RGBA16F ? n * 8 : n * 4));
+// ---- the wire forms, host side: one row per BBR_SHARD_* value (the device side: bb_kernels.hip.h, "wire forms") ----
+struct WireForm {
+  size_t (*block_bytes)(size_t n);  // bytes of one rank's block of n pixels
+  size_t whole_pixel_bytes;         // per pixel of the whole frame an exchange of this form leaves behind
+  bool presented;                   // made of the presented shard (needs bbr_present), not of the fp32 frame (no present_fused)
+  void (*pack)(const float4 *shard, void *block, size_t n, hipStream_t st);  // nullptr: the shard already is the block
+  void (*unpack)(const bbr_context *c, const void *gathered, void *whole, hipStream_t st);
+};
+dim3 pixel_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }  // every exchange kernel: 256 threads, a pixel each
+void pack_packed(const float4 *shard, void *block, size_t n, hipStream_t st) {
+  hipLaunchKernelGGL(k_pack_shard, pixel_grid(n), dim3(256), 0, st, shard, (float *)block,
+                     (unsigned long long *)((uint8_t *)block + WirePacked::mask_offset(n)), n);
 }
-// bytes per pixel of the whole frame an exchange of this form leaves behind (the binary16 form is widened to fp32)
-size_t whole_pixel_bytes(int form) { return form == BBR_SHARD_RGBA8 ? 4 : 16; }
+void pack_half(const float4 *shard, void *block, size_t n, hipStream_t st) {
+  hipLaunchKernelGGL(k_pack_shard_half, pixel_grid(n), dim3(256), 0, st, shard, (uint2 *)block, n);
+}
+template <class Form>
+void unpack(const bbr_context *c, const void *gathered, void *whole, hipStream_t st) {
+  hipLaunchKernelGGL(k_unpack_gathered<Form>, pixel_grid((size_t)c->width * c->height), dim3(256), 0, st, (const uint8_t *)gathered,
+                     (typename Form::Whole *)whole, c->width, c->height, c->world, c->eff_band_rows(), c->shard_pixels());
+}
+template <class Form>
+constexpr WireForm wire_form(bool presented, decltype(WireForm::pack) pack) {
+  return {&Form::block_bytes, sizeof(typename Form::Whole), presented, pack, &unpack<Form>};
+}
+const WireForm kWireForms[] = {wire_form<WireRgba32f>(false, nullptr), wire_form<WirePacked>(false, pack_packed),
+                               wire_form<WireRgba8>(true, nullptr), wire_form<WireRgba16f>(false, pack_half)};
+static_assert(BBR_SHARD_RGBA32F == 0 && BBR_SHARD_PACKED == 1 && BBR_SHARD_RGBA8 == 2 && BBR_SHARD_RGBA16F == 3, "kWireForms");
+
+bool valid_form(int form) { return form >= 0 && form < (int)(sizeof(kWireForms) / sizeof(kWireForms[0])); }
+size_t exchange_block_bytes(const bbr_context *c, int form) { return kWireForms[form].block_bytes(c->shard_pixels()); }
+size_t whole_frame_bytes(const bbr_context *c, int form) { return (size_t)c->width * c->height * kWireForms[form].whole_pixel_bytes; }
 
 int open_rccl(bbr_context *c) {
   std::lock_guard<std::mutex> lock(g_rccl_mutex);
@@ -2160,29 +2121,23 @@ int open_rccl(bbr_context *c) {
 // Put this rank's block of the last frame where the exchange reads it: `dst` (the rank's slot of a gather buffer, or a
 // peer's).  rgba32f / rgba8 blocks that already live there (the frame was rendered into the slot) cost nothing.
 int stage_block(bbr_context *c, FrameSlot &s, int form, void *dst, hipStream_t st) {
-  const size_t n = (size_t)c->width * c->shard_rows();
-  if (form == BBR_SHARD_PACKED) {
-    hipLaunchKernelGGL(k_pack_shard, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)s.out_used, (float *)dst,
-                       (unsigned long long *)((uint8_t *)dst + packed_mask_offset(c)), n);
+  const WireForm &f = kWireForms[form];
+  const void *shard = f.presented ? (const void *)s.present.out : (const void *)s.out_used;
+  if (f.pack) {
+    f.pack((const float4 *)shard, dst, c->shard_pixels(), st);
     HIP_TRY(c, hipGetLastError());
-    return BBR_OK;
+  } else if (shard != dst) {
+    HIP_TRY(c, hipMemcpyAsync(dst, shard, exchange_block_bytes(c, form), hipMemcpyDeviceToDevice, st));
   }
-  if (form == BBR_SHARD_RGBA16F) {
-    hipLaunchKernelGGL(k_pack_shard_half, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)s.out_used, (uint2 *)dst, n);
-    HIP_TRY(c, hipGetLastError());
-    return BBR_OK;
-  }
-  const void *src = form == BBR_SHARD_RGBA32F ? (const void *)s.out_used : (const void *)s.present.out;
-  if (src != dst) HIP_TRY(c, hipMemcpyAsync(dst, src, exchange_block_bytes(c, form), hipMemcpyDeviceToDevice, st));
   return BBR_OK;
 }
 
 int check_exchange(bbr_context *c, int form, const char *who) {
-  if (form != BBR_SHARD_RGBA32F && form != BBR_SHARD_PACKED && form != BBR_SHARD_RGBA8 && form != BBR_SHARD_RGBA16F)
+  if (!valid_form(form))
     return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": form must be BBR_SHARD_RGBA32F, _PACKED, _RGBA8 or _RGBA16F");
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, std::string(who) + ": nothing rendered");
   const FrameSlot &s = c->slots[c->last_slot];
-  if (form == BBR_SHARD_RGBA8) {
+  if (kWireForms[form].presented) {
     if (!s.present.active || !s.present.out) return fail(c, BBR_ERR_NOT_IN_FRAME, std::string(who) + ": BBR_SHARD_RGBA8 needs bbr_present first");
   } else if (s.fused) {
     return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": no fp32 frame with option present_fused (use BBR_SHARD_RGBA8)");
@@ -2191,25 +2146,23 @@ int check_exchange(bbr_context *c, int form, const char *who) {
 }
 
 int unpack_whole(bbr_context *c, int form, const void *gathered, void *whole, hipStream_t st) {
-  const size_t n = (size_t)c->width * c->height;
-  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (form == BBR_SHARD_RGBA32F)
-    hipLaunchKernelGGL(k_unpack_gathered, grid, block, 0, st, (const float4 *)gathered, (float4 *)whole, c->width, c->height, c->world,
-                       c->eff_band_rows(), c->shard_rows());
-  else if (form == BBR_SHARD_PACKED)
-    hipLaunchKernelGGL(k_unpack_gathered_packed, grid, block, 0, st, (const uint8_t *)gathered, (float4 *)whole, c->width, c->height,
-                       c->world, c->eff_band_rows(), c->shard_rows(), packed_block_bytes(c), packed_mask_offset(c));
-  else if (form == BBR_SHARD_RGBA16F)
-    hipLaunchKernelGGL(k_unpack_gathered_half, grid, block, 0, st, (const uint2 *)gathered, (float4 *)whole, c->width, c->height,
-                       c->world, c->eff_band_rows(), c->shard_rows());
-  else
-    hipLaunchKernelGGL(k_unpack_gathered_rgba8, grid, block, 0, st, (const uint32_t *)gathered, (uint32_t *)whole, c->width, c->height,
-                       c->world, c->eff_band_rows(), c->shard_rows());
+  kWireForms[form].unpack(c, gathered, whole, st);
   HIP_TRY(c, hipGetLastError());
   return BBR_OK;
 }
 
+// the per-form bbr_unpack_gathered* calls: bbr_unpack_whole without its bookkeeping -- no rendered frame needed, the
+// caller's `frame`, the context's shading stream by default, no trace in what bbr_read_whole_frame reads
+int unpack_gathered(bbr_context *c, int form, const void *gathered, void *frame, void *stream) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!gathered || !frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "unpack_gathered: NULL");
+  return unpack_whole(c, form, gathered, frame, stream ? (hipStream_t)stream : c->shade_stream());
+}
+
 }  // namespace
+
+extern "C" {
 
 int bbr_comm_unique_id(bbr_context *c, uint8_t *out_id) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
@@ -2281,7 +2234,7 @@ int bbr_comm_destroy(bbr_context *c) {
 }
 
 int bbr_exchange_block_bytes(const bbr_context *c, int32_t form, uint64_t *out_bytes) {
-  if (!c || !out_bytes || form < 0 || form > BBR_SHARD_RGBA16F) return BBR_ERR_INVALID_ARGUMENT;
+  if (!c || !out_bytes || !valid_form(form)) return BBR_ERR_INVALID_ARGUMENT;
   *out_bytes = exchange_block_bytes(c, form);
   return BBR_OK;
 }
@@ -2301,7 +2254,7 @@ int bbr_allgather_frame(bbr_context *c, int32_t form, void *gathered, void *whol
     gathered = s.d_gathered.ptr;
   }
   if (!whole) {
-    HIP_TRY(c, s.d_whole.ensure((size_t)c->width * c->height * whole_pixel_bytes(form)));
+    HIP_TRY(c, s.d_whole.ensure(whole_frame_bytes(c, form)));
     whole = s.d_whole.ptr;
   }
   hipStream_t st = stream ? (hipStream_t)stream : s.stream_used;
@@ -2389,11 +2342,11 @@ int bbr_push_state(const bbr_context *c, int32_t *out_direct) {
 int bbr_unpack_whole(bbr_context *c, int32_t form, const void *gathered, void *whole, void *stream) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
-  if (form < 0 || form > BBR_SHARD_RGBA16F || !gathered) return fail(c, BBR_ERR_INVALID_ARGUMENT, "unpack_whole: bad form / NULL");
+  if (!valid_form(form) || !gathered) return fail(c, BBR_ERR_INVALID_ARGUMENT, "unpack_whole: bad form / NULL");
   if (c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "unpack_whole: nothing rendered");
   FrameSlot &s = c->slots[c->last_slot];
   if (!whole) {
-    HIP_TRY(c, s.d_whole.ensure((size_t)c->width * c->height * whole_pixel_bytes(form)));
+    HIP_TRY(c, s.d_whole.ensure(whole_frame_bytes(c, form)));
     whole = s.d_whole.ptr;
   }
   int rc = unpack_whole(c, form, gathered, whole, stream ? (hipStream_t)stream : s.stream_used);
@@ -2404,12 +2357,22 @@ int bbr_unpack_whole(bbr_context *c, int32_t form, const void *gathered, void *w
   return BBR_OK;
 }
 
+// ---- the per-form calls that came before the general ones: each is one form of bbr_stage_shard / bbr_unpack_whole ----
+int bbr_unpack_gathered(bbr_context *c, const void *g, void *frame, void *st) { return unpack_gathered(c, BBR_SHARD_RGBA32F, g, frame, st); }
+int bbr_unpack_gathered_packed(bbr_context *c, const void *g, void *frame, void *st) { return unpack_gathered(c, BBR_SHARD_PACKED, g, frame, st); }
+int bbr_unpack_gathered_rgba8(bbr_context *c, const void *g, void *frame, void *st) { return unpack_gathered(c, BBR_SHARD_RGBA8, g, frame, st); }
+int bbr_packed_shard_bytes(const bbr_context *c, uint64_t *out_bytes) { return bbr_exchange_block_bytes(c, BBR_SHARD_PACKED, out_bytes); }
+int bbr_pack_shard(bbr_context *c, void *packed, void *stream) {
+  if (c && !packed) return fail(c, BBR_ERR_INVALID_ARGUMENT, "pack_shard: NULL");  // (reported ahead of the frame's state)
+  return bbr_stage_shard(c, BBR_SHARD_PACKED, packed, stream);
+}
+
 int bbr_whole_frame_device_ptr(bbr_context *c, void **out_ptr, uint64_t *out_bytes) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   if (!out_ptr) return fail(c, BBR_ERR_INVALID_ARGUMENT, "whole_frame_device_ptr: NULL");
   if (c->exchange_slot < 0 || !c->exchange_whole) return fail(c, BBR_ERR_NOT_IN_FRAME, "whole_frame_device_ptr: no exchange yet");
   *out_ptr = c->exchange_whole;
-  if (out_bytes) *out_bytes = (uint64_t)c->width * c->height * (c->exchange_form == BBR_SHARD_RGBA8 ? 4 : 16);
+  if (out_bytes) *out_bytes = whole_frame_bytes(c, c->exchange_form);
   return BBR_OK;
 }
 
@@ -2420,8 +2383,7 @@ int bbr_read_whole_frame(bbr_context *c, void *host) {
   if (c->exchange_slot < 0 || !c->exchange_whole) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_whole_frame: no exchange yet");
   int rc = drain(c);  // (not sync_and_fix: a re-render on one rank alone would leave the collective unmatched)
   if (rc) return rc;
-  HIP_TRY(c, hipMemcpy(host, c->exchange_whole, (size_t)c->width * c->height * (c->exchange_form == BBR_SHARD_RGBA8 ? 4 : 16),
-                       hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(host, c->exchange_whole, whole_frame_bytes(c, c->exchange_form), hipMemcpyDeviceToHost));
   return BBR_OK;
 }
 
@@ -2588,7 +2550,7 @@ int bbr_tone_map(bbr_context *c, int32_t enable, float exposure) {
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "tone_map: nothing rendered");
   if (c->slots[c->last_slot].fused) return fail(c, BBR_ERR_INVALID_ARGUMENT, "tone_map: no fp32 frame with option present_fused");
   float4 *frame = c->slots[c->last_slot].out_used;
-  size_t n = (size_t)c->width * (c->world > 1 ? c->shard_rows() : c->height);
+  size_t n = c->shard_pixels();
   // same stream as the frame's shade kernel: ordered after it
   hipLaunchKernelGGL(k_tone_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->slots[c->last_slot].stream_used, frame, n, enable, exposure);
   HIP_TRY(c, hipGetLastError());

@@ -7,6 +7,8 @@ shard_rows(H, R, band_rows) rows so that every rank contributes an equal-sized b
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import numpy as np
 
 
@@ -75,33 +77,52 @@ def pack_shard_bits(shard):
     return out
 
 
+def unpack_shard_bits(block, rows, width):
+    """one packed block (uint8) -> shard [rows, W, 4] float32: the inverse of pack_shard_bits"""
+    n = rows * width
+    mask_offset = packed_layout(rows, width)[1]
+    shard = np.zeros((rows, width, 4), np.float32)
+    shard[..., :3] = block[:n * 12].view(np.float32).reshape(rows, width, 3)
+    bits = np.unpackbits(block[mask_offset:mask_offset + ((n + 63) // 64) * 8], bitorder="little")[:n]
+    shard[..., 3] = bits.reshape(rows, width).astype(np.float32)
+    return shard
+
+
 def unpack_gathered_packed(gathered, height, width, world, band_rows):
     """gathered: world packed blocks back to back (uint8) -> row-major frame [H, W, 4] float32."""
-    rows = shard_rows(height, world, band_rows)
-    n = rows * width
-    block, mask_offset = packed_layout(rows, width)
-    g = np.ascontiguousarray(gathered, np.uint8).reshape(world, block)
-    shards = np.zeros((world, rows, width, 4), np.float32)
-    for r in range(world):
-        shards[r, ..., :3] = g[r, :n * 12].view(np.float32).reshape(rows, width, 3)
-        bits = np.unpackbits(g[r, mask_offset:mask_offset + ((n + 63) // 64) * 8], bitorder="little")[:n]
-        shards[r, ..., 3] = bits.reshape(rows, width).astype(np.float32)
-    return unpack_gathered(shards, height, band_rows)
+    return decode_gathered(gathered, SHARD_PACKED, height, width, world, band_rows)
 
 
 # ---- the native exchange (bbr_allgather_frame / bbr_push_shard, include/bibim_hip.h): block sizes and copy order ----
 
+# what a rank's shard looks like while it travels (csrc/bb_kernels.hip.h, "wire forms"): whole = channel dtype of the whole
+# frame [H, W, 4] an exchange leaves behind; block_bytes(rows, width) of one rank's block; encode(shard [rows, W, 4]) -> block
+# (uint8); decode(block, rows, width) -> shard of dtype `whole`
+WireForm = namedtuple("WireForm", "whole block_bytes encode decode")
+
+
+def _plain_form(wire, whole):
+    """the block is the shard itself, its channels stored as `wire` (a narrowing conversion rounds to nearest, ties to even:
+    numpy's; the tests pin it to the CPU checker's rounding) and widened back to `whole`"""
+    def encode(shard):
+        with np.errstate(over="ignore"):
+            return np.ascontiguousarray(shard, whole).astype(wire, copy=False).view(np.uint8).reshape(-1)
+    return WireForm(whole, lambda rows, width: rows * width * 4 * np.dtype(wire).itemsize, encode,
+                    lambda block, rows, width: block.view(wire).reshape(rows, width, 4).astype(whole, copy=False))
+
+
 SHARD_RGBA32F, SHARD_PACKED, SHARD_RGBA8, SHARD_RGBA16F = 0, 1, 2, 3
-# bytes per pixel of the forms with a fixed pixel size (the packed form: packed_layout)
-_PIXEL_BYTES = {SHARD_RGBA32F: 16, SHARD_RGBA8: 4, SHARD_RGBA16F: 8}
+FORMS = {
+    SHARD_RGBA32F: _plain_form(np.float32, np.float32),
+    SHARD_PACKED: WireForm(np.float32, lambda rows, width: packed_layout(rows, width)[0], pack_shard_bits, unpack_shard_bits),
+    SHARD_RGBA8: _plain_form(np.uint8, np.uint8),          # the presented shard
+    SHARD_RGBA16F: _plain_form(np.float16, np.float32),    # lossy; every binary16 value is a binary32 value
+}
 
 
 def exchange_block_bytes(form, height, width, world, band_rows):
     """bytes one rank contributes to the exchange (bbr_exchange_block_bytes)"""
-    rows = shard_rows(height, world, band_rows)
-    if form == SHARD_PACKED:
-        return packed_layout(rows, width)[0]
-    return rows * width * _PIXEL_BYTES[form]
+    return FORMS[form].block_bytes(shard_rows(height, world, band_rows), width)
 
 
 def push_order(rank, world):
@@ -134,21 +155,11 @@ def push_offset(rank, block_bytes):
 
 def encode_block(shard, form):
     """a rank's shard [rows, W, 4] as the bytes that travel (uint8): float32 RGBA, the packed form, RGBA8, or binary16 RGBA"""
-    if form == SHARD_PACKED:
-        return pack_shard_bits(shard)
-    if form == SHARD_RGBA16F:   # every channel to the nearest binary16 value, ties to even (numpy's conversion; the tests pin it to the CPU checker's rounding)
-        with np.errstate(over="ignore"):
-            return np.ascontiguousarray(shard, np.float32).astype(np.float16).view(np.uint8).reshape(-1)
-    return np.ascontiguousarray(shard, np.float32 if form == SHARD_RGBA32F else np.uint8).view(np.uint8).reshape(-1)
+    return FORMS[form].encode(shard)
 
 
 def decode_gathered(gathered, form, height, width, world, band_rows):
     """world blocks back to back (uint8) -> the whole frame [H, W, 4] (what bbr_unpack_whole leaves in `whole`)"""
-    g = np.ascontiguousarray(gathered, np.uint8)
-    if form == SHARD_PACKED:
-        return unpack_gathered_packed(g, height, width, world, band_rows)
     rows = shard_rows(height, world, band_rows)
-    if form == SHARD_RGBA16F:   # widened back to RGBA32F (every binary16 value is a binary32 value)
-        return unpack_gathered(g.view(np.float16).reshape(world, rows, width, 4), height, band_rows).astype(np.float32)
-    dt = np.float32 if form == SHARD_RGBA32F else np.uint8
-    return unpack_gathered(g.view(dt).reshape(world, rows, width, 4), height, band_rows)
+    blocks = np.ascontiguousarray(gathered, np.uint8).reshape(world, -1)
+    return unpack_gathered(np.stack([FORMS[form].decode(b, rows, width) for b in blocks]), height, band_rows)

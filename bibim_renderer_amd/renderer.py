@@ -7,7 +7,7 @@ import weakref
 
 import numpy as np
 
-from . import _capi
+from . import _capi, partition
 from ._capi import BbrImage, BbrStats, BibimError, lib
 
 MAP_NAMES = ("albedo", "metallic", "roughness", "ao", "normal", "height")
@@ -352,7 +352,7 @@ class Renderer:
         return p.value, n.value
 
     def read_whole_frame(self, form=0):
-        out = np.empty((self.height, self.width, 4), np.uint8 if form == _capi.SHARD_RGBA8 else np.float32)
+        out = np.empty((self.height, self.width, 4), partition.FORMS[form].whole)
         self._check(self._L.bbr_read_whole_frame(self._ctx, _ptr(out)))
         return out
 

@@ -148,7 +148,8 @@ int bbr_set_partition(bbr_context *ctx, int32_t rank, int32_t world, int32_t ban
 int bbr_shard_rows(const bbr_context *ctx, int32_t *out_rows);
 int bbr_read_shard(bbr_context *ctx, float *rgba32f_host); /* shard_rows*width*4 floats */
 /* Device-side un-interleave of an all-gathered buffer [world][shard_rows][width][4] into a row-major frame, queued on
- * `hip_stream` (NULL = the context's shading stream). */
+ * `hip_stream` (NULL = the context's shading stream).  = bbr_unpack_whole(BBR_SHARD_RGBA32F) into the caller's frame; like
+ * its _packed and _rgba8 siblings it needs no rendered frame and leaves bbr_read_whole_frame's state alone. */
 int bbr_unpack_gathered(bbr_context *ctx, const void *gathered_device, void *frame_device, void *hip_stream);
 /* The same exchange with a quarter less payload, lossless: alpha is 1.0 on shaded pixels and 0.0 on cleared ones
  * (forward_brdf.frag:75, clear colour src/main.cpp:84; the deferred path writes 1 everywhere), so a shard travels as
@@ -157,9 +158,9 @@ int bbr_unpack_gathered(bbr_context *ctx, const void *gathered_device, void *fra
  *                               frame was shaded on; a caller's stream must already wait for the frame, bbr_stream_wait_frame)
  *   bbr_unpack_gathered_packed  [world] packed blocks -> the row-major RGBA32F frame, bit for bit what bbr_unpack_gathered
  *                               makes of the RGBA32F shards */
-int bbr_packed_shard_bytes(const bbr_context *ctx, uint64_t *out_bytes);
-int bbr_pack_shard(bbr_context *ctx, void *packed_device, void *hip_stream);
-int bbr_unpack_gathered_packed(bbr_context *ctx, const void *gathered_device, void *frame_device, void *hip_stream);
+int bbr_packed_shard_bytes(const bbr_context *ctx, uint64_t *out_bytes);                 /* = bbr_exchange_block_bytes(BBR_SHARD_PACKED) */
+int bbr_pack_shard(bbr_context *ctx, void *packed_device, void *hip_stream);             /* = bbr_stage_shard(BBR_SHARD_PACKED) */
+int bbr_unpack_gathered_packed(bbr_context *ctx, const void *gathered_device, void *frame_device, void *hip_stream); /* BBR_SHARD_PACKED */
 int bbr_tile_height(const bbr_context *ctx, int32_t *out_tile_h);
 
 /* ---- diagnostics ---- */
@@ -301,7 +302,7 @@ int bbr_read_presented(bbr_context *ctx, uint8_t *rgba8_host); /* rows*width*4 b
 int bbr_present_buffer(bbr_context *ctx, const void *rgba32f_device, void *rgba8_device, uint64_t n_pixels,
                        int32_t enable_tone_mapping, float exposure, int32_t hdr16, void *hip_stream);
 int bbr_presented_device_ptr(bbr_context *ctx, void **out_ptr, uint64_t *out_bytes);
-int bbr_unpack_gathered_rgba8(bbr_context *ctx, const void *gathered_device, void *frame_device, void *hip_stream);
+int bbr_unpack_gathered_rgba8(bbr_context *ctx, const void *gathered_device, void *frame_device, void *hip_stream); /* BBR_SHARD_RGBA8 */
 /* with option "timing" on: launches of k_present since bbr_timing_reset and their average duration (HIP events) */
 int bbr_present_timing(bbr_context *ctx, uint32_t *out_launches, float *out_avg_ms);
 /* hdr_tone_mapping.frag:9-18 alone on the fp32 frame, in place (no quantisation) */

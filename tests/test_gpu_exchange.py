@@ -9,7 +9,7 @@ import sys
 import numpy as np
 import pytest
 
-from bibim_renderer_amd import Renderer, BibimError, configs, partition as P
+from bibim_renderer_amd import Renderer, BibimError, _capi, configs, partition as P
 from oracle import bbo, scenes
 
 pytestmark = pytest.mark.gpu
@@ -115,6 +115,131 @@ def test_peer_form_among_contexts_on_one_device(scene_and_frames, world, form, p
         r.unpack_whole(form, b.data_ptr())
         assert np.array_equal(r.read_whole_frame(form).view(np.uint8), want.view(np.uint8))
         r.close()
+
+
+FORMS = (P.SHARD_RGBA32F, P.SHARD_PACKED, P.SHARD_RGBA8, P.SHARD_RGBA16F)
+
+
+@pytest.fixture(scope="module")
+def odd_scene(maps64):
+    """71 x 37: an odd pixel count, a width that is no multiple of anything, a last band of 5 rows"""
+    cfg = configs.C3.scaled(71, 37, 64)
+    sc = scenes.shaderball_scene(cfg, bbo.MaterialData(maps64))
+    sc.frame["enable_tone_mapping"], sc.frame["exposure"] = 1, 1.2
+    ref, _, _, _ = bbo.render(sc)
+    return cfg, sc, {P.SHARD_RGBA32F: ref, P.SHARD_PACKED: ref, P.SHARD_RGBA8: bbo.present(ref, 1, 1.2),
+                     P.SHARD_RGBA16F: bbo.half_round(ref)}
+
+
+def _settled(cfg, sc, rank, world, band):
+    r = Renderer(cfg.width, cfg.height)
+    r.set_partition(rank, world, band)
+    r.render_scene(sc)
+    r.synchronize()          # (first frame: capacities)
+    r.render_scene(sc)
+    return r
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_staged_block_of_an_odd_shard_is_the_models(odd_scene, form):
+    """world 1, n = 2627 pixels: 12 n mod 8 = 4 (the packed block's padding in front of the masks is live) and n mod 64 = 3
+    (its last mask word is partial).  stage_shard into a zero-filled buffer leaves the model's block, byte for byte."""
+    import torch
+    cfg, sc, _ = odd_scene
+    r = _settled(cfg, sc, 0, 1, 32)
+    assert r.shard_rows() * cfg.width == 2627
+    block = r.exchange_block_bytes(form)
+    assert block == P.exchange_block_bytes(form, cfg.height, cfg.width, 1, 32)
+    assert P.packed_layout(cfg.height, cfg.width) == (31872, 31528)
+    assert r.packed_shard_bytes() == r.exchange_block_bytes(P.SHARD_PACKED) == 31872
+    if form == P.SHARD_RGBA8:
+        r.present()
+        r.synchronize()      # (the presentation may run on a stream of its own)
+    staged, packed = (torch.zeros(block, dtype=torch.uint8, device="cuda") for _ in range(2))
+    torch.cuda.synchronize()
+    r.stage_shard(form, staged.data_ptr())
+    if form == P.SHARD_PACKED:
+        r.pack_shard(packed.data_ptr())                    # the older name of the same thing
+    r.synchronize()
+    shard = r.read_presented() if form == P.SHARD_RGBA8 else r.read_shard()
+    want = P.encode_block(shard, form)
+    assert want.size == block and np.array_equal(staged.cpu().numpy(), want)
+    if form == P.SHARD_PACKED:
+        assert np.array_equal(packed.cpu().numpy(), want)
+    r.close()
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_uneven_ownership_and_the_older_names(odd_scene, form):
+    """world 3 on 37 rows of band 32: rank 0 owns 32 rows, rank 1 owns 5 rows of its 32-row shard, rank 2 owns nothing;
+    n = 2272, n mod 64 = 32.  The whole frame after push_shard + unpack_whole is the oracle's, and the per-form calls that
+    came before the general ones leave the same bytes -- on a context that has rendered nothing."""
+    import torch
+    cfg, sc, wants = odd_scene
+    world, band, want = 3, 32, wants[form]
+    assert [len(P.owned_rows(cfg.height, k, world, band)) for k in range(world)] == [32, 5, 0]
+    rs = [_settled(cfg, sc, rank, world, band) for rank in range(world)]
+    assert rs[0].shard_rows() * cfg.width == 2272
+    block = rs[0].exchange_block_bytes(form)
+    assert block == P.exchange_block_bytes(form, cfg.height, cfg.width, world, band)
+    bufs = [torch.full((world * block,), 0xAB, dtype=torch.uint8, device="cuda") for _ in range(world)]
+    torch.cuda.synchronize()
+    ptrs, devs = [b.data_ptr() for b in bufs], [0] * world
+    for r in rs:
+        if form == P.SHARD_RGBA8:
+            r.present()
+        r.push_shard(form, ptrs, devs)
+    for r in rs:
+        r.synchronize()          # "all pushes have landed"
+    for r, b in zip(rs, bufs):
+        r.unpack_whole(form, b.data_ptr())
+        assert np.array_equal(r.read_whole_frame(form).view(np.uint8), want.view(np.uint8))
+    older = {P.SHARD_RGBA32F: Renderer.unpack_gathered, P.SHARD_PACKED: Renderer.unpack_gathered_packed,
+             P.SHARD_RGBA8: Renderer.unpack_gathered_rgba8}.get(form)
+    if older:
+        bare = Renderer(cfg.width, cfg.height)               # renders nothing
+        bare.set_partition(1, world, band)
+        frame = torch.zeros(want.nbytes, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        older(bare, bufs[1].data_ptr(), frame.data_ptr())
+        bare.synchronize()
+        assert np.array_equal(frame.cpu().numpy(), rs[1].read_whole_frame(form).view(np.uint8).reshape(-1))
+        with pytest.raises(BibimError):
+            bare.read_whole_frame(form)                      # the older names record no exchange
+        bare.close()
+    if form == P.SHARD_PACKED:                               # pack_shard == stage_shard(SHARD_PACKED), padding rows included
+        assert rs[1].packed_shard_bytes() == block
+        staged, packed = (torch.zeros(block, dtype=torch.uint8, device="cuda") for _ in range(2))
+        torch.cuda.synchronize()
+        rs[1].stage_shard(form, staged.data_ptr())
+        rs[1].pack_shard(packed.data_ptr())
+        rs[1].synchronize()
+        assert np.array_equal(staged.cpu().numpy(), packed.cpu().numpy())
+    for r in rs:
+        r.close()
+
+
+def test_pack_shard_keeps_its_preconditions(odd_scene):
+    import torch
+    cfg, sc, _ = odd_scene
+    r = Renderer(cfg.width, cfg.height)
+    buf = torch.zeros(r.packed_shard_bytes(), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    with pytest.raises(BibimError) as e:
+        r.pack_shard(buf.data_ptr())                       # nothing rendered
+    assert _capi.STATUS[e.value.code] == "BBR_ERR_NOT_IN_FRAME"
+    r.set_option("present_fused", 1)
+    r.render_scene(sc)
+    r.synchronize()
+    with pytest.raises(BibimError) as e:
+        r.pack_shard(buf.data_ptr())                       # no fp32 frame
+    assert _capi.STATUS[e.value.code] == "BBR_ERR_INVALID_ARGUMENT"
+    r.set_option("present_fused", 0)
+    r.render_scene(sc)
+    r.pack_shard(buf.data_ptr())
+    r.synchronize()
+    assert np.array_equal(buf.cpu().numpy(), P.encode_block(r.read_shard(), P.SHARD_PACKED))
+    r.close()
 
 
 _IPC_CHILD = r"""
