@@ -2478,6 +2478,345 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_shade_aniso: k_shade with the sampler's anisotropic filter (option "max_anisotropy" >= 2; src/render.cpp:1349-1350:
+// anisotropyEnable, maxAnisotropy = 16, one mip, LOD 0).
+//
+// With one mip the extra taps are implementation-defined; the rule pinned here is the Vulkan specification's example
+// scheme ("Texel Anisotropic Filtering"), in binary32 and in this operand order (restated
+// independently in tests/aniso_reference.py):
+//   differences  dudx = u(gx + 1, gy) - u(gx, gy), dudy = u(gx, gy + 1) - u(gx, gy), the same for v, where u(X, Y) is this
+//                fragment's OWN evaluation of vUV at that pixel centre -- the planes of its (sub-)triangle, its clip-slot
+//                matrix -- whatever wins the neighbouring pixel (the hardware's helper lane): nothing is read from another
+//                pixel, tile or rank
+//   footprint    per map of w x h texels: px2 = (dudx w)^2 + (dvdx h)^2, py2 likewise; the long axis is x iff px2 > py2
+//   tap count    N = 1 + #{n in 1..15: n^2 min < max} (= ceil(min(ratio, 16)) without a root or a division), capped by the
+//                option; N = 1 when the long axis is at most one texel or a difference is not finite
+//   taps         N = 1: the one tap of k_shade, untouched.  Otherwise tap i = 1..N sits at uv + (i / (N + 1) - 1/2) * (the
+//                long axis' differences), each a whole bilinear_taps + filter_channel
+//   average      the taps summed in order, times the correctly rounded 1 / N
+// One launch shades every item (each wave walks the list with the launch's stride), every lane gathers its own record,
+// and a lane's tap loop runs two taps per trip so that eight loads are in flight before the first is used; the wave stays
+// in the loop until its widest footprint is done.  DUMP = true (bbr_read_surface) also stores what the filter saw and
+// produced, 32 floats per covered pixel; the shipped instantiations have no trace of it.
+// ------------------------------------------------------------------------------------------------
+constexpr int kMaxAnisotropy = 16;
+// R[k] = 1 / k correctly rounded, k = 1 .. 17 (R[N + 1] places the taps, R[N] averages them)
+__constant__ float kAnisoRcp[kMaxAnisotropy + 2] = {
+    0.0f,        1.0f,        1.0f / 2.0f,  1.0f / 3.0f,  1.0f / 4.0f,  1.0f / 5.0f,  1.0f / 6.0f,  1.0f / 7.0f,  1.0f / 8.0f,
+    1.0f / 9.0f, 1.0f / 10.0f, 1.0f / 11.0f, 1.0f / 12.0f, 1.0f / 13.0f, 1.0f / 14.0f, 1.0f / 15.0f, 1.0f / 16.0f, 1.0f / 17.0f};
+constexpr int kSurfaceFloats = 32;  // one record of bbr_read_surface
+
+// the fragment's vUV at the centre of pixel (px, py), from the planes of its own (sub-)triangle: the statements of
+// k_shade's `barycentrics` and its fmaf chain over the three vertex uvs
+struct PlaneUV {
+  float b0, b1, b2, u, v;
+};
+BB_DEV PlaneUV plane_uv(const PlaneHead &h, bool clipped, const float (&cb)[3][3], const float (&uv)[3][2], int px, int py) {
+  const int Xc = px * 256 + 128, Yc = py * 256 + 128;
+  const float dxp = (float)(Xc - h.X0), dyp = (float)(Yc - h.Y0);
+  const float l1 = fmaf(h.l1dx, dxp, h.l1dy * dyp);
+  const float l2 = fmaf(h.l2dx, dxp, h.l2dy * dyp);
+  const float l0 = (1.0f - l1) - l2;
+  const float u0 = l0 * h.rw0, u1 = l1 * h.rw1, u2 = l2 * h.rw2;
+  const float r = bb_rcp((u0 + u1) + u2);
+  PlaneUV o;
+  o.b0 = u0 * r; o.b1 = u1 * r; o.b2 = u2 * r;
+  if (clipped) {  // barycentrics with respect to the unclipped primitive
+    const float c0 = fmaf(o.b2, cb[2][0], fmaf(o.b1, cb[1][0], o.b0 * cb[0][0]));
+    const float c1 = fmaf(o.b2, cb[2][1], fmaf(o.b1, cb[1][1], o.b0 * cb[0][1]));
+    const float c2 = fmaf(o.b2, cb[2][2], fmaf(o.b1, cb[1][2], o.b0 * cb[0][2]));
+    o.b0 = c0; o.b1 = c1; o.b2 = c2;
+  }
+  o.u = fmaf(o.b2, uv[2][0], fmaf(o.b1, uv[1][0], o.b0 * uv[0][0]));
+  o.v = fmaf(o.b2, uv[2][1], fmaf(o.b1, uv[1][1], o.b0 * uv[0][1]));
+  return o;
+}
+
+struct UvFootprint {
+  float u, v, dudx, dvdx, dudy, dvdy;
+};
+// tap count and the differences of the long axis for a map of w x h texels
+struct AnisoTaps {
+  int n;
+  float du, dv;
+};
+BB_DEV AnisoTaps aniso_taps(const UvFootprint &f, int w, int h, int max_aniso) {
+  const float fw = (float)w, fh = (float)h;
+  const float ax = f.dudx * fw, ay = f.dvdx * fh;
+  const float px2 = fmaf(ax, ax, ay * ay);
+  const float bx = f.dudy * fw, by = f.dvdy * fh;
+  const float py2 = fmaf(bx, bx, by * by);
+  const bool x_axis = px2 > py2;
+  const float mx = x_axis ? px2 : py2, mn = x_axis ? py2 : px2;
+  int n = 1;
+#pragma unroll
+  for (int k = 1; k < kMaxAnisotropy; ++k) n += ((float)(k * k) * mn < mx) ? 1 : 0;
+  n = n < max_aniso ? n : max_aniso;
+  const float big = 3.402823466e+38f;
+  const bool finite = fabsf(f.dudx) <= big && fabsf(f.dvdx) <= big && fabsf(f.dudy) <= big && fabsf(f.dvdy) <= big;
+  if (!(mx > 1.0f) || !finite) n = 1;
+  AnisoTaps t;
+  t.n = n;
+  t.du = x_axis ? f.dudx : f.dudy;
+  t.dv = x_axis ? f.dvdx : f.dvdy;
+  return t;
+}
+
+// What a tap is made of, for the two storage forms.  load() asks for the four texels of the bilinear footprint at (u, v),
+// add() filters them and adds every channel to the running sums.
+struct PackedFetch {  // the packed material: 9-byte records, block-linear (issue_taps of k_shade)
+  static constexpr int kChannels = 9;  // albedo rgb, metallic, roughness, ao, normal xyz
+  GlobalBytes texels;
+  int w, h;
+  struct Raw {
+    u32x3 q00, q10, q01, q11;
+    float fx, fy;
+  };
+  BB_DEV Raw load(float u, float v) const {
+    const BilinearTaps tp = bilinear_taps<true>(u, v, w, h);
+    Raw r;
+    r.q00 = *(GlobalTap)(texels + texel_offset(tp.o00)); r.q10 = *(GlobalTap)(texels + texel_offset(tp.o10));
+    r.q01 = *(GlobalTap)(texels + texel_offset(tp.o01)); r.q11 = *(GlobalTap)(texels + texel_offset(tp.o11));
+    r.fx = tp.fx; r.fy = tp.fy;
+    return r;
+  }
+  BB_DEV static void add(const Raw &r, float (&acc)[kChannels]) {
+    acc[0] = acc[0] + filter_channel(r.q00.x, r.q10.x, r.q01.x, r.q11.x, 0, r.fx, r.fy);
+    acc[1] = acc[1] + filter_channel(r.q00.x, r.q10.x, r.q01.x, r.q11.x, 8, r.fx, r.fy);
+    acc[2] = acc[2] + filter_channel(r.q00.x, r.q10.x, r.q01.x, r.q11.x, 16, r.fx, r.fy);
+    acc[3] = acc[3] + filter_channel(r.q00.x, r.q10.x, r.q01.x, r.q11.x, 24, r.fx, r.fy);
+    acc[4] = acc[4] + filter_channel(r.q00.y, r.q10.y, r.q01.y, r.q11.y, 24, r.fx, r.fy);
+    acc[5] = acc[5] + filter_channel(r.q00.z, r.q10.z, r.q01.z, r.q11.z, 0, r.fx, r.fy);
+    acc[6] = acc[6] + filter_channel(r.q00.y, r.q10.y, r.q01.y, r.q11.y, 0, r.fx, r.fy);
+    acc[7] = acc[7] + filter_channel(r.q00.y, r.q10.y, r.q01.y, r.q11.y, 8, r.fx, r.fy);
+    acc[8] = acc[8] + filter_channel(r.q00.y, r.q10.y, r.q01.y, r.q11.y, 16, r.fx, r.fy);
+  }
+};
+template <int CHANNELS>
+struct MapFetch {  // one RGBA8 map of the material table, its first CHANNELS channels
+  static constexpr int kChannels = CHANNELS;
+  const uint32_t *texels;
+  int w, h;
+  struct Raw {
+    uint32_t t00, t10, t01, t11;
+    float fx, fy;
+  };
+  BB_DEV Raw load(float u, float v) const {
+    const BilinearTaps tp = bilinear_taps(u, v, w, h);
+    Raw r;
+    r.t00 = texels[tp.o00]; r.t10 = texels[tp.o10]; r.t01 = texels[tp.o01]; r.t11 = texels[tp.o11];
+    r.fx = tp.fx; r.fy = tp.fy;
+    return r;
+  }
+  BB_DEV static void add(const Raw &r, float (&acc)[kChannels]) {
+#pragma unroll
+    for (int k = 0; k < kChannels; ++k) acc[k] = acc[k] + filter_channel(r.t00, r.t10, r.t01, r.t11, 8 * k, r.fx, r.fy);
+  }
+};
+
+// the filtered value of every channel: the average of t.n taps along the long axis (the one tap at (u, v) when t.n = 1)
+template <class Fetch>
+BB_DEV void aniso_sample(const Fetch &fetch, const UvFootprint &f, const AnisoTaps &t, float (&value)[Fetch::kChannels]) {
+  float acc[Fetch::kChannels];
+#pragma unroll
+  for (int k = 0; k < Fetch::kChannels; ++k) acc[k] = 0.0f;  // (0 + t_1 = t_1 exactly: a tap is never -0)
+  const float step = kAnisoRcp[t.n + 1];
+  for (int i = 1; i <= t.n; i += 2) {
+    // taps i and i + 1: both sets of loads are out before either is filtered
+    const bool second = i + 1 <= t.n;
+    const float oa = fmaf((float)i, step, -0.5f), ob = fmaf((float)(i + 1), step, -0.5f);
+    const float ua = t.n == 1 ? f.u : fmaf(oa, t.du, f.u), va = t.n == 1 ? f.v : fmaf(oa, t.dv, f.v);
+    const typename Fetch::Raw ra = fetch.load(ua, va);
+    typename Fetch::Raw rb = ra;
+    if (second) rb = fetch.load(fmaf(ob, t.du, f.u), fmaf(ob, t.dv, f.v));
+    Fetch::add(ra, acc);
+    if (second) Fetch::add(rb, acc);
+  }
+  const float rn = kAnisoRcp[t.n];
+#pragma unroll
+  for (int k = 0; k < Fetch::kChannels; ++k) value[k] = t.n == 1 ? acc[k] : acc[k] * rn;
+}
+
+template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
+__global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
+    const uint32_t *__restrict__ items, const uint32_t *__restrict__ item_count,
+    const unsigned long long *__restrict__ frags, const uint32_t *__restrict__ frag_count,
+    const ShadeRec *__restrict__ recs, const ClipSlot *__restrict__ clip_arena,
+    FrameParams fp, ShadeParams sp, const CookedLight *__restrict__ cooked,
+    const MaterialDesc *__restrict__ materials, float4 *__restrict__ out,
+    uint2 *__restrict__ gbuffer, const SrgbTables *__restrict__ tables, uint32_t *__restrict__ out8,
+    Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups, int max_aniso,
+    float *__restrict__ dump) {
+  constexpr int TILE_PIXELS = TILE_W * TILE_H;
+  const ConstLights lights_c{(ConstCooked)cooked};
+  // the frame's counter block and chunk totals: as the main launch of k_shade
+  if (blockIdx.x == 0 && threadIdx.x < sizeof(Counters) / 4) {
+    reinterpret_cast<uint32_t *>(ctr_done)[threadIdx.x] = reinterpret_cast<uint32_t *>(ctr)[threadIdx.x];
+    reinterpret_cast<uint32_t *>(ctr)[threadIdx.x] = 0u;
+  }
+  if (blockIdx.x == 0 && item_groups)
+    for (uint32_t g = threadIdx.x; g < (uint32_t)kItemGroups; g += kShadeThreads) item_groups[g * kItemGroupStride] = 0u;
+  const int lane = (int)(threadIdx.x & 63u);
+  const uint32_t n_items = *item_count;
+  for (uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (uint32_t)kShadeWaves + (threadIdx.x >> 6)));
+       j < n_items; j += gridDim.x * (uint32_t)kShadeWaves) {
+    const uint32_t item = items[1u + j];
+    const int chunk = (int)(item & 63u);
+    const int tx = (int)((item >> kItemChunkBits) & ((1u << kItemTxBits) - 1u));
+    int ty, out_tile_row;
+    tile_row(fp, (int)((item & ~kFullTile) >> (kItemChunkBits + kItemTxBits)), ty, out_tile_row);
+    const uint32_t tile = (uint32_t)ty * (uint32_t)fp.tiles_x + (uint32_t)tx;
+    bool valid;
+    unsigned long long frag;
+    if (item & kFullTile) {  // a tile one triangle covers completely: one word, the pixel is the lane's own
+      frag = frags[(size_t)tile * TILE_PIXELS] + ((unsigned long long)((uint32_t)chunk * 64u + (uint32_t)lane) << 32);
+      valid = true;
+    } else {
+      const uint32_t n_frag = frag_count[tile];
+      valid = (uint32_t)chunk * 64u + (uint32_t)lane < n_frag;
+      frag = frags[(size_t)tile * TILE_PIXELS + (uint32_t)chunk * 64u + (uint32_t)lane];
+    }
+    const uint32_t ref = (uint32_t)frag;
+    int x, y;
+    tile_pixel<TILE_W>((int)(frag >> 32) & (TILE_PIXELS - 1), x, y);
+    const int gx = tx * TILE_W + x, gy = ty * TILE_H + y;
+    const size_t o = (size_t)((uint32_t)(out_tile_row * TILE_H + y) * (uint32_t)fp.width + (uint32_t)gx);
+
+    // the head of the primitive record and, for a clipped fragment, its sub-triangle's clip slot
+    const ShadeRec *rp = recs + (ref >> 3);
+    const uint32_t clip1 = (uint32_t)(frag >> (32 + kFragPixBits));  // clip-arena slot + 1, 0: none / unknown
+    bool clipped = clip1 != 0u;
+    const ClipSlot *cp = clip_arena + (clipped ? clip1 - 1u : 0u);
+    PlaneHead h = clipped ? cp->h : rp->h;
+    float uv[3][2], cb[3][3] = {};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { uv[k][0] = rp->uv[k][0]; uv[k][1] = rp->uv[k][1]; }
+    const uint32_t packed_dims = rp->packed_dims, material = rp->material, clip_base = rp->clip_base;
+    const GlobalBytes packed_texels = (GlobalBytes)rp->packed;
+    if (!clipped && clip_base != kNotClipped) {  // a slot k_raster could not put into the fragment word: through the record
+      cp = clip_arena + (clip_base + (ref & 7u));
+      h = cp->h;
+      clipped = true;
+    }
+    if (clipped) {
+#pragma unroll
+      for (int jj = 0; jj < 3; ++jj)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cb[jj][k] = cp->bary[jj][k];
+    }
+    const PlaneUV here = plane_uv(h, clipped, cb, uv, gx, gy);
+    const PlaneUV right = plane_uv(h, clipped, cb, uv, gx + 1, gy), below = plane_uv(h, clipped, cb, uv, gx, gy + 1);
+    UvFootprint f;
+    f.u = here.u; f.v = here.v;
+    f.dudx = right.u - here.u; f.dvdx = right.v - here.v;
+    f.dudy = below.u - here.u; f.dvdy = below.v - here.v;
+    const float b0 = here.b0, b1 = here.b1, b2 = here.b2;
+    float a[kNumVary];
+    a[0] = f.u; a[1] = f.v;
+#pragma unroll
+    for (int jj = 0; jj < kNumBodyVary; ++jj) a[2 + jj] = fmaf(b2, rp->vary[jj][2], fmaf(b1, rp->vary[jj][1], b0 * rp->vary[jj][0]));
+
+    // texture filtering, forward_brdf.frag:16-22 / gbuffer.frag
+    f3 albedo, normal, nt = mk3(0.f, 0.f, 0.f);
+    float metallic, roughness, ao, height = 0.0f;
+    uint32_t taps[kMapCount] = {};  // (DUMP: the tap count used for each map, 0 = not sampled)
+    const MaterialDesc &md = materials[material];
+    if (packed_dims != 0u) {
+      const PackedFetch fetch{packed_texels, (int)(packed_dims & 0xFFFFu), (int)(packed_dims >> 16)};
+      const AnisoTaps t = aniso_taps(f, fetch.w, fetch.h, max_aniso);
+      float s[PackedFetch::kChannels];
+      aniso_sample(fetch, f, t, s);
+      albedo = mk3(s[0], s[1], s[2]);
+      metallic = s[3]; roughness = s[4]; ao = s[5];
+      if (sp.enable_normal_map != 0) nt = mk3(fmaf(s[6], 2.0f, -1.0f), fmaf(s[7], 2.0f, -1.0f), fmaf(s[8], 2.0f, -1.0f));
+      taps[kMapAlbedo] = taps[kMapMetallic] = taps[kMapRoughness] = taps[kMapAO] = (uint32_t)t.n;
+      if (sp.enable_normal_map != 0) taps[kMapNormal] = (uint32_t)t.n;
+    } else {
+      // maps of different sizes: a tap count and a tap loop per map
+      auto one = [&](int map, auto channels, float *value) {
+        const TexDesc &td = md.maps[map];
+        const MapFetch<decltype(channels)::value> fetch{reinterpret_cast<const uint32_t *>(td.texels), td.w, td.h};
+        const AnisoTaps t = aniso_taps(f, td.w, td.h, max_aniso);
+        float s[decltype(channels)::value];
+        aniso_sample(fetch, f, t, s);
+#pragma unroll
+        for (int k = 0; k < decltype(channels)::value; ++k) value[k] = s[k];
+        taps[map] = (uint32_t)t.n;
+      };
+      float s3[3];
+      one(kMapAlbedo, std::integral_constant<int, 3>{}, s3);
+      albedo = mk3(s3[0], s3[1], s3[2]);
+      one(kMapMetallic, std::integral_constant<int, 1>{}, &metallic);
+      one(kMapRoughness, std::integral_constant<int, 1>{}, &roughness);
+      one(kMapAO, std::integral_constant<int, 1>{}, &ao);
+      if (sp.enable_normal_map != 0) {
+        one(kMapNormal, std::integral_constant<int, 3>{}, s3);
+        nt = mk3(fmaf(s3[0], 2.0f, -1.0f), fmaf(s3[1], 2.0f, -1.0f), fmaf(s3[2], 2.0f, -1.0f));
+      }
+    }
+    if (sp.enable_normal_map != 0) {  // vTBN * nt, vTBN = mat3(T, B, N)
+      normal.x = fmaf(a[5], nt.z, fmaf(a[11], nt.y, a[8] * nt.x));
+      normal.y = fmaf(a[6], nt.z, fmaf(a[12], nt.y, a[9] * nt.x));
+      normal.z = fmaf(a[7], nt.z, fmaf(a[13], nt.y, a[10] * nt.x));
+    } else {
+      normal = DEFERRED ? mk3(a[5], a[6], a[7]) : normalize3(mk3(a[5], a[6], a[7]));  // gbuffer.frag:29 / forward :24
+    }
+    if (DEFERRED && (DUMP || gbuffer) && valid) {  // gbuffer.frag's sixth fetch: only when somebody asked to see the texel
+      const TexDesc &td = md.maps[kMapHeight];
+      const MapFetch<1> fetch{reinterpret_cast<const uint32_t *>(td.texels), td.w, td.h};
+      const AnisoTaps t = aniso_taps(f, td.w, td.h, max_aniso);
+      float s[1];
+      aniso_sample(fetch, f, t, s);
+      height = s[0];
+      taps[kMapHeight] = (uint32_t)t.n;
+    }
+    if (DUMP && valid) {
+      float *d = dump + ((size_t)gy * (size_t)fp.width + (size_t)gx) * kSurfaceFloats;
+      const float rec[kSurfaceFloats] = {f.u, f.v, f.dudx, f.dvdx, f.dudy, f.dvdy, a[2], a[3], a[4], normal.x, normal.y, normal.z,
+                                         albedo.x, albedo.y, albedo.z, metallic, roughness, ao, height, nt.x, nt.y, nt.z,
+                                         (float)taps[0], (float)taps[1], (float)taps[2], (float)taps[3], (float)taps[4], (float)taps[5],
+                                         0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < kSurfaceFloats; ++k) d[k] = rec[k];
+    }
+
+    float4 color;
+    if (DEFERRED) {
+      // gbuffer.frag:24-32 into four RGBA16F attachments, then brdf.frag:12-73 on the pixel's own texel (k_shade)
+      const f3 P = mk3(bb_half_round(a[2]), bb_half_round(a[3]), bb_half_round(a[4]));
+      normal = mk3(bb_half_round(normal.x), bb_half_round(normal.y), bb_half_round(normal.z));
+      albedo = mk3(bb_half_round(albedo.x), bb_half_round(albedo.y), bb_half_round(albedo.z));
+      metallic = bb_half_round(metallic); roughness = bb_half_round(roughness); ao = bb_half_round(ao);
+      if (gbuffer && valid) {
+        height = bb_half_round(height);
+        _Float16 g[16] = {(_Float16)P.x, (_Float16)P.y, (_Float16)P.z, (_Float16)1.0f,
+                          (_Float16)normal.x, (_Float16)normal.y, (_Float16)normal.z, (_Float16)0.0f,
+                          (_Float16)albedo.x, (_Float16)albedo.y, (_Float16)albedo.z, (_Float16)0.0f,
+                          (_Float16)metallic, (_Float16)roughness, (_Float16)ao, (_Float16)height};
+        uint4 *dst = reinterpret_cast<uint4 *>(gbuffer) + 2 * ((size_t)gy * (size_t)fp.width + (size_t)gx);
+        uint4 lo, hi;
+        __builtin_memcpy(&lo, g, 16);
+        __builtin_memcpy(&hi, g + 8, 16);
+        dst[0] = lo;
+        dst[1] = hi;
+      }
+      if (fp.gbuffer_view >= 0) {  // buffer_visualize.frag:8-12 instead of brdf.frag
+        const f3 shown = fp.gbuffer_view == 0 ? P : (fp.gbuffer_view == 1 ? normal : (fp.gbuffer_view == 2 ? albedo : mk3(metallic, roughness, ao)));
+        color = make_float4(shown.x, shown.y, shown.z, 1.0f);
+      } else {
+        color = light_surface(sp, lights_c, P, normal, albedo, metallic, roughness, ao);
+      }
+    } else {
+      color = light_surface(sp, lights_c, mk3(a[2], a[3], a[4]), normal, albedo, metallic, roughness, ao);
+    }
+    if (valid) {
+      if (PRESENT) store_pixel(&out8[o], present_pixel(color.x, color.y, color.z, *tables, sp.tone_enable, sp.exposure, 1));
+      else store_pixel(&out[o], color);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // small utility kernels
 // ------------------------------------------------------------------------------------------------
 

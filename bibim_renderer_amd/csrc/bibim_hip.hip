@@ -245,6 +245,9 @@ struct bbr_context {
   bool deferred = false;  // option "render_pass": the reference's deferred path (its default) instead of the forward one
   bool dump_gbuffer = false;
   DeviceBuffer<uint2> d_gbuffer;  // width*height*4 (four RGBA16F texels per pixel), only while bbr_read_gbuffer runs
+  int max_anisotropy = 1;         // option "max_anisotropy": 1 = k_shade's bilinear tap, 2..16 = k_shade_aniso
+  bool dump_surface = false;
+  DeviceBuffer<float> d_surface;  // width*height*32 floats, only while bbr_read_surface runs
   uint32_t ablate = 0;
   int n_cus = 256;         // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   int timing = 0;  // 0 off, 1 five events per frame, 2 only the two events around k_shade
@@ -430,6 +433,7 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s) {
     if (rc_t) return rc_t;
   }
   if (c->dump_gbuffer) HIP_TRY(c, c->d_gbuffer.ensure((size_t)c->width * c->height * 4, true));
+  if (c->dump_surface) HIP_TRY(c, c->d_surface.ensure((size_t)c->width * c->height * kSurfaceFloats, true));
   if (!c->ext_out) HIP_TRY(c, s.d_frame.ensure(out_rows * c->width));
   if (c->dump_vis) {
     HIP_TRY(c, c->d_vis_prim.ensure((size_t)c->width * c->height));
@@ -558,6 +562,20 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameSlot *prev, const Fra
   // one stream an empty tail would still cost the frame a kernel boundary (~4 us).
   const bool tail = main_wgs * kShadeWaves < max_items;
   auto shade = [&](auto deferred, auto present) {
+    if (c->max_anisotropy > 1 || c->dump_surface) {
+      // option "max_anisotropy" / bbr_read_surface: k_shade_aniso, one launch whose waves walk the whole item list
+      if (ev) (void)hipEventRecord(ev[3], ss);
+      auto aniso_launch = [&](auto dump) {
+        hipLaunchKernelGGL((k_shade_aniso<TW, TH, decltype(deferred)::value, decltype(present)::value, decltype(dump)::value>),
+                           dim3(main_wgs), dim3(kShadeThreads), 0, ss, s.d_items.ptr, item_count, s.d_frags.ptr, s.d_frag_count.ptr,
+                           s.d_attrs.ptr, s.d_clip.ptr, fp, sp, s.d_cooked.ptr, c->d_materials.ptr, out, gbuf, tables, out8, ctr,
+                           ctr_done, short_frame ? nullptr : s.d_item_groups.ptr, c->max_anisotropy,
+                           decltype(dump)::value ? c->d_surface.ptr : nullptr);
+      };
+      if (c->dump_surface) aniso_launch(std::true_type{});
+      else aniso_launch(std::false_type{});
+      return;
+    }
     if (tail) {
       hipLaunchKernelGGL((k_shade<TW, TH, decltype(deferred)::value, decltype(present)::value, true, true>), dim3(32), dim3(kShadeThreads),
                          0, sr, s.d_items.ptr, item_count, main_wgs * (uint32_t)kShadeWaves, s.d_frags.ptr, s.d_frag_count.ptr, s.d_attrs.ptr,
@@ -1769,6 +1787,28 @@ int bbr_read_gbuffer(bbr_context *c, float *host) {
   return BBR_OK;
 }
 
+int bbr_read_surface(bbr_context *c, float *host) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface: NULL");
+  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_surface: nothing rendered");
+  if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface: not available on a partitioned context");
+  int rc = sync_and_fix(c, nullptr);
+  if (rc) return rc;
+  // nothing of this lives in memory after a frame: render it once more with the dumping instantiation of k_shade_aniso
+  c->dump_surface = true;
+  rc = resubmit_last_frame(c);
+  if (rc == BBR_OK) rc = sync_and_fix(c, nullptr);
+  c->dump_surface = false;
+  if (rc == BBR_OK) {
+    const size_t n = (size_t)c->width * c->height * kSurfaceFloats;
+    hipError_t e = hipMemcpy(host, c->d_surface.ptr, n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(c, BBR_ERR_HIP, std::string("read_surface: ") + hipGetErrorString(e));
+  }
+  c->d_surface.release();  // (uncovered pixels are the zeros of a fresh buffer)
+  return rc;
+}
+
 int bbr_last_frame_time_ms(bbr_context *c, float *out_frame_ms, float *out_shade_ms) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
@@ -1917,6 +1957,9 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
 #else
     if (value != 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, "ablate: diagnostic builds only (make EXTRA=-DBB_ABLATE)");
 #endif
+  } else if (n == "max_anisotropy") {
+    if (value < 1 || value > kMaxAnisotropy) return fail(c, BBR_ERR_INVALID_ARGUMENT, "max_anisotropy: 1 (bilinear) .. 16");
+    c->max_anisotropy = (int)value;
   } else if (n == "present_fused") {
     c->present_fused = value != 0;
   } else if (n == "overlays") {

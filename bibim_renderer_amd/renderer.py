@@ -162,6 +162,13 @@ class Renderer:
         self._check(self._L.bbr_read_gbuffer(self._ctx, _ptr(out)))
         return out
 
+    def read_surface(self):
+        """what the fragment stage saw and produced per pixel, [h, w, 32] float32 (layout: include/bibim_hip.h,
+        "surface read-back"); re-renders the last frame"""
+        out = np.empty((self.height, self.width, 32), np.float32)
+        self._check(self._L.bbr_read_surface(self._ctx, _ptr(out)))
+        return out
+
     # -- overlay subpass (light markers + corner gizmo over the presented image; SURVEY 8(f) rank 4) --
     def upload_gizmo(self, vertices, indices=None):
         """vertices: float32 [n, 9] = pos, colour, normal (bb::GizmoVertex); indices: uint32 [m] or None"""

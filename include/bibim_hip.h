@@ -204,6 +204,12 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            0 position, 1 normal, 2 albedo, 3 metallic / roughness / ao; -1 (default) the lit scene.
  *                            The frame then goes through presentation like any other
  *   "render_pass" 0|1        0: forward path (default, the path BASELINE measures), 1: deferred path
+ *   "max_anisotropy" 1..16   texture filtering of the fragment stages (src/render.cpp:1349-1350: the reference's sampler has
+ *                            anisotropyEnable, maxAnisotropy = 16).  1 (default): one bilinear tap at LOD 0, the kernels and
+ *                            pixels of every earlier release.  2..16: up to that many bilinear taps along the long axis of
+ *                            the pixel's footprint, averaged (the Vulkan specification's example scheme; the rule is
+ *                            spelled out in DESIGN.md section 3 and under "surface read-back" below).  The TBN overlay's
+ *                            vertex-stage fetch has no derivatives and stays one tap.  Anything else: INVALID_ARGUMENT
  *   "present_fused" 0|1      frames are produced as presented RGBA8 pixels directly (binary16 stage, tone map and sRGB
  *                            encode fused into the raster / shade kernels): no fp32 frame, no k_present pass; bbr_present
  *                            then only marks (or copies to a caller buffer), bbr_read_framebuffer / bbr_read_shard fail
@@ -246,6 +252,27 @@ int bbr_selftest_rcp(bbr_context *ctx, uint32_t lo_bits, uint32_t hi_bits, uint6
  * bbr_read_gbuffer re-renders the last frame and returns width*height*16 floats, per pixel
  * position.xyz 1 | normal.xyz 0 | albedo.rgb 0 | metallic roughness ao height (binary16 values widened); synchronises. */
 int bbr_read_gbuffer(bbr_context *ctx, float *gbuffer_host);
+
+/* ---- surface read-back ----
+ * What the fragment stage saw and produced at every pixel, before lighting: a diagnostic in the family of
+ * bbr_read_visibility / bbr_read_gbuffer.  Re-renders the last frame with a dumping instantiation of the shading kernel
+ * and synchronises; BBR_ERR_NOT_IN_FRAME before a first frame and after bbr_resize, BBR_ERR_INVALID_ARGUMENT on a
+ * partitioned context.  Both passes, any "max_anisotropy" (1 included).  `out` holds height*width*32 floats; an uncovered
+ * pixel is 32 zeros, a covered one
+ *   [0..1]   vUV                        [2..5]   dudx dvdx dudy dvdy
+ *   [6..8]   vPosWorld                  [9..11]  the normal handed to the light loop, before its normalize (deferred:
+ *                                                before the binary16 rounding)
+ *   [12..14] albedo   [15] metallic   [16] roughness   [17] ao   [18] height (deferred only, else 0)
+ *   [19..21] the normal-map sample s*2-1 (0 when EnableNormalMap is 0)
+ *   [22..27] taps N used for each map, PBRMapType order (0: a map the pass did not sample)       [28..31] 0
+ * all filtered values before any binary16 rounding.  The differences and N follow the filter rule of "max_anisotropy":
+ *   dudx = u(x+1, y) - u(x, y), dudy = u(x, y+1) - u(x, y) (v likewise), u(X, Y) being the fragment's own planes
+ *   evaluated at that pixel centre, whatever wins there; per map of w x h texels px2 = (dudx w)^2 + (dvdx h)^2, py2
+ *   likewise, long axis x iff px2 > py2; N = 1 + #{n in 1..15: n^2 min < max}, capped by the option, 1 when max <= 1 (a
+ *   footprint of at most one texel) or a difference is not finite; tap i of N >= 2 at uv + (i / (N + 1) - 1/2) * (the long
+ *   axis' differences); the taps are summed in order and multiplied by 1 / N.  A packed material (five maps of one size)
+ *   has one N, a material whose maps differ in size one per map. */
+int bbr_read_surface(bbr_context *ctx, float *out);
 
 /* ---- overlay subpass ----
  * The reference draws its light markers and the corner gizmo into the swapchain image after tone mapping, depth-tested
