@@ -47,6 +47,8 @@ SIGNATURES = {
     "bbr_device_count": (C.c_int, []),
     "bbr_upload_mesh": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_int32)]),
     "bbr_upload_material": (C.c_int, [_P, C.POINTER(BbrImage), C.POINTER(C.c_int32)]),
+    "bbr_pack_material": (C.c_int, [C.POINTER(BbrImage), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_uint64), _P, C.c_uint64]),
     "bbr_free_mesh": (C.c_int, [_P, C.c_int32]),
     "bbr_free_material": (C.c_int, [_P, C.c_int32]),
     "bbr_set_frame_uniforms": (C.c_int, [_P, _P]),

@@ -23,6 +23,7 @@
 
 #include "../../include/bibim_hip.h"
 #include "bb_kernels.hip.h"
+#include "bb_pack.h"
 
 using namespace bbr;
 
@@ -1292,11 +1293,10 @@ int bbr_create(int32_t width, int32_t height, int32_t device, bbr_context **out_
     CREATE_TRY(hipStreamCreateWithPriority(&c->s_shade, hipStreamNonBlocking, prio_low));
     CREATE_TRY(hipStreamCreateWithPriority(&c->s_present, hipStreamNonBlocking, prio_low));
   }
-  // `default` material maps (resources/pbr/default/*.png are uniform images): 1x1 RGBA8 each
-  static const uint8_t k_default[kMapCount][4] = {{255, 255, 255, 255}, {0, 0, 0, 255},       {0, 0, 0, 255},
-                                                  {255, 255, 255, 255}, {127, 127, 255, 255}, {0, 0, 0, 255}};
-  CREATE_TRY(hipMalloc(&c->d_default_texels, sizeof k_default));
-  CREATE_TRY(upload_sync(c->d_default_texels, k_default, sizeof k_default));
+  // `default` material maps (resources/pbr/default/*.png are uniform images): 1x1 RGBA8 each -- the table a packed material
+  // broadcasts from (bb_pack.h)
+  CREATE_TRY(hipMalloc(&c->d_default_texels, sizeof kDefaultTexel));
+  CREATE_TRY(upload_sync(c->d_default_texels, kDefaultTexel, sizeof kDefaultTexel));
 #undef CREATE_TRY
   {
     std::lock_guard<std::mutex> lock(g_live_mutex);
@@ -1394,48 +1394,18 @@ int bbr_upload_material(bbr_context *c, const bbr_image maps[BBR_MAP_COUNT], int
       m.desc.maps[i] = TexDesc{c->d_default_texels + 4 * i, 1, 1};
     }
   }
-  // Interleave the five shaded maps when they agree on one size (missing maps are uniform, so they broadcast):
-  // a bilinear tap then costs one 12-byte load of a 9-byte record instead of five 4-byte loads from five arrays.
+  // Interleave the five shaded maps when the supplied ones agree on one size (bb_pack.h; missing maps are uniform, so they
+  // broadcast): a bilinear tap then costs one 12-byte load of a 9-byte record instead of five 4-byte loads from five arrays.
   {
-    static const uint8_t k_default[kMapCount][4] = {{255, 255, 255, 255}, {0, 0, 0, 255},       {0, 0, 0, 255},
-                                                    {255, 255, 255, 255}, {127, 127, 255, 255}, {0, 0, 0, 255}};
-    const int used[5] = {kMapAlbedo, kMapMetallic, kMapRoughness, kMapAO, kMapNormal};
-    int pw = 1, ph = 1;
-    bool ok = true;
-    for (int k : used) {
-      const bbr_image &im = maps[k];
-      if (!(im.rgba && im.width > 0 && im.height > 0)) continue;
-      if (pw == 1 && ph == 1) {
-        pw = im.width;
-        ph = im.height;
-      } else if (im.width != pw || im.height != ph) {
-        ok = false;
-      }
-    }
-    if (ok) {
-      // block-linear: 4 x 4 texel blocks of 144 bytes, blocks in row-major order (packed_texel_index in bb_kernels.hip.h):
-      // the 2 x 2 footprint of a bilinear tap set then falls into one block 9 times out of 16
-      const size_t n_texels = (size_t)pw * ph;
-      const size_t w4 = ((size_t)pw + 3) / 4, h4 = ((size_t)ph + 3) / 4;
-      std::vector<uint8_t> host(w4 * h4 * 16 * kPackedTexelBytes + kPackedTexelPad, 0);
-      auto texel = [&](int k, size_t i) -> const uint8_t * {
-        const bbr_image &im = maps[k];
-        return (im.rgba && im.width > 0 && im.height > 0) ? im.rgba + 4 * i : k_default[k];
-      };
-      for (size_t i = 0; i < n_texels; ++i) {
-        const uint8_t *al = texel(kMapAlbedo, i), *me = texel(kMapMetallic, i), *ro = texel(kMapRoughness, i);
-        const uint8_t *ao = texel(kMapAO, i), *no = texel(kMapNormal, i);
-        const size_t x = i % (size_t)pw, y = i / (size_t)pw;
-        uint8_t *t = host.data() + (((y >> 2) * w4 + (x >> 2)) * 16 + (y & 3) * 4 + (x & 3)) * kPackedTexelBytes;
-        t[0] = al[0]; t[1] = al[1]; t[2] = al[2]; t[3] = me[0];
-        t[4] = no[0]; t[5] = no[1]; t[6] = no[2]; t[7] = ro[0];
-        t[8] = ao[0];
-      }
+    const PackPlan plan = pack_plan(maps);
+    if (plan.packable) {
+      std::vector<uint8_t> host(plan.bytes);
+      pack_fill(maps, plan, host.data());
       HIP_TRY(c, hipMalloc(&m.d_packed, host.size()));
       HIP_TRY(c, upload_sync(m.d_packed, host.data(), host.size()));
       m.desc.packed = m.d_packed;
-      m.desc.pw = pw;
-      m.desc.ph = ph;
+      m.desc.pw = plan.pw;
+      m.desc.ph = plan.ph;
     }
   }
   m.alive = true;
@@ -1461,6 +1431,23 @@ int bbr_free_material(bbr_context *c, int32_t material) {
   m = Material();
   c->materials_dirty = true;
   c->have_frame = false;
+  return BBR_OK;
+}
+
+int bbr_pack_material(const bbr_image maps[BBR_MAP_COUNT], int32_t *out_packable, int32_t *out_width, int32_t *out_height,
+                      uint64_t *out_bytes, uint8_t *out_or_null, uint64_t capacity) {
+  if (!maps || !out_packable || !out_width || !out_height || !out_bytes) return BBR_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < kMapCount; ++i)
+    if (map_supplied(maps[i]) && (maps[i].width > 16384 || maps[i].height > 16384)) return BBR_ERR_INVALID_ARGUMENT;
+  const PackPlan plan = pack_plan(maps);
+  *out_packable = plan.packable ? 1 : 0;
+  *out_width = plan.packable ? plan.pw : 0;
+  *out_height = plan.packable ? plan.ph : 0;
+  *out_bytes = plan.bytes;
+  if (out_or_null && plan.packable) {
+    if (capacity < plan.bytes) return BBR_ERR_CAPACITY;
+    pack_fill(maps, plan, out_or_null);
+  }
   return BBR_OK;
 }
 

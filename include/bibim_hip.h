@@ -95,6 +95,12 @@ int bbr_device_count(void);
 int bbr_upload_mesh(bbr_context *ctx, const void *vertices, uint32_t n_vertices, const uint32_t *indices_or_null,
                     uint32_t n_indices, int32_t *out_mesh);
 int bbr_upload_material(bbr_context *ctx, const bbr_image maps[BBR_MAP_COUNT], int32_t *out_material);
+/* What bbr_upload_material does with the five shaded maps, on the host alone (no context, no device): whether they pack
+ * (every supplied one of the same size; a supplied map of another size, 1 x 1 included, leaves the material unpacked), the
+ * packed size, the bytes of the packed form and -- with out_or_null of at least that capacity -- the bytes themselves.
+ * Not packable: *out_width = *out_height = 0, *out_bytes = 0. */
+int bbr_pack_material(const bbr_image maps[BBR_MAP_COUNT], int32_t *out_packable, int32_t *out_width, int32_t *out_height,
+                      uint64_t *out_bytes, uint8_t *out_or_null, uint64_t capacity);
 int bbr_free_mesh(bbr_context *ctx, int32_t mesh);
 int bbr_free_material(bbr_context *ctx, int32_t material);
 
