@@ -30,6 +30,18 @@ class BbrStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class BbrUiCmd(C.Structure):
+    """bbr_ui_cmd: one ImDrawCmd without its pointers (32 bytes)"""
+    _fields_ = [("clip_rect", C.c_float * 4), ("texture", C.c_int32), ("vtx_offset", C.c_uint32), ("idx_offset", C.c_uint32),
+                ("elem_count", C.c_uint32)]
+
+
+class BbrUiDraw(C.Structure):
+    _fields_ = [("vertices", C.c_void_p), ("n_vertices", C.c_uint32), ("indices", C.c_void_p), ("n_indices", C.c_uint32),
+                ("cmds", C.c_void_p), ("n_cmds", C.c_uint32), ("display_pos", C.c_float * 2), ("display_size", C.c_float * 2),
+                ("framebuffer_scale", C.c_float * 2)]
+
+
 class BibimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{STATUS.get(code, code)}: {msg}")
@@ -85,6 +97,10 @@ SIGNATURES = {
     "bbr_read_surface": (C.c_int, [_P, C.c_void_p]),
     "bbr_upload_gizmo": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "bbr_draw_overlays": (C.c_int, [_P, C.c_int32]),
+    "bbr_upload_ui_texture": (C.c_int, [_P, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "bbr_free_ui_texture": (C.c_int, [_P, C.c_int32]),
+    "bbr_draw_ui": (C.c_int, [_P, C.POINTER(BbrUiDraw)]),
+    "bbr_ui_validate": (C.c_int, [C.POINTER(BbrUiDraw), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "bbr_read_tbn_segments": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "bbr_selftest_lines": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "bbr_present": (C.c_int, [_P, C.c_void_p, C.c_int32]),

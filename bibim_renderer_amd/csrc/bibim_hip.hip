@@ -24,6 +24,7 @@
 #include "../../include/bibim_hip.h"
 #include "bb_kernels.hip.h"
 #include "bb_pack.h"
+#include "bb_ui_kernels.hip.h"
 
 using namespace bbr;
 
@@ -144,6 +145,17 @@ struct FrameSlot {
     float exposure = 1.f;
   } present;
   hipEvent_t ev_geom_done = nullptr, ev_raster_done = nullptr, ev_shade_done = nullptr, ev_tail_done = nullptr;
+  // GUI pass (bbr_draw_ui) of the frame in this slot: pinned staging [commands | vertices | indices], its device copy and
+  // the per-triangle records; ev_copied says the staging may be written again
+  struct {
+    void *h_staging = nullptr;
+    size_t staging_cap = 0;
+    DeviceBuffer<uint8_t> d_staging;
+    DeviceBuffer<UiTri> d_tris;
+    DeviceBuffer<UiBox> d_boxes;
+    hipEvent_t ev_copied = nullptr;
+    bool copy_pending = false;
+  } ui;
   bool in_flight = false;
   int32_t tone_enable = 0;  // FrameUniformBlock.EnableToneMapping / Exposure of the frame in this slot
   float tone_exposure = 1.f;
@@ -165,6 +177,13 @@ struct FrameSlot {
     if (h_flags) (void)hipHostFree(h_flags);
     h_flags = nullptr;
     staging_cap = 0;
+    ui.d_staging.release(); ui.d_tris.release(); ui.d_boxes.release();
+    if (ui.h_staging) (void)hipHostFree(ui.h_staging);
+    ui.h_staging = nullptr;
+    ui.staging_cap = 0;
+    if (ui.ev_copied) (void)hipEventDestroy(ui.ev_copied);
+    ui.ev_copied = nullptr;
+    ui.copy_pending = false;
   }
 };
 
@@ -214,6 +233,12 @@ struct bbr_context {
   int last_slot = -1;
 
   DeviceBuffer<SrgbTables> d_srgb_tables;  // thresholds t_k (linear value at which the sRGB byte becomes k) + the keyed table
+  struct UiTexture {
+    uint32_t *d_texels = nullptr;  // RGBA8, row-major
+    int32_t w = 0, h = 0;
+  };
+  std::vector<UiTexture> ui_textures;  // bbr_upload_ui_texture: handle = index + 1, a freed one has no texels
+  DeviceBuffer<float> d_ui_dec;        // the blend's decode table (ui_dec_table)
   DeviceBuffer<uint32_t> d_vis_prim;
   DeviceBuffer<float> d_vis_depth;
   void *ext_out = nullptr;
@@ -1190,6 +1215,175 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
 }
 
 // ================================================================================================
+// GUI pass (src/main.cpp:172): the back end's draw lists blended into the presented image
+// ================================================================================================
+
+extern "C" int bbr_ui_validate(const bbr_ui_draw *draw, int32_t fb_width, int32_t fb_height, int32_t *out_box) {
+  return ui_validate(draw, fb_width, fb_height, out_box);
+}
+
+extern "C" int bbr_upload_ui_texture(bbr_context *c, const uint8_t *rgba8, int32_t w, int32_t h, int32_t *out_texture) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!rgba8 || !out_texture || w <= 0 || h <= 0 || w > 16384 || h > 16384)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "upload_ui_texture: null input or size outside 1..16384");
+  bbr_context::UiTexture t;
+  const size_t bytes = (size_t)w * h * 4;
+  HIP_TRY(c, hipMalloc(&t.d_texels, bytes));
+  const hipError_t e = upload_sync(t.d_texels, rgba8, bytes);
+  if (e != hipSuccess) {
+    (void)hipFree(t.d_texels);
+    return fail(c, BBR_ERR_HIP, std::string("upload_ui_texture: ") + hipGetErrorString(e));
+  }
+  t.w = w;
+  t.h = h;
+  // handles start at 1: 0 is the GUI's null ImTextureID.  The lowest freed handle is handed out again, so a host that
+  // rebuilds its atlas again and again does not grow the table.
+  size_t at = 0;
+  while (at < c->ui_textures.size() && c->ui_textures[at].d_texels) ++at;
+  if (at == c->ui_textures.size()) c->ui_textures.push_back(t);
+  else c->ui_textures[at] = t;
+  *out_texture = (int32_t)at + 1;
+  return BBR_OK;
+}
+
+extern "C" int bbr_free_ui_texture(bbr_context *c, int32_t texture) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  if (!is_live(c)) return BBR_ERR_BAD_HANDLE;
+  BBR_ON_DEVICE(c);
+  if (texture < 1 || texture > (int32_t)c->ui_textures.size() || !c->ui_textures[texture - 1].d_texels)
+    return fail(c, BBR_ERR_BAD_HANDLE, "free_ui_texture: bad handle");
+  int rc = drain(c);  // a queued GUI pass may still sample it
+  if (rc) return rc;
+  (void)hipFree(c->ui_textures[texture - 1].d_texels);
+  c->ui_textures[texture - 1] = bbr_context::UiTexture();
+  return BBR_OK;
+}
+
+extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!draw) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_ui: NULL");
+  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "draw_ui: nothing rendered");
+  if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_ui: not available with a partition");
+  FrameSlot &s = c->slots[c->last_slot];
+  if (!s.present.active || !s.present.out)
+    return fail(c, BBR_ERR_NOT_IN_FRAME, "draw_ui: call bbr_present first (the GUI goes into the presented image)");
+  // int fb_width = (int)(DisplaySize.x * FramebufferScale.x), as the back end computes it
+  for (int k = 0; k < 2; ++k) {
+    const float f = draw->display_size[k] * draw->framebuffer_scale[k];
+    if (!(draw->display_size[k] > 0.0f) || !(f >= 0.0f && f < 65536.0f) || (int32_t)f != (k == 0 ? c->width : c->height))
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_ui: (int)(display_size * framebuffer_scale) is not the context's extent");
+  }
+  int32_t box[4];
+  if (ui_validate(draw, c->width, c->height, box) != BBR_OK)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_ui: malformed draw data (see bbr_ui_validate)");
+  for (uint32_t i = 0; i < draw->n_cmds; ++i) {
+    const int32_t t = draw->cmds[i].texture;
+    if (draw->cmds[i].elem_count && (t < 1 || t > (int32_t)c->ui_textures.size() || !c->ui_textures[t - 1].d_texels))
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_ui: a command names a texture that is not alive");
+  }
+  if (box[2] <= box[0] || box[3] <= box[1]) return BBR_OK;  // nothing can pass a scissor
+
+  // ---- staging: [commands | vertices | indices]; a command whose scissor admits nothing has no triangles ----
+  std::vector<UiCmd> cmds;
+  cmds.reserve(draw->n_cmds);
+  uint64_t n_tris64 = 0;
+  for (uint32_t i = 0; i < draw->n_cmds; ++i) {
+    const bbr_ui_cmd &in = draw->cmds[i];
+    int32_t sc[4];
+    if (!in.elem_count || !ui_scissor(in.clip_rect, *draw, c->width, c->height, sc)) continue;
+    const bbr_context::UiTexture &t = c->ui_textures[in.texture - 1];
+    UiCmd u = {};
+    u.texels = t.d_texels; u.tw = t.w; u.th = t.h;
+    u.vtx_offset = in.vtx_offset; u.idx_offset = in.idx_offset;
+    u.first_tri = (uint32_t)n_tris64;
+    u.sx0 = sc[0]; u.sy0 = sc[1]; u.sx1 = sc[2]; u.sy1 = sc[3];
+    cmds.push_back(u);
+    n_tris64 += in.elem_count / 3u;
+  }
+  if (!n_tris64 || n_tris64 > 0x7FFFFFFFull) return n_tris64 ? fail(c, BBR_ERR_TOO_MANY_PRIMITIVES, "draw_ui: too many triangles") : (int)BBR_OK;
+  const uint32_t n_tris = (uint32_t)n_tris64;
+  const size_t cmds_bytes = cmds.size() * sizeof(UiCmd);
+  const size_t vtx_at = (cmds_bytes + 15) & ~(size_t)15, vtx_bytes = (size_t)draw->n_vertices * kUiVertexBytes;
+  const size_t idx_at = (vtx_at + vtx_bytes + 15) & ~(size_t)15, idx_bytes = (size_t)draw->n_indices * sizeof(uint16_t);
+  const size_t total = idx_at + idx_bytes;
+
+  int rc = ensure_srgb_tables(c);
+  if (rc) return rc;
+  if (!c->d_ui_dec.ptr) {
+    float dec[256];
+    ui_dec_table(dec);
+    HIP_TRY(c, c->d_ui_dec.ensure(256));
+    HIP_TRY(c, upload_sync(c->d_ui_dec.ptr, dec, sizeof dec));
+  }
+  auto &ui = s.ui;
+  if (!ui.ev_copied) HIP_TRY(c, hipEventCreateWithFlags(&ui.ev_copied, hipEventDisableTiming));
+  // Each buffer is tested against its own capacity, so that a call after a failed allocation grows what is still missing.
+  if (total > ui.staging_cap || total > ui.d_staging.cap || n_tris > ui.d_tris.cap || n_tris > ui.d_boxes.cap) {
+    // growing: everything queued for this slot (an earlier GUI pass included) must have left the buffers first
+    HIP_TRY(c, hipEventSynchronize(s.ev_shade_done));
+    ui.copy_pending = false;
+    if (total > ui.staging_cap) {
+      if (ui.h_staging) (void)hipHostFree(ui.h_staging);
+      ui.h_staging = nullptr;
+      ui.staging_cap = 0;
+      const size_t cap = std::max<size_t>(total * 2, 1 << 16);
+      HIP_TRY(c, hipHostMalloc(&ui.h_staging, cap, hipHostMallocDefault));
+      ui.staging_cap = cap;  // the pinned block exists; the device block has a capacity of its own
+    }
+    if (total > ui.d_staging.cap) HIP_TRY(c, ui.d_staging.ensure(ui.staging_cap));
+    const size_t tri_cap = std::max<size_t>((size_t)n_tris * 2, 4096);
+    if (n_tris > ui.d_tris.cap) HIP_TRY(c, ui.d_tris.ensure(tri_cap));
+    if (n_tris > ui.d_boxes.cap) HIP_TRY(c, ui.d_boxes.ensure(tri_cap));
+  }
+  if (ui.copy_pending) {  // an earlier call for this slot: its copy must have read the staging before it is overwritten
+    HIP_TRY(c, hipEventSynchronize(ui.ev_copied));
+    ui.copy_pending = false;
+  }
+  uint8_t *h = static_cast<uint8_t *>(ui.h_staging);
+  std::memcpy(h, cmds.data(), cmds_bytes);
+  std::memcpy(h + vtx_at, draw->vertices, vtx_bytes);
+  std::memcpy(h + idx_at, draw->indices, idx_bytes);
+
+  // behind the presentation (and whatever was queued on the image since), on the stream the presentation used
+  hipStream_t ps = (c->pipelined() && s.stream_used && s.stream_used != c->shade_stream()) ? s.stream_used : c->present_stream();
+  HIP_TRY(c, hipStreamWaitEvent(ps, s.ev_shade_done, 0));
+  HIP_TRY(c, hipMemcpyAsync(ui.d_staging.ptr, ui.h_staging, total, hipMemcpyHostToDevice, ps));
+  HIP_TRY(c, hipEventRecord(ui.ev_copied, ps));
+  ui.copy_pending = true;
+  const UiTransform t = ui_transform(*draw, c->width, c->height);
+  UiParams p = {};
+  for (int k = 0; k < 2; ++k) {
+    p.scale[k] = t.scale[k];
+    p.translate[k] = t.translate[k];
+    p.half[k] = t.half[k];
+  }
+  p.width = c->width;
+  p.height = c->height;
+  hipLaunchKernelGGL(k_ui_setup, dim3((n_tris + 255u) / 256u), dim3(256), 0, ps, p,
+                     reinterpret_cast<const UiCmd *>(ui.d_staging.ptr), (uint32_t)cmds.size(),
+                     reinterpret_cast<const uint32_t *>(ui.d_staging.ptr + vtx_at),
+                     reinterpret_cast<const uint16_t *>(ui.d_staging.ptr + idx_at), n_tris, ui.d_tris.ptr, ui.d_boxes.ptr);
+  // only the tiles of the union of the scissors
+  const int32_t tx0 = box[0] / kUiTile, ty0 = box[1] / kUiTile;
+  const int32_t tx1 = (box[2] + kUiTile - 1) / kUiTile, ty1 = (box[3] + kUiTile - 1) / kUiTile;
+  hipLaunchKernelGGL(k_ui_tiles, dim3((unsigned)(tx1 - tx0), (unsigned)(ty1 - ty0)), dim3(kUiThreads), 0, ps, ui.d_tris.ptr,
+                     ui.d_boxes.ptr, n_tris, tx0, ty0, c->width, c->height, c->d_ui_dec.ptr, c->d_srgb_tables.ptr,
+                     s.present.out);
+  HIP_TRY(c, hipGetLastError());
+  if (s.fused && s.present.copy_to) {
+    // fused presentation into a caller's buffer: bbr_present copied the slot's image there before the GUI was in it, so the
+    // rows the pass may have touched (those of the union box, whole and contiguous) are copied again behind it
+    const size_t first = (size_t)box[1] * c->width, count = (size_t)(box[3] - box[1]) * c->width;
+    HIP_TRY(c, hipMemcpyAsync(static_cast<uint32_t *>(s.present.copy_to) + first, s.present.out + first, count * 4,
+                              hipMemcpyDeviceToDevice, ps));
+  }
+  HIP_TRY(c, hipEventRecord(s.ev_shade_done, ps));  // the slot is busy until the GUI is in the image
+  return BBR_OK;
+}
+
+// ================================================================================================
 // C ABI
 // ================================================================================================
 
@@ -1218,6 +1412,9 @@ static void release_context(bbr_context *c) {
     if (m.d_packed) (void)hipFree(m.d_packed);
   }
   if (c->d_default_texels) (void)hipFree(c->d_default_texels);
+  for (auto &t : c->ui_textures)
+    if (t.d_texels) (void)hipFree(t.d_texels);
+  c->d_ui_dec.release();
   c->d_materials.release();
   c->d_counters.release();
   c->d_counters_done.release();

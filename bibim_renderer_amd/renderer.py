@@ -8,7 +8,7 @@ import weakref
 import numpy as np
 
 from . import _capi, partition
-from ._capi import BbrImage, BbrStats, BibimError, lib
+from ._capi import BbrImage, BbrStats, BbrUiDraw, BibimError, lib
 
 MAP_NAMES = ("albedo", "metallic", "roughness", "ao", "normal", "height")
 # bbr_tbn_segment (include/bibim_hip.h): endpoints in 1/256 pixel, z / w at both ends, key = primitive * 8 + segment
@@ -16,8 +16,45 @@ TBN_SEGMENT_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1"
                               ("key", "<u4"), ("pad", "<u4")])
 
 
+# bbr_ui_cmd and ImDrawVert (include/bibim_hip.h, "GUI pass")
+UI_CMD_DTYPE = np.dtype([("clip_rect", "<f4", (4,)), ("texture", "<i4"), ("vtx_offset", "<u4"), ("idx_offset", "<u4"),
+                         ("elem_count", "<u4")])
+UI_VERTEX_DTYPE = np.dtype([("pos", "<f4", (2,)), ("uv", "<f4", (2,)), ("col", "<u4")])
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+class UiDrawData:
+    """A bbr_ui_draw over numpy arrays (which it keeps alive): vertices UI_VERTEX_DTYPE [n], indices uint16 [m], commands
+    UI_CMD_DTYPE [k] -- all command lists flattened in order, offsets made global."""
+
+    def __init__(self, vertices, indices, cmds, display_pos, display_size, framebuffer_scale=(1.0, 1.0)):
+        self.vertices = np.ascontiguousarray(vertices, UI_VERTEX_DTYPE).reshape(-1)
+        self.indices = np.ascontiguousarray(indices, np.uint16).reshape(-1)
+        self.cmds = np.ascontiguousarray(cmds, UI_CMD_DTYPE).reshape(-1)
+        self.display_pos = tuple(float(x) for x in display_pos)
+        self.display_size = tuple(float(x) for x in display_size)
+        self.framebuffer_scale = tuple(float(x) for x in framebuffer_scale)
+
+    def struct(self):
+        d = BbrUiDraw()
+        d.vertices, d.n_vertices = (self.vertices.ctypes.data if len(self.vertices) else None), len(self.vertices)
+        d.indices, d.n_indices = (self.indices.ctypes.data if len(self.indices) else None), len(self.indices)
+        d.cmds, d.n_cmds = (self.cmds.ctypes.data if len(self.cmds) else None), len(self.cmds)
+        d.display_pos[:] = self.display_pos
+        d.display_size[:] = self.display_size
+        d.framebuffer_scale[:] = self.framebuffer_scale
+        return d
+
+
+def ui_validate(draw, fb_width, fb_height):
+    """bbr_ui_validate (host only): (status, (x0, y0, x1, y1)) -- the union of the drawing commands' scissors in the frame"""
+    box = (C.c_int32 * 4)()
+    d = draw.struct()
+    rc = lib().bbr_ui_validate(C.byref(d), int(fb_width), int(fb_height), box)
+    return rc, tuple(box)
 
 
 class Renderer:
@@ -178,6 +215,23 @@ class Renderer:
 
     def draw_overlays(self, gizmo_extent=100):
         self._check(self._L.bbr_draw_overlays(self._ctx, int(gizmo_extent)))
+
+    # -- GUI pass (the back end's draw lists blended into the presented image; src/main.cpp:172) --
+    def upload_ui_texture(self, rgba8):
+        """uint8 [h, w, 4] -> the handle (>= 1) a bbr_ui_cmd names"""
+        a = np.ascontiguousarray(rgba8, np.uint8)
+        assert a.ndim == 3 and a.shape[2] == 4
+        out = C.c_int32()
+        self._check(self._L.bbr_upload_ui_texture(self._ctx, _ptr(a), a.shape[1], a.shape[0], C.byref(out)))
+        return out.value
+
+    def free_ui_texture(self, texture):
+        self._check(self._L.bbr_free_ui_texture(self._ctx, int(texture)))
+
+    def draw_ui(self, draw):
+        """queue the GUI pass over the image of the last present (asynchronous); draw: UiDrawData"""
+        d = draw.struct()
+        self._check(self._L.bbr_draw_ui(self._ctx, C.byref(d)))
 
     # -- presentation (tone map + sRGB + UNORM8; SURVEY 8(f) rank 1) --
     # -- TBN line overlay (option "tbn": bbr_draw_overlays draws the tangent frames of the last frame first) --

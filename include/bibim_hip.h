@@ -320,6 +320,75 @@ int bbr_read_tbn_segments(bbr_context *ctx, bbr_tbn_segment *out, uint32_t cap, 
 int bbr_selftest_lines(bbr_context *ctx, const bbr_tbn_segment *segs, uint32_t n, int32_t width, int32_t height,
                        const float *depth, uint32_t *out_keys);
 
+/* ---- GUI pass: the last statement of the overlay subpass (src/main.cpp:172) ----
+ * ImGui_ImplVulkan_RenderDrawData(ImGui::GetDrawData(), cmdBuffer) blends the GUI's draw lists into the swapchain image
+ * inside the render pass this library replaces.  The window system, input and widget logic stay the host's; the library
+ * takes the DRAW DATA the GUI code hands to Vulkan: ImDrawVert / ImDrawIdx arrays and the ImDrawCmd records without their
+ * pointers, all command lists flattened in order with their offsets made global (INTEGRATION.md has the loop).
+ *   bbr_upload_ui_texture   ImGui_ImplVulkan_CreateFontsTexture / ImGui_ImplVulkan_AddTexture: an RGBA8 image, row-major;
+ *                           the handle (>= 1) is what the host stores as ImTextureID.  At most 16384 x 16384 texels
+ *   bbr_free_ui_texture     drains the context first.  The handle is dead at once and the lowest dead handle is what the next
+ *                           bbr_upload_ui_texture returns, so a host that rebuilds its atlas keeps a bounded table
+ *   bbr_draw_ui             blends the draw data into the image the last bbr_present wrote -- after bbr_draw_overlays if the
+ *                           host calls that: the same image, a caller's buffer and option "present_fused" included.  With
+ *                           both (a fused frame that bbr_present copied to a caller's buffer) the pass blends into the slot's
+ *                           image and copies the rows of the union box to the caller's buffer again behind itself, so the
+ *                           buffer and bbr_presented_device_ptr hold the same bytes.
+ *                           BBR_ERR_NOT_IN_FRAME before a frame, before a present and after bbr_resize;
+ *                           BBR_ERR_INVALID_ARGUMENT on a partitioned context, when (int)(display_size * framebuffer_scale)
+ *                           is not the context's extent, when bbr_ui_validate fails, or when a command that draws
+ *                           (elem_count > 0) names a texture that is not alive.  Nothing is launched in any of these cases.
+ *                           ASYNCHRONOUS, unlike the debugging overlays (a host draws its GUI every frame): the draw data
+ *                           is copied into pinned staging owned by the frame slot before the call returns and the kernels are
+ *                           queued behind the presentation on the slot's stream.  The call blocks only to grow a buffer (or,
+ *                           called again for the same frame, until the earlier call's copy has left the staging).
+ *                           It never re-renders, and a re-render does not repeat it: a frame that is resubmitted (capacity
+ *                           growth found by a synchronising call, a diagnostic read such as bbr_read_visibility) or
+ *                           presented again has no GUI until the host calls bbr_draw_ui again.
+ *   bbr_ui_validate         host only -- no context, no device: everything bbr_draw_ui requires of the draw data itself.
+ *                           BBR_ERR_INVALID_ARGUMENT for elem_count % 3 != 0, idx_offset + elem_count > n_indices, any
+ *                           vtx_offset + index >= n_vertices, a non-finite pos or uv (of any vertex in the array), a position
+ *                           whose snapped coordinate leaves +-2^23 (1/256 pixel), display_size <= 0, a non-finite
+ *                           display_pos / framebuffer_scale, a NULL array with a non-zero count, a frame beyond 32768.
+ *                           out_box (may be NULL): the union of the scissors of the commands that draw, cut to the frame,
+ *                           x0 y0 x1 y1 with exclusive ends (all 0: nothing to draw); only its tiles are launched.
+ * The rule, binary32 without contraction, in this operand order:
+ *   vertex    scale = 2.0f / display_size, translate = -1.0f - display_pos * scale, ndc = pos * scale + translate (a multiply,
+ *             then an add), w = 1 (external/imgui/imgui_impl_vulkan.cpp:122-126, 301-306); viewport transform and 1/256 snap
+ *             as for scene triangles
+ *   coverage  pixel centres at + 0.5, integer edge functions on the snapped coordinates, top-left rule; cullMode NONE
+ *             (external/imgui/imgui_impl_vulkan.cpp:716): a triangle of negative area has vertices 1 and 2 exchanged WITH their
+ *             attributes before setup, zero area draws nothing
+ *   scissor   external/imgui/imgui_impl_vulkan.cpp:406-425: r = (clip_rect - display_pos) * framebuffer_scale; the command is
+ *             skipped unless r.x < fb_w && r.y < fb_h && r.z >= 0 && r.w >= 0; negative r.x / r.y become 0; offset =
+ *             (int32)r.x, extent = (uint32)(r.z - r.x) -- the difference is truncated, not the ends (a negative difference:
+ *             extent 0); a fragment passes iff offset <= p < offset + extent on both axes
+ *   attribute l1 = fmaf(l1dx, dx, l1dy * dy), l2 likewise, from planes set up once per triangle in binary64 and rounded once,
+ *             (dx, dy) the pixel centre minus snapped vertex 0 in 1/256 pixel; a = fmaf(l2, a2 - a0, fmaf(l1, a1 - a0, a0))
+ *             for u, v and the four colour channels, a colour channel being (float)byte * (1.0f / 255.0f)
+ *   fragment  src = colour * texel per channel (external/imgui/imgui_impl_vulkan.cpp:181-183), texel = one bilinear tap at
+ *             LOD 0, REPEAT (sampler external/imgui/imgui_impl_vulkan.cpp:610-618), the sampler of "max_anisotropy" 1
+ *   blend     external/imgui/imgui_impl_vulkan.cpp:724-732 on the sRGB UNORM8 image: the pixel's BYTES are the destination,
+ *             d = dec[byte] ((float) of the binary64 EOTF of byte / 255.0), ia = 1.0f - sa, o = fmaf(s, sa, d * ia), byte =
+ *             the sRGB encode of o as in bbr_present; alpha oa = sa * ia (factors ONE_MINUS_SRC_ALPHA and ZERO, as the back end
+ *             sets them), byte = rintf(255.0f * clamp01(oa)).  Requantised to bytes after EVERY fragment
+ *   order     the fragments of a pixel are blended in command order and, within a command, in index order */
+typedef struct bbr_ui_cmd {            /* one ImDrawCmd without its pointers; 32 bytes */
+  float    clip_rect[4];               /* x1 y1 x2 y2, as ImDrawCmd::ClipRect */
+  int32_t  texture;                    /* handle from bbr_upload_ui_texture */
+  uint32_t vtx_offset, idx_offset, elem_count;
+} bbr_ui_cmd;
+typedef struct bbr_ui_draw {
+  const void     *vertices;  uint32_t n_vertices;  /* ImDrawVert, 20 B: pos f32x2 @0, uv f32x2 @8, col RGBA8 @16 (R = low byte) */
+  const uint16_t *indices;   uint32_t n_indices;   /* ImDrawIdx = unsigned short in the reference's build */
+  const bbr_ui_cmd *cmds;    uint32_t n_cmds;      /* all command lists flattened in order, offsets made global */
+  float display_pos[2], display_size[2], framebuffer_scale[2];
+} bbr_ui_draw;
+int bbr_upload_ui_texture(bbr_context *ctx, const uint8_t *rgba8, int32_t w, int32_t h, int32_t *out_texture);
+int bbr_free_ui_texture(bbr_context *ctx, int32_t texture);
+int bbr_draw_ui(bbr_context *ctx, const bbr_ui_draw *draw);
+int bbr_ui_validate(const bbr_ui_draw *draw, int32_t fb_width, int32_t fb_height, int32_t *out_box /* x0 y0 x1 y1 */);
+
 /* ---- presentation: the step after the path ----
  * Replaces the tone-map subpass + swapchain write (src/main.cpp:123-126, src/shaders/hdr_tone_mapping.frag:9-18,
  * HDR attachment R16G16B16A16_SFLOAT src/render.h:94, sRGB swapchain format src/render.cpp:242-254):

@@ -9,6 +9,8 @@
   default_texels.json      resources/pbr/default/*.png decoded by the reference's stb_image 2.25
   gizmo.npz                gizmo.obj/.mtl expanded to bb::GizmoVertex[] + indices
   oracle_frames.npz, n_shaded.json, presented.npz   outputs of the oracle itself, frozen
+  ui_drawdata.npz          draw data of a headless GUI frame (tools/ui_fixture_mint.cpp, built against the reference's GUI
+                           library) and the font atlas' alpha; ui_tables.json: the bits of the GUI blend's decode table
 
 Fixtures are data (inputs / expected outputs); no reference source text is stored.
 """
@@ -419,6 +421,40 @@ def light_gold():
     print("light_gold", {k: v.shape for k, v in maps.items()})
 
 
+def ui_drawdata():
+    """tools/ui_fixture_mint.cpp -> tests/golden/ui_drawdata.npz, and the decode table of tests/ui_reference.py -> ui_tables.json"""
+    import subprocess
+    tmp = os.path.join(ROOT, "tools", "_tmp")
+    os.makedirs(tmp, exist_ok=True)
+    exe, raw = os.path.join(tmp, "ui_fixture_mint"), os.path.join(tmp, "ui_drawdata.bin")
+    gui = os.path.join(REF, "src", "external", "imgui")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I" + os.path.join(REF, "src"), "-I" + os.path.join(REF, "src", "external"),
+                           os.path.join(ROOT, "tools", "ui_fixture_mint.cpp")] +
+                          [os.path.join(gui, f) for f in ("imgui.cpp", "imgui_draw.cpp", "imgui_widgets.cpp")] + ["-o", exe])
+    print(subprocess.check_output([exe, raw], text=True).strip())
+    b = open(raw, "rb").read()
+    nv, ni, nc, nl, aw, ah = np.frombuffer(b, "<u4", 6)
+    geo = np.frombuffer(b, "<f4", 6, 24)
+    at = 48
+    vertices = np.frombuffer(b, "<u4", int(nv) * 5, at).reshape(-1, 5)
+    at += int(nv) * 20
+    indices = np.frombuffer(b, "<u2", int(ni), at)
+    at += int(ni) * 2
+    cmds = np.frombuffer(b, "<u4", int(nc) * 8, at).reshape(-1, 8)
+    at += int(nc) * 32
+    alpha = np.frombuffer(b, np.uint8, int(aw) * int(ah), at).reshape(int(ah), int(aw))
+    assert at + alpha.size == len(b)
+    np.savez_compressed(os.path.join(GOLD, "ui_drawdata.npz"), vertices=vertices, indices=indices, cmds=cmds, n_lists=np.uint32(nl),
+                        display_pos=geo[0:2], display_size=geo[2:4], framebuffer_scale=geo[4:6], atlas_alpha=alpha)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ui_reference
+    json.dump({"note": "dec[b] = (float) of the binary64 sRGB EOTF of b / 255.0, as binary32 bit patterns (the destination of the "
+                       "GUI pass's blend; DESIGN.md section 3)",
+               "dec_bits": [int(x) for x in ui_reference.DEC.view(np.uint32)]},
+              open(os.path.join(GOLD, "ui_tables.json"), "w"), indent=1)
+    print("ui_drawdata", os.path.getsize(os.path.join(GOLD, "ui_drawdata.npz")), "bytes")
+
+
 def contract_manifest():
     """tests/golden/CONTRACT.json: which revision of the arithmetic contract (oracle/bb_oracle.h, BBO_CONTRACT_REVISION)
     minted the frozen frames, and their hashes -- a re-mint shows up as a diff of this file next to a new revision."""
@@ -444,7 +480,7 @@ def contract_manifest():
 
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
-    which = sys.argv[1:] or ["shaderball", "math_golden", "default_texels", "gizmo", "golden_frames", "n_shaded", "present", "deferred", "reference_pngs", "uv_sphere", "overlays", "math_random", "reference_citations", "reference_assets", "light_gold"]
+    which = sys.argv[1:] or ["shaderball", "math_golden", "default_texels", "gizmo", "golden_frames", "n_shaded", "present", "deferred", "reference_pngs", "uv_sphere", "overlays", "math_random", "reference_citations", "reference_assets", "light_gold", "ui_drawdata"]
     if sys.argv[1:] == ["contract_manifest"]:
         contract_manifest()
         sys.exit(0)
