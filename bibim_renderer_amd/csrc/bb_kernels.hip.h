@@ -8,6 +8,9 @@
 //                also cooks the frame's light table
 //   k_shade      forward_brdf.frag + brdf.glsl once per visible pixel (src/shaders/forward_brdf.frag:15-76,
 //                brdf.glsl:2-36): one wave per item; a TAIL instantiation loops over what the main launch's estimate missed
+//   (in front of k_shade, "what the fragment kernels share": barycentrics, item decode, fragment fetch, late clip slot, counter
+//                hand-over, normal, one map tap, deferred tail and final store, each stated once for k_shade, k_shade_aniso
+//                and k_shade_overlay)
 //   k_present, k_tone_map, k_deferred_background, k_shade_overlay, k_pack_shard / k_unpack_*: the rows either side of the path
 //   k_tbn_segments, k_tbn_raster, k_tbn_colour: the TBN line overlay (option "tbn"; tbn.vert / tbn.geom)
 //
@@ -2064,14 +2067,162 @@ typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 typedef u32x3 __attribute__((aligned(1))) u32x3_any;  // 12 bytes at any byte address: one global_load_dwordx3
 typedef const u32x3_any __attribute__((address_space(1))) *GlobalTap;
 
-// one work item as the loop carries it: where its 64 fragments are (all uniform, held in scalar registers) and the
-// fragment word of this lane
-struct ItemFrag {
-  unsigned long long frag;
-  uint32_t n_frag;                  // fragments in the tile's list
-  int tx, ty, out_tile_row, chunk;
-  bool live;                        // the item exists
+// ------------------------------------------------------------------------------------------------
+// What the fragment kernels share: the rules of the fragment stage that k_shade, k_shade_aniso and k_shade_overlay all
+// follow, each stated once.  Everything here is forced inline: the kernels compile to the code they had with the
+// statements written out in place.
+// ------------------------------------------------------------------------------------------------
+
+// a varying at barycentrics (b0, b1, b2) from its values at the three vertices
+BB_DEV float interp3(float b0, float b1, float b2, float v0, float v1, float v2) { return fmaf(b2, v2, fmaf(b1, v1, b0 * v0)); }
+
+// perspective-correct barycentrics of the centre of pixel (px, py) from the screen-space planes of a (sub-)triangle; for a
+// clipped sub-triangle then taken through its clip slot's 3 x 3 to those of the unclipped primitive
+BB_DEV void plane_bary(const PlaneHead &h, bool clipped, const float (&cb)[3][3], int px, int py, float &b0, float &b1, float &b2) {
+  const int Xc = px * 256 + 128, Yc = py * 256 + 128;
+  const float dxp = (float)(Xc - h.X0), dyp = (float)(Yc - h.Y0);
+  const float l1 = fmaf(h.l1dx, dxp, h.l1dy * dyp);
+  const float l2 = fmaf(h.l2dx, dxp, h.l2dy * dyp);
+  const float l0 = (1.0f - l1) - l2;
+  const float u0 = l0 * h.rw0, u1 = l1 * h.rw1, u2 = l2 * h.rw2;
+  const float r = bb_rcp((u0 + u1) + u2);
+  b0 = u0 * r; b1 = u1 * r; b2 = u2 * r;
+  if (clipped) {
+    const float c0 = interp3(b0, b1, b2, cb[0][0], cb[1][0], cb[2][0]);
+    const float c1 = interp3(b0, b1, b2, cb[0][1], cb[1][1], cb[2][1]);
+    const float c2 = interp3(b0, b1, b2, cb[0][2], cb[1][2], cb[2][2]);
+    b0 = c0; b1 = c1; b2 = c2;
+  }
+}
+
+// one work item: where its 64 fragments are (all wave-uniform, held in scalar registers)
+struct ItemPlace {
+  int chunk, tx, ty, out_tile_row;
+  uint32_t tile;
 };
+BB_DEV ItemPlace decode_item(const FrameParams &fp, uint32_t item) {
+  ItemPlace p;
+  p.chunk = (int)(item & 63u);
+  p.tx = (int)((item >> kItemChunkBits) & ((1u << kItemTxBits) - 1u));
+  tile_row(fp, (int)((item & ~kFullTile) >> (kItemChunkBits + kItemTxBits)), p.ty, p.out_tile_row);
+  p.tile = (uint32_t)p.ty * (uint32_t)fp.tiles_x + (uint32_t)p.tx;
+  return p;
+}
+
+// this lane's fragment word of an item, and whether the lane has one.  A tile one triangle covers completely has no list and
+// no count: one word, the pixel is the lane's own (and the wave is uniform).  CONST_WORD: that word comes through the scalar
+// cache (constant address space).
+template <int TILE_PIXELS, bool CONST_WORD>
+BB_DEV unsigned long long fetch_fragment(uint32_t item, const ItemPlace &p, int lane, const unsigned long long *__restrict__ frags,
+                                         const uint32_t *__restrict__ frag_count, bool &valid) {
+  typedef const unsigned long long __attribute__((address_space(4))) *ConstFrags;
+  unsigned long long frag;
+  if (item & kFullTile) {
+    frag = (CONST_WORD ? ((ConstFrags)frags)[(size_t)p.tile * TILE_PIXELS] : frags[(size_t)p.tile * TILE_PIXELS]) +
+           ((unsigned long long)((uint32_t)p.chunk * 64u + (uint32_t)lane) << 32);
+    valid = true;
+  } else {
+    const uint32_t n_frag = frag_count[p.tile];
+    valid = (uint32_t)p.chunk * 64u + (uint32_t)lane < n_frag;
+    frag = frags[(size_t)p.tile * TILE_PIXELS + (uint32_t)p.chunk * 64u + (uint32_t)lane];
+  }
+  return frag;
+}
+
+// The "late" clip slot.  k_raster names a clipped sub-triangle's slot in the fragment word for the first kClipRefs of a
+// tile only; a fragment of any further one carries 0 there, although its record says the primitive was clipped.  Its slot
+// is then found through the record, one round trip later: sub-triangle (ref & 7) of the primitive's run.
+BB_DEV bool late_clip_slot(bool clipped, uint32_t clip_base) { return !clipped && clip_base != kNotClipped; }
+BB_DEV uint32_t record_clip_slot(uint32_t clip_base, uint32_t ref) { return clip_base + (ref & 7u); }
+
+// The frame's counter block has done its job (k_geometry filled it, k_raster read it): keep a copy for the host's
+// statistics / overflow check and clear the block for the next frame of this slot, and the chunk totals k_shade_items is
+// done with.  Frames of different slots share nothing, so their kernels may overlap freely.
+BB_DEV void retire_counters(Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups) {
+  if (blockIdx.x == 0 && threadIdx.x < sizeof(Counters) / 4) {
+    reinterpret_cast<uint32_t *>(ctr_done)[threadIdx.x] = reinterpret_cast<uint32_t *>(ctr)[threadIdx.x];
+    reinterpret_cast<uint32_t *>(ctr)[threadIdx.x] = 0u;
+  }
+  if (blockIdx.x == 0 && item_groups)
+    for (uint32_t g = threadIdx.x; g < (uint32_t)kItemGroups; g += kShadeThreads) item_groups[g * kItemGroupStride] = 0u;
+}
+
+// the shading normal from the interpolated varyings a[]: vTBN * nt with vTBN = mat3(T, B, N) and nt the normal map's
+// vector (map_vector(): sampled only when the map is on), or without the map the interpolated normal, normalised
+// (forward_brdf.frag:24) or as it is (gbuffer.frag:29)
+template <bool DEFERRED, class MapVector>
+BB_DEV f3 surface_normal(const float (&a)[kNumVary], int enable_normal_map, MapVector map_vector) {
+  if (enable_normal_map != 0) {
+    const f3 nt = map_vector();
+    return mk3(interp3(nt.x, nt.y, nt.z, a[8], a[11], a[5]), interp3(nt.x, nt.y, nt.z, a[9], a[12], a[6]),
+               interp3(nt.x, nt.y, nt.z, a[10], a[13], a[7]));
+  }
+  return DEFERRED ? mk3(a[5], a[6], a[7]) : normalize3(mk3(a[5], a[6], a[7]));
+}
+BB_DEV float normal_map_axis(float texel) { return fmaf(texel, 2.0f, -1.0f); }  // UNORM channel -> [-1, 1]
+
+// one bilinear tap of one RGBA8 map of the material table: the four texels of the footprint at (u, v), and channel k of them
+struct MapTap {
+  uint32_t t00, t10, t01, t11;
+  float fx, fy;
+};
+BB_DEV MapTap load_map_tap(const TexDesc &td, float u, float v) {
+  const BilinearTaps tp = bilinear_taps(u, v, td.w, td.h);
+  const uint32_t *texels = reinterpret_cast<const uint32_t *>(td.texels);
+  MapTap r;
+  r.t00 = texels[tp.o00]; r.t10 = texels[tp.o10]; r.t01 = texels[tp.o01]; r.t11 = texels[tp.o11];
+  r.fx = tp.fx; r.fy = tp.fy;
+  return r;
+}
+BB_DEV float map_channel(const MapTap &r, int k) { return filter_channel(r.t00, r.t10, r.t01, r.t11, 8 * k, r.fx, r.fy); }
+BB_DEV float sample_map_r(const TexDesc &td, float u, float v) { return map_channel(load_map_tap(td, u, v), 0); }
+BB_DEV f3 sample_map_rgb(const TexDesc &td, float u, float v) {
+  const MapTap r = load_map_tap(td, u, v);
+  return mk3(map_channel(r, 0), map_channel(r, 1), map_channel(r, 2));
+}
+
+// From the filtered surface to the pixel's colour.  Forward: brdf.glsl on the surface.  Deferred: gbuffer.frag:24-32 into
+// four RGBA16F attachments (binary16, round to nearest even), then brdf.frag:12-73 on the pixel's own texel -- fused, the
+// texel only goes to memory when somebody asked to see it, and only then is the height map sampled (height(): the
+// filtered, unrounded value); with gbuffer_view, buffer_visualize.frag:8-12 instead of brdf.frag (recordCommand,
+// src/main.cpp:96-121): the rgb of one attachment.
+template <bool DEFERRED, class Lights, class Height>
+BB_DEV float4 surface_colour(const FrameParams &fp, const ShadeParams &sp, const Lights lights, f3 P, f3 normal, f3 albedo,
+                             float metallic, float roughness, float ao, uint2 *__restrict__ gbuffer, bool valid, int gx, int gy,
+                             Height height) {
+  if (!DEFERRED) return light_surface(sp, lights, P, normal, albedo, metallic, roughness, ao);
+  P = mk3(bb_half_round(P.x), bb_half_round(P.y), bb_half_round(P.z));
+  normal = mk3(bb_half_round(normal.x), bb_half_round(normal.y), bb_half_round(normal.z));
+  albedo = mk3(bb_half_round(albedo.x), bb_half_round(albedo.y), bb_half_round(albedo.z));
+  metallic = bb_half_round(metallic); roughness = bb_half_round(roughness); ao = bb_half_round(ao);
+  if (gbuffer && valid) {
+    const float h = bb_half_round(height());
+    _Float16 g[16] = {(_Float16)P.x, (_Float16)P.y, (_Float16)P.z, (_Float16)1.0f,
+                      (_Float16)normal.x, (_Float16)normal.y, (_Float16)normal.z, (_Float16)0.0f,
+                      (_Float16)albedo.x, (_Float16)albedo.y, (_Float16)albedo.z, (_Float16)0.0f,
+                      (_Float16)metallic, (_Float16)roughness, (_Float16)ao, (_Float16)h};
+    uint4 *dst = reinterpret_cast<uint4 *>(gbuffer) + 2 * ((size_t)gy * (size_t)fp.width + (size_t)gx);
+    uint4 lo, hi;
+    __builtin_memcpy(&lo, g, 16);
+    __builtin_memcpy(&hi, g + 8, 16);
+    dst[0] = lo;
+    dst[1] = hi;
+  }
+  if (fp.gbuffer_view >= 0) {
+    const f3 shown = fp.gbuffer_view == 0 ? P : (fp.gbuffer_view == 1 ? normal : (fp.gbuffer_view == 2 ? albedo : mk3(metallic, roughness, ao)));
+    return make_float4(shown.x, shown.y, shown.z, 1.0f);
+  }
+  return light_surface(sp, lights, P, normal, albedo, metallic, roughness, ao);
+}
+
+// the pixel's colour into the frame, or (PRESENT) through present_pixel into the presented RGBA8 image
+template <bool PRESENT>
+BB_DEV void store_colour(bool valid, float4 color, size_t o, float4 *__restrict__ out, uint32_t *__restrict__ out8,
+                         const SrgbTables *__restrict__ tables, const ShadeParams &sp) {
+  if (!valid) return;
+  if (PRESENT) store_pixel(&out8[o], present_pixel(color.x, color.y, color.z, *tables, sp.tone_enable, sp.exposure, 1));
+  else store_pixel(&out[o], color);
+}
 
 // PRESENT = true (option "present_fused"): the colour goes through present_pixel and is stored as RGBA8 -- the tone-map
 // subpass fused into the producing kernel: 4 bytes written per pixel instead of 16, and no k_present pass (16 B read +
@@ -2099,15 +2250,7 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
     Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups) {
   constexpr int TILE_PIXELS = TILE_W * TILE_H;
   const ConstLights lights_c{(ConstCooked)cooked};
-  // The frame's counter block has done its job (k_geometry filled it, k_raster read it): keep a copy for the host's
-  // statistics / overflow check and clear the block for the next frame of this slot.  Frames of different slots
-  // share nothing, so their kernels may overlap freely.
-  if (!TAIL && blockIdx.x == 0 && threadIdx.x < sizeof(Counters) / 4) {  // (the main launch only)
-    reinterpret_cast<uint32_t *>(ctr_done)[threadIdx.x] = reinterpret_cast<uint32_t *>(ctr)[threadIdx.x];
-    reinterpret_cast<uint32_t *>(ctr)[threadIdx.x] = 0u;
-  }
-  if (!TAIL && blockIdx.x == 0 && item_groups)  // (k_shade_items is done with them)
-    for (uint32_t g = threadIdx.x; g < (uint32_t)kItemGroups; g += kShadeThreads) item_groups[g * kItemGroupStride] = 0u;
+  if (!TAIL) retire_counters(ctr, ctr_done, item_groups);  // (the main launch only)
 #ifdef BB_STAMPS
   unsigned long long st_t[8];
   st_t[0] = __builtin_amdgcn_s_memtime();
@@ -2139,34 +2282,19 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
   if (j >= n_items) return;  // a wave without an item (the kernel has no barrier: waves come and go on their own)
   do {  // (a loop only in the TAIL instantiation)
   if (TAIL) item = items[1u + j];
-  const int chunk = (int)(item & 63u);
-  const int tx = (int)((item >> kItemChunkBits) & ((1u << kItemTxBits) - 1u));
-  int ty, out_tile_row;
-  tile_row(fp, (int)((item & ~kFullTile) >> (kItemChunkBits + kItemTxBits)), ty, out_tile_row);
-  const uint32_t tile = (uint32_t)ty * (uint32_t)fp.tiles_x + (uint32_t)tx;
+  const ItemPlace at = decode_item(fp, item);
   bool valid;
-  unsigned long long frag;
-  if (item & kFullTile) {
-    // a tile one triangle covers completely: no list, no count -- one word through the scalar cache, the pixel is the
-    // lane's own (and the wave is uniform: its primitive record comes through the scalar cache too)
-    typedef const unsigned long long __attribute__((address_space(4))) *ConstFrags;
-    frag = ((ConstFrags)frags)[(size_t)tile * TILE_PIXELS] + ((unsigned long long)((uint32_t)chunk * 64u + (uint32_t)lane) << 32);
-    valid = true;
-  } else {
-    const uint32_t n_frag = frag_count[tile];
-    valid = (uint32_t)chunk * 64u + (uint32_t)lane < n_frag;
-    frag = frags[(size_t)tile * TILE_PIXELS + (uint32_t)chunk * 64u + (uint32_t)lane];
-  }
+  const unsigned long long frag = fetch_fragment<TILE_PIXELS, true>(item, at, lane, frags, frag_count, valid);
   BB_KSTAMP(1);  // item word, count and fragment arrived
   const uint32_t ref = (uint32_t)frag;
   uint32_t prim = BB_ABLATE(16u) ? 0u : (ref >> 3);
   if (BB_ABLATE(1024u)) prim = (uint32_t)__builtin_amdgcn_readfirstlane((int)prim);  // the record through the scalar cache
   int x, y;
   tile_pixel<TILE_W>((int)(frag >> 32) & (TILE_PIXELS - 1), x, y);
-  const int gx = tx * TILE_W + x, gy = ty * TILE_H + y;
+  const int gx = at.tx * TILE_W + x, gy = at.ty * TILE_H + y;
   // the pixel's index in the output (32 bits: a frame has at most 2^30 pixels) -- formed here, so that ONE register, not the
   // pixel's coordinates, lives through the two load groups below (the kernel runs at the 64 registers of eight waves per SIMD)
-  uint32_t opix = (uint32_t)(out_tile_row * TILE_H + y) * (uint32_t)fp.width + (uint32_t)gx;
+  uint32_t opix = (uint32_t)(at.out_tile_row * TILE_H + y) * (uint32_t)fp.width + (uint32_t)gx;
   asm volatile("" : "+v"(opix));
   const size_t o = (size_t)opix;
 
@@ -2188,24 +2316,7 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
   float a[kNumVary];
   uint32_t packed_dims, material;
   const uint8_t *packed_texels;
-  float b0, b1, b2;  // perspective-correct barycentrics with respect to the (unclipped) primitive
-  // perspective-correct barycentrics from the screen-space planes of the (sub-)triangle
-  auto barycentrics = [&](const PlaneHead &h, bool clipped, const float (&cb)[3][3]) {
-    const int Xc = gx * 256 + 128, Yc = gy * 256 + 128;
-    const float dxp = (float)(Xc - h.X0), dyp = (float)(Yc - h.Y0);
-    const float l1 = fmaf(h.l1dx, dxp, h.l1dy * dyp);
-    const float l2 = fmaf(h.l2dx, dxp, h.l2dy * dyp);
-    const float l0 = (1.0f - l1) - l2;
-    const float u0 = l0 * h.rw0, u1 = l1 * h.rw1, u2 = l2 * h.rw2;
-    const float r = bb_rcp((u0 + u1) + u2);
-    b0 = u0 * r; b1 = u1 * r; b2 = u2 * r;
-    if (clipped) {  // barycentrics with respect to the unclipped primitive
-      const float c0 = fmaf(b2, cb[2][0], fmaf(b1, cb[1][0], b0 * cb[0][0]));
-      const float c1 = fmaf(b2, cb[2][1], fmaf(b1, cb[1][1], b0 * cb[0][1]));
-      const float c2 = fmaf(b2, cb[2][2], fmaf(b1, cb[1][2], b0 * cb[0][2]));
-      b0 = c0; b1 = c1; b2 = c2;
-    }
-  };
+  float b0, b1, b2;  // perspective-correct barycentrics with respect to the (unclipped) primitive: plane_bary
   // texels of the packed material (one set of taps, four 12-byte loads of 9-byte records) -- global loads, issued in group B
   BilinearTaps tp = {};
   uint32_t t00[3] = {}, t10[3] = {}, t01[3] = {}, t11[3] = {};
@@ -2256,10 +2367,8 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
       uint32_t clip_base = rp->clip_base;
       asm volatile("" :: "s"(h.X0), "s"(h.Y0), "s"(h.l1dx), "s"(h.l1dy), "s"(h.l2dx), "s"(h.l2dy), "s"(h.rw0), "s"(h.rw1), "s"(h.rw2), "s"(uv[0][0]), "s"(uv[0][1]), "s"(uv[1][0]), "s"(uv[1][1]), "s"(uv[2][0]), "s"(uv[2][1]), "s"(packed_dims), "s"(material), "s"(packed_bits), "s"(clip_base), "s"(cb[0][0]), "s"(cb[0][1]), "s"(cb[0][2]), "s"(cb[1][0]), "s"(cb[1][1]), "s"(cb[1][2]), "s"(cb[2][0]), "s"(cb[2][1]), "s"(cb[2][2]) : "memory");
       packed_texels = (const uint8_t *)(uintptr_t)packed_bits;
-      if (!clipped && clip_base != kNotClipped) {
-        // a clipped primitive whose slot k_raster could not put into the fragment word (more than 32 clipped sub-triangles
-        // on one tile): found through the record, one round trip later
-        const ConstClip cq = (ConstClip)clip_arena + (clip_base + (ref_u & 7u));
+      if (late_clip_slot(clipped, clip_base)) {
+        const ConstClip cq = (ConstClip)clip_arena + record_clip_slot(clip_base, ref_u);
         h.X0 = cq->h.X0; h.Y0 = cq->h.Y0; h.l1dx = cq->h.l1dx; h.l1dy = cq->h.l1dy; h.l2dx = cq->h.l2dx; h.l2dy = cq->h.l2dy;
         h.rw0 = cq->h.rw0; h.rw1 = cq->h.rw1; h.rw2 = cq->h.rw2;
 #pragma unroll
@@ -2268,9 +2377,9 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
           for (int k = 0; k < 3; ++k) cb[jj][k] = cq->bary[jj][k];
         clipped = true;
       }
-      barycentrics(h, clipped, cb);
-      a[0] = fmaf(b2, uv[2][0], fmaf(b1, uv[1][0], b0 * uv[0][0]));
-      a[1] = fmaf(b2, uv[2][1], fmaf(b1, uv[1][1], b0 * uv[0][1]));
+      plane_bary(h, clipped, cb, gx, gy, b0, b1, b2);
+      a[0] = interp3(b0, b1, b2, uv[0][0], uv[1][0], uv[2][0]);
+      a[1] = interp3(b0, b1, b2, uv[0][1], uv[1][1], uv[2][1]);
       BB_KSTAMP(2);  // head (+ clip slot) arrived, barycentrics and uv done
       // group B: the texel taps first (vector loads, the long pole), the body of the record behind them (scalar loads)
       issue_taps((const void *)(const ShadeRec *)(uintptr_t)rp);
@@ -2283,7 +2392,7 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
       for (int q = 0; q < kNumBodyVary; q += 4)
         asm volatile("" :: "s"(body[q][0]), "s"(body[q][1]), "s"(body[q][2]), "s"(body[q + 1][0]), "s"(body[q + 1][1]), "s"(body[q + 1][2]), "s"(body[q + 2][0]), "s"(body[q + 2][1]), "s"(body[q + 2][2]), "s"(body[q + 3][0]), "s"(body[q + 3][1]), "s"(body[q + 3][2]) : "memory");
 #pragma unroll
-      for (int jj = 0; jj < kNumBodyVary; ++jj) a[2 + jj] = fmaf(b2, body[jj][2], fmaf(b1, body[jj][1], b0 * body[jj][0]));
+      for (int jj = 0; jj < kNumBodyVary; ++jj) a[2 + jj] = interp3(b0, b1, b2, body[jj][0], body[jj][1], body[jj][2]);
     } else {
       // ---- each lane gathers the record of its own fragment's primitive ----
       const ShadeRec *rp = recs + prim;
@@ -2308,10 +2417,10 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
       }
       asm volatile("" :: "v"(h.X0), "v"(h.Y0), "v"(h.l1dx), "v"(h.l1dy), "v"(h.l2dx), "v"(h.l2dy), "v"(h.rw0), "v"(h.rw1), "v"(h.rw2), "v"(uv[0][0]), "v"(uv[0][1]), "v"(uv[1][0]), "v"(uv[1][1]), "v"(uv[2][0]), "v"(uv[2][1]), "v"(packed_dims), "v"(material), "v"(packed_bits), "v"(clip_base), "v"(cb[0][0]), "v"(cb[0][1]), "v"(cb[0][2]), "v"(cb[1][0]), "v"(cb[1][1]), "v"(cb[1][2]), "v"(cb[2][0]), "v"(cb[2][1]), "v"(cb[2][2]) : "memory");
       packed_texels = (const uint8_t *)(uintptr_t)packed_bits;
-      const bool late = !clipped && clip_base != kNotClipped;  // (see the uniform form)
+      const bool late = late_clip_slot(clipped, clip_base);
       if (__builtin_expect(__ballot(late) != 0ull, 0)) {
         if (late) {
-          const ClipSlot cs = clip_arena[clip_base + (ref & 7u)];
+          const ClipSlot cs = clip_arena[record_clip_slot(clip_base, ref)];
           h = cs.h;
 #pragma unroll
           for (int jj = 0; jj < 3; ++jj)
@@ -2320,9 +2429,9 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
           clipped = true;
         }
       }
-      barycentrics(h, clipped, cb);
-      a[0] = fmaf(b2, uv[2][0], fmaf(b1, uv[1][0], b0 * uv[0][0]));
-      a[1] = fmaf(b2, uv[2][1], fmaf(b1, uv[1][1], b0 * uv[0][1]));
+      plane_bary(h, clipped, cb, gx, gy, b0, b1, b2);
+      a[0] = interp3(b0, b1, b2, uv[0][0], uv[1][0], uv[2][0]);
+      a[1] = interp3(b0, b1, b2, uv[0][1], uv[1][1], uv[2][1]);
       BB_KSTAMP(2);  // head (+ clip slot) arrived, barycentrics and uv done
       // group B: the first 80 bytes of the record's body (varyings 0..5 whole and two thirds of the sixth), the four texel
       // taps behind them, and -- as soon as the first part has arrived and its six varyings are interpolated, their eighteen
@@ -2336,15 +2445,15 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
       issue_taps(rp);
       asm volatile("" :: "v"(p1[0]), "v"(p1[1]), "v"(p1[2]), "v"(p1[3]), "v"(p1[4]), "v"(p1[5]), "v"(p1[6]), "v"(p1[7]), "v"(p1[8]), "v"(p1[9]), "v"(p1[10]), "v"(p1[11]), "v"(p1[12]), "v"(p1[13]), "v"(p1[14]), "v"(p1[15]), "v"(p1[16]), "v"(p1[17]), "v"(p1[18]), "v"(p1[19]) : "memory");
 #pragma unroll
-      for (int jj = 0; jj < 6; ++jj) a[2 + jj] = fmaf(b2, p1[3 * jj + 2], fmaf(b1, p1[3 * jj + 1], b0 * p1[3 * jj]));
+      for (int jj = 0; jj < 6; ++jj) a[2 + jj] = interp3(b0, b1, b2, p1[3 * jj], p1[3 * jj + 1], p1[3 * jj + 2]);
       asm volatile("" :: "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]) : "memory");  // (the second part is asked for HERE, not earlier)
       float p2[16];
 #pragma unroll
       for (int q = 0; q < 16; ++q) p2[q] = bp[20 + q];
       asm volatile("" :: "v"(p2[0]), "v"(p2[1]), "v"(p2[2]), "v"(p2[3]), "v"(p2[4]), "v"(p2[5]), "v"(p2[6]), "v"(p2[7]), "v"(p2[8]), "v"(p2[9]), "v"(p2[10]), "v"(p2[11]), "v"(p2[12]), "v"(p2[13]), "v"(p2[14]), "v"(p2[15]) : "memory");
-      a[8] = fmaf(b2, p2[0], fmaf(b1, p1[19], b0 * p1[18]));
+      a[8] = interp3(b0, b1, b2, p1[18], p1[19], p2[0]);
 #pragma unroll
-      for (int jj = 7; jj < kNumBodyVary; ++jj) a[2 + jj] = fmaf(b2, p2[3 * jj - 18], fmaf(b1, p2[3 * jj - 19], b0 * p2[3 * jj - 20]));
+      for (int jj = 7; jj < kNumBodyVary; ++jj) a[2 + jj] = interp3(b0, b1, b2, p2[3 * jj - 20], p2[3 * jj - 19], p2[3 * jj - 18]);
     }
   }
   // the taps are used from here on: pin them behind the body's fence (they were issued in front of it)
@@ -2362,105 +2471,30 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
     metallic = filter_channel(t00[0], t10[0], t01[0], t11[0], 24, tp.fx, tp.fy);
     roughness = filter_channel(t00[1], t10[1], t01[1], t11[1], 24, tp.fx, tp.fy);
     ao = filter_channel(t00[2], t10[2], t01[2], t11[2], 0, tp.fx, tp.fy);
-    if (sp.enable_normal_map != 0) {
-      const f3 nt = mk3(fmaf(filter_channel(t00[1], t10[1], t01[1], t11[1], 0, tp.fx, tp.fy), 2.0f, -1.0f),
-                        fmaf(filter_channel(t00[1], t10[1], t01[1], t11[1], 8, tp.fx, tp.fy), 2.0f, -1.0f),
-                        fmaf(filter_channel(t00[1], t10[1], t01[1], t11[1], 16, tp.fx, tp.fy), 2.0f, -1.0f));
-      // vTBN * nt, vTBN = mat3(T, B, N)
-      normal.x = fmaf(a[5], nt.z, fmaf(a[11], nt.y, a[8] * nt.x));
-      normal.y = fmaf(a[6], nt.z, fmaf(a[12], nt.y, a[9] * nt.x));
-      normal.z = fmaf(a[7], nt.z, fmaf(a[13], nt.y, a[10] * nt.x));
-    } else {
-      normal = DEFERRED ? mk3(a[5], a[6], a[7]) : normalize3(mk3(a[5], a[6], a[7]));  // gbuffer.frag:29 / forward :24
-    }
+    normal = surface_normal<DEFERRED>(a, sp.enable_normal_map, [&] {
+      return mk3(normal_map_axis(filter_channel(t00[1], t10[1], t01[1], t11[1], 0, tp.fx, tp.fy)),
+                 normal_map_axis(filter_channel(t00[1], t10[1], t01[1], t11[1], 8, tp.fx, tp.fy)),
+                 normal_map_axis(filter_channel(t00[1], t10[1], t01[1], t11[1], 16, tp.fx, tp.fy)));
+    });
   } else {
     // maps of different sizes: one set of taps per map
     const MaterialDesc &md = materials[material];
-    {
-      const TexDesc &td = md.maps[kMapAlbedo];
-      BilinearTaps tp = bilinear_taps(u, v, td.w, td.h);
-      const uint32_t *tx32 = reinterpret_cast<const uint32_t *>(td.texels);
-      uint32_t t00 = tx32[tp.o00], t10 = tx32[tp.o10], t01 = tx32[tp.o01], t11 = tx32[tp.o11];
-      albedo.x = filter_channel(t00, t10, t01, t11, 0, tp.fx, tp.fy);
-      albedo.y = filter_channel(t00, t10, t01, t11, 8, tp.fx, tp.fy);
-      albedo.z = filter_channel(t00, t10, t01, t11, 16, tp.fx, tp.fy);
-    }
-    {
-      const TexDesc &td = md.maps[kMapMetallic];
-      BilinearTaps tp = bilinear_taps(u, v, td.w, td.h);
-      const uint32_t *tx32 = reinterpret_cast<const uint32_t *>(td.texels);
-      metallic = filter_channel(tx32[tp.o00], tx32[tp.o10], tx32[tp.o01], tx32[tp.o11], 0, tp.fx, tp.fy);
-    }
-    {
-      const TexDesc &td = md.maps[kMapRoughness];
-      BilinearTaps tp = bilinear_taps(u, v, td.w, td.h);
-      const uint32_t *tx32 = reinterpret_cast<const uint32_t *>(td.texels);
-      roughness = filter_channel(tx32[tp.o00], tx32[tp.o10], tx32[tp.o01], tx32[tp.o11], 0, tp.fx, tp.fy);
-    }
-    {
-      const TexDesc &td = md.maps[kMapAO];
-      BilinearTaps tp = bilinear_taps(u, v, td.w, td.h);
-      const uint32_t *tx32 = reinterpret_cast<const uint32_t *>(td.texels);
-      ao = filter_channel(tx32[tp.o00], tx32[tp.o10], tx32[tp.o01], tx32[tp.o11], 0, tp.fx, tp.fy);
-    }
-    if (sp.enable_normal_map != 0) {
-      const TexDesc &td = md.maps[kMapNormal];
-      BilinearTaps tp = bilinear_taps(u, v, td.w, td.h);
-      const uint32_t *tx32 = reinterpret_cast<const uint32_t *>(td.texels);
-      uint32_t t00 = tx32[tp.o00], t10 = tx32[tp.o10], t01 = tx32[tp.o01], t11 = tx32[tp.o11];
-      f3 nt = mk3(fmaf(filter_channel(t00, t10, t01, t11, 0, tp.fx, tp.fy), 2.0f, -1.0f),
-                  fmaf(filter_channel(t00, t10, t01, t11, 8, tp.fx, tp.fy), 2.0f, -1.0f),
-                  fmaf(filter_channel(t00, t10, t01, t11, 16, tp.fx, tp.fy), 2.0f, -1.0f));
-      normal.x = fmaf(a[5], nt.z, fmaf(a[11], nt.y, a[8] * nt.x));
-      normal.y = fmaf(a[6], nt.z, fmaf(a[12], nt.y, a[9] * nt.x));
-      normal.z = fmaf(a[7], nt.z, fmaf(a[13], nt.y, a[10] * nt.x));
-    } else {
-      normal = DEFERRED ? mk3(a[5], a[6], a[7]) : normalize3(mk3(a[5], a[6], a[7]));
-    }
+    albedo = sample_map_rgb(md.maps[kMapAlbedo], u, v);
+    metallic = sample_map_r(md.maps[kMapMetallic], u, v);
+    roughness = sample_map_r(md.maps[kMapRoughness], u, v);
+    ao = sample_map_r(md.maps[kMapAO], u, v);
+    normal = surface_normal<DEFERRED>(a, sp.enable_normal_map, [&] {
+      const f3 t = sample_map_rgb(md.maps[kMapNormal], u, v);
+      return mk3(normal_map_axis(t.x), normal_map_axis(t.y), normal_map_axis(t.z));
+    });
   }
 
   BB_KSTAMP(3);  // varyings, taps arrived, filtered
-  float4 color;
-  if (DEFERRED) {
-    // gbuffer.frag:24-32 into four RGBA16F attachments (binary16, round to nearest even), then brdf.frag:12-73 on
-    // the pixel's own texel: fused, the texel only goes to memory when somebody asked to see it
-    f3 P = mk3(bb_half_round(a[2]), bb_half_round(a[3]), bb_half_round(a[4]));
-    normal = mk3(bb_half_round(normal.x), bb_half_round(normal.y), bb_half_round(normal.z));
-    albedo = mk3(bb_half_round(albedo.x), bb_half_round(albedo.y), bb_half_round(albedo.z));
-    metallic = bb_half_round(metallic); roughness = bb_half_round(roughness); ao = bb_half_round(ao);
-    if (gbuffer && valid) {
-      const MaterialDesc &md = materials[material];
-      const TexDesc &td = md.maps[kMapHeight];
-      BilinearTaps tp = bilinear_taps(u, v, td.w, td.h);
-      const uint32_t *tx32 = reinterpret_cast<const uint32_t *>(td.texels);
-      const float height = bb_half_round(filter_channel(tx32[tp.o00], tx32[tp.o10], tx32[tp.o01], tx32[tp.o11], 0, tp.fx, tp.fy));
-      _Float16 g[16] = {(_Float16)P.x, (_Float16)P.y, (_Float16)P.z, (_Float16)1.0f,
-                        (_Float16)normal.x, (_Float16)normal.y, (_Float16)normal.z, (_Float16)0.0f,
-                        (_Float16)albedo.x, (_Float16)albedo.y, (_Float16)albedo.z, (_Float16)0.0f,
-                        (_Float16)metallic, (_Float16)roughness, (_Float16)ao, (_Float16)height};
-      uint4 *dst = reinterpret_cast<uint4 *>(gbuffer) + 2 * ((size_t)gy * (size_t)fp.width + (size_t)gx);
-      uint4 lo, hi;
-      __builtin_memcpy(&lo, g, 16);
-      __builtin_memcpy(&hi, g + 8, 16);
-      dst[0] = lo;
-      dst[1] = hi;
-    }
-    if (fp.gbuffer_view >= 0) {
-      // buffer_visualize.frag:8-12 instead of brdf.frag (recordCommand, src/main.cpp:96-121): the rgb of one attachment
-      const f3 shown = fp.gbuffer_view == 0 ? P : (fp.gbuffer_view == 1 ? normal : (fp.gbuffer_view == 2 ? albedo : mk3(metallic, roughness, ao)));
-      color = make_float4(shown.x, shown.y, shown.z, 1.0f);
-    } else {
-      color = light_surface(sp, lights_c, P, normal, albedo, metallic, roughness, ao);
-    }
-  } else {
-    color = light_surface(sp, lights_c, mk3(a[2], a[3], a[4]), normal, albedo, metallic, roughness, ao);
-  }
+  float4 color = surface_colour<DEFERRED>(fp, sp, lights_c, mk3(a[2], a[3], a[4]), normal, albedo, metallic, roughness, ao, gbuffer, valid,
+                                          gx, gy, [&] { return sample_map_r(materials[material].maps[kMapHeight], u, v); });
   BB_KSTAMP(4);  // light loop done
   if (BB_ABLATE(2u)) color = make_float4(1.f, 1.f, 1.f, 1.f);
-  if (valid) {
-    if (PRESENT) store_pixel(&out8[o], present_pixel(color.x, color.y, color.z, *tables, sp.tone_enable, sp.exposure, 1));
-    else store_pixel(&out[o], color);
-  }
+  store_colour<PRESENT>(valid, color, o, out, out8, tables, sp);
 #ifdef BB_STAMPS
   {
     BB_KSTAMP(5);
@@ -2506,29 +2540,15 @@ __constant__ float kAnisoRcp[kMaxAnisotropy + 2] = {
     1.0f / 9.0f, 1.0f / 10.0f, 1.0f / 11.0f, 1.0f / 12.0f, 1.0f / 13.0f, 1.0f / 14.0f, 1.0f / 15.0f, 1.0f / 16.0f, 1.0f / 17.0f};
 constexpr int kSurfaceFloats = 32;  // one record of bbr_read_surface
 
-// the fragment's vUV at the centre of pixel (px, py), from the planes of its own (sub-)triangle: the statements of
-// k_shade's `barycentrics` and its fmaf chain over the three vertex uvs
+// the fragment's vUV at the centre of pixel (px, py), from the planes of its own (sub-)triangle
 struct PlaneUV {
   float b0, b1, b2, u, v;
 };
 BB_DEV PlaneUV plane_uv(const PlaneHead &h, bool clipped, const float (&cb)[3][3], const float (&uv)[3][2], int px, int py) {
-  const int Xc = px * 256 + 128, Yc = py * 256 + 128;
-  const float dxp = (float)(Xc - h.X0), dyp = (float)(Yc - h.Y0);
-  const float l1 = fmaf(h.l1dx, dxp, h.l1dy * dyp);
-  const float l2 = fmaf(h.l2dx, dxp, h.l2dy * dyp);
-  const float l0 = (1.0f - l1) - l2;
-  const float u0 = l0 * h.rw0, u1 = l1 * h.rw1, u2 = l2 * h.rw2;
-  const float r = bb_rcp((u0 + u1) + u2);
   PlaneUV o;
-  o.b0 = u0 * r; o.b1 = u1 * r; o.b2 = u2 * r;
-  if (clipped) {  // barycentrics with respect to the unclipped primitive
-    const float c0 = fmaf(o.b2, cb[2][0], fmaf(o.b1, cb[1][0], o.b0 * cb[0][0]));
-    const float c1 = fmaf(o.b2, cb[2][1], fmaf(o.b1, cb[1][1], o.b0 * cb[0][1]));
-    const float c2 = fmaf(o.b2, cb[2][2], fmaf(o.b1, cb[1][2], o.b0 * cb[0][2]));
-    o.b0 = c0; o.b1 = c1; o.b2 = c2;
-  }
-  o.u = fmaf(o.b2, uv[2][0], fmaf(o.b1, uv[1][0], o.b0 * uv[0][0]));
-  o.v = fmaf(o.b2, uv[2][1], fmaf(o.b1, uv[1][1], o.b0 * uv[0][1]));
+  plane_bary(h, clipped, cb, px, py, o.b0, o.b1, o.b2);
+  o.u = interp3(o.b0, o.b1, o.b2, uv[0][0], uv[1][0], uv[2][0]);
+  o.v = interp3(o.b0, o.b1, o.b2, uv[0][1], uv[1][1], uv[2][1]);
   return o;
 }
 
@@ -2595,22 +2615,12 @@ struct PackedFetch {  // the packed material: 9-byte records, block-linear (issu
 template <int CHANNELS>
 struct MapFetch {  // one RGBA8 map of the material table, its first CHANNELS channels
   static constexpr int kChannels = CHANNELS;
-  const uint32_t *texels;
-  int w, h;
-  struct Raw {
-    uint32_t t00, t10, t01, t11;
-    float fx, fy;
-  };
-  BB_DEV Raw load(float u, float v) const {
-    const BilinearTaps tp = bilinear_taps(u, v, w, h);
-    Raw r;
-    r.t00 = texels[tp.o00]; r.t10 = texels[tp.o10]; r.t01 = texels[tp.o01]; r.t11 = texels[tp.o11];
-    r.fx = tp.fx; r.fy = tp.fy;
-    return r;
-  }
+  TexDesc td;
+  typedef MapTap Raw;
+  BB_DEV Raw load(float u, float v) const { return load_map_tap(td, u, v); }
   BB_DEV static void add(const Raw &r, float (&acc)[kChannels]) {
 #pragma unroll
-    for (int k = 0; k < kChannels; ++k) acc[k] = acc[k] + filter_channel(r.t00, r.t10, r.t01, r.t11, 8 * k, r.fx, r.fy);
+    for (int k = 0; k < kChannels; ++k) acc[k] = acc[k] + map_channel(r, k);
   }
 };
 
@@ -2649,38 +2659,20 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
     float *__restrict__ dump) {
   constexpr int TILE_PIXELS = TILE_W * TILE_H;
   const ConstLights lights_c{(ConstCooked)cooked};
-  // the frame's counter block and chunk totals: as the main launch of k_shade
-  if (blockIdx.x == 0 && threadIdx.x < sizeof(Counters) / 4) {
-    reinterpret_cast<uint32_t *>(ctr_done)[threadIdx.x] = reinterpret_cast<uint32_t *>(ctr)[threadIdx.x];
-    reinterpret_cast<uint32_t *>(ctr)[threadIdx.x] = 0u;
-  }
-  if (blockIdx.x == 0 && item_groups)
-    for (uint32_t g = threadIdx.x; g < (uint32_t)kItemGroups; g += kShadeThreads) item_groups[g * kItemGroupStride] = 0u;
+  retire_counters(ctr, ctr_done, item_groups);
   const int lane = (int)(threadIdx.x & 63u);
   const uint32_t n_items = *item_count;
   for (uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (uint32_t)kShadeWaves + (threadIdx.x >> 6)));
        j < n_items; j += gridDim.x * (uint32_t)kShadeWaves) {
     const uint32_t item = items[1u + j];
-    const int chunk = (int)(item & 63u);
-    const int tx = (int)((item >> kItemChunkBits) & ((1u << kItemTxBits) - 1u));
-    int ty, out_tile_row;
-    tile_row(fp, (int)((item & ~kFullTile) >> (kItemChunkBits + kItemTxBits)), ty, out_tile_row);
-    const uint32_t tile = (uint32_t)ty * (uint32_t)fp.tiles_x + (uint32_t)tx;
+    const ItemPlace at = decode_item(fp, item);
     bool valid;
-    unsigned long long frag;
-    if (item & kFullTile) {  // a tile one triangle covers completely: one word, the pixel is the lane's own
-      frag = frags[(size_t)tile * TILE_PIXELS] + ((unsigned long long)((uint32_t)chunk * 64u + (uint32_t)lane) << 32);
-      valid = true;
-    } else {
-      const uint32_t n_frag = frag_count[tile];
-      valid = (uint32_t)chunk * 64u + (uint32_t)lane < n_frag;
-      frag = frags[(size_t)tile * TILE_PIXELS + (uint32_t)chunk * 64u + (uint32_t)lane];
-    }
+    const unsigned long long frag = fetch_fragment<TILE_PIXELS, false>(item, at, lane, frags, frag_count, valid);
     const uint32_t ref = (uint32_t)frag;
     int x, y;
     tile_pixel<TILE_W>((int)(frag >> 32) & (TILE_PIXELS - 1), x, y);
-    const int gx = tx * TILE_W + x, gy = ty * TILE_H + y;
-    const size_t o = (size_t)((uint32_t)(out_tile_row * TILE_H + y) * (uint32_t)fp.width + (uint32_t)gx);
+    const int gx = at.tx * TILE_W + x, gy = at.ty * TILE_H + y;
+    const size_t o = (size_t)((uint32_t)(at.out_tile_row * TILE_H + y) * (uint32_t)fp.width + (uint32_t)gx);
 
     // the head of the primitive record and, for a clipped fragment, its sub-triangle's clip slot
     const ShadeRec *rp = recs + (ref >> 3);
@@ -2693,8 +2685,8 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
     for (int k = 0; k < 3; ++k) { uv[k][0] = rp->uv[k][0]; uv[k][1] = rp->uv[k][1]; }
     const uint32_t packed_dims = rp->packed_dims, material = rp->material, clip_base = rp->clip_base;
     const GlobalBytes packed_texels = (GlobalBytes)rp->packed;
-    if (!clipped && clip_base != kNotClipped) {  // a slot k_raster could not put into the fragment word: through the record
-      cp = clip_arena + (clip_base + (ref & 7u));
+    if (late_clip_slot(clipped, clip_base)) {
+      cp = clip_arena + record_clip_slot(clip_base, ref);
       h = cp->h;
       clipped = true;
     }
@@ -2714,10 +2706,11 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
     float a[kNumVary];
     a[0] = f.u; a[1] = f.v;
 #pragma unroll
-    for (int jj = 0; jj < kNumBodyVary; ++jj) a[2 + jj] = fmaf(b2, rp->vary[jj][2], fmaf(b1, rp->vary[jj][1], b0 * rp->vary[jj][0]));
+    for (int jj = 0; jj < kNumBodyVary; ++jj) a[2 + jj] = interp3(b0, b1, b2, rp->vary[jj][0], rp->vary[jj][1], rp->vary[jj][2]);
 
     // texture filtering, forward_brdf.frag:16-22 / gbuffer.frag
-    f3 albedo, normal, nt = mk3(0.f, 0.f, 0.f);
+    const bool normal_map = sp.enable_normal_map != 0;
+    f3 albedo, nt = mk3(0.f, 0.f, 0.f);
     float metallic, roughness, ao, height = 0.0f;
     uint32_t taps[kMapCount] = {};  // (DUMP: the tap count used for each map, 0 = not sampled)
     const MaterialDesc &md = materials[material];
@@ -2728,14 +2721,14 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
       aniso_sample(fetch, f, t, s);
       albedo = mk3(s[0], s[1], s[2]);
       metallic = s[3]; roughness = s[4]; ao = s[5];
-      if (sp.enable_normal_map != 0) nt = mk3(fmaf(s[6], 2.0f, -1.0f), fmaf(s[7], 2.0f, -1.0f), fmaf(s[8], 2.0f, -1.0f));
+      if (normal_map) nt = mk3(normal_map_axis(s[6]), normal_map_axis(s[7]), normal_map_axis(s[8]));
       taps[kMapAlbedo] = taps[kMapMetallic] = taps[kMapRoughness] = taps[kMapAO] = (uint32_t)t.n;
-      if (sp.enable_normal_map != 0) taps[kMapNormal] = (uint32_t)t.n;
+      if (normal_map) taps[kMapNormal] = (uint32_t)t.n;
     } else {
       // maps of different sizes: a tap count and a tap loop per map
       auto one = [&](int map, auto channels, float *value) {
         const TexDesc &td = md.maps[map];
-        const MapFetch<decltype(channels)::value> fetch{reinterpret_cast<const uint32_t *>(td.texels), td.w, td.h};
+        const MapFetch<decltype(channels)::value> fetch{td};
         const AnisoTaps t = aniso_taps(f, td.w, td.h, max_aniso);
         float s[decltype(channels)::value];
         aniso_sample(fetch, f, t, s);
@@ -2749,21 +2742,15 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
       one(kMapMetallic, std::integral_constant<int, 1>{}, &metallic);
       one(kMapRoughness, std::integral_constant<int, 1>{}, &roughness);
       one(kMapAO, std::integral_constant<int, 1>{}, &ao);
-      if (sp.enable_normal_map != 0) {
+      if (normal_map) {
         one(kMapNormal, std::integral_constant<int, 3>{}, s3);
-        nt = mk3(fmaf(s3[0], 2.0f, -1.0f), fmaf(s3[1], 2.0f, -1.0f), fmaf(s3[2], 2.0f, -1.0f));
+        nt = mk3(normal_map_axis(s3[0]), normal_map_axis(s3[1]), normal_map_axis(s3[2]));
       }
     }
-    if (sp.enable_normal_map != 0) {  // vTBN * nt, vTBN = mat3(T, B, N)
-      normal.x = fmaf(a[5], nt.z, fmaf(a[11], nt.y, a[8] * nt.x));
-      normal.y = fmaf(a[6], nt.z, fmaf(a[12], nt.y, a[9] * nt.x));
-      normal.z = fmaf(a[7], nt.z, fmaf(a[13], nt.y, a[10] * nt.x));
-    } else {
-      normal = DEFERRED ? mk3(a[5], a[6], a[7]) : normalize3(mk3(a[5], a[6], a[7]));  // gbuffer.frag:29 / forward :24
-    }
+    const f3 normal = surface_normal<DEFERRED>(a, sp.enable_normal_map, [&] { return nt; });
     if (DEFERRED && (DUMP || gbuffer) && valid) {  // gbuffer.frag's sixth fetch: only when somebody asked to see the texel
       const TexDesc &td = md.maps[kMapHeight];
-      const MapFetch<1> fetch{reinterpret_cast<const uint32_t *>(td.texels), td.w, td.h};
+      const MapFetch<1> fetch{td};
       const AnisoTaps t = aniso_taps(f, td.w, td.h, max_aniso);
       float s[1];
       aniso_sample(fetch, f, t, s);
@@ -2780,39 +2767,9 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
       for (int k = 0; k < kSurfaceFloats; ++k) d[k] = rec[k];
     }
 
-    float4 color;
-    if (DEFERRED) {
-      // gbuffer.frag:24-32 into four RGBA16F attachments, then brdf.frag:12-73 on the pixel's own texel (k_shade)
-      const f3 P = mk3(bb_half_round(a[2]), bb_half_round(a[3]), bb_half_round(a[4]));
-      normal = mk3(bb_half_round(normal.x), bb_half_round(normal.y), bb_half_round(normal.z));
-      albedo = mk3(bb_half_round(albedo.x), bb_half_round(albedo.y), bb_half_round(albedo.z));
-      metallic = bb_half_round(metallic); roughness = bb_half_round(roughness); ao = bb_half_round(ao);
-      if (gbuffer && valid) {
-        height = bb_half_round(height);
-        _Float16 g[16] = {(_Float16)P.x, (_Float16)P.y, (_Float16)P.z, (_Float16)1.0f,
-                          (_Float16)normal.x, (_Float16)normal.y, (_Float16)normal.z, (_Float16)0.0f,
-                          (_Float16)albedo.x, (_Float16)albedo.y, (_Float16)albedo.z, (_Float16)0.0f,
-                          (_Float16)metallic, (_Float16)roughness, (_Float16)ao, (_Float16)height};
-        uint4 *dst = reinterpret_cast<uint4 *>(gbuffer) + 2 * ((size_t)gy * (size_t)fp.width + (size_t)gx);
-        uint4 lo, hi;
-        __builtin_memcpy(&lo, g, 16);
-        __builtin_memcpy(&hi, g + 8, 16);
-        dst[0] = lo;
-        dst[1] = hi;
-      }
-      if (fp.gbuffer_view >= 0) {  // buffer_visualize.frag:8-12 instead of brdf.frag
-        const f3 shown = fp.gbuffer_view == 0 ? P : (fp.gbuffer_view == 1 ? normal : (fp.gbuffer_view == 2 ? albedo : mk3(metallic, roughness, ao)));
-        color = make_float4(shown.x, shown.y, shown.z, 1.0f);
-      } else {
-        color = light_surface(sp, lights_c, P, normal, albedo, metallic, roughness, ao);
-      }
-    } else {
-      color = light_surface(sp, lights_c, mk3(a[2], a[3], a[4]), normal, albedo, metallic, roughness, ao);
-    }
-    if (valid) {
-      if (PRESENT) store_pixel(&out8[o], present_pixel(color.x, color.y, color.z, *tables, sp.tone_enable, sp.exposure, 1));
-      else store_pixel(&out[o], color);
-    }
+    const float4 color = surface_colour<DEFERRED>(fp, sp, lights_c, mk3(a[2], a[3], a[4]), normal, albedo, metallic, roughness, ao, gbuffer,
+                                                  valid, gx, gy, [&] { return height; });
+    store_colour<PRESENT>(valid, color, o, out, out8, tables, sp);
   }
 }
 
@@ -3023,30 +2980,25 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_overlay(
   tile_pixel<TILE_W>((int)(frag >> 32) & (TILE_PIXELS - 1), x, y);
   const int gx = tx * TILE_W + x, gy = ty * TILE_H + y;
   const ShadeRec pa = recs[prim];
-  // perspective-correct barycentrics: the same statements as k_shade
+  // the overlay pass writes no slot into its fragment words: a clipped primitive's slot is always found through the record
   const bool clipped = pa.clip_base != kNotClipped;
-  const ClipSlot *cs = clipped ? &clip_arena[pa.clip_base + (ref & 7u)] : nullptr;
+  const ClipSlot *cs = clipped ? &clip_arena[record_clip_slot(pa.clip_base, ref)] : nullptr;
   const PlaneHead h = clipped ? cs->h : pa.h;
-  const int Xc = gx * 256 + 128, Yc = gy * 256 + 128;
-  const float dxp = (float)(Xc - h.X0), dyp = (float)(Yc - h.Y0);
-  const float l1 = fmaf(h.l1dx, dxp, h.l1dy * dyp);
-  const float l2 = fmaf(h.l2dx, dxp, h.l2dy * dyp);
-  const float l0 = (1.0f - l1) - l2;
-  const float u0 = l0 * h.rw0, u1 = l1 * h.rw1, u2 = l2 * h.rw2;
-  const float r = bb_rcp((u0 + u1) + u2);
-  float b0 = u0 * r, b1 = u1 * r, b2 = u2 * r;
+  float cb[3][3] = {};
   if (clipped) {
-    const float c0 = fmaf(b2, cs->bary[2][0], fmaf(b1, cs->bary[1][0], b0 * cs->bary[0][0]));
-    const float c1 = fmaf(b2, cs->bary[2][1], fmaf(b1, cs->bary[1][1], b0 * cs->bary[0][1]));
-    const float c2 = fmaf(b2, cs->bary[2][2], fmaf(b1, cs->bary[1][2], b0 * cs->bary[0][2]));
-    b0 = c0; b1 = c1; b2 = c2;
+#pragma unroll
+    for (int jj = 0; jj < 3; ++jj)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) cb[jj][k] = cs->bary[jj][k];
   }
+  float b0, b1, b2;
+  plane_bary(h, clipped, cb, gx, gy, b0, b1, b2);
   // varyings 0..5 of the overlay programs (k_geometry<..., OVERLAY>): 0, 1 sit in the record's head, 2..5 in its body
   float a[6];
 #pragma unroll
-  for (int k = 0; k < 2; ++k) a[k] = fmaf(b2, pa.uv[2][k], fmaf(b1, pa.uv[1][k], b0 * pa.uv[0][k]));
+  for (int k = 0; k < 2; ++k) a[k] = interp3(b0, b1, b2, pa.uv[0][k], pa.uv[1][k], pa.uv[2][k]);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) a[2 + k] = fmaf(b2, pa.vary[k][2], fmaf(b1, pa.vary[k][1], b0 * pa.vary[k][0]));
+  for (int k = 0; k < 4; ++k) a[2 + k] = interp3(b0, b1, b2, pa.vary[k][0], pa.vary[k][1], pa.vary[k][2]);
   float col[3] = {a[0], a[1], a[2]};  // light.frag: outColor = vec4(vColor, 1)
   if (pa.material == 2u) {             // gizmo.frag:10-17: L = -(0,0,1); diff = max(dot(L, normalize(vNormal)), 0)
     const f3 N = normalize3(mk3(a[3], a[4], a[5]));

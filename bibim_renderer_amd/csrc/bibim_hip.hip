@@ -494,7 +494,7 @@ int upload_material_table(bbr_context *c) {
 }
 
 template <int TW, int TH>
-void launch_frame(bbr_context *c, FrameSlot &s, const FrameSlot *prev, const FrameParams &fp_in, const Mat4 &pv,
+void launch_frame(bbr_context *c, FrameSlot &s, const FrameParams &fp_in, const Mat4 &pv,
                   const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DrawDesc *d_draws, uint32_t n_draws, float4 *out,
                   uint32_t *d_item_head) {
   const int slot_index = (int)(&s - c->slots);
@@ -540,7 +540,6 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameSlot *prev, const Fra
   // same buffer (single external output), raster has to wait for it; geometry above still overlapped
   // (every frame still in flight, not just the previous one: with one stream per slot, or while the layout is being
   //  switched, "after the previous frame" no longer implies "after the one before")
-  (void)prev;
   for (const FrameSlot &o : c->slots)
     if (&o != &s && o.in_flight && o.out_used == out && o.stream_used != sr) (void)hipStreamWaitEvent(sr, o.ev_shade_done, 0);
   // option "present_fused": k_raster / k_shade write presented pixels into the slot's RGBA8 image
@@ -763,11 +762,10 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   sp.exposure = c->frame_u.exposure;
   sp.num_lights = n_lights;
   float4 *out = c->ext_out ? reinterpret_cast<float4 *>(c->ext_out) : s.d_frame.ptr;
-  const FrameSlot *prev = (c->last_slot >= 0 && c->last_slot != slot_index) ? &c->slots[c->last_slot] : nullptr;
 
   HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, s.h_staging, total, hipMemcpyHostToDevice, sg));
-  if (c->tile_mode == 0) launch_frame<64, 64>(c, s, prev, fp, pv, view, sp, d_lights, d_draws, c->n_live_draws, out, d_item_head);
-  else launch_frame<32, 32>(c, s, prev, fp, pv, view, sp, d_lights, d_draws, c->n_live_draws, out, d_item_head);
+  if (c->tile_mode == 0) launch_frame<64, 64>(c, s, fp, pv, view, sp, d_lights, d_draws, c->n_live_draws, out, d_item_head);
+  else launch_frame<32, 32>(c, s, fp, pv, view, sp, d_lights, d_draws, c->n_live_draws, out, d_item_head);
   HIP_TRY(c, hipGetLastError());
   s.in_flight = true;
   s.fused = c->present_fused;

@@ -26,6 +26,7 @@ GEOMETRY_VGPR_SHIPPED_MAX = 64  # the step of 8 waves per SIMD, the footprint of
 RASTER_VGPR_MAX = 64
 # plain k_shade<32, 32, DEFERRED, PRESENT, TAIL = false, MIXED = false>
 SHADE_VGPR_MAX = {(0, 0): 58, (0, 1): 58, (1, 0): 60, (1, 1): 60}
+ANISO_VGPR_MAX = 128            # the allocation step of the four waves per SIMD k_shade_aniso runs at
 
 
 def _makefile_command():
@@ -97,3 +98,11 @@ def test_k_shade_did_not_grow(kernels, deferred, present):
     print(f"k_shade<32,32,{deferred},{present},false,false>: {k}")
     assert k["private_segment_fixed_size"] == 0
     assert k["vgpr_count"] <= SHADE_VGPR_MAX[(deferred, present)]
+
+
+@pytest.mark.parametrize("deferred,present", sorted(SHADE_VGPR_MAX))
+def test_k_shade_aniso_stays_at_four_waves(kernels, deferred, present):
+    k = _one(kernels, f"_ZN3bbr13k_shade_anisoILi32ELi32ELb{deferred}ELb{present}ELb0EEE")
+    print(f"k_shade_aniso<32,32,{deferred},{present},false>: {k}")
+    assert k["private_segment_fixed_size"] == 0
+    assert k["vgpr_count"] <= ANISO_VGPR_MAX
