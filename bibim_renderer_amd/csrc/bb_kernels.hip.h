@@ -1327,15 +1327,15 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
 
   __builtin_amdgcn_s_setprio(3);  // (as k_geometry: a latency-bound wave's instruction goes out when it is ready)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // {overflow bits, bin_need, -, every-tile entries asked for, clip slots asked for} of this frame straight into pinned host
-  // memory (final since k_geometry ended): the host looks at them when it reuses the frame's slot -- a few stores instead
-  // of a copy kernel on the stream.  (Word 2 is the frame's shade item count, stored by k_shade_items.)
+  // This frame's pinned flag words (HostFlagWord, bb_types.h) straight into pinned host memory (final since k_geometry
+  // ended): the host looks at them when it reuses the frame's slot -- a few stores instead of a copy kernel on the stream.
+  // (kFlagItemCount, the frame's shade item count, is stored by k_shade_items.)
   if (host_flags && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
-    host_flags[0] = ctr->overflow;
-    host_flags[1] = ctr->bin_need;
-    host_flags[3] = ctr->n_broad;
-    host_flags[4] = ctr->n_clip_slots;
-    host_flags[5] = ctr->n_heavy;   // sizes the heavy rows of this slot's next frame
+    host_flags[kFlagOverflow] = ctr->overflow;
+    host_flags[kFlagBinNeed] = ctr->bin_need;
+    host_flags[kFlagBroadNeed] = ctr->n_broad;
+    host_flags[kFlagClipNeed] = ctr->n_clip_slots;
+    host_flags[kFlagHeavyTiles] = ctr->n_heavy;   // sizes the heavy rows of this slot's next frame
   }
   // SHORT FRAMES (item_head != nullptr; the host decides by the frame's tile count): there is no k_shade_items launch.  The
   // tiles append their items to the frame's list themselves -- one returning atomic per tile on the list's head word, which
@@ -2020,7 +2020,7 @@ __global__ __launch_bounds__(kItemsThreads) void k_shade_items(FrameParams fp, c
   // the workgroup of the last slot knows the total
   if (first + (uint32_t)kItemsThreads >= n_slots && tid == kItemsThreads - 1) {
     items[0] = at + chunks - 1u;
-    if (host_count) *host_count = at + chunks - 1u;  // pinned host memory: sizes the launch of this slot's next frame
+    if (host_count) *host_count = at + chunks - 1u;  // the slot's pinned kFlagItemCount word: sizes the launch of its next frame
   }
 }
 

@@ -201,6 +201,19 @@ struct Counters {
 };
 static_assert(sizeof(Counters) == 128, "Counters");
 
+// The pinned flag words of a frame slot (FrameSlot::h_flags: host memory the kernels store to through a uint32_t *).  They
+// describe the frame last rendered in the slot, so that a host that never synchronises can still size the slot's next one:
+//   word             written by                            read by (host)
+//   kFlagOverflow    k_raster, Counters::overflow          submit_frame_into: non-zero = grow the capacities before this frame
+//   kFlagBinNeed     k_raster, Counters::bin_need          submit_frame_into, for that growth
+//   kFlagItemCount   k_shade_items (long frames only)      launch_frame: sizes k_shade's main launch
+//   kFlagBroadNeed   k_raster, Counters::n_broad           submit_frame_into, for that growth
+//   kFlagClipNeed    k_raster, Counters::n_clip_slots      submit_frame_into, for that growth
+//   kFlagHeavyTiles  k_raster, Counters::n_heavy           launch_frame: sizes k_raster's heavy rows
+// The host zeroes them at allocation and clears some when they go stale (FrameSlot::forget_capacities / forget_extent).
+enum HostFlagWord : int { kFlagOverflow = 0, kFlagBinNeed, kFlagItemCount, kFlagBroadNeed, kFlagClipNeed, kFlagHeavyTiles };
+constexpr int kHostFlagWords = 8;  // allocated (the words behind kFlagHeavyTiles are spare)
+
 // k_geometry statistics of one workgroup
 struct BlockStats {
   uint32_t raster_tris, clipped_prims, bin_refs;

@@ -110,9 +110,8 @@ struct DeviceBuffer {
 // Everything one frame in flight owns.
 struct FrameSlot {
   void *h_staging = nullptr;  // pinned: lights, draw descriptors, instances
-  static constexpr int kHostFlagWords = 8;
-  uint32_t *h_flags = nullptr;  // pinned, device-visible {overflow bits, bin_need, shade items, every-tile entries, clip slots} of the frame last rendered in this
-                                // slot (stored by its k_raster): lets a host that never synchronises still grow capacities
+  uint32_t *h_flags = nullptr;  // pinned, device-visible: the kHostFlagWords words of HostFlagWord (bb_types.h), stored by the kernels
+                                // of the frame last rendered in this slot and read when the slot's next frame is submitted
   size_t staging_cap = 0;
   DeviceBuffer<uint8_t> d_staging;
   DeviceBuffer<RasterTri> d_tris;
@@ -144,7 +143,17 @@ struct FrameSlot {
     int32_t enable = 0, hdr16 = 1;
     float exposure = 1.f;
   } present;
-  hipEvent_t ev_geom_done = nullptr, ev_raster_done = nullptr, ev_shade_done = nullptr, ev_tail_done = nullptr;
+  hipEvent_t ev_geom_done = nullptr, ev_raster_done = nullptr, ev_tail_done = nullptr;  // edges between the streams of a frame
+  // Everything queued on this slot's image so far: the frame's k_shade, then whatever was put behind it (presentation, the
+  // GUI pass, a copy to the caller's buffer, the exchange).  Work on the image goes between follow() and busy_until().
+  hipEvent_t ev_done = nullptr;
+  // `st` follows everything queued on the slot so far.  (Also needed on the slot's own stream once something ran elsewhere:
+  // a separate presentation pass may have run on another stream and moved the event there.)
+  hipError_t follow(hipStream_t st) const { return hipStreamWaitEvent(st, ev_done, 0); }
+  // the slot is busy until what `st` holds now
+  hipError_t busy_until(hipStream_t st) { return hipEventRecord(ev_done, st); }
+  bool idle() const { return hipEventQuery(ev_done) == hipSuccess; }  // (hipErrorNotReady: still on the GPU)
+  hipError_t wait_idle() const { return hipEventSynchronize(ev_done); }  // the host waits
   // GUI pass (bbr_draw_ui) of the frame in this slot: pinned staging [commands | vertices | indices], its device copy and
   // the per-triangle records; ev_copied says the staging may be written again
   struct {
@@ -157,12 +166,18 @@ struct FrameSlot {
     bool copy_pending = false;
   } ui;
   bool in_flight = false;
-  int32_t tone_enable = 0;  // FrameUniformBlock.EnableToneMapping / Exposure of the frame in this slot
-  float tone_exposure = 1.f;
   float4 *out_used = nullptr;  // where the frame in this slot wrote its pixels
   hipStream_t stream_used = nullptr;  // the stream its k_shade ran on
   uint32_t n_prims = 0;
 
+  // The flag words describe frames rendered with the old capacities (apply_growth) / the old extent (bbr_resize).  Two sets,
+  // kept apart as they were; the heavy-tile count survives both (a list that does not fit its rows is merely not used).
+  void forget_capacities() {
+    if (h_flags) h_flags[kFlagOverflow] = h_flags[kFlagBinNeed] = h_flags[kFlagItemCount] = h_flags[kFlagBroadNeed] = h_flags[kFlagClipNeed] = 0u;
+  }
+  void forget_extent() {
+    if (h_flags) h_flags[kFlagOverflow] = h_flags[kFlagBinNeed] = h_flags[kFlagItemCount] = 0u;
+  }
   void release_tile_buffers() {
     d_tile_count.release(); d_bins.release(); d_frags.release(); d_frag_count.release(); d_items.release(); d_item_groups.release(); d_cooked.release(); d_heavy.release();
   }
@@ -181,10 +196,17 @@ struct FrameSlot {
     if (ui.h_staging) (void)hipHostFree(ui.h_staging);
     ui.h_staging = nullptr;
     ui.staging_cap = 0;
-    if (ui.ev_copied) (void)hipEventDestroy(ui.ev_copied);
-    ui.ev_copied = nullptr;
     ui.copy_pending = false;
+    for (hipEvent_t *e : {&ev_geom_done, &ev_raster_done, &ev_tail_done, &ev_done, &ui.ev_copied}) {
+      if (*e) (void)hipEventDestroy(*e);
+      *e = nullptr;
+    }
   }
+};
+
+// The streams the kernels of one frame run on (bbr_context::frame_streams).
+struct FrameStreams {
+  hipStream_t geom, raster, shade;
 };
 
 // Live contexts: a scene object (bb::SceneBase, bbs_scene) frees its meshes through the context it was created on; if
@@ -220,8 +242,6 @@ struct bbr_context {
   std::vector<RecordedDraw> draws;
   std::vector<InstanceBlock> host_instances;
   uint32_t n_prims = 0;
-  uint32_t n_live_draws = 0;
-  FirstPrims first_prims = {{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}};  // of the recorded frame's draws 1 .. 3 (k_geometry)
 
   static constexpr int kMaxSlots = 4;
   static constexpr int kCounterBlocks = kMaxSlots + 1;  // one per frame slot + one for the overlay pass
@@ -279,7 +299,6 @@ struct bbr_context {
   int timing = 0;  // 0 off, 1 five events per frame, 2 only the two events around k_shade
   int timing_stride = 1;  // option "timing_stride": events on every n-th frame only (two events a frame cost ~4 % at C3)
   uint64_t timing_tick = 0;
-  bool timing_this = false;  // the frame being submitted carries events
   // timing ring: (frame start, geometry done, raster done, shade start, shade done) per frame since the last reset
   std::vector<hipEvent_t> ring;
   uint32_t ring_frames = 0;
@@ -293,21 +312,6 @@ struct bbr_context {
   // the frame slot's previous frame had not left the GPU yet
   uint64_t host_frames = 0, host_submit_ns = 0, host_blocked_ns = 0, host_blocked_frames = 0;
 
-  hipStream_t geom_stream() const { return user_stream ? user_stream : s_geom; }
-  // k_raster on a stream of its own: geometry of frame N+1 (other slot, other counter block) need not wait for the
-  // raster of frame N.  At 1080p that chain -- not the GPU -- set the frame rate (C2: 72 -> 41 us per frame)
-  // Stream layout of the frames in flight (option "stream_layout").  All three render the same bits:
-  //   0  geometry + raster on s_geom, shade on s_shade, present on s_present          (stage streams)
-  //   1  as 0, but k_raster on s_raster: geometry of frame N+1 need not wait for the raster of frame N
-  //   2  every kernel of a frame (copy, geometry, raster, shade, present) on the stream of its slot: frames share
-  //      nothing (each slot has its own buffers and counter block), so whole frames overlap and no event is needed
-  //      inside a frame.  The four context streams double as the slot streams: a process that owns more than a
-  //      handful of HIP streams gets slower as a whole -- with seven streams every layout lost 60 %
-  // A plain option with a fixed default, 2: measured with three frames in flight (us per frame, layouts 0 / 1 / 2) it is
-  // the fastest everywhere -- C2 1080p 84.5 / 67.1 / 37.3, C3 4K 191.5 / 153.6 / 148.6 -- because a frame's chain of
-  // dependent kernels (copy -> geometry -> raster -> items -> shade) then only waits for itself.  (Round 1 timed the
-  // layouts on the first ~500 frames of every workload and switched by itself; the measurement was fragile and made
-  // the frame rate a function of history.)
   ncclComm_t comm = nullptr;
   int comm_rank = -1, comm_world = 0;
   int exchange_slot = -1, exchange_form = -1;  // where the last exchange left the whole frame (library-owned buffers)
@@ -323,21 +327,42 @@ struct bbr_context {
   // with three frames in flight the frame period 1-2 % LONGER (32: 7 %): the other frames' kernels fill the tail that
   // the order removes, and the light tiles' background stores then come in one burst instead of spread over the launch.
   int64_t heavy_tiles = -1;
+  std::vector<hipEvent_t> pending_waits;  // bbr_wait_event: applied to the first stream of the next frame
   static constexpr int kLayouts = 3;
-  int layout_mode = 2;  // the option
-  int layout = 2;       // layout of the frame being submitted
+  int layout_mode = 2;  // option "stream_layout"
   bool pipelined() const { return !user_stream && frames_in_flight > 1; }
   hipStream_t slot_stream(int i) const { return i == 0 ? s_raster : (i == 1 ? s_shade : (i == 2 ? s_present : s_geom)); }
-  hipStream_t frame_geom_stream(int slot) const { return (pipelined() && layout == 2) ? slot_stream(slot) : geom_stream(); }
-  std::vector<hipEvent_t> pending_waits;  // bbr_wait_event: applied to the first stream of the next frame
-  hipStream_t raster_stream(int slot) const {
-    return !pipelined() ? geom_stream() : (layout == 2 ? slot_stream(slot) : (layout == 1 ? s_raster : s_geom));
-  }
-  hipStream_t frame_shade_stream(int slot) const { return (pipelined() && layout == 2) ? slot_stream(slot) : shade_stream(); }
+  // Outside a frame (synchronous passes, self-tests, waiting): the context's first stream, and the one shading runs on
+  hipStream_t geom_stream() const { return user_stream ? user_stream : s_geom; }
   hipStream_t shade_stream() const { return user_stream ? user_stream : (frames_in_flight > 1 ? s_shade : s_geom); }
   // k_present is bandwidth-bound, k_shade issue-bound: on its own stream the presentation of frame N overlaps the
   // shading of frame N+1 instead of delaying it
   hipStream_t present_stream() const { return (user_stream || frames_in_flight == 1) ? shade_stream() : s_present; }
+  // Stream layout of the frames in flight (option "stream_layout"), decided here and in slot_present_stream, nowhere else.
+  // A caller's stream (bbr_set_stream) or one frame in flight: everything on one stream.  Otherwise all three render the
+  // same bits:
+  //   0  geometry + raster on s_geom, shade on s_shade, present on s_present          (stage streams)
+  //   1  as 0, but k_raster on s_raster: geometry of frame N+1 need not wait for the raster of frame N.  At 1080p that
+  //      chain -- not the GPU -- set the frame rate (C2: 72 -> 41 us per frame)
+  //   2  every kernel of a frame (copy, geometry, raster, shade, present) on the stream of its slot: frames share
+  //      nothing (each slot has its own buffers and counter block), so whole frames overlap and no event is needed
+  //      inside a frame.  The four context streams double as the slot streams: a process that owns more than a
+  //      handful of HIP streams gets slower as a whole -- with seven streams every layout lost 60 %
+  // A plain option with a fixed default, 2: measured with three frames in flight (us per frame, layouts 0 / 1 / 2) it is
+  // the fastest everywhere -- C2 1080p 84.5 / 67.1 / 37.3, C3 4K 191.5 / 153.6 / 148.6 -- because a frame's chain of
+  // dependent kernels (copy -> geometry -> raster -> items -> shade) then only waits for itself.  (Round 1 timed the
+  // layouts on the first ~500 frames of every workload and switched by itself; the measurement was fragile and made
+  // the frame rate a function of history.)
+  FrameStreams frame_streams(int slot) const {
+    if (!pipelined()) return {geom_stream(), geom_stream(), geom_stream()};
+    if (layout_mode == 2) return {slot_stream(slot), slot_stream(slot), slot_stream(slot)};
+    return {s_geom, layout_mode == 1 ? s_raster : s_geom, s_shade};
+  }
+  // The stream the presentation and the GUI pass of the frame in `s` run on.  Layout 2: the slot's own stream, behind its
+  // k_shade (the other slots' streams keep the GPU busy meanwhile); otherwise the presentation stream.
+  hipStream_t slot_present_stream(const FrameSlot &s) const {
+    return (pipelined() && s.stream_used && s.stream_used != shade_stream()) ? s.stream_used : present_stream();
+  }
   int n_slots() const { return user_stream ? 1 : frames_in_flight; }
   int tile_w() const { return tile_mode == 0 ? 64 : 32; }
   int tile_h() const { return tile_mode == 0 ? 64 : 32; }
@@ -421,19 +446,20 @@ int drain(bbr_context *c) {
 
 int ensure_srgb_tables(bbr_context *c);
 
-int ensure_slot_buffers(bbr_context *c, FrameSlot &s) {
-  size_t tiles = (size_t)c->tiles_x() * c->tiles_y();
-  size_t out_rows = (size_t)std::max(c->height, c->shard_rows());
-  HIP_TRY(c, s.d_tris.ensure(std::max<size_t>(c->n_prims, 1)));
-  HIP_TRY(c, s.d_attrs.ensure(std::max<size_t>(c->n_prims, 1)));
+// The buffers of one binned pass (k_geometry -> k_raster) over `n_prims` primitives at the context's tile grid and
+// capacities.  The main pass (ensure_slot_buffers) adds its items, item groups, cooked lights, heavy list, frame, present,
+// depth and dump buffers; the overlay pass (bbr_draw_overlays) passes n_prims > 0 and needs none of those.
+int ensure_pass_buffers(bbr_context *c, FrameSlot &s, uint32_t n_prims) {
+  const size_t tiles = (size_t)c->tiles_x() * c->tiles_y();
+  HIP_TRY(c, s.d_tris.ensure(std::max<size_t>(n_prims, 1)));
+  HIP_TRY(c, s.d_attrs.ensure(std::max<size_t>(n_prims, 1)));
 #ifdef BB_STAMPS
   HIP_TRY(c, s.d_clip.ensure(c->clip_cap + 8192));  // diagnostic build: room for per-workgroup time stamps
 #else
   HIP_TRY(c, s.d_clip.ensure(c->clip_cap));
 #endif
   HIP_TRY(c, c->d_counters.ensure(bbr_context::kCounterBlocks, true));
-  HIP_TRY(c, c->d_counters_done.ensure(bbr_context::kCounterBlocks, true));
-  HIP_TRY(c, s.d_block_stats.ensure(std::max<size_t>((c->n_prims + 255) / 256, 1) * 4, true));
+  HIP_TRY(c, s.d_block_stats.ensure(std::max<size_t>((n_prims + 255) / 256, 1) * 4, true));
   HIP_TRY(c, s.d_tile_count.ensure(tiles * kBinClasses, true));
   HIP_TRY(c, s.d_bins.ensure(tiles * kBinClasses * c->bin_cap));
   // (at least kBroadSpec entries: k_raster's light-tile path reads that many before it knows how many the frame wrote)
@@ -444,6 +470,15 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s) {
 #else
   HIP_TRY(c, s.d_frag_count.ensure(tiles, true));
 #endif
+  return BBR_OK;
+}
+
+int ensure_slot_buffers(bbr_context *c, FrameSlot &s) {
+  size_t tiles = (size_t)c->tiles_x() * c->tiles_y();
+  size_t out_rows = (size_t)std::max(c->height, c->shard_rows());
+  int rc = ensure_pass_buffers(c, s, c->n_prims);
+  if (rc) return rc;
+  HIP_TRY(c, c->d_counters_done.ensure(bbr_context::kCounterBlocks, true));
   // (+ kShadeWaves: the last workgroup of k_shade's main launch reads the item words of all its waves before it knows the count)
   HIP_TRY(c, s.d_items.ensure(1 + tiles * (size_t)(c->tile_w() * c->tile_h() / 64) + kShadeWaves, true));
   if (tiles > (size_t)kItemGroupSlots * kItemGroups)  // 65536 launch slots: 8192 x 8192 pixels at 32 x 32 tiles
@@ -466,14 +501,28 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s) {
     HIP_TRY(c, c->d_vis_depth.ensure((size_t)c->width * c->height));
   }
   if (!s.h_flags) {
-    HIP_TRY(c, hipHostMalloc((void **)&s.h_flags, FrameSlot::kHostFlagWords * sizeof(uint32_t), hipHostMallocDefault));
-    for (int i = 0; i < FrameSlot::kHostFlagWords; ++i) s.h_flags[i] = 0u;
+    HIP_TRY(c, hipHostMalloc((void **)&s.h_flags, kHostFlagWords * sizeof(uint32_t), hipHostMallocDefault));
+    for (int i = 0; i < kHostFlagWords; ++i) s.h_flags[i] = 0u;
   }
-  if (!s.ev_geom_done) HIP_TRY(c, hipEventCreateWithFlags(&s.ev_geom_done, hipEventDisableTiming));
-  if (!s.ev_raster_done) HIP_TRY(c, hipEventCreateWithFlags(&s.ev_raster_done, hipEventDisableTiming));
-  if (!s.ev_shade_done) HIP_TRY(c, hipEventCreateWithFlags(&s.ev_shade_done, hipEventDisableTiming));
-  if (!s.ev_tail_done) HIP_TRY(c, hipEventCreateWithFlags(&s.ev_tail_done, hipEventDisableTiming));
+  for (hipEvent_t *e : {&s.ev_geom_done, &s.ev_raster_done, &s.ev_done, &s.ev_tail_done})
+    if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
   return BBR_OK;
+}
+
+// The timing ring's events (option "timing": made there, not in the first timed frame -- 2560 hipEventCreate calls take
+// half a millisecond)
+int ensure_timing_ring(bbr_context *c) {
+  if (!c->ring.empty()) return BBR_OK;
+  c->ring.resize(bbr_context::kRingEvents * bbr_context::kRingCap);
+  for (auto &e : c->ring) HIP_TRY(c, hipEventCreate(&e));
+  return BBR_OK;
+}
+
+// An edge between two streams of a frame: `to` goes on behind what `from` holds now.  Nothing to do on one stream.
+void stream_edge(hipStream_t from, hipStream_t to, hipEvent_t ev) {
+  if (from == to) return;
+  (void)hipEventRecord(ev, from);
+  (void)hipStreamWaitEvent(to, ev, 0);
 }
 
 int upload_material_table(bbr_context *c) {
@@ -493,11 +542,11 @@ int upload_material_table(bbr_context *c) {
   return BBR_OK;
 }
 
+// `ev`: the frame's five timing events, or nullptr
 template <int TW, int TH>
-void launch_frame(bbr_context *c, FrameSlot &s, const FrameParams &fp_in, const Mat4 &pv,
-                  const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DrawDesc *d_draws, uint32_t n_draws, float4 *out,
-                  uint32_t *d_item_head) {
-  const int slot_index = (int)(&s - c->slots);
+void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent_t *ev, const FrameParams &fp_in, const Mat4 &pv,
+                  const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DrawDesc *d_draws, uint32_t n_draws,
+                  const FirstPrims &first_prims, float4 *out, uint32_t *d_item_head) {
   FrameParams fp = fp_in;
   // a rank without bands (more ranks than bands) still launches one row: its blocks fall off tiles_y and exit
   const int grid_y = std::max(1, c->world > 1 ? c->local_bands() * fp.band_tiles : fp.tiles_y);
@@ -508,47 +557,34 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameParams &fp_in, const 
   const uint32_t max_items = (uint32_t)(fp.tiles_x * grid_y) * (uint32_t)(TW * TH / 64);
   const bool short_frame = max_items <= (uint32_t)c->no_tail_items;
   // Heavy tiles first (long frames; k_raster): the heavy rows in front of the launch are sized from the length of the list
-  // the slot's previous frame produced (pinned word 5, written by k_raster) + 1/8 + 8.  A list that does not fit them is not
+  // the slot's previous frame produced (pinned word kFlagHeavyTiles) + 1/8 + 8.  A list that does not fit them is not
   // used by that frame at all (plain screen order), so the first frame of a slot, or one after a jump, is merely slower.
   const int64_t heavy_tiles = c->heavy_tiles >= 0 ? c->heavy_tiles : (c->pipelined() ? 0 : 64);
   if (!short_frame && heavy_tiles > 0 && !c->dump_vis) {
     fp.heavy_threshold = (uint32_t)heavy_tiles;
-    const uint32_t seen_heavy = s.h_flags ? s.h_flags[5] : 0u;
+    const uint32_t seen_heavy = s.h_flags ? s.h_flags[kFlagHeavyTiles] : 0u;
     if (seen_heavy) fp.heavy_rows = (int32_t)((seen_heavy + seen_heavy / 8u + 8u + (uint32_t)fp.tiles_x - 1u) / (uint32_t)fp.tiles_x);
   }
-  hipStream_t sg = c->frame_geom_stream(slot_index), sr = c->raster_stream(slot_index), ss = c->frame_shade_stream(slot_index);
+  const hipStream_t sg = st.geom, sr = st.raster, ss = st.shade;
   Counters *ctr = c->d_counters.ptr + s.ctr_index, *ctr_done = c->d_counters_done.ptr + s.ctr_index;
-  hipEvent_t *ev = c->timing_this ? &c->ring[bbr_context::kRingEvents * (c->ring_frames % bbr_context::kRingCap)] : nullptr;
-#ifdef BB_ABLATE
-  // diagnostic builds only (tools/_gpu_overlap.py): bit 17 = launch nothing but k_shade -- the lists of the slot's last whole
-  // frame are shaded again -- which measures the shading's own pipelined rate.  (There is no "front half only" twin: k_shade is
-  // what clears the slot's counters and chunk totals, and a frame without it overruns the item list.)
-  const bool skip_front = (c->ablate & (1u << 17)) != 0u;
-#else
-  constexpr bool skip_front = false;
-#endif
-  if (c->n_prims && !skip_front)
+  if (c->n_prims)
     hipLaunchKernelGGL((k_geometry<TW, TH>), dim3((c->n_prims + 255) / 256), dim3(256), 0, sg, d_draws, n_draws,
-                       c->n_prims, c->first_prims, s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv, view, fp, s.d_clip.ptr,
+                       c->n_prims, first_prims, s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv, view, fp, s.d_clip.ptr,
                        s.d_broad.ptr, c->d_materials.ptr, s.d_block_stats.ptr, s.d_heavy.ptr);
   if (ev && c->timing == 1) (void)hipEventRecord(ev[1], sg);
-  if (sr != sg) {
-    (void)hipEventRecord(s.ev_geom_done, sg);
-    (void)hipStreamWaitEvent(sr, s.ev_geom_done, 0);
-  }
+  stream_edge(sg, sr, s.ev_geom_done);
   // k_raster writes the background pixels of `out`: if the frame still shading on the other stream writes the
   // same buffer (single external output), raster has to wait for it; geometry above still overlapped
   // (every frame still in flight, not just the previous one: with one stream per slot, or while the layout is being
   //  switched, "after the previous frame" no longer implies "after the one before")
   for (const FrameSlot &o : c->slots)
-    if (&o != &s && o.in_flight && o.out_used == out && o.stream_used != sr) (void)hipStreamWaitEvent(sr, o.ev_shade_done, 0);
+    if (&o != &s && o.in_flight && o.out_used == out && o.stream_used != sr) (void)o.follow(sr);
   // option "present_fused": k_raster / k_shade write presented pixels into the slot's RGBA8 image
   uint32_t *out8 = c->present_fused ? s.d_present.ptr : nullptr;
   const SrgbTables *tables = c->present_fused ? c->d_srgb_tables.ptr : nullptr;
   if (fp.deferred)
     hipLaunchKernelGGL(k_deferred_background, dim3(1), dim3(kBackgroundThreads), 0, sr, sp, d_lights, s.d_background.ptr, tables, fp.gbuffer_view);
   uint32_t *item_head = short_frame ? d_item_head : nullptr;
-  if (!skip_front)
   hipLaunchKernelGGL((k_raster<TW, TH>), dim3(fp.tiles_x, fp.heavy_rows + grid_y), dim3(kTileThreads), 0, sr, s.d_tile_count.ptr, ctr,
                      s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, out, fp, s.d_tris.ptr, s.d_clip.ptr, s.d_bins.ptr,
                      c->dump_vis ? c->d_vis_prim.ptr : nullptr,
@@ -559,23 +595,20 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameParams &fp_in, const 
   s.has_depth = c->overlays && c->world == 1;
   // k_shade's work list (64 fragments per item), built from the per-tile fragment counts as soon as k_raster is done; the
   // same launch cooks the frame's light table
-  if (!short_frame && !skip_front)
+  if (!short_frame)
     hipLaunchKernelGGL((k_shade_items<TW, TH>), dim3((unsigned)((fp.tiles_x * grid_y + kItemsThreads - 1) / kItemsThreads)), dim3(kItemsThreads), 0, sr, fp, s.d_frag_count.ptr, s.d_item_groups.ptr, s.d_items.ptr,
-                       fp.tiles_x, grid_y, s.h_flags ? s.h_flags + 2 : nullptr, d_lights, sp.num_lights, s.d_cooked.ptr,
+                       fp.tiles_x, grid_y, s.h_flags ? s.h_flags + kFlagItemCount : nullptr, d_lights, sp.num_lights, s.d_cooked.ptr,
                        s.d_tile_count.ptr, ctr, s.d_heavy.ptr);
   const uint32_t *item_count = short_frame ? item_head : s.d_items.ptr;   // where k_shade finds the number of items
   if (ev && c->timing == 1) (void)hipEventRecord(ev[2], sr);
-  if (ss != sr) {
-    (void)hipEventRecord(s.ev_raster_done, sr);
-    (void)hipStreamWaitEvent(ss, s.ev_raster_done, 0);
-  }
+  stream_edge(sr, ss, s.ev_raster_done);
   // (ev[3], the start of the shading interval, is recorded in front of the MAIN launch below -- behind the tail launch when
   //  both are on one stream: the interval is then the dominant kernel's own, which the kernel trace can be held against)
   uint2 *gbuf = (fp.deferred && c->dump_gbuffer) ? c->d_gbuffer.ptr : nullptr;
   // Main launch: one item (64 fragments) per wave, four per workgroup, sized from the item count of the frame this slot
   // rendered last (k_shade_items leaves it in pinned host memory) plus 3 %; tail launch: a small persistent grid for
   // whatever lies behind that (a scene that suddenly grew; normally nothing, and its workgroups exit at once).
-  const uint32_t seen = s.h_flags ? s.h_flags[2] : 0u;
+  const uint32_t seen = s.h_flags ? s.h_flags[kFlagItemCount] : 0u;
   uint32_t est = seen ? seen + seen / 32u + 64u : max_items;
   if (est > max_items) est = max_items;
   // A small frame is launched at full coverage instead: workgroups without an item leave after one scalar load, and a few
@@ -601,12 +634,10 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameParams &fp_in, const 
       else aniso_launch(std::false_type{});
       return;
     }
-    if (tail) {
+    if (tail)
       hipLaunchKernelGGL((k_shade<TW, TH, decltype(deferred)::value, decltype(present)::value, true, true>), dim3(32), dim3(kShadeThreads),
                          0, sr, s.d_items.ptr, item_count, main_wgs * (uint32_t)kShadeWaves, s.d_frags.ptr, s.d_frag_count.ptr, s.d_attrs.ptr,
                          s.d_clip.ptr, fp, sp, s.d_cooked.ptr, c->d_materials.ptr, out, gbuf, tables, out8, ctr, ctr_done, nullptr);
-      if (ss != sr) (void)hipEventRecord(s.ev_tail_done, sr);
-    }
     if (ev) (void)hipEventRecord(ev[3], ss);
     // (the main launch without the per-map sampling path when every material is packed: k_shade, MIXED)
     auto main_launch = [&](auto mixed) {
@@ -617,7 +648,7 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameParams &fp_in, const 
     };
     if (c->all_packed) main_launch(std::false_type{});
     else main_launch(std::true_type{});
-    if (tail && ss != sr) (void)hipStreamWaitEvent(ss, s.ev_tail_done, 0);
+    if (tail) stream_edge(sr, ss, s.ev_tail_done);  // (nothing else went onto sr since the tail launch)
   };
   if (fp.deferred) {
     if (out8) shade(std::true_type{}, std::true_type{});
@@ -626,7 +657,7 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameParams &fp_in, const 
     if (out8) shade(std::false_type{}, std::true_type{});
     else shade(std::false_type{}, std::false_type{});
   }
-  (void)hipEventRecord(s.ev_shade_done, ss);
+  (void)s.busy_until(ss);
   s.stream_used = ss;
   if (ev) {
     (void)hipEventRecord(ev[4], ss);
@@ -652,11 +683,37 @@ int apply_growth(bbr_context *c, uint32_t overflow, uint32_t bin_need, uint32_t 
   if (overflow & 4u) c->clip_cap = grown(c->clip_cap, clip_need);
   ++c->retries;
   for (FrameSlot &s : c->slots) {
-    if (s.h_flags) s.h_flags[0] = s.h_flags[1] = s.h_flags[2] = s.h_flags[3] = s.h_flags[4] = 0u;  // they describe frames rendered with the old capacities
+    s.forget_capacities();
     // tile counters may hold residue of references that did not fit
     if (s.d_tile_count.ptr) HIP_TRY(c, zero_fill_sync(s.d_tile_count.ptr, s.d_tile_count.cap * sizeof(uint32_t)));
   }
   return BBR_OK;
+}
+
+// The recorded frame's draw descriptors as k_geometry reads them, into `hd`; `d_inst_base` is where the device copy of the
+// instance data will be.  Returns how many there are: empty draws would break the first_prim search and get none.
+uint32_t fill_draw_descs(const bbr_context *c, DrawDesc *hd, const InstanceBlock *d_inst_base, FirstPrims &first_prims) {
+  uint32_t k = 0;
+  for (const RecordedDraw &rd : c->draws) {
+    if (!rd.n_instances || !rd.tris_per_instance) continue;
+    const Mesh &m = c->meshes[rd.mesh];
+    DrawDesc d;
+    d.vertices = m.d_vertices;
+    d.indices = m.d_indices;
+    d.instances = d_inst_base + rd.first_instance;
+    d.n_instances = rd.n_instances;
+    d.tris_per_instance = rd.tris_per_instance;
+    d.first_prim = rd.first_prim;
+    d.material = (uint32_t)rd.material;
+    const MaterialDesc &md = c->materials[rd.material].desc;
+    d.packed = md.packed;
+    d.packed_dims = md.packed ? ((uint32_t)md.pw | ((uint32_t)md.ph << 16)) : 0u;
+    d.pad = 0;
+    if (k >= 1 && k <= (uint32_t)kInlineFirstPrims) first_prims.v[k - 1] = d.first_prim;
+    hd[k++] = d;
+  }
+  for (uint32_t q = std::max(k, 1u); q <= (uint32_t)kInlineFirstPrims; ++q) first_prims.v[q - 1] = 0xFFFFFFFFu;
+  return k;
 }
 
 // Queue the recorded frame into slot `slot_index`.  Asynchronous.
@@ -667,9 +724,9 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   FrameSlot &s = c->slots[slot_index];
   // the slot's previous frame (two frames ago) must have left the GPU before its buffers are reused
   if (s.in_flight) {
-    if (hipEventQuery(s.ev_shade_done) != hipSuccess) {  // (hipErrorNotReady: still on the GPU -- the host waits, and says so)
+    if (!s.idle()) {  // still on the GPU: the host waits, and says so
       const auto b0 = std::chrono::steady_clock::now();
-      HIP_TRY(c, hipEventSynchronize(s.ev_shade_done));
+      HIP_TRY(c, s.wait_idle());
       c->host_blocked_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - b0).count();
       ++c->host_blocked_frames;
     }
@@ -678,8 +735,9 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   // Self-healing for hosts that only stream frames: the frame that last used this slot reported an overflow.  Its
   // pixels (and those of the frames queued since) are incomplete and already handed out; from this frame on the
   // capacities fit.  (Synchronising calls do better: they re-render the overflowed frame, sync_and_fix.)
-  if (s.h_flags && s.h_flags[0]) {
-    const uint32_t overflow = s.h_flags[0], bin_need = s.h_flags[1], broad_need = s.h_flags[3], clip_need = s.h_flags[4];
+  if (s.h_flags && s.h_flags[kFlagOverflow]) {
+    const uint32_t overflow = s.h_flags[kFlagOverflow], bin_need = s.h_flags[kFlagBinNeed], broad_need = s.h_flags[kFlagBroadNeed],
+                   clip_need = s.h_flags[kFlagClipNeed];
     rc = drain(c);
     if (rc) return rc;
     rc = apply_growth(c, overflow, bin_need, broad_need, clip_need);
@@ -704,49 +762,25 @@ int submit_frame_into(bbr_context *c, int slot_index) {
     HIP_TRY(c, s.d_staging.ensure(cap));
   }
   std::memcpy(s.h_staging, c->frame_u.lights, lights_bytes);
-  {
-    // draw descriptors point into the device copy of the instance data made by the same transfer
-    const InstanceBlock *d_inst_base = reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + lights_bytes + draws_bytes);
-    DrawDesc *hd = reinterpret_cast<DrawDesc *>((uint8_t *)s.h_staging + lights_bytes);
-    uint32_t k = 0;
-    for (const RecordedDraw &rd : c->draws) {
-      if (!rd.n_instances || !rd.tris_per_instance) continue;  // empty draws would break the first_prim search
-      const Mesh &m = c->meshes[rd.mesh];
-      DrawDesc d;
-      d.vertices = m.d_vertices;
-      d.indices = m.d_indices;
-      d.instances = d_inst_base + rd.first_instance;
-      d.n_instances = rd.n_instances;
-      d.tris_per_instance = rd.tris_per_instance;
-      d.first_prim = rd.first_prim;
-      d.material = (uint32_t)rd.material;
-      const MaterialDesc &md = c->materials[rd.material].desc;
-      d.packed = md.packed;
-      d.packed_dims = md.packed ? ((uint32_t)md.pw | ((uint32_t)md.ph << 16)) : 0u;
-      d.pad = 0;
-      if (k >= 1 && k <= (uint32_t)kInlineFirstPrims) c->first_prims.v[k - 1] = d.first_prim;
-      hd[k++] = d;
-    }
-    for (uint32_t q = k; q <= (uint32_t)kInlineFirstPrims; ++q)
-      if (q >= 1) c->first_prims.v[q - 1] = 0xFFFFFFFFu;
-    c->n_live_draws = k;
-  }
+  // draw descriptors point into the device copy of the instance data made by the same transfer
+  FirstPrims first_prims;  // first_prim of the frame's draws 1 .. 3 (k_geometry)
+  const uint32_t n_live_draws =
+      fill_draw_descs(c, reinterpret_cast<DrawDesc *>((uint8_t *)s.h_staging + lights_bytes),
+                      reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + lights_bytes + draws_bytes), first_prims);
   if (inst_bytes) std::memcpy((uint8_t *)s.h_staging + lights_bytes + draws_bytes, c->host_instances.data(), inst_bytes);
   std::memset((uint8_t *)s.h_staging + head_offset, 0, 16);
   uint32_t *d_item_head = reinterpret_cast<uint32_t *>(s.d_staging.ptr + head_offset);
 
   const int n_lights = std::min(std::max(c->frame_u.num_lights, 0), kMaxNumLights);
-  c->layout = c->pipelined() ? c->layout_mode : 0;
-  hipStream_t sg = c->frame_geom_stream(slot_index);
-  for (hipEvent_t e : c->pending_waits) HIP_TRY(c, hipStreamWaitEvent(sg, e, 0));  // bbr_wait_event
+  const FrameStreams st = c->frame_streams(slot_index);
+  for (hipEvent_t e : c->pending_waits) HIP_TRY(c, hipStreamWaitEvent(st.geom, e, 0));  // bbr_wait_event
   c->pending_waits.clear();
-  c->timing_this = c->timing && (c->timing_tick++ % (uint64_t)c->timing_stride) == 0;
-  if (c->timing_this) {
-    if (c->ring.empty()) {
-      c->ring.resize(bbr_context::kRingEvents * bbr_context::kRingCap);
-      for (auto &e : c->ring) HIP_TRY(c, hipEventCreate(&e));
-    }
-    if (c->timing == 1) HIP_TRY(c, hipEventRecord(c->ring[bbr_context::kRingEvents * (c->ring_frames % bbr_context::kRingCap)], sg));
+  hipEvent_t *ev = nullptr;  // this frame's timing events, if it carries any
+  if (c->timing && (c->timing_tick++ % (uint64_t)c->timing_stride) == 0) {
+    rc = ensure_timing_ring(c);
+    if (rc) return rc;
+    ev = &c->ring[bbr_context::kRingEvents * (c->ring_frames % bbr_context::kRingCap)];
+    if (c->timing == 1) HIP_TRY(c, hipEventRecord(ev[0], st.geom));
   }
   s.ctr_index = slot_index;
   const Light *d_lights = reinterpret_cast<const Light *>(s.d_staging.ptr);
@@ -763,9 +797,9 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   sp.num_lights = n_lights;
   float4 *out = c->ext_out ? reinterpret_cast<float4 *>(c->ext_out) : s.d_frame.ptr;
 
-  HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, s.h_staging, total, hipMemcpyHostToDevice, sg));
-  if (c->tile_mode == 0) launch_frame<64, 64>(c, s, fp, pv, view, sp, d_lights, d_draws, c->n_live_draws, out, d_item_head);
-  else launch_frame<32, 32>(c, s, fp, pv, view, sp, d_lights, d_draws, c->n_live_draws, out, d_item_head);
+  HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, s.h_staging, total, hipMemcpyHostToDevice, st.geom));
+  if (c->tile_mode == 0) launch_frame<64, 64>(c, s, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head);
+  else launch_frame<32, 32>(c, s, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head);
   HIP_TRY(c, hipGetLastError());
   s.in_flight = true;
   s.fused = c->present_fused;
@@ -777,8 +811,6 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   s.present.copy_to = nullptr;
   s.frame_u = c->frame_u;
   s.view_u = c->view_u;
-  s.tone_enable = c->frame_u.enable_tone_mapping;
-  s.tone_exposure = c->frame_u.exposure;
   s.out_used = out;
   s.n_prims = c->n_prims;
   c->last_slot = slot_index;
@@ -823,9 +855,8 @@ int queue_present(bbr_context *c, FrameSlot &s) {
   int rc_tables = ensure_srgb_tables(c);
   if (rc_tables) return rc_tables;
   const size_t n = c->shard_pixels();
-  // layout 2: on the slot's own stream, behind its k_shade (the other slots' streams keep the GPU busy meanwhile)
-  hipStream_t ps = (c->pipelined() && s.stream_used && s.stream_used != c->shade_stream()) ? s.stream_used : c->present_stream();
-  if (ps != s.stream_used) HIP_TRY(c, hipStreamWaitEvent(ps, s.ev_shade_done, 0));  // behind the frame's k_shade
+  const hipStream_t ps = c->slot_present_stream(s);
+  if (ps != s.stream_used) HIP_TRY(c, s.follow(ps));  // behind the frame's k_shade
   hipEvent_t *pe = nullptr;
   if (c->timing) {
     if (c->present_ring.empty()) {
@@ -844,8 +875,16 @@ int queue_present(bbr_context *c, FrameSlot &s) {
     HIP_TRY(c, hipEventRecord(pe[1], ps));
     ++c->present_launches;
   }
-  // the slot is busy until the presented image exists
-  HIP_TRY(c, hipEventRecord(s.ev_shade_done, ps));
+  HIP_TRY(c, s.busy_until(ps));  // ... until the presented image exists
+  return BBR_OK;
+}
+
+// Fused presentation: the slot's image (the frame itself) copied to the caller's buffer
+int copy_presented(bbr_context *c, FrameSlot &s, void *dst) {
+  const hipStream_t ps = c->present_stream();
+  HIP_TRY(c, s.follow(ps));
+  HIP_TRY(c, hipMemcpyAsync(dst, s.d_present.ptr, c->shard_pixels() * 4, hipMemcpyDeviceToDevice, ps));
+  HIP_TRY(c, s.busy_until(ps));
   return BBR_OK;
 }
 
@@ -873,11 +912,8 @@ int resubmit_last_frame(bbr_context *c) {
     rc = queue_present(c, s);
     if (rc) return rc;
   } else if (s.fused && present.copy_to) {  // fused: the re-rendered frame is the image; redo the caller's copy
-    const size_t n = c->shard_pixels();
     s.present.copy_to = present.copy_to;
-    HIP_TRY(c, hipStreamWaitEvent(c->present_stream(), s.ev_shade_done, 0));
-    HIP_TRY(c, hipMemcpyAsync(present.copy_to, s.d_present.ptr, n * 4, hipMemcpyDeviceToDevice, c->present_stream()));
-    HIP_TRY(c, hipEventRecord(s.ev_shade_done, c->present_stream()));
+    return copy_presented(c, s, present.copy_to);
   }
   return BBR_OK;
 }
@@ -897,6 +933,18 @@ int sync_and_fix(bbr_context *c, Counters *out_counters) {
     if (rc) return rc;
   }
   return fail(c, BBR_ERR_CAPACITY, "bin capacity still exceeded after 8 growth steps");
+}
+
+// Render the last frame again with a dump switched on (bbr_context::dump_vis / dump_gbuffer / dump_surface): nothing of
+// what the read-backs hand out lives in memory after a frame.  The dump's buffer is filled when this returns BBR_OK.
+int rerender_with(bbr_context *c, bool bbr_context::*dump) {
+  int rc = sync_and_fix(c, nullptr);
+  if (rc) return rc;
+  c->*dump = true;
+  rc = resubmit_last_frame(c);
+  if (rc == BBR_OK) rc = sync_and_fix(c, nullptr);
+  c->*dump = false;
+  return rc;
 }
 
 const void *last_output(const bbr_context *c) {
@@ -1155,18 +1203,8 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
   for (size_t q = 1; q < draws.size() && q <= (size_t)kInlineFirstPrims; ++q) ov_first.v[q - 1] = draws[q].first_prim;
 
   for (int attempt = 0; attempt < 8; ++attempt) {
-    const size_t tiles = (size_t)c->tiles_x() * c->tiles_y();
-    HIP_TRY(c, s.d_tris.ensure(n_prims));
-    HIP_TRY(c, s.d_attrs.ensure(n_prims));
-    HIP_TRY(c, s.d_clip.ensure(c->clip_cap));
-    HIP_TRY(c, c->d_counters.ensure(bbr_context::kCounterBlocks, true));
-    HIP_TRY(c, s.d_block_stats.ensure(((n_prims + 255) / 256) * 4, true));
-    HIP_TRY(c, s.d_tile_count.ensure(tiles * kBinClasses, true));
-    HIP_TRY(c, s.d_bins.ensure(tiles * kBinClasses * c->bin_cap));
-    // (at least kBroadSpec entries: k_raster's light-tile path reads that many before it knows how many the frame wrote)
-  HIP_TRY(c, s.d_broad.ensure(std::max<size_t>(c->broad_cap, kBroadSpec), true));
-    HIP_TRY(c, s.d_frags.ensure(tiles * (size_t)(c->tile_w() * c->tile_h())));
-    HIP_TRY(c, s.d_frag_count.ensure(tiles, true));
+    rc = ensure_pass_buffers(c, s, n_prims);  // (again after a growth)
+    if (rc) return rc;
     FrameParams fp = make_params(c);
     fp.deferred = 0;
     fp.gbuffer_view = -1;
@@ -1320,7 +1358,7 @@ extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
   // Each buffer is tested against its own capacity, so that a call after a failed allocation grows what is still missing.
   if (total > ui.staging_cap || total > ui.d_staging.cap || n_tris > ui.d_tris.cap || n_tris > ui.d_boxes.cap) {
     // growing: everything queued for this slot (an earlier GUI pass included) must have left the buffers first
-    HIP_TRY(c, hipEventSynchronize(s.ev_shade_done));
+    HIP_TRY(c, s.wait_idle());
     ui.copy_pending = false;
     if (total > ui.staging_cap) {
       if (ui.h_staging) (void)hipHostFree(ui.h_staging);
@@ -1345,8 +1383,8 @@ extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
   std::memcpy(h + idx_at, draw->indices, idx_bytes);
 
   // behind the presentation (and whatever was queued on the image since), on the stream the presentation used
-  hipStream_t ps = (c->pipelined() && s.stream_used && s.stream_used != c->shade_stream()) ? s.stream_used : c->present_stream();
-  HIP_TRY(c, hipStreamWaitEvent(ps, s.ev_shade_done, 0));
+  const hipStream_t ps = c->slot_present_stream(s);
+  HIP_TRY(c, s.follow(ps));
   HIP_TRY(c, hipMemcpyAsync(ui.d_staging.ptr, ui.h_staging, total, hipMemcpyHostToDevice, ps));
   HIP_TRY(c, hipEventRecord(ui.ev_copied, ps));
   ui.copy_pending = true;
@@ -1377,7 +1415,7 @@ extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
     HIP_TRY(c, hipMemcpyAsync(static_cast<uint32_t *>(s.present.copy_to) + first, s.present.out + first, count * 4,
                               hipMemcpyDeviceToDevice, ps));
   }
-  HIP_TRY(c, hipEventRecord(s.ev_shade_done, ps));  // the slot is busy until the GUI is in the image
+  HIP_TRY(c, s.busy_until(ps));  // ... until the GUI is in the image
   return BBR_OK;
 }
 
@@ -1419,23 +1457,13 @@ static void release_context(bbr_context *c) {
   c->d_vis_prim.release();
   c->d_vis_depth.release();
   c->d_gbuffer.release();
-  for (FrameSlot &s : c->slots) {
-    s.release_all();
-    if (s.ev_geom_done) (void)hipEventDestroy(s.ev_geom_done);
-    if (s.ev_raster_done) (void)hipEventDestroy(s.ev_raster_done);
-    if (s.ev_shade_done) (void)hipEventDestroy(s.ev_shade_done);
-    if (s.ev_tail_done) (void)hipEventDestroy(s.ev_tail_done);
-  }
+  for (FrameSlot &s : c->slots) s.release_all();
   for (Mesh *m : {&c->marker_mesh, &c->gizmo_mesh}) {
     if (m->d_vertices) (void)hipFree(m->d_vertices);
     if (m->d_indices) (void)hipFree(m->d_indices);
   }
   c->ov.release_all();
   c->tbn_pass.release();
-  if (c->ov.ev_geom_done) (void)hipEventDestroy(c->ov.ev_geom_done);
-  if (c->ov.ev_raster_done) (void)hipEventDestroy(c->ov.ev_raster_done);
-  if (c->ov.ev_shade_done) (void)hipEventDestroy(c->ov.ev_shade_done);
-  if (c->ov.ev_tail_done) (void)hipEventDestroy(c->ov.ev_tail_done);
   for (auto &e : c->ring)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : c->present_ring)
@@ -1799,7 +1827,7 @@ int bbr_stream_wait_frame(bbr_context *c, void *stream) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "stream_wait_frame: nothing rendered");
-  HIP_TRY(c, hipStreamWaitEvent((hipStream_t)stream, c->slots[c->last_slot].ev_shade_done, 0));
+  HIP_TRY(c, c->slots[c->last_slot].follow((hipStream_t)stream));
   return BBR_OK;
 }
 
@@ -1855,7 +1883,7 @@ int bbr_resize(bbr_context *c, int32_t width, int32_t height) {
     s.present.copy_to = nullptr;
     s.out_used = nullptr;
     s.in_flight = false;
-    if (s.h_flags) s.h_flags[0] = s.h_flags[1] = s.h_flags[2] = 0u;
+    s.forget_extent();
   };
   for (FrameSlot &s : c->slots) drop(s);
   drop(c->ov);
@@ -1933,12 +1961,7 @@ int bbr_read_visibility(bbr_context *c, uint32_t *prim_host, float *depth_host) 
   BBR_ON_DEVICE(c);
   if (!c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_visibility: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_visibility: not available on a partitioned context");
-  int rc = sync_and_fix(c, nullptr);
-  if (rc) return rc;
-  c->dump_vis = true;
-  rc = resubmit_last_frame(c);
-  if (!rc) rc = sync_and_fix(c, nullptr);
-  c->dump_vis = false;
+  int rc = rerender_with(c, &bbr_context::dump_vis);
   if (rc) return rc;
   size_t n = (size_t)c->width * c->height;
   if (prim_host) HIP_TRY(c, hipMemcpy(prim_host, c->d_vis_prim.ptr, n * 4, hipMemcpyDeviceToHost));
@@ -1953,13 +1976,7 @@ int bbr_read_gbuffer(bbr_context *c, float *host) {
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_gbuffer: nothing rendered");
   if (!c->deferred) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_gbuffer: option render_pass is not 1 (deferred)");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_gbuffer: not available with a partition");
-  int rc = sync_and_fix(c, nullptr);
-  if (rc) return rc;
-  // the fused deferred kernel keeps the G-buffer in registers; render the frame once more with the dump enabled
-  c->dump_gbuffer = true;
-  rc = resubmit_last_frame(c);
-  if (rc == BBR_OK) rc = sync_and_fix(c, nullptr);
-  c->dump_gbuffer = false;
+  int rc = rerender_with(c, &bbr_context::dump_gbuffer);  // (the fused deferred kernel keeps the G-buffer in registers)
   if (rc) return rc;
   const size_t n = (size_t)c->width * c->height * 16;
   std::vector<_Float16> h(n);
@@ -1975,13 +1992,7 @@ int bbr_read_surface(bbr_context *c, float *host) {
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface: NULL");
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_surface: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface: not available on a partitioned context");
-  int rc = sync_and_fix(c, nullptr);
-  if (rc) return rc;
-  // nothing of this lives in memory after a frame: render it once more with the dumping instantiation of k_shade_aniso
-  c->dump_surface = true;
-  rc = resubmit_last_frame(c);
-  if (rc == BBR_OK) rc = sync_and_fix(c, nullptr);
-  c->dump_surface = false;
+  int rc = rerender_with(c, &bbr_context::dump_surface);  // (the dumping instantiation of k_shade_aniso)
   if (rc == BBR_OK) {
     const size_t n = (size_t)c->width * c->height * kSurfaceFloats;
     hipError_t e = hipMemcpy(host, c->d_surface.ptr, n * sizeof(float), hipMemcpyDeviceToHost);
@@ -2105,10 +2116,7 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   if (n == "timing") {
     if (value < 0 || value > 2) return fail(c, BBR_ERR_INVALID_ARGUMENT, "timing: 0, 1 or 2");
     c->timing = (int)value;
-    if (value && c->ring.empty()) {  // here, not in the first timed frame: 2560 hipEventCreate calls take half a millisecond
-      c->ring.resize(bbr_context::kRingEvents * bbr_context::kRingCap);
-      for (auto &e : c->ring) HIP_TRY(c, hipEventCreate(&e));
-    }
+    if (value && (rc = ensure_timing_ring(c)) != BBR_OK) return rc;
     c->ring_frames = 0;
     c->present_launches = 0;
     c->timing_tick = 0;
@@ -2163,8 +2171,6 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   } else if (n == "broad_cap" || n == "clip_cap") {
     // starting capacity of the every-tile list / the clip arena (entries); both double when a frame overflows them
     if (value < 1 || value > (1 << 24)) return fail(c, BBR_ERR_INVALID_ARGUMENT, n + " out of range (1 .. 2^24)");
-    int rc = drain(c);
-    if (rc) return rc;
     (n == "broad_cap" ? c->broad_cap : c->clip_cap) = (uint32_t)value;
     for (FrameSlot &s : c->slots) {
       if (n == "broad_cap") s.d_broad.release();
@@ -2205,23 +2211,17 @@ int bbr_present(bbr_context *c, void *rgba8_device, int32_t hdr16) {
   BBR_ON_DEVICE(c);
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "present: nothing rendered");
   FrameSlot &s = c->slots[c->last_slot];
-  const size_t n = c->shard_pixels();
   if (c->present_fused && s.present.active && s.present.out == s.d_present.ptr) {
     // the frame was rendered as presented pixels already (binary16 stage included); a caller buffer gets a copy
     if (!hdr16) return fail(c, BBR_ERR_INVALID_ARGUMENT, "present: option present_fused always applies the binary16 stage");
     s.present.copy_to = rgba8_device;
-    if (rgba8_device) {
-      HIP_TRY(c, hipStreamWaitEvent(c->present_stream(), s.ev_shade_done, 0));
-      HIP_TRY(c, hipMemcpyAsync(rgba8_device, s.d_present.ptr, n * 4, hipMemcpyDeviceToDevice, c->present_stream()));
-      HIP_TRY(c, hipEventRecord(s.ev_shade_done, c->present_stream()));
-    }
-    return BBR_OK;
+    return rgba8_device ? copy_presented(c, s, rgba8_device) : (int)BBR_OK;
   }
-  if (!rgba8_device) HIP_TRY(c, s.d_present.ensure(n));
+  if (!rgba8_device) HIP_TRY(c, s.d_present.ensure(c->shard_pixels()));
   s.present.active = true;
   s.present.out = rgba8_device ? (uint32_t *)rgba8_device : s.d_present.ptr;
-  s.present.enable = s.tone_enable;
-  s.present.exposure = s.tone_exposure;
+  s.present.enable = s.frame_u.enable_tone_mapping;  // of the frame in the slot, not the uniforms set since
+  s.present.exposure = s.frame_u.exposure;
   s.present.hdr16 = hdr16 != 0;
   return queue_present(c, s);
 }
@@ -2483,8 +2483,7 @@ int bbr_allgather_frame(bbr_context *c, int32_t form, void *gathered, void *whol
     whole = s.d_whole.ptr;
   }
   hipStream_t st = stream ? (hipStream_t)stream : s.stream_used;
-  // (also on the slot's own stream: a separate presentation pass may have run on another one and moved the event there)
-  HIP_TRY(c, hipStreamWaitEvent(st, s.ev_shade_done, 0));
+  HIP_TRY(c, s.follow(st));
   uint8_t *mine = (uint8_t *)gathered + block * (size_t)c->rank;
   rc = stage_block(c, s, form, mine, st);
   if (rc) return rc;
@@ -2492,7 +2491,7 @@ int bbr_allgather_frame(bbr_context *c, int32_t form, void *gathered, void *whol
   RCCL_TRY(c, g_rccl.all_gather(mine, gathered, block, ncclUint8, c->comm, st));
   rc = unpack_whole(c, form, gathered, whole, st);
   if (rc) return rc;
-  if (!stream) HIP_TRY(c, hipEventRecord(s.ev_shade_done, st));  // "the frame is done" now includes its exchange
+  if (!stream) HIP_TRY(c, s.busy_until(st));  // ... until its exchange is through
   c->exchange_slot = c->last_slot;
   c->exchange_form = form;
   c->exchange_whole = whole;
@@ -2508,8 +2507,7 @@ int bbr_push_shard(bbr_context *c, int32_t form, void *const *peer_gathered, con
   FrameSlot &s = c->slots[c->last_slot];
   const size_t block = exchange_block_bytes(c, form);
   hipStream_t st = stream ? (hipStream_t)stream : s.stream_used;
-  // (also on the slot's own stream: a separate presentation pass may have run on another one and moved the event there)
-  HIP_TRY(c, hipStreamWaitEvent(st, s.ev_shade_done, 0));
+  HIP_TRY(c, s.follow(st));
   for (int p = 0; p < c->world; ++p)
     if (!peer_gathered[p]) return fail(c, BBR_ERR_INVALID_ARGUMENT, "push_shard: a peer's gather buffer is NULL");
   // the block is made once, in this rank's own gather buffer, and goes from there to the peers
@@ -2554,7 +2552,7 @@ int bbr_push_shard(bbr_context *c, int32_t form, void *const *peer_gathered, con
     }
   }
   c->last_push_direct = direct;
-  if (!stream) HIP_TRY(c, hipEventRecord(s.ev_shade_done, st));
+  if (!stream) HIP_TRY(c, s.busy_until(st));
   return BBR_OK;
 }
 

@@ -104,6 +104,47 @@ def test_gizmo_follows_the_camera_and_overflowing_bins_are_outgrown(maps64):
     r.close()
 
 
+@pytest.fixture(scope="module")
+def near_marker_case(maps64):
+    """the lights of test_markers_behind_geometry_close_to_the_camera_and_without_gizmo at 320 x 180, no gizmo.  The
+    marker of light 2, at (0.02, 0, 0.15) with radius 0.1, reaches through the near plane: the triangles of its near cap
+    are CLIPPED (clip arena), and the ones around them cover most of the screen, i.e. far more than one tile (WIDE: the
+    every-tile list once broad_threshold is 1)"""
+    cfg = configs.C2.scaled(320, 180, 64)
+    sc = scenes.shaderball_scene(cfg, bbo.MaterialData(maps64))
+    sc.frame = scenes.frame_uniforms([scenes.light(0, pos=(0.0, -0.5, 2.0), color=(1, 0, 0), intensity=5.0),
+                                      scenes.light(0, pos=(0.3, 0.1, 1.0), color=(0, 1, 0), intensity=5.0),
+                                      scenes.light(0, pos=(0.02, 0.0, 0.15), color=(0.2, 0.3, 1), intensity=5.0),
+                                      scenes.light(0, pos=(0.0, 0.0, -3.0), color=(1, 1, 0), intensity=5.0),
+                                      scenes.light(2, dir=(0, -1, 0), color=(0.5, 0.5, 0.5), intensity=1.0)])
+    hdr, _, depth, _ = bbo.render(sc)
+    base = bbo.present(hdr, 0, 1.0)
+    want, st = bbo.overlay(sc.frame, sc.view, depth, base, None, None, 0)
+    assert st["n_clipped_prims"] > 0
+    return sc, base, want
+
+
+@pytest.mark.parametrize("tile_mode", [0, 1])
+@pytest.mark.parametrize("caps", [{"clip_cap": 1}, {"broad_cap": 1, "broad_threshold": 1}], ids=["clip_cap", "broad_cap"])
+def test_overlay_pass_outgrows_the_clip_arena_and_the_every_tile_list(near_marker_case, tile_mode, caps):
+    """the overlay pass sizes its own buffers: a clip arena / every-tile list of one entry is outgrown by the pass itself
+    (the capacities are set once the frame is on the screen, so the growth can only be the overlay pass's)"""
+    sc, base, want = near_marker_case
+    r = Renderer(sc.width, sc.height)
+    r.set_option("tile_mode", tile_mode)
+    r.set_option("overlays", 1)
+    r.render_scene(sc)
+    r.present()
+    assert np.array_equal(r.read_presented(), base)
+    for k, v in caps.items():
+        r.set_option(k, v)
+    before = r.capacity_growths()
+    r.draw_overlays(0)
+    assert r.capacity_growths() > before
+    assert np.array_equal(r.read_presented(), want)
+    r.close()
+
+
 def test_error_paths(maps64):
     cfg = configs.C2.scaled(128, 96, 64)
     sc = scenes.shaderball_scene(cfg, bbo.MaterialData(maps64))

@@ -517,31 +517,59 @@ def test_present_after_an_overflow_replay_and_into_a_caller_buffer(maps64, item_
 
 
 def test_diagnostic_reads_keep_the_presented_image(maps64):
-    """bbr_read_visibility / bbr_read_gbuffer render the frame once more: the slot's presentation state must survive it
-    (bbr_read_presented afterwards, and a caller's presented buffer refreshed with the same pixels)."""
+    """bbr_read_visibility / bbr_read_gbuffer / bbr_read_surface render the frame once more: the slot's presentation state
+    must survive it (bbr_read_presented afterwards, and a caller's presented buffer refreshed with the same pixels) -- with
+    a separate presentation pass into the caller's tensor, and with option present_fused, where bbr_present copied the
+    slot's image there."""
     import torch
     sc = scenes.shaderball_scene(configs.C2.scaled(256, 144, 64), bbo.MaterialData(maps64))
     sc.frame["enable_tone_mapping"], sc.frame["exposure"] = 1, 1.5
     ref, rprim, _, _ = bbo.render(sc)
-    want = bbo.present(ref, 1, 1.5)
-    for deferred in (0, 1):
-        r = Renderer(sc.width, sc.height)
-        r.set_option("render_pass", deferred)
-        out = torch.zeros((sc.height, sc.width, 4), dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()
-        r.render_scene(sc)
-        r.present(out.data_ptr())
-        prim, _ = r.read_visibility()
-        if deferred:
-            r.read_gbuffer()
-        else:
-            assert np.array_equal(prim, rprim)
-            assert np.array_equal(r.read_presented(), want)
+    want = {0: bbo.present(ref, 1, 1.5), 1: bbo.present(bbo.render_deferred(sc)[0], 1, 1.5)}
+    for fused in (0, 1):
+        for deferred in (0, 1):
+            r = Renderer(sc.width, sc.height)
+            r.set_option("render_pass", deferred)
+            r.set_option("present_fused", fused)
+            out = torch.zeros((sc.height, sc.width, 4), dtype=torch.uint8, device="cuda")
             torch.cuda.synchronize()
-            assert np.array_equal(out.cpu().numpy(), want)
-        first = r.read_presented()
-        assert np.array_equal(first, r.read_presented())
-        r.close()
+            r.render_scene(sc)
+            r.present(out.data_ptr())
+            for read in ["visibility"] + (["gbuffer"] if deferred else []) + ["surface"]:
+                got = getattr(r, "read_" + read)()
+                if read == "visibility" and not deferred:
+                    assert np.array_equal(got[0], rprim)
+                assert np.array_equal(r.read_presented(), want[deferred]), (fused, deferred, read)
+                torch.cuda.synchronize()
+                assert np.array_equal(out.cpu().numpy(), want[deferred]), (fused, deferred, read)
+            first = r.read_presented()
+            assert np.array_equal(first, r.read_presented())
+            r.close()
+
+
+def test_present_uses_the_tone_mapping_of_the_frame_in_the_slot(maps64):
+    """bbr_present tone-maps with the uniforms the frame in the slot was rendered with, not with the ones set since: a
+    frame at exposure 1.5, then bbr_set_frame_uniforms with 0.5 and nothing submitted -- in the first slot, and again after
+    the frame was replayed into the other one (two frames in flight)."""
+    sc = scenes.shaderball_scene(configs.C2.scaled(256, 144, 64), bbo.MaterialData(maps64))
+    sc.frame["enable_tone_mapping"], sc.frame["exposure"] = 1, 1.5
+    ref, _, _, _ = bbo.render(sc)
+    want = bbo.present(ref, 1, 1.5)
+    later = sc.frame.copy()
+    later["exposure"] = 0.5
+    assert not np.array_equal(bbo.present(ref, 1, 0.5), want)
+    r = Renderer(sc.width, sc.height)
+    r.set_option("frames_in_flight", 2)
+    r.render_scene(sc)
+    r.synchronize()                                      # (capacities sized: nothing below renders a frame again)
+    for slot in (0, 1):
+        if slot == 1:
+            r.set_frame_uniforms(sc.frame)
+            r.replay_frame()                             # the same frame, in the other slot
+        r.set_frame_uniforms(later)
+        r.present()
+        assert np.array_equal(r.read_presented(), want), slot
+    r.close()
 
 
 def test_api_lifecycle_user_stream_frees_and_timing(maps64):
@@ -714,6 +742,26 @@ def test_resize_keeps_resources_and_renders_the_new_extent_exactly(maps64):
     with pytest.raises(BibimError):
         r.resize(0, 64)
     r.resize(320, 180)                                   # same extent: a no-op apart from the wait
+    r.close()
+
+
+def test_resize_then_long_route_frames_with_heavy_tiles_first(maps64):
+    """the pinned words a resize leaves alone -- the heavy-tile count of the slot's last frame at the old extent among them
+    -- size the first launches at the new extent: heavy rows for a list of another tile grid.  One frame in flight, long
+    route, heavy tiles first; every frame at the new extent is the oracle's, bit for bit."""
+    mat = bbo.MaterialData(maps64)
+    r = Renderer(320, 180)
+    for k, v in (("no_tail_items", 0), ("heavy_tiles", 4), ("frames_in_flight", 1)):
+        r.set_option(k, v)
+    before = scenes.shaderball_scene(configs.C3.scaled(320, 180, 64), mat)
+    h = r.render_scene(before)
+    assert np.array_equal(r.read_framebuffer().view(np.uint32), bbo.render(before)[0].view(np.uint32))
+    r.resize(200, 300)
+    after = scenes.shaderball_scene(configs.C3.scaled(200, 300, 64), mat)
+    ref = bbo.render(after)[0]
+    for i in range(3):
+        h = r.render_scene(after, h)
+        assert np.array_equal(r.read_framebuffer().view(np.uint32), ref.view(np.uint32)), f"frame {i} after the resize"
     r.close()
 
 
