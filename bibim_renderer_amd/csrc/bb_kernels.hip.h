@@ -1056,6 +1056,40 @@ BB_DEV int tile_index(int x, int y) {
   return (((y >> 3) * BX + (x >> 3)) << 6) | ((y & 7) << 3) | (x & 7);
 }
 
+// The nine words coverage and depth need of a triangle: the first 36 bytes of a RasterTri (bb_types.h) and of an
+// every-tile-list entry, a column of k_raster's StagedTri.  Vertices in 24.8 fixed point, the depth plane relative to vertex 0.
+struct TriCore {
+  int X0, Y0, X1, Y1, X2, Y2;
+  float z0, dzdx, dzdy;
+};
+BB_DEV TriCore tri_core(const RasterTri &t) { return TriCore{t.X0, t.Y0, t.X1, t.Y1, t.X2, t.Y2, t.z0, t.dzdx, t.dzdy}; }
+// Pixels [x0, x1] x [y0, y1], both ends included: a tile, the frame, the gizmo's scissor, a triangle's box; and what two share.
+struct PixRect {
+  int x0, x1, y0, y1;
+  BB_DEV bool any() const { return x0 <= x1 && y0 <= y1; }
+};
+BB_DEV PixRect intersect(const PixRect &a, const PixRect &b) { return PixRect{max(a.x0, b.x0), min(a.x1, b.x1), max(a.y0, b.y0), min(a.y1, b.y1)}; }
+// the larger side of a triangle's bounding box, in 1/256 pixel
+BB_DEV int tri_span(const TriCore &t) { return max(max(t.X0, max(t.X1, t.X2)) - min(t.X0, min(t.X1, t.X2)), max(t.Y0, max(t.Y1, t.Y2)) - min(t.Y0, min(t.Y1, t.Y2))); }
+// The pixels whose CENTRES lie inside a triangle's bounding box and inside rectangles `a` and `b`, clamped in this order.
+BB_DEV PixRect pixel_box(const TriCore &t, const PixRect &a, const PixRect &b) {
+  const int32_t minX = min(t.X0, min(t.X1, t.X2)), maxX = max(t.X0, max(t.X1, t.X2));
+  const int32_t minY = min(t.Y0, min(t.Y1, t.Y2)), maxY = max(t.Y0, max(t.Y1, t.Y2));
+  return PixRect{max(max((minX - 128 + 255) >> 8, a.x0), b.x0), min(min((maxX - 128) >> 8, a.x1), b.x1),
+                 max(max((minY - 128 + 255) >> 8, a.y0), b.y0), min(min((maxY - 128) >> 8, a.y1), b.y1)};
+}
+BB_DEV PixRect pixel_box(const TriCore &t, const PixRect &r) { return pixel_box(t, r, r); }
+
+// overlay pass: primitives from fp.ov_first_gizmo_prim on are the gizmo -- scissored to its rectangle (src/main.cpp:767-772)
+// and lifted above every other depth (see depth_max); `ref` is a bin reference (primitive << 3 | sub-triangle)
+template <bool OVERLAY>
+BB_DEV bool gizmo_ref(const FrameParams &fp, uint32_t ref) { return OVERLAY && (ref >> 3) >= fp.ov_first_gizmo_prim; }
+// the scissor rectangle of a primitive: the gizmo's own, no scissor (every pixel a frame can have) for everything else
+template <bool OVERLAY>
+BB_DEV PixRect scissor_rect(const FrameParams &fp, uint32_t ref) {
+  return gizmo_ref<OVERLAY>(fp, ref) ? PixRect{fp.ov_x0, fp.ov_x1 - 1, fp.ov_y0, fp.ov_y1 - 1} : PixRect{0, (1 << 30) - 1, 0, (1 << 30) - 1};
+}
+
 // A triangle against a rectangle of pixel centres [x0,x1] x [y0,y1]: 0 = no centre covered, 1 = some, 2 = all.
 // Edge functions are affine, so their extrema over the rectangle sit at corners picked by the gradient signs.
 struct EdgeSetup {
@@ -1063,7 +1097,7 @@ struct EdgeSetup {
   int X[3], Y[3];
 };
 
-BB_DEV EdgeSetup edge_setup(const RasterTri &t) {
+BB_DEV EdgeSetup edge_setup(const TriCore &t) {
   EdgeSetup e;
   e.X[0] = t.X0; e.Y[0] = t.Y0; e.X[1] = t.X1; e.Y[1] = t.Y1; e.X[2] = t.X2; e.Y[2] = t.Y2;
   e.dx[0] = t.X1 - t.X0; e.dy[0] = t.Y1 - t.Y0;  // |coordinates| < 2^30 (project_vertex), differences fit 32 bits
@@ -1080,7 +1114,8 @@ BB_DEV long long edge_eval(const EdgeSetup &e, int i, int px, int py) {
   return (long long)e.dx[i] * (long long)(Yc - e.Y[i]) - (long long)e.dy[i] * (long long)(Xc - e.X[i]) + (long long)e.bias[i];
 }
 
-BB_DEV int classify_rect(const EdgeSetup &e, int x0, int x1, int y0, int y1) {
+BB_DEV int classify_rect(const EdgeSetup &e, const PixRect &b) {
+  const int x0 = b.x0, x1 = b.x1, y0 = b.y0, y1 = b.y1;
   bool all_in = true;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -1096,7 +1131,7 @@ BB_DEV int classify_rect(const EdgeSetup &e, int x0, int x1, int y0, int y1) {
 // zbias (overlay pass only): added to the depth BITS of the key, order-preserving -- 0x40000000 lifts the gizmo's
 // fragments above every depth in [0, 1] drawn before (the reference clears the rectangle's depth before the gizmo)
 // while they still compete among themselves by depth.
-BB_DEV void depth_max(const RasterTri &t, int px, int py, uint32_t ref, unsigned long long *keys, int key_index,
+BB_DEV void depth_max(const TriCore &t, int px, int py, uint32_t ref, unsigned long long *keys, int key_index,
                       uint32_t zbias = 0u) {
   int Xc = px * 256 + 128, Yc = py * 256 + 128;
   float dxp = (float)(Xc - t.X0), dyp = (float)(Yc - t.Y0);
@@ -1110,21 +1145,17 @@ BB_DEV void depth_max(const RasterTri &t, int px, int py, uint32_t ref, unsigned
 // One wave rasterises one (wave-uniform) triangle into the tile's LDS keys: 8x8 pixel blocks of bounding box ^ tile,
 // one pixel per lane.  Rectangles fully inside the triangle skip the edge tests.  Triangles spanning <= 64 px use
 // 32-bit edge functions stepped with 24-bit multiply-adds (exact: every term < 2^30); larger ones use 64-bit products.
+// `clip`: the frame's pixels (the gizmo's: inside its scissor rectangle)
 template <int TILE_W, int TILE_H>
-BB_DEV void raster_triangle_wave(const RasterTri &t, uint32_t ref, int tile_x0, int tile_y0, const FrameParams &fp,
-                                 unsigned long long *keys, int lane, uint32_t zbias = 0u, int sx0 = 0, int sy0 = 0,
-                                 int sx1 = 1 << 30, int sy1 = 1 << 30) {
-  int32_t minX = min(t.X0, min(t.X1, t.X2)), maxX = max(t.X0, max(t.X1, t.X2));
-  int32_t minY = min(t.Y0, min(t.Y1, t.Y2)), maxY = max(t.Y0, max(t.Y1, t.Y2));
-  int px0 = max(max((minX - 128 + 255) >> 8, sx0), tile_x0);
-  int px1 = min(min((maxX - 128) >> 8, min(fp.width, sx1) - 1), tile_x0 + TILE_W - 1);
-  int py0 = max(max((minY - 128 + 255) >> 8, sy0), tile_y0);
-  int py1 = min(min((maxY - 128) >> 8, min(fp.height, sy1) - 1), tile_y0 + TILE_H - 1);
-  if (px0 > px1 || py0 > py1) return;
+BB_DEV void raster_triangle_wave(const TriCore &t, uint32_t ref, const PixRect &clip, int tile_x0, int tile_y0,
+                                 unsigned long long *keys, int lane, uint32_t zbias) {
+  const PixRect box = pixel_box(t, clip, PixRect{tile_x0, tile_x0 + TILE_W - 1, tile_y0, tile_y0 + TILE_H - 1});
+  if (!box.any()) return;
+  const int px0 = box.x0, px1 = box.x1, py0 = box.y0, py1 = box.y1;
   const EdgeSetup e = edge_setup(t);
   const int w = px1 - px0 + 1, h = py1 - py0 + 1;
   const int lx = lane & 7, ly = lane >> 3;
-  if (max(maxX - minX, maxY - minY) <= (1 << 14)) {
+  if (tri_span(t) <= (1 << 14)) {
     const int Xc0 = px0 * 256 + 128, Yc0 = py0 * 256 + 128;
     int o[3], sx[3], sy[3];
     bool none = false, all = true;
@@ -1154,7 +1185,7 @@ BB_DEV void raster_triangle_wave(const RasterTri &t, uint32_t ref, int tile_x0, 
     }
     return;
   }
-  const int cls = classify_rect(e, px0, px1, py0, py1);
+  const int cls = classify_rect(e, box);
   if (cls == 0) return;
   for (int by = 0; by < h; by += 8) {
     for (int bx = 0; bx < w; bx += 8) {
@@ -1187,9 +1218,11 @@ constexpr int kTileWaves = kTileThreads / 64;
 // Same values as the 64-bit form (edge_eval) at every pixel centre: E' = E + (top-left ? 0 : -1), covered <=> all E' >= 0.
 // The depth is depth_max's expression with its row-constant half hoisted: z = fma(dzdx, dxp, fma(dzdy, dyp, z0)), and
 // dxp = float(Xc - X0) is stepped by 256.0f (exact: |Xc - X0| <= 2^14 + 2^8 inside the bounding box).
-template <int TILE_W, int TILE_H>
-BB_DEV void raster_triangle_row(int X0, int Y0, int X1, int Y1, int X2, int Y2, float z0, float dzdx, float dzdy, uint32_t ref,
-                                int px0, int px1, int py, int tile_x0, int tile_y0, unsigned long long *keys, uint32_t zbias) {
+template <int TILE_W>
+BB_DEV void raster_triangle_row(const TriCore &t, uint32_t ref, int px0, int px1, int py, int tile_x0, int tile_y0,
+                                unsigned long long *keys, uint32_t zbias) {
+  const int X0 = t.X0, Y0 = t.Y0, X1 = t.X1, Y1 = t.Y1, X2 = t.X2, Y2 = t.Y2;
+  const float z0 = t.z0, dzdx = t.dzdx, dzdy = t.dzdy;
   const int dx0 = X1 - X0, dy0 = Y1 - Y0;
   const int dx1 = X2 - X1, dy1 = Y2 - Y1;
   const int dx2 = X0 - X2, dy2 = Y0 - Y2;
@@ -1233,6 +1266,51 @@ BB_DEV bool tile_row(const FrameParams &fp, int grid_y, int &ty, int &out_tile_r
   return ty < fp.tiles_y;
 }
 
+// ---- The two words k_raster hands to the fragment kernels, each with its encoder next to its decoder ----
+// item = full-tile flag (kFullTile, or 0) | grid row << 18 | tile column << 6 | chunk of 64 fragments
+BB_DEV uint32_t item_word(uint32_t full, uint32_t grid_row, uint32_t tx, uint32_t chunk) { return full | (grid_row << (kItemChunkBits + kItemTxBits)) | (tx << kItemChunkBits) | chunk; }
+// one work item: where its 64 fragments are (all wave-uniform, held in scalar registers)
+struct ItemPlace {
+  int chunk, tx, ty, out_tile_row;
+  uint32_t tile;
+};
+BB_DEV ItemPlace decode_item(const FrameParams &fp, uint32_t item) {
+  ItemPlace p;
+  p.chunk = (int)(item & 63u);
+  p.tx = (int)((item >> kItemChunkBits) & ((1u << kItemTxBits) - 1u));
+  tile_row(fp, (int)((item & ~kFullTile) >> (kItemChunkBits + kItemTxBits)), p.ty, p.out_tile_row);
+  p.tile = (uint32_t)p.ty * (uint32_t)fp.tiles_x + (uint32_t)p.tx;
+  return p;
+}
+
+// fragment = ((clip slot + 1) << kFragPixBits | pixel in tile) << 32 | reference
+BB_DEV unsigned long long fragment_word(uint32_t clip_slot1, uint32_t pixel, uint32_t ref) {
+  return ((((unsigned long long)clip_slot1 << kFragPixBits) | (unsigned long long)pixel) << 32) | (unsigned long long)ref;
+}
+template <int TILE_PIXELS>
+BB_DEV int fragment_pixel(unsigned long long frag) { return (int)(frag >> 32) & (TILE_PIXELS - 1); }
+// (the clip slot + 1 is read in place, `frag >> (32 + kFragPixBits)`: k_shade compiled to other code with a helper here)
+
+// this lane's fragment word of an item, and whether the lane has one.  A tile one triangle covers completely has no list and
+// no count: one word, the pixel is the lane's own (and the wave is uniform).  CONST_WORD: that word comes through the scalar
+// cache (constant address space).
+template <int TILE_PIXELS, bool CONST_WORD>
+BB_DEV unsigned long long fetch_fragment(uint32_t item, const ItemPlace &p, int lane, const unsigned long long *__restrict__ frags,
+                                         const uint32_t *__restrict__ frag_count, bool &valid) {
+  typedef const unsigned long long __attribute__((address_space(4))) *ConstFrags;
+  unsigned long long frag;
+  if (item & kFullTile) {
+    frag = (CONST_WORD ? ((ConstFrags)frags)[(size_t)p.tile * TILE_PIXELS] : frags[(size_t)p.tile * TILE_PIXELS]) +
+           ((unsigned long long)((uint32_t)p.chunk * 64u + (uint32_t)lane) << 32);
+    valid = true;
+  } else {
+    const uint32_t n_frag = frag_count[p.tile];
+    valid = (uint32_t)p.chunk * 64u + (uint32_t)lane < n_frag;
+    frag = frags[(size_t)p.tile * TILE_PIXELS + (uint32_t)p.chunk * 64u + (uint32_t)lane];
+  }
+  return frag;
+}
+
 // ------------------------------------------------------------------------------------------------
 // k_raster: one workgroup per screen tile.  LDS-resident 64-bit keys (depth bits << 32 | primitive) filled with
 // ds_max_u64 -- depth op GREATER_OR_EQUAL with "later primitive wins ties" falls out of the key order -- then
@@ -1252,15 +1330,11 @@ struct StagedTri {  // struct-of-arrays in LDS: thread j owns column j when fill
   float z0[kStage], dzdx[kStage], dzdy[kStage];
   uint32_t ref[kStage];
   uint32_t box[kStage];  // px0 | px1 << 8 | py0 << 16 | py1 << 24 relative to the tile; 0xFFFFFFFF = skip
+  BB_DEV void store(int j, const TriCore &t) {
+    X0[j] = t.X0; Y0[j] = t.Y0; X1[j] = t.X1; Y1[j] = t.Y1; X2[j] = t.X2; Y2[j] = t.Y2; z0[j] = t.z0; dzdx[j] = t.dzdx; dzdy[j] = t.dzdy;
+  }
+  BB_DEV TriCore load(int j) const { return TriCore{X0[j], Y0[j], X1[j], Y1[j], X2[j], Y2[j], z0[j], dzdx[j], dzdy[j]}; }
 };
-
-BB_DEV RasterTri staged_tri(const StagedTri &st, int j) {
-  RasterTri t;
-  t.X0 = st.X0[j]; t.Y0 = st.Y0[j]; t.X1 = st.X1[j]; t.Y1 = st.Y1[j]; t.X2 = st.X2[j]; t.Y2 = st.Y2[j];
-  t.z0 = st.z0[j]; t.dzdx = st.dzdx[j]; t.dzdy = st.dzdy[j];
-  t.l1dx = t.l1dy = t.l2dx = t.l2dy = t.rw0 = t.rw1 = t.rw2 = 0.0f;  // not needed for coverage / depth
-  return t;
-}
 
 // One light as the loop consumes it: 48 bytes, written once per frame by cook_light.
 struct CookedLight {
@@ -1294,15 +1368,101 @@ BB_DEV CookedLight cook_light(const Light &l) {
   return c;
 }
 
+// the frame's (or a workgroup's) light table: every thread of the workgroup calls this
+template <int THREADS>
+BB_DEV void cook_lights(const Light *lights, int n, CookedLight *cooked) {
+  for (int li = (int)threadIdx.x; li < n; li += THREADS) cooked[li] = cook_light(lights[li]);
+}
+
+// ---- k_raster's phases that are functions (forced inline); why the others are blocks of its body: profiles/r10_raster_phases.txt ----
+// SHORT FRAMES: a tile's items go to the frame's list.  In: its chunks of 64 fragments, the full-tile flag.  Out: items[].
+// (called by the first wave of the workgroup, all of its lanes; short frames have no heavy rows: blockIdx is the tile's launch slot)
+BB_DEV void append_items(uint32_t *item_head, uint32_t *items, int lane, uint32_t chunks, uint32_t flag) {
+  uint32_t at = 0u;
+  if (lane == 0) at = atomicAdd(item_head, chunks);
+  at = (uint32_t)__shfl((int)at, 0);
+  if ((uint32_t)lane < chunks) items[1u + at + (uint32_t)lane] = item_word(flag, blockIdx.y, blockIdx.x, (uint32_t)lane);
+}
+// overlay pass: the gizmo's fragments are lifted above every other depth (see depth_max); 0 everywhere else
+template <bool OVERLAY>
+BB_DEV uint32_t zbias_of(const FrameParams &fp, uint32_t ref) { return gizmo_ref<OVERLAY>(fp, ref) ? 0x40000000u : 0u; }
+
+// The tile a workgroup of k_raster rasterises.
+struct RasterTile {
+  int tx, ty;
+  uint32_t tile;  // ty * fp.tiles_x + tx
+  int x0, y0;     // its first pixel in the frame
+  int out_y0;     // the row of that pixel in this rank's output
+  PixRect rect;   // its pixels inside the frame
+};
+
+// CLEAR.  Out: keys = 0; overlay pass: the depth the scene left behind, low word 0 = "no overlay primitive here".
+template <int TILE_W, int TILE_H, bool OVERLAY>
+BB_DEV void clear_keys(unsigned long long *keys, const RasterTile &tg, const FrameParams &fp, const float *depth_io, int tid) {
+  for (int p = tid; p < TILE_W * TILE_H; p += kTileThreads) {
+    unsigned long long k0 = 0ull;
+    if (OVERLAY) {  // depth test against what the scene left behind; low word 0 = "no overlay primitive here"
+      int x, y;
+      tile_pixel<TILE_W>(p, x, y);
+      const int gx = tg.x0 + x, gy = tg.y0 + y;
+      if (gx < fp.width && gy < fp.height)
+        k0 = (unsigned long long)__float_as_uint(depth_io[(size_t)gy * (size_t)fp.width + (size_t)gx]) << 32;
+    }
+    keys[p] = k0;
+  }
+}
+
+// LARGE TRIANGLES (class 2 and the every-tile list): one wave per triangle.  In: entries [lo, hi) of the staged chunk that
+// begins at entry `base`.  Out: keys.
+template <int TILE_W, int TILE_H, bool OVERLAY>
+BB_DEV void raster_large(const StagedTri &st, uint32_t lo, uint32_t hi, uint32_t base, const RasterTile &tg, const FrameParams &fp,
+                         unsigned long long *keys, int lane, int wave) {
+  for (uint32_t e = lo + (uint32_t)wave; e < hi; e += kTileWaves) {
+    const int j = __builtin_amdgcn_readfirstlane((int)(e - base));
+    if (st.box[j] == 0xFFFFFFFFu) continue;
+    const TriCore t = st.load(j);
+    const uint32_t ref = st.ref[j];
+    // (frame and scissor first, the whole tile second: the order the clamps always had here)
+    raster_triangle_wave<TILE_W, TILE_H>(t, ref, intersect(PixRect{0, fp.width - 1, 0, fp.height - 1}, scissor_rect<OVERLAY>(fp, ref)), tg.x0,
+                                         tg.y0, keys, lane, zbias_of<OVERLAY>(fp, ref));
+  }
+}
+
+// A tile's entries in the order they are rasterised: class 0 | class 1 | class 2 | every-tile list.
+struct TileEntries {
+  uint32_t e1, e2, e3, e_end;  // where class 1, class 2, the every-tile list and the end begin
+  const uint32_t *bin0;        // the tile's three bins, bin_cap references each
+  uint32_t bin_cap;
+  BB_DEV uint32_t fetch_ref(uint32_t e) const {  // bin reference of entry e (0 for the every-tile list and past the end)
+    if (e >= e3) return 0u;
+    const uint32_t c = e < e1 ? 0u : (e < e2 ? 1u : 2u);
+    const uint32_t i = e - (c == 0u ? 0u : (c == 1u ? e1 : e2));
+    return bin0[(size_t)c * bin_cap + i];
+  }
+};
+struct Fetched {  // what the staging keeps of an entry
+  TriCore core;
+  uint32_t ref, clip_slot1;
+};
+BB_DEV Fetched fetch_tri(const TileEntries &en, uint32_t e, uint32_t ref, const RasterTri *tris, const BroadTri *broad_list) {
+  Fetched f = {};
+  if (e >= en.e_end) return f;
+  const RasterTri *t = e < en.e3 ? &tris[ref >> 3] : &broad_list[e - en.e3].tri;  // binned triangles are never clipped
+  f.core = tri_core(*t);
+  f.ref = ref;
+  if (e >= en.e3) {
+    f.ref = broad_list[e - en.e3].ref;
+    f.clip_slot1 = broad_list[e - en.e3].pad[0];
+  }
+  return f;
+}
+
 // OVERLAY = true (overlay subpass): the keys start from the scene's resolved depth (`depth_io`, read) instead of 0,
 // gizmo primitives are scissored to their rectangle and biased above everything else, pixels no overlay primitive
 // wins are left alone (no background fill).  OVERLAY = false with depth_io != nullptr stores the resolved depth.
 #ifndef BB_RASTER_WAVES
 #define BB_RASTER_WAVES 8  // waves per SIMD the 32 x 32 instantiation is compiled for (64 registers; 20.3 KB of LDS allow eight
                            // workgroups per CU).  64 x 64 tiles hold 32 KB of keys: three.
-#endif
-#ifndef BB_RASTER_PREFETCH
-#define BB_RASTER_PREFETCH 1
 #endif
 template <int TILE_W, int TILE_H, bool OVERLAY = false>
 __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TILE_W > 32 ? 3 : (OVERLAY ? 7 : BB_RASTER_WAVES)))) void k_raster(
@@ -1318,15 +1478,23 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
     uint32_t *__restrict__ items, const Light *__restrict__ lights, int num_lights, CookedLight *__restrict__ cooked,
     const uint32_t *__restrict__ heavy) {
   constexpr int TILE_PIXELS = TILE_W * TILE_H;
-  __shared__ unsigned long long keys[TILE_PIXELS];
-  __shared__ StagedTri st;
-  __shared__ uint32_t s_count;
+  // ---- the workgroup's LDS ----
+  __shared__ unsigned long long keys[TILE_PIXELS];  // depth bits << 32 | reference + 1; 0: nothing drawn
+  __shared__ StagedTri st;                          // the chunk being rasterised
+  __shared__ uint32_t s_count;                      // the tile's fragments
   // the row list of the chunk's small triangles (see the chunk loop)
   __shared__ uint16_t s_row0[kStage];          // first row of staged entry j in its wave's list
-  __shared__ uint32_t s_wave_rows[kTileWaves];  // rows in each wave's list
+  __shared__ uint32_t s_wave_rows[kTileWaves];  // rows in each wave's list (compaction: covered pixels of each wave)
+  // Clipped sub-triangles that touch this tile: (reference, clip-arena slot + 1).  The slot goes into the fragment word,
+  // so that k_shade can fetch the sub-triangle's planes together with the primitive record instead of after it.
+  // More than kClipRefs of them: the field stays 0 and k_shade finds the slot through the record (one more round trip).
+  constexpr uint32_t kClipRefs = 32;
+  __shared__ uint32_t s_clip_ref[kClipRefs], s_clip_slot[kClipRefs], s_n_clip_refs;
+  __shared__ unsigned long long s_pad_frag;  // the fragment list's first word
 
   __builtin_amdgcn_s_setprio(3);  // (as k_geometry: a latency-bound wave's instruction goes out when it is ready)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // ---- pinned flag words.  In: the frame's counters.  Out: host_flags[] ----
   // This frame's pinned flag words (HostFlagWord, bb_types.h) straight into pinned host memory (final since k_geometry
   // ended): the host looks at them when it reuses the frame's slot -- a few stores instead of a copy kernel on the stream.
   // (kFlagItemCount, the frame's shade item count, is stored by k_shade_items.)
@@ -1337,6 +1505,7 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
     host_flags[kFlagClipNeed] = ctr->n_clip_slots;
     host_flags[kFlagHeavyTiles] = ctr->n_heavy;   // sizes the heavy rows of this slot's next frame
   }
+  // ---- short frames: the light table.  In: lights[].  Out: cooked[] ----
   // SHORT FRAMES (item_head != nullptr; the host decides by the frame's tile count): there is no k_shade_items launch.  The
   // tiles append their items to the frame's list themselves -- one returning atomic per tile on the list's head word, which
   // the frame's staging copy has zeroed -- and this kernel's first workgroup cooks the light table.  A 1080p frame is a
@@ -1344,17 +1513,10 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
   // 9 of its 90 us.  The list is then in tile COMPLETION order, not screen order: at 4K that cost 13 % more texel traffic
   // than it saved (round 2), which is why long frames keep k_shade_items.
   if (item_head && cooked && blockIdx.x == 0 && blockIdx.y == 0)
-    for (int li = tid; li < num_lights; li += kTileThreads) cooked[li] = cook_light(lights[li]);
-  // (called by the first wave of the workgroup, all of its lanes)
-  auto append_items = [&](uint32_t chunks, uint32_t flag) {
-    uint32_t at = 0u;
-    if (lane == 0) at = atomicAdd(item_head, chunks);
-    at = (uint32_t)__shfl((int)at, 0);
-    if ((uint32_t)lane < chunks)
-      items[1u + at + (uint32_t)lane] = flag | ((uint32_t)blockIdx.y << (kItemChunkBits + kItemTxBits)) | ((uint32_t)blockIdx.x << kItemChunkBits) | (uint32_t)lane;
-  };  // (short frames only: they have no heavy rows, blockIdx is the tile's launch slot)
+    cook_lights<kTileThreads>(lights, num_lights, cooked);
   static_assert(TILE_PIXELS / 64 <= 64, "a tile's items are written by one wave");
-  // launch slot -> tile: plain row order ...
+  // ---- launch slot -> tile.  In: blockIdx, the heavy list.  Out: slot, heavy_slot / heavy_class, tg; or the workgroup leaves ----
+  // plain row order ...
   uint32_t slot = blockIdx.y * gridDim.x + blockIdx.x;
   // ... behind fp.heavy_rows rows of HEAVY SLOTS (long frames only).  A tile's life is 1.6 us when nothing is binned to it and
   // 14-39 us when a ball is; in plain screen order the last heavy tile starts when the kernel's work is half done and the
@@ -1384,23 +1546,17 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
   int ty, out_tile_row;
   const bool live = tile_row(fp, grid_row, ty, out_tile_row);
   if (!live) return;
-  const uint32_t tile = (uint32_t)ty * (uint32_t)fp.tiles_x + (uint32_t)tx;
+  const int tile_x0 = tx * TILE_W, tile_y0 = ty * TILE_H;
+  const RasterTile tg = {tx, ty, (uint32_t)ty * (uint32_t)fp.tiles_x + (uint32_t)tx, tile_x0, tile_y0, out_tile_row * TILE_H,
+                         PixRect{tile_x0, min(tile_x0 + TILE_W, fp.width) - 1, tile_y0, min(tile_y0 + TILE_H, fp.height) - 1}};
 #ifdef BB_STAMPS
-#define BB_RSTAMP(i) do { if (tid == 0) reinterpret_cast<unsigned long long *>(frag_count + fp.tiles_x * fp.tiles_y)[tile * 8 + (i)] = wall_clock64(); } while (0)
+#define BB_RSTAMP(i) do { if (tid == 0) reinterpret_cast<unsigned long long *>(frag_count + fp.tiles_x * fp.tiles_y)[tg.tile * 8 + (i)] = wall_clock64(); } while (0)
 #else
 #define BB_RSTAMP(i) do { } while (0)
 #endif
   BB_RSTAMP(0);
-  const int tile_x0 = tx * TILE_W, tile_y0 = ty * TILE_H;
-  const int out_y0 = out_tile_row * TILE_H;
-  const int rx1 = min(tile_x0 + TILE_W, fp.width) - 1, ry1 = min(tile_y0 + TILE_H, fp.height) - 1;
 
-  // Clipped sub-triangles that touch this tile: (reference, clip-arena slot + 1).  The slot goes into the fragment word,
-  // so that k_shade can fetch the sub-triangle's planes together with the primitive record instead of after it.
-  // More than kClipRefs of them: the field stays 0 and k_shade finds the slot through the record (one more round trip).
-  constexpr uint32_t kClipRefs = 32;
-  __shared__ uint32_t s_clip_ref[kClipRefs], s_clip_slot[kClipRefs], s_n_clip_refs;
-  __shared__ unsigned long long s_pad_frag;
+  // ---- the tile's counts.  In: tile_count[], ctr.  Out: n_cls[], n_broad; or the workgroup leaves (a heavy slot does the tile) ----
   // The tile's bin counts: every thread reads them itself (uniform address: one line), decides with them, and only AFTER
   // the workgroup's first barrier are they cleared for the slot's next frame -- a wave arrives at that barrier with its
   // loads returned, so no wave, however late it started, can see the cleared value.  (Cleared right after the read, a
@@ -1410,7 +1566,7 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
   bool at_threshold[kBinClasses];
 #pragma unroll
   for (uint32_t c = 0; c < kBinClasses; ++c) {
-    const uint32_t raw = tile_count[tile * kBinClasses + c];
+    const uint32_t raw = tile_count[tg.tile * kBinClasses + c];
     at_threshold[c] = raw >= fp.heavy_threshold;
     n_cls[c] = BB_ABLATE(1u | (256u << c)) ? 0u : min(raw, fp.bin_cap);
   }
@@ -1448,12 +1604,12 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
     bg8 = (uint32_t)__builtin_amdgcn_readfirstlane((int)bg8);
   }
   auto store_background = [&](int x, int y) {
-    const size_t o = (size_t)(out_y0 + y) * (size_t)fp.width + (size_t)(tile_x0 + x);
+    const size_t o = (size_t)(tg.out_y0 + y) * (size_t)fp.width + (size_t)(tg.x0 + x);
     if (out8) store_pixel(&out8[o], bg8);
     else store_pixel(&out[o], bg);
   };
 
-  // ---- light tiles: no LDS, no barrier ----
+  // ---- light tiles: no LDS, no barrier.  In: the counts, <= 64 every-tile entries.  Out: background or ONE fragment word ----
   // Most tiles of a frame hold no binned triangle at all: sky, or ground that ONE huge (every-tile-list) triangle covers
   // completely -- 6595 of C3's 8160.  Each of the four waves settles that by itself from the same uniform data (the bin
   // counts above and a classification of the <= 64 list entries, one per lane), so the workgroup agrees without talking:
@@ -1476,17 +1632,15 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
       BroadTri b;
       if ((uint32_t)lane < kBroadSpec) b = spec;
       else b = broad_list[lane];
-      const RasterTri t = b.tri;
+      const TriCore t = tri_core(b.tri);
       ref = b.ref;
       clip_slot1 = b.pad[0];
-      const int32_t minX = min(t.X0, min(t.X1, t.X2)), maxX = max(t.X0, max(t.X1, t.X2));
-      const int32_t minY = min(t.Y0, min(t.Y1, t.Y2)), maxY = max(t.Y0, max(t.Y1, t.Y2));
-      const int px0 = max((minX - 128 + 255) >> 8, tile_x0), px1 = min((maxX - 128) >> 8, rx1);
-      const int py0 = max((minY - 128 + 255) >> 8, tile_y0), py1 = min((maxY - 128) >> 8, ry1);
-      if (px0 <= px1 && py0 <= py1) {
-        const int cls_rect = classify_rect(edge_setup(t), px0, px1, py0, py1);
+      const PixRect box = pixel_box(t, tg.rect);
+      const int w = box.x1 - box.x0 + 1, h = box.y1 - box.y0 + 1;  // (in front of the test on purpose)
+      if (box.any()) {
+        const int cls_rect = classify_rect(edge_setup(t), box);
         ok = cls_rect != 0;
-        full = cls_rect == 2 && px1 - px0 + 1 == TILE_W && py1 - py0 + 1 == TILE_H;
+        full = cls_rect == 2 && w == TILE_W && h == TILE_H;
       }
     }
     const unsigned long long m_ok = __ballot(ok);
@@ -1501,38 +1655,29 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
       for (int k = 0; k < PASSES; ++k) {
         const int block = (tid >> 6) + k * (kTileThreads / 64);
         const int x = (block % BX) * 8 + (tid & 7), y = (block / BX) * 8 + ((tid >> 3) & 7);
-        if (tile_x0 + x < fp.width && tile_y0 + y < fp.height) store_background(x, y);
+        if (tg.x0 + x < fp.width && tg.y0 + y < fp.height) store_background(x, y);
       }
-      if (tid == 0) frag_count[tile] = 0u;
+      if (tid == 0) frag_count[tg.tile] = 0u;
       BB_RSTAMP(1); BB_RSTAMP(2); BB_RSTAMP(3); BB_RSTAMP(4);   // (diagnostic build: a light tile's phases all end here)
       return;
     }
     if (__popcll(m_ok) == 1 && __ballot(full) == m_ok) {
       if (tid == 0) {
         const int src = __ffsll((long long)m_ok) - 1;
-        const unsigned long long fref = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)ref, src);
-        const unsigned long long fhi = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)clip_slot1, src) << kFragPixBits;
-        frags[(size_t)tile * TILE_PIXELS] = (fhi << 32) | fref;  // the whole list: 8 bytes instead of 8 KB
-        frag_count[tile] = (uint32_t)TILE_PIXELS | kFullTile;
+        // the whole list: 8 bytes instead of 8 KB (pixel field 0: fetch_fragment adds the lane's own)
+        frags[(size_t)tg.tile * TILE_PIXELS] = fragment_word((uint32_t)__builtin_amdgcn_readlane((int)clip_slot1, src), 0u,
+                                                          (uint32_t)__builtin_amdgcn_readlane((int)ref, src));
+        frag_count[tg.tile] = (uint32_t)TILE_PIXELS | kFullTile;
         if (item_groups) atomicAdd(&item_groups[(slot / kItemGroupSlots) * kItemGroupStride], (uint32_t)(TILE_PIXELS / 64));
       }
-      if (item_head && wave == 0) append_items((uint32_t)(TILE_PIXELS / 64), kFullTile);
+      if (item_head && wave == 0) append_items(item_head, items, lane, (uint32_t)(TILE_PIXELS / 64), kFullTile);
       BB_RSTAMP(1); BB_RSTAMP(2); BB_RSTAMP(3); BB_RSTAMP(4);   // (diagnostic build: a light tile's phases all end here)
       return;
     }
   }
 
-  for (int p = tid; p < TILE_PIXELS; p += kTileThreads) {
-    unsigned long long k0 = 0ull;
-    if (OVERLAY) {  // depth test against what the scene left behind; low word 0 = "no overlay primitive here"
-      int x, y;
-      tile_pixel<TILE_W>(p, x, y);
-      const int gx = tile_x0 + x, gy = tile_y0 + y;
-      if (gx < fp.width && gy < fp.height)
-        k0 = (unsigned long long)__float_as_uint(depth_io[(size_t)gy * (size_t)fp.width + (size_t)gx]) << 32;
-    }
-    keys[p] = k0;
-  }
+  // ---- clear.  Out: keys, s_count, s_n_clip_refs; behind the barrier the tile's bin counts ----
+  clear_keys<TILE_W, TILE_H, OVERLAY>(keys, tg, fp, depth_io, tid);
   if (tid == 0) {
     s_count = 0;
     s_n_clip_refs = 0;
@@ -1541,71 +1686,36 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
   // (a tile rasterised from a heavy slot keeps its counts: its own workgroup may not have looked at them yet.  k_shade_items
   //  clears them.)
   if (!heavy_slot && tid < (int)kBinClasses && (tid == 0 ? n_cls[0] : (tid == 1 ? n_cls[1] : n_cls[2])))
-    tile_count[tile * kBinClasses + tid] = 0;  // ready for the slot's next frame
+    tile_count[tg.tile * kBinClasses + tid] = 0;  // ready for the slot's next frame
 
   // entry order: class 0 | class 1 | class 2 | every-tile list
   const uint32_t e1 = n_cls[0], e2 = e1 + n_cls[1], e3 = e2 + n_cls[2], e_end = e3 + n_broad;
-  const uint32_t *bin0 = bins + (size_t)(tile * kBinClasses) * fp.bin_cap;
+  const uint32_t *bin0 = bins + (size_t)(tg.tile * kBinClasses) * fp.bin_cap;
 
-  // overlay pass: the gizmo's fragments are lifted above every other depth (see depth_max); 0 everywhere else
-  auto zbias_of = [&](uint32_t ref) -> uint32_t {
-    return (OVERLAY && (ref >> 3) >= fp.ov_first_gizmo_prim) ? 0x40000000u : 0u;
-  };
   BB_RSTAMP(1);
   // ---- the chunk loop: up to kStage entries at a time ----
   // An entry is fetched in two dependent trips (bin reference -> triangle record; an every-tile entry in one).  Both run
   // AHEAD of the chunk they belong to: the references of chunk k + 2 and the triangles of chunk k + 1 are asked for before
   // chunk k is rasterised, so a tile with several chunks (a far ball puts 2500 tiny triangles into one tile: ten chunks)
   // pays the two trips once, not once per chunk -- they had been the critical path of the frame's heaviest tiles.
-  struct Fetched {  // what the staging keeps of an entry (the first 36 bytes of its RasterTri)
-    int X0, Y0, X1, Y1, X2, Y2;
-    float z0, dzdx, dzdy;
-    uint32_t ref, clip_slot1;
-  };
-  auto fetch_ref = [&](uint32_t e) -> uint32_t {  // bin reference of entry e (0 for the every-tile list and past the end)
-    if (e >= e3) return 0u;
-    const uint32_t c = e < e1 ? 0u : (e < e2 ? 1u : 2u);
-    const uint32_t i = e - (c == 0u ? 0u : (c == 1u ? e1 : e2));
-    return bin0[(size_t)c * fp.bin_cap + i];
-  };
-  auto fetch_tri = [&](uint32_t e, uint32_t ref) -> Fetched {
-    Fetched f = {};
-    if (e >= e_end) return f;
-    const RasterTri *t = e < e3 ? &tris[ref >> 3] : &broad_list[e - e3].tri;  // binned triangles are never clipped
-    f.X0 = t->X0; f.Y0 = t->Y0; f.X1 = t->X1; f.Y1 = t->Y1; f.X2 = t->X2; f.Y2 = t->Y2;
-    f.z0 = t->z0; f.dzdx = t->dzdx; f.dzdy = t->dzdy;
-    f.ref = ref;
-    if (e >= e3) {
-      f.ref = broad_list[e - e3].ref;
-      f.clip_slot1 = broad_list[e - e3].pad[0];
-    }
-    return f;
-  };
-  uint32_t ref_next = fetch_ref((uint32_t)tid + (uint32_t)kStage);
-  Fetched cur = fetch_tri((uint32_t)tid, fetch_ref((uint32_t)tid));
+  const TileEntries en = {e1, e2, e3, e_end, bin0, fp.bin_cap};
+  uint32_t ref_next = en.fetch_ref((uint32_t)tid + (uint32_t)kStage);
+  Fetched cur = fetch_tri(en, (uint32_t)tid, en.fetch_ref((uint32_t)tid), tris, broad_list);
   for (uint32_t base = 0; base < e_end; base += kStage) {
     if (base) __syncthreads();  // previous chunk consumed
     // ---- stage: every thread files one entry; the rows of the small triangles (classes 0 and 1) are counted ----
+    // In: cur.  Out: column tid of st (box 0xFFFFFFFF: nothing to draw), the clip references, s_row0[tid], s_wave_rows[wave]
     {
       const uint32_t e = base + (uint32_t)tid;
       uint32_t box = 0xFFFFFFFFu;
       int rows = 0;
       if (e < e_end) {
         const Fetched &t = cur;
-        int32_t minX = min(t.X0, min(t.X1, t.X2)), maxX = max(t.X0, max(t.X1, t.X2));
-        int32_t minY = min(t.Y0, min(t.Y1, t.Y2)), maxY = max(t.Y0, max(t.Y1, t.Y2));
-        int px0 = max((minX - 128 + 255) >> 8, tile_x0), px1 = min((maxX - 128) >> 8, rx1);
-        int py0 = max((minY - 128 + 255) >> 8, tile_y0), py1 = min((maxY - 128) >> 8, ry1);
-        if (OVERLAY && (t.ref >> 3) >= fp.ov_first_gizmo_prim) {  // the gizmo's scissor rectangle (src/main.cpp:767-772)
-          px0 = max(px0, fp.ov_x0); px1 = min(px1, fp.ov_x1 - 1);
-          py0 = max(py0, fp.ov_y0); py1 = min(py1, fp.ov_y1 - 1);
-        }
-        bool ok = px0 <= px1 && py0 <= py1;
-        if (ok && e >= e3) {  // every-tile list: accept / reject
-          RasterTri rt;
-          rt.X0 = t.X0; rt.Y0 = t.Y0; rt.X1 = t.X1; rt.Y1 = t.Y1; rt.X2 = t.X2; rt.Y2 = t.Y2;
-          ok = classify_rect(edge_setup(rt), px0, px1, py0, py1) != 0;
-        }
+        // (only the gizmo is intersected with its scissor: the main passes keep their two clamps per bound)
+        const PixRect b = pixel_box(t.core, gizmo_ref<OVERLAY>(fp, t.ref) ? intersect(tg.rect, scissor_rect<OVERLAY>(fp, t.ref)) : tg.rect);
+        const int px0 = b.x0, px1 = b.x1, py0 = b.y0, py1 = b.y1;
+        bool ok = b.any();
+        if (ok && e >= e3) ok = classify_rect(edge_setup(t.core), b) != 0;  // every-tile list: accept / reject
         if (ok) {
           if (t.clip_slot1) {
             const uint32_t k = atomicAdd(&s_n_clip_refs, 1u);
@@ -1614,10 +1724,9 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
               s_clip_slot[k] = t.clip_slot1;
             }
           }
-          box = (uint32_t)(px0 - tile_x0) | ((uint32_t)(px1 - tile_x0) << 8) | ((uint32_t)(py0 - tile_y0) << 16) |
-                ((uint32_t)(py1 - tile_y0) << 24);
-          st.X0[tid] = t.X0; st.Y0[tid] = t.Y0; st.X1[tid] = t.X1; st.Y1[tid] = t.Y1; st.X2[tid] = t.X2; st.Y2[tid] = t.Y2;
-          st.z0[tid] = t.z0; st.dzdx[tid] = t.dzdx; st.dzdy[tid] = t.dzdy;
+          box = (uint32_t)(px0 - tg.x0) | ((uint32_t)(px1 - tg.x0) << 8) | ((uint32_t)(py0 - tg.y0) << 16) |
+                ((uint32_t)(py1 - tg.y0) << 24);
+          st.store(tid, t.core);
           st.ref[tid] = t.ref;
           if (e < e2) rows = py1 - py0 + 1;
         }
@@ -1640,30 +1749,13 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
     __syncthreads();
     if (base == 0) BB_RSTAMP(2);
     const uint32_t hi = min(base + (uint32_t)kStage, e_end);
-    // ---- class 2 and the every-tile list: one wave per large triangle ----
-    {
-      const uint32_t lo = max(base, e2);
-      for (uint32_t e = lo + (uint32_t)wave; e < hi; e += kTileWaves) {
-        const int j = __builtin_amdgcn_readfirstlane((int)(e - base));
-        if (st.box[j] == 0xFFFFFFFFu) continue;
-        const RasterTri t = staged_tri(st, j);
-        if (OVERLAY && (st.ref[j] >> 3) >= fp.ov_first_gizmo_prim)
-          raster_triangle_wave<TILE_W, TILE_H>(t, st.ref[j], tile_x0, tile_y0, fp, keys, lane, zbias_of(st.ref[j]), fp.ov_x0,
-                                               fp.ov_y0, fp.ov_x1, fp.ov_y1);
-        else
-          raster_triangle_wave<TILE_W, TILE_H>(t, st.ref[j], tile_x0, tile_y0, fp, keys, lane);
-      }
-    }
+    raster_large<TILE_W, TILE_H, OVERLAY>(st, max(base, e2), hi, base, tg, fp, keys, lane, wave);
     // (behind the wave-per-triangle loop, whose 64-bit edge functions need the registers)
     // the next chunk's triangles and the references of the one after it: in flight while this chunk is rasterised
-#if BB_RASTER_PREFETCH
-    {
-      const uint32_t e_next = base + (uint32_t)kStage + (uint32_t)tid;
-      cur = fetch_tri(e_next, ref_next);
-      ref_next = fetch_ref(e_next + (uint32_t)kStage);
-    }
-#endif
-    // ---- classes 0 and 1 (small triangles): one ROW of one triangle per lane ----
+    const uint32_t e_next = base + (uint32_t)kStage + (uint32_t)tid;
+    cur = fetch_tri(en, e_next, ref_next, tris, broad_list);
+    ref_next = en.fetch_ref(e_next + (uint32_t)kStage);
+    // ---- the row list, classes 0 and 1 (small triangles): one ROW of one triangle per lane.  In: st, s_row0, s_wave_rows.  Out: keys ----
     // Round 4 gave a tiny triangle one lane (its whole bounding box, pixel by pixel: 16 % of the lanes busy) and a small one
     // sixteen lanes (4 x 4 pixel blocks over its box, a 70-instruction edge setup repeated in each of them: 56 % busy); a tile's
     // life was the life of its unluckiest lane group.  Now the rows of all of them are one list and the 256 threads take rows
@@ -1684,26 +1776,19 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
         for (int step = 32; step; step >>= 1)
           if ((uint32_t)s_row0[j + step] <= local) j += step;
         const uint32_t box = st.box[j];
-        const int py = tile_y0 + (int)((box >> 16) & 255u) + (int)(local - (uint32_t)s_row0[j]);
+        const int py = tg.y0 + (int)((box >> 16) & 255u) + (int)(local - (uint32_t)s_row0[j]);
         const uint32_t ref = st.ref[j];
-        raster_triangle_row<TILE_W, TILE_H>(st.X0[j], st.Y0[j], st.X1[j], st.Y1[j], st.X2[j], st.Y2[j], st.z0[j], st.dzdx[j],
-                                            st.dzdy[j], ref, tile_x0 + (int)(box & 255u), tile_x0 + (int)((box >> 8) & 255u), py,
-                                            tile_x0, tile_y0, keys, zbias_of(ref));
+        raster_triangle_row<TILE_W>(st.load(j), ref, tg.x0 + (int)(box & 255u), tg.x0 + (int)((box >> 8) & 255u), py, tg.x0, tg.y0,
+                                    keys, zbias_of<OVERLAY>(fp, ref));
       }
     }
-#if !BB_RASTER_PREFETCH
-    if (base + (uint32_t)kStage < e_end) {
-      const uint32_t e_next = base + (uint32_t)kStage + (uint32_t)tid;
-      cur = fetch_tri(e_next, fetch_ref(e_next));
-    }
-#endif
   }
   __syncthreads();
   BB_RSTAMP(3);
 
   // ---- compaction: covered pixels -> fragment list (ballot + popcount prefix); background written here ----
-  // fragment = ((clip slot + 1) << kFragPixBits | pixel in tile) << 32 | reference
-  unsigned long long *my_frags = frags + (size_t)tile * TILE_PIXELS;
+  // In: keys, the clip references.  Out: my_frags[] padded to a multiple of 64, s_count, background / visibility / depth pixels
+  unsigned long long *my_frags = frags + (size_t)tg.tile * TILE_PIXELS;
   const uint32_t n_clip_refs = s_n_clip_refs <= kClipRefs ? s_n_clip_refs : 0u;  // too many: k_shade looks the slots up
   // (The wave counts the covered pixels of ALL its passes first and gets the place of its run from a prefix over the four
   //  waves' totals -- no atomic at all; round 4 reserved per pass, four dependent returning LDS atomics per wave of every ball tile.)
@@ -1722,7 +1807,7 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
     const int p = pass_pixel(k);
     int x, y;
     tile_pixel<TILE_W>(p, x, y);
-    const bool in_frame = tile_x0 + x < fp.width && tile_y0 + y < fp.height;
+    const bool in_frame = tg.x0 + x < fp.width && tg.y0 + y < fp.height;
     const unsigned long long key = keys[p];
     pass_mask[k] = __ballot(in_frame && (OVERLAY ? (uint32_t)key != 0u : key != 0ull));
     wave_total += (uint32_t)__popcll(pass_mask[k]);
@@ -1743,7 +1828,7 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
     int p = pass_pixel(k);
     int x, y;
     tile_pixel<TILE_W>(p, x, y);
-    int gx = tile_x0 + x, gy = tile_y0 + y;
+    int gx = tg.x0 + x, gy = tg.y0 + y;
     bool in_frame = gx < fp.width && gy < fp.height;
     unsigned long long key = keys[p];
     // main passes: any key; overlay pass: only pixels an overlay primitive won (low word = reference + 1)
@@ -1755,8 +1840,7 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
       uint32_t clip_slot1 = 0u;
       for (uint32_t k = 0; k < n_clip_refs; ++k)  // (uniform trip count: a handful of clipped sub-triangles per tile at most)
         if (s_clip_ref[k] == ref) clip_slot1 = s_clip_slot[k];
-      const unsigned long long fw =
-          ((((unsigned long long)clip_slot1 << kFragPixBits) | (unsigned long long)(uint32_t)p) << 32) | (unsigned long long)ref;
+      const unsigned long long fw = fragment_word(clip_slot1, (uint32_t)p, ref);
       my_frags[wave_base + rank_in_wave] = fw;
       if (wave_base + rank_in_wave == 0u) s_pad_frag = fw;  // the list's first fragment doubles as its padding (below)
     } else if (in_frame && !OVERLAY) {
@@ -1779,18 +1863,18 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
     if (n != 0u && (n & 63u) != 0u && tid < (int)(64u - (n & 63u))) my_frags[n + (uint32_t)tid] = s_pad_frag;
   }
   if (tid == 0) {
-    frag_count[tile] = s_count;  // (N_shaded = sum of these, taken on the host on demand)
+    frag_count[tg.tile] = s_count;  // (N_shaded = sum of these, taken on the host on demand)
     // 64-fragment chunks per group of 256 launch slots: what k_shade_items needs to place this group's items
     if (item_groups && s_count) atomicAdd(&item_groups[(slot / kItemGroupSlots) * kItemGroupStride], (s_count + 63u) >> 6);
   }
-  if (item_head && wave == 0 && s_count) append_items((s_count + 63u) >> 6, 0u);
+  if (item_head && wave == 0 && s_count) append_items(item_head, items, lane, (s_count + 63u) >> 6, 0u);
   BB_RSTAMP(4);
   if (tid == 0) {
     BB_RSTAMP(5);
 #ifdef BB_STAMPS
-    reinterpret_cast<unsigned long long *>(frag_count + fp.tiles_x * fp.tiles_y)[tile * 8 + 6] =
+    reinterpret_cast<unsigned long long *>(frag_count + fp.tiles_x * fp.tiles_y)[tg.tile * 8 + 6] =
         ((unsigned long long)e_end << 32) | s_count;
-    reinterpret_cast<unsigned long long *>(frag_count + fp.tiles_x * fp.tiles_y)[tile * 8 + 7] =
+    reinterpret_cast<unsigned long long *>(frag_count + fp.tiles_x * fp.tiles_y)[tg.tile * 8 + 7] =
         (unsigned long long)n_cls[0] | ((unsigned long long)n_cls[1] << 16) | ((unsigned long long)n_cls[2] << 32) |
         ((unsigned long long)n_broad << 48);
 #endif
@@ -1816,14 +1900,8 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
 // k_deferred_background still stages them in LDS (LdsLights).
 // ------------------------------------------------------------------------------------------------
 
-// every thread of the workgroup; the caller synchronises
-template <int THREADS>
-BB_DEV void stage_lights(const ShadeParams &sp, const Light *__restrict__ lights, ShadeShared &sh) {
-  for (int li = (int)threadIdx.x; li < sp.num_lights; li += THREADS) sh.lights[li] = cook_light(lights[li]);
-}
-
 // Where the light loop finds its cooked lights.
-//  * LdsLights: a table staged by the workgroup itself (stage_lights + barrier): k_deferred_background.
+//  * LdsLights: a table staged by the workgroup itself (cook_lights + barrier): k_deferred_background.
 //  * ConstLights: the frame's table in global memory, cooked once per frame by k_shade_items and read through the SCALAR
 //    cache (constant address space -> s_load into scalar registers): k_shade.  No LDS, no staging code, and above all no
 //    workgroup barrier in front of the light loop -- the four waves of a workgroup never wait for each other, and a light's
@@ -1921,7 +1999,7 @@ __global__ __launch_bounds__(kBackgroundThreads) void k_deferred_background(Shad
                                                                             float4 *__restrict__ out,
                                                                             const SrgbTables *__restrict__ tables, int gbuffer_view) {
   __shared__ ShadeShared sh;
-  stage_lights<kBackgroundThreads>(sp, lights, sh);
+  cook_lights<kBackgroundThreads>(lights, sp.num_lights, sh.lights);
   __syncthreads();
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     // (buffer_visualize.frag on a cleared texel: rgb 0, alpha 1)
@@ -1984,7 +2062,7 @@ __global__ __launch_bounds__(kItemsThreads) void k_shade_items(FrameParams fp, c
   // the frame's cooked light table (k_shade reads it through the scalar cache): once per frame, by the last workgroup
   // (the one with the fewest slots to scan)
   if (blockIdx.x == gridDim.x - 1)
-    for (int li = tid; li < num_lights; li += kItemsThreads) cooked[li] = cook_light(lights[li]);
+    cook_lights<kItemsThreads>(lights, num_lights, cooked);
   const uint32_t n_slots = (uint32_t)grid_x * (uint32_t)grid_y;
   const uint32_t first = blockIdx.x * (uint32_t)kItemsThreads;
   uint32_t before = 0u;  // (independent loads: one round trip)
@@ -2014,8 +2092,7 @@ __global__ __launch_bounds__(kItemsThreads) void k_shade_items(FrameParams fp, c
   const uint32_t slot = first + (uint32_t)tid;
   if (chunks != 0u) {
     const uint32_t gy = slot / (uint32_t)grid_x, tx = slot - gy * (uint32_t)grid_x;
-    const uint32_t word = (chunks_flag & kFullTile) | (gy << (kItemChunkBits + kItemTxBits)) | (tx << kItemChunkBits);
-    for (uint32_t c = 0; c < chunks; ++c) items[at + c] = word | c;
+    for (uint32_t c = 0; c < chunks; ++c) items[at + c] = item_word(chunks_flag & kFullTile, gy, tx, c);
   }
   // the workgroup of the last slot knows the total
   if (first + (uint32_t)kItemsThreads >= n_slots && tid == kItemsThreads - 1) {
@@ -2093,40 +2170,6 @@ BB_DEV void plane_bary(const PlaneHead &h, bool clipped, const float (&cb)[3][3]
     const float c2 = interp3(b0, b1, b2, cb[0][2], cb[1][2], cb[2][2]);
     b0 = c0; b1 = c1; b2 = c2;
   }
-}
-
-// one work item: where its 64 fragments are (all wave-uniform, held in scalar registers)
-struct ItemPlace {
-  int chunk, tx, ty, out_tile_row;
-  uint32_t tile;
-};
-BB_DEV ItemPlace decode_item(const FrameParams &fp, uint32_t item) {
-  ItemPlace p;
-  p.chunk = (int)(item & 63u);
-  p.tx = (int)((item >> kItemChunkBits) & ((1u << kItemTxBits) - 1u));
-  tile_row(fp, (int)((item & ~kFullTile) >> (kItemChunkBits + kItemTxBits)), p.ty, p.out_tile_row);
-  p.tile = (uint32_t)p.ty * (uint32_t)fp.tiles_x + (uint32_t)p.tx;
-  return p;
-}
-
-// this lane's fragment word of an item, and whether the lane has one.  A tile one triangle covers completely has no list and
-// no count: one word, the pixel is the lane's own (and the wave is uniform).  CONST_WORD: that word comes through the scalar
-// cache (constant address space).
-template <int TILE_PIXELS, bool CONST_WORD>
-BB_DEV unsigned long long fetch_fragment(uint32_t item, const ItemPlace &p, int lane, const unsigned long long *__restrict__ frags,
-                                         const uint32_t *__restrict__ frag_count, bool &valid) {
-  typedef const unsigned long long __attribute__((address_space(4))) *ConstFrags;
-  unsigned long long frag;
-  if (item & kFullTile) {
-    frag = (CONST_WORD ? ((ConstFrags)frags)[(size_t)p.tile * TILE_PIXELS] : frags[(size_t)p.tile * TILE_PIXELS]) +
-           ((unsigned long long)((uint32_t)p.chunk * 64u + (uint32_t)lane) << 32);
-    valid = true;
-  } else {
-    const uint32_t n_frag = frag_count[p.tile];
-    valid = (uint32_t)p.chunk * 64u + (uint32_t)lane < n_frag;
-    frag = frags[(size_t)p.tile * TILE_PIXELS + (uint32_t)p.chunk * 64u + (uint32_t)lane];
-  }
-  return frag;
 }
 
 // The "late" clip slot.  k_raster names a clipped sub-triangle's slot in the fragment word for the first kClipRefs of a
@@ -2290,7 +2333,7 @@ __global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(T
   uint32_t prim = BB_ABLATE(16u) ? 0u : (ref >> 3);
   if (BB_ABLATE(1024u)) prim = (uint32_t)__builtin_amdgcn_readfirstlane((int)prim);  // the record through the scalar cache
   int x, y;
-  tile_pixel<TILE_W>((int)(frag >> 32) & (TILE_PIXELS - 1), x, y);
+  tile_pixel<TILE_W>(fragment_pixel<TILE_PIXELS>(frag), x, y);
   const int gx = at.tx * TILE_W + x, gy = at.ty * TILE_H + y;
   // the pixel's index in the output (32 bits: a frame has at most 2^30 pixels) -- formed here, so that ONE register, not the
   // pixel's coordinates, lives through the two load groups below (the kernel runs at the 64 registers of eight waves per SIMD)
@@ -2670,13 +2713,13 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
     const unsigned long long frag = fetch_fragment<TILE_PIXELS, false>(item, at, lane, frags, frag_count, valid);
     const uint32_t ref = (uint32_t)frag;
     int x, y;
-    tile_pixel<TILE_W>((int)(frag >> 32) & (TILE_PIXELS - 1), x, y);
+    tile_pixel<TILE_W>(fragment_pixel<TILE_PIXELS>(frag), x, y);
     const int gx = at.tx * TILE_W + x, gy = at.ty * TILE_H + y;
     const size_t o = (size_t)((uint32_t)(at.out_tile_row * TILE_H + y) * (uint32_t)fp.width + (uint32_t)gx);
 
     // the head of the primitive record and, for a clipped fragment, its sub-triangle's clip slot
     const ShadeRec *rp = recs + (ref >> 3);
-    const uint32_t clip1 = (uint32_t)(frag >> (32 + kFragPixBits));  // clip-arena slot + 1, 0: none / unknown
+    const uint32_t clip1 = (uint32_t)(frag >> (32 + kFragPixBits));  // clip-arena slot + 1 of a clipped sub-triangle, 0: none / unknown
     bool clipped = clip1 != 0u;
     const ClipSlot *cp = clip_arena + (clipped ? clip1 - 1u : 0u);
     PlaneHead h = clipped ? cp->h : rp->h;
@@ -2977,7 +3020,7 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_overlay(
   const unsigned long long frag = frags[(size_t)tile * TILE_PIXELS + i];
   const uint32_t ref = (uint32_t)frag, prim = ref >> 3;
   int x, y;
-  tile_pixel<TILE_W>((int)(frag >> 32) & (TILE_PIXELS - 1), x, y);
+  tile_pixel<TILE_W>(fragment_pixel<TILE_PIXELS>(frag), x, y);
   const int gx = tx * TILE_W + x, gy = ty * TILE_H + y;
   const ShadeRec pa = recs[prim];
   // the overlay pass writes no slot into its fragment words: a clipped primitive's slot is always found through the record
