@@ -2002,6 +2002,37 @@ int bbr_read_surface(bbr_context *c, float *host) {
   return rc;
 }
 
+int bbr_read_records(bbr_context *c, void *records, void *triangles, uint32_t cap, uint32_t *out_count) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!out_count) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_records: NULL count");
+  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_records: nothing rendered");
+  if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_records: not available on a partitioned context");
+  int rc = sync_and_fix(c, nullptr);
+  if (rc) return rc;
+  // k_geometry writes neither a record nor a triangle for a primitive it culls, and the slot's buffers have held other
+  // frames: fill both, so that "not written" is readable, and have the frame's own k_geometry write them again.
+  const size_t n = c->n_prims;
+  {
+    FrameSlot &s = c->slots[c->last_slot];
+    if (n > s.d_attrs.cap || n > s.d_tris.cap) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_records: the last frame's buffers are gone");
+    if (n) {
+      HIP_TRY(c, hipMemset(s.d_attrs.ptr, 0xFF, n * sizeof(ShadeRec)));
+      HIP_TRY(c, hipMemset(s.d_tris.ptr, 0xFF, n * sizeof(RasterTri)));
+      HIP_TRY(c, hipStreamSynchronize(nullptr));  // (the context's streams do not order themselves after the NULL stream)
+    }
+  }
+  rc = resubmit_last_frame(c);
+  if (rc == BBR_OK) rc = sync_and_fix(c, nullptr);
+  if (rc) return rc;
+  const FrameSlot &s = c->slots[c->last_slot];
+  const size_t m = std::min<size_t>(cap, n);
+  if (records && m) HIP_TRY(c, hipMemcpy(records, s.d_attrs.ptr, m * sizeof(ShadeRec), hipMemcpyDeviceToHost));
+  if (triangles && m) HIP_TRY(c, hipMemcpy(triangles, s.d_tris.ptr, m * sizeof(RasterTri), hipMemcpyDeviceToHost));
+  *out_count = (uint32_t)n;
+  return BBR_OK;
+}
+
 int bbr_last_frame_time_ms(bbr_context *c, float *out_frame_ms, float *out_shade_ms) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);

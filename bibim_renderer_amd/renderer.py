@@ -15,6 +15,15 @@ MAP_NAMES = ("albedo", "metallic", "roughness", "ao", "normal", "height")
 TBN_SEGMENT_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("za", "<f4"), ("zb", "<f4"),
                               ("key", "<u4"), ("pad", "<u4")])
 
+# one primitive record and one triangle of bbr_read_records (include/bibim_hip.h, "primitive-record read-back")
+RECORD_DTYPE = np.dtype([("X0", "<i4"), ("Y0", "<i4"), ("l1dx", "<f4"), ("l1dy", "<f4"), ("l2dx", "<f4"), ("l2dy", "<f4"),
+                         ("rw", "<f4", (3,)), ("uv", "<f4", (3, 2)), ("packed_dims", "<u4"), ("packed", "<u8"),
+                         ("material", "<u4"), ("clip_base", "<u4"), ("vary", "<f4", (12, 3))])
+TRIANGLE_DTYPE = np.dtype([("X0", "<i4"), ("Y0", "<i4"), ("X1", "<i4"), ("Y1", "<i4"), ("X2", "<i4"), ("Y2", "<i4"),
+                           ("z0", "<f4"), ("dzdx", "<f4"), ("dzdy", "<f4"), ("l1dx", "<f4"), ("l1dy", "<f4"), ("l2dx", "<f4"),
+                           ("l2dy", "<f4"), ("rw", "<f4", (3,))])
+assert RECORD_DTYPE.itemsize == 224 and TRIANGLE_DTYPE.itemsize == 64
+
 
 # bbr_ui_cmd and ImDrawVert (include/bibim_hip.h, "GUI pass")
 UI_CMD_DTYPE = np.dtype([("clip_rect", "<f4", (4,)), ("texture", "<i4"), ("vtx_offset", "<u4"), ("idx_offset", "<u4"),
@@ -205,6 +214,16 @@ class Renderer:
         out = np.empty((self.height, self.width, 32), np.float32)
         self._check(self._L.bbr_read_surface(self._ctx, _ptr(out)))
         return out
+
+    def read_records(self):
+        """what k_geometry wrote per primitive of the last frame: (records RECORD_DTYPE [n], triangles TRIANGLE_DTYPE [n]);
+        a culled primitive keeps the 0xFF fill (material == 0xFFFFFFFF); re-renders the last frame"""
+        n = C.c_uint32()
+        self._check(self._L.bbr_read_records(self._ctx, None, None, 0, C.byref(n)))
+        recs, tris = np.zeros(n.value, RECORD_DTYPE), np.zeros(n.value, TRIANGLE_DTYPE)
+        self._check(self._L.bbr_read_records(self._ctx, _ptr(recs), _ptr(tris), n.value, C.byref(n)))
+        assert n.value == len(recs)
+        return recs, tris
 
     # -- overlay subpass (light markers + corner gizmo over the presented image; SURVEY 8(f) rank 4) --
     def upload_gizmo(self, vertices, indices=None):

@@ -280,6 +280,35 @@ int bbr_read_gbuffer(bbr_context *ctx, float *gbuffer_host);
  *   has one N, a material whose maps differ in size one per map. */
 int bbr_read_surface(bbr_context *ctx, float *out);
 
+/* ---- primitive-record read-back ----
+ * What the vertex stage (k_geometry: forward_brdf.vert / gbuffer.vert, clip test, viewport, snap, triangle setup) wrote
+ * for every primitive of the last frame: a diagnostic in the family of bbr_read_visibility / bbr_read_gbuffer /
+ * bbr_read_surface.  Fills the last frame slot's record and triangle buffers with 0xFF bytes (k_geometry writes nothing for
+ * a primitive it culls, so what they hold after a frame is partly an earlier frame's), re-renders the last frame and synchronises.  *out_count = the frame's
+ * primitives n; min(cap, n) records of 224 bytes and triangles of 64 bytes are copied (either pointer may be NULL), in
+ * primitive order (API order of the draws, instance-major inside a draw).  BBR_ERR_NOT_IN_FRAME before a first frame and
+ * after bbr_resize, BBR_ERR_INVALID_ARGUMENT on a partitioned context.
+ * A primitive that was culled (outside the frustum, back-facing, no pixel centre in its box) keeps the fill in both: its
+ * `material` reads 0xFFFFFFFF.  A primitive that goes through the clipper has a record whose head [0..8] is zero (its
+ * sub-triangles carry their own planes) and no triangle (the fill).
+ * One record, by dword (float unless said otherwise):
+ *   [0..1]   X0 Y0 (int32): vertex 0 in 1/256 pixel, pixel (px, py) has its centre at (256 px + 128, 256 py + 128)
+ *   [2..5]   l1dx l1dy l2dx l2dy: the screen-space planes of the barycentrics of vertices 1 and 2, per 1/256 pixel,
+ *            relative to vertex 0 (binary64 expressions rounded once)
+ *   [6..8]   rw0 rw1 rw2: 1 / w of gl_Position at the three vertices
+ *   [9..14]  uv[3][2]: aUV of vertex 0, 1, 2 (copies: every bit of the input, a NaN's payload included)
+ *   [15]     packed_dims (uint32): width | height << 16 of a packed material, 0 otherwise
+ *   [16..17] packed (a device pointer; only "is it null" has a meaning for the caller)
+ *   [18]     material (uint32): the draw's material handle
+ *   [19]     clip_base (uint32): 0xFFFFFFFF unless the clipper produced sub-triangles for the primitive
+ *   [20..55] vary[12][3], varying-major ([varying][vertex]): vPosWorld.xyz, then N.xyz, T.xyz, B.xyz of vTBN
+ *            (forward_brdf.vert:25,31-35)
+ * One triangle (unclipped survivors only), by dword:
+ *   [0..5]   X0 Y0 X1 Y1 X2 Y2 (int32), 1/256 pixel        [6..8]   z0 dzdx dzdy: z / w at vertex 0 and its plane per
+ *   [9..12]  l1dx l1dy l2dx l2dy as in the record                   1/256 pixel
+ *   [13..15] rw0 rw1 rw2 */
+int bbr_read_records(bbr_context *ctx, void *records, void *triangles, uint32_t cap, uint32_t *out_count);
+
 /* ---- overlay subpass ----
  * The reference draws its light markers and the corner gizmo into the swapchain image after tone mapping, depth-tested
  * against the scene (recordCommand, src/main.cpp:128-171; light.vert/.frag on generateUVSphereMesh(0.1, 16, 16), one

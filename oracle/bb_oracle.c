@@ -130,6 +130,11 @@ void bbo_vertex_stage(const bbo_view_uniforms *view, const bbo_instance *inst, c
   vertex_stage(&pv, NULL, inst, v, out_clip, out_vary);
 }
 
+void bbo_vertex_stage_deferred(const bbo_view_uniforms *view, const bbo_instance *inst, const bbo_vertex *v,
+                               float *out_clip, float *out_vary) {
+  vertex_stage(&view->proj, &view->view, inst, v, out_clip, out_vary); /* gbuffer.vert:19-22 */
+}
+
 /* ------------------------------------------------------------------------------------------ */
 /* texture sampling: SMP_LINEAR, REPEAT, single mip (src/render.cpp:1338-1371, :860)          */
 /* ------------------------------------------------------------------------------------------ */

@@ -189,6 +189,9 @@ void bbo_uv_sphere(float radius, int32_t hdiv, int32_t vdiv, float *out_pos3, ui
 /* forward_brdf.vert: out_clip[4], out_vary[14] = uv(2) posWorld(3) N(3) T(3) B(3) */
 void bbo_vertex_stage(const bbo_view_uniforms *view, const bbo_instance *inst, const bbo_vertex *v,
                       float *out_clip, float *out_vary);
+/* gbuffer.vert: the same outputs, gl_Position = P * (V * posWorld) (gbuffer.vert:19-22) instead of (P*V) * posWorld */
+void bbo_vertex_stage_deferred(const bbo_view_uniforms *view, const bbo_instance *inst, const bbo_vertex *v,
+                               float *out_clip, float *out_vary);
 /* P*V as the vertex stage uses it */
 void bbo_proj_view(const bbo_view_uniforms *view, bbo_mat4 *out);
 /* bilinear REPEAT sample of one map; out[4] in [0,1] */

@@ -105,6 +105,7 @@ def lib():
         L.bbo_render_gizmo.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int32,
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.bbo_vertex_stage.argtypes = [C.c_void_p] * 5
+        L.bbo_vertex_stage_deferred.argtypes = [C.c_void_p] * 5
         L.bbo_proj_view.argtypes = [C.c_void_p] * 2
         L.bbo_sample.argtypes = [C.POINTER(Image), C.c_int, C.c_float, C.c_float, C.c_void_p]
         L.bbo_shade_fragment.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Material), C.c_void_p, C.c_void_p]
@@ -401,9 +402,11 @@ def render_gizmo(view, vertices, indices, width, height):
     return rgba, prim, depth, st.as_dict()
 
 
-def vertex_stage(view, inst, vertex):
+def vertex_stage(view, inst, vertex, deferred=False):
+    """forward_brdf.vert, or gbuffer.vert (deferred: the same varyings, gl_Position = P * (V * posWorld)): clip[4], vary[14]"""
     clip = np.zeros(4, np.float32); vary = np.zeros(14, np.float32)
-    lib().bbo_vertex_stage(_p(view), _p(inst), _p(vertex), _p(clip), _p(vary))
+    fn = lib().bbo_vertex_stage_deferred if deferred else lib().bbo_vertex_stage
+    fn(_p(view), _p(inst), _p(vertex), _p(clip), _p(vary))
     return clip, vary
 
 
