@@ -1678,10 +1678,12 @@ int bbr_set_frame_uniforms(bbr_context *c, const void *block) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!block) return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_frame_uniforms: NULL");
-  std::memcpy(&c->frame_u, block, sizeof(FrameUniformBlock));
-  // the reference asserts NumLights < MAX_NUM_LIGHTS (src/main.cpp:1289-1290)
-  if (c->frame_u.num_lights < 0 || c->frame_u.num_lights >= kMaxNumLights)
+  // the reference asserts NumLights < MAX_NUM_LIGHTS (src/main.cpp:1289-1290); a refused block leaves the context's own as it was
+  int32_t num_lights;
+  std::memcpy(&num_lights, static_cast<const char *>(block) + offsetof(FrameUniformBlock, num_lights), sizeof num_lights);
+  if (num_lights < 0 || num_lights >= kMaxNumLights)
     return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_frame_uniforms: NumLights must be in [0, 100)");
+  std::memcpy(&c->frame_u, block, sizeof(FrameUniformBlock));
   return BBR_OK;
 }
 

@@ -154,11 +154,13 @@ class _PolyVertex:
         self.c, self.e_any, self.e_along, self.slid, self.tag, self.generated = c, e_any, e_along, slid, tag, generated
 
 
-def _clip_polygon64(c3):
+def _clip_polygon64(c3, clip_err=None):
     """binary64 Sutherland-Hodgman against near, far and the guard band: the clipped polygon's vertices, which line each of
     its edges lies on, and the bound of the binary32 clipper's error on each vertex (docstring of the module).  Tolerance
-    bookkeeping only; decides no pixel (clipped primitives are examined over the whole frame)."""
-    poly = [_PolyVertex(np.array(c, np.float64), np.zeros(4), np.zeros(4), None, k, False) for k, c in enumerate(c3)]
+    bookkeeping only; decides no pixel (clipped primitives are examined over the whole frame).  `clip_err` [3, 4]: what the
+    original vertices already carry (clip coordinates that are not binary32 inputs), in any direction."""
+    seed = np.zeros((3, 4)) if clip_err is None else np.asarray(clip_err, np.float64)
+    poly = [_PolyVertex(np.array(c, np.float64), seed[k].copy(), np.zeros(4), None, k, False) for k, c in enumerate(c3)]
     for n_plane, coef in enumerate(_PLANES):
         coef = np.array(coef, np.float64)
         out = []
@@ -203,20 +205,31 @@ def _segment_in_rect(a, b, lo, hi):
 
 
 class Prim:
-    """exact setup of one primitive; None-like (self.skip) when it can touch no pixel"""
+    """exact setup of one primitive; None-like (self.skip) when it can touch no pixel.  `clip_err` [3, 4]: bound of the error the
+    clip coordinates carry when they are not the binary32 inputs themselves (a vertex stage evaluated in binary64), projected to
+    pixels the way the clipper's share is; `origin`: where this W x H viewport sits in a larger target (the third rounding of the
+    viewport transform is relative to the coordinate in that target)."""
 
-    def __init__(self, index, clip, uv, W, H):
+    def __init__(self, index, clip, uv, W, H, clip_err=None, origin=(0.0, 0.0)):
         self.index, self.skip = index, True
         ints, den = _common_ints(clip.reshape(-1))
         x, y, z, w = ([ints[4 * i + k] for i in range(3)] for k in range(4))
         # exact trivial reject: all three vertices outside one plane of the clip volume or of the viewport
-        if (all(w[i] - z[i] < 0 for i in range(3)) or all(z[i] < 0 for i in range(3)) or all(w[i] + x[i] < 0 for i in range(3))
+        if clip_err is not None:   # ... by more than the error they carry (binary64: 2^-29 of the margin it leaves is ample)
+            c, e = clip.astype(np.float64), np.asarray(clip_err, np.float64) * (1.0 + 2.0 ** -20)
+            outside = [(c[:, 3] - c[:, 2], e[:, 3] + e[:, 2]), (c[:, 2], e[:, 2]), (c[:, 3] + c[:, 0], e[:, 3] + e[:, 0]),
+                       (c[:, 3] - c[:, 0], e[:, 3] + e[:, 0]), (c[:, 3] + c[:, 1], e[:, 3] + e[:, 1]), (c[:, 3] - c[:, 1], e[:, 3] + e[:, 1])]
+            if any(bool((v + ev < 0).all()) for v, ev in outside):
+                return
+        elif (all(w[i] - z[i] < 0 for i in range(3)) or all(z[i] < 0 for i in range(3)) or all(w[i] + x[i] < 0 for i in range(3))
                 or all(w[i] - x[i] < 0 for i in range(3)) or all(w[i] + y[i] < 0 for i in range(3)) or all(w[i] - y[i] < 0 for i in range(3))):
             return
         self.all_in = all(0 <= z[i] <= w[i] and w[i] > 0 and abs(x[i]) <= GUARD * w[i] and abs(y[i]) <= GUARD * w[i] for i in range(3))
         r = [(x[i], y[i], w[i]) for i in range(3)]
         col = [_cross(r[(i + 1) % 3], r[(i + 2) % 3]) for i in range(3)]
         det = sum(r[0][k] * col[0][k] for k in range(3))
+        if det == 0:   # zero area: no fragment (and no plane to take a depth from)
+            return
         self.front = det > 0
         sgn = (det > 0) - (det < 0)
         comb = lambda q: tuple(sum(q[i] * col[i][k] for i in range(3)) for k in range(3))
@@ -256,8 +269,13 @@ class Prim:
             self.z0 = abs(c64[0, 2] / c64[0, 3])
             self.zmax = float(np.max(np.abs(c64[:, 2] / c64[:, 3])))
             self.rw_max = float(np.max(1.0 / c64[:, 3]))
+            if clip_err is not None:
+                e, r = np.asarray(clip_err, np.float64), 1.0 / c64[:, 3]
+                any_extra = float(np.max((hw * (e[:, 0] + np.abs(c64[:, 0] * r) * e[:, 3]) + hh * (e[:, 1] + np.abs(c64[:, 1] * r) * e[:, 3])) * r))
+                plane_extra = [any_extra] * 5
+                extra_z = float(np.max((e[:, 2] + np.abs(c64[:, 2] * r) * e[:, 3]) * r))
         else:
-            poly = _clip_polygon64(c64)
+            poly = _clip_polygon64(c64, clip_err)
             ok = len(poly) >= 3 and all(v.c[3] > 0 for v in poly)
             if ok:
                 P = np.array([v.c for v in poly])
@@ -286,9 +304,11 @@ class Prim:
                 # planes below still decide every pixel; the vertices are taken to sit anywhere inside the guard band
                 pts = np.array([[-1.0, -1.0], [W + 1.0, -1.0], [W + 1.0, H + 1.0], [-1.0, H + 1.0]]) * (GUARD + 0.5)
                 self.rw_max = math.inf
+                if clip_err is not None:
+                    any_extra = math.inf   # no polygon to project the carried error on: position unknown
             self.z0 = self.zmax = 1.0
         self.pts = pts
-        m = float(np.max(np.abs(np.concatenate([pts.reshape(-1), (pts - [hw, hh]).reshape(-1)]))))
+        m = float(np.max(np.abs(np.concatenate([(pts + np.asarray(origin, np.float64)).reshape(-1), (pts - [hw, hh]).reshape(-1)]))))
         m = min(m, (GUARD + 0.5) * max(W, H))
         self.m = m
         base = 1.0 / 512 + C_POS * U * m
@@ -401,13 +421,39 @@ class Prim:
             val.append(a); tol.append(t)
         return np.stack(val, -1), np.stack(tol, -1)
 
+    def attr(self, X, Y, av):
+        """vuv's value and tolerance for ANY per-vertex attribute av [3] (finite): a = sum a_i e_i / sum e_i in binary64"""
+        av = np.asarray(av, np.float64)
+        wn, we = self.Wn.f64(X, Y)
+        Dx, Dy = self._reach(X, Y)
+        if self.all_in:
+            F = 1.0 + sum(abs(self.edge[i].a * self.lam[i]) * Dx + abs(self.edge[i].b * self.lam[i]) * Dy for i in (1, 2))
+        else:
+            F = 1.0 + self.F_slope * np.maximum(Dx, Dy)
+        amp = self.rw_max * self.rw_scale * self.detf / wn
+        ua, ub = (sum(av[i] * getattr(self.edge[i], k) for i in range(3)) for k in "ab")
+        ev = [self.edge[i].f64(X, Y) for i in range(3)]
+        un, ue = sum(av[i] * ev[i][0] for i in range(3)), sum(abs(av[i]) * ev[i][1] for i in range(3))
+        a = un / wn
+        gx, gy = (ua * wn - un * self.Wn.a) / (wn * wn), (ub * wn - un * self.Wn.b) / (wn * wn)
+        D, M = float(np.max(np.abs(av - av[0]))), float(np.max(np.abs(av)))
+        t = self.delta_f * (np.abs(gx) + np.abs(gy)) + K_VARY * U * (amp * F * D + M)
+        return a, t + 4 * (ue / np.abs(wn) + np.abs(a) * we / np.abs(wn))
+
 
 def rasterise(scene, only=None, want_uv=True):
     """The ideal frame of `scene` (finite primitives only; `only` = iterable of primitive indices to draw alone).  Returns a
     namespace: per pixel `winner` (primitive index or NONE), `decided`, the winner's exact `depth` / `depth_tol` and `uv` /
     `uv_tol`; per primitive `sure_count` (pixels surely covered) and the Prim objects."""
-    W, H = scene.width, scene.height
     clip, uv = scene_primitives(scene)
+    return rasterise_clip(clip, uv, scene.width, scene.height, only, want_uv)
+
+
+def rasterise_clip(clip, uv, W, H, only=None, want_uv=True, clip_err=None, origin=(0.0, 0.0), groups=None):
+    """rasterise() on bare clip coordinates [n, 3, 4] and attributes uv [n, 3, 2] of a W x H viewport.  With `clip_err`
+    [n, 3, 4] (see Prim) the clip coordinates may be binary64.  Also returns `hi`: per pixel the largest depth + tolerance of
+    every primitive that surely or possibly covers it (-inf: none can); with `groups` (per primitive a tuple of labels),
+    `group_sure`: {label: [H, W] bool, the pixels a primitive of that label surely covers}."""
     n = len(clip)
     finite = np.isfinite(clip).all(axis=(1, 2))
     keep = finite.copy()
@@ -431,6 +477,13 @@ def rasterise(scene, only=None, want_uv=True):
         pad = 1.0 / 16 + 64 * U * m
         no_centre = wpos & inside_z & ((np.floor(sx.min(1) - pad - 0.5) == np.floor(sx.max(1) + pad - 0.5))
                                        | (np.floor(sy.min(1) - pad - 0.5) == np.floor(sy.max(1) + pad - 0.5)))
+    if clip_err is not None:   # the margins above (3 pixels, 1/16 pixel) pre-select only where the carried error is far below them
+        e = np.asarray(clip_err, np.float64)
+        with np.errstate(all="ignore"):
+            pe = ((0.5 * W * (e[..., 0] + np.abs(c[..., 0] / c[..., 3]) * e[..., 3]) + 0.5 * H * (e[..., 1] + np.abs(c[..., 1] / c[..., 3]) * e[..., 3]))
+                  / c[..., 3]).max(1)
+        small = pe < 1.0 / 64
+        off, back_fat, no_centre = off & small, back_fat & small, no_centre & small
     keep &= ~off & ~back_fat & ~no_centre
 
     res = SimpleNamespace()
@@ -440,10 +493,10 @@ def rasterise(scene, only=None, want_uv=True):
     hi1 = np.full(npx, -np.inf); id1 = np.full(npx, NONE, np.int64); hi2 = np.full(npx, -np.inf)
     lo_best = np.full(npx, -np.inf); id_best = np.full(npx, NONE, np.int64)
     d_best = np.zeros(npx); tol_best = np.zeros(npx)
-    res.prims, res.sure_count = {}, {}
+    res.prims, res.sure_count, res.group_sure = {}, {}, {}
     res.max_delta = 0.0
     for p in np.nonzero(keep)[0].tolist():
-        pr = Prim(p, clip[p], uv[p], W, H)
+        pr = Prim(p, clip[p], uv[p], W, H, None if clip_err is None else clip_err[p], origin)
         if pr.skip:
             continue
         sure, may, X, Y = pr.coverage()
@@ -470,6 +523,9 @@ def rasterise(scene, only=None, want_uv=True):
         lo_best[fb], id_best[fb], d_best[fb], tol_best[fb] = lo[better], p, d[s][better], tol[s][better]
         res.prims[p] = pr
         res.sure_count[p] = int(s.sum())
+        if groups is not None and s.any():
+            for g in groups[p]:
+                res.group_sure.setdefault(g, np.zeros(npx, bool))[fs] = True
     rival = np.where(id1 == id_best, hi2, hi1)
     nothing = (id1 == NONE)
     with np.errstate(invalid="ignore"):   # (-inf) - (-inf) where nothing is
@@ -478,6 +534,8 @@ def rasterise(scene, only=None, want_uv=True):
     res.winner = np.where(won, id_best, NONE).reshape(H, W)
     res.depth = np.where(won, d_best, 0.0).reshape(H, W)
     res.depth_tol = np.where(won, tol_best, 0.0).reshape(H, W)
+    res.hi = hi1.reshape(H, W)
+    res.group_sure = {g: m.reshape(H, W) for g, m in res.group_sure.items()}
     res.clip = clip
     res.not_all_in = int((finite & ~all_in(clip)).sum())
     if want_uv:
