@@ -210,6 +210,30 @@ BB_DEV f4 mat4_mul(const M4 &m, f4 v) {
   return r;
 }
 
+// The nine words coverage and depth need of a triangle: the first 36 bytes of a RasterTri (bb_types.h) and of an
+// every-tile-list entry, a column of k_raster's StagedTri.  Vertices in 24.8 fixed point, the depth plane relative to vertex 0.
+struct TriCore {
+  int X0, Y0, X1, Y1, X2, Y2;
+  float z0, dzdx, dzdy;
+};
+BB_DEV TriCore tri_core(const RasterTri &t) { return TriCore{t.X0, t.Y0, t.X1, t.Y1, t.X2, t.Y2, t.z0, t.dzdx, t.dzdy}; }
+// Pixels [x0, x1] x [y0, y1], both ends included: a tile, the frame, the gizmo's scissor, a triangle's box; and what two share.
+struct PixRect {
+  int x0, x1, y0, y1;
+  BB_DEV bool any() const { return x0 <= x1 && y0 <= y1; }
+};
+BB_DEV PixRect intersect(const PixRect &a, const PixRect &b) { return PixRect{max(a.x0, b.x0), min(a.x1, b.x1), max(a.y0, b.y0), min(a.y1, b.y1)}; }
+// the larger side of a triangle's bounding box, in 1/256 pixel
+BB_DEV int tri_span(const TriCore &t) { return max(max(t.X0, max(t.X1, t.X2)) - min(t.X0, min(t.X1, t.X2)), max(t.Y0, max(t.Y1, t.Y2)) - min(t.Y0, min(t.Y1, t.Y2))); }
+// The pixels whose CENTRES lie inside a triangle's bounding box and inside rectangles `a` and `b`, clamped in this order.
+BB_DEV PixRect pixel_box(const TriCore &t, const PixRect &a, const PixRect &b) {
+  const int32_t minX = min(t.X0, min(t.X1, t.X2)), maxX = max(t.X0, max(t.X1, t.X2));
+  const int32_t minY = min(t.Y0, min(t.Y1, t.Y2)), maxY = max(t.Y0, max(t.Y1, t.Y2));
+  return PixRect{max(max((minX - 128 + 255) >> 8, a.x0), b.x0), min(min((maxX - 128) >> 8, a.x1), b.x1),
+                 max(max((minY - 128 + 255) >> 8, a.y0), b.y0), min(min((maxY - 128) >> 8, a.y1), b.y1)};
+}
+BB_DEV PixRect pixel_box(const TriCore &t, const PixRect &r) { return pixel_box(t, r, r); }
+
 // ------------------------------------------------------------------------------------------------
 // geometry: vertex stage, clip, setup, binning
 // ------------------------------------------------------------------------------------------------
@@ -329,21 +353,26 @@ BB_DEV bool setup_tri(RasterTri &t, float z0, float z1, float z2) {
   return true;
 }
 
-// ---- statistics: accumulated per workgroup in LDS, written out as one BlockStats record per workgroup ----
+// ---- tiles and bins ----
 
 struct TileRange {
   int tx0, tx1, ty0, ty1;
 };
 
-// pixel-centre bounding box -> tile range; false if the box holds no pixel centre
+// The geometry stage's one box: the pixels whose CENTRES lie inside a triangle's bounding box and inside the frame.
+// tile_range and raster_class read it, for a survivor and for a fan triangle of the clipper.  (pixel_box with the frame's
+// rectangle is the same box; stated through it k_geometry came out one instruction longer: profiles/r11_geometry_stage.txt.)
+BB_DEV PixRect frame_box(const RasterTri &t, const FrameParams &fp) {
+  const int32_t minX = min(t.X0, min(t.X1, t.X2)), maxX = max(t.X0, max(t.X1, t.X2));
+  const int32_t minY = min(t.Y0, min(t.Y1, t.Y2)), maxY = max(t.Y0, max(t.Y1, t.Y2));
+  return PixRect{max((minX - 128 + 255) >> 8, 0), min((maxX - 128) >> 8, fp.width - 1), max((minY - 128 + 255) >> 8, 0), min((maxY - 128) >> 8, fp.height - 1)};
+}
+
+// box of pixel centres -> tile range; false if the box holds no pixel centre
 template <int TILE_W, int TILE_H>
-BB_DEV bool tile_range(const RasterTri &t, const FrameParams &fp, TileRange &r) {
-  int32_t minX = min(t.X0, min(t.X1, t.X2)), maxX = max(t.X0, max(t.X1, t.X2));
-  int32_t minY = min(t.Y0, min(t.Y1, t.Y2)), maxY = max(t.Y0, max(t.Y1, t.Y2));
-  int32_t px0 = max((minX - 128 + 255) >> 8, 0), px1 = min((maxX - 128) >> 8, fp.width - 1);
-  int32_t py0 = max((minY - 128 + 255) >> 8, 0), py1 = min((maxY - 128) >> 8, fp.height - 1);
-  if (px0 > px1 || py0 > py1) return false;
-  r.tx0 = px0 / TILE_W; r.tx1 = px1 / TILE_W; r.ty0 = py0 / TILE_H; r.ty1 = py1 / TILE_H;
+BB_DEV bool tile_range(const PixRect &box, TileRange &r) {
+  if (!box.any()) return false;
+  r.tx0 = box.x0 / TILE_W; r.tx1 = box.x1 / TILE_W; r.ty0 = box.y0 / TILE_H; r.ty1 = box.y1 / TILE_H;
   return true;
 }
 
@@ -352,17 +381,13 @@ BB_DEV bool tile_range(const RasterTri &t, const FrameParams &fp, TileRange &r) 
 //   0: tiny  (box <= 64 px, spans <= 32 px)      one triangle per lane, 32-bit stepped edge functions
 //   1: small (spans <= 64 px)                    16 lanes per triangle, 4x4 pixel blocks, 24-bit multiply-adds
 //   2: large                                     one wave per triangle, 8x8 blocks, trivial accept / reject
+// box: the frame-clamped box of pixel centres; span: tri_span, the unclamped extent in 1/256 pixel
 constexpr uint32_t kBinClasses = 3;
 
-BB_DEV uint32_t raster_class(const RasterTri &t, const FrameParams &fp) {
-  int32_t minX = min(t.X0, min(t.X1, t.X2)), maxX = max(t.X0, max(t.X1, t.X2));
-  int32_t minY = min(t.Y0, min(t.Y1, t.Y2)), maxY = max(t.Y0, max(t.Y1, t.Y2));
-  int32_t px0 = max((minX - 128 + 255) >> 8, 0), px1 = min((maxX - 128) >> 8, fp.width - 1);
-  int32_t py0 = max((minY - 128 + 255) >> 8, 0), py1 = min((maxY - 128) >> 8, fp.height - 1);
-  int ext = max(maxX - minX, maxY - minY);
-  int area = (px1 - px0 + 1) * (py1 - py0 + 1);
-  if (ext <= 32 * 256 && area <= 64) return 0u;
-  if (ext <= 64 * 256) return 1u;
+BB_DEV uint32_t raster_class(const PixRect &box, int span) {
+  const int area = (box.x1 - box.x0 + 1) * (box.y1 - box.y0 + 1);
+  if (span <= 32 * 256 && area <= 64) return 0u;
+  if (span <= 64 * 256) return 1u;
   return 2u;
 }
 
@@ -379,8 +404,51 @@ BB_DEV void broad_insert(const RasterTri &t, uint32_t ref, const FrameParams &fp
   }
 }
 
+// ---- screen-band partition (fp.world > 1): tile rows in bands of fp.band_tiles, band b belongs to rank b mod world ----
+BB_DEV int band_of_row(const FrameParams &fp, int ty) { return ty / fp.band_tiles; }
+// tile row ty is this rank's (every row of an unpartitioned frame is)
+BB_DEV bool row_owned(const FrameParams &fp, int ty) { return fp.world <= 1 || band_of_row(fp, ty) % fp.world == fp.rank; }
+// tile rows [ty0, ty1] hold a row of this rank's: the first owned band at or behind ty0's is not behind ty1's
+BB_DEV bool rows_owned(const FrameParams &fp, int ty0, int ty1) {
+  if (fp.world <= 1) return true;
+  const int b0 = band_of_row(fp, ty0), b1 = band_of_row(fp, ty1);
+  const int first = b0 + ((fp.rank - b0 % fp.world) + fp.world) % fp.world;
+  return first <= b1;
+}
+// owned tile row -> row of this rank's launch grid: the inverse of tile_row (k_raster)
+BB_DEV uint32_t grid_row(const FrameParams &fp, uint32_t ty) {
+  if (fp.world <= 1) return ty;
+  const uint32_t band = ty / (uint32_t)fp.band_tiles;
+  return (band / (uint32_t)fp.world) * (uint32_t)fp.band_tiles + (ty - band * (uint32_t)fp.band_tiles);
+}
+
+// Wave grouping: the lanes with `has` that name the same key form a group (ballot loop, ALU only); every member learns the
+// group's lowest lane, its own rank among the members and the group's size.  Must be called by all lanes of the wave.
+struct WaveGroup {
+  int leader;
+  uint32_t rank, size;
+};
+BB_DEV WaveGroup wave_group(bool has, uint32_t key) {
+  const int lane = threadIdx.x & 63;
+  unsigned long long pending = __ballot(has);
+  WaveGroup g = {lane, 0u, 0u};
+  while (pending) {
+    int l = __builtin_amdgcn_readfirstlane(__ffsll((long long)pending) - 1);
+    uint32_t lk = (uint32_t)__builtin_amdgcn_readlane((int)key, l);
+    bool mine = has && key == lk;
+    unsigned long long m = __ballot(mine);
+    if (mine) {
+      g.leader = l;
+      g.rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      g.size = (uint32_t)__popcll(m);
+    }
+    pending &= ~m;
+  }
+  return g;
+}
+
 // Wave-aggregated bin insertion.  Consecutive primitives of a mesh land in the same few tiles, so the lanes of
-// a wave that target one bin segment are grouped (ballot loop, ALU only) and the lowest lane of each group
+// a wave that target one bin segment are grouped (wave_group) and the lowest lane of each group
 // reserves all the group's slots with ONE returning atomic; the leaders of all groups issue their atomics in the
 // same instruction, so a wave pays one memory round trip however many tiles it touches, and a tile that
 // receives thousands of tiny triangles sees tens of atomics instead of thousands.
@@ -395,49 +463,27 @@ struct BinTicket {
 };
 
 BB_DEV BinTicket wave_bin_reserve(bool has, uint32_t seg, uint32_t *tile_count) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long pending = __ballot(has);
-  BinTicket t;
-  t.leader = lane;
-  t.rank = 0;
-  t.base = 0;
-  uint32_t gsize = 0;
-  while (pending) {
-    int l = __builtin_amdgcn_readfirstlane(__ffsll((long long)pending) - 1);
-    uint32_t ls = (uint32_t)__builtin_amdgcn_readlane((int)seg, l);
-    bool mine = has && seg == ls;
-    unsigned long long m = __ballot(mine);
-    if (mine) {
-      t.leader = l;
-      t.rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      gsize = (uint32_t)__popcll(m);
-    }
-    pending &= ~m;
-  }
-  if (has && lane == t.leader) t.base = atomicAdd(&tile_count[seg], gsize);
-  t.gsize = gsize;
+  const WaveGroup g = wave_group(has, seg);
+  BinTicket t = {0u, g.rank, g.size, g.leader};
+  if (has && (int)(threadIdx.x & 63) == g.leader) t.base = atomicAdd(&tile_count[seg], g.size);
   return t;
 }
+// redeem: this lane's slot in the bin (waits for the leader's atomic)
+BB_DEV uint32_t bin_slot(const BinTicket &t) { return (uint32_t)__shfl((int)t.base, t.leader) + t.rank; }
 
 // heavy: the frame's heavy-tile list (fp.heavy_threshold != 0).  The ONE reservation that takes a bin's count across the
 // threshold appends the tile -- as the launch slot k_raster's screen order gives it, and the class of the bin -- so a tile
 // is listed at most once per class, and which of its entries does the work follows from the final counts (k_raster).
 BB_DEV void wave_bin_write(bool has, uint32_t seg, uint32_t ref, const BinTicket &t, const FrameParams &fp, Counters *ctr,
                            uint32_t *bins, uint32_t *heavy) {
-  const uint32_t base = (uint32_t)__shfl((int)t.base, t.leader);
+  const uint32_t slot = bin_slot(t);
   if (heavy && has && (int)(threadIdx.x & 63) == t.leader && t.base < fp.heavy_threshold && t.base + t.gsize >= fp.heavy_threshold) {
     const uint32_t tile = seg / kBinClasses, c = seg - tile * kBinClasses;
     const uint32_t ty = tile / (uint32_t)fp.tiles_x, tx = tile - ty * (uint32_t)fp.tiles_x;
-    uint32_t gy = ty;  // owned tile row -> grid row: the inverse of tile_row
-    if (fp.world > 1) {
-      const uint32_t band = ty / (uint32_t)fp.band_tiles;
-      gy = (band / (uint32_t)fp.world) * (uint32_t)fp.band_tiles + (ty - band * (uint32_t)fp.band_tiles);
-    }
     const uint32_t k = atomicAdd(&ctr->n_heavy, 1u);
-    if (k < kBinClasses * (uint32_t)(fp.tiles_x * fp.tiles_y)) heavy[k] = (gy * (uint32_t)fp.tiles_x + tx) | (c << 30);
+    if (k < kBinClasses * (uint32_t)(fp.tiles_x * fp.tiles_y)) heavy[k] = (grid_row(fp, ty) * (uint32_t)fp.tiles_x + tx) | (c << 30);
   }
   if (has) {
-    uint32_t slot = base + t.rank;
     if (slot < fp.bin_cap) {
       bins[(size_t)seg * fp.bin_cap + slot] = ref;
     } else {
@@ -451,7 +497,6 @@ BB_DEV void wave_bin_write(bool has, uint32_t seg, uint32_t ref, const BinTicket
 // clip, lane i projects vertex i and then sets up fan triangle i (binary64 planes), stores its ClipSlot and its
 // entry of the every-tile list -- a clipped primitive is typically huge (the ground plane), so its sub-triangles skip
 // the bins.  One atomic reserves the arena slots, one the list entries.  Results in w.n_valid / w.base.
-template <int TILE_W, int TILE_H>
 BB_DEV void clip_primitive_wave(ClipWork &w, int owner, const float (*clip)[4], uint32_t prim, const FrameParams &fp,
                                 const Viewport &vp, ClipSlot *clip_arena, Counters *ctr, BroadTri *broad_list) {
   const int lane = threadIdx.x & 63;
@@ -497,8 +542,7 @@ BB_DEV void clip_primitive_wave(ClipWork &w, int owner, const float (*clip)[4], 
     tri.X2 = w.X[i + 1]; tri.Y2 = w.Y[i + 1];
     tri.rw0 = w.rw[0]; tri.rw1 = w.rw[i]; tri.rw2 = w.rw[i + 1];
     ok = setup_tri(tri, w.z[0], w.z[i], w.z[i + 1]);
-    TileRange tr;
-    ok = ok && tile_range<TILE_W, TILE_H>(tri, fp, tr);
+    ok = ok && frame_box(tri, fp).any();
   }
   const unsigned long long m = __ballot(ok);
   const int n_valid = (int)__popcll(m);
@@ -549,19 +593,23 @@ BB_DEV void clip_primitive_wave(ClipWork &w, int owner, const float (*clip)[4], 
   }
 }
 
-// ---- k_geometry's view of a primitive's inputs ----
+// ---- a primitive's inputs, as k_geometry and k_tbn_segments find them ----
 // (global, not flat, loads: through pointers the compiler knows to be global memory)
 typedef const Vertex __attribute__((address_space(1))) *GlobalVertex;
 typedef const uint32_t __attribute__((address_space(1))) *GlobalIndex;
 typedef const InstanceBlock __attribute__((address_space(1))) *GlobalInstance;
 
+// which draw, from the table alone, starting at draw d
+BB_DEV uint32_t find_draw(const DrawDesc *__restrict__ draws, uint32_t n_draws, uint32_t prim, uint32_t d = 0) {
+  while (d + 1 < n_draws && prim >= draws[d + 1].first_prim) ++d;
+  return d;
+}
 // which draw: the first few draws' first_prim are kernel arguments (no load); more draws than that: the table
 BB_DEV uint32_t find_draw(const DrawDesc *__restrict__ draws, uint32_t n_draws, const FirstPrims &first_prims, uint32_t prim) {
   uint32_t d = 0;
 #pragma unroll
   for (int q = 0; q < kInlineFirstPrims; ++q) d += prim >= first_prims.v[q] ? 1u : 0u;
-  if (n_draws > (uint32_t)kInlineFirstPrims + 1u)
-    while (d + 1 < n_draws && prim >= draws[d + 1].first_prim) ++d;
+  if (n_draws > (uint32_t)kInlineFirstPrims + 1u) d = find_draw(draws, n_draws, prim, d);
   return d;
 }
 
@@ -590,7 +638,7 @@ BB_DEV PrimSource prim_source(const DrawDesc &draw, uint32_t prim) {
   return s;
 }
 
-// Phase 1's loads: the three positions and the instance's model matrix, one batch.  The fence keeps the compiler from
+// The positions phase's loads: the three positions and the instance's model matrix, one batch.  The fence keeps the compiler from
 // sinking the loads to their first use (one round trip for the batch, not one per matrix column).
 BB_DEV void load_positions(const PrimSource &s, float (*pos)[3], Mat4 &model) {
 #pragma unroll
@@ -607,25 +655,63 @@ BB_DEV void load_positions(const PrimSource &s, float (*pos)[3], Mat4 &model) {
                "v"(model.M[3][1]), "v"(model.M[3][2]), "v"(model.M[3][3]) : "memory");
 }
 
-// gl_Position of one vertex (and posWorld of the main passes' vertex program).  k_geometry evaluates it for every primitive,
-// and once more for the few that go through the clipper: the same expressions on the same operands, hence the same bits.
+// ---- the vertex program's expressions (forward_brdf.vert:25,31-35 = tbn.vert:18-25), each stated once: k_geometry and
+// k_tbn_segments both call them, so the TBN overlay's N, T, B and posWorld are the forward pass's, bit for bit ----
+// posWorld = model * (pos, 1)
+template <typename M4>
+BB_DEV f4 vertex_world(const M4 &model, const float *pos) { return mat4_mul(model, f4{pos[0], pos[1], pos[2], 1.0f}); }
+// a direction (normal, tangent) through normalMat = transpose(mat3(aInvModel)), im = the inverse model matrix's upper 3 x 3:
+// normalize(normalMat * v).  B = cross3(N, T).
+BB_DEV f3 normal_dir(const float (*im)[3], f3 v) { return normalize3(mk3(dot3(ld3(im[0]), v), dot3(ld3(im[1]), v), dot3(ld3(im[2]), v))); }
+
+// gl_Position of one vertex (and posWorld of the main passes' vertex program).
 template <bool OVERLAY>
 BB_DEV f4 vertex_clip_pos(const Mat4 &model, const float *pos, const Mat4 &pv, const Mat4 &view, const FrameParams &fp, f3 &world) {
+  // OVERLAY: the host folds the matrices: ib.model = (P*V)*modelMat of the light (light.vert:11-14) or the gizmo's own
+  // projMat*viewMat (gizmo.vert:13-24)
+  const f4 w = vertex_world(model, pos);
   if (OVERLAY) {
-    // The host folds the matrices: ib.model = (P*V)*modelMat of the light (light.vert:11-14) or the gizmo's own
-    // projMat*viewMat (gizmo.vert:13-24)
     world = mk3(0.0f, 0.0f, 0.0f);
-    return mat4_mul(model, f4{pos[0], pos[1], pos[2], 1.0f});
+    return w;
   }
-  // forward_brdf.vert:25,27
-  const f4 w = mat4_mul(model, f4{pos[0], pos[1], pos[2], 1.0f});
   world = mk3(w.x, w.y, w.z);
   // forward_brdf.vert:27 multiplies (P*V) * posWorld (pv = P*V); gbuffer.vert:19-22 P * (V * posWorld) (pv = P)
   return fp.deferred ? mat4_mul(pv, mat4_mul(view, w)) : mat4_mul(pv, w);
 }
 
+// The clip-space positions of a primitive: draw -> source -> positions and model matrix -> gl_Position of the three vertices
+// (and posWorld).  k_geometry evaluates it for every primitive, and once more for the few that go through the clipper: the
+// same expressions on the same operands, hence the same bits.  stamp(i): the caller's timing hooks (1: the draw is known,
+// 6: the loads have been asked for).
+struct PrimInputs {
+  DrawDesc draw;
+  PrimSource src;
+};
+template <bool OVERLAY, class Stamp>
+BB_DEV PrimInputs prim_clip_positions(const DrawDesc *__restrict__ draws, uint32_t n_draws, const FirstPrims &first_prims, uint32_t prim,
+                                      const Mat4 &pv, const Mat4 &view, const FrameParams &fp, float (*clip)[4], float (*pw)[3],
+                                      Stamp stamp) {
+  PrimInputs in;
+  in.draw = draws[find_draw(draws, n_draws, first_prims, prim)];
+  stamp(1);
+  in.src = prim_source(in.draw, prim);
+  float pos[3][3];
+  Mat4 model;
+  load_positions(in.src, pos, model);
+  stamp(6);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    f3 w;
+    const f4 c = vertex_clip_pos<OVERLAY>(model, pos[k], pv, view, fp, w);
+    pw[k][0] = w.x; pw[k][1] = w.y; pw[k][2] = w.z;
+    clip[k][0] = c.x; clip[k][1] = c.y; clip[k][2] = c.z; clip[k][3] = c.w;
+  }
+  return in;
+}
+
 // Four dwords of a primitive record.  The record leaves k_geometry in 16-byte pieces as soon as their values exist --
 // never as one 56-register struct -- and the pieces are the same fourteen dwordx4 stores the struct assignment was.
+// `dword`: kRecPlanes, kRecHeadRest, kRecBody (bb_types.h, next to ShadeRec) plus a multiple of four.
 typedef uint32_t rec_u32x4_ __attribute__((ext_vector_type(4)));
 typedef rec_u32x4_ rec_u32x4 __attribute__((aligned(8)));  // (a record is 8-byte aligned: it holds a pointer)
 BB_DEV void rec_store4(ShadeRec *rec, int dword, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
@@ -636,10 +722,21 @@ BB_DEV void rec_store4(ShadeRec *rec, int dword, uint32_t a, uint32_t b, uint32_
 BB_DEV void rec_store4(ShadeRec *rec, int dword, float a, float b, float c, float d) {
   rec_store4(rec, dword, __float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d));
 }
+// The rest of the head, three pieces: rw2, the first two varyings of the three vertices (uv; the overlay programs' own),
+// packed_dims, packed, material, clip_base.  (A clipped primitive's clip_base is patched in once the clipper has its arena slots.)
+BB_DEV void rec_store_head_rest(ShadeRec *rec, float rw2, const float *v0, const float *v1, const float *v2, uint32_t packed_dims,
+                                const uint8_t *packed, uint32_t material) {
+  const unsigned long long packed_bits = (unsigned long long)reinterpret_cast<uintptr_t>(packed);
+  rec_store4(rec, kRecHeadRest, rw2, v0[0], v0[1], v1[0]);
+  rec_store4(rec, kRecHeadRest + 4, __float_as_uint(v1[1]), __float_as_uint(v2[0]), __float_as_uint(v2[1]), packed_dims);
+  rec_store4(rec, kRecHeadRest + 8, (uint32_t)packed_bits, (uint32_t)(packed_bits >> 32), material, kNotClipped);
+}
 
 // One thread per primitive, all draw calls of the frame in one launch (API order = primitive index order).
 // OVERLAY = true is the overlay subpass (light markers, corner gizmo): other vertex programs and a
 // per-primitive viewport, everything downstream of the vertex stage shared.
+// The body's phases, each a marked block that states its inputs and outputs: positions, frustum fate, setup and ownership,
+// record, bins, clipper, statistics (which of them can be functions: profiles/r11_geometry_stage.txt).
 template <int TILE_W, int TILE_H, bool OVERLAY = false>
 __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ draws, uint32_t n_draws, uint32_t n_prims,
                                                   FirstPrims first_prims,
@@ -652,8 +749,13 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
                                                   BlockStats *__restrict__ block_stats, uint32_t *__restrict__ heavy) {
 #ifdef BB_STAMPS
 #define BB_STAMP(i) do { if (threadIdx.x == 0) reinterpret_cast<unsigned long long *>(clip_arena + fp.clip_cap)[blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
+  const auto phase1_stamp = [&](int i) {
+    if (i == 6) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (the loads have arrived)
+    BB_STAMP(i);
+  };
 #else
 #define BB_STAMP(i) do { } while (0)
+  const auto phase1_stamp = [](int) {};
 #endif
   // This kernel's waves issue one instruction in ~18 cycles and wait for memory most of their lives; with frames in flight
   // they share their SIMDs with k_shade's, which want to issue all the time.  At the highest issue priority their few
@@ -673,34 +775,20 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
   uint32_t clipped_raster = 0;  // wave-uniform: sub-triangles of this wave's clipped primitives that reached the every-tile list
   Viewport vp = {fp.half_w, fp.half_h, fp.half_w, fp.half_h};
   if (prim < n_prims) {
-    const DrawDesc draw = draws[find_draw(draws, n_draws, first_prims, prim)];
-    BB_STAMP(1);
-    const PrimSource src = prim_source(draw, prim);
-    ShadeRec *const rec = recs + prim;
-    // ---- phase 1, every lane: positions and the model matrix only.  gl_Position of the three vertices decides whether the
+    // ---- positions.  In: prim.  Out: clip (gl_Position of the three vertices), pw (posWorld, main passes), the draw and
+    // where the primitive's inputs are.  Every lane, positions and the model matrix only: gl_Position decides whether the
     // primitive can touch a pixel at all; half of a closed mesh faces away from the camera and is culled below.  Normals,
     // tangents, texture coordinates and the inverse model matrix are asked for behind the cull, by the survivors alone: carried
     // through the cull and the binary64 setup they made this kernel the largest register holder of the pipelined frame ----
     float clip[3][4];
-    float pw[3][3];  // posWorld (main passes)
-    {
-      float pos[3][3];
-      Mat4 model;
-      load_positions(src, pos, model);
-#ifdef BB_STAMPS
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      BB_STAMP(6);
-#endif
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        f3 w;
-        const f4 c = vertex_clip_pos<OVERLAY>(model, pos[k], pv, view, fp, w);
-        pw[k][0] = w.x; pw[k][1] = w.y; pw[k][2] = w.z;
-        clip[k][0] = c.x; clip[k][1] = c.y; clip[k][2] = c.z; clip[k][3] = c.w;
-      }
-    }
+    float pw[3][3];
+    const PrimInputs in = prim_clip_positions<OVERLAY>(draws, n_draws, first_prims, prim, pv, view, fp, clip, pw, phase1_stamp);
+    const DrawDesc &draw = in.draw;
+    const PrimSource &src = in.src;
+    ShadeRec *const rec = recs + prim;
     if (OVERLAY && prim >= fp.ov_first_gizmo_prim) vp = Viewport{fp.ov_half, fp.ov_half, fp.ov_cx, fp.ov_cy};
-    // trivial reject against the true frustum (cannot change any pixel)
+    // ---- frustum fate.  In: clip.  Out: culled (all three vertices outside one plane of the TRUE frustum: cannot change any
+    // pixel), all_in (every vertex inside near, far and the guard band: rasterised as it is); neither: crossing, the clipper's ----
     bool o_l = true, o_r = true, o_t = true, o_b = true, o_n = true, o_f = true, all_in = true;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -711,48 +799,44 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
 #pragma unroll
       for (int p = 0; p < 6; ++p) all_in &= (plane_dist(c, p) >= 0.0f);
     }
+    const bool culled = o_l | o_r | o_t | o_b | o_n | o_f;
+    // ---- setup and ownership.  In: clip, vp, culled, all_in.  Out: t (set up; zero unless all_in), its tile range tr, survives
+    // (unclipped, front-facing, holds a pixel centre of this rank's bands), needs_clip ----
     RasterTri t = {};
-    bool survives = false;  // unclipped, front-facing, holds a pixel centre (of this rank's bands)
-    if (!(o_l | o_r | o_t | o_b | o_n | o_f)) {
+    bool survives = false;
+    if (!culled) {
       if (all_in) {
         float z0, z1, z2;
         if (project_vertex(clip[0], vp, t.X0, t.Y0, t.rw0, z0) && project_vertex(clip[1], vp, t.X1, t.Y1, t.rw1, z1) &&
             project_vertex(clip[2], vp, t.X2, t.Y2, t.rw2, z2) && setup_tri(t, z0, z1, z2) &&
-            tile_range<TILE_W, TILE_H>(t, fp, tr)) {
-          survives = true;
-          if (fp.world > 1) {
-            // screen-band partition: a primitive whose tile rows hold none of this rank's bands (band b belongs to rank
-            // b mod world) is somebody else's: no record, no bin entry.  (Every rank still runs the vertex positions of
-            // every primitive -- that is what tells it whose they are.)
-            const int b0 = tr.ty0 / fp.band_tiles, b1 = tr.ty1 / fp.band_tiles;
-            const int first = b0 + ((fp.rank - b0 % fp.world) + fp.world) % fp.world;
-            survives = first <= b1;
-          }
+            tile_range<TILE_W, TILE_H>(frame_box(t, fp), tr)) {
+          // screen-band partition: a primitive whose tile rows hold none of this rank's bands is somebody else's: no record,
+          // no bin entry.  (Every rank still runs the vertex positions of every primitive -- that is what tells it whose they are.)
+          survives = rows_owned(fp, tr.ty0, tr.ty1);
         }
       } else if (!BB_ABLATE(128u)) {
         needs_clip = true;
       }
     }
-#ifdef BB_STAMPS
     BB_STAMP(7);
-#endif
     if (survives || needs_clip) {
-      // ---- phase 2, survivors: ask for the attributes and the upper 3 x 3 of the instance's inverse model matrix (the normal
-      // matrix; the overlay programs' colour / view rows) -- one batch, one more dependent round trip, closed by a fence like
-      // phase 1's -- and, while they travel, send off everything phase 1 already knows: the triangle, the record's planes and
-      // posWorld.  Only two values of phase 1 (rw2, posWorld.z of vertex 2: the first dwords of 16-byte pieces that the
-      // attributes complete) and the tile range wait for the loads with the lane. ----
+      // ---- record.  In: t, tr, pw, draw, src.  Out: tris[prim], recs[prim]; binned, cls; an every-tile-list entry for a
+      // survivor of more than fp.broad_threshold tiles.  Survivors ask for the attributes and the upper 3 x 3 of the instance's
+      // inverse model matrix (the normal matrix; the overlay programs' colour / view rows) -- one batch, one more dependent
+      // round trip, closed by a fence like the positions' -- and, while they travel, send off everything known already: the
+      // triangle, the record's planes and posWorld.  Only two values (rw2, posWorld.z of vertex 2: the first dwords of 16-byte
+      // pieces that the attributes complete) and the tile range wait for the loads with the lane. ----
       const bool keep = !BB_ABLATE(64u);
       if (keep) {
         if (survives) tris[prim] = t;
         // planes of the unclipped triangle; zero for a primitive that goes through the clipper (its sub-triangles have their
         // own): t is written in the unclipped branch only, so there it still holds the zeros it was initialised with
-        rec_store4(rec, 0, (uint32_t)t.X0, (uint32_t)t.Y0, __float_as_uint(t.l1dx), __float_as_uint(t.l1dy));
-        rec_store4(rec, 4, t.l2dx, t.l2dy, t.rw0, t.rw1);
+        rec_store4(rec, kRecPlanes, (uint32_t)t.X0, (uint32_t)t.Y0, __float_as_uint(t.l1dx), __float_as_uint(t.l1dy));
+        rec_store4(rec, kRecPlanes + 4, t.l2dx, t.l2dy, t.rw0, t.rw1);
         if (!OVERLAY) {
-          // varyings 2..4 (posWorld), varying-major: vary[j][k] = pw[k][j], dwords 20..28
-          rec_store4(rec, 20, pw[0][0], pw[1][0], pw[2][0], pw[0][1]);
-          rec_store4(rec, 24, pw[1][1], pw[2][1], pw[0][2], pw[1][2]);
+          // body varyings 0..2 (posWorld), varying-major: vary[j][k] = pw[k][j]
+          rec_store4(rec, kRecBody, pw[0][0], pw[1][0], pw[2][0], pw[0][1]);
+          rec_store4(rec, kRecBody + 4, pw[1][1], pw[2][1], pw[0][2], pw[1][2]);
         }
       }
       const float rw2 = t.rw2, pwz2 = pw[2][2];
@@ -761,7 +845,7 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
         uint32_t ntiles = (uint32_t)(tr.tx1 - tr.tx0 + 1) * (uint32_t)(tr.ty1 - tr.ty0 + 1);
         if (ntiles > fp.broad_threshold) broad_insert(t, prim << 3, fp, ctr, broad_list);
         else binned = true;
-        cls = raster_class(t, fp);
+        cls = raster_class(frame_box(t, fp), tri_span(tri_core(t)));  // (the box again, not kept from the setup: two registers)
       }
       float nrm[3][3], tng[3][3], uv[3][2], im_[3][3];
 #pragma unroll
@@ -777,19 +861,10 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
       asm volatile("" :: "v"(im_[0][0]), "v"(im_[0][1]), "v"(im_[0][2]), "v"(im_[1][0]), "v"(im_[1][1]), "v"(im_[1][2]), "v"(im_[2][0]),
                    "v"(im_[2][1]), "v"(im_[2][2]), "v"(nrm[0][0]), "v"(nrm[1][0]), "v"(nrm[2][0]), "v"(tng[0][0]), "v"(tng[1][0]),
                    "v"(tng[2][0]), "v"(uv[0][0]), "v"(uv[1][0]), "v"(uv[2][0]) : "memory");
-      // the rest of the head: dwords 8..19 = rw2, uv[3][2], packed_dims, packed, material, clip_base
-      uint32_t material = draw.material;  // (overlay pass: the overlay program, not an index into the material table)
-      const uint8_t *packed = nullptr;
-      uint32_t packed_dims = 0u;
-      if (!OVERLAY) {
-        // (the material's packed form travels in the draw descriptor: no load of the material table here)
-        packed = draw.packed;
-        packed_dims = draw.packed ? draw.packed_dims : 0u;
-      }
-      const unsigned long long packed_bits = (unsigned long long)reinterpret_cast<uintptr_t>(packed);
       if (OVERLAY) {
         // ib.inv_model row 0 = the light's colour, or the gizmo's viewMat whose upper 3x3 turns the normals
-        // (gizmo.vert:27).  draw.material is the program: 1 marker, 2 gizmo.  Varyings 0, 1 sit in the head, 2..5 in the body.
+        // (gizmo.vert:27).  draw.material is the program: 1 marker, 2 gizmo (not an index into the material table).
+        // Varyings 0, 1 sit in the head, 2..5 in the body.
         float o[3][6];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -806,58 +881,45 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
           }
         }
         if (keep) {
-          rec_store4(rec, 8, rw2, o[0][0], o[0][1], o[1][0]);
-          rec_store4(rec, 12, __float_as_uint(o[1][1]), __float_as_uint(o[2][0]), __float_as_uint(o[2][1]), packed_dims);
-          rec_store4(rec, 16, (uint32_t)packed_bits, (uint32_t)(packed_bits >> 32), material, kNotClipped);
-          rec_store4(rec, 20, o[0][2], o[1][2], o[2][2], o[0][3]);
-          rec_store4(rec, 24, o[1][3], o[2][3], o[0][4], o[1][4]);
-          rec_store4(rec, 28, o[2][4], o[0][5], o[1][5], o[2][5]);
+          rec_store_head_rest(rec, rw2, o[0], o[1], o[2], 0u, nullptr, draw.material);
+          rec_store4(rec, kRecBody, o[0][2], o[1][2], o[2][2], o[0][3]);
+          rec_store4(rec, kRecBody + 4, o[1][3], o[2][3], o[0][4], o[1][4]);
+          rec_store4(rec, kRecBody + 8, o[2][4], o[0][5], o[1][5], o[2][5]);
 #pragma unroll
-          for (int q = 32; q < kShadeRecDwords; q += 4) rec_store4(rec, q, 0.0f, 0.0f, 0.0f, 0.0f);
+          for (int q = kRecBody + 12; q < kShadeRecDwords; q += 4) rec_store4(rec, q, 0.0f, 0.0f, 0.0f, 0.0f);
         }
       } else {
-        if (keep) {
-          rec_store4(rec, 8, rw2, uv[0][0], uv[0][1], uv[1][0]);
-          rec_store4(rec, 12, __float_as_uint(uv[1][1]), __float_as_uint(uv[2][0]), __float_as_uint(uv[2][1]), packed_dims);
-          // (a clipped primitive's clip_base is patched in once the clipper has its arena slots, below)
-          rec_store4(rec, 16, (uint32_t)packed_bits, (uint32_t)(packed_bits >> 32), material, kNotClipped);
-        }
-        // :31-36  normalMat = transpose(mat3(aInvModel)).  Varying-major like the record's body: N of the three vertices, then
-        // T, then B, each 16-byte piece stored when its last value exists.
-        const f3 im0 = mk3(im_[0][0], im_[0][1], im_[0][2]), im1 = mk3(im_[1][0], im_[1][1], im_[1][2]),
-                 im2 = mk3(im_[2][0], im_[2][1], im_[2][2]);
+        // (the material's packed form travels in the draw descriptor: no load of the material table here)
+        if (keep) rec_store_head_rest(rec, rw2, uv[0], uv[1], uv[2], draw.packed ? draw.packed_dims : 0u, draw.packed, draw.material);
+        // Body varyings 3..11, varying-major like the rest of the body: N of the three vertices, then T, then B, each
+        // 16-byte piece stored when its last value exists (the interleaving holds the kernel at 64 registers).
         f3 N[3], T[3], B[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const f3 n = ld3(nrm[k]);
-          N[k] = normalize3(mk3(dot3(im0, n), dot3(im1, n), dot3(im2, n)));
-        }
+        for (int k = 0; k < 3; ++k) N[k] = normal_dir(im_, ld3(nrm[k]));
         if (keep) {
-          rec_store4(rec, 28, pwz2, N[0].x, N[1].x, N[2].x);
-          rec_store4(rec, 32, N[0].y, N[1].y, N[2].y, N[0].z);
+          rec_store4(rec, kRecBody + 8, pwz2, N[0].x, N[1].x, N[2].x);
+          rec_store4(rec, kRecBody + 12, N[0].y, N[1].y, N[2].y, N[0].z);
         }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const f3 tg = ld3(tng[k]);
-          T[k] = normalize3(mk3(dot3(im0, tg), dot3(im1, tg), dot3(im2, tg)));
-        }
+        for (int k = 0; k < 3; ++k) T[k] = normal_dir(im_, ld3(tng[k]));
         if (keep) {
-          rec_store4(rec, 36, N[1].z, N[2].z, T[0].x, T[1].x);
-          rec_store4(rec, 40, T[2].x, T[0].y, T[1].y, T[2].y);
+          rec_store4(rec, kRecBody + 16, N[1].z, N[2].z, T[0].x, T[1].x);
+          rec_store4(rec, kRecBody + 20, T[2].x, T[0].y, T[1].y, T[2].y);
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) B[k] = cross3(N[k], T[k]);
         if (keep) {
-          rec_store4(rec, 44, T[0].z, T[1].z, T[2].z, B[0].x);
-          rec_store4(rec, 48, B[1].x, B[2].x, B[0].y, B[1].y);
-          rec_store4(rec, 52, B[2].y, B[0].z, B[1].z, B[2].z);
+          rec_store4(rec, kRecBody + 24, T[0].z, T[1].z, T[2].z, B[0].x);
+          rec_store4(rec, kRecBody + 28, B[1].x, B[2].x, B[0].y, B[1].y);
+          rec_store4(rec, kRecBody + 32, B[2].y, B[0].z, B[1].z, B[2].z);
         }
       }
     }
   }
   BB_STAMP(2);
-  // ---- tile bins: walk each lane's tile range in lock-step, aggregating per tile across the wave; four insertions
-  // per lane are reserved back to back, so their returning atomics share one memory round trip ----
+  // ---- bins.  In: binned, tr, cls.  Out: bins / tile_count, refs (the references the wave wrote).  The lanes walk their tile
+  // ranges in lock-step, aggregating per tile across the wave; four insertions per lane are reserved back to back, so their
+  // returning atomics share one memory round trip ----
   uint32_t refs = 0;
   {
     const int tw = binned ? tr.tx1 - tr.tx0 + 1 : 0;
@@ -871,7 +933,7 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
         const int k = k0 + j;
         has[j] = k < nt;
         const int ty = has[j] ? tr.ty0 + k / tw : 0, tx = has[j] ? tr.tx0 + k % tw : 0;
-        if (has[j] && fp.world > 1 && ((ty / fp.band_tiles) % fp.world) != fp.rank) has[j] = false;  // another rank's band
+        if (has[j] && !row_owned(fp, ty)) has[j] = false;  // another rank's band
         seg[j] = ((uint32_t)ty * (uint32_t)fp.tiles_x + (uint32_t)tx) * kBinClasses + cls;
         tk[j] = wave_bin_reserve(has[j], seg[j], tile_count);
         refs += (uint32_t)__popcll(__ballot(has[j]));
@@ -881,41 +943,34 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
     }
   }
   BB_STAMP(3);
-  // ---- clipper (after the bins, so the other lanes' insertions never wait for it): the wave clips its clipped
-  // primitives one after the other, all lanes on the same polygon ----
+  // ---- clipper (after the bins, so the other lanes' insertions never wait for it).  In: needs_clip, vp.  Out: the clip arena's
+  // slots and the every-tile-list entries of the wave's clipped primitives, recs[prim].clip_base, clipped_raster.  The wave
+  // clips its clipped primitives one after the other, all lanes on the same polygon ----
   for (unsigned long long cm = __ballot(needs_clip); cm; cm &= cm - 1ull) {
     const int owner = __builtin_amdgcn_readfirstlane(__ffsll((long long)cm) - 1);
     ClipWork &w = s_clip[threadIdx.x >> 6];
-    // The owner's clip-space vertices and primitive index are the wave's input.  The vertices are not kept from phase 1
-    // (twelve registers in every lane, through the bin loop, for a handful of primitives per frame): the lanes that clip
-    // evaluate them again here from their positions -- vertex_clip_pos, the same bits.
+    // The owner's clip-space vertices and primitive index are the wave's input.  The vertices are not kept from the positions
+    // phase (twelve registers in every lane, through the bin loop, for a handful of primitives per frame): the lanes that clip
+    // evaluate them again here.
     float cv[3][4] = {};
     if (needs_clip) {
-      const DrawDesc cdraw = draws[find_draw(draws, n_draws, first_prims, prim)];
-      float pos[3][3];
-      Mat4 model;
-      load_positions(prim_source(cdraw, prim), pos, model);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        f3 unused;
-        const f4 c = vertex_clip_pos<OVERLAY>(model, pos[i], pv, view, fp, unused);
-        cv[i][0] = c.x; cv[i][1] = c.y; cv[i][2] = c.z; cv[i][3] = c.w;
-      }
+      float unused[3][3];
+      prim_clip_positions<OVERLAY>(draws, n_draws, first_prims, prim, pv, view, fp, cv, unused, [](int) {});
     }
     Viewport ovp = vp;  // the owner's viewport for the whole wave
     if (OVERLAY) {
       ovp.half_w = __shfl(vp.half_w, owner); ovp.half_h = __shfl(vp.half_h, owner);
       ovp.cx = __shfl(vp.cx, owner); ovp.cy = __shfl(vp.cy, owner);
     }
-    clip_primitive_wave<TILE_W, TILE_H>(w, owner, cv, prim, fp, ovp, clip_arena, ctr, broad_list);
+    clip_primitive_wave(w, owner, cv, prim, fp, ovp, clip_arena, ctr, broad_list);
     __builtin_amdgcn_wave_barrier();
     clipped_raster += (uint32_t)w.n_valid;
     if ((int)(threadIdx.x & 63) == owner && w.n_valid) recs[prim].clip_base = w.base;  // (the record itself was written above, with zero planes)
     __builtin_amdgcn_wave_barrier();
   }
   BB_STAMP(4);
-  // statistics leave the kernel as one record per WAVE (summed on the host on demand): a few thousand atomics on ONE
-  // counter word would serialise at ~90 per microsecond and dominate this kernel
+  // ---- statistics.  In: survives_out, needs_clip, clipped_raster, refs.  Out: one BlockStats record per WAVE (summed on the
+  // host on demand): a few thousand atomics on ONE counter word would serialise at ~90 per microsecond and dominate this kernel ----
   {
     const uint32_t n_survivors = (uint32_t)__popcll(__ballot(survives_out));
     const uint32_t n_clipped = (uint32_t)__popcll(__ballot(needs_clip));
@@ -1055,30 +1110,6 @@ BB_DEV int tile_index(int x, int y) {
   constexpr int BX = TILE_W / 8;
   return (((y >> 3) * BX + (x >> 3)) << 6) | ((y & 7) << 3) | (x & 7);
 }
-
-// The nine words coverage and depth need of a triangle: the first 36 bytes of a RasterTri (bb_types.h) and of an
-// every-tile-list entry, a column of k_raster's StagedTri.  Vertices in 24.8 fixed point, the depth plane relative to vertex 0.
-struct TriCore {
-  int X0, Y0, X1, Y1, X2, Y2;
-  float z0, dzdx, dzdy;
-};
-BB_DEV TriCore tri_core(const RasterTri &t) { return TriCore{t.X0, t.Y0, t.X1, t.Y1, t.X2, t.Y2, t.z0, t.dzdx, t.dzdy}; }
-// Pixels [x0, x1] x [y0, y1], both ends included: a tile, the frame, the gizmo's scissor, a triangle's box; and what two share.
-struct PixRect {
-  int x0, x1, y0, y1;
-  BB_DEV bool any() const { return x0 <= x1 && y0 <= y1; }
-};
-BB_DEV PixRect intersect(const PixRect &a, const PixRect &b) { return PixRect{max(a.x0, b.x0), min(a.x1, b.x1), max(a.y0, b.y0), min(a.y1, b.y1)}; }
-// the larger side of a triangle's bounding box, in 1/256 pixel
-BB_DEV int tri_span(const TriCore &t) { return max(max(t.X0, max(t.X1, t.X2)) - min(t.X0, min(t.X1, t.X2)), max(t.Y0, max(t.Y1, t.Y2)) - min(t.Y0, min(t.Y1, t.Y2))); }
-// The pixels whose CENTRES lie inside a triangle's bounding box and inside rectangles `a` and `b`, clamped in this order.
-BB_DEV PixRect pixel_box(const TriCore &t, const PixRect &a, const PixRect &b) {
-  const int32_t minX = min(t.X0, min(t.X1, t.X2)), maxX = max(t.X0, max(t.X1, t.X2));
-  const int32_t minY = min(t.Y0, min(t.Y1, t.Y2)), maxY = max(t.Y0, max(t.Y1, t.Y2));
-  return PixRect{max(max((minX - 128 + 255) >> 8, a.x0), b.x0), min(min((maxX - 128) >> 8, a.x1), b.x1),
-                 max(max((minY - 128 + 255) >> 8, a.y0), b.y0), min(min((maxY - 128) >> 8, a.y1), b.y1)};
-}
-BB_DEV PixRect pixel_box(const TriCore &t, const PixRect &r) { return pixel_box(t, r, r); }
 
 // overlay pass: primitives from fp.ov_first_gizmo_prim on are the gizmo -- scissored to its rectangle (src/main.cpp:767-772)
 // and lifted above every other depth (see depth_max); `ref` is a bin reference (primitive << 3 | sub-triangle)
@@ -3123,31 +3154,6 @@ BB_DEV bool tbn_make_segment(const float *p0, const float *p1, const Viewport &v
   return r.X0 != r.X1 || r.Y0 != r.Y1;
 }
 
-// Reserve `has` lanes a slot in tile `tile`'s bin: lanes of the wave that name the same tile share ONE returning atomic
-// (neighbouring triangles of a wave land in the same few tiles; one atomic per lane on a far ball's tile counter
-// serialised the whole pass).  Called by every active lane of the wave.
-BB_DEV uint32_t tbn_wave_reserve(bool has, uint32_t tile, uint32_t *tile_count) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long pending = __ballot(has);
-  int leader = lane;
-  uint32_t rank = 0, gsize = 0;
-  while (pending) {
-    const int l = __builtin_amdgcn_readfirstlane(__ffsll((long long)pending) - 1);
-    const uint32_t lt = (uint32_t)__builtin_amdgcn_readlane((int)tile, l);
-    const bool mine = has && tile == lt;
-    const unsigned long long m = __ballot(mine);
-    if (mine) {
-      leader = l;
-      rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      gsize = (uint32_t)__popcll(m);
-    }
-    pending &= ~m;
-  }
-  uint32_t base = 0;
-  if (has && lane == leader) base = atomicAdd(&tile_count[tile], gsize);
-  return (uint32_t)__shfl((int)base, leader) + rank;
-}
-
 // Bin a segment (valid) to every tile its pixel bounding box (one pixel of slack each side) meets inside the target; the
 // lanes of a wave walk their tile ranges in lock-step.  A full bin raises overflow bit 0 and reports the count it needed;
 // the host grows the bins and redoes the pass.  Called by every active lane of the wave.
@@ -3160,7 +3166,7 @@ BB_DEV void tbn_bin(bool valid, const TbnSeg &s, uint32_t index, const TbnParams
   for (int k = 0; __ballot(k < nt) != 0ull; ++k) {
     const bool has = k < nt;
     const uint32_t t = has ? (uint32_t)(ty0 + k / tw) * (uint32_t)tp.tiles_x + (uint32_t)(tx0 + k % tw) : 0u;
-    const uint32_t slot = tbn_wave_reserve(has, t, tile_count);
+    const uint32_t slot = bin_slot(wave_bin_reserve(has, t, tile_count));
     if (!has) continue;
     if (slot < tp.bin_cap) {
       bins[(size_t)t * tp.bin_cap + slot] = index;
@@ -3181,34 +3187,27 @@ __global__ __launch_bounds__(256) void k_tbn_segments(const DrawDesc *__restrict
                                                       uint32_t *__restrict__ bins, uint32_t *__restrict__ ctr) {
   const uint32_t prim = blockIdx.x * blockDim.x + threadIdx.x;
   if (prim >= n_prims) return;
-  uint32_t d = 0;
-  while (d + 1 < n_draws && prim >= draws[d + 1].first_prim) ++d;
-  const DrawDesc draw = draws[d];
-  const uint32_t local = prim - draw.first_prim;
-  const uint32_t inst = local / draw.tris_per_instance;
-  const uint32_t tri = local - inst * draw.tris_per_instance;
-  const InstanceBlock &ib = draw.instances[inst];
-  uint32_t vi[3] = {3u * tri, 3u * tri + 1u, 3u * tri + 2u};
-  if (draw.indices) {
-    vi[0] = draw.indices[3u * tri]; vi[1] = draw.indices[3u * tri + 1u]; vi[2] = draw.indices[3u * tri + 2u];
-  }
-  const f3 im0 = mk3(ib.inv_model.M[0][0], ib.inv_model.M[0][1], ib.inv_model.M[0][2]);
-  const f3 im1 = mk3(ib.inv_model.M[1][0], ib.inv_model.M[1][1], ib.inv_model.M[1][2]);
-  const f3 im2 = mk3(ib.inv_model.M[2][0], ib.inv_model.M[2][1], ib.inv_model.M[2][2]);
+  const DrawDesc draw = draws[find_draw(draws, n_draws, prim)];
+  const PrimSource src = prim_source(draw, prim);
+  float im_[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int cc = 0; cc < 3; ++cc) im_[r][cc] = src.ib->inv_model.M[r][cc];
   f3 P[3], T[3], B[3], N[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const Vertex &v = draw.vertices[vi[k]];
-    // tbn.vert:18-25 -- the same expressions as k_geometry's vertex stage (forward_brdf.vert:25,31-35)
-    const f4 w = mat4_mul(ib.model, f4{v.pos[0], v.pos[1], v.pos[2], 1.0f});
-    const f3 n = ld3(v.normal), tg = ld3(v.tangent);
-    f3 Nk = normalize3(mk3(dot3(im0, n), dot3(im1, n), dot3(im2, n)));
-    f3 Tk = normalize3(mk3(dot3(im0, tg), dot3(im1, tg), dot3(im2, tg)));
+    const GlobalVertex v = src.v[k];
+    // tbn.vert:18-25 is the forward pass's vertex program: the same functions as k_geometry
+    const float pos[3] = {v->pos[0], v->pos[1], v->pos[2]};
+    const f4 w = vertex_world(src.ib->model, pos);
+    f3 Nk = normal_dir(im_, mk3(v->normal[0], v->normal[1], v->normal[2]));
+    f3 Tk = normal_dir(im_, mk3(v->tangent[0], v->tangent[1], v->tangent[2]));
     f3 Bk = cross3(Nk, Tk);
     if (enable_normal_map != 0) {
       // tbn.vert:27-42: a vertex-stage fetch with k_shade's sampler (bilinear, REPEAT, LOD 0), then the TBN product
       const TexDesc td = materials[draw.material].maps[kMapNormal];
-      const BilinearTaps tp_ = bilinear_taps(v.uv[0], v.uv[1], td.w, td.h);
+      const BilinearTaps tp_ = bilinear_taps(v->uv[0], v->uv[1], td.w, td.h);
       const uint32_t *tx32 = reinterpret_cast<const uint32_t *>(td.texels);
       const uint32_t t00 = tx32[tp_.o00], t10 = tx32[tp_.o10], t01 = tx32[tp_.o01], t11 = tx32[tp_.o11];
       const float sx = filter_channel(t00, t10, t01, t11, 0, tp_.fx, tp_.fy) * 2.0f - 1.0f;

@@ -155,6 +155,13 @@ static_assert(sizeof(ShadeRec) == 224 && offsetof(ShadeRec, uv) == 36 && offseto
                   offsetof(ShadeRec, vary) == 80, "ShadeRec");
 constexpr uint32_t kNotClipped = 0xFFFFFFFFu;
 constexpr int kShadeRecDwords = sizeof(ShadeRec) / 4;
+// k_geometry stores the record in sixteen-byte pieces (rec_store4); where they start, in dwords: the planes (two pieces), the
+// rest of the head from h.rw2 on (three), the body (nine: piece i holds vary[][] flat elements 4 i .. 4 i + 3)
+constexpr int kRecPlanes = offsetof(ShadeRec, h) / 4;
+constexpr int kRecHeadRest = offsetof(ShadeRec, h.rw2) / 4;
+constexpr int kRecBody = offsetof(ShadeRec, vary) / 4;
+static_assert(kRecHeadRest == kRecPlanes + 8 && offsetof(ShadeRec, clip_base) / 4 == kRecHeadRest + 11 && kRecBody == kRecHeadRest + 12 &&
+                  kRecBody % 4 == 0 && kShadeRecDwords == kRecBody + 36, "ShadeRec pieces");
 
 struct DrawDesc {
   const Vertex *vertices;

@@ -8,7 +8,7 @@ pass and tile size both are rendered, and what k_geometry wrote per primitive is
      infinities included), its material binding is its draw's, its clip_base says whether it was clipped
   3  setup: of the unclipped ones, snapped coordinates, 1/w, z0 and the five planes of head and triangle are the contract's
      projection and setup_tri of the oracle's clip position (the pass's own order of P, V), restated in numpy
-  4  k_tbn_segments, the other copy of the expressions, against tests/tbn_reference.py on the same scenes
+  4  k_tbn_segments, the other caller of the expressions, against tests/tbn_reference.py on the same scenes
   5  the read-back is idempotent, survives the overlay pass and fails as documented
 Each case is two frames of 20 480 pixels and 154 primitives; the file's wall time is recorded in tests/golden/vertex_chart.json."""
 import ctypes as C
