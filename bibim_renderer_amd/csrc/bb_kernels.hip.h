@@ -2920,13 +2920,16 @@ __global__ __launch_bounds__(kPresentThreads) void k_present(const float4 *__res
 // ------------------------------------------------------------------------------------------------
 // The wire forms of the exchange (include/bibim_hip.h, BBR_SHARD_*): what a rank's shard of n = shard_rows * width pixels
 // looks like while it travels.  One struct per form: Whole = pixel of the whole frame it unpacks to, block_bytes(n) = size
-// of one rank's block, load(block, j, n) = pixel j of a block.  How a block is made from the shard: bibim_hip.hip, kWireForms.
+// of one rank's block, load(block, j, n) = pixel j of a block, kLoadAlign = the widest access load() makes (what a gather
+// buffer must be aligned to; every block size is a multiple of it, so every block of the buffer is aligned with its first).
+// How a block is made from the shard: bibim_hip.hip, kWireForms.
 // ------------------------------------------------------------------------------------------------
 
 // the shard as it is, [shard_rows][width] pixels: the fp32 one, or the presented RGBA8 one
 template <class Pixel>
 struct WirePlain {
   using Whole = Pixel;
+  static constexpr size_t kLoadAlign = sizeof(Pixel);
   static constexpr __host__ __device__ size_t block_bytes(size_t n) { return n * sizeof(Pixel); }
   static __device__ Whole load(const uint8_t *block, size_t j, size_t) { return reinterpret_cast<const Pixel *>(block)[j]; }
 };
@@ -2937,9 +2940,10 @@ using WireRgba8 = WirePlain<uint32_t>;
 // geometry was shaded and 0.0 on cleared pixels (forward_brdf.frag:75 writes 1, the clear colour is 0, src/main.cpp:84;
 // the deferred path writes 1 everywhere), so it travels as one bit.
 //   block = rgb[n][3] float, padding to 8 bytes, one 64-bit mask per 64 pixels (bit k of word w = pixel 64 w + k), padding
-//   to 16 bytes
+//   to 16 bytes; the padding bytes are zero
 struct WirePacked {
   using Whole = float4;
+  static constexpr size_t kLoadAlign = 8;  // the mask words
   static constexpr __host__ __device__ size_t mask_offset(size_t n) { return (n * 12 + 7) & ~(size_t)7; }
   static constexpr __host__ __device__ size_t block_bytes(size_t n) { return (mask_offset(n) + ((n + 63) / 64) * 8 + 15) & ~(size_t)15; }
   static __device__ Whole load(const uint8_t *block, size_t j, size_t n) {
@@ -2955,6 +2959,7 @@ struct WirePacked {
 // frame is widened back to RGBA32F (every binary16 value is a binary32 value).
 struct WireRgba16f {
   using Whole = float4;
+  static constexpr size_t kLoadAlign = 8;  // a pixel's four halves in one load
   static constexpr __host__ __device__ size_t block_bytes(size_t n) { return n * 8; }
   static __device__ Whole load(const uint8_t *block, size_t j, size_t) {
     const uint2 w = reinterpret_cast<const uint2 *>(block)[j];
@@ -2978,6 +2983,12 @@ __global__ void k_pack_shard(const float4 *__restrict__ shard, float *__restrict
   }
   const unsigned long long m = __ballot(live && __float_as_uint(p.w) == 0x3F800000u);
   if ((threadIdx.x & 63) == 0 && live) mask[i >> 6] = m;
+  if (i == 0) {
+    // the block's padding is zero: a block is a function of the shard alone, whatever the buffer held before
+    const size_t words = (n + 63) / 64;
+    if (n & 1) rgb[3 * n] = 0.f;                                                // 12 n mod 8 = 4: four bytes in front of the masks
+    if ((WirePacked::mask_offset(n) + words * 8) & 15) mask[words] = 0ull;      // eight bytes behind them
+  }
 }
 
 // fp32 shard -> WireRgba16f block

@@ -2319,6 +2319,10 @@ struct WireForm {
   size_t (*block_bytes)(size_t n);  // bytes of one rank's block of n pixels
   size_t whole_pixel_bytes;         // per pixel of the whole frame an exchange of this form leaves behind
   bool presented;                   // made of the presented shard (needs bbr_present), not of the fp32 frame (no present_fused)
+  // alignment (include/bibim_hip.h, "Alignment"), each the widest access a kernel makes there: of a block that is written
+  // (pack's stores; a plain form is copied, and k_push_block's narrow form stores 4-byte words), of a gather buffer that is
+  // un-interleaved (Form::load).  The whole frame is stored a pixel at a time: whole_pixel_bytes.
+  size_t block_align, gathered_align;
   void (*pack)(const float4 *shard, void *block, size_t n, hipStream_t st);  // nullptr: the shard already is the block
   void (*unpack)(const bbr_context *c, const void *gathered, void *whole, hipStream_t st);
 };
@@ -2337,13 +2341,21 @@ void unpack(const bbr_context *c, const void *gathered, void *whole, hipStream_t
 }
 template <class Form>
 constexpr WireForm wire_form(bool presented, decltype(WireForm::pack) pack) {
-  return {&Form::block_bytes, sizeof(typename Form::Whole), presented, pack, &unpack<Form>};
+  return {&Form::block_bytes, sizeof(typename Form::Whole), presented, pack ? (size_t)8 : (size_t)4, Form::kLoadAlign, pack, &unpack<Form>};
 }
 const WireForm kWireForms[] = {wire_form<WireRgba32f>(false, nullptr), wire_form<WirePacked>(false, pack_packed),
                                wire_form<WireRgba8>(true, nullptr), wire_form<WireRgba16f>(false, pack_half)};
 static_assert(BBR_SHARD_RGBA32F == 0 && BBR_SHARD_PACKED == 1 && BBR_SHARD_RGBA8 == 2 && BBR_SHARD_RGBA16F == 3, "kWireForms");
 
 bool valid_form(int form) { return form >= 0 && form < (int)(sizeof(kWireForms) / sizeof(kWireForms[0])); }
+bool aligned(const void *p, size_t a) { return ((uintptr_t)p % a) == 0; }
+// nothing is launched on a pointer a kernel would access misaligned
+int check_unpack_pointers(bbr_context *c, int form, const void *gathered, const void *whole, const char *who) {
+  const WireForm &f = kWireForms[form];
+  if (!aligned(gathered, f.gathered_align) || !aligned(whole, f.whole_pixel_bytes))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": gather buffer or whole frame not aligned for this form (include/bibim_hip.h, Alignment)");
+  return BBR_OK;
+}
 size_t exchange_block_bytes(const bbr_context *c, int form) { return kWireForms[form].block_bytes(c->shard_pixels()); }
 size_t whole_frame_bytes(const bbr_context *c, int form) { return (size_t)c->width * c->height * kWireForms[form].whole_pixel_bytes; }
 
@@ -2415,6 +2427,7 @@ int unpack_gathered(bbr_context *c, int form, const void *gathered, void *frame,
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!gathered || !frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "unpack_gathered: NULL");
+  if (int rc = check_unpack_pointers(c, form, gathered, frame, "unpack_gathered")) return rc;
   return unpack_whole(c, form, gathered, frame, stream ? (hipStream_t)stream : c->shade_stream());
 }
 
@@ -2472,6 +2485,8 @@ int bbr_stage_shard(bbr_context *c, int32_t form, void *block_device, void *stre
   int rc = check_exchange(c, form, "stage_shard");
   if (rc) return rc;
   if (!block_device) return fail(c, BBR_ERR_INVALID_ARGUMENT, "stage_shard: NULL");
+  if (!aligned(block_device, kWireForms[form].block_align))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "stage_shard: block not aligned for this form (include/bibim_hip.h, Alignment)");
   FrameSlot &s = c->slots[c->last_slot];
   hipStream_t st = stream ? (hipStream_t)stream : s.stream_used;  // a caller's stream must already wait for the frame
   return stage_block(c, s, form, block_device, st);
@@ -2505,6 +2520,10 @@ int bbr_allgather_frame(bbr_context *c, int32_t form, void *gathered, void *whol
   if (!c->comm) return fail(c, BBR_ERR_NOT_IN_FRAME, "allgather_frame: no communicator (bbr_comm_init)");
   if (c->comm_rank != c->rank || c->comm_world != c->world)
     return fail(c, BBR_ERR_INVALID_ARGUMENT, "allgather_frame: the communicator's rank / world differ from the partition's (bbr_set_partition)");
+  if (!aligned(gathered, kWireForms[form].block_align))  // (NULL passes every check: the slot's own buffers are hipMalloc'ed)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "allgather_frame: gather buffer not aligned for this form (include/bibim_hip.h, Alignment)");
+  rc = check_unpack_pointers(c, form, gathered, whole, "allgather_frame");
+  if (rc) return rc;
   FrameSlot &s = c->slots[c->last_slot];
   const size_t block = exchange_block_bytes(c, form);
   if (!gathered) {
@@ -2543,6 +2562,9 @@ int bbr_push_shard(bbr_context *c, int32_t form, void *const *peer_gathered, con
   HIP_TRY(c, s.follow(st));
   for (int p = 0; p < c->world; ++p)
     if (!peer_gathered[p]) return fail(c, BBR_ERR_INVALID_ARGUMENT, "push_shard: a peer's gather buffer is NULL");
+  for (int p = 0; p < c->world; ++p)
+    if (!aligned(peer_gathered[p], kWireForms[form].block_align))
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, "push_shard: a peer's gather buffer is not aligned for this form (include/bibim_hip.h, Alignment)");
   // the block is made once, in this rank's own gather buffer, and goes from there to the peers
   uint8_t *mine = (uint8_t *)peer_gathered[c->rank] + block * (size_t)c->rank;
   rc = stage_block(c, s, form, mine, st);
@@ -2600,6 +2622,7 @@ int bbr_unpack_whole(bbr_context *c, int32_t form, const void *gathered, void *w
   BBR_ON_DEVICE(c);
   if (!valid_form(form) || !gathered) return fail(c, BBR_ERR_INVALID_ARGUMENT, "unpack_whole: bad form / NULL");
   if (c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "unpack_whole: nothing rendered");
+  if (int rc = check_unpack_pointers(c, form, gathered, whole, "unpack_whole")) return rc;
   FrameSlot &s = c->slots[c->last_slot];
   if (!whole) {
     HIP_TRY(c, s.d_whole.ensure(whole_frame_bytes(c, form)));

@@ -464,6 +464,20 @@ int bbr_tone_map(bbr_context *ctx, int32_t enable_tone_mapping, float exposure);
  * output, see the define).  `gathered` / `whole` = NULL use buffers owned by the frame's slot
  * (bbr_whole_frame_device_ptr, bbr_read_whole_frame).  An exchange never re-renders (one rank alone must not repeat a
  * collective): let the capacities settle with one synchronised frame first, as after any scene change.
+ * BBR_SHARD_PACKED in full: rgb[n][3] float (n = shard_rows * width), padding to 8 bytes, one little-endian 64-bit mask per
+ * 64 pixels (bit k of word w = pixel 64 w + k, set where alpha has the bits of 1.0f; unused bits of the last word clear),
+ * padding to 16 bytes.  The padding bytes are written as zero: a block depends on the shard alone.
+ * Alignment.  Every pointer below is accessed by a kernel at the width given (bytes); a call whose pointer is not a
+ * multiple of it returns BBR_ERR_INVALID_ARGUMENT and launches nothing.  Every block size is a multiple of its form's
+ * figures (with a partition, of 16), so block r of an aligned gather buffer is aligned as well.
+ *                                                                      RGBA32F  PACKED  RGBA8  RGBA16F
+ *   block written: bbr_stage_shard / bbr_pack_shard `block_device`,
+ *     bbr_push_shard every peer_gathered[], bbr_allgather_frame gathered      4       8      4        8
+ *   gather buffer read: bbr_unpack_whole, bbr_unpack_gathered*,
+ *     bbr_allgather_frame `gathered_device`                                  16       8      4        8
+ *   whole frame written: `whole_device` / `frame_device` of the same         16      16      4       16
+ * (the mask words and a binary16 pixel are 8-byte accesses, an RGBA32F pixel a 16-byte one; a plain block is copied, and
+ * stored by bbr_push_shard in 16-byte pieces when every gather buffer is 16-byte aligned, in 4-byte words otherwise).
  * Not yet run on more than one GPU: see DESIGN.md section 5. */
 #define BBR_COMM_ID_BYTES 128
 #define BBR_IPC_HANDLE_BYTES 64
