@@ -2633,6 +2633,8 @@ struct UvFootprint {
 struct AnisoTaps {
   int n;
   float du, dv;
+  float mx;     // the long axis' squared length in texels (the level rule of k_shade_mip starts from it)
+  bool finite;  // all four differences are
 };
 BB_DEV AnisoTaps aniso_taps(const UvFootprint &f, int w, int h, int max_aniso) {
   const float fw = (float)w, fh = (float)h;
@@ -2653,7 +2655,15 @@ BB_DEV AnisoTaps aniso_taps(const UvFootprint &f, int w, int h, int max_aniso) {
   t.n = n;
   t.du = x_axis ? f.dudx : f.dudy;
   t.dv = x_axis ? f.dvdx : f.dvdy;
+  t.mx = mx;
+  t.finite = finite;
   return t;
+}
+
+// extent of level d of a chain whose level 0 has n texels along this axis: max(1, n >> d)
+BB_DEV int level_extent(int n, int d) {
+  const int m = n >> d;
+  return m > 0 ? m : 1;
 }
 
 // What a tap is made of, for the two storage forms.  load() asks for the four texels of the bilinear footprint at (u, v),
@@ -2674,6 +2684,10 @@ struct PackedFetch {  // the packed material: 9-byte records, block-linear (issu
     r.fx = tp.fx; r.fy = tp.fy;
     return r;
   }
+  BB_DEV int width() const { return w; }
+  BB_DEV int height() const { return h; }
+  // the same set on level d of its chain, whose texels start at `level`
+  BB_DEV PackedFetch at(const uint8_t *level, int d) const { return PackedFetch{(GlobalBytes)level, level_extent(w, d), level_extent(h, d)}; }
   BB_DEV static void add(const Raw &r, float (&acc)[kChannels]) {
     acc[0] = acc[0] + filter_channel(r.q00.x, r.q10.x, r.q01.x, r.q11.x, 0, r.fx, r.fy);
     acc[1] = acc[1] + filter_channel(r.q00.x, r.q10.x, r.q01.x, r.q11.x, 8, r.fx, r.fy);
@@ -2692,6 +2706,9 @@ struct MapFetch {  // one RGBA8 map of the material table, its first CHANNELS ch
   TexDesc td;
   typedef MapTap Raw;
   BB_DEV Raw load(float u, float v) const { return load_map_tap(td, u, v); }
+  BB_DEV int width() const { return td.w; }
+  BB_DEV int height() const { return td.h; }
+  BB_DEV MapFetch at(const uint8_t *level, int d) const { return MapFetch{TexDesc{level, level_extent(td.w, d), level_extent(td.h, d)}}; }
   BB_DEV static void add(const Raw &r, float (&acc)[kChannels]) {
 #pragma unroll
     for (int k = 0; k < kChannels; ++k) acc[k] = acc[k] + map_channel(r, k);
@@ -2721,15 +2738,37 @@ BB_DEV void aniso_sample(const Fetch &fetch, const UvFootprint &f, const AnisoTa
   for (int k = 0; k < Fetch::kChannels; ++k) value[k] = t.n == 1 ? acc[k] : acc[k] * rn;
 }
 
-template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
-__global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
+// The level of detail a filter chose for one texture: level d and the weight delta of level d + 1 (both 0 on level 0 alone)
+struct Lod {
+  int d;
+  float delta;
+};
+
+// The filter of "max_anisotropy": level 0 alone.  A filter's sample() takes one texture of a material -- `set` = its map, or
+// kMapCount for the packed set -- as the Fetch of its level 0, fills the filtered value of every channel and the level
+// choice, and returns the tap count N.
+struct AnisoFilter {
+  int max_aniso;
+  template <class Fetch>
+  BB_DEV uint32_t sample(const Fetch &fetch, uint32_t material, int set, const UvFootprint &f, float (&value)[Fetch::kChannels], Lod &lod) const {
+    const AnisoTaps t = aniso_taps(f, fetch.width(), fetch.height(), max_aniso);
+    aniso_sample(fetch, f, t, value);
+    lod = Lod{0, 0.0f};
+    return (uint32_t)t.n;
+  }
+};
+
+// The fragment stage with a footprint: what k_shade_aniso and k_shade_mip are, up to the filter.  One launch shades every
+// item (each wave walks the list with the launch's stride) and every lane gathers its own record.
+template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP, class Filter>
+BB_DEV void shade_item_list(
     const uint32_t *__restrict__ items, const uint32_t *__restrict__ item_count,
     const unsigned long long *__restrict__ frags, const uint32_t *__restrict__ frag_count,
     const ShadeRec *__restrict__ recs, const ClipSlot *__restrict__ clip_arena,
-    FrameParams fp, ShadeParams sp, const CookedLight *__restrict__ cooked,
+    const FrameParams &fp, const ShadeParams &sp, const CookedLight *__restrict__ cooked,
     const MaterialDesc *__restrict__ materials, float4 *__restrict__ out,
     uint2 *__restrict__ gbuffer, const SrgbTables *__restrict__ tables, uint32_t *__restrict__ out8,
-    Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups, int max_aniso,
+    Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups, const Filter &filter,
     float *__restrict__ dump) {
   constexpr int TILE_PIXELS = TILE_W * TILE_H;
   const ConstLights lights_c{(ConstCooked)cooked};
@@ -2787,56 +2826,51 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
     f3 albedo, nt = mk3(0.f, 0.f, 0.f);
     float metallic, roughness, ao, height = 0.0f;
     uint32_t taps[kMapCount] = {};  // (DUMP: the tap count used for each map, 0 = not sampled)
+    Lod lod = {0, 0.0f}, height_lod = {0, 0.0f};  // (DUMP: the level choice of the packed set / the albedo map, and of the height map)
     const MaterialDesc &md = materials[material];
     if (packed_dims != 0u) {
       const PackedFetch fetch{packed_texels, (int)(packed_dims & 0xFFFFu), (int)(packed_dims >> 16)};
-      const AnisoTaps t = aniso_taps(f, fetch.w, fetch.h, max_aniso);
       float s[PackedFetch::kChannels];
-      aniso_sample(fetch, f, t, s);
+      const uint32_t n = filter.sample(fetch, material, kMapCount, f, s, lod);
       albedo = mk3(s[0], s[1], s[2]);
       metallic = s[3]; roughness = s[4]; ao = s[5];
       if (normal_map) nt = mk3(normal_map_axis(s[6]), normal_map_axis(s[7]), normal_map_axis(s[8]));
-      taps[kMapAlbedo] = taps[kMapMetallic] = taps[kMapRoughness] = taps[kMapAO] = (uint32_t)t.n;
-      if (normal_map) taps[kMapNormal] = (uint32_t)t.n;
+      taps[kMapAlbedo] = taps[kMapMetallic] = taps[kMapRoughness] = taps[kMapAO] = n;
+      if (normal_map) taps[kMapNormal] = n;
     } else {
-      // maps of different sizes: a tap count and a tap loop per map
-      auto one = [&](int map, auto channels, float *value) {
-        const TexDesc &td = md.maps[map];
-        const MapFetch<decltype(channels)::value> fetch{td};
-        const AnisoTaps t = aniso_taps(f, td.w, td.h, max_aniso);
+      // maps of different sizes: a tap count, a level choice and a tap loop per map
+      auto one = [&](int map, auto channels, float *value, Lod &map_lod) {
+        const MapFetch<decltype(channels)::value> fetch{md.maps[map]};
         float s[decltype(channels)::value];
-        aniso_sample(fetch, f, t, s);
+        taps[map] = filter.sample(fetch, material, map, f, s, map_lod);
 #pragma unroll
         for (int k = 0; k < decltype(channels)::value; ++k) value[k] = s[k];
-        taps[map] = (uint32_t)t.n;
       };
       float s3[3];
-      one(kMapAlbedo, std::integral_constant<int, 3>{}, s3);
+      Lod other;
+      one(kMapAlbedo, std::integral_constant<int, 3>{}, s3, lod);
       albedo = mk3(s3[0], s3[1], s3[2]);
-      one(kMapMetallic, std::integral_constant<int, 1>{}, &metallic);
-      one(kMapRoughness, std::integral_constant<int, 1>{}, &roughness);
-      one(kMapAO, std::integral_constant<int, 1>{}, &ao);
+      one(kMapMetallic, std::integral_constant<int, 1>{}, &metallic, other);
+      one(kMapRoughness, std::integral_constant<int, 1>{}, &roughness, other);
+      one(kMapAO, std::integral_constant<int, 1>{}, &ao, other);
       if (normal_map) {
-        one(kMapNormal, std::integral_constant<int, 3>{}, s3);
+        one(kMapNormal, std::integral_constant<int, 3>{}, s3, other);
         nt = mk3(normal_map_axis(s3[0]), normal_map_axis(s3[1]), normal_map_axis(s3[2]));
       }
     }
     const f3 normal = surface_normal<DEFERRED>(a, sp.enable_normal_map, [&] { return nt; });
     if (DEFERRED && (DUMP || gbuffer) && valid) {  // gbuffer.frag's sixth fetch: only when somebody asked to see the texel
-      const TexDesc &td = md.maps[kMapHeight];
-      const MapFetch<1> fetch{td};
-      const AnisoTaps t = aniso_taps(f, td.w, td.h, max_aniso);
+      const MapFetch<1> fetch{md.maps[kMapHeight]};
       float s[1];
-      aniso_sample(fetch, f, t, s);
+      taps[kMapHeight] = filter.sample(fetch, material, kMapHeight, f, s, height_lod);
       height = s[0];
-      taps[kMapHeight] = (uint32_t)t.n;
     }
     if (DUMP && valid) {
       float *d = dump + ((size_t)gy * (size_t)fp.width + (size_t)gx) * kSurfaceFloats;
       const float rec[kSurfaceFloats] = {f.u, f.v, f.dudx, f.dvdx, f.dudy, f.dvdy, a[2], a[3], a[4], normal.x, normal.y, normal.z,
                                          albedo.x, albedo.y, albedo.z, metallic, roughness, ao, height, nt.x, nt.y, nt.z,
                                          (float)taps[0], (float)taps[1], (float)taps[2], (float)taps[3], (float)taps[4], (float)taps[5],
-                                         0.f, 0.f, 0.f, 0.f};
+                                         (float)lod.d, lod.delta, (float)height_lod.d, height_lod.delta};
 #pragma unroll
       for (int k = 0; k < kSurfaceFloats; ++k) d[k] = rec[k];
     }
@@ -2845,6 +2879,152 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
                                                   valid, gx, gy, [&] { return height; });
     store_colour<PRESENT>(valid, color, o, out, out8, tables, sp);
   }
+}
+
+template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
+__global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
+    const uint32_t *__restrict__ items, const uint32_t *__restrict__ item_count,
+    const unsigned long long *__restrict__ frags, const uint32_t *__restrict__ frag_count,
+    const ShadeRec *__restrict__ recs, const ClipSlot *__restrict__ clip_arena,
+    FrameParams fp, ShadeParams sp, const CookedLight *__restrict__ cooked,
+    const MaterialDesc *__restrict__ materials, float4 *__restrict__ out,
+    uint2 *__restrict__ gbuffer, const SrgbTables *__restrict__ tables, uint32_t *__restrict__ out8,
+    Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups, int max_aniso,
+    float *__restrict__ dump) {
+  shade_item_list<TILE_W, TILE_H, DEFERRED, PRESENT, DUMP>(items, item_count, frags, frag_count, recs, clip_arena, fp, sp, cooked, materials, out,
+                                                           gbuffer, tables, out8, ctr, ctr_done, item_groups, AnisoFilter{max_aniso}, dump);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Mip chains and the trilinear filter (option "mip_levels" >= 2; src/render.cpp:1363-1365: the reference's sampler has
+// mipmapMode LINEAR, on images of one level).  The rule, in binary32 and in this operand order (DESIGN.md section 3;
+// restated independently in tests/mip_reference.py):
+//   chain      a map of w x h texels has L = min(mip_levels, 1 + floor(log2 max(w, h))) levels, level k of max(1, w >> k) x
+//              max(1, h >> k) texels.  Per channel byte, texel (x, y) of level k + 1 = (s + 2) >> 2, s the integer sum of
+//              the level-k bytes at columns min(2x, w_k - 1), min(2x + 1, w_k - 1) and the same two rows.  A packed
+//              material's level k is the packed form (bb_pack.h) of the five level-k maps.
+//   N          the anisotropic rule's footprint and tap count on the LEVEL-0 size (mx: the long axis' squared length)
+//   level      P = mx * R2[N], R2[k] the binary32 nearest to 1 / k^2.  A difference not finite, or !(P > 1): d = 0, delta = 0.
+//              Otherwise from P's bits b: e = (b >> 23) - 127, d = e >> 1, delta = 0.5 * ((float)(e & 1) + (float)(b &
+//              0x7FFFFF) * 2^-23), every step exact; d >= L - 1 (+inf included): d = L - 1, delta = 0.  (lambda = 1/2 log2 P
+//              with log2(1 + t) taken as t: low by at most 0.043 level)
+//   value      hi = the anisotropic rule's taps and average on level d's size (tap offsets are in uv: the same on every
+//              level; wrapping and the 2^30 cutoff per level); delta == 0: value = hi, nothing else happens; otherwise lo =
+//              the same on level d + 1 and value = fmaf(delta, lo - hi, hi) per channel.
+// The chain is built at upload / option time by k_mip_reduce and k_mip_pack; the shading kernel finds the levels through
+// a table per material (MipTable) that only it reads.
+// ------------------------------------------------------------------------------------------------
+constexpr int kMaxMipLevels = 15;        // the full chain of the largest map the ABI takes (16384)
+constexpr int kMipSets = kMapCount + 1;  // the six maps, and the packed set (index kMapCount)
+struct MipSet {
+  int32_t levels;  // L >= 1 of a live material
+  int32_t pad;
+  const uint8_t *level[kMaxMipLevels];  // where level k's texels start (level 0: the material's own allocation)
+};
+struct MipTable {
+  MipSet set[kMipSets];
+};
+static_assert(sizeof(MipSet) == 128 && sizeof(MipTable) == 896, "MipTable");
+
+// R2[k] = 1 / k^2 correctly rounded, k = 1 .. 16
+__constant__ float kMipRcp2[kMaxAnisotropy + 1] = {
+    0.0f,         1.0f,          1.0f / 4.0f,   1.0f / 9.0f,   1.0f / 16.0f,  1.0f / 25.0f,  1.0f / 36.0f,  1.0f / 49.0f, 1.0f / 64.0f,
+    1.0f / 81.0f, 1.0f / 100.0f, 1.0f / 121.0f, 1.0f / 144.0f, 1.0f / 169.0f, 1.0f / 196.0f, 1.0f / 225.0f, 1.0f / 256.0f};
+
+// the level rule: d and delta from the footprint's long axis mx, the tap count n and the number of levels
+BB_DEV Lod mip_level(const AnisoTaps &t, int levels) {
+  Lod lod = {0, 0.0f};
+  const float P = t.mx * kMipRcp2[t.n];
+  if (t.finite && P > 1.0f) {
+    const uint32_t b = __float_as_uint(P);
+    const int e = (int)(b >> 23) - 127;
+    lod.d = e >> 1;
+    lod.delta = 0.5f * ((float)(e & 1) + (float)(b & 0x7FFFFFu) * 1.1920928955078125e-07f);
+    if (lod.d >= levels - 1) lod = Lod{levels - 1, 0.0f};
+  }
+  return lod;
+}
+
+struct MipFilter {
+  int max_aniso;
+  const MipTable *__restrict__ tables;
+  template <class Fetch>
+  BB_DEV uint32_t sample(const Fetch &fetch, uint32_t material, int set, const UvFootprint &f, float (&value)[Fetch::kChannels], Lod &lod) const {
+    const MipSet &ms = tables[material].set[set];
+    const AnisoTaps t = aniso_taps(f, fetch.width(), fetch.height(), max_aniso);
+    lod = mip_level(t, ms.levels);
+    aniso_sample(fetch.at(ms.level[lod.d], lod.d), f, t, value);
+    if (lod.delta != 0.0f) {  // (d + 1 <= L - 1 here; a wave whose lanes all sit on one level skips this)
+      float lo[Fetch::kChannels];
+      aniso_sample(fetch.at(ms.level[lod.d + 1], lod.d + 1), f, t, lo);
+#pragma unroll
+      for (int k = 0; k < Fetch::kChannels; ++k) value[k] = fmaf(lod.delta, lo[k] - value[k], value[k]);
+    }
+    return (uint32_t)t.n;
+  }
+};
+
+// k_shade_mip: the fragment stage with the trilinear filter, whatever "max_anisotropy" is.  DUMP as in k_shade_aniso.
+template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
+__global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_shade_mip(
+    const uint32_t *__restrict__ items, const uint32_t *__restrict__ item_count,
+    const unsigned long long *__restrict__ frags, const uint32_t *__restrict__ frag_count,
+    const ShadeRec *__restrict__ recs, const ClipSlot *__restrict__ clip_arena,
+    FrameParams fp, ShadeParams sp, const CookedLight *__restrict__ cooked,
+    const MaterialDesc *__restrict__ materials, float4 *__restrict__ out,
+    uint2 *__restrict__ gbuffer, const SrgbTables *__restrict__ tables, uint32_t *__restrict__ out8,
+    Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups, int max_aniso,
+    const MipTable *__restrict__ mip_tables, float *__restrict__ dump) {
+  shade_item_list<TILE_W, TILE_H, DEFERRED, PRESENT, DUMP>(items, item_count, frags, frag_count, recs, clip_arena, fp, sp, cooked, materials, out,
+                                                           gbuffer, tables, out8, ctr, ctr_done, item_groups,
+                                                           MipFilter{max_aniso, mip_tables}, dump);
+}
+
+// One level of a row-major RGBA8 chain from the one above: texel (x, y) of the w1 x h1 level below a w0 x h0 level.  One
+// thread per texel; the four bytes of a texel are reduced side by side.
+constexpr int kMipThreads = 256;
+__global__ __launch_bounds__(kMipThreads) void k_mip_reduce(const uint32_t *__restrict__ src, int w0, int h0, uint32_t *__restrict__ dst,
+                                                            int w1, int h1) {
+  const uint32_t i = blockIdx.x * (uint32_t)kMipThreads + threadIdx.x;
+  if (i >= (uint32_t)w1 * (uint32_t)h1) return;
+  const int x = (int)(i % (uint32_t)w1), y = (int)(i / (uint32_t)w1);
+  const int x0 = min(2 * x, w0 - 1), x1 = min(2 * x + 1, w0 - 1), y0 = min(2 * y, h0 - 1), y1 = min(2 * y + 1, h0 - 1);
+  const uint32_t a = src[(size_t)y0 * w0 + x0], b = src[(size_t)y0 * w0 + x1], c = src[(size_t)y1 * w0 + x0], d = src[(size_t)y1 * w0 + x1];
+  uint32_t r = 0;
+#pragma unroll
+  for (int k = 0; k < 32; k += 8) {
+    const uint32_t s = ((a >> k) & 255u) + ((b >> k) & 255u) + ((c >> k) & 255u) + ((d >> k) & 255u);
+    r |= ((s + 2u) >> 2) << k;
+  }
+  dst[i] = r;
+}
+
+// One packed level from the row-major level of the five shaded maps (PBRMapType order; nullptr: the map is not supplied
+// and broadcasts its texel of `defaults`, kMapCount RGBA8 texels): the records of bb_pack.h, block-linear.  One thread
+// per record SLOT of the ceil(w / 4) x ceil(h / 4) blocks, so the padding records of the last block column / row are
+// written (zero), and the first kPackedTexelPad threads also zero the bytes behind the last record: every byte of the level.
+struct MipPackMaps {
+  const uint8_t *map[5];
+};
+__global__ __launch_bounds__(kMipThreads) void k_mip_pack(MipPackMaps maps, const uint8_t *__restrict__ defaults, int w, int h,
+                                                          uint8_t *__restrict__ out) {
+  const uint32_t w4 = ((uint32_t)w + 3u) >> 2, h4 = ((uint32_t)h + 3u) >> 2, n_slots = w4 * h4 * 16u;
+  const uint32_t i = blockIdx.x * (uint32_t)kMipThreads + threadIdx.x;
+  if (i < kPackedTexelPad) out[(size_t)n_slots * kPackedTexelBytes + i] = 0;
+  if (i >= n_slots) return;
+  const uint32_t block = i >> 4, x = (block % w4) * 4u + (i & 3u), y = (block / w4) * 4u + ((i >> 2) & 3u);
+  uint8_t t[kPackedTexelBytes] = {};
+  if (x < (uint32_t)w && y < (uint32_t)h) {
+    const size_t at = ((size_t)y * (size_t)w + x) * 4;
+    auto texel = [&](int k) { return maps.map[k] ? maps.map[k] + at : defaults + 4 * k; };
+    const uint8_t *al = texel(kMapAlbedo), *me = texel(kMapMetallic), *ro = texel(kMapRoughness), *ao = texel(kMapAO), *no = texel(kMapNormal);
+    t[0] = al[0]; t[1] = al[1]; t[2] = al[2]; t[3] = me[0];
+    t[4] = no[0]; t[5] = no[1]; t[6] = no[2]; t[7] = ro[0];
+    t[8] = ao[0];
+  }
+  uint8_t *o = out + (size_t)i * kPackedTexelBytes;
+#pragma unroll
+  for (int k = 0; k < (int)kPackedTexelBytes; ++k) o[k] = t[k];
 }
 
 // ------------------------------------------------------------------------------------------------

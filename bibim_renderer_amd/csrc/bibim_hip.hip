@@ -56,6 +56,8 @@ struct Mesh {
 struct Material {
   uint8_t *d_texels[kMapCount] = {};
   uint8_t *d_packed = nullptr;
+  uint8_t *d_chain = nullptr;  // option "mip_levels" >= 2: levels >= 1 of every supplied map and of the packed form, one allocation
+  MipTable mip = {};           // where every level of every set starts (valid while "mip_levels" >= 2)
   MaterialDesc desc = {};
   bool alive = false;
 };
@@ -292,6 +294,8 @@ struct bbr_context {
   bool dump_gbuffer = false;
   DeviceBuffer<uint2> d_gbuffer;  // width*height*4 (four RGBA16F texels per pixel), only while bbr_read_gbuffer runs
   int max_anisotropy = 1;         // option "max_anisotropy": 1 = k_shade's bilinear tap, 2..16 = k_shade_aniso
+  int mip_levels = 1;             // option "mip_levels": 1 = no chain, the kernels above; 2..15 = chains of up to that many levels, k_shade_mip
+  DeviceBuffer<MipTable> d_mip_tables;  // one per material slot, beside d_materials (only while "mip_levels" >= 2)
   bool dump_surface = false;
   DeviceBuffer<float> d_surface;  // width*height*32 floats, only while bbr_read_surface runs
   uint32_t ablate = 0;
@@ -525,6 +529,75 @@ void stream_edge(hipStream_t from, hipStream_t to, hipEvent_t ev) {
   (void)hipStreamWaitEvent(to, ev, 0);
 }
 
+// ---- mip chains (option "mip_levels" >= 2) ----
+// L of a w x h map under the option's value n: min(n, 1 + floor(log2 max(w, h)))
+int mip_level_count(int w, int h, int n) {
+  int levels = 1;
+  for (int m = std::max(w, h); m > 1; m >>= 1) ++levels;
+  return std::min(levels, n);
+}
+int mip_extent(int n, int level) { return std::max(1, n >> level); }
+size_t packed_level_bytes(int w, int h) { return (((size_t)w + 3) / 4) * (((size_t)h + 3) / 4) * 16 * kPackedTexelBytes + kPackedTexelPad; }
+
+void free_chain(Material &m) {
+  if (m.d_chain) (void)hipFree(m.d_chain);
+  m.d_chain = nullptr;
+  m.mip = MipTable{};
+}
+
+// Levels >= 1 of every supplied map (k_mip_reduce, each from the level above) and, for a packed material, of the packed form
+// (k_mip_pack, from the level-k maps), in one allocation -- every level starts on a multiple of 256 bytes, so a third of the
+// material's own bytes plus at most 255 per level; and the level table.
+// The context is drained and the material's level 0 is on the device.  Synchronises.
+int build_chain(bbr_context *c, Material &m) {
+  free_chain(m);
+  const int n = c->mip_levels;
+  auto aligned = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+  size_t total = 0, offset[kMipSets][kMaxMipLevels] = {};
+  for (int i = 0; i < kMapCount; ++i) {
+    const TexDesc &td = m.desc.maps[i];
+    MipSet &ms = m.mip.set[i];
+    ms.levels = m.d_texels[i] ? mip_level_count(td.w, td.h, n) : 1;  // (a defaulted map is 1 x 1)
+    ms.level[0] = td.texels;
+    for (int k = 1; k < ms.levels; ++k) {
+      offset[i][k] = total;
+      total += aligned((size_t)mip_extent(td.w, k) * mip_extent(td.h, k) * 4);
+    }
+  }
+  MipSet &ps = m.mip.set[kMapCount];
+  ps.levels = m.desc.packed ? mip_level_count(m.desc.pw, m.desc.ph, n) : 1;
+  ps.level[0] = m.desc.packed;
+  for (int k = 1; k < ps.levels; ++k) {
+    offset[kMapCount][k] = total;
+    total += aligned(packed_level_bytes(mip_extent(m.desc.pw, k), mip_extent(m.desc.ph, k)));
+  }
+  if (!total) return BBR_OK;
+  HIP_TRY(c, hipMalloc(&m.d_chain, total));
+  for (int i = 0; i < kMipSets; ++i)
+    for (int k = 1; k < m.mip.set[i].levels; ++k) m.mip.set[i].level[k] = m.d_chain + offset[i][k];
+  for (int i = 0; i < kMapCount; ++i) {
+    const TexDesc &td = m.desc.maps[i];
+    const MipSet &ms = m.mip.set[i];
+    for (int k = 1; k < ms.levels; ++k) {
+      const int w0 = mip_extent(td.w, k - 1), h0 = mip_extent(td.h, k - 1), w1 = mip_extent(td.w, k), h1 = mip_extent(td.h, k);
+      hipLaunchKernelGGL(k_mip_reduce, dim3((unsigned)(((size_t)w1 * h1 + kMipThreads - 1) / kMipThreads)), dim3(kMipThreads), 0, nullptr,
+                         (const uint32_t *)ms.level[k - 1], w0, h0, (uint32_t *)(m.d_chain + offset[i][k]), w1, h1);
+    }
+  }
+  for (int k = 1; k < ps.levels; ++k) {
+    // (the supplied shaded maps of a packed material have its size, so each has this level)
+    MipPackMaps maps;
+    for (int j = 0; j < 5; ++j) maps.map[j] = m.d_texels[j] ? m.mip.set[j].level[k] : nullptr;
+    const int w = mip_extent(m.desc.pw, k), h = mip_extent(m.desc.ph, k);
+    const size_t slots = std::max<size_t>((((size_t)w + 3) / 4) * (((size_t)h + 3) / 4) * 16, kPackedTexelPad);
+    hipLaunchKernelGGL(k_mip_pack, dim3((unsigned)((slots + kMipThreads - 1) / kMipThreads)), dim3(kMipThreads), 0, nullptr, maps,
+                       (const uint8_t *)c->d_default_texels, w, h, m.d_chain + offset[kMapCount][k]);
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(nullptr));
+  return BBR_OK;
+}
+
 int upload_material_table(bbr_context *c) {
   if (!c->materials_dirty) return BBR_OK;
   size_t n = std::max<size_t>(c->materials.size(), 1);
@@ -538,6 +611,15 @@ int upload_material_table(bbr_context *c) {
   if (rc) return rc;
   HIP_TRY(c, c->d_materials.ensure(n));
   HIP_TRY(c, upload_sync(c->d_materials.ptr, h.data(), n * sizeof(MaterialDesc)));
+  if (c->mip_levels > 1) {
+    std::vector<MipTable> t(n);
+    for (MipTable &m : t)
+      for (MipSet &ms : m.set) ms.levels = 1;  // (a slot without a live material: never sampled)
+    for (size_t i = 0; i < c->materials.size(); ++i)
+      if (c->materials[i].alive) t[i] = c->materials[i].mip;
+    HIP_TRY(c, c->d_mip_tables.ensure(n));
+    HIP_TRY(c, upload_sync(c->d_mip_tables.ptr, t.data(), n * sizeof(MipTable)));
+  }
   c->materials_dirty = false;
   return BBR_OK;
 }
@@ -620,6 +702,20 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
   // one stream an empty tail would still cost the frame a kernel boundary (~4 us).
   const bool tail = main_wgs * kShadeWaves < max_items;
   auto shade = [&](auto deferred, auto present) {
+    if (c->mip_levels > 1) {
+      // option "mip_levels": k_shade_mip, launched like k_shade_aniso
+      if (ev) (void)hipEventRecord(ev[3], ss);
+      auto mip_launch = [&](auto dump) {
+        hipLaunchKernelGGL((k_shade_mip<TW, TH, decltype(deferred)::value, decltype(present)::value, decltype(dump)::value>),
+                           dim3(main_wgs), dim3(kShadeThreads), 0, ss, s.d_items.ptr, item_count, s.d_frags.ptr, s.d_frag_count.ptr,
+                           s.d_attrs.ptr, s.d_clip.ptr, fp, sp, s.d_cooked.ptr, c->d_materials.ptr, out, gbuf, tables, out8, ctr,
+                           ctr_done, short_frame ? nullptr : s.d_item_groups.ptr, c->max_anisotropy, c->d_mip_tables.ptr,
+                           decltype(dump)::value ? c->d_surface.ptr : nullptr);
+      };
+      if (c->dump_surface) mip_launch(std::true_type{});
+      else mip_launch(std::false_type{});
+      return;
+    }
     if (c->max_anisotropy > 1 || c->dump_surface) {
       // option "max_anisotropy" / bbr_read_surface: k_shade_aniso, one launch whose waves walk the whole item list
       if (ev) (void)hipEventRecord(ev[3], ss);
@@ -1446,7 +1542,9 @@ static void release_context(bbr_context *c) {
     for (auto &p : m.d_texels)
       if (p) (void)hipFree(p);
     if (m.d_packed) (void)hipFree(m.d_packed);
+    free_chain(m);
   }
+  c->d_mip_tables.release();
   if (c->d_default_texels) (void)hipFree(c->d_default_texels);
   for (auto &t : c->ui_textures)
     if (t.d_texels) (void)hipFree(t.d_texels);
@@ -1602,6 +1700,7 @@ int bbr_upload_material(bbr_context *c, const bbr_image maps[BBR_MAP_COUNT], int
       for (auto &p : m->d_texels)
         if (p) (void)hipFree(p);
       if (m->d_packed) (void)hipFree(m->d_packed);
+      free_chain(*m);
     }
   } guard{&m};
   for (int i = 0; i < kMapCount; ++i) {
@@ -1631,6 +1730,10 @@ int bbr_upload_material(bbr_context *c, const bbr_image maps[BBR_MAP_COUNT], int
       m.desc.ph = plan.ph;
     }
   }
+  if (c->mip_levels > 1) {
+    const int rc = build_chain(c, m);
+    if (rc) return rc;
+  }
   m.alive = true;
   guard.m = nullptr;  // ownership passes to the context
   c->materials.push_back(m);
@@ -1651,6 +1754,7 @@ int bbr_free_material(bbr_context *c, int32_t material) {
   for (auto &p : m.d_texels)
     if (p) (void)hipFree(p);
   if (m.d_packed) (void)hipFree(m.d_packed);
+  free_chain(m);
   m = Material();
   c->materials_dirty = true;
   c->have_frame = false;
@@ -2004,6 +2108,56 @@ int bbr_read_surface(bbr_context *c, float *host) {
   return rc;
 }
 
+// a copy of the set of a live material that has level `level`, for the chain read-backs (nothing of the context changes)
+static int chain_set(bbr_context *c, int32_t material, int set, int32_t level, const char *who, MipSet *out) {
+  if (material < 0 || material >= (int32_t)c->materials.size() || !c->materials[material].alive)
+    return fail(c, BBR_ERR_BAD_HANDLE, std::string(who) + ": bad material handle");
+  const Material &m = c->materials[material];
+  if (c->mip_levels > 1) *out = m.mip.set[set];
+  else *out = MipSet{1, 0, {set < kMapCount ? m.desc.maps[set].texels : m.desc.packed}};  // no chain: level 0 alone
+  if (level < 0 || level >= out->levels) return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": the chain has no such level");
+  return BBR_OK;
+}
+
+int bbr_read_material_level(bbr_context *c, int32_t material, int32_t map, int32_t level, uint8_t *out_rgba8, uint64_t cap,
+                            int32_t *out_width, int32_t *out_height) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (map < 0 || map >= kMapCount || !out_width || !out_height) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_material_level: bad map or NULL size");
+  int rc = drain(c);
+  if (rc) return rc;
+  MipSet ms;
+  if ((rc = chain_set(c, material, map, level, "read_material_level", &ms)) != BBR_OK) return rc;
+  const TexDesc &td = c->materials[material].desc.maps[map];
+  *out_width = mip_extent(td.w, level);
+  *out_height = mip_extent(td.h, level);
+  const uint64_t bytes = (uint64_t)*out_width * (uint64_t)*out_height * 4;
+  if (out_rgba8) {
+    if (cap < bytes) return fail(c, BBR_ERR_CAPACITY, "read_material_level: capacity below width * height * 4");
+    HIP_TRY(c, hipMemcpy(out_rgba8, ms.level[level], bytes, hipMemcpyDeviceToHost));
+  }
+  return BBR_OK;
+}
+
+int bbr_read_packed_level(bbr_context *c, int32_t material, int32_t level, uint8_t *out, uint64_t cap, uint64_t *out_bytes) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!out_bytes) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_packed_level: NULL size");
+  int rc = drain(c);
+  if (rc) return rc;
+  *out_bytes = 0;
+  MipSet ms;
+  if ((rc = chain_set(c, material, kMapCount, level, "read_packed_level", &ms)) != BBR_OK) return rc;
+  const MaterialDesc &md = c->materials[material].desc;
+  if (!md.packed) return BBR_OK;  // not packed: nothing to read
+  *out_bytes = packed_level_bytes(mip_extent(md.pw, level), mip_extent(md.ph, level));
+  if (out) {
+    if (cap < *out_bytes) return fail(c, BBR_ERR_CAPACITY, "read_packed_level: capacity below the level's bytes");
+    HIP_TRY(c, hipMemcpy(out, ms.level[level], *out_bytes, hipMemcpyDeviceToHost));
+  }
+  return BBR_OK;
+}
+
 int bbr_read_records(bbr_context *c, void *records, void *triangles, uint32_t cap, uint32_t *out_count) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
@@ -2183,6 +2337,19 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   } else if (n == "max_anisotropy") {
     if (value < 1 || value > kMaxAnisotropy) return fail(c, BBR_ERR_INVALID_ARGUMENT, "max_anisotropy: 1 (bilinear) .. 16");
     c->max_anisotropy = (int)value;
+  } else if (n == "mip_levels") {
+    if (value < 1 || value > kMaxMipLevels) return fail(c, BBR_ERR_INVALID_ARGUMENT, "mip_levels: 1 (no chain) .. 15");
+    // every chain is built for the option's value: drop them all, then build the new ones of every live material
+    for (Material &m : c->materials) free_chain(m);
+    c->mip_levels = (int)value;
+    c->materials_dirty = true;
+    if (value == 1) c->d_mip_tables.release();
+    for (Material &m : c->materials)
+      if (m.alive && value > 1 && (rc = build_chain(c, m)) != BBR_OK) {
+        for (Material &q : c->materials) free_chain(q);
+        c->mip_levels = 1;
+        return rc;
+      }
   } else if (n == "present_fused") {
     c->present_fused = value != 0;
   } else if (n == "overlays") {

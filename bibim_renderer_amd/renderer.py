@@ -215,6 +215,23 @@ class Renderer:
         self._check(self._L.bbr_read_surface(self._ctx, _ptr(out)))
         return out
 
+    def read_material_level(self, material, map_index, level):
+        """level `level` of one of a material's six maps (PBRMapType order), uint8 [h, w, 4] (option "mip_levels")"""
+        w, h = C.c_int32(), C.c_int32()
+        self._check(self._L.bbr_read_material_level(self._ctx, material, map_index, level, None, 0, C.byref(w), C.byref(h)))
+        out = np.empty((h.value, w.value, 4), np.uint8)
+        self._check(self._L.bbr_read_material_level(self._ctx, material, map_index, level, _ptr(out), out.nbytes, C.byref(w), C.byref(h)))
+        return out
+
+    def read_packed_level(self, material, level):
+        """the packed form of one level of a material, uint8 [bytes] (empty for an unpacked material)"""
+        n = C.c_uint64()
+        self._check(self._L.bbr_read_packed_level(self._ctx, material, level, None, 0, C.byref(n)))
+        out = np.empty(n.value, np.uint8)
+        if n.value:
+            self._check(self._L.bbr_read_packed_level(self._ctx, material, level, _ptr(out), out.nbytes, C.byref(n)))
+        return out
+
     def read_records(self):
         """what k_geometry wrote per primitive of the last frame: (records RECORD_DTYPE [n], triangles TRIANGLE_DTYPE [n]);
         a culled primitive keeps the 0xFF fill (material == 0xFFFFFFFF); re-renders the last frame"""

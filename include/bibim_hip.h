@@ -216,6 +216,19 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            the pixel's footprint, averaged (the Vulkan specification's example scheme; the rule is
  *                            spelled out in DESIGN.md section 3 and under "surface read-back" below).  The TBN overlay's
  *                            vertex-stage fetch has no derivatives and stays one tap.  Anything else: INVALID_ARGUMENT
+ *   "mip_levels" 1..15       mip chains and the trilinear half of the reference's sampler (src/render.cpp:1363-1365:
+ *                            mipmapMode LINEAR, which the reference pins to its images' single level).  1 (default): no
+ *                            chain exists; the kernels, statements and pixels of "max_anisotropy" alone.  n >= 2: a map of
+ *                            w x h texels gets L = min(n, 1 + floor(log2 max(w, h))) levels, level k of max(1, w >> k) x
+ *                            max(1, h >> k) texels (15: the full chain of a 16384 map), built on the GPU -- of every live
+ *                            material when the option goes above 1, by bbr_upload_material while it is, freed by
+ *                            bbr_free_material and when it returns to 1.  The extra memory is a third of the maps' own
+ *                            bytes, plus what placement adds: every level starts on a multiple of 256 bytes (a 2 x 2 map
+ *                            of 16 bytes gets a 256-byte level), and a packed level's 4 x 4 blocks round its extents up
+ *                            (a 16384 x 3 set: half again, not a third).  Frames are then
+ *                            shaded by k_shade_mip, whatever "max_anisotropy" is (the rule: "mip chains" below).  The TBN
+ *                            overlay's vertex-stage fetch and the GUI sampler have no derivatives and stay on level 0.
+ *                            Anything else: INVALID_ARGUMENT
  *   "present_fused" 0|1      frames are produced as presented RGBA8 pixels directly (binary16 stage, tone map and sRGB
  *                            encode fused into the raster / shade kernels): no fp32 frame, no k_present pass; bbr_present
  *                            then only marks (or copies to a caller buffer), bbr_read_framebuffer / bbr_read_shard fail
@@ -270,7 +283,9 @@ int bbr_read_gbuffer(bbr_context *ctx, float *gbuffer_host);
  *                                                before the binary16 rounding)
  *   [12..14] albedo   [15] metallic   [16] roughness   [17] ao   [18] height (deferred only, else 0)
  *   [19..21] the normal-map sample s*2-1 (0 when EnableNormalMap is 0)
- *   [22..27] taps N used for each map, PBRMapType order (0: a map the pass did not sample)       [28..31] 0
+ *   [22..27] taps N used for each map, PBRMapType order (0: a map the pass did not sample)
+ *   [28..31] 0 with "mip_levels" 1; otherwise the level choice (see "mip chains"): [28] d and [29] delta of the packed set, or
+ *            of the albedo map of an unpacked material; [30] d and [31] delta of the height map (deferred pass, else 0)
  * all filtered values before any binary16 rounding.  The differences and N follow the filter rule of "max_anisotropy":
  *   dudx = u(x+1, y) - u(x, y), dudy = u(x, y+1) - u(x, y) (v likewise), u(X, Y) being the fragment's own planes
  *   evaluated at that pixel centre, whatever wins there; per map of w x h texels px2 = (dudx w)^2 + (dvdx h)^2, py2
@@ -279,6 +294,33 @@ int bbr_read_gbuffer(bbr_context *ctx, float *gbuffer_host);
  *   axis' differences); the taps are summed in order and multiplied by 1 / N.  A packed material (five maps of one size)
  *   has one N, a material whose maps differ in size one per map. */
 int bbr_read_surface(bbr_context *ctx, float *out);
+
+/* ---- mip chains (option "mip_levels" >= 2) ----
+ * The rule, in binary32, without contraction, in this operand order (tests/mip_reference.py):
+ *   chain    level k + 1, per channel byte of all six maps: texel (x, y) = (s + 2) >> 2, s the integer sum of the four
+ *            level-k bytes at columns min(2x, w_k - 1), min(2x + 1, w_k - 1) and the same two rows.  A defaulted (NULL)
+ *            map is 1 x 1 and has one level.  A packed material's level k is what bbr_pack_material makes of the five
+ *            level-k maps: the same 9-byte block-linear records, the same tail padding, per level.
+ *   N        the footprint and tap count of "max_anisotropy" (1 included) on the map's LEVEL-0 size; mx its long axis
+ *   level    P = mx * R2[N], R2[k] the binary32 nearest to 1 / k^2.  A difference not finite, or !(P > 1): d = 0, delta = 0.
+ *            Otherwise, b the bits of P: e = (b >> 23) - 127, d = e >> 1, delta = 0.5f * ((float)(e & 1) + (float)(b &
+ *            0x7FFFFF) * 2^-23), all exact.  d >= L - 1 (+inf included): d = L - 1, delta = 0 -- so a footprint that is
+ *            huge but finite (a steep, nearly edge-on or degenerate primitive) samples the LAST level; only differences
+ *            that are not finite, and footprints of at most a texel, stay on level 0.  This is lambda = 1/2 log2 P with
+ *            log2(1 + t) taken as t: it reads low by at most 0.043 level (slightly sharp), a documented deviation
+ *   value    hi = the taps and average of "max_anisotropy" on level d's size (tap offsets are in uv: the same on every
+ *            level; wrapping and the 2^30 cutoff per level).  delta == 0: value = hi and nothing else happens -- a
+ *            magnified pixel and a one-level map keep the bits of the "max_anisotropy" path.  Otherwise lo = the same on
+ *            level d + 1 and value = fmaf(delta, lo - hi, hi) per channel; the normal sample is fmaf(value, 2, -1) as ever.
+ *            A packed material has one (N, d, delta), a material with maps of different sizes one per map.
+ * Chain read-back, in the family of the other diagnostics; both synchronise and return BBR_ERR_INVALID_ARGUMENT for a
+ * level the chain does not have (with "mip_levels" 1 every map has level 0 alone), BBR_ERR_BAD_HANDLE for a material
+ * that is not live, BBR_ERR_CAPACITY when `capacity` (bytes) is too small; `out` may be NULL to ask for the size:
+ *   bbr_read_material_level  the row-major RGBA8 level of one of the six maps (PBRMapType order) and its size
+ *   bbr_read_packed_level    the packed form of that level and its bytes; 0 bytes for an unpacked material */
+int bbr_read_material_level(bbr_context *ctx, int32_t material, int32_t map, int32_t level, uint8_t *out_rgba8, uint64_t capacity,
+                            int32_t *out_width, int32_t *out_height);
+int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uint8_t *out, uint64_t capacity, uint64_t *out_bytes);
 
 /* ---- primitive-record read-back ----
  * What the vertex stage (k_geometry: forward_brdf.vert / gbuffer.vert, clip test, viewport, snap, triangle setup) wrote
