@@ -71,6 +71,7 @@ SIGNATURES = {
     "bbr_replay_frame": (C.c_int, [_P]),
     "bbr_synchronize": (C.c_int, [_P]),
     "bbr_read_framebuffer": (C.c_int, [_P, _P]),
+    "bbr_read_samples": (C.c_int, [_P, _P]),
     "bbr_framebuffer_device_ptr": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     "bbr_set_output_device_ptr": (C.c_int, [_P, _P, C.c_uint64]),
     "bbr_set_stream": (C.c_int, [_P, _P]),
@@ -111,6 +112,7 @@ SIGNATURES = {
     "bbr_read_presented": (C.c_int, [_P, C.c_void_p]),
     "bbr_present_buffer": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
     "bbr_present_timing": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "bbr_resolve_timing": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "bbr_presented_device_ptr": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "bbr_unpack_gathered_rgba8": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bbr_comm_unique_id": (C.c_int, [_P, _P]),

@@ -13,6 +13,7 @@
 //                and k_shade_overlay)
 //   k_present, k_tone_map, k_deferred_background, k_shade_overlay, k_pack_shard / k_unpack_*: the rows either side of the path
 //   k_tbn_segments, k_tbn_raster, k_tbn_colour: the TBN line overlay (option "tbn"; tbn.vert / tbn.geom)
+//   k_resolve    option "supersample": the n x n samples of the fine frame averaged into the output pixel, in a pinned order
 //
 // Arithmetic contract: every floating-point expression below has the same operand order and the same
 // explicit fmaf() placement as the CPU oracle; the file is compiled with -ffp-contract=off, IEEE
@@ -3094,6 +3095,76 @@ __global__ __launch_bounds__(kPresentThreads) void k_present(const float4 *__res
     const v4f c = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(frame) + i);
     const uint32_t px = present_pixel(c.x, c.y, c.z, t, enable, exposure, hdr16);
     store_pixel(&out_rgba8[i], px);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// supersampling (option "supersample", n = 2..4): the resolve of the fine frame, VK_RESOLVE_MODE_AVERAGE over the n x n
+// regular grid.  Output pixel (x, y) of the W x rows frame, all four channels, in binary32 without contraction:
+//   acc = f(nx, ny);  acc += f(nx + i, ny + j) for (i, j) != (0, 0), row-major, i fastest;  out = acc * R[n]
+// A streaming kernel: 16 n^2 B read + 16 B written per output pixel (PRESENT: + 4 B), nothing reused.  One lane per output
+// pixel; per fine row it loads its n contiguous float4 (16-byte non-temporal loads: the 64 lanes of a wave cover 64 * 16 n
+// contiguous bytes of the row), adds them in the pinned order, and stores non-temporally like k_present.  blockIdx.y is the
+// output row, so no lane divides; addresses are size_t (a 32768-wide fine frame passes 2^32 bytes within a few rows).
+// The rows below the first are a rolled loop: a lane then holds one fine row of its pixel at a time (n float4) instead of
+// all n^2, and the kernel keeps the 64-register allocation of eight waves per SIMD.
+// PRESENT (option "present_fused" with n >= 2): the resolved pixel goes through present_pixel (binary16 stage included)
+// and is stored as RGBA8; the tables are staged in LDS as k_present stages them -- once per workgroup, i.e. per 256 pixels
+// of one row: 4.3 KB of L2 reads beside the 16 KB of samples at n = 2.  A form in which a workgroup covered eight rows with one
+// staging measured no faster (116.0 against 115.1 us at 3840 x 2160), so the tables' traffic is not what the form costs.
+// ------------------------------------------------------------------------------------------------
+constexpr int kResolveThreads = 256;
+template <int N>
+BB_DEV constexpr float resolve_scale() {
+  static_assert(N >= 2 && N <= 4, "supersample: n = 2 .. 4 are resolved");
+  return N == 2 ? 0.25f : (N == 3 ? 1.0f / 9.0f : 0.0625f);  // R[3]: the binary32 nearest 1/9 (0x3DE38E39), a constant
+}
+BB_DEV v4f resolve_add(v4f a, v4f b) {
+  // (plain adds: nothing here may become an fma, and the order is the rule's)
+  return v4f{__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w)};
+}
+template <int N>
+BB_DEV v4f resolve_row(const v4f *__restrict__ row, v4f acc, bool first) {
+  v4f v[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = __builtin_nontemporal_load(row + i);
+  if (first) acc = v[0];
+  else acc = resolve_add(acc, v[0]);
+#pragma unroll
+  for (int i = 1; i < N; ++i) acc = resolve_add(acc, v[i]);
+  return acc;
+}
+template <int N>
+BB_DEV float4 resolve_pixel(const float4 *__restrict__ fine, int32_t width, int32_t x, size_t y) {
+  const size_t fine_pitch = (size_t)width * N;
+  const v4f *row = reinterpret_cast<const v4f *>(fine) + (y * N) * fine_pitch + (size_t)x * N;
+  v4f acc = resolve_row<N>(row, v4f{0.f, 0.f, 0.f, 0.f}, true);
+#pragma unroll 1
+  for (int j = 1; j < N; ++j) {
+    row += fine_pitch;
+    acc = resolve_row<N>(row, acc, false);
+  }
+  constexpr float r = resolve_scale<N>();
+  return make_float4(__fmul_rn(acc.x, r), __fmul_rn(acc.y, r), __fmul_rn(acc.z, r), __fmul_rn(acc.w, r));
+}
+template <int N, bool PRESENT>
+__global__ __launch_bounds__(kResolveThreads) void k_resolve(const float4 *__restrict__ fine, float4 *__restrict__ out,
+                                                              uint32_t *__restrict__ out_rgba8, int32_t width,
+                                                              const SrgbTables *__restrict__ tables, int enable, float exposure) {
+  const int32_t x = (int32_t)(blockIdx.x * kResolveThreads + threadIdx.x);
+  const size_t y = blockIdx.y, o = y * (size_t)width + (size_t)x;
+  if constexpr (PRESENT) {
+    __shared__ SrgbTables t;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(tables);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(&t);
+    for (uint32_t w = threadIdx.x; w < sizeof(SrgbTables) / 4; w += kResolveThreads) dst[w] = src[w];
+    __syncthreads();
+    if (x >= width) return;
+    const float4 px = resolve_pixel<N>(fine, width, x, y);
+    store_pixel(&out_rgba8[o], present_pixel(px.x, px.y, px.z, t, enable, exposure, 1));
+  } else {
+    if (x >= width) return;
+    store_pixel(&out[o], resolve_pixel<N>(fine, width, x, y));
   }
 }
 

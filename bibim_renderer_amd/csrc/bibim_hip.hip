@@ -131,6 +131,7 @@ struct FrameSlot {
   DeviceBuffer<uint32_t> d_heavy;       // the frame's heavy-tile list (k_geometry -> k_raster; option "heavy_tiles")
   DeviceBuffer<uint32_t> d_item_groups; // 64-fragment chunks per group of 256 launch slots (k_raster -> k_shade_items)
   DeviceBuffer<float4> d_frame;
+  DeviceBuffer<float4> d_fine;        // option "supersample" >= 2: the fine frame k_resolve reads (always library-owned)
   DeviceBuffer<float4> d_background;  // deferred path: colour of the pixels no geometry covers
   DeviceBuffer<float> d_depth;        // option "overlays": the frame's resolved depth, for bbr_draw_overlays
   bool has_depth = false;
@@ -169,6 +170,7 @@ struct FrameSlot {
   } ui;
   bool in_flight = false;
   float4 *out_used = nullptr;  // where the frame in this slot wrote its pixels
+  float4 *fine_used = nullptr;  // option "supersample" >= 2: the fine frame those pixels were resolved from
   hipStream_t stream_used = nullptr;  // the stream its k_shade ran on
   uint32_t n_prims = 0;
 
@@ -188,7 +190,7 @@ struct FrameSlot {
   void release_all() {
     d_staging.release(); d_tris.release(); d_attrs.release(); d_clip.release(); d_gathered.release(); d_whole.release();
     d_block_stats.release();
-    release_tile_buffers(); d_broad.release(); d_frame.release(); d_present.release(); d_background.release(); d_depth.release();
+    release_tile_buffers(); d_broad.release(); d_frame.release(); d_fine.release(); d_present.release(); d_background.release(); d_depth.release();
     if (h_staging) (void)hipHostFree(h_staging);
     h_staging = nullptr;
     if (h_flags) (void)hipHostFree(h_flags);
@@ -225,7 +227,12 @@ bool is_live(const bbr_context *c) {
 
 struct bbr_context {
   int device = 0;
-  int32_t width = 0, height = 0;
+  int32_t width = 0, height = 0;  // the OUTPUT extent: what every output, shard, present, exchange, GUI and caller buffer is sized by
+  // option "supersample": everything up to and including shading (tiles, bins, fragment lists, items, the viewport, the flag
+  // words) works on the render extent n * width x n * height; k_resolve brings the fine frame to the output extent
+  int supersample = 1;
+  int32_t render_width() const { return width * supersample; }
+  int32_t render_height() const { return height * supersample; }
   hipStream_t s_geom = nullptr, s_raster = nullptr, s_shade = nullptr, s_present = nullptr;  // context-owned streams
   hipStream_t user_stream = nullptr;                 // bbr_set_stream: everything on the caller's stream, 1 frame in flight
   std::string last_error;
@@ -308,6 +315,8 @@ struct bbr_context {
   uint32_t ring_frames = 0;
   std::vector<hipEvent_t> present_ring;  // (start, stop) around each k_present while timing is on
   uint32_t present_launches = 0;
+  std::vector<hipEvent_t> resolve_ring;  // (start, stop) around the k_resolve of each timed frame: the pair of ring frame i
+  uint32_t resolve_launches = 0;
   static constexpr uint32_t kRingCap = 512;
   static constexpr uint32_t kRingEvents = 5;
   int retries = 0;
@@ -370,9 +379,13 @@ struct bbr_context {
   int n_slots() const { return user_stream ? 1 : frames_in_flight; }
   int tile_w() const { return tile_mode == 0 ? 64 : 32; }
   int tile_h() const { return tile_mode == 0 ? 64 : 32; }
-  int tiles_x() const { return (width + tile_w() - 1) / tile_w(); }
-  int tiles_y() const { return (height + tile_h() - 1) / tile_h(); }
+  int tiles_x() const { return (render_width() + tile_w() - 1) / tile_w(); }
+  int tiles_y() const { return (render_height() + tile_h() - 1) / tile_h(); }
+  // The partition is stated in output rows; a band is `supersample` times as many fine rows, so the band count, the
+  // ownership and the shard's layout are those of the output, and the fine shard is n x the output shard.
   int eff_band_rows() const { return band_rows > 0 ? band_rows : tile_h(); }
+  int band_tiles() const { return supersample * eff_band_rows() / tile_h(); }  // tile rows of one band of the render extent
+  size_t fine_pixels() const { return (size_t)render_width() * ((size_t)supersample * std::max(height, shard_rows())); }
   int n_bands() const { return (height + eff_band_rows() - 1) / eff_band_rows(); }
   int local_bands() const { return world > 1 ? (n_bands() - rank + world - 1) / world : n_bands(); }
   int shard_rows() const { return world > 1 ? ((n_bands() + world - 1) / world) * eff_band_rows() : height; }
@@ -417,10 +430,10 @@ Mat4 proj_view(const ViewUniformBlock &v) {
 
 FrameParams make_params(const bbr_context *c) {
   FrameParams fp = {};  // (the overlay fields stay 0 for the main pass)
-  fp.width = c->width;
-  fp.height = c->height;
-  fp.half_w = 0.5f * (float)c->width;
-  fp.half_h = 0.5f * (float)c->height;
+  fp.width = c->render_width();
+  fp.height = c->render_height();
+  fp.half_w = 0.5f * (float)c->render_width();
+  fp.half_h = 0.5f * (float)c->render_height();
   fp.tiles_x = c->tiles_x();
   fp.tiles_y = c->tiles_y();
   fp.bin_cap = c->bin_cap;
@@ -429,8 +442,8 @@ FrameParams make_params(const bbr_context *c) {
   fp.broad_threshold = c->broad_threshold;
   fp.rank = c->rank;
   fp.world = c->world;
-  fp.band_tiles = c->eff_band_rows() / c->tile_h();
-  fp.shard_rows = c->shard_rows();
+  fp.band_tiles = c->band_tiles();
+  fp.shard_rows = c->supersample * c->shard_rows();
   fp.ablate = c->ablate;
   fp.deferred = c->deferred ? 1 : 0;
   fp.gbuffer_view = c->deferred ? c->gbuffer_view : -1;
@@ -491,7 +504,10 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s) {
   HIP_TRY(c, s.d_cooked.ensure(kMaxNumLights));
   HIP_TRY(c, s.d_heavy.ensure(tiles * kBinClasses, true));
   if (c->deferred) HIP_TRY(c, s.d_background.ensure(2));
-  if (c->overlays && &s != &c->ov) HIP_TRY(c, s.d_depth.ensure((size_t)c->width * c->height));
+  // (bbr_draw_overlays is refused with "supersample" >= 2: no depth is kept there until a depth resolve rule exists)
+  if (c->overlays && c->supersample == 1 && &s != &c->ov) HIP_TRY(c, s.d_depth.ensure((size_t)c->width * c->height));
+  // (zero filled: the padding rows of a fine shard are never written, and k_resolve reads them)
+  if (c->supersample > 1 && &s != &c->ov) HIP_TRY(c, s.d_fine.ensure(c->fine_pixels(), true));
   if (c->present_fused && &s != &c->ov) {
     HIP_TRY(c, s.d_present.ensure((size_t)c->width * out_rows));
     int rc_t = ensure_srgb_tables(c);
@@ -499,7 +515,8 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s) {
   }
   if (c->dump_gbuffer) HIP_TRY(c, c->d_gbuffer.ensure((size_t)c->width * c->height * 4, true));
   if (c->dump_surface) HIP_TRY(c, c->d_surface.ensure((size_t)c->width * c->height * kSurfaceFloats, true));
-  if (!c->ext_out) HIP_TRY(c, s.d_frame.ensure(out_rows * c->width));
+  // (option "present_fused" with "supersample" >= 2: k_resolve writes the presented image, there is no W x H fp32 frame)
+  if (!c->ext_out && !(c->present_fused && c->supersample > 1)) HIP_TRY(c, s.d_frame.ensure(out_rows * c->width));
   if (c->dump_vis) {
     HIP_TRY(c, c->d_vis_prim.ensure((size_t)c->width * c->height));
     HIP_TRY(c, c->d_vis_depth.ensure((size_t)c->width * c->height));
@@ -515,10 +532,15 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s) {
 
 // The timing ring's events (option "timing": made there, not in the first timed frame -- 2560 hipEventCreate calls take
 // half a millisecond)
-int ensure_timing_ring(bbr_context *c) {
-  if (!c->ring.empty()) return BBR_OK;
-  c->ring.resize(bbr_context::kRingEvents * bbr_context::kRingCap);
-  for (auto &e : c->ring) HIP_TRY(c, hipEventCreate(&e));
+int ensure_timing_ring(bbr_context *c, bool resolve_pairs) {
+  if (c->ring.empty()) {
+    c->ring.resize(bbr_context::kRingEvents * bbr_context::kRingCap);
+    for (auto &e : c->ring) HIP_TRY(c, hipEventCreate(&e));
+  }
+  if (resolve_pairs && c->resolve_ring.empty()) {  // (start, stop) around k_resolve, one pair per ring frame
+    c->resolve_ring.resize(2 * bbr_context::kRingCap);
+    for (auto &e : c->resolve_ring) HIP_TRY(c, hipEventCreate(&e));
+  }
   return BBR_OK;
 }
 
@@ -628,8 +650,11 @@ int upload_material_table(bbr_context *c) {
 template <int TW, int TH>
 void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent_t *ev, const FrameParams &fp_in, const Mat4 &pv,
                   const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DrawDesc *d_draws, uint32_t n_draws,
-                  const FirstPrims &first_prims, float4 *out, uint32_t *d_item_head) {
+                  const FirstPrims &first_prims, float4 *final_out, uint32_t *d_item_head) {
   FrameParams fp = fp_in;
+  // option "supersample" >= 2: the kernels below render the fine frame, k_resolve (at the end) writes `final_out`
+  const bool resolve = c->supersample > 1;
+  float4 *out = resolve ? s.d_fine.ptr : final_out;
   // a rank without bands (more ranks than bands) still launches one row: its blocks fall off tiles_y and exit
   const int grid_y = std::max(1, c->world > 1 ? c->local_bands() * fp.band_tiles : fp.tiles_y);
   // A SHORT frame (at most option "no_tail_items" item slots: 1080p has 32 640) has no k_shade_items launch: k_raster's tiles
@@ -660,10 +685,11 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
   // (every frame still in flight, not just the previous one: with one stream per slot, or while the layout is being
   //  switched, "after the previous frame" no longer implies "after the one before")
   for (const FrameSlot &o : c->slots)
-    if (&o != &s && o.in_flight && o.out_used == out && o.stream_used != sr) (void)o.follow(sr);
-  // option "present_fused": k_raster / k_shade write presented pixels into the slot's RGBA8 image
-  uint32_t *out8 = c->present_fused ? s.d_present.ptr : nullptr;
-  const SrgbTables *tables = c->present_fused ? c->d_srgb_tables.ptr : nullptr;
+    if (&o != &s && o.in_flight && final_out && o.out_used == final_out && o.stream_used != sr) (void)o.follow(sr);
+  // option "present_fused": k_raster / k_shade write presented pixels into the slot's RGBA8 image (a fine frame is fp32: a
+  // presented byte cannot be averaged, k_resolve presents)
+  uint32_t *out8 = (c->present_fused && !resolve) ? s.d_present.ptr : nullptr;
+  const SrgbTables *tables = (c->present_fused && !resolve) ? c->d_srgb_tables.ptr : nullptr;
   if (fp.deferred)
     hipLaunchKernelGGL(k_deferred_background, dim3(1), dim3(kBackgroundThreads), 0, sr, sp, d_lights, s.d_background.ptr, tables, fp.gbuffer_view);
   uint32_t *item_head = short_frame ? d_item_head : nullptr;
@@ -671,10 +697,10 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
                      s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, out, fp, s.d_tris.ptr, s.d_clip.ptr, s.d_bins.ptr,
                      c->dump_vis ? c->d_vis_prim.ptr : nullptr,
                      c->dump_vis ? c->d_vis_depth.ptr : nullptr,
-                     fp.deferred ? s.d_background.ptr : nullptr, (c->overlays && c->world == 1) ? s.d_depth.ptr : nullptr,
+                     fp.deferred ? s.d_background.ptr : nullptr, (c->overlays && c->world == 1 && !resolve) ? s.d_depth.ptr : nullptr,
                      s.h_flags, out8, short_frame ? nullptr : s.d_item_groups.ptr, item_head, s.d_items.ptr, d_lights, sp.num_lights,
                      s.d_cooked.ptr, s.d_heavy.ptr);
-  s.has_depth = c->overlays && c->world == 1;
+  s.has_depth = c->overlays && c->world == 1 && !resolve;
   // k_shade's work list (64 fragments per item), built from the per-tile fragment counts as soon as k_raster is done; the
   // same launch cooks the frame's light table
   if (!short_frame)
@@ -753,10 +779,35 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
     if (out8) shade(std::false_type{}, std::true_type{});
     else shade(std::false_type{}, std::false_type{});
   }
+  if (resolve) {
+    // k_resolve, right behind k_shade (and the tail launch, whose edge `ss` already follows) on the frame's own stream.  The
+    // shading interval ends in front of it, the frame's interval behind it (the stop event of its own pair).
+    if (ev) (void)hipEventRecord(ev[4], ss);
+    hipEvent_t *re = ev ? &c->resolve_ring[2 * (c->ring_frames % bbr_context::kRingCap)] : nullptr;
+    if (re) (void)hipEventRecord(re[0], ss);
+    const int32_t rows = c->world > 1 ? c->shard_rows() : c->height;
+    const dim3 grid((unsigned)((c->width + kResolveThreads - 1) / kResolveThreads), (unsigned)rows);
+    auto launch = [&](auto n) {
+      constexpr int N = decltype(n)::value;
+      if (c->present_fused)
+        hipLaunchKernelGGL((k_resolve<N, true>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out, (float4 *)nullptr, s.d_present.ptr,
+                           c->width, c->d_srgb_tables.ptr, sp.tone_enable, sp.exposure);
+      else
+        hipLaunchKernelGGL((k_resolve<N, false>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out, final_out, (uint32_t *)nullptr,
+                           c->width, (const SrgbTables *)nullptr, 0, 0.f);
+    };
+    if (c->supersample == 2) launch(std::integral_constant<int, 2>{});
+    else if (c->supersample == 3) launch(std::integral_constant<int, 3>{});
+    else launch(std::integral_constant<int, 4>{});
+    if (re) {
+      (void)hipEventRecord(re[1], ss);
+      ++c->resolve_launches;
+    }
+  }
   (void)s.busy_until(ss);
   s.stream_used = ss;
   if (ev) {
-    (void)hipEventRecord(ev[4], ss);
+    if (!resolve) (void)hipEventRecord(ev[4], ss);
     ++c->ring_frames;
   }
 }
@@ -873,7 +924,7 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   c->pending_waits.clear();
   hipEvent_t *ev = nullptr;  // this frame's timing events, if it carries any
   if (c->timing && (c->timing_tick++ % (uint64_t)c->timing_stride) == 0) {
-    rc = ensure_timing_ring(c);
+    rc = ensure_timing_ring(c, c->supersample > 1);
     if (rc) return rc;
     ev = &c->ring[bbr_context::kRingEvents * (c->ring_frames % bbr_context::kRingCap)];
     if (c->timing == 1) HIP_TRY(c, hipEventRecord(ev[0], st.geom));
@@ -892,6 +943,7 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   sp.exposure = c->frame_u.exposure;
   sp.num_lights = n_lights;
   float4 *out = c->ext_out ? reinterpret_cast<float4 *>(c->ext_out) : s.d_frame.ptr;
+  if (c->present_fused && c->supersample > 1) out = nullptr;  // k_resolve writes the presented image: no W x H fp32 frame
 
   HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, s.h_staging, total, hipMemcpyHostToDevice, st.geom));
   if (c->tile_mode == 0) launch_frame<64, 64>(c, s, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head);
@@ -908,6 +960,7 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   s.frame_u = c->frame_u;
   s.view_u = c->view_u;
   s.out_used = out;
+  s.fine_used = c->supersample > 1 ? s.d_fine.ptr : nullptr;
   s.n_prims = c->n_prims;
   c->last_slot = slot_index;
   return BBR_OK;
@@ -1227,6 +1280,7 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
   BBR_ON_DEVICE(c);
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "draw_overlays: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_overlays: not available with a partition");
+  if (c->supersample > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_overlays: not available with option supersample >= 2 (no depth resolve rule)");
   int rc = sync_and_fix(c, nullptr);  // the overlay pass is synchronous: it is a debugging aid, not part of the hot path
   if (rc) return rc;
   FrameSlot &fs = c->slots[c->last_slot];
@@ -1566,6 +1620,8 @@ static void release_context(bbr_context *c) {
     if (e) (void)hipEventDestroy(e);
   for (auto &e : c->present_ring)
     if (e) (void)hipEventDestroy(e);
+  for (auto &e : c->resolve_ring)
+    if (e) (void)hipEventDestroy(e);
   c->d_srgb_tables.release();
   if (c->s_geom) (void)hipStreamDestroy(c->s_geom);
   if (c->s_raster) (void)hipStreamDestroy(c->s_raster);
@@ -1886,6 +1942,19 @@ int bbr_read_shard(bbr_context *c, float *host) {
   return BBR_OK;
 }
 
+int bbr_read_samples(bbr_context *c, float *host) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_samples: NULL");
+  if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_samples: not available on a partitioned context");
+  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_samples: nothing rendered");
+  if (c->supersample == 1) return bbr_read_framebuffer(c, host);  // one sample per pixel: the frame itself
+  int rc = sync_and_fix(c, nullptr);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpy(host, c->slots[c->last_slot].fine_used, (size_t)c->render_width() * c->render_height() * 16, hipMemcpyDeviceToHost));
+  return BBR_OK;
+}
+
 int bbr_framebuffer_device_ptr(bbr_context *c, void **out_ptr, uint64_t *out_bytes) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
@@ -1954,6 +2023,7 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
   c->rank = rank;
   c->world = world;
   c->band_rows = band_rows;
+  for (FrameSlot &s : c->slots) s.d_fine.release();  // (a fine shard's padding rows are the zeros of a fresh buffer)
   c->exchange_slot = -1;  // (block sizes change with the partition)
   c->exchange_whole = nullptr;
   if (c->ext_out) {
@@ -1966,28 +2036,19 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
   return BBR_OK;
 }
 
-// onWindowResize (src/main.cpp:1042-1061): wait for the device, drop everything whose size follows the swap-chain
-// extent, keep meshes, materials and options.  Buffers come back lazily with the next frame.
-int bbr_resize(bbr_context *c, int32_t width, int32_t height) {
-  if (!c) return BBR_ERR_INVALID_ARGUMENT;
-  BBR_ON_DEVICE(c);
-  if (width <= 0 || height <= 0 || width > 32768 || height > 32768)
-    return fail(c, BBR_ERR_INVALID_ARGUMENT, "resize: width/height out of range");
-  if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "resize: between begin_frame and end_frame");
-  int rc = drain(c);
-  if (rc) return rc;
-  if (width == c->width && height == c->height) return BBR_OK;
-  c->width = width;
-  c->height = height;
+// The render or the output extent changed (bbr_resize, option "supersample"): everything sized by either goes, the flag words
+// are forgotten and there is no current frame.  The context is drained.
+static void drop_extent_buffers(bbr_context *c) {
   auto drop = [](FrameSlot &s) {
     s.release_tile_buffers();
-    s.d_frame.release(); s.d_present.release(); s.d_depth.release();
+    s.d_frame.release(); s.d_fine.release(); s.d_present.release(); s.d_depth.release();
     s.has_depth = false;
     s.fused = false;
     s.present.active = false;
     s.present.out = nullptr;
     s.present.copy_to = nullptr;
     s.out_used = nullptr;
+    s.fine_used = nullptr;
     s.in_flight = false;
     s.forget_extent();
   };
@@ -2001,6 +2062,24 @@ int bbr_resize(bbr_context *c, int32_t width, int32_t height) {
   c->exchange_whole = nullptr;
   c->have_frame = false;
   c->last_slot = -1;
+}
+
+// onWindowResize (src/main.cpp:1042-1061): wait for the device, drop everything whose size follows the swap-chain
+// extent, keep meshes, materials and options.  Buffers come back lazily with the next frame.
+int bbr_resize(bbr_context *c, int32_t width, int32_t height) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (width <= 0 || height <= 0 || width > 32768 || height > 32768)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "resize: width/height out of range");
+  if ((int64_t)width * c->supersample > 32768 || (int64_t)height * c->supersample > 32768)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "resize: supersample x width/height exceeds 32768");
+  if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "resize: between begin_frame and end_frame");
+  int rc = drain(c);
+  if (rc) return rc;
+  if (width == c->width && height == c->height) return BBR_OK;
+  c->width = width;
+  c->height = height;
+  drop_extent_buffers(c);
   // a caller-owned output buffer was sized for the old extent: the caller sets it again (bbr_set_output_device_ptr)
   c->ext_out = nullptr;
   c->ext_out_bytes = 0;
@@ -2048,7 +2127,7 @@ int bbr_get_stats(bbr_context *c, bbr_stats *out) {
     size_t tiles = (size_t)c->tiles_x() * c->tiles_y();
     std::vector<uint32_t> fc(tiles);
     HIP_TRY(c, hipMemcpy(fc.data(), s.d_frag_count.ptr, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    int band_tiles = c->eff_band_rows() / c->tile_h();
+    int band_tiles = c->band_tiles();
     for (int ty = 0; ty < c->tiles_y(); ++ty) {
       if (c->world > 1 && ((ty / band_tiles) % c->world) != c->rank) continue;
       for (int tx = 0; tx < c->tiles_x(); ++tx) out->n_shaded += fc[(size_t)ty * c->tiles_x() + tx] & ~kFullTile;
@@ -2065,6 +2144,7 @@ int bbr_get_stats(bbr_context *c, bbr_stats *out) {
 int bbr_read_visibility(bbr_context *c, uint32_t *prim_host, float *depth_host) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
+  if (c->supersample > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_visibility: not available with option supersample >= 2 (its buffers have the output extent)");
   if (!c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_visibility: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_visibility: not available on a partitioned context");
   int rc = rerender_with(c, &bbr_context::dump_vis);
@@ -2079,6 +2159,7 @@ int bbr_read_gbuffer(bbr_context *c, float *host) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_gbuffer: NULL");
+  if (c->supersample > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_gbuffer: not available with option supersample >= 2 (its buffers have the output extent)");
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_gbuffer: nothing rendered");
   if (!c->deferred) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_gbuffer: option render_pass is not 1 (deferred)");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_gbuffer: not available with a partition");
@@ -2096,6 +2177,7 @@ int bbr_read_surface(bbr_context *c, float *host) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface: NULL");
+  if (c->supersample > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface: not available with option supersample >= 2 (its buffers have the output extent)");
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_surface: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface: not available on a partitioned context");
   int rc = rerender_with(c, &bbr_context::dump_surface);  // (the dumping instantiation of k_shade_aniso)
@@ -2162,6 +2244,7 @@ int bbr_read_records(bbr_context *c, void *records, void *triangles, uint32_t ca
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!out_count) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_records: NULL count");
+  if (c->supersample > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_records: not available with option supersample >= 2 (its buffers have the output extent)");
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_records: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_records: not available on a partitioned context");
   int rc = sync_and_fix(c, nullptr);
@@ -2198,7 +2281,9 @@ int bbr_last_frame_time_ms(bbr_context *c, float *out_frame_ms, float *out_shade
   if (rc) return rc;
   const hipEvent_t *e = &c->ring[bbr_context::kRingEvents * ((c->ring_frames - 1) % bbr_context::kRingCap)];
   float a = 0.f, b = 0.f;
-  if (c->timing == 1) HIP_TRY(c, hipEventElapsedTime(&a, e[0], e[4]));
+  // (option "supersample" >= 2: the frame ends behind its k_resolve, the stop event of the frame's resolve pair)
+  const hipEvent_t frame_end = c->supersample > 1 ? c->resolve_ring[2 * ((c->ring_frames - 1) % bbr_context::kRingCap) + 1] : e[4];
+  if (c->timing == 1) HIP_TRY(c, hipEventElapsedTime(&a, e[0], frame_end));
   HIP_TRY(c, hipEventElapsedTime(&b, e[3], e[4]));
   if (out_frame_ms) *out_frame_ms = a;
   if (out_shade_ms) *out_shade_ms = b;
@@ -2234,6 +2319,7 @@ int bbr_timing_reset(bbr_context *c) {
   if (rc) return rc;
   c->ring_frames = 0;
   c->present_launches = 0;
+  c->resolve_launches = 0;
   return BBR_OK;
 }
 
@@ -2250,7 +2336,7 @@ int bbr_timing_summary(bbr_context *c, uint32_t *out_frames, float *out_avg_fram
     const hipEvent_t *e = &c->ring[bbr_context::kRingEvents * i];
     float a = 0.f, b = 0.f, d = 0.f, h = 0.f;
     if (c->timing == 1) {
-      HIP_TRY(c, hipEventElapsedTime(&a, e[0], e[4]));
+      HIP_TRY(c, hipEventElapsedTime(&a, e[0], c->supersample > 1 ? c->resolve_ring[2 * i + 1] : e[4]));
       HIP_TRY(c, hipEventElapsedTime(&b, e[0], e[1]));
       HIP_TRY(c, hipEventElapsedTime(&d, e[1], e[2]));
     }
@@ -2283,6 +2369,24 @@ int bbr_present_timing(bbr_context *c, uint32_t *out_launches, float *out_avg_ms
   return BBR_OK;
 }
 
+int bbr_resolve_timing(bbr_context *c, uint32_t *out_launches, float *out_avg_ms) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!c->timing) return fail(c, BBR_ERR_INVALID_ARGUMENT, "resolve_timing: enable option \"timing\" first");
+  int rc = drain(c);
+  if (rc) return rc;
+  uint32_t n = std::min(c->resolve_launches, bbr_context::kRingCap);
+  double t = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->resolve_ring[2 * i], c->resolve_ring[2 * i + 1]));
+    t += ms;
+  }
+  if (out_launches) *out_launches = n;
+  if (out_avg_ms) *out_avg_ms = n ? (float)(t / n) : 0.f;
+  return BBR_OK;
+}
+
 int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
@@ -2303,9 +2407,10 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   if (n == "timing") {
     if (value < 0 || value > 2) return fail(c, BBR_ERR_INVALID_ARGUMENT, "timing: 0, 1 or 2");
     c->timing = (int)value;
-    if (value && (rc = ensure_timing_ring(c)) != BBR_OK) return rc;
+    if (value && (rc = ensure_timing_ring(c, c->supersample > 1)) != BBR_OK) return rc;
     c->ring_frames = 0;
     c->present_launches = 0;
+    c->resolve_launches = 0;
     c->timing_tick = 0;
   } else if (n == "timing_stride") {
     if (value < 1 || value > 1024) return fail(c, BBR_ERR_INVALID_ARGUMENT, "timing_stride: 1 .. 1024");
@@ -2350,6 +2455,21 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
         c->mip_levels = 1;
         return rc;
       }
+  } else if (n == "supersample") {
+    // like a resize of the render extent; the output extent, and with it a caller's output buffer, stay
+    if (value < 1 || value > 4) return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: 1 (off) .. 4");
+    if (value * c->width > 32768 || value * c->height > 32768)
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: supersample x width/height exceeds 32768");
+    if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: between begin_frame and end_frame");
+    if ((int)value != c->supersample) {
+      // (the one step that can fail comes first: a refused call leaves the context as it was)
+      if (c->timing && (rc = ensure_timing_ring(c, value > 1)) != BBR_OK) return rc;
+      c->supersample = (int)value;
+      drop_extent_buffers(c);
+      c->ring_frames = 0;  // (a frame's interval ends behind its k_resolve: the ring holds frames of one kind)
+      c->resolve_launches = 0;
+      c->timing_tick = 0;
+    }
   } else if (n == "present_fused") {
     c->present_fused = value != 0;
   } else if (n == "overlays") {
@@ -2574,6 +2694,8 @@ int check_exchange(bbr_context *c, int form, const char *who) {
     return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": form must be BBR_SHARD_RGBA32F, _PACKED, _RGBA8 or _RGBA16F");
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, std::string(who) + ": nothing rendered");
   const FrameSlot &s = c->slots[c->last_slot];
+  if (form == BBR_SHARD_PACKED && c->supersample > 1)  // (the form keeps one alpha BIT: a resolved alpha is a covered fraction)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": BBR_SHARD_PACKED is not lossless with option supersample >= 2");
   if (kWireForms[form].presented) {
     if (!s.present.active || !s.present.out) return fail(c, BBR_ERR_NOT_IN_FRAME, std::string(who) + ": BBR_SHARD_RGBA8 needs bbr_present first");
   } else if (s.fused) {

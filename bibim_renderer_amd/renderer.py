@@ -74,6 +74,7 @@ class Renderer:
         if rc != 0:
             raise BibimError(rc, (self._L.bbr_last_error(None) or b"").decode())
         self.width, self.height = int(width), int(height)
+        self.supersample = 1  # option "supersample": the fine frame is supersample x the output extent
         self._scenes = weakref.WeakSet()  # host-shim scenes hold meshes of this context: they must go first
 
     # -- plumbing --
@@ -166,6 +167,13 @@ class Renderer:
         self._check(self._L.bbr_read_framebuffer(self._ctx, _ptr(out)))
         return out
 
+    def read_samples(self):
+        """the fine frame of the last frame (option "supersample" = n): [n*height, n*width, 4] float32"""
+        n = self.supersample
+        out = np.empty((n * self.height, n * self.width, 4), np.float32)
+        self._check(self._L.bbr_read_samples(self._ctx, _ptr(out)))
+        return out
+
     def read_visibility(self):
         prim = np.empty((self.height, self.width), np.uint32)
         depth = np.empty((self.height, self.width), np.float32)
@@ -179,6 +187,8 @@ class Renderer:
 
     def set_option(self, name, value):
         self._check(self._L.bbr_set_option(self._ctx, name.encode(), int(value)))
+        if name == "supersample":
+            self.supersample = int(value)
 
     def last_frame_time_ms(self):
         a, b = C.c_float(), C.c_float()
@@ -309,6 +319,12 @@ class Renderer:
         """(launches, average k_present ms) since timing_reset(), option "timing" on"""
         n, t = C.c_uint32(), C.c_float()
         self._check(self._L.bbr_present_timing(self._ctx, C.byref(n), C.byref(t)))
+        return n.value, t.value
+
+    def resolve_timing(self):
+        """(launches, average k_resolve ms) since timing_reset(), options "timing" on and "supersample" >= 2"""
+        n, t = C.c_uint32(), C.c_float()
+        self._check(self._L.bbr_resolve_timing(self._ctx, C.byref(n), C.byref(t)))
         return n.value, t.value
 
     def presented_device_ptr(self):

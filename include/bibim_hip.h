@@ -86,7 +86,8 @@ int bbr_destroy(bbr_context *ctx);
  * for the frames in flight, drops every buffer whose size follows the extent and continues with the new one.  Meshes,
  * materials, options, the partition and the grown capacities stay.  There is no current frame afterwards (read-backs
  * fail with BBR_ERR_NOT_IN_FRAME until one is rendered) and a caller-owned output buffer has to be set again.
- * Not allowed between bbr_begin_frame and bbr_end_frame. */
+ * Not allowed between bbr_begin_frame and bbr_end_frame.  Option "supersample" stays: BBR_ERR_INVALID_ARGUMENT, with the
+ * context unchanged, when supersample x width or supersample x height exceeds 32768. */
 int bbr_resize(bbr_context *ctx, int32_t width, int32_t height);
 const char *bbr_last_error(const bbr_context *ctx); /* ctx may be NULL: last creation error */
 int bbr_device_count(void);
@@ -125,6 +126,10 @@ int bbr_synchronize(bbr_context *ctx);
 /* Full frame: height*width*4 floats, row-major, RGBA.  On a partitioned context (world > 1) this fails with
  * BBR_ERR_INVALID_ARGUMENT: the output is a compact shard, use bbr_read_shard. */
 int bbr_read_framebuffer(bbr_context *ctx, float *rgba32f_host);
+/* The fine frame of the last frame (option "supersample" = n): n*height * n*width * 4 floats, row-major -- the samples
+ * k_resolve averaged.  Synchronises.  BBR_ERR_NOT_IN_FRAME before a frame, BBR_ERR_INVALID_ARGUMENT on a partitioned context.
+ * With n = 1 it is bbr_read_framebuffer; with "present_fused" and n >= 2 it works (the fine frame exists). */
+int bbr_read_samples(bbr_context *ctx, float *rgba32f_host);
 int bbr_framebuffer_device_ptr(bbr_context *ctx, void **out_device_ptr, uint64_t *out_bytes);
 /* Render into caller-provided device memory instead (e.g. a torch tensor that RCCL all-gathers);
  * NULL restores the internal buffer.  bytes must cover the frame (or the shard when partitioned). */
@@ -170,6 +175,8 @@ int bbr_unpack_gathered_packed(bbr_context *ctx, const void *gathered_device, vo
 int bbr_tile_height(const bbr_context *ctx, int32_t *out_tile_h);
 
 /* ---- diagnostics ---- */
+/* (with option "supersample" = n >= 2 the counts are those of the render extent: n_shaded counts fine samples, n_tiles,
+ *  n_bin_refs and n_broad_tris fine tiles and their references) */
 int bbr_get_stats(bbr_context *ctx, bbr_stats *out);                            /* synchronises (and re-renders an overflowed frame) */
 /* How often a capacity (bins, every-tile list, clip arena) has been grown since bbr_create (= bbr_stats.bin_overflow), without
  * synchronising or touching the GPU: a host that times frames can tell afterwards whether one of them overflowed. */
@@ -189,7 +196,9 @@ int bbr_read_visibility(bbr_context *ctx, uint32_t *prim_host, float *depth_host
 int bbr_last_frame_time_ms(bbr_context *ctx, float *out_frame_ms, float *out_shade_kernel_ms);
 /* With option "timing" = 1 every frame records HIP events on the context's stream (frame start, geometry kernel
  * done, raster kernel done, shade kernel done) into a ring of 512 frames.  bbr_timing_summary averages the frames
- * recorded since bbr_timing_reset: whole frame, geometry (incl. the H2D of instances/lights), raster, shade. */
+ * recorded since bbr_timing_reset: whole frame, geometry (incl. the H2D of instances/lights), raster, shade.
+ * With option "supersample" >= 2 the frame interval (here and in bbr_last_frame_time_ms) ends behind the frame's k_resolve;
+ * the shade interval does not include it (bbr_resolve_timing has the kernel's own). */
 int bbr_timing_reset(bbr_context *ctx);
 int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_frame_ms, float *out_avg_geometry_ms,
                        float *out_avg_raster_ms, float *out_avg_shade_ms);
@@ -229,10 +238,42 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            shaded by k_shade_mip, whatever "max_anisotropy" is (the rule: "mip chains" below).  The TBN
  *                            overlay's vertex-stage fetch and the GUI sampler have no derivatives and stay on level 0.
  *                            Anything else: INVALID_ARGUMENT
+ *   "supersample" 1..4       n x n supersampling: rasterizationSamples = n^2 on a regular grid, sampleShadingEnable with
+ *                            minSampleShading = 1 and VK_RESOLVE_MODE_AVERAGE (the reference pins 1 sample,
+ *                            src/render.cpp:1104-1112).  1 (default): nothing changes, no kernel of the option runs.
+ *                            n >= 2: a context of W x H renders the FINE frame of nW x nH -- by definition what the same
+ *                            calls produce on a context created as nW x nH with "supersample" 1 (same uniforms, draws and
+ *                            options, the same 1/256 snap of the fine pixel grid, texture differences per fine pixel) --
+ *                            and k_resolve writes the W x H output.  Output pixel (x, y), all four channels, in binary32
+ *                            without contraction:
+ *                              acc = f(nx, ny)
+ *                              for j in 0..n-1, i in 0..n-1, (i, j) != (0, 0), row-major (i fastest): acc = acc + f(nx+i, ny+j)
+ *                              out = acc * R[n]    R[2] = 0.25f, R[3] = the binary32 nearest 1/9, R[4] = 0.0625f
+ *                            Alpha is averaged like the colours (forward: the covered fraction; deferred: 1); NaN and inf go
+ *                            through the additions as they are.  The resolve happens in linear HDR: bbr_present,
+ *                            bbr_tone_map, the exchange forms and bbr_draw_ui act on the resolved W x H values.  width /
+ *                            height everywhere else in this header stay the OUTPUT extent (outputs, shards, presented
+ *                            images, caller buffers); tiles, bins, the "tile_mode" limit of 65 536 tile slots and
+ *                            bbr_get_stats follow the render extent.  The fine frame is always library-owned.
+ *                            Setting it acts like a resize of the render extent: extent-sized buffers are dropped and
+ *                            there is no current frame afterwards; a caller's output buffer stays (the output size did
+ *                            not change).  INVALID_ARGUMENT, context unchanged, outside 1..4 or when n x width or
+ *                            n x height exceeds 32768.
+ *                            With "present_fused" and n >= 2 the fine frame is rendered by the fp32 kernels and k_resolve
+ *                            writes the presented RGBA8 image directly (binary16 stage included: the bytes of the unfused
+ *                            route with hdr16 = 1); there is no W x H fp32 frame and no k_present pass.
+ *                            Partition: bbr_set_partition keeps its meaning in OUTPUT rows (bands are n x band_rows fine
+ *                            rows); a rank's resolved shard is the shard of the resolved whole frame.  BBR_SHARD_PACKED
+ *                            keeps one alpha bit per pixel and is refused with n >= 2: bbr_stage_shard, bbr_pack_shard,
+ *                            bbr_allgather_frame and bbr_push_shard return INVALID_ARGUMENT for it and launch nothing.
+ *                            Also refused with n >= 2 (INVALID_ARGUMENT): bbr_draw_overlays, TBN included (its depth test
+ *                            needs a depth resolve rule), bbr_read_visibility, bbr_read_gbuffer, bbr_read_surface and
+ *                            bbr_read_records (their buffers have the output extent)
  *   "present_fused" 0|1      frames are produced as presented RGBA8 pixels directly (binary16 stage, tone map and sRGB
  *                            encode fused into the raster / shade kernels): no fp32 frame, no k_present pass; bbr_present
  *                            then only marks (or copies to a caller buffer), bbr_read_framebuffer / bbr_read_shard fail
- *   "overlays" 0|1           keep every frame's resolved depth for bbr_draw_overlays (default 0)
+ *   "overlays" 0|1           keep every frame's resolved depth for bbr_draw_overlays (default 0; nothing is kept while
+ *                            "supersample" >= 2, where bbr_draw_overlays is refused)
  *   "tbn" 0|1                bbr_draw_overlays first draws the TBN lines of the last frame (default 0; see below)
  *   "stream_layout" 0|1|2    how the kernels of the frames in flight are spread over HIP streams.  Same pixels in every
  *                            layout.  0: geometry + raster on one stream, shade on a second, present on a third.
@@ -478,6 +519,9 @@ int bbr_presented_device_ptr(bbr_context *ctx, void **out_ptr, uint64_t *out_byt
 int bbr_unpack_gathered_rgba8(bbr_context *ctx, const void *gathered_device, void *frame_device, void *hip_stream); /* BBR_SHARD_RGBA8 */
 /* with option "timing" on: launches of k_present since bbr_timing_reset and their average duration (HIP events) */
 int bbr_present_timing(bbr_context *ctx, uint32_t *out_launches, float *out_avg_ms);
+/* its sibling for option "supersample" >= 2: the k_resolve launches of the timed frames since bbr_timing_reset (one per frame
+ * that carries events, see "timing_stride") and their average duration */
+int bbr_resolve_timing(bbr_context *ctx, uint32_t *out_launches, float *out_avg_ms);
 /* hdr_tone_mapping.frag:9-18 alone on the fp32 frame, in place (no quantisation) */
 int bbr_tone_map(bbr_context *ctx, int32_t enable_tone_mapping, float exposure);
 
