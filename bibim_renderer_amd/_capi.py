@@ -72,6 +72,7 @@ SIGNATURES = {
     "bbr_synchronize": (C.c_int, [_P]),
     "bbr_read_framebuffer": (C.c_int, [_P, _P]),
     "bbr_read_samples": (C.c_int, [_P, _P]),
+    "bbr_read_sample_map": (C.c_int, [_P, _P]),
     "bbr_framebuffer_device_ptr": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     "bbr_set_output_device_ptr": (C.c_int, [_P, _P, C.c_uint64]),
     "bbr_set_stream": (C.c_int, [_P, _P]),

@@ -14,6 +14,8 @@
 //   k_present, k_tone_map, k_deferred_background, k_shade_overlay, k_pack_shard / k_unpack_*: the rows either side of the path
 //   k_tbn_segments, k_tbn_raster, k_tbn_colour: the TBN line overlay (option "tbn"; tbn.vert / tbn.geom)
 //   k_resolve    option "supersample": the n x n samples of the fine frame averaged into the output pixel, in a pinned order
+//   k_sample_merge, k_resolve_merged    option "sample_shading" 0: the fragment lists thinned to one fragment per primitive and
+//                output pixel behind k_raster, and the resolve that knows which sample stands for which
 //
 // Arithmetic contract: every floating-point expression below has the same operand order and the same
 // explicit fmaf() placement as the CPU oracle; the file is compiled with -ffp-contract=off, IEEE
@@ -3147,6 +3149,13 @@ BB_DEV float4 resolve_pixel(const float4 *__restrict__ fine, int32_t width, int3
   constexpr float r = resolve_scale<N>();
   return make_float4(__fmul_rn(acc.x, r), __fmul_rn(acc.y, r), __fmul_rn(acc.z, r), __fmul_rn(acc.w, r));
 }
+// PRESENT: the workgroup's copy of the presentation tables (every thread calls this; it ends in a barrier)
+BB_DEV void resolve_stage_tables(SrgbTables &t, const SrgbTables *__restrict__ tables) {
+  const uint32_t *src = reinterpret_cast<const uint32_t *>(tables);
+  uint32_t *dst = reinterpret_cast<uint32_t *>(&t);
+  for (uint32_t w = threadIdx.x; w < sizeof(SrgbTables) / 4; w += kResolveThreads) dst[w] = src[w];
+  __syncthreads();
+}
 template <int N, bool PRESENT>
 __global__ __launch_bounds__(kResolveThreads) void k_resolve(const float4 *__restrict__ fine, float4 *__restrict__ out,
                                                               uint32_t *__restrict__ out_rgba8, int32_t width,
@@ -3155,16 +3164,210 @@ __global__ __launch_bounds__(kResolveThreads) void k_resolve(const float4 *__res
   const size_t y = blockIdx.y, o = y * (size_t)width + (size_t)x;
   if constexpr (PRESENT) {
     __shared__ SrgbTables t;
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(tables);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(&t);
-    for (uint32_t w = threadIdx.x; w < sizeof(SrgbTables) / 4; w += kResolveThreads) dst[w] = src[w];
-    __syncthreads();
+    resolve_stage_tables(t, tables);
     if (x >= width) return;
     const float4 px = resolve_pixel<N>(fine, width, x, y);
     store_pixel(&out_rgba8[o], present_pixel(px.x, px.y, px.z, t, enable, exposure, 1));
   } else {
     if (x >= width) return;
     store_pixel(&out[o], resolve_pixel<N>(fine, width, x, y));
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// multisampling (option "sample_shading" 0 with "supersample" n = 2 or 4): one fragment is shaded per primitive and output
+// pixel.  The block of output pixel (x, y) is the fine pixels (nx + i, ny + j), indexed k = j * n + i; P(s) is the primitive
+// (reference >> 3: the sub-triangles of one clipped primitive are one primitive) that wins fine pixel s.
+//   rep(s) = the first s' of s's block, in index order, with P(s') == P(s)   (covered s);   rep(s) = s   (uncovered s)
+//   g(s)   = f(rep(s));   out = the resolve rule above applied to g
+// Only the samples with rep(s) == s, the representatives, are shaded -- as the fine pixels they are -- so the fine frame
+// holds f at them (and the background at uncovered samples) and nothing defined anywhere else.
+//
+// The SAMPLE MAP: one word per output pixel, a 4-bit field per sample holding rep(k) (16 bits at n = 2, 64 at n = 4), laid out
+// like the output frame (a rank's shard rows on a partitioned context).
+//
+// k_sample_merge, between k_raster and k_shade_items: one workgroup per fine tile, the tiles the rank owns in plain screen
+// order.  It reads the tile's fragment list (a kFullTile tile: the one word stands for all pixels) into registers, writes the
+// winner of every pixel into LDS, derives the map words of the tile's output pixels from that (written for empty tiles too:
+// identity), and rewrites the list in place with the representatives only -- their words unchanged, in their original
+// order: the list k_raster would have written had only they been covered, padded to 64 with its first word as k_raster
+// pads.  A full tile becomes an explicit list of TILE_PIXELS / n^2 words, in ascending pixel-field order, without the flag.
+// It does the accounting k_raster leaves out in this mode (frag_count, item_groups).
+// Blocks never straddle a tile (n divides 8, the side of the pixel field's 8 x 8 blocks) nor the frame (its extent is n x
+// the output's), so a tile's map words depend on that tile alone.
+// ------------------------------------------------------------------------------------------------
+constexpr int kMergeThreads = 256;
+constexpr uint32_t kNoPrim = 0xFFFFFFFFu;  // (a primitive index has 29 bits)
+template <int N> struct SampleMap;
+template <> struct SampleMap<2> { typedef uint16_t Word; };
+template <> struct SampleMap<4> { typedef unsigned long long Word; };
+// rep(k) of a map word
+template <int N>
+BB_DEV int sample_rep(typename SampleMap<N>::Word w, int k) { return (int)((w >> (4 * k)) & (typename SampleMap<N>::Word)(N * N - 1)); }
+
+template <int TILE_W, int TILE_H, int N>
+__global__ __launch_bounds__(kMergeThreads) void k_sample_merge(FrameParams fp, uint32_t *__restrict__ frag_count,
+                                                                unsigned long long *__restrict__ frags,
+                                                                typename SampleMap<N>::Word *__restrict__ map,
+                                                                uint32_t *__restrict__ item_groups) {
+  typedef typename SampleMap<N>::Word Word;
+  constexpr int TILE_PIXELS = TILE_W * TILE_H;
+  constexpr int PASSES = TILE_PIXELS / kMergeThreads;  // list words per thread
+  constexpr int WAVES = kMergeThreads / 64;
+  constexpr int OUT_W = TILE_W / N, OUT_H = TILE_H / N, OUT_PIXELS = OUT_W * OUT_H;
+  static_assert(8 % N == 0 && TILE_W % 8 == 0 && TILE_H % 8 == 0, "a block lies inside one 8 x 8 block of the pixel field");
+  static_assert(PASSES * WAVES <= 64, "the runs of kept words are scanned by one wave");
+  __shared__ uint32_t s_prim[TILE_PIXELS];       // P of every pixel of the tile, by pixel field; kNoPrim: nothing drawn
+  __shared__ Word s_map[OUT_PIXELS];             // the tile's map words
+  __shared__ uint32_t s_kept[PASSES * WAVES];    // representatives in each run of 64 list words
+  __shared__ unsigned long long s_pad_frag;      // the new list's first word
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tx = blockIdx.x;
+  int ty, out_tile_row;
+  if (!tile_row(fp, (int)blockIdx.y, ty, out_tile_row)) return;
+  const uint32_t tile = (uint32_t)ty * (uint32_t)fp.tiles_x + (uint32_t)tx;
+  unsigned long long *list = frags + (size_t)tile * TILE_PIXELS;
+
+  // ---- the whole list, into registers ----
+  const uint32_t raw = frag_count[tile];
+  const bool full = (raw & kFullTile) != 0u;
+  const uint32_t count = full ? (uint32_t)TILE_PIXELS : min(raw, (uint32_t)TILE_PIXELS);
+  unsigned long long fw[PASSES];
+  const unsigned long long word0 = full ? list[0] : 0ull;  // (pixel field 0: word i of the implied list is this one with pixel i)
+#pragma unroll
+  for (int k = 0; k < PASSES; ++k) {
+    const uint32_t i = (uint32_t)(k * kMergeThreads + tid);
+    fw[k] = full ? word0 + ((unsigned long long)i << 32) : (i < count ? list[i] : 0ull);
+    s_prim[i] = kNoPrim;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < PASSES; ++k)
+    if ((uint32_t)(k * kMergeThreads + tid) < count) s_prim[fragment_pixel<TILE_PIXELS>(fw[k])] = (uint32_t)fw[k] >> 3;
+  __syncthreads();
+
+  // ---- the map words of the tile's output pixels ----
+  const int out_width = fp.width / N;
+  for (int o = tid; o < OUT_PIXELS; o += kMergeThreads) {
+    const int bx = o % OUT_W, by = o / OUT_W;
+    uint32_t prim[N * N];
+#pragma unroll
+    for (int k = 0; k < N * N; ++k) prim[k] = s_prim[tile_index<TILE_W>(bx * N + k % N, by * N + k / N)];
+    Word w = 0;
+#pragma unroll
+    for (int k = 0; k < N * N; ++k) {
+      int rep = k;
+#pragma unroll
+      for (int e = k - 1; e >= 0; --e)
+        if (prim[k] != kNoPrim && prim[e] == prim[k]) rep = e;
+      w |= (Word)((Word)rep << (4 * k));
+    }
+    s_map[o] = w;
+    if (tx * TILE_W + bx * N < fp.width && ty * TILE_H + by * N < fp.height)
+      map[(size_t)(out_tile_row * OUT_H + by) * (size_t)out_width + (size_t)(tx * OUT_W + bx)] = w;
+  }
+  __syncthreads();
+
+  // ---- which words stay, and where ----
+  unsigned long long kept_mask[PASSES];
+#pragma unroll
+  for (int k = 0; k < PASSES; ++k) {
+    bool keep = false;
+    if ((uint32_t)(k * kMergeThreads + tid) < count) {
+      int x, y;
+      tile_pixel<TILE_W>(fragment_pixel<TILE_PIXELS>(fw[k]), x, y);
+      const int s = (y % N) * N + (x % N);
+      keep = sample_rep<N>(s_map[(y / N) * OUT_W + (x / N)], s) == s;
+    }
+    kept_mask[k] = __ballot(keep);
+    if (lane == 0) s_kept[k * WAVES + wave] = (uint32_t)__popcll(kept_mask[k]);
+  }
+  __syncthreads();  // (every load of the list has returned: its words went into the ballots above)
+  // the runs in list order: run r = k * WAVES + wave holds words [64 r, 64 r + 64); every wave scans the totals itself
+  const uint32_t mine = lane < PASSES * WAVES ? s_kept[lane] : 0u;
+  uint32_t incl = mine;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+    if (lane >= d) incl += up;
+  }
+  const uint32_t m = (uint32_t)__shfl((int)incl, 63);
+#pragma unroll
+  for (int k = 0; k < PASSES; ++k) {
+    const uint32_t base = (uint32_t)__shfl((int)(incl - mine), k * WAVES + wave);
+    if ((kept_mask[k] >> lane) & 1ull) {
+      const uint32_t at = base + (uint32_t)__popcll(kept_mask[k] & ((1ull << lane) - 1ull));
+      list[at] = fw[k];
+      if (at == 0u) s_pad_frag = fw[k];
+    }
+  }
+  __syncthreads();
+  // (k_shade loads 64 words before it knows the count: padded to a multiple of 64 with copies of the first, as k_raster pads)
+  if (m != 0u && (m & 63u) != 0u && tid < (int)(64u - (m & 63u))) list[m + (uint32_t)tid] = s_pad_frag;
+  if (tid == 0) {
+    frag_count[tile] = m;  // (N_shaded = sum of these: the representatives)
+    const uint32_t slot = blockIdx.y * gridDim.x + blockIdx.x;
+    if (item_groups && m) atomicAdd(&item_groups[(slot / kItemGroupSlots) * kItemGroupStride], (m + 63u) >> 6);
+  }
+}
+// Instantiated HERE, not where the host launches them: the compiler lays kernels out in the order they are instantiated, and
+// a kernel instantiated between k_raster's and k_shade_items' launches would move the kernels of the default path against
+// each other in the code object (they run side by side on pipelined frames).  From here all of them move together.
+template __global__ void k_sample_merge<32, 32, 2>(FrameParams, uint32_t *__restrict__, unsigned long long *__restrict__, SampleMap<2>::Word *__restrict__, uint32_t *__restrict__);
+template __global__ void k_sample_merge<32, 32, 4>(FrameParams, uint32_t *__restrict__, unsigned long long *__restrict__, SampleMap<4>::Word *__restrict__, uint32_t *__restrict__);
+template __global__ void k_sample_merge<64, 64, 2>(FrameParams, uint32_t *__restrict__, unsigned long long *__restrict__, SampleMap<2>::Word *__restrict__, uint32_t *__restrict__);
+template __global__ void k_sample_merge<64, 64, 4>(FrameParams, uint32_t *__restrict__, unsigned long long *__restrict__, SampleMap<4>::Word *__restrict__, uint32_t *__restrict__);
+
+// k_resolve_merged: k_resolve on g.  Per output pixel the map word, then fine[block + rep(k)] for k = 0 .. n^2 - 1 added in
+// the pinned order, a fine row of the block at a time as k_resolve does.  A pixel whose fields are all 0 (one primitive
+// covers the block: most pixels of a frame) loads its one value once; the n^2 - 1 additions stay, they are the rule.
+// Traffic per output pixel: the map word, 16 B per distinct representative, the store.
+template <int N>
+BB_DEV float4 resolve_merged_pixel(const float4 *__restrict__ fine, typename SampleMap<N>::Word w, int32_t width, int32_t x, size_t y) {
+  const size_t fine_pitch = (size_t)width * N;
+  const v4f *block = reinterpret_cast<const v4f *>(fine) + (y * N) * fine_pitch + (size_t)x * N;
+  v4f acc;
+  if (w == 0) {
+    const v4f v = __builtin_nontemporal_load(block);
+    acc = v;
+#pragma unroll
+    for (int k = 1; k < N * N; ++k) acc = resolve_add(acc, v);
+  } else {
+    acc = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int j = 0; j < N; ++j) {
+      v4f v[N];
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        const int r = sample_rep<N>(w, i);
+        v[i] = __builtin_nontemporal_load(block + (size_t)(r / N) * fine_pitch + (size_t)(r % N));
+      }
+      acc = j == 0 ? v[0] : resolve_add(acc, v[0]);
+#pragma unroll
+      for (int i = 1; i < N; ++i) acc = resolve_add(acc, v[i]);
+      w = (typename SampleMap<N>::Word)(w >> (4 * N));
+    }
+  }
+  constexpr float r = resolve_scale<N>();
+  return make_float4(__fmul_rn(acc.x, r), __fmul_rn(acc.y, r), __fmul_rn(acc.z, r), __fmul_rn(acc.w, r));
+}
+template <int N, bool PRESENT>
+__global__ __launch_bounds__(kResolveThreads) void k_resolve_merged(const float4 *__restrict__ fine,
+                                                                     const typename SampleMap<N>::Word *__restrict__ map,
+                                                                     float4 *__restrict__ out, uint32_t *__restrict__ out_rgba8,
+                                                                     int32_t width, const SrgbTables *__restrict__ tables, int enable,
+                                                                     float exposure) {
+  const int32_t x = (int32_t)(blockIdx.x * kResolveThreads + threadIdx.x);
+  const size_t y = blockIdx.y, o = y * (size_t)width + (size_t)x;
+  if constexpr (PRESENT) {
+    __shared__ SrgbTables t;
+    resolve_stage_tables(t, tables);
+    if (x >= width) return;
+    const float4 px = resolve_merged_pixel<N>(fine, map[o], width, x, y);
+    store_pixel(&out_rgba8[o], present_pixel(px.x, px.y, px.z, t, enable, exposure, 1));
+  } else {
+    if (x >= width) return;
+    store_pixel(&out[o], resolve_merged_pixel<N>(fine, map[o], width, x, y));
   }
 }
 

@@ -132,6 +132,8 @@ struct FrameSlot {
   DeviceBuffer<uint32_t> d_item_groups; // 64-fragment chunks per group of 256 launch slots (k_raster -> k_shade_items)
   DeviceBuffer<float4> d_frame;
   DeviceBuffer<float4> d_fine;        // option "supersample" >= 2: the fine frame k_resolve reads (always library-owned)
+  DeviceBuffer<unsigned long long> d_sample_map;  // option "sample_shading" 0: the frame's sample map (k_sample_merge ->
+                                      // k_resolve_merged), one word of 2 (n = 2) or 8 (n = 4) bytes per output pixel
   DeviceBuffer<float4> d_background;  // deferred path: colour of the pixels no geometry covers
   DeviceBuffer<float> d_depth;        // option "overlays": the frame's resolved depth, for bbr_draw_overlays
   bool has_depth = false;
@@ -171,6 +173,7 @@ struct FrameSlot {
   bool in_flight = false;
   float4 *out_used = nullptr;  // where the frame in this slot wrote its pixels
   float4 *fine_used = nullptr;  // option "supersample" >= 2: the fine frame those pixels were resolved from
+  const void *map_used = nullptr;  // option "sample_shading" 0: the sample map they were resolved with (else nullptr)
   hipStream_t stream_used = nullptr;  // the stream its k_shade ran on
   uint32_t n_prims = 0;
 
@@ -190,7 +193,7 @@ struct FrameSlot {
   void release_all() {
     d_staging.release(); d_tris.release(); d_attrs.release(); d_clip.release(); d_gathered.release(); d_whole.release();
     d_block_stats.release();
-    release_tile_buffers(); d_broad.release(); d_frame.release(); d_fine.release(); d_present.release(); d_background.release(); d_depth.release();
+    release_tile_buffers(); d_broad.release(); d_frame.release(); d_fine.release(); d_sample_map.release(); d_present.release(); d_background.release(); d_depth.release();
     if (h_staging) (void)hipHostFree(h_staging);
     h_staging = nullptr;
     if (h_flags) (void)hipHostFree(h_flags);
@@ -231,6 +234,11 @@ struct bbr_context {
   // option "supersample": everything up to and including shading (tiles, bins, fragment lists, items, the viewport, the flag
   // words) works on the render extent n * width x n * height; k_resolve brings the fine frame to the output extent
   int supersample = 1;
+  // option "sample_shading": 1 = every sample of the fine frame is shaded; 0 = one fragment per primitive and output pixel
+  // (k_sample_merge, k_resolve_merged).  Stored at any "supersample", in effect with n >= 2; the pair (3, 0) is refused.
+  int sample_shading = 1;
+  bool merged() const { return supersample > 1 && sample_shading == 0; }
+  size_t sample_map_bytes() const { return (size_t)width * (size_t)std::max(height, shard_rows()) * (supersample == 2 ? 2u : 8u); }
   int32_t render_width() const { return width * supersample; }
   int32_t render_height() const { return height * supersample; }
   hipStream_t s_geom = nullptr, s_raster = nullptr, s_shade = nullptr, s_present = nullptr;  // context-owned streams
@@ -508,6 +516,8 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s) {
   if (c->overlays && c->supersample == 1 && &s != &c->ov) HIP_TRY(c, s.d_depth.ensure((size_t)c->width * c->height));
   // (zero filled: the padding rows of a fine shard are never written, and k_resolve reads them)
   if (c->supersample > 1 && &s != &c->ov) HIP_TRY(c, s.d_fine.ensure(c->fine_pixels(), true));
+  // (zero filled like the fine frame: rep 0 for every sample of a shard's padding rows, which no tile writes)
+  if (c->merged() && &s != &c->ov) HIP_TRY(c, s.d_sample_map.ensure((c->sample_map_bytes() + 7) / 8, true));
   if (c->present_fused && &s != &c->ov) {
     HIP_TRY(c, s.d_present.ensure((size_t)c->width * out_rows));
     int rc_t = ensure_srgb_tables(c);
@@ -662,7 +672,10 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
   // the lights.  One kernel and one kernel boundary less on the frame's chain of dependent kernels; such a frame is also
   // shaded at full coverage, without the tail launch (below).
   const uint32_t max_items = (uint32_t)(fp.tiles_x * grid_y) * (uint32_t)(TW * TH / 64);
-  const bool short_frame = max_items <= (uint32_t)c->no_tail_items;
+  // option "sample_shading" 0 (n >= 2): always the long route -- k_sample_merge thins the lists behind k_raster and does the
+  // accounting of the items, which k_raster therefore leaves alone (both of its pointers are guarded)
+  const bool merged = c->merged();
+  const bool short_frame = !merged && max_items <= (uint32_t)c->no_tail_items;
   // Heavy tiles first (long frames; k_raster): the heavy rows in front of the launch are sized from the length of the list
   // the slot's previous frame produced (pinned word kFlagHeavyTiles) + 1/8 + 8.  A list that does not fit them is not
   // used by that frame at all (plain screen order), so the first frame of a slot, or one after a jump, is merely slower.
@@ -698,9 +711,18 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
                      c->dump_vis ? c->d_vis_prim.ptr : nullptr,
                      c->dump_vis ? c->d_vis_depth.ptr : nullptr,
                      fp.deferred ? s.d_background.ptr : nullptr, (c->overlays && c->world == 1 && !resolve) ? s.d_depth.ptr : nullptr,
-                     s.h_flags, out8, short_frame ? nullptr : s.d_item_groups.ptr, item_head, s.d_items.ptr, d_lights, sp.num_lights,
+                     s.h_flags, out8, (short_frame || merged) ? nullptr : s.d_item_groups.ptr, item_head, s.d_items.ptr, d_lights, sp.num_lights,
                      s.d_cooked.ptr, s.d_heavy.ptr);
   s.has_depth = c->overlays && c->world == 1 && !resolve;
+  if (merged) {
+    const dim3 grid((unsigned)fp.tiles_x, (unsigned)grid_y);
+    if (c->supersample == 2)
+      hipLaunchKernelGGL((k_sample_merge<TW, TH, 2>), grid, dim3(kMergeThreads), 0, sr, fp, s.d_frag_count.ptr, s.d_frags.ptr,
+                         reinterpret_cast<SampleMap<2>::Word *>(s.d_sample_map.ptr), s.d_item_groups.ptr);
+    else
+      hipLaunchKernelGGL((k_sample_merge<TW, TH, 4>), grid, dim3(kMergeThreads), 0, sr, fp, s.d_frag_count.ptr, s.d_frags.ptr,
+                         reinterpret_cast<SampleMap<4>::Word *>(s.d_sample_map.ptr), s.d_item_groups.ptr);
+  }
   // k_shade's work list (64 fragments per item), built from the per-tile fragment counts as soon as k_raster is done; the
   // same launch cooks the frame's light table
   if (!short_frame)
@@ -787,6 +809,16 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
     if (re) (void)hipEventRecord(re[0], ss);
     const int32_t rows = c->world > 1 ? c->shard_rows() : c->height;
     const dim3 grid((unsigned)((c->width + kResolveThreads - 1) / kResolveThreads), (unsigned)rows);
+    auto launch_merged = [&](auto n) {
+      constexpr int N = decltype(n)::value;
+      const auto *map = reinterpret_cast<const typename SampleMap<N>::Word *>(s.d_sample_map.ptr);
+      if (c->present_fused)
+        hipLaunchKernelGGL((k_resolve_merged<N, true>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out, map, (float4 *)nullptr,
+                           s.d_present.ptr, c->width, c->d_srgb_tables.ptr, sp.tone_enable, sp.exposure);
+      else
+        hipLaunchKernelGGL((k_resolve_merged<N, false>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out, map, final_out,
+                           (uint32_t *)nullptr, c->width, (const SrgbTables *)nullptr, 0, 0.f);
+    };
     auto launch = [&](auto n) {
       constexpr int N = decltype(n)::value;
       if (c->present_fused)
@@ -796,7 +828,9 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
         hipLaunchKernelGGL((k_resolve<N, false>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out, final_out, (uint32_t *)nullptr,
                            c->width, (const SrgbTables *)nullptr, 0, 0.f);
     };
-    if (c->supersample == 2) launch(std::integral_constant<int, 2>{});
+    if (merged && c->supersample == 2) launch_merged(std::integral_constant<int, 2>{});
+    else if (merged) launch_merged(std::integral_constant<int, 4>{});
+    else if (c->supersample == 2) launch(std::integral_constant<int, 2>{});
     else if (c->supersample == 3) launch(std::integral_constant<int, 3>{});
     else launch(std::integral_constant<int, 4>{});
     if (re) {
@@ -961,6 +995,7 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   s.view_u = c->view_u;
   s.out_used = out;
   s.fine_used = c->supersample > 1 ? s.d_fine.ptr : nullptr;
+  s.map_used = c->merged() ? s.d_sample_map.ptr : nullptr;
   s.n_prims = c->n_prims;
   c->last_slot = slot_index;
   return BBR_OK;
@@ -1942,6 +1977,30 @@ int bbr_read_shard(bbr_context *c, float *host) {
   return BBR_OK;
 }
 
+// rep(s) of every fine pixel of the last frame, row-major, as an index 0 .. n^2 - 1 of its block (the identity without a
+// map).  The frame has completed; whole-frame contexts only.
+static int read_sample_map_synced(bbr_context *c, uint8_t *host) {
+  const int n = c->supersample;
+  const size_t fw = (size_t)c->render_width(), fh = (size_t)c->render_height();
+  const void *map = c->slots[c->last_slot].map_used;
+  if (!map) {
+    for (size_t y = 0; y < fh; ++y)
+      for (size_t x = 0; x < fw; ++x) host[y * fw + x] = (uint8_t)((y % n) * n + (x % n));
+    return BBR_OK;
+  }
+  const size_t pixels = (size_t)c->width * c->height;
+  std::vector<unsigned long long> words((c->sample_map_bytes() + 7) / 8);
+  HIP_TRY(c, hipMemcpy(words.data(), map, pixels * (n == 2 ? 2 : 8), hipMemcpyDeviceToHost));
+  const uint16_t *w2 = reinterpret_cast<const uint16_t *>(words.data());
+  for (size_t y = 0; y < fh; ++y)
+    for (size_t x = 0; x < fw; ++x) {
+      const size_t o = (y / n) * (size_t)c->width + x / n;
+      const unsigned long long w = n == 2 ? (unsigned long long)w2[o] : words[o];
+      host[y * fw + x] = (uint8_t)((w >> (4 * ((y % n) * n + (x % n)))) & (unsigned long long)(n * n - 1));
+    }
+  return BBR_OK;
+}
+
 int bbr_read_samples(bbr_context *c, float *host) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
@@ -1952,7 +2011,33 @@ int bbr_read_samples(bbr_context *c, float *host) {
   int rc = sync_and_fix(c, nullptr);
   if (rc) return rc;
   HIP_TRY(c, hipMemcpy(host, c->slots[c->last_slot].fine_used, (size_t)c->render_width() * c->render_height() * 16, hipMemcpyDeviceToHost));
+  if (c->slots[c->last_slot].map_used) {
+    // option "sample_shading" 0: g, every sample the value of its representative (a diagnostic: replicated here, on the host;
+    // the fine frame holds nothing defined at a sample that is not one).  A representative precedes what it stands for.
+    std::vector<uint8_t> rep((size_t)c->render_width() * c->render_height());
+    rc = read_sample_map_synced(c, rep.data());
+    if (rc) return rc;
+    const int n = c->supersample;
+    const size_t fw = (size_t)c->render_width();
+    for (size_t y = 0; y < (size_t)c->render_height(); ++y)
+      for (size_t x = 0; x < fw; ++x) {
+        const int r = rep[y * fw + x];
+        const size_t src = ((y / n) * n + (size_t)(r / n)) * fw + (x / n) * n + (size_t)(r % n);
+        if (src != y * fw + x) memcpy(host + 4 * (y * fw + x), host + 4 * src, 16);
+      }
+  }
   return BBR_OK;
+}
+
+int bbr_read_sample_map(bbr_context *c, uint8_t *host) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_sample_map: NULL");
+  if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_sample_map: not available on a partitioned context");
+  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_sample_map: nothing rendered");
+  int rc = sync_and_fix(c, nullptr);
+  if (rc) return rc;
+  return read_sample_map_synced(c, host);
 }
 
 int bbr_framebuffer_device_ptr(bbr_context *c, void **out_ptr, uint64_t *out_bytes) {
@@ -2023,7 +2108,10 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
   c->rank = rank;
   c->world = world;
   c->band_rows = band_rows;
-  for (FrameSlot &s : c->slots) s.d_fine.release();  // (a fine shard's padding rows are the zeros of a fresh buffer)
+  for (FrameSlot &s : c->slots) {  // (a fine shard's padding rows, and their map words, are the zeros of a fresh buffer)
+    s.d_fine.release();
+    s.d_sample_map.release();
+  }
   c->exchange_slot = -1;  // (block sizes change with the partition)
   c->exchange_whole = nullptr;
   if (c->ext_out) {
@@ -2041,7 +2129,7 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
 static void drop_extent_buffers(bbr_context *c) {
   auto drop = [](FrameSlot &s) {
     s.release_tile_buffers();
-    s.d_frame.release(); s.d_fine.release(); s.d_present.release(); s.d_depth.release();
+    s.d_frame.release(); s.d_fine.release(); s.d_sample_map.release(); s.d_present.release(); s.d_depth.release();
     s.has_depth = false;
     s.fused = false;
     s.present.active = false;
@@ -2049,6 +2137,7 @@ static void drop_extent_buffers(bbr_context *c) {
     s.present.copy_to = nullptr;
     s.out_used = nullptr;
     s.fine_used = nullptr;
+    s.map_used = nullptr;
     s.in_flight = false;
     s.forget_extent();
   };
@@ -2461,6 +2550,8 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
     if (value * c->width > 32768 || value * c->height > 32768)
       return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: supersample x width/height exceeds 32768");
     if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: between begin_frame and end_frame");
+    if (value == 3 && c->sample_shading == 0)
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: 3 is not available with option sample_shading 0 (a 3 x 3 block straddles the tiles)");
     if ((int)value != c->supersample) {
       // (the one step that can fail comes first: a refused call leaves the context as it was)
       if (c->timing && (rc = ensure_timing_ring(c, value > 1)) != BBR_OK) return rc;
@@ -2469,6 +2560,23 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
       c->ring_frames = 0;  // (a frame's interval ends behind its k_resolve: the ring holds frames of one kind)
       c->resolve_launches = 0;
       c->timing_tick = 0;
+    }
+  } else if (n == "sample_shading") {
+    // no extent changes: only the sample maps go, and there is no current frame (its samples were of the other kind)
+    if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "sample_shading: 1 (every sample) or 0 (one fragment per primitive and pixel)");
+    if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "sample_shading: between begin_frame and end_frame");
+    if (value == 0 && c->supersample == 3)
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, "sample_shading: 0 is not available with option supersample 3 (a 3 x 3 block straddles the tiles)");
+    if ((int)value != c->sample_shading) {
+      c->sample_shading = (int)value;
+      for (FrameSlot &s : c->slots) {
+        s.d_sample_map.release();
+        s.map_used = nullptr;
+      }
+      c->exchange_slot = -1;
+      c->exchange_whole = nullptr;
+      c->have_frame = false;
+      c->last_slot = -1;
     }
   } else if (n == "present_fused") {
     c->present_fused = value != 0;

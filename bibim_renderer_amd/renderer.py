@@ -174,6 +174,14 @@ class Renderer:
         self._check(self._L.bbr_read_samples(self._ctx, _ptr(out)))
         return out
 
+    def read_sample_map(self):
+        """rep(s) of every fine pixel of the last frame (option "sample_shading"): [n*height, n*width] uint8, each an index
+        0 .. n*n - 1 into the sample's block; the identity with "sample_shading" 1 or n = 1"""
+        n = self.supersample
+        out = np.empty((n * self.height, n * self.width), np.uint8)
+        self._check(self._L.bbr_read_sample_map(self._ctx, _ptr(out)))
+        return out
+
     def read_visibility(self):
         prim = np.empty((self.height, self.width), np.uint32)
         depth = np.empty((self.height, self.width), np.float32)

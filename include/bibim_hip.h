@@ -130,6 +130,13 @@ int bbr_read_framebuffer(bbr_context *ctx, float *rgba32f_host);
  * k_resolve averaged.  Synchronises.  BBR_ERR_NOT_IN_FRAME before a frame, BBR_ERR_INVALID_ARGUMENT on a partitioned context.
  * With n = 1 it is bbr_read_framebuffer; with "present_fused" and n >= 2 it works (the fine frame exists). */
 int bbr_read_samples(bbr_context *ctx, float *rgba32f_host);
+/* With option "sample_shading" 0 (and n >= 2) bbr_read_samples returns g: every sample holds the value of its
+ * representative (replicated on the host from the fine frame and the sample map).
+ * bbr_read_sample_map: rep(s) of every fine pixel of the last frame, n*width * n*height bytes, row-major over the fine frame,
+ * each an index 0 .. n^2 - 1 into the sample's block (k = j * n + i).  The identity (each sample its own index) with
+ * "sample_shading" 1 or n = 1.  Synchronises.  BBR_ERR_NOT_IN_FRAME before a frame, BBR_ERR_INVALID_ARGUMENT on a
+ * partitioned context. */
+int bbr_read_sample_map(bbr_context *ctx, uint8_t *out);
 int bbr_framebuffer_device_ptr(bbr_context *ctx, void **out_device_ptr, uint64_t *out_bytes);
 /* Render into caller-provided device memory instead (e.g. a torch tensor that RCCL all-gathers);
  * NULL restores the internal buffer.  bytes must cover the frame (or the shard when partitioned). */
@@ -176,7 +183,8 @@ int bbr_tile_height(const bbr_context *ctx, int32_t *out_tile_h);
 
 /* ---- diagnostics ---- */
 /* (with option "supersample" = n >= 2 the counts are those of the render extent: n_shaded counts fine samples, n_tiles,
- *  n_bin_refs and n_broad_tris fine tiles and their references) */
+ *  n_bin_refs and n_broad_tris fine tiles and their references; with option "sample_shading" 0 n_shaded counts the
+ *  representatives, i.e. the fragments that were shaded) */
 int bbr_get_stats(bbr_context *ctx, bbr_stats *out);                            /* synchronises (and re-renders an overflowed frame) */
 /* How often a capacity (bins, every-tile list, clip arena) has been grown since bbr_create (= bbr_stats.bin_overflow), without
  * synchronising or touching the GPU: a host that times frames can tell afterwards whether one of them overflowed. */
@@ -269,6 +277,32 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            Also refused with n >= 2 (INVALID_ARGUMENT): bbr_draw_overlays, TBN included (its depth test
  *                            needs a depth resolve rule), bbr_read_visibility, bbr_read_gbuffer, bbr_read_surface and
  *                            bbr_read_records (their buffers have the output extent)
+ *   "sample_shading" 0|1     with "supersample" n >= 2: 1 (default) shades every sample (sampleShadingEnable = VK_TRUE, the
+ *                            rule above, bit for bit; no kernel of this option runs).  0 is multisampling
+ *                            (sampleShadingEnable = VK_FALSE): one fragment is shaded per primitive and output pixel.
+ *                            The block of output pixel (x, y) is the fine pixels (nx + i, ny + j), indexed k = j * n + i;
+ *                            P(s) is the primitive that wins fine pixel s (the sub-triangles of a clipped primitive are one
+ *                            primitive):
+ *                              rep(s) = the first s' of s's block, in index order, with P(s') == P(s)   (covered s)
+ *                              rep(s) = s                                                               (uncovered s)
+ *                              g(s)   = f(rep(s))                                                       all four channels
+ *                              out    = the resolve rule of "supersample" applied to g
+ *                            Only the samples with rep(s) == s, the representatives, are shaded, each as the fine pixel it
+ *                            is (its own planes, clip slot and per-fine-pixel texture differences): its value is the fine
+ *                            frame's, bit for bit.  A representative is a covered sample; nothing is extrapolated outside
+ *                            its primitive.  An interior pixel returns its representative's bits at n = 2 and comes back
+ *                            within the rounding of the sixteen additions at n = 4; forward alpha stays the covered
+ *                            fraction.  Deviations from Vulkan multisampling: the shading position is sample 0's of the
+ *                            primitive in the pixel, not the pixel centre, and the texture footprint stays the fine
+ *                            pixel's (not differences over n fine pixels).  k_sample_merge thins the fragment lists behind
+ *                            k_raster (the frame always takes the k_shade_items route, whatever "no_tail_items" says) and
+ *                            k_resolve_merged replaces k_resolve, also under "present_fused".  bbr_get_stats' n_shaded is
+ *                            then the number of representatives.  With "timing" the merge falls into the raster interval.
+ *                            The value is stored at any "supersample" and takes effect with n >= 2.  "supersample" 3 with
+ *                            "sample_shading" 0 is refused (a 3 x 3 block straddles the tiles): whichever call would
+ *                            complete the pair returns INVALID_ARGUMENT and leaves the context unchanged.  Values other
+ *                            than 0 and 1: INVALID_ARGUMENT.  Setting it leaves no current frame; only the sample maps
+ *                            are dropped.  Everything "supersample" >= 2 refuses stays refused
  *   "present_fused" 0|1      frames are produced as presented RGBA8 pixels directly (binary16 stage, tone map and sRGB
  *                            encode fused into the raster / shade kernels): no fp32 frame, no k_present pass; bbr_present
  *                            then only marks (or copies to a caller buffer), bbr_read_framebuffer / bbr_read_shard fail
