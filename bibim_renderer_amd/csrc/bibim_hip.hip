@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/bibim_hip.h"
@@ -107,6 +108,46 @@ struct DeviceBuffer {
   }
 };
 
+// What the options in force mean for a frame: decided in frame_mode (below) and nowhere else.  ensure_slot_buffers allocates
+// from it, launch_frame takes its pointers from it, and the slot keeps it for the read-backs.  The default is "no frame".
+struct FrameMode {
+  int n = 1;             // option "supersample": samples per output pixel along each axis
+  bool resolve = false;  // n >= 2: the kernels up to shading write the fine frame (library-owned), k_resolve the output
+  bool merged = false;   // ... with option "sample_shading" 0: a sample map, k_sample_merge, k_resolve_merged
+  bool depth = false;    // option "overlays": the frame keeps its depth for bbr_draw_overlays (whole frame, n = 1)
+  bool fused = false;    // option "present_fused": the frame is written as presented RGBA8 (the slot's d_present) ...
+  bool shade_presents() const { return fused && !resolve; }   // ... by k_raster / k_shade
+  bool resolve_presents() const { return fused && resolve; }  // ... by k_resolve (a presented byte cannot be averaged): then
+  bool frame32() const { return !resolve_presents(); }        //     there is no W x H fp32 frame at all
+  size_t out_rows = 0, fine_pixels = 0, map_words = 0;  // output rows (a shard's padding included); resolve: fine pixels; merged: the map in 8-byte words
+};
+inline size_t sample_map_word_bytes(int n) { return n == 2 ? sizeof(SampleMap<2>::Word) : sizeof(SampleMap<4>::Word); }
+
+// A ring of (start, stop) event pairs around one kind of launch while option "timing" is on, with the number of launches
+// since the last reset.  The events are made on demand and live as long as the context.
+constexpr uint32_t kRingCap = 512;
+struct PairRing {
+  std::vector<hipEvent_t> events;
+  uint32_t launches = 0;
+  hipError_t ensure() {
+    for (hipEvent_t e = nullptr; events.size() < 2 * kRingCap; events.push_back(e))
+      if (hipError_t err = hipEventCreate(&e)) return err;
+    return hipSuccess;
+  }
+  hipEvent_t start(uint32_t i) const { return events[2 * (i % kRingCap)]; }
+  hipEvent_t stop(uint32_t i) const { return events[2 * (i % kRingCap) + 1]; }
+  hipError_t begin(hipStream_t st) { return hipEventRecord(start(launches), st); }
+  hipError_t end(hipStream_t st) { return hipEventRecord(stop(launches++), st); }
+  void reset() { launches = 0; }
+  void destroy() { for (hipEvent_t e : events) (void)hipEventDestroy(e); }
+};
+
+// A run-time choice as a compile-time constant: f(std::true_type or std::false_type), f(std::integral_constant<int, n>)
+template <class F> void with_bool(bool b, F &&f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F> void with_samples(int n, F &&f) {  // n = 2, 3 or 4
+  n == 2 ? f(std::integral_constant<int, 2>{}) : n == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 4>{});
+}
+
 }  // namespace
 
 // Everything one frame in flight owns.
@@ -136,8 +177,7 @@ struct FrameSlot {
                                       // k_resolve_merged), one word of 2 (n = 2) or 8 (n = 4) bytes per output pixel
   DeviceBuffer<float4> d_background;  // deferred path: colour of the pixels no geometry covers
   DeviceBuffer<float> d_depth;        // option "overlays": the frame's resolved depth, for bbr_draw_overlays
-  bool has_depth = false;
-  bool fused = false;                 // rendered with option "present_fused": d_present holds the frame, d_frame nothing
+  FrameMode mode;                     // of the frame in this slot: which of the buffers above hold it (fused: d_present, d_frame nothing)
   FrameUniformBlock frame_u = {};     // the uniforms the frame in this slot was rendered with (overlays need them)
   ViewUniformBlock view_u = {};
   DeviceBuffer<uint32_t> d_present;  // RGBA8 presented image of this slot's frame (bbr_present)
@@ -172,8 +212,6 @@ struct FrameSlot {
   } ui;
   bool in_flight = false;
   float4 *out_used = nullptr;  // where the frame in this slot wrote its pixels
-  float4 *fine_used = nullptr;  // option "supersample" >= 2: the fine frame those pixels were resolved from
-  const void *map_used = nullptr;  // option "sample_shading" 0: the sample map they were resolved with (else nullptr)
   hipStream_t stream_used = nullptr;  // the stream its k_shade ran on
   uint32_t n_prims = 0;
 
@@ -237,8 +275,6 @@ struct bbr_context {
   // option "sample_shading": 1 = every sample of the fine frame is shaded; 0 = one fragment per primitive and output pixel
   // (k_sample_merge, k_resolve_merged).  Stored at any "supersample", in effect with n >= 2; the pair (3, 0) is refused.
   int sample_shading = 1;
-  bool merged() const { return supersample > 1 && sample_shading == 0; }
-  size_t sample_map_bytes() const { return (size_t)width * (size_t)std::max(height, shard_rows()) * (supersample == 2 ? 2u : 8u); }
   int32_t render_width() const { return width * supersample; }
   int32_t render_height() const { return height * supersample; }
   hipStream_t s_geom = nullptr, s_raster = nullptr, s_shade = nullptr, s_present = nullptr;  // context-owned streams
@@ -321,11 +357,9 @@ struct bbr_context {
   // timing ring: (frame start, geometry done, raster done, shade start, shade done) per frame since the last reset
   std::vector<hipEvent_t> ring;
   uint32_t ring_frames = 0;
-  std::vector<hipEvent_t> present_ring;  // (start, stop) around each k_present while timing is on
-  uint32_t present_launches = 0;
-  std::vector<hipEvent_t> resolve_ring;  // (start, stop) around the k_resolve of each timed frame: the pair of ring frame i
-  uint32_t resolve_launches = 0;
-  static constexpr uint32_t kRingCap = 512;
+  PairRing present_ring;  // around each k_present while timing is on
+  PairRing resolve_ring;  // around the k_resolve of each timed frame: pair i is ring frame i's (the two counts are reset together)
+  static constexpr uint32_t kRingCap = ::kRingCap;
   static constexpr uint32_t kRingEvents = 5;
   int retries = 0;
   // host side of the frame loop since the last bbr_host_timing_reset (steady_clock; no GPU call is made to keep them):
@@ -424,6 +458,41 @@ int fail(bbr_context *ctx, int code, const std::string &msg) {
                   std::string(#expr) + ": " + hipGetErrorString(_e));                                          \
   } while (0)
 
+// The mode of the next frame: what the options in force imply, stated here and nowhere else.
+FrameMode frame_mode(const bbr_context *c) {
+  FrameMode m;
+  m.n = c->supersample;
+  m.resolve = c->supersample > 1;
+  m.merged = m.resolve && c->sample_shading == 0;
+  m.fused = c->present_fused;
+  // (bbr_draw_overlays is refused on a partition, and with n >= 2: no depth is kept there until a depth resolve rule exists)
+  m.depth = c->overlays && c->world == 1 && !m.resolve;
+  m.out_rows = (size_t)std::max(c->height, c->shard_rows());
+  if (m.resolve) m.fine_pixels = c->fine_pixels();
+  if (m.merged) m.map_words = ((size_t)c->width * m.out_rows * sample_map_word_bytes(m.n) + 7) / 8;
+  return m;
+}
+
+// What has the output extent (the overlay pass's depth, the dumps, the records) does not exist with n >= 2.
+int refuse_supersampled(bbr_context *c, const char *who, const char *why = "its buffers have the output extent") {
+  if (!frame_mode(c).resolve) return BBR_OK;
+  return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": not available with option supersample >= 2 (" + why + ")");
+}
+// the pair of options that is refused, in whichever order it is asked for: a 3 x 3 block straddles the tiles
+bool refused_pair(int64_t supersample, int64_t sample_shading) { return supersample == 3 && sample_shading == 0; }
+// the render extent n * width x n * height has the limit of the output extent (bbr_create)
+constexpr int32_t kMaxExtent = 32768;
+int check_render_extent(bbr_context *c, const char *who, int64_t n, int32_t width, int32_t height) {
+  if (n * width <= kMaxExtent && n * height <= kMaxExtent) return BBR_OK;
+  return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": supersample x width/height exceeds 32768");
+}
+// there is no current frame any more, and no whole frame of an exchange
+void forget_current_frame(bbr_context *c) {
+  c->exchange_slot = c->last_slot = -1;
+  c->exchange_whole = nullptr;
+  c->have_frame = false;
+}
+
 // P*V exactly as the vertex stage's contract evaluates it (column j = P * V[j], fmaf chain)
 Mat4 proj_view(const ViewUniformBlock &v) {
   Mat4 r;
@@ -498,9 +567,8 @@ int ensure_pass_buffers(bbr_context *c, FrameSlot &s, uint32_t n_prims) {
   return BBR_OK;
 }
 
-int ensure_slot_buffers(bbr_context *c, FrameSlot &s) {
+int ensure_slot_buffers(bbr_context *c, FrameSlot &s, const FrameMode &m) {
   size_t tiles = (size_t)c->tiles_x() * c->tiles_y();
-  size_t out_rows = (size_t)std::max(c->height, c->shard_rows());
   int rc = ensure_pass_buffers(c, s, c->n_prims);
   if (rc) return rc;
   HIP_TRY(c, c->d_counters_done.ensure(bbr_context::kCounterBlocks, true));
@@ -512,21 +580,19 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s) {
   HIP_TRY(c, s.d_cooked.ensure(kMaxNumLights));
   HIP_TRY(c, s.d_heavy.ensure(tiles * kBinClasses, true));
   if (c->deferred) HIP_TRY(c, s.d_background.ensure(2));
-  // (bbr_draw_overlays is refused with "supersample" >= 2: no depth is kept there until a depth resolve rule exists)
-  if (c->overlays && c->supersample == 1 && &s != &c->ov) HIP_TRY(c, s.d_depth.ensure((size_t)c->width * c->height));
+  if (m.depth) HIP_TRY(c, s.d_depth.ensure((size_t)c->width * c->height));
   // (zero filled: the padding rows of a fine shard are never written, and k_resolve reads them)
-  if (c->supersample > 1 && &s != &c->ov) HIP_TRY(c, s.d_fine.ensure(c->fine_pixels(), true));
+  if (m.resolve) HIP_TRY(c, s.d_fine.ensure(m.fine_pixels, true));
   // (zero filled like the fine frame: rep 0 for every sample of a shard's padding rows, which no tile writes)
-  if (c->merged() && &s != &c->ov) HIP_TRY(c, s.d_sample_map.ensure((c->sample_map_bytes() + 7) / 8, true));
-  if (c->present_fused && &s != &c->ov) {
-    HIP_TRY(c, s.d_present.ensure((size_t)c->width * out_rows));
+  if (m.merged) HIP_TRY(c, s.d_sample_map.ensure(m.map_words, true));
+  if (m.fused) {
+    HIP_TRY(c, s.d_present.ensure((size_t)c->width * m.out_rows));
     int rc_t = ensure_srgb_tables(c);
     if (rc_t) return rc_t;
   }
   if (c->dump_gbuffer) HIP_TRY(c, c->d_gbuffer.ensure((size_t)c->width * c->height * 4, true));
   if (c->dump_surface) HIP_TRY(c, c->d_surface.ensure((size_t)c->width * c->height * kSurfaceFloats, true));
-  // (option "present_fused" with "supersample" >= 2: k_resolve writes the presented image, there is no W x H fp32 frame)
-  if (!c->ext_out && !(c->present_fused && c->supersample > 1)) HIP_TRY(c, s.d_frame.ensure(out_rows * c->width));
+  if (!c->ext_out && m.frame32()) HIP_TRY(c, s.d_frame.ensure(m.out_rows * c->width));
   if (c->dump_vis) {
     HIP_TRY(c, c->d_vis_prim.ensure((size_t)c->width * c->height));
     HIP_TRY(c, c->d_vis_depth.ensure((size_t)c->width * c->height));
@@ -547,11 +613,14 @@ int ensure_timing_ring(bbr_context *c, bool resolve_pairs) {
     c->ring.resize(bbr_context::kRingEvents * bbr_context::kRingCap);
     for (auto &e : c->ring) HIP_TRY(c, hipEventCreate(&e));
   }
-  if (resolve_pairs && c->resolve_ring.empty()) {  // (start, stop) around k_resolve, one pair per ring frame
-    c->resolve_ring.resize(2 * bbr_context::kRingCap);
-    for (auto &e : c->resolve_ring) HIP_TRY(c, hipEventCreate(&e));
-  }
+  if (resolve_pairs) HIP_TRY(c, c->resolve_ring.ensure());  // around k_resolve, one pair per ring frame
   return BBR_OK;
+}
+
+// The event that ends the interval of ring frame `i`: behind the frame's k_resolve if it has one -- the stop event of its resolve
+// pair -- and behind its shading otherwise.  (The ring holds frames of one kind: option "supersample" empties it.)
+hipEvent_t frame_end_event(const bbr_context *c, uint32_t i) {
+  return frame_mode(c).resolve ? c->resolve_ring.stop(i) : c->ring[bbr_context::kRingEvents * (i % bbr_context::kRingCap) + 4];
 }
 
 // An edge between two streams of a frame: `to` goes on behind what `from` holds now.  Nothing to do on one stream.
@@ -656,15 +725,20 @@ int upload_material_table(bbr_context *c) {
   return BBR_OK;
 }
 
-// `ev`: the frame's five timing events, or nullptr
+// `ev`: the frame's five timing events, or nullptr; `final_out`: the W x H fp32 frame (nullptr if the mode has none)
 template <int TW, int TH>
-void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent_t *ev, const FrameParams &fp_in, const Mat4 &pv,
-                  const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DrawDesc *d_draws, uint32_t n_draws,
+void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const FrameStreams &st, hipEvent_t *ev, const FrameParams &fp_in,
+                  const Mat4 &pv, const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DrawDesc *d_draws, uint32_t n_draws,
                   const FirstPrims &first_prims, float4 *final_out, uint32_t *d_item_head) {
   FrameParams fp = fp_in;
-  // option "supersample" >= 2: the kernels below render the fine frame, k_resolve (at the end) writes `final_out`
-  const bool resolve = c->supersample > 1;
+  // Where the kernels up to shading write.  With a resolve they render the fine frame and k_resolve (at the end) writes
+  // `final_out`; with fused presentation k_raster / k_shade write presented pixels into the slot's RGBA8 image, unless there is a
+  // resolve (a fine frame is fp32: a presented byte cannot be averaged, k_resolve presents)
+  const bool resolve = mode.resolve, merged = mode.merged;
   float4 *out = resolve ? s.d_fine.ptr : final_out;
+  uint32_t *out8 = mode.shade_presents() ? s.d_present.ptr : nullptr;
+  const SrgbTables *tables = mode.shade_presents() ? c->d_srgb_tables.ptr : nullptr;
+  float *depth = mode.depth ? s.d_depth.ptr : nullptr;
   // a rank without bands (more ranks than bands) still launches one row: its blocks fall off tiles_y and exit
   const int grid_y = std::max(1, c->world > 1 ? c->local_bands() * fp.band_tiles : fp.tiles_y);
   // A SHORT frame (at most option "no_tail_items" item slots: 1080p has 32 640) has no k_shade_items launch: k_raster's tiles
@@ -674,7 +748,6 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
   const uint32_t max_items = (uint32_t)(fp.tiles_x * grid_y) * (uint32_t)(TW * TH / 64);
   // option "sample_shading" 0 (n >= 2): always the long route -- k_sample_merge thins the lists behind k_raster and does the
   // accounting of the items, which k_raster therefore leaves alone (both of its pointers are guarded)
-  const bool merged = c->merged();
   const bool short_frame = !merged && max_items <= (uint32_t)c->no_tail_items;
   // Heavy tiles first (long frames; k_raster): the heavy rows in front of the launch are sized from the length of the list
   // the slot's previous frame produced (pinned word kFlagHeavyTiles) + 1/8 + 8.  A list that does not fit them is not
@@ -699,10 +772,6 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
   //  switched, "after the previous frame" no longer implies "after the one before")
   for (const FrameSlot &o : c->slots)
     if (&o != &s && o.in_flight && final_out && o.out_used == final_out && o.stream_used != sr) (void)o.follow(sr);
-  // option "present_fused": k_raster / k_shade write presented pixels into the slot's RGBA8 image (a fine frame is fp32: a
-  // presented byte cannot be averaged, k_resolve presents)
-  uint32_t *out8 = (c->present_fused && !resolve) ? s.d_present.ptr : nullptr;
-  const SrgbTables *tables = (c->present_fused && !resolve) ? c->d_srgb_tables.ptr : nullptr;
   if (fp.deferred)
     hipLaunchKernelGGL(k_deferred_background, dim3(1), dim3(kBackgroundThreads), 0, sr, sp, d_lights, s.d_background.ptr, tables, fp.gbuffer_view);
   uint32_t *item_head = short_frame ? d_item_head : nullptr;
@@ -710,19 +779,15 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
                      s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, out, fp, s.d_tris.ptr, s.d_clip.ptr, s.d_bins.ptr,
                      c->dump_vis ? c->d_vis_prim.ptr : nullptr,
                      c->dump_vis ? c->d_vis_depth.ptr : nullptr,
-                     fp.deferred ? s.d_background.ptr : nullptr, (c->overlays && c->world == 1 && !resolve) ? s.d_depth.ptr : nullptr,
-                     s.h_flags, out8, (short_frame || merged) ? nullptr : s.d_item_groups.ptr, item_head, s.d_items.ptr, d_lights, sp.num_lights,
+                     fp.deferred ? s.d_background.ptr : nullptr, depth, s.h_flags, out8, (short_frame || merged) ? nullptr : s.d_item_groups.ptr, item_head, s.d_items.ptr, d_lights, sp.num_lights,
                      s.d_cooked.ptr, s.d_heavy.ptr);
-  s.has_depth = c->overlays && c->world == 1 && !resolve;
-  if (merged) {
-    const dim3 grid((unsigned)fp.tiles_x, (unsigned)grid_y);
-    if (c->supersample == 2)
-      hipLaunchKernelGGL((k_sample_merge<TW, TH, 2>), grid, dim3(kMergeThreads), 0, sr, fp, s.d_frag_count.ptr, s.d_frags.ptr,
-                         reinterpret_cast<SampleMap<2>::Word *>(s.d_sample_map.ptr), s.d_item_groups.ptr);
-    else
-      hipLaunchKernelGGL((k_sample_merge<TW, TH, 4>), grid, dim3(kMergeThreads), 0, sr, fp, s.d_frag_count.ptr, s.d_frags.ptr,
-                         reinterpret_cast<SampleMap<4>::Word *>(s.d_sample_map.ptr), s.d_item_groups.ptr);
-  }
+  if (merged)
+    with_samples(mode.n, [&](auto n) {
+      constexpr int N = decltype(n)::value;
+      if constexpr (N != 3)  // (refused_pair)
+        hipLaunchKernelGGL((k_sample_merge<TW, TH, N>), dim3((unsigned)fp.tiles_x, (unsigned)grid_y), dim3(kMergeThreads), 0, sr, fp, s.d_frag_count.ptr,
+                           s.d_frags.ptr, reinterpret_cast<typename SampleMap<N>::Word *>(s.d_sample_map.ptr), s.d_item_groups.ptr);
+    });
   // k_shade's work list (64 fragments per item), built from the per-tile fragment counts as soon as k_raster is done; the
   // same launch cooks the frame's light table
   if (!short_frame)
@@ -750,93 +815,59 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameStreams &st, hipEvent
   // one stream an empty tail would still cost the frame a kernel boundary (~4 us).
   const bool tail = main_wgs * kShadeWaves < max_items;
   auto shade = [&](auto deferred, auto present) {
-    if (c->mip_levels > 1) {
-      // option "mip_levels": k_shade_mip, launched like k_shade_aniso
+    constexpr bool DEFERRED = decltype(deferred)::value, PRESENT = decltype(present)::value;
+    // The shading kernels' arguments, stated once.  A launch names its kernel, grid and stream, k_shade's `first_item` word (a
+    // tuple: k_shade_aniso and k_shade_mip take none), the item groups, and what its kernel takes behind those.
+    auto launch = [&](auto kernel, uint32_t wgs, hipStream_t stream, auto first_item, uint32_t *item_groups, auto... trailing) {
+      std::apply([&](auto... first) {
+        hipLaunchKernelGGL(kernel, dim3(wgs), dim3(kShadeThreads), 0, stream, s.d_items.ptr, item_count, first..., s.d_frags.ptr,
+                           s.d_frag_count.ptr, s.d_attrs.ptr, s.d_clip.ptr, fp, sp, s.d_cooked.ptr, c->d_materials.ptr, out, gbuf, tables,
+                           out8, ctr, ctr_done, item_groups, trailing...);
+      }, first_item);
+    };
+    uint32_t *groups = short_frame ? nullptr : s.d_item_groups.ptr;
+    if (c->mip_levels > 1 || c->max_anisotropy > 1 || c->dump_surface) {
+      // option "mip_levels": k_shade_mip; option "max_anisotropy" / bbr_read_surface (the kernels' DUMP forms): k_shade_aniso.
+      // Either is one launch whose waves walk the whole item list.
       if (ev) (void)hipEventRecord(ev[3], ss);
-      auto mip_launch = [&](auto dump) {
-        hipLaunchKernelGGL((k_shade_mip<TW, TH, decltype(deferred)::value, decltype(present)::value, decltype(dump)::value>),
-                           dim3(main_wgs), dim3(kShadeThreads), 0, ss, s.d_items.ptr, item_count, s.d_frags.ptr, s.d_frag_count.ptr,
-                           s.d_attrs.ptr, s.d_clip.ptr, fp, sp, s.d_cooked.ptr, c->d_materials.ptr, out, gbuf, tables, out8, ctr,
-                           ctr_done, short_frame ? nullptr : s.d_item_groups.ptr, c->max_anisotropy, c->d_mip_tables.ptr,
-                           decltype(dump)::value ? c->d_surface.ptr : nullptr);
-      };
-      if (c->dump_surface) mip_launch(std::true_type{});
-      else mip_launch(std::false_type{});
+      float *surface = c->dump_surface ? c->d_surface.ptr : nullptr;
+      with_bool(c->mip_levels > 1, [&](auto mip) { with_bool(c->dump_surface, [&](auto dump) {
+        constexpr bool DUMP = decltype(dump)::value;
+        if constexpr (decltype(mip)::value) launch(k_shade_mip<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, c->d_mip_tables.ptr, surface);
+        else launch(k_shade_aniso<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface);
+      }); });
       return;
     }
-    if (c->max_anisotropy > 1 || c->dump_surface) {
-      // option "max_anisotropy" / bbr_read_surface: k_shade_aniso, one launch whose waves walk the whole item list
-      if (ev) (void)hipEventRecord(ev[3], ss);
-      auto aniso_launch = [&](auto dump) {
-        hipLaunchKernelGGL((k_shade_aniso<TW, TH, decltype(deferred)::value, decltype(present)::value, decltype(dump)::value>),
-                           dim3(main_wgs), dim3(kShadeThreads), 0, ss, s.d_items.ptr, item_count, s.d_frags.ptr, s.d_frag_count.ptr,
-                           s.d_attrs.ptr, s.d_clip.ptr, fp, sp, s.d_cooked.ptr, c->d_materials.ptr, out, gbuf, tables, out8, ctr,
-                           ctr_done, short_frame ? nullptr : s.d_item_groups.ptr, c->max_anisotropy,
-                           decltype(dump)::value ? c->d_surface.ptr : nullptr);
-      };
-      if (c->dump_surface) aniso_launch(std::true_type{});
-      else aniso_launch(std::false_type{});
-      return;
-    }
-    if (tail)
-      hipLaunchKernelGGL((k_shade<TW, TH, decltype(deferred)::value, decltype(present)::value, true, true>), dim3(32), dim3(kShadeThreads),
-                         0, sr, s.d_items.ptr, item_count, main_wgs * (uint32_t)kShadeWaves, s.d_frags.ptr, s.d_frag_count.ptr, s.d_attrs.ptr,
-                         s.d_clip.ptr, fp, sp, s.d_cooked.ptr, c->d_materials.ptr, out, gbuf, tables, out8, ctr, ctr_done, nullptr);
+    if (tail) launch(k_shade<TW, TH, DEFERRED, PRESENT, true, true>, 32u, sr, std::make_tuple(main_wgs * (uint32_t)kShadeWaves), nullptr);
     if (ev) (void)hipEventRecord(ev[3], ss);
     // (the main launch without the per-map sampling path when every material is packed: k_shade, MIXED)
-    auto main_launch = [&](auto mixed) {
-      hipLaunchKernelGGL((k_shade<TW, TH, decltype(deferred)::value, decltype(present)::value, false, decltype(mixed)::value>), dim3(main_wgs),
-                         dim3(kShadeThreads), 0, ss, s.d_items.ptr, item_count, 0u, s.d_frags.ptr, s.d_frag_count.ptr, s.d_attrs.ptr,
-                         s.d_clip.ptr, fp, sp, s.d_cooked.ptr, c->d_materials.ptr, out, gbuf, tables, out8, ctr, ctr_done,
-                         short_frame ? nullptr : s.d_item_groups.ptr);
-    };
-    if (c->all_packed) main_launch(std::false_type{});
-    else main_launch(std::true_type{});
+    with_bool(c->all_packed, [&](auto packed) { launch(k_shade<TW, TH, DEFERRED, PRESENT, false, !decltype(packed)::value>, main_wgs, ss, std::make_tuple(0u), groups); });
     if (tail) stream_edge(sr, ss, s.ev_tail_done);  // (nothing else went onto sr since the tail launch)
   };
-  if (fp.deferred) {
-    if (out8) shade(std::true_type{}, std::true_type{});
-    else shade(std::true_type{}, std::false_type{});
-  } else {
-    if (out8) shade(std::false_type{}, std::true_type{});
-    else shade(std::false_type{}, std::false_type{});
-  }
+  with_bool(fp.deferred, [&](auto deferred) { with_bool(out8 != nullptr, [&](auto present) { shade(deferred, present); }); });
   if (resolve) {
     // k_resolve, right behind k_shade (and the tail launch, whose edge `ss` already follows) on the frame's own stream.  The
     // shading interval ends in front of it, the frame's interval behind it (the stop event of its own pair).
     if (ev) (void)hipEventRecord(ev[4], ss);
-    hipEvent_t *re = ev ? &c->resolve_ring[2 * (c->ring_frames % bbr_context::kRingCap)] : nullptr;
-    if (re) (void)hipEventRecord(re[0], ss);
+    if (ev) (void)c->resolve_ring.begin(ss);
     const int32_t rows = c->world > 1 ? c->shard_rows() : c->height;
     const dim3 grid((unsigned)((c->width + kResolveThreads - 1) / kResolveThreads), (unsigned)rows);
-    auto launch_merged = [&](auto n) {
+    // One launch over (merged, n, present).  It writes `final_out` or, presenting, the slot's RGBA8 image (`final_out` is nullptr
+    // then; only the PRESENT forms read the tables, tone mapping and exposure); k_resolve_merged reads the sample map besides.
+    uint32_t *present_to = mode.resolve_presents() ? s.d_present.ptr : nullptr;
+    const SrgbTables *present_tables = present_to ? c->d_srgb_tables.ptr : nullptr;
+    with_bool(merged, [&](auto merged_c) { with_samples(mode.n, [&](auto n) { with_bool(present_to != nullptr, [&](auto present) {
       constexpr int N = decltype(n)::value;
-      const auto *map = reinterpret_cast<const typename SampleMap<N>::Word *>(s.d_sample_map.ptr);
-      if (c->present_fused)
-        hipLaunchKernelGGL((k_resolve_merged<N, true>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out, map, (float4 *)nullptr,
-                           s.d_present.ptr, c->width, c->d_srgb_tables.ptr, sp.tone_enable, sp.exposure);
-      else
-        hipLaunchKernelGGL((k_resolve_merged<N, false>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out, map, final_out,
-                           (uint32_t *)nullptr, c->width, (const SrgbTables *)nullptr, 0, 0.f);
-    };
-    auto launch = [&](auto n) {
-      constexpr int N = decltype(n)::value;
-      if (c->present_fused)
-        hipLaunchKernelGGL((k_resolve<N, true>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out, (float4 *)nullptr, s.d_present.ptr,
-                           c->width, c->d_srgb_tables.ptr, sp.tone_enable, sp.exposure);
-      else
-        hipLaunchKernelGGL((k_resolve<N, false>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out, final_out, (uint32_t *)nullptr,
-                           c->width, (const SrgbTables *)nullptr, 0, 0.f);
-    };
-    if (merged && c->supersample == 2) launch_merged(std::integral_constant<int, 2>{});
-    else if (merged) launch_merged(std::integral_constant<int, 4>{});
-    else if (c->supersample == 2) launch(std::integral_constant<int, 2>{});
-    else if (c->supersample == 3) launch(std::integral_constant<int, 3>{});
-    else launch(std::integral_constant<int, 4>{});
-    if (re) {
-      (void)hipEventRecord(re[1], ss);
-      ++c->resolve_launches;
-    }
+      constexpr bool PRESENT = decltype(present)::value;
+      if constexpr (!decltype(merged_c)::value)
+        hipLaunchKernelGGL((k_resolve<N, PRESENT>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out, final_out, present_to, c->width,
+                           present_tables, sp.tone_enable, sp.exposure);
+      else if constexpr (N != 3)  // (refused_pair)
+        hipLaunchKernelGGL((k_resolve_merged<N, PRESENT>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out,
+                           reinterpret_cast<const typename SampleMap<N>::Word *>(s.d_sample_map.ptr), final_out, present_to, c->width,
+                           present_tables, sp.tone_enable, sp.exposure);
+    }); }); });
+    if (ev) (void)c->resolve_ring.end(ss);
   }
   (void)s.busy_until(ss);
   s.stream_used = ss;
@@ -924,7 +955,8 @@ int submit_frame_into(bbr_context *c, int slot_index) {
     rc = apply_growth(c, overflow, bin_need, broad_need, clip_need);
     if (rc) return rc;
   }
-  rc = ensure_slot_buffers(c, s);
+  const FrameMode mode = frame_mode(c);  // decided once for the frame: the buffers, the launches, what the slot remembers
+  rc = ensure_slot_buffers(c, s, mode);
   if (rc) return rc;
 
   // staging layout: [lights (100 * 64 B)] [draw descriptors] [instances]
@@ -958,7 +990,7 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   c->pending_waits.clear();
   hipEvent_t *ev = nullptr;  // this frame's timing events, if it carries any
   if (c->timing && (c->timing_tick++ % (uint64_t)c->timing_stride) == 0) {
-    rc = ensure_timing_ring(c, c->supersample > 1);
+    rc = ensure_timing_ring(c, mode.resolve);
     if (rc) return rc;
     ev = &c->ring[bbr_context::kRingEvents * (c->ring_frames % bbr_context::kRingCap)];
     if (c->timing == 1) HIP_TRY(c, hipEventRecord(ev[0], st.geom));
@@ -976,17 +1008,16 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   sp.tone_enable = c->frame_u.enable_tone_mapping;
   sp.exposure = c->frame_u.exposure;
   sp.num_lights = n_lights;
-  float4 *out = c->ext_out ? reinterpret_cast<float4 *>(c->ext_out) : s.d_frame.ptr;
-  if (c->present_fused && c->supersample > 1) out = nullptr;  // k_resolve writes the presented image: no W x H fp32 frame
+  float4 *out = !mode.frame32() ? nullptr : (c->ext_out ? reinterpret_cast<float4 *>(c->ext_out) : s.d_frame.ptr);
 
   HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, s.h_staging, total, hipMemcpyHostToDevice, st.geom));
-  if (c->tile_mode == 0) launch_frame<64, 64>(c, s, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head);
-  else launch_frame<32, 32>(c, s, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head);
+  if (c->tile_mode == 0) launch_frame<64, 64>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head);
+  else launch_frame<32, 32>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head);
   HIP_TRY(c, hipGetLastError());
   s.in_flight = true;
-  s.fused = c->present_fused;
-  s.present.active = c->present_fused;  // fused presentation: the frame IS the presented image
-  s.present.out = c->present_fused ? s.d_present.ptr : nullptr;
+  s.mode = mode;
+  s.present.active = mode.fused;  // fused presentation: the frame IS the presented image
+  s.present.out = mode.fused ? s.d_present.ptr : nullptr;
   s.present.enable = c->frame_u.enable_tone_mapping;
   s.present.exposure = c->frame_u.exposure;
   s.present.hdr16 = 1;
@@ -994,8 +1025,6 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   s.frame_u = c->frame_u;
   s.view_u = c->view_u;
   s.out_used = out;
-  s.fine_used = c->supersample > 1 ? s.d_fine.ptr : nullptr;
-  s.map_used = c->merged() ? s.d_sample_map.ptr : nullptr;
   s.n_prims = c->n_prims;
   c->last_slot = slot_index;
   return BBR_OK;
@@ -1041,24 +1070,16 @@ int queue_present(bbr_context *c, FrameSlot &s) {
   const size_t n = c->shard_pixels();
   const hipStream_t ps = c->slot_present_stream(s);
   if (ps != s.stream_used) HIP_TRY(c, s.follow(ps));  // behind the frame's k_shade
-  hipEvent_t *pe = nullptr;
   if (c->timing) {
-    if (c->present_ring.empty()) {
-      c->present_ring.resize(2 * bbr_context::kRingCap);
-      for (auto &e : c->present_ring) HIP_TRY(c, hipEventCreate(&e));
-    }
-    pe = &c->present_ring[2 * (c->present_launches % bbr_context::kRingCap)];
-    HIP_TRY(c, hipEventRecord(pe[0], ps));
+    HIP_TRY(c, c->present_ring.ensure());
+    HIP_TRY(c, c->present_ring.begin(ps));
   }
   const size_t per_block = (size_t)kPresentThreads * kPresentPerThread;
   hipLaunchKernelGGL(k_present, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(kPresentThreads), 0,
                      ps, s.out_used, s.present.out, n, c->d_srgb_tables.ptr, s.present.enable,
                      s.present.exposure, s.present.hdr16);
   HIP_TRY(c, hipGetLastError());
-  if (pe) {
-    HIP_TRY(c, hipEventRecord(pe[1], ps));
-    ++c->present_launches;
-  }
+  if (c->timing) HIP_TRY(c, c->present_ring.end(ps));
   HIP_TRY(c, s.busy_until(ps));  // ... until the presented image exists
   return BBR_OK;
 }
@@ -1091,11 +1112,11 @@ int resubmit_last_frame(bbr_context *c) {
   const auto present = s.present;
   int rc = submit_frame_into(c, c->last_slot);
   if (rc) return rc;
-  if (present.active && !s.fused) {
+  if (present.active && !s.mode.fused) {
     s.present = present;
     rc = queue_present(c, s);
     if (rc) return rc;
-  } else if (s.fused && present.copy_to) {  // fused: the re-rendered frame is the image; redo the caller's copy
+  } else if (s.mode.fused && present.copy_to) {  // fused: the re-rendered frame is the image; redo the caller's copy
     s.present.copy_to = present.copy_to;
     return copy_presented(c, s, present.copy_to);
   }
@@ -1315,11 +1336,11 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
   BBR_ON_DEVICE(c);
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "draw_overlays: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_overlays: not available with a partition");
-  if (c->supersample > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_overlays: not available with option supersample >= 2 (no depth resolve rule)");
+  if (int rc = refuse_supersampled(c, "draw_overlays", "no depth resolve rule")) return rc;
   int rc = sync_and_fix(c, nullptr);  // the overlay pass is synchronous: it is a debugging aid, not part of the hot path
   if (rc) return rc;
   FrameSlot &fs = c->slots[c->last_slot];
-  if (!fs.has_depth) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_overlays: the frame was rendered without option \"overlays\"");
+  if (!fs.mode.depth) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_overlays: the frame was rendered without option \"overlays\"");
   if (!fs.present.active) return fail(c, BBR_ERR_NOT_IN_FRAME, "draw_overlays: call bbr_present first (overlays go into the presented image)");
   if (c->tbn) {  // the TBN lines first, then the markers and the gizmo over them (src/main.cpp:132-136)
     rc = draw_tbn(c, fs);
@@ -1593,7 +1614,7 @@ extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
                      ui.d_boxes.ptr, n_tris, tx0, ty0, c->width, c->height, c->d_ui_dec.ptr, c->d_srgb_tables.ptr,
                      s.present.out);
   HIP_TRY(c, hipGetLastError());
-  if (s.fused && s.present.copy_to) {
+  if (s.mode.fused && s.present.copy_to) {
     // fused presentation into a caller's buffer: bbr_present copied the slot's image there before the GUI was in it, so the
     // rows the pass may have touched (those of the union box, whole and contiguous) are copied again behind it
     const size_t first = (size_t)box[1] * c->width, count = (size_t)(box[3] - box[1]) * c->width;
@@ -1653,10 +1674,8 @@ static void release_context(bbr_context *c) {
   c->tbn_pass.release();
   for (auto &e : c->ring)
     if (e) (void)hipEventDestroy(e);
-  for (auto &e : c->present_ring)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : c->resolve_ring)
-    if (e) (void)hipEventDestroy(e);
+  c->present_ring.destroy();
+  c->resolve_ring.destroy();
   c->d_srgb_tables.release();
   if (c->s_geom) (void)hipStreamDestroy(c->s_geom);
   if (c->s_raster) (void)hipStreamDestroy(c->s_raster);
@@ -1668,7 +1687,7 @@ static void release_context(bbr_context *c) {
 int bbr_create(int32_t width, int32_t height, int32_t device, bbr_context **out_ctx) {
   if (!out_ctx) return fail(nullptr, BBR_ERR_INVALID_ARGUMENT, "out_ctx is NULL");
   *out_ctx = nullptr;
-  if (width <= 0 || height <= 0 || width > 32768 || height > 32768)
+  if (width <= 0 || height <= 0 || width > kMaxExtent || height > kMaxExtent)
     return fail(nullptr, BBR_ERR_INVALID_ARGUMENT, "width/height out of range");
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
@@ -1956,7 +1975,7 @@ int bbr_read_framebuffer(bbr_context *c, float *host) {
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_framebuffer: NULL");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_framebuffer on a partitioned context: use bbr_read_shard");
   if (!c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_framebuffer: nothing rendered");
-  if (c->last_slot >= 0 && c->slots[c->last_slot].fused)
+  if (c->last_slot >= 0 && c->slots[c->last_slot].mode.fused)
     return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_framebuffer: the frame was rendered with option present_fused (no fp32 frame); use bbr_read_presented");
   int rc = sync_and_fix(c, nullptr);
   if (rc) return rc;
@@ -1969,7 +1988,7 @@ int bbr_read_shard(bbr_context *c, float *host) {
   BBR_ON_DEVICE(c);
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shard: NULL");
   if (!c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_shard: nothing rendered");
-  if (c->last_slot >= 0 && c->slots[c->last_slot].fused)
+  if (c->last_slot >= 0 && c->slots[c->last_slot].mode.fused)
     return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shard: the frame was rendered with option present_fused (no fp32 frame); use bbr_read_presented");
   int rc = sync_and_fix(c, nullptr);
   if (rc) return rc;
@@ -1980,17 +1999,17 @@ int bbr_read_shard(bbr_context *c, float *host) {
 // rep(s) of every fine pixel of the last frame, row-major, as an index 0 .. n^2 - 1 of its block (the identity without a
 // map).  The frame has completed; whole-frame contexts only.
 static int read_sample_map_synced(bbr_context *c, uint8_t *host) {
-  const int n = c->supersample;
+  const FrameSlot &s = c->slots[c->last_slot];
+  const int n = s.mode.n;
   const size_t fw = (size_t)c->render_width(), fh = (size_t)c->render_height();
-  const void *map = c->slots[c->last_slot].map_used;
-  if (!map) {
+  if (!s.mode.merged) {
     for (size_t y = 0; y < fh; ++y)
       for (size_t x = 0; x < fw; ++x) host[y * fw + x] = (uint8_t)((y % n) * n + (x % n));
     return BBR_OK;
   }
   const size_t pixels = (size_t)c->width * c->height;
-  std::vector<unsigned long long> words((c->sample_map_bytes() + 7) / 8);
-  HIP_TRY(c, hipMemcpy(words.data(), map, pixels * (n == 2 ? 2 : 8), hipMemcpyDeviceToHost));
+  std::vector<unsigned long long> words(s.mode.map_words);
+  HIP_TRY(c, hipMemcpy(words.data(), s.d_sample_map.ptr, pixels * sample_map_word_bytes(n), hipMemcpyDeviceToHost));
   const uint16_t *w2 = reinterpret_cast<const uint16_t *>(words.data());
   for (size_t y = 0; y < fh; ++y)
     for (size_t x = 0; x < fw; ++x) {
@@ -2007,17 +2026,18 @@ int bbr_read_samples(bbr_context *c, float *host) {
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_samples: NULL");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_samples: not available on a partitioned context");
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_samples: nothing rendered");
-  if (c->supersample == 1) return bbr_read_framebuffer(c, host);  // one sample per pixel: the frame itself
+  const FrameSlot &s = c->slots[c->last_slot];
+  if (!s.mode.resolve) return bbr_read_framebuffer(c, host);  // one sample per pixel: the frame itself
   int rc = sync_and_fix(c, nullptr);
   if (rc) return rc;
-  HIP_TRY(c, hipMemcpy(host, c->slots[c->last_slot].fine_used, (size_t)c->render_width() * c->render_height() * 16, hipMemcpyDeviceToHost));
-  if (c->slots[c->last_slot].map_used) {
+  HIP_TRY(c, hipMemcpy(host, s.d_fine.ptr, (size_t)c->render_width() * c->render_height() * 16, hipMemcpyDeviceToHost));
+  if (s.mode.merged) {
     // option "sample_shading" 0: g, every sample the value of its representative (a diagnostic: replicated here, on the host;
     // the fine frame holds nothing defined at a sample that is not one).  A representative precedes what it stands for.
     std::vector<uint8_t> rep((size_t)c->render_width() * c->render_height());
     rc = read_sample_map_synced(c, rep.data());
     if (rc) return rc;
-    const int n = c->supersample;
+    const int n = s.mode.n;
     const size_t fw = (size_t)c->render_width();
     for (size_t y = 0; y < (size_t)c->render_height(); ++y)
       for (size_t x = 0; x < fw; ++x) {
@@ -2130,14 +2150,11 @@ static void drop_extent_buffers(bbr_context *c) {
   auto drop = [](FrameSlot &s) {
     s.release_tile_buffers();
     s.d_frame.release(); s.d_fine.release(); s.d_sample_map.release(); s.d_present.release(); s.d_depth.release();
-    s.has_depth = false;
-    s.fused = false;
+    s.mode = FrameMode{};
     s.present.active = false;
     s.present.out = nullptr;
     s.present.copy_to = nullptr;
     s.out_used = nullptr;
-    s.fine_used = nullptr;
-    s.map_used = nullptr;
     s.in_flight = false;
     s.forget_extent();
   };
@@ -2147,10 +2164,7 @@ static void drop_extent_buffers(bbr_context *c) {
   c->d_vis_prim.release();
   c->d_vis_depth.release();
   c->d_gbuffer.release();
-  c->exchange_slot = -1;  // (the whole frame of the last exchange had the old extent)
-  c->exchange_whole = nullptr;
-  c->have_frame = false;
-  c->last_slot = -1;
+  forget_current_frame(c);  // (the whole frame of the last exchange had the old extent, too)
 }
 
 // onWindowResize (src/main.cpp:1042-1061): wait for the device, drop everything whose size follows the swap-chain
@@ -2158,10 +2172,9 @@ static void drop_extent_buffers(bbr_context *c) {
 int bbr_resize(bbr_context *c, int32_t width, int32_t height) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
-  if (width <= 0 || height <= 0 || width > 32768 || height > 32768)
+  if (width <= 0 || height <= 0 || width > kMaxExtent || height > kMaxExtent)
     return fail(c, BBR_ERR_INVALID_ARGUMENT, "resize: width/height out of range");
-  if ((int64_t)width * c->supersample > 32768 || (int64_t)height * c->supersample > 32768)
-    return fail(c, BBR_ERR_INVALID_ARGUMENT, "resize: supersample x width/height exceeds 32768");
+  if (int rc = check_render_extent(c, "resize", c->supersample, width, height)) return rc;
   if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "resize: between begin_frame and end_frame");
   int rc = drain(c);
   if (rc) return rc;
@@ -2233,7 +2246,7 @@ int bbr_get_stats(bbr_context *c, bbr_stats *out) {
 int bbr_read_visibility(bbr_context *c, uint32_t *prim_host, float *depth_host) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
-  if (c->supersample > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_visibility: not available with option supersample >= 2 (its buffers have the output extent)");
+  if (int rc = refuse_supersampled(c, "read_visibility")) return rc;
   if (!c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_visibility: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_visibility: not available on a partitioned context");
   int rc = rerender_with(c, &bbr_context::dump_vis);
@@ -2248,7 +2261,7 @@ int bbr_read_gbuffer(bbr_context *c, float *host) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_gbuffer: NULL");
-  if (c->supersample > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_gbuffer: not available with option supersample >= 2 (its buffers have the output extent)");
+  if (int rc = refuse_supersampled(c, "read_gbuffer")) return rc;
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_gbuffer: nothing rendered");
   if (!c->deferred) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_gbuffer: option render_pass is not 1 (deferred)");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_gbuffer: not available with a partition");
@@ -2266,7 +2279,7 @@ int bbr_read_surface(bbr_context *c, float *host) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface: NULL");
-  if (c->supersample > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface: not available with option supersample >= 2 (its buffers have the output extent)");
+  if (int rc = refuse_supersampled(c, "read_surface")) return rc;
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_surface: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface: not available on a partitioned context");
   int rc = rerender_with(c, &bbr_context::dump_surface);  // (the dumping instantiation of k_shade_aniso)
@@ -2333,7 +2346,7 @@ int bbr_read_records(bbr_context *c, void *records, void *triangles, uint32_t ca
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!out_count) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_records: NULL count");
-  if (c->supersample > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_records: not available with option supersample >= 2 (its buffers have the output extent)");
+  if (int rc = refuse_supersampled(c, "read_records")) return rc;
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_records: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_records: not available on a partitioned context");
   int rc = sync_and_fix(c, nullptr);
@@ -2370,9 +2383,7 @@ int bbr_last_frame_time_ms(bbr_context *c, float *out_frame_ms, float *out_shade
   if (rc) return rc;
   const hipEvent_t *e = &c->ring[bbr_context::kRingEvents * ((c->ring_frames - 1) % bbr_context::kRingCap)];
   float a = 0.f, b = 0.f;
-  // (option "supersample" >= 2: the frame ends behind its k_resolve, the stop event of the frame's resolve pair)
-  const hipEvent_t frame_end = c->supersample > 1 ? c->resolve_ring[2 * ((c->ring_frames - 1) % bbr_context::kRingCap) + 1] : e[4];
-  if (c->timing == 1) HIP_TRY(c, hipEventElapsedTime(&a, e[0], frame_end));
+  if (c->timing == 1) HIP_TRY(c, hipEventElapsedTime(&a, e[0], frame_end_event(c, c->ring_frames - 1)));
   HIP_TRY(c, hipEventElapsedTime(&b, e[3], e[4]));
   if (out_frame_ms) *out_frame_ms = a;
   if (out_shade_ms) *out_shade_ms = b;
@@ -2406,9 +2417,11 @@ int bbr_timing_reset(bbr_context *c) {
   BBR_ON_DEVICE(c);
   int rc = drain(c);
   if (rc) return rc;
+  // (the three places that reset timing state reset different sets, and stay apart: this one the ring, present and resolve;
+  //  option "timing" those and the stride's tick; option "supersample" the ring, resolve and the tick, not present)
   c->ring_frames = 0;
-  c->present_launches = 0;
-  c->resolve_launches = 0;
+  c->present_ring.reset();
+  c->resolve_ring.reset();
   return BBR_OK;
 }
 
@@ -2425,7 +2438,7 @@ int bbr_timing_summary(bbr_context *c, uint32_t *out_frames, float *out_avg_fram
     const hipEvent_t *e = &c->ring[bbr_context::kRingEvents * i];
     float a = 0.f, b = 0.f, d = 0.f, h = 0.f;
     if (c->timing == 1) {
-      HIP_TRY(c, hipEventElapsedTime(&a, e[0], c->supersample > 1 ? c->resolve_ring[2 * i + 1] : e[4]));
+      HIP_TRY(c, hipEventElapsedTime(&a, e[0], frame_end_event(c, i)));
       HIP_TRY(c, hipEventElapsedTime(&b, e[0], e[1]));
       HIP_TRY(c, hipEventElapsedTime(&d, e[1], e[2]));
     }
@@ -2440,17 +2453,19 @@ int bbr_timing_summary(bbr_context *c, uint32_t *out_frames, float *out_avg_fram
   return BBR_OK;
 }
 
-int bbr_present_timing(bbr_context *c, uint32_t *out_launches, float *out_avg_ms) {
+// bbr_present_timing / bbr_resolve_timing: launches and average milliseconds of one ring of pairs
+static int pair_ring_timing(bbr_context *c, PairRing bbr_context::*which, const char *who, uint32_t *out_launches, float *out_avg_ms) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
-  if (!c->timing) return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_timing: enable option \"timing\" first");
+  if (!c->timing) return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": enable option \"timing\" first");
   int rc = drain(c);
   if (rc) return rc;
-  uint32_t n = std::min(c->present_launches, bbr_context::kRingCap);
+  const PairRing &ring = c->*which;
+  uint32_t n = std::min(ring.launches, kRingCap);
   double t = 0;
   for (uint32_t i = 0; i < n; ++i) {
     float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->present_ring[2 * i], c->present_ring[2 * i + 1]));
+    HIP_TRY(c, hipEventElapsedTime(&ms, ring.start(i), ring.stop(i)));
     t += ms;
   }
   if (out_launches) *out_launches = n;
@@ -2458,22 +2473,12 @@ int bbr_present_timing(bbr_context *c, uint32_t *out_launches, float *out_avg_ms
   return BBR_OK;
 }
 
+int bbr_present_timing(bbr_context *c, uint32_t *out_launches, float *out_avg_ms) {
+  return pair_ring_timing(c, &bbr_context::present_ring, "present_timing", out_launches, out_avg_ms);
+}
+
 int bbr_resolve_timing(bbr_context *c, uint32_t *out_launches, float *out_avg_ms) {
-  if (!c) return BBR_ERR_INVALID_ARGUMENT;
-  BBR_ON_DEVICE(c);
-  if (!c->timing) return fail(c, BBR_ERR_INVALID_ARGUMENT, "resolve_timing: enable option \"timing\" first");
-  int rc = drain(c);
-  if (rc) return rc;
-  uint32_t n = std::min(c->resolve_launches, bbr_context::kRingCap);
-  double t = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->resolve_ring[2 * i], c->resolve_ring[2 * i + 1]));
-    t += ms;
-  }
-  if (out_launches) *out_launches = n;
-  if (out_avg_ms) *out_avg_ms = n ? (float)(t / n) : 0.f;
-  return BBR_OK;
+  return pair_ring_timing(c, &bbr_context::resolve_ring, "resolve_timing", out_launches, out_avg_ms);
 }
 
 int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
@@ -2496,10 +2501,10 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   if (n == "timing") {
     if (value < 0 || value > 2) return fail(c, BBR_ERR_INVALID_ARGUMENT, "timing: 0, 1 or 2");
     c->timing = (int)value;
-    if (value && (rc = ensure_timing_ring(c, c->supersample > 1)) != BBR_OK) return rc;
-    c->ring_frames = 0;
-    c->present_launches = 0;
-    c->resolve_launches = 0;
+    if (value && (rc = ensure_timing_ring(c, frame_mode(c).resolve)) != BBR_OK) return rc;
+    c->ring_frames = 0;  // (see bbr_timing_reset on what each of the three reset sites resets)
+    c->present_ring.reset();
+    c->resolve_ring.reset();
     c->timing_tick = 0;
   } else if (n == "timing_stride") {
     if (value < 1 || value > 1024) return fail(c, BBR_ERR_INVALID_ARGUMENT, "timing_stride: 1 .. 1024");
@@ -2547,10 +2552,9 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   } else if (n == "supersample") {
     // like a resize of the render extent; the output extent, and with it a caller's output buffer, stay
     if (value < 1 || value > 4) return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: 1 (off) .. 4");
-    if (value * c->width > 32768 || value * c->height > 32768)
-      return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: supersample x width/height exceeds 32768");
+    if ((rc = check_render_extent(c, "supersample", value, c->width, c->height)) != BBR_OK) return rc;
     if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: between begin_frame and end_frame");
-    if (value == 3 && c->sample_shading == 0)
+    if (refused_pair(value, c->sample_shading))
       return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: 3 is not available with option sample_shading 0 (a 3 x 3 block straddles the tiles)");
     if ((int)value != c->supersample) {
       // (the one step that can fail comes first: a refused call leaves the context as it was)
@@ -2558,25 +2562,19 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
       c->supersample = (int)value;
       drop_extent_buffers(c);
       c->ring_frames = 0;  // (a frame's interval ends behind its k_resolve: the ring holds frames of one kind)
-      c->resolve_launches = 0;
+      c->resolve_ring.reset();
       c->timing_tick = 0;
     }
   } else if (n == "sample_shading") {
     // no extent changes: only the sample maps go, and there is no current frame (its samples were of the other kind)
     if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "sample_shading: 1 (every sample) or 0 (one fragment per primitive and pixel)");
     if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "sample_shading: between begin_frame and end_frame");
-    if (value == 0 && c->supersample == 3)
+    if (refused_pair(c->supersample, value))
       return fail(c, BBR_ERR_INVALID_ARGUMENT, "sample_shading: 0 is not available with option supersample 3 (a 3 x 3 block straddles the tiles)");
     if ((int)value != c->sample_shading) {
       c->sample_shading = (int)value;
-      for (FrameSlot &s : c->slots) {
-        s.d_sample_map.release();
-        s.map_used = nullptr;
-      }
-      c->exchange_slot = -1;
-      c->exchange_whole = nullptr;
-      c->have_frame = false;
-      c->last_slot = -1;
+      for (FrameSlot &s : c->slots) s.d_sample_map.release();
+      forget_current_frame(c);
     }
   } else if (n == "present_fused") {
     c->present_fused = value != 0;
@@ -2806,7 +2804,7 @@ int check_exchange(bbr_context *c, int form, const char *who) {
     return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": BBR_SHARD_PACKED is not lossless with option supersample >= 2");
   if (kWireForms[form].presented) {
     if (!s.present.active || !s.present.out) return fail(c, BBR_ERR_NOT_IN_FRAME, std::string(who) + ": BBR_SHARD_RGBA8 needs bbr_present first");
-  } else if (s.fused) {
+  } else if (s.mode.fused) {
     return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": no fp32 frame with option present_fused (use BBR_SHARD_RGBA8)");
   }
   return BBR_OK;
@@ -3224,7 +3222,7 @@ int bbr_tone_map(bbr_context *c, int32_t enable, float exposure) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "tone_map: nothing rendered");
-  if (c->slots[c->last_slot].fused) return fail(c, BBR_ERR_INVALID_ARGUMENT, "tone_map: no fp32 frame with option present_fused");
+  if (c->slots[c->last_slot].mode.fused) return fail(c, BBR_ERR_INVALID_ARGUMENT, "tone_map: no fp32 frame with option present_fused");
   float4 *frame = c->slots[c->last_slot].out_used;
   size_t n = c->shard_pixels();
   // same stream as the frame's shade kernel: ordered after it
