@@ -88,6 +88,8 @@ SIGNATURES = {
     "bbr_tile_height": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "bbr_get_stats": (C.c_int, [_P, C.POINTER(BbrStats)]),
     "bbr_read_visibility": (C.c_int, [_P, _P, _P]),
+    "bbr_read_sample_visibility": (C.c_int, [_P, _P, _P]),
+    "bbr_read_depth": (C.c_int, [_P, _P]),
     "bbr_last_frame_time_ms": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "bbr_timing_reset": (C.c_int, [_P]),
     "bbr_timing_summary": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),

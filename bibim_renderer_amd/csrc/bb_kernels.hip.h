@@ -16,6 +16,7 @@
 //   k_resolve    option "supersample": the n x n samples of the fine frame averaged into the output pixel, in a pinned order
 //   k_sample_merge, k_resolve_merged    option "sample_shading" 0: the fragment lists thinned to one fragment per primitive and
 //                output pixel behind k_raster, and the resolve that knows which sample stands for which
+//   k_resolve_depth    option "depth_resolve": the depth (and winner) of one sample of the block for the output pixel
 //
 // Arithmetic contract: every floating-point expression below has the same operand order and the same
 // explicit fmaf() placement as the CPU oracle; the file is compiled with -ffp-contract=off, IEEE
@@ -3370,6 +3371,89 @@ __global__ __launch_bounds__(kResolveThreads) void k_resolve_merged(const float4
     store_pixel(&out[o], resolve_merged_pixel<N>(fine, map[o], width, x, y));
   }
 }
+
+// ------------------------------------------------------------------------------------------------
+// depth resolve (option "depth_resolve" with "supersample" n = 2..4): one depth, and on the dump path one winner, per output
+// pixel, taken from ONE sample k* of the pixel's block (k = j * n + i, the colour resolve's block and index):
+//   kDepthZero  k* = 0
+//   kDepthMin   k* = the first k, in index order, whose depth bit pattern (an unsigned 32-bit integer) is smallest
+//   kDepthMax   k* = the first k, in index order, whose depth bit pattern is largest
+// Stored depths lie in [0, 1] and an uncovered sample holds the cleared 0.0, so the order of the bit patterns is the order
+// of the values, and it is the comparison k_raster's keys make (reverse-Z: MAX is the nearest sample).  The fine depth (and,
+// PRIM, the fine winners: 0xFFFFFFFF where a sample is uncovered) is what k_raster stored through depth_io (vis_depth,
+// vis_prim) at the render extent; nothing here interprets a depth as a number.
+// A streaming kernel shaped like k_resolve: one lane per output pixel, blockIdx.y the output row, size_t addresses, the n
+// contiguous depths of a fine row in one load where the address allows it (8 bytes at n = 2, 16 at n = 4; at n = 3 a row
+// starts at a multiple of 12 bytes, so three 4-byte loads), the rows below the first a rolled loop.  kDepthZero loads
+// sample 0 alone.  4 n^2 B read + 4 B written per output pixel (PRIM: + 4 B read at k* and 4 B written); no LDS, no scratch.
+// ------------------------------------------------------------------------------------------------
+enum : int { kDepthZero = 1, kDepthMin = 4, kDepthMax = 8 };  // VkResolveModeFlagBits
+typedef uint32_t depth_u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t depth_u32x4 __attribute__((ext_vector_type(4)));
+template <int N>
+BB_DEV void depth_row_load(const uint32_t *__restrict__ row, uint32_t (&v)[N]) {
+  static_assert(N >= 2 && N <= 4, "supersample: n = 2 .. 4 are resolved");
+  if constexpr (N == 2) {
+    const depth_u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const depth_u32x2 *>(row));
+    v[0] = w.x; v[1] = w.y;
+  } else if constexpr (N == 4) {
+    const depth_u32x4 w = __builtin_nontemporal_load(reinterpret_cast<const depth_u32x4 *>(row));
+    v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = __builtin_nontemporal_load(row + i);
+  }
+}
+// one fine row of the block against the best so far; `k` is the index of the row's first sample (strict: the first k stays)
+template <int N, int MODE>
+BB_DEV void depth_row_select(const uint32_t *__restrict__ row, uint32_t k, bool first, uint32_t &best, uint32_t &best_k) {
+  uint32_t v[N];
+  depth_row_load<N>(row, v);
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const bool better = (first && i == 0) || (MODE == kDepthMin ? v[i] < best : v[i] > best);
+    best = better ? v[i] : best;
+    best_k = better ? k + (uint32_t)i : best_k;
+  }
+}
+template <int N, int MODE, bool PRIM>
+__global__ __launch_bounds__(kResolveThreads) void k_resolve_depth(const uint32_t *__restrict__ fine_depth,
+                                                                    const uint32_t *__restrict__ fine_prim,
+                                                                    uint32_t *__restrict__ out_depth, uint32_t *__restrict__ out_prim,
+                                                                    int32_t width) {
+  static_assert(MODE == kDepthZero || MODE == kDepthMin || MODE == kDepthMax, "depth_resolve: SAMPLE_ZERO, MIN or MAX");
+  const int32_t x = (int32_t)(blockIdx.x * kResolveThreads + threadIdx.x);
+  if (x >= width) return;
+  const size_t y = blockIdx.y, o = y * (size_t)width + (size_t)x;
+  const size_t fine_pitch = (size_t)width * N, block = (y * N) * fine_pitch + (size_t)x * N;
+  uint32_t best, best_k = 0u;
+  if constexpr (MODE == kDepthZero) {
+    best = __builtin_nontemporal_load(fine_depth + block);
+  } else {
+    const uint32_t *row = fine_depth + block;
+    best = 0u;
+    depth_row_select<N, MODE>(row, 0u, true, best, best_k);
+#pragma unroll 1
+    for (int j = 1; j < N; ++j) {
+      row += fine_pitch;
+      depth_row_select<N, MODE>(row, (uint32_t)(j * N), false, best, best_k);
+    }
+  }
+  store_pixel(&out_depth[o], best);
+  if constexpr (PRIM)
+    store_pixel(&out_prim[o], __builtin_nontemporal_load(fine_prim + block + (size_t)(best_k / N) * fine_pitch + (size_t)(best_k % N)));
+}
+// Instantiated HERE, behind every kernel above, for the reason given at k_sample_merge: the kernels of the default path keep
+// their places against each other in the code object.
+#define BB_RESOLVE_DEPTH(N, MODE)                                                                                                      \
+  template __global__ void k_resolve_depth<N, MODE, false>(const uint32_t *__restrict__, const uint32_t *__restrict__, uint32_t *__restrict__, \
+                                                           uint32_t *__restrict__, int32_t);                                          \
+  template __global__ void k_resolve_depth<N, MODE, true>(const uint32_t *__restrict__, const uint32_t *__restrict__, uint32_t *__restrict__,  \
+                                                          uint32_t *__restrict__, int32_t);
+BB_RESOLVE_DEPTH(2, kDepthZero) BB_RESOLVE_DEPTH(2, kDepthMin) BB_RESOLVE_DEPTH(2, kDepthMax)
+BB_RESOLVE_DEPTH(3, kDepthZero) BB_RESOLVE_DEPTH(3, kDepthMin) BB_RESOLVE_DEPTH(3, kDepthMax)
+BB_RESOLVE_DEPTH(4, kDepthZero) BB_RESOLVE_DEPTH(4, kDepthMin) BB_RESOLVE_DEPTH(4, kDepthMax)
+#undef BB_RESOLVE_DEPTH
 
 // ------------------------------------------------------------------------------------------------
 // The wire forms of the exchange (include/bibim_hip.h, BBR_SHARD_*): what a rank's shard of n = shard_rows * width pixels

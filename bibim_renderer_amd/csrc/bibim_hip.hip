@@ -114,7 +114,8 @@ struct FrameMode {
   int n = 1;             // option "supersample": samples per output pixel along each axis
   bool resolve = false;  // n >= 2: the kernels up to shading write the fine frame (library-owned), k_resolve the output
   bool merged = false;   // ... with option "sample_shading" 0: a sample map, k_sample_merge, k_resolve_merged
-  bool depth = false;    // option "overlays": the frame keeps its depth for bbr_draw_overlays (whole frame, n = 1)
+  bool depth = false;    // option "overlays": the frame keeps its depth for bbr_draw_overlays (whole frame; n >= 2: a rule)
+  int depth_rule = 0;    // n >= 2: option "depth_resolve" (0: no depth is kept; else k_resolve_depth's MODE, VkResolveModeFlagBits)
   bool fused = false;    // option "present_fused": the frame is written as presented RGBA8 (the slot's d_present) ...
   bool shade_presents() const { return fused && !resolve; }   // ... by k_raster / k_shade
   bool resolve_presents() const { return fused && resolve; }  // ... by k_resolve (a presented byte cannot be averaged): then
@@ -148,6 +149,11 @@ template <class F> void with_samples(int n, F &&f) {  // n = 2, 3 or 4
   n == 2 ? f(std::integral_constant<int, 2>{}) : n == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 4>{});
 }
 
+template <class F> void with_depth_rule(int rule, F &&f) {  // option "depth_resolve": 1, 4 or 8
+  rule == kDepthZero ? f(std::integral_constant<int, kDepthZero>{})
+                     : rule == kDepthMin ? f(std::integral_constant<int, kDepthMin>{}) : f(std::integral_constant<int, kDepthMax>{});
+}
+
 }  // namespace
 
 // Everything one frame in flight owns.
@@ -177,6 +183,7 @@ struct FrameSlot {
                                       // k_resolve_merged), one word of 2 (n = 2) or 8 (n = 4) bytes per output pixel
   DeviceBuffer<float4> d_background;  // deferred path: colour of the pixels no geometry covers
   DeviceBuffer<float> d_depth;        // option "overlays": the frame's resolved depth, for bbr_draw_overlays
+  DeviceBuffer<float> d_fine_depth;   // ... with n >= 2 and a rule: k_raster's depth of the render extent (k_resolve_depth -> d_depth)
   FrameMode mode;                     // of the frame in this slot: which of the buffers above hold it (fused: d_present, d_frame nothing)
   FrameUniformBlock frame_u = {};     // the uniforms the frame in this slot was rendered with (overlays need them)
   ViewUniformBlock view_u = {};
@@ -231,7 +238,7 @@ struct FrameSlot {
   void release_all() {
     d_staging.release(); d_tris.release(); d_attrs.release(); d_clip.release(); d_gathered.release(); d_whole.release();
     d_block_stats.release();
-    release_tile_buffers(); d_broad.release(); d_frame.release(); d_fine.release(); d_sample_map.release(); d_present.release(); d_background.release(); d_depth.release();
+    release_tile_buffers(); d_broad.release(); d_frame.release(); d_fine.release(); d_sample_map.release(); d_present.release(); d_background.release(); d_depth.release(); d_fine_depth.release();
     if (h_staging) (void)hipHostFree(h_staging);
     h_staging = nullptr;
     if (h_flags) (void)hipHostFree(h_flags);
@@ -275,6 +282,9 @@ struct bbr_context {
   // option "sample_shading": 1 = every sample of the fine frame is shaded; 0 = one fragment per primitive and output pixel
   // (k_sample_merge, k_resolve_merged).  Stored at any "supersample", in effect with n >= 2; the pair (3, 0) is refused.
   int sample_shading = 1;
+  // option "depth_resolve": which sample of a block gives the output pixel its depth and winner (VkResolveModeFlagBits: 0 none,
+  // 1 SAMPLE_ZERO, 4 MIN, 8 MAX).  Stored at any "supersample", in effect with n >= 2 (frame_mode).
+  int depth_resolve = 0;
   int32_t render_width() const { return width * supersample; }
   int32_t render_height() const { return height * supersample; }
   hipStream_t s_geom = nullptr, s_raster = nullptr, s_shade = nullptr, s_present = nullptr;  // context-owned streams
@@ -312,8 +322,10 @@ struct bbr_context {
   };
   std::vector<UiTexture> ui_textures;  // bbr_upload_ui_texture: handle = index + 1, a freed one has no texels
   DeviceBuffer<float> d_ui_dec;        // the blend's decode table (ui_dec_table)
-  DeviceBuffer<uint32_t> d_vis_prim;
+  DeviceBuffer<uint32_t> d_vis_prim;  // bbr_read_visibility's dump, width x height (n >= 2: resolved by k_resolve_depth from ...
   DeviceBuffer<float> d_vis_depth;
+  DeviceBuffer<uint32_t> d_vis_fine_prim;  // ... k_raster's dump of the render extent: bbr_read_sample_visibility)
+  DeviceBuffer<float> d_vis_fine_depth;
   void *ext_out = nullptr;
   uint64_t ext_out_bytes = 0;
 
@@ -465,8 +477,9 @@ FrameMode frame_mode(const bbr_context *c) {
   m.resolve = c->supersample > 1;
   m.merged = m.resolve && c->sample_shading == 0;
   m.fused = c->present_fused;
-  // (bbr_draw_overlays is refused on a partition, and with n >= 2: no depth is kept there until a depth resolve rule exists)
-  m.depth = c->overlays && c->world == 1 && !m.resolve;
+  m.depth_rule = m.resolve ? c->depth_resolve : 0;
+  // (bbr_draw_overlays is refused on a partition, and with n >= 2 unless option "depth_resolve" names a rule)
+  m.depth = c->overlays && c->world == 1 && (!m.resolve || m.depth_rule != 0);
   m.out_rows = (size_t)std::max(c->height, c->shard_rows());
   if (m.resolve) m.fine_pixels = c->fine_pixels();
   if (m.merged) m.map_words = ((size_t)c->width * m.out_rows * sample_map_word_bytes(m.n) + 7) / 8;
@@ -477,6 +490,10 @@ FrameMode frame_mode(const bbr_context *c) {
 int refuse_supersampled(bbr_context *c, const char *who, const char *why = "its buffers have the output extent") {
   if (!frame_mode(c).resolve) return BBR_OK;
   return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": not available with option supersample >= 2 (" + why + ")");
+}
+// ... unless option "depth_resolve" names the rule that gives an output pixel its depth and its winner
+int refuse_without_depth_rule(bbr_context *c, const char *who, const char *why) {
+  return frame_mode(c).depth_rule ? BBR_OK : refuse_supersampled(c, who, why);
 }
 // the pair of options that is refused, in whichever order it is asked for: a 3 x 3 block straddles the tiles
 bool refused_pair(int64_t supersample, int64_t sample_shading) { return supersample == 3 && sample_shading == 0; }
@@ -526,6 +543,20 @@ FrameParams make_params(const bbr_context *c) {
   fp.gbuffer_view = c->deferred ? c->gbuffer_view : -1;
   return fp;
 }
+// The overlay pass draws one sample per OUTPUT pixel into the presented image (whole frame only): with n >= 2 its extent,
+// half extents, tile grid and rows are the output's, not the render extent's.  At n = 1 this is make_params.
+FrameParams make_output_params(const bbr_context *c) {
+  FrameParams fp = make_params(c);
+  fp.width = c->width;
+  fp.height = c->height;
+  fp.half_w = 0.5f * (float)c->width;
+  fp.half_h = 0.5f * (float)c->height;
+  fp.tiles_x = (c->width + c->tile_w() - 1) / c->tile_w();
+  fp.tiles_y = (c->height + c->tile_h() - 1) / c->tile_h();
+  fp.band_tiles = c->eff_band_rows() / c->tile_h();
+  fp.shard_rows = c->shard_rows();
+  return fp;
+}
 
 // Wait for everything this context has queued.
 int drain(bbr_context *c) {
@@ -541,10 +572,10 @@ int drain(bbr_context *c) {
 int ensure_srgb_tables(bbr_context *c);
 
 // The buffers of one binned pass (k_geometry -> k_raster) over `n_prims` primitives at the context's tile grid and
-// capacities.  The main pass (ensure_slot_buffers) adds its items, item groups, cooked lights, heavy list, frame, present,
+// capacities (`tiles`: the pass's grid -- the render extent's, or the output extent's for an overlay pass over a resolved frame).
+// The main pass (ensure_slot_buffers) adds its items, item groups, cooked lights, heavy list, frame, present,
 // depth and dump buffers; the overlay pass (bbr_draw_overlays) passes n_prims > 0 and needs none of those.
-int ensure_pass_buffers(bbr_context *c, FrameSlot &s, uint32_t n_prims) {
-  const size_t tiles = (size_t)c->tiles_x() * c->tiles_y();
+int ensure_pass_buffers(bbr_context *c, FrameSlot &s, uint32_t n_prims, size_t tiles) {
   HIP_TRY(c, s.d_tris.ensure(std::max<size_t>(n_prims, 1)));
   HIP_TRY(c, s.d_attrs.ensure(std::max<size_t>(n_prims, 1)));
 #ifdef BB_STAMPS
@@ -569,7 +600,7 @@ int ensure_pass_buffers(bbr_context *c, FrameSlot &s, uint32_t n_prims) {
 
 int ensure_slot_buffers(bbr_context *c, FrameSlot &s, const FrameMode &m) {
   size_t tiles = (size_t)c->tiles_x() * c->tiles_y();
-  int rc = ensure_pass_buffers(c, s, c->n_prims);
+  int rc = ensure_pass_buffers(c, s, c->n_prims, tiles);
   if (rc) return rc;
   HIP_TRY(c, c->d_counters_done.ensure(bbr_context::kCounterBlocks, true));
   // (+ kShadeWaves: the last workgroup of k_shade's main launch reads the item words of all its waves before it knows the count)
@@ -581,6 +612,7 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s, const FrameMode &m) {
   HIP_TRY(c, s.d_heavy.ensure(tiles * kBinClasses, true));
   if (c->deferred) HIP_TRY(c, s.d_background.ensure(2));
   if (m.depth) HIP_TRY(c, s.d_depth.ensure((size_t)c->width * c->height));
+  if (m.depth && m.resolve) HIP_TRY(c, s.d_fine_depth.ensure((size_t)c->render_width() * c->render_height()));
   // (zero filled: the padding rows of a fine shard are never written, and k_resolve reads them)
   if (m.resolve) HIP_TRY(c, s.d_fine.ensure(m.fine_pixels, true));
   // (zero filled like the fine frame: rep 0 for every sample of a shard's padding rows, which no tile writes)
@@ -593,9 +625,15 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s, const FrameMode &m) {
   if (c->dump_gbuffer) HIP_TRY(c, c->d_gbuffer.ensure((size_t)c->width * c->height * 4, true));
   if (c->dump_surface) HIP_TRY(c, c->d_surface.ensure((size_t)c->width * c->height * kSurfaceFloats, true));
   if (!c->ext_out && m.frame32()) HIP_TRY(c, s.d_frame.ensure(m.out_rows * c->width));
-  if (c->dump_vis) {
-    HIP_TRY(c, c->d_vis_prim.ensure((size_t)c->width * c->height));
-    HIP_TRY(c, c->d_vis_depth.ensure((size_t)c->width * c->height));
+  if (c->dump_vis) {  // (n >= 2: k_raster dumps the render extent; the output extent exists where a rule resolves it)
+    if (m.resolve) {
+      HIP_TRY(c, c->d_vis_fine_prim.ensure((size_t)c->render_width() * c->render_height()));
+      HIP_TRY(c, c->d_vis_fine_depth.ensure((size_t)c->render_width() * c->render_height()));
+    }
+    if (!m.resolve || m.depth_rule) {
+      HIP_TRY(c, c->d_vis_prim.ensure((size_t)c->width * c->height));
+      HIP_TRY(c, c->d_vis_depth.ensure((size_t)c->width * c->height));
+    }
   }
   if (!s.h_flags) {
     HIP_TRY(c, hipHostMalloc((void **)&s.h_flags, kHostFlagWords * sizeof(uint32_t), hipHostMallocDefault));
@@ -738,7 +776,10 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   float4 *out = resolve ? s.d_fine.ptr : final_out;
   uint32_t *out8 = mode.shade_presents() ? s.d_present.ptr : nullptr;
   const SrgbTables *tables = mode.shade_presents() ? c->d_srgb_tables.ptr : nullptr;
-  float *depth = mode.depth ? s.d_depth.ptr : nullptr;
+  // (with a resolve k_raster stores the depth, and dumps, at the render extent; k_resolve_depth, behind it, the output's)
+  float *depth = !mode.depth ? nullptr : (resolve ? s.d_fine_depth.ptr : s.d_depth.ptr);
+  uint32_t *vis_prim = !c->dump_vis ? nullptr : (resolve ? c->d_vis_fine_prim.ptr : c->d_vis_prim.ptr);
+  float *vis_depth = !c->dump_vis ? nullptr : (resolve ? c->d_vis_fine_depth.ptr : c->d_vis_depth.ptr);
   // a rank without bands (more ranks than bands) still launches one row: its blocks fall off tiles_y and exit
   const int grid_y = std::max(1, c->world > 1 ? c->local_bands() * fp.band_tiles : fp.tiles_y);
   // A SHORT frame (at most option "no_tail_items" item slots: 1080p has 32 640) has no k_shade_items launch: k_raster's tiles
@@ -777,8 +818,7 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   uint32_t *item_head = short_frame ? d_item_head : nullptr;
   hipLaunchKernelGGL((k_raster<TW, TH>), dim3(fp.tiles_x, fp.heavy_rows + grid_y), dim3(kTileThreads), 0, sr, s.d_tile_count.ptr, ctr,
                      s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, out, fp, s.d_tris.ptr, s.d_clip.ptr, s.d_bins.ptr,
-                     c->dump_vis ? c->d_vis_prim.ptr : nullptr,
-                     c->dump_vis ? c->d_vis_depth.ptr : nullptr,
+                     vis_prim, vis_depth,
                      fp.deferred ? s.d_background.ptr : nullptr, depth, s.h_flags, out8, (short_frame || merged) ? nullptr : s.d_item_groups.ptr, item_head, s.d_items.ptr, d_lights, sp.num_lights,
                      s.d_cooked.ptr, s.d_heavy.ptr);
   if (merged)
@@ -794,6 +834,19 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
     hipLaunchKernelGGL((k_shade_items<TW, TH>), dim3((unsigned)((fp.tiles_x * grid_y + kItemsThreads - 1) / kItemsThreads)), dim3(kItemsThreads), 0, sr, fp, s.d_frag_count.ptr, s.d_item_groups.ptr, s.d_items.ptr,
                        fp.tiles_x, grid_y, s.h_flags ? s.h_flags + kFlagItemCount : nullptr, d_lights, sp.num_lights, s.d_cooked.ptr,
                        s.d_tile_count.ptr, ctr, s.d_heavy.ptr);
+  if (mode.depth_rule && (depth || vis_prim)) {
+    // k_resolve_depth, on k_raster's stream behind it and in front of the edge to the shading stream: the slot's ev_done, recorded
+    // behind shading, covers it in every stream layout.  The plain form for the overlay pass's depth, the PRIM form for the dump.
+    const dim3 grid((unsigned)((c->width + kResolveThreads - 1) / kResolveThreads), (unsigned)c->height);
+    auto launch = [&](auto n, auto rule, auto prim, const float *fine_depth, const uint32_t *fine_prim, float *to_depth, uint32_t *to_prim) {
+      hipLaunchKernelGGL((k_resolve_depth<decltype(n)::value, decltype(rule)::value, decltype(prim)::value>), grid, dim3(kResolveThreads), 0, sr,
+                         reinterpret_cast<const uint32_t *>(fine_depth), fine_prim, reinterpret_cast<uint32_t *>(to_depth), to_prim, c->width);
+    };
+    with_samples(mode.n, [&](auto n) { with_depth_rule(mode.depth_rule, [&](auto rule) {
+      if (depth) launch(n, rule, std::false_type{}, depth, nullptr, s.d_depth.ptr, nullptr);
+      if (vis_prim) launch(n, rule, std::true_type{}, vis_depth, vis_prim, c->d_vis_depth.ptr, c->d_vis_prim.ptr);
+    }); });
+  }
   const uint32_t *item_count = short_frame ? item_head : s.d_items.ptr;   // where k_shade finds the number of items
   if (ev && c->timing == 1) (void)hipEventRecord(ev[2], sr);
   stream_edge(sr, ss, s.ev_raster_done);
@@ -1336,7 +1389,7 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
   BBR_ON_DEVICE(c);
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "draw_overlays: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_overlays: not available with a partition");
-  if (int rc = refuse_supersampled(c, "draw_overlays", "no depth resolve rule")) return rc;
+  if (int rc = refuse_without_depth_rule(c, "draw_overlays", "no depth resolve rule: option depth_resolve is 0")) return rc;
   int rc = sync_and_fix(c, nullptr);  // the overlay pass is synchronous: it is a debugging aid, not part of the hot path
   if (rc) return rc;
   FrameSlot &fs = c->slots[c->last_slot];
@@ -1409,9 +1462,9 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
   for (size_t q = 1; q < draws.size() && q <= (size_t)kInlineFirstPrims; ++q) ov_first.v[q - 1] = draws[q].first_prim;
 
   for (int attempt = 0; attempt < 8; ++attempt) {
-    rc = ensure_pass_buffers(c, s, n_prims);  // (again after a growth)
+    FrameParams fp = make_output_params(c);
+    rc = ensure_pass_buffers(c, s, n_prims, (size_t)fp.tiles_x * fp.tiles_y);  // (again after a growth)
     if (rc) return rc;
-    FrameParams fp = make_params(c);
     fp.deferred = 0;
     fp.gbuffer_view = -1;
     fp.ov_first_gizmo_prim = gizmo ? marker_tris * (uint32_t)n_lights : 0xFFFFFFFFu;
@@ -1664,6 +1717,8 @@ static void release_context(bbr_context *c) {
   c->d_counters_done.release();
   c->d_vis_prim.release();
   c->d_vis_depth.release();
+  c->d_vis_fine_prim.release();
+  c->d_vis_fine_depth.release();
   c->d_gbuffer.release();
   for (FrameSlot &s : c->slots) s.release_all();
   for (Mesh *m : {&c->marker_mesh, &c->gizmo_mesh}) {
@@ -2130,6 +2185,7 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
   c->band_rows = band_rows;
   for (FrameSlot &s : c->slots) {  // (a fine shard's padding rows, and their map words, are the zeros of a fresh buffer)
     s.d_fine.release();
+    s.d_fine_depth.release();
     s.d_sample_map.release();
   }
   c->exchange_slot = -1;  // (block sizes change with the partition)
@@ -2149,7 +2205,7 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
 static void drop_extent_buffers(bbr_context *c) {
   auto drop = [](FrameSlot &s) {
     s.release_tile_buffers();
-    s.d_frame.release(); s.d_fine.release(); s.d_sample_map.release(); s.d_present.release(); s.d_depth.release();
+    s.d_frame.release(); s.d_fine.release(); s.d_sample_map.release(); s.d_present.release(); s.d_depth.release(); s.d_fine_depth.release();
     s.mode = FrameMode{};
     s.present.active = false;
     s.present.out = nullptr;
@@ -2163,6 +2219,8 @@ static void drop_extent_buffers(bbr_context *c) {
   c->tbn_pass.release();  // (its records were snapped to the old extent)
   c->d_vis_prim.release();
   c->d_vis_depth.release();
+  c->d_vis_fine_prim.release();
+  c->d_vis_fine_depth.release();
   c->d_gbuffer.release();
   forget_current_frame(c);  // (the whole frame of the last exchange had the old extent, too)
 }
@@ -2246,14 +2304,45 @@ int bbr_get_stats(bbr_context *c, bbr_stats *out) {
 int bbr_read_visibility(bbr_context *c, uint32_t *prim_host, float *depth_host) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
-  if (int rc = refuse_supersampled(c, "read_visibility")) return rc;
+  if (int rc = refuse_without_depth_rule(c, "read_visibility", "its buffers have the output extent and option depth_resolve is 0")) return rc;
   if (!c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_visibility: nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_visibility: not available on a partitioned context");
-  int rc = rerender_with(c, &bbr_context::dump_vis);
+  int rc = rerender_with(c, &bbr_context::dump_vis);  // (n >= 2: k_resolve_depth's PRIM form fills the two buffers)
   if (rc) return rc;
   size_t n = (size_t)c->width * c->height;
   if (prim_host) HIP_TRY(c, hipMemcpy(prim_host, c->d_vis_prim.ptr, n * 4, hipMemcpyDeviceToHost));
   if (depth_host) HIP_TRY(c, hipMemcpy(depth_host, c->d_vis_depth.ptr, n * 4, hipMemcpyDeviceToHost));
+  return BBR_OK;
+}
+
+// the winners and depths of the render extent, as k_raster dumps them: no rule is involved
+int bbr_read_sample_visibility(bbr_context *c, uint32_t *prim_host, float *depth_host) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_sample_visibility: not available on a partitioned context");
+  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_sample_visibility: nothing rendered");
+  if (!frame_mode(c).resolve) return bbr_read_visibility(c, prim_host, depth_host);  // one sample per pixel
+  int rc = rerender_with(c, &bbr_context::dump_vis);
+  if (rc) return rc;
+  const size_t n = (size_t)c->render_width() * c->render_height();
+  if (prim_host) HIP_TRY(c, hipMemcpy(prim_host, c->d_vis_fine_prim.ptr, n * 4, hipMemcpyDeviceToHost));
+  if (depth_host) HIP_TRY(c, hipMemcpy(depth_host, c->d_vis_fine_depth.ptr, n * 4, hipMemcpyDeviceToHost));
+  return BBR_OK;
+}
+
+// the depth the last frame kept for the overlay pass (n >= 2: k_resolve_depth's plain form wrote it)
+int bbr_read_depth(bbr_context *c, float *depth_host) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!depth_host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_depth: NULL");
+  if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_depth: not available on a partitioned context");
+  if (int rc = refuse_without_depth_rule(c, "read_depth", "no depth resolve rule: option depth_resolve is 0")) return rc;
+  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_depth: nothing rendered");
+  int rc = sync_and_fix(c, nullptr);
+  if (rc) return rc;
+  const FrameSlot &s = c->slots[c->last_slot];
+  if (!s.mode.depth) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_depth: the frame was rendered without option \"overlays\"");
+  HIP_TRY(c, hipMemcpy(depth_host, s.d_depth.ptr, (size_t)c->width * c->height * 4, hipMemcpyDeviceToHost));
   return BBR_OK;
 }
 
@@ -2575,6 +2664,19 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
       c->sample_shading = (int)value;
       for (FrameSlot &s : c->slots) s.d_sample_map.release();
       forget_current_frame(c);
+    }
+  } else if (n == "depth_resolve") {
+    // VkResolveModeFlagBits; AVERAGE (2) has no winner.  At n = 1 the value is only stored; with n >= 2 the current frame was
+    // rendered under the other rule (or kept no depth at all): there is none any more, and the fine depth goes
+    if (value != 0 && value != kDepthZero && value != kDepthMin && value != kDepthMax)
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, "depth_resolve: 0 (none), 1 (SAMPLE_ZERO), 4 (MIN) or 8 (MAX)");
+    if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "depth_resolve: between begin_frame and end_frame");
+    if ((int)value != c->depth_resolve) {
+      c->depth_resolve = (int)value;
+      if (c->supersample > 1) {
+        for (FrameSlot &s : c->slots) s.d_fine_depth.release();
+        forget_current_frame(c);
+      }
     }
   } else if (n == "present_fused") {
     c->present_fused = value != 0;

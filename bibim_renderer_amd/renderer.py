@@ -188,6 +188,22 @@ class Renderer:
         self._check(self._L.bbr_read_visibility(self._ctx, _ptr(prim), _ptr(depth)))
         return prim, depth
 
+    def read_sample_visibility(self):
+        """winner and depth of every fine pixel of the last frame (option "supersample" = n): two [n*height, n*width] arrays,
+        uint32 and float32 -- the samples option "depth_resolve" chooses from; read_visibility() with n = 1"""
+        n = self.supersample
+        prim = np.empty((n * self.height, n * self.width), np.uint32)
+        depth = np.empty((n * self.height, n * self.width), np.float32)
+        self._check(self._L.bbr_read_sample_visibility(self._ctx, _ptr(prim), _ptr(depth)))
+        return prim, depth
+
+    def read_depth(self):
+        """the depth the last frame kept for the overlay pass (option "overlays"; n >= 2: under option "depth_resolve"):
+        [height, width] float32"""
+        depth = np.empty((self.height, self.width), np.float32)
+        self._check(self._L.bbr_read_depth(self._ctx, _ptr(depth)))
+        return depth
+
     def stats(self):
         s = BbrStats()
         self._check(self._L.bbr_get_stats(self._ctx, C.byref(s)))

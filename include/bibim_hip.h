@@ -200,6 +200,18 @@ int bbr_host_timing_reset(bbr_context *ctx);
 /* winning primitive (global API-order index, 0xFFFFFFFF = none) and depth per pixel; synchronises.
  * Re-runs the frame once with the visibility dump enabled. */
 int bbr_read_visibility(bbr_context *ctx, uint32_t *prim_host, float *depth_host);
+/* With option "supersample" = n >= 2 and a rule in option "depth_resolve", bbr_read_visibility returns the RESOLVED winner and
+ * depth, width x height (the option's rule; the dump path of k_resolve_depth).  Its siblings:
+ *   bbr_read_sample_visibility  the winners and depths of the render extent, n*height * n*width values each, row-major -- the
+ *                               samples the rule chooses from, whatever the option's value; in the family of bbr_read_samples.
+ *                               With n = 1 it is bbr_read_visibility.  Re-runs the frame once, synchronises.
+ *   bbr_read_depth              the depth the last frame KEPT for the overlay pass (option "overlays"), width x height: with
+ *                               n = 1 the bits of bbr_read_visibility's depth, with n >= 2 what k_resolve_depth wrote behind
+ *                               k_raster.  Nothing is rendered again.  INVALID_ARGUMENT when the frame was rendered without
+ *                               "overlays", or with n >= 2 and "depth_resolve" 0.
+ * Both: BBR_ERR_NOT_IN_FRAME before a frame, BBR_ERR_INVALID_ARGUMENT on a partitioned context. */
+int bbr_read_sample_visibility(bbr_context *ctx, uint32_t *prim_host, float *depth_host);
+int bbr_read_depth(bbr_context *ctx, float *depth_host);
 /* device time of the last bbr_end_frame/bbr_replay_frame in ms, and of its dominant kernel (k_shade); synchronises */
 int bbr_last_frame_time_ms(bbr_context *ctx, float *out_frame_ms, float *out_shade_kernel_ms);
 /* With option "timing" = 1 every frame records HIP events on the context's stream (frame start, geometry kernel
@@ -274,9 +286,34 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            rows); a rank's resolved shard is the shard of the resolved whole frame.  BBR_SHARD_PACKED
  *                            keeps one alpha bit per pixel and is refused with n >= 2: bbr_stage_shard, bbr_pack_shard,
  *                            bbr_allgather_frame and bbr_push_shard return INVALID_ARGUMENT for it and launch nothing.
- *                            Also refused with n >= 2 (INVALID_ARGUMENT): bbr_draw_overlays, TBN included (its depth test
- *                            needs a depth resolve rule), bbr_read_visibility, bbr_read_gbuffer, bbr_read_surface and
- *                            bbr_read_records (their buffers have the output extent)
+ *                            Also refused with n >= 2 (INVALID_ARGUMENT): bbr_draw_overlays, TBN included, and
+ *                            bbr_read_visibility (both need a depth resolve rule: while option "depth_resolve" is 0),
+ *                            bbr_read_gbuffer, bbr_read_surface and bbr_read_records (their buffers have the output
+ *                            extent), whatever "depth_resolve" is
+ *   "depth_resolve" 0|1|4|8  with "supersample" n >= 2: which sample of an output pixel's block gives the pixel its depth and
+ *                            its winning primitive.  The values are VkResolveModeFlagBits (pass (int)depthResolveMode):
+ *                              0  NONE         default: no depth is kept while n >= 2, and bbr_draw_overlays, bbr_read_visibility
+ *                                              and bbr_read_depth are refused as above
+ *                              1  SAMPLE_ZERO  k* = 0
+ *                              4  MIN          k* = the first k, in index order, whose depth bit pattern is smallest
+ *                              8  MAX          k* = the first k, in index order, whose depth bit pattern is largest
+ *                            The block of output pixel (x, y) is the fine pixels (nx + i, ny + j) and k = j * n + i, as in
+ *                            the colour resolve; bit patterns are compared as unsigned 32-bit integers.  The resolved depth
+ *                            is the bit pattern of sample k*, the resolved primitive the winner of sample k* (0xFFFFFFFF
+ *                            where that sample is uncovered).  Stored depths lie in [0, 1] and an uncovered sample holds
+ *                            the cleared 0.0, so the order of the bit patterns is the order of the values, and it is the
+ *                            comparison the rasteriser's keys make.  Depth is reverse-Z (the larger value wins): MAX is
+ *                            the nearest sample, MIN the farthest, and one uncovered sample makes MIN return 0.  With
+ *                            "sample_shading" 0 the samples keep their own depth: the rule is the same.
+ *                            k_resolve_depth runs behind k_raster in every frame that keeps its depth ("overlays" 1), and in
+ *                            bbr_read_visibility's re-render.  bbr_draw_overlays then draws the markers, the gizmo and the
+ *                            TBN lines one sample per OUTPUT pixel into the presented width x height image, depth-tested
+ *                            against the resolved depth.  Deviation: a multisampled Vulkan pass would rasterise them at n^2
+ *                            samples and resolve their colour with the scene's.
+ *                            2 (AVERAGE: an averaged depth has no winner) and every other value: INVALID_ARGUMENT.  The
+ *                            value is stored at any "supersample"; at n = 1 it changes nothing and no kernel of it runs.
+ *                            Setting a new value while n >= 2 leaves no current frame; the fine depth is dropped.  A
+ *                            partition refuses all of these calls as before
  *   "sample_shading" 0|1     with "supersample" n >= 2: 1 (default) shades every sample (sampleShadingEnable = VK_TRUE, the
  *                            rule above, bit for bit; no kernel of this option runs).  0 is multisampling
  *                            (sampleShadingEnable = VK_FALSE): one fragment is shaded per primitive and output pixel.
@@ -306,8 +343,8 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *   "present_fused" 0|1      frames are produced as presented RGBA8 pixels directly (binary16 stage, tone map and sRGB
  *                            encode fused into the raster / shade kernels): no fp32 frame, no k_present pass; bbr_present
  *                            then only marks (or copies to a caller buffer), bbr_read_framebuffer / bbr_read_shard fail
- *   "overlays" 0|1           keep every frame's resolved depth for bbr_draw_overlays (default 0; nothing is kept while
- *                            "supersample" >= 2, where bbr_draw_overlays is refused)
+ *   "overlays" 0|1           keep every frame's resolved depth for bbr_draw_overlays (default 0; with "supersample" >= 2 only
+ *                            under a rule of "depth_resolve": with its value 0 nothing is kept and bbr_draw_overlays is refused)
  *   "tbn" 0|1                bbr_draw_overlays first draws the TBN lines of the last frame (default 0; see below)
  *   "stream_layout" 0|1|2    how the kernels of the frames in flight are spread over HIP streams.  Same pixels in every
  *                            layout.  0: geometry + raster on one stream, shade on a second, present on a third.
