@@ -24,6 +24,7 @@
 
 #include "../../include/bibim_hip.h"
 #include "bb_kernels.hip.h"
+#include "bb_own.h"
 #include "bb_pack.h"
 #include "bb_ui_kernels.hip.h"
 
@@ -47,17 +48,18 @@ struct Rccl {
 Rccl g_rccl;
 std::mutex g_rccl_mutex;
 
+// (Mesh, Material: move-only through their buffers; `m = Mesh()` frees a handle)
 struct Mesh {
-  Vertex *d_vertices = nullptr;
-  uint32_t *d_indices = nullptr;
+  DeviceBuffer<Vertex> d_vertices;
+  DeviceBuffer<uint32_t> d_indices;
   uint32_t n_vertices = 0, n_indices = 0;
   bool alive = false;
 };
 
 struct Material {
-  uint8_t *d_texels[kMapCount] = {};
-  uint8_t *d_packed = nullptr;
-  uint8_t *d_chain = nullptr;  // option "mip_levels" >= 2: levels >= 1 of every supplied map and of the packed form, one allocation
+  DeviceBuffer<uint8_t> d_texels[kMapCount];
+  DeviceBuffer<uint8_t> d_packed;
+  DeviceBuffer<uint8_t> d_chain;  // option "mip_levels" >= 2: levels >= 1 of every supplied map and of the packed form, one allocation
   MipTable mip = {};           // where every level of every set starts (valid while "mip_levels" >= 2)
   MaterialDesc desc = {};
   bool alive = false;
@@ -68,45 +70,13 @@ struct RecordedDraw {
   uint32_t n_instances, first_instance, first_prim, tris_per_instance;
 };
 
-// hipMemset runs on the NULL stream and may return before the fill has happened; the context's streams are created
-// hipStreamNonBlocking, i.e. they do NOT order themselves after the NULL stream.  A kernel launched right after an
-// allocation could therefore run BEFORE the zero fill and have its counters / fragment counts wiped afterwards
-// (seen as an empty first frame when several processes share the GPU).  Every zero fill is completed here.
-inline hipError_t zero_fill_sync(void *ptr, size_t bytes) {
-  hipError_t e = hipMemset(ptr, 0, bytes);
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  return e;
-}
-
 // Host -> device copies that kernels on the (non-blocking) context streams read right afterwards: completed on the
-// NULL stream before returning, for the same reason.
+// NULL stream before returning, for the reason given at zero_fill_sync (bb_own.h).
 inline hipError_t upload_sync(void *dst, const void *src, size_t bytes) {
   hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   return e;
 }
-
-template <typename T>
-struct DeviceBuffer {
-  T *ptr = nullptr;
-  size_t cap = 0;  // elements
-  hipError_t ensure(size_t n, bool zero = false) {
-    if (n <= cap) return hipSuccess;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&ptr, n * sizeof(T));
-    if (e != hipSuccess) return e;
-    cap = n;
-    if (zero) e = zero_fill_sync(ptr, n * sizeof(T));
-    return e;
-  }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-  }
-};
 
 // What the options in force mean for a frame: decided in frame_mode (below) and nowhere else.  ensure_slot_buffers allocates
 // from it, launch_frame takes its pointers from it, and the slot keeps it for the read-backs.  The default is "no frame".
@@ -127,20 +97,22 @@ inline size_t sample_map_word_bytes(int n) { return n == 2 ? sizeof(SampleMap<2>
 // A ring of (start, stop) event pairs around one kind of launch while option "timing" is on, with the number of launches
 // since the last reset.  The events are made on demand and live as long as the context.
 constexpr uint32_t kRingCap = 512;
+// `n` timing events in `events`, made where there are fewer (plain ones, as hipEventCreate makes them)
+inline hipError_t ensure_events(std::vector<Event> &events, size_t n) {
+  events.reserve(n);
+  for (Event e; events.size() < n; events.push_back(std::move(e)))
+    if (hipError_t err = e.ensure()) return err;
+  return hipSuccess;
+}
 struct PairRing {
-  std::vector<hipEvent_t> events;
+  std::vector<Event> events;
   uint32_t launches = 0;
-  hipError_t ensure() {
-    for (hipEvent_t e = nullptr; events.size() < 2 * kRingCap; events.push_back(e))
-      if (hipError_t err = hipEventCreate(&e)) return err;
-    return hipSuccess;
-  }
+  hipError_t ensure() { return ensure_events(events, 2 * kRingCap); }
   hipEvent_t start(uint32_t i) const { return events[2 * (i % kRingCap)]; }
   hipEvent_t stop(uint32_t i) const { return events[2 * (i % kRingCap) + 1]; }
   hipError_t begin(hipStream_t st) { return hipEventRecord(start(launches), st); }
   hipError_t end(hipStream_t st) { return hipEventRecord(stop(launches++), st); }
   void reset() { launches = 0; }
-  void destroy() { for (hipEvent_t e : events) (void)hipEventDestroy(e); }
 };
 
 // A run-time choice as a compile-time constant: f(std::true_type or std::false_type), f(std::integral_constant<int, n>)
@@ -156,38 +128,49 @@ template <class F> void with_depth_rule(int rule, F &&f) {  // option "depth_res
 
 }  // namespace
 
-// Everything one frame in flight owns.
-struct FrameSlot {
-  void *h_staging = nullptr;  // pinned: lights, draw descriptors, instances
-  uint32_t *h_flags = nullptr;  // pinned, device-visible: the kHostFlagWords words of HostFlagWord (bb_types.h), stored by the kernels
-                                // of the frame last rendered in this slot and read when the slot's next frame is submitted
-  size_t staging_cap = 0;
-  DeviceBuffer<uint8_t> d_staging;
-  DeviceBuffer<RasterTri> d_tris;
-  DeviceBuffer<ShadeRec> d_attrs;
-  DeviceBuffer<ClipSlot> d_clip;
-  int ctr_index = 0;                        // the slot's counter block (slot index; the overlay slot has the last one)
-  DeviceBuffer<BlockStats> d_block_stats;  // one record per k_geometry wave
+// A group of members stated once, at its declaration: dropping the group is assigning a fresh one, so a new buffer needs its
+// declaration and nothing else.
+template <class Group, class Whole> void drop(Whole &w) { static_cast<Group &>(w) = Group(); }
+
+// What a slot holds that is sized by the tile grid: option "tile_mode" drops it (bins and fragment lists are laid out per
+// tile, and ensure() zeroes the fresh counters), and so does whatever drops the ExtentSized group.
+struct TileSized {
   DeviceBuffer<uint32_t> d_tile_count;
   DeviceBuffer<uint32_t> d_bins;
-  DeviceBuffer<BroadTri> d_broad;
   DeviceBuffer<unsigned long long> d_frags;  // per tile: compacted (pixel << 32 | primitive ref) of covered pixels
   DeviceBuffer<uint32_t> d_frag_count;
   DeviceBuffer<uint32_t> d_items;       // k_shade's work list: [0] = count, then slot << 6 | chunk of 64 fragments
   DeviceBuffer<CookedLight> d_cooked;   // the frame's light table as the light loop consumes it (k_shade_items -> k_shade)
   DeviceBuffer<uint32_t> d_heavy;       // the frame's heavy-tile list (k_geometry -> k_raster; option "heavy_tiles")
   DeviceBuffer<uint32_t> d_item_groups; // 64-fragment chunks per group of 256 launch slots (k_raster -> k_shade_items)
+};
+// ... by the render or the output extent: bbr_resize and option "supersample" drop it (drop_extent_buffers)
+struct ExtentSized {
   DeviceBuffer<float4> d_frame;
   DeviceBuffer<float4> d_fine;        // option "supersample" >= 2: the fine frame k_resolve reads (always library-owned)
   DeviceBuffer<unsigned long long> d_sample_map;  // option "sample_shading" 0: the frame's sample map (k_sample_merge ->
                                       // k_resolve_merged), one word of 2 (n = 2) or 8 (n = 4) bytes per output pixel
-  DeviceBuffer<float4> d_background;  // deferred path: colour of the pixels no geometry covers
   DeviceBuffer<float> d_depth;        // option "overlays": the frame's resolved depth, for bbr_draw_overlays
   DeviceBuffer<float> d_fine_depth;   // ... with n >= 2 and a rule: k_raster's depth of the render extent (k_resolve_depth -> d_depth)
+  DeviceBuffer<uint32_t> d_present;   // RGBA8 presented image of this slot's frame (bbr_present)
+};
+
+// Everything one frame in flight owns.  What is in neither group survives an option change and a resize.
+struct FrameSlot : TileSized, ExtentSized {
+  PinnedBlock<uint8_t> h_staging;  // pinned: lights, draw descriptors, instances
+  PinnedBlock<uint32_t> h_flags;   // pinned, device-visible: the kHostFlagWords words of HostFlagWord (bb_types.h), stored by the kernels
+                                   // of the frame last rendered in this slot and read when the slot's next frame is submitted
+  DeviceBuffer<uint8_t> d_staging;
+  DeviceBuffer<RasterTri> d_tris;
+  DeviceBuffer<ShadeRec> d_attrs;
+  DeviceBuffer<ClipSlot> d_clip;
+  int ctr_index = 0;                        // the slot's counter block (slot index; the overlay slot has the last one)
+  DeviceBuffer<BlockStats> d_block_stats;  // one record per k_geometry wave
+  DeviceBuffer<BroadTri> d_broad;
+  DeviceBuffer<float4> d_background;  // deferred path: colour of the pixels no geometry covers
   FrameMode mode;                     // of the frame in this slot: which of the buffers above hold it (fused: d_present, d_frame nothing)
   FrameUniformBlock frame_u = {};     // the uniforms the frame in this slot was rendered with (overlays need them)
   ViewUniformBlock view_u = {};
-  DeviceBuffer<uint32_t> d_present;  // RGBA8 presented image of this slot's frame (bbr_present)
   struct {
     bool active = false;  // bbr_present was queued for the frame in this slot (re-queued if the frame is replayed)
     uint32_t *out = nullptr;
@@ -195,10 +178,10 @@ struct FrameSlot {
     int32_t enable = 0, hdr16 = 1;
     float exposure = 1.f;
   } present;
-  hipEvent_t ev_geom_done = nullptr, ev_raster_done = nullptr, ev_tail_done = nullptr;  // edges between the streams of a frame
+  Event ev_geom_done, ev_raster_done, ev_tail_done;  // edges between the streams of a frame
   // Everything queued on this slot's image so far: the frame's k_shade, then whatever was put behind it (presentation, the
   // GUI pass, a copy to the caller's buffer, the exchange).  Work on the image goes between follow() and busy_until().
-  hipEvent_t ev_done = nullptr;
+  Event ev_done;
   // `st` follows everything queued on the slot so far.  (Also needed on the slot's own stream once something ran elsewhere:
   // a separate presentation pass may have run on another stream and moved the event there.)
   hipError_t follow(hipStream_t st) const { return hipStreamWaitEvent(st, ev_done, 0); }
@@ -209,12 +192,11 @@ struct FrameSlot {
   // GUI pass (bbr_draw_ui) of the frame in this slot: pinned staging [commands | vertices | indices], its device copy and
   // the per-triangle records; ev_copied says the staging may be written again
   struct {
-    void *h_staging = nullptr;
-    size_t staging_cap = 0;
+    PinnedBlock<uint8_t> h_staging;
     DeviceBuffer<uint8_t> d_staging;
     DeviceBuffer<UiTri> d_tris;
     DeviceBuffer<UiBox> d_boxes;
-    hipEvent_t ev_copied = nullptr;
+    Event ev_copied;
     bool copy_pending = false;
   } ui;
   bool in_flight = false;
@@ -225,35 +207,13 @@ struct FrameSlot {
   // The flag words describe frames rendered with the old capacities (apply_growth) / the old extent (bbr_resize).  Two sets,
   // kept apart as they were; the heavy-tile count survives both (a list that does not fit its rows is merely not used).
   void forget_capacities() {
-    if (h_flags) h_flags[kFlagOverflow] = h_flags[kFlagBinNeed] = h_flags[kFlagItemCount] = h_flags[kFlagBroadNeed] = h_flags[kFlagClipNeed] = 0u;
+    if (uint32_t *f = h_flags.ptr) f[kFlagOverflow] = f[kFlagBinNeed] = f[kFlagItemCount] = f[kFlagBroadNeed] = f[kFlagClipNeed] = 0u;
   }
   void forget_extent() {
-    if (h_flags) h_flags[kFlagOverflow] = h_flags[kFlagBinNeed] = h_flags[kFlagItemCount] = 0u;
-  }
-  void release_tile_buffers() {
-    d_tile_count.release(); d_bins.release(); d_frags.release(); d_frag_count.release(); d_items.release(); d_item_groups.release(); d_cooked.release(); d_heavy.release();
+    if (uint32_t *f = h_flags.ptr) f[kFlagOverflow] = f[kFlagBinNeed] = f[kFlagItemCount] = 0u;
   }
   // native exchange (bbr_allgather_frame / bbr_push_shard) with library-owned buffers: every rank's block, the whole frame
   DeviceBuffer<uint8_t> d_gathered, d_whole;
-  void release_all() {
-    d_staging.release(); d_tris.release(); d_attrs.release(); d_clip.release(); d_gathered.release(); d_whole.release();
-    d_block_stats.release();
-    release_tile_buffers(); d_broad.release(); d_frame.release(); d_fine.release(); d_sample_map.release(); d_present.release(); d_background.release(); d_depth.release(); d_fine_depth.release();
-    if (h_staging) (void)hipHostFree(h_staging);
-    h_staging = nullptr;
-    if (h_flags) (void)hipHostFree(h_flags);
-    h_flags = nullptr;
-    staging_cap = 0;
-    ui.d_staging.release(); ui.d_tris.release(); ui.d_boxes.release();
-    if (ui.h_staging) (void)hipHostFree(ui.h_staging);
-    ui.h_staging = nullptr;
-    ui.staging_cap = 0;
-    ui.copy_pending = false;
-    for (hipEvent_t *e : {&ev_geom_done, &ev_raster_done, &ev_tail_done, &ev_done, &ui.ev_copied}) {
-      if (*e) (void)hipEventDestroy(*e);
-      *e = nullptr;
-    }
-  }
 };
 
 // The streams the kernels of one frame run on (bbr_context::frame_streams).
@@ -273,7 +233,16 @@ bool is_live(const bbr_context *c) {
 }
 }  // namespace
 
-struct bbr_context {
+// The context's buffers of the output or the render extent: the dumps of the read-backs.  drop_extent_buffers drops the group.
+struct ExtentDumps {
+  DeviceBuffer<uint32_t> d_vis_prim;  // bbr_read_visibility's dump, width x height (n >= 2: resolved by k_resolve_depth from ...
+  DeviceBuffer<float> d_vis_depth;
+  DeviceBuffer<uint32_t> d_vis_fine_prim;  // ... k_raster's dump of the render extent: bbr_read_sample_visibility)
+  DeviceBuffer<float> d_vis_fine_depth;
+  DeviceBuffer<uint2> d_gbuffer;  // width*height*4 (four RGBA16F texels per pixel), only while bbr_read_gbuffer runs
+};
+
+struct bbr_context : ExtentDumps {
   int device = 0;
   int32_t width = 0, height = 0;  // the OUTPUT extent: what every output, shard, present, exchange, GUI and caller buffer is sized by
   // option "supersample": everything up to and including shading (tiles, bins, fragment lists, items, the viewport, the flag
@@ -287,13 +256,13 @@ struct bbr_context {
   int depth_resolve = 0;
   int32_t render_width() const { return width * supersample; }
   int32_t render_height() const { return height * supersample; }
-  hipStream_t s_geom = nullptr, s_raster = nullptr, s_shade = nullptr, s_present = nullptr;  // context-owned streams
+  Stream s_geom, s_raster, s_shade, s_present;  // context-owned streams (declared first, so destroyed last: behind every event and buffer)
   hipStream_t user_stream = nullptr;                 // bbr_set_stream: everything on the caller's stream, 1 frame in flight
   std::string last_error;
 
   std::vector<Mesh> meshes;
   std::vector<Material> materials;
-  uint8_t *d_default_texels = nullptr;  // 6 x RGBA8 (1x1 default maps)
+  DeviceBuffer<uint8_t> d_default_texels;  // 6 x RGBA8 (1x1 default maps)
   DeviceBuffer<MaterialDesc> d_materials;
   bool materials_dirty = true;
   bool all_packed = true;  // every live material has a packed form (k_shade's MIXED = false instantiation may be used)
@@ -317,15 +286,11 @@ struct bbr_context {
 
   DeviceBuffer<SrgbTables> d_srgb_tables;  // thresholds t_k (linear value at which the sRGB byte becomes k) + the keyed table
   struct UiTexture {
-    uint32_t *d_texels = nullptr;  // RGBA8, row-major
+    DeviceBuffer<uint32_t> d_texels;  // RGBA8, row-major
     int32_t w = 0, h = 0;
   };
   std::vector<UiTexture> ui_textures;  // bbr_upload_ui_texture: handle = index + 1, a freed one has no texels
   DeviceBuffer<float> d_ui_dec;        // the blend's decode table (ui_dec_table)
-  DeviceBuffer<uint32_t> d_vis_prim;  // bbr_read_visibility's dump, width x height (n >= 2: resolved by k_resolve_depth from ...
-  DeviceBuffer<float> d_vis_depth;
-  DeviceBuffer<uint32_t> d_vis_fine_prim;  // ... k_raster's dump of the render extent: bbr_read_sample_visibility)
-  DeviceBuffer<float> d_vis_fine_depth;
   void *ext_out = nullptr;
   uint64_t ext_out_bytes = 0;
 
@@ -338,24 +303,20 @@ struct bbr_context {
   Mesh marker_mesh, gizmo_mesh;  // generateUVSphereMesh(0.1, 16, 16) and the caller's gizmo, both as Vertex meshes
   FrameSlot ov;           // buffers of the overlay pass (its own little frame)
   bool tbn = false;       // option "tbn": bbr_draw_overlays first draws the TBN lines of the last frame (tbn.vert/.geom/.frag)
-  struct TbnPass {
+  struct TbnRecords {  // what drop_extent_buffers drops of the pass (its records were snapped to the old extent)
     DeviceBuffer<uint8_t> d_staging;   // the frame's draw descriptors + instances
     DeviceBuffer<TbnSeg> d_segs;       // eight slots per primitive (slot = key)
     DeviceBuffer<uint32_t> d_tile_count, d_bins, d_ctr;
     DeviceBuffer<uint32_t> d_keys;     // per pixel: key + 1 of the winning segment, 0 = none
-    uint32_t bin_cap = 1024;           // bin entries per 32 x 32 tile (grows on overflow)
     uint32_t n_slots = 0;
     bool valid = false;                // d_segs holds the records of the last TBN draw
-    void release() {
-      d_staging.release(); d_segs.release(); d_tile_count.release(); d_bins.release(); d_ctr.release(); d_keys.release();
-      n_slots = 0;
-      valid = false;
-    }
+  };
+  struct TbnPass : TbnRecords {
+    uint32_t bin_cap = 1024;           // bin entries per 32 x 32 tile (grows on overflow)
   } tbn_pass;
   int gbuffer_view = -1;  // option "gbuffer_view": GBufferVisualizingOption (src/scene.h:27-35) while the deferred path runs
   bool deferred = false;  // option "render_pass": the reference's deferred path (its default) instead of the forward one
   bool dump_gbuffer = false;
-  DeviceBuffer<uint2> d_gbuffer;  // width*height*4 (four RGBA16F texels per pixel), only while bbr_read_gbuffer runs
   int max_anisotropy = 1;         // option "max_anisotropy": 1 = k_shade's bilinear tap, 2..16 = k_shade_aniso
   int mip_levels = 1;             // option "mip_levels": 1 = no chain, the kernels above; 2..15 = chains of up to that many levels, k_shade_mip
   DeviceBuffer<MipTable> d_mip_tables;  // one per material slot, beside d_materials (only while "mip_levels" >= 2)
@@ -367,7 +328,7 @@ struct bbr_context {
   int timing_stride = 1;  // option "timing_stride": events on every n-th frame only (two events a frame cost ~4 % at C3)
   uint64_t timing_tick = 0;
   // timing ring: (frame start, geometry done, raster done, shade start, shade done) per frame since the last reset
-  std::vector<hipEvent_t> ring;
+  std::vector<Event> ring;
   uint32_t ring_frames = 0;
   PairRing present_ring;  // around each k_present while timing is on
   PairRing resolve_ring;  // around the k_resolve of each timed frame: pair i is ring frame i's (the two counts are reset together)
@@ -635,22 +596,18 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s, const FrameMode &m) {
       HIP_TRY(c, c->d_vis_depth.ensure((size_t)c->width * c->height));
     }
   }
-  if (!s.h_flags) {
-    HIP_TRY(c, hipHostMalloc((void **)&s.h_flags, kHostFlagWords * sizeof(uint32_t), hipHostMallocDefault));
-    for (int i = 0; i < kHostFlagWords; ++i) s.h_flags[i] = 0u;
+  if (!s.h_flags.ptr) {
+    HIP_TRY(c, s.h_flags.ensure(kHostFlagWords * sizeof(uint32_t)));
+    for (int i = 0; i < kHostFlagWords; ++i) s.h_flags.ptr[i] = 0u;
   }
-  for (hipEvent_t *e : {&s.ev_geom_done, &s.ev_raster_done, &s.ev_done, &s.ev_tail_done})
-    if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+  for (Event *e : {&s.ev_geom_done, &s.ev_raster_done, &s.ev_done, &s.ev_tail_done}) HIP_TRY(c, e->ensure(hipEventDisableTiming));
   return BBR_OK;
 }
 
 // The timing ring's events (option "timing": made there, not in the first timed frame -- 2560 hipEventCreate calls take
 // half a millisecond)
 int ensure_timing_ring(bbr_context *c, bool resolve_pairs) {
-  if (c->ring.empty()) {
-    c->ring.resize(bbr_context::kRingEvents * bbr_context::kRingCap);
-    for (auto &e : c->ring) HIP_TRY(c, hipEventCreate(&e));
-  }
+  HIP_TRY(c, ensure_events(c->ring, bbr_context::kRingEvents * bbr_context::kRingCap));
   if (resolve_pairs) HIP_TRY(c, c->resolve_ring.ensure());  // around k_resolve, one pair per ring frame
   return BBR_OK;
 }
@@ -679,8 +636,7 @@ int mip_extent(int n, int level) { return std::max(1, n >> level); }
 size_t packed_level_bytes(int w, int h) { return (((size_t)w + 3) / 4) * (((size_t)h + 3) / 4) * 16 * kPackedTexelBytes + kPackedTexelPad; }
 
 void free_chain(Material &m) {
-  if (m.d_chain) (void)hipFree(m.d_chain);
-  m.d_chain = nullptr;
+  m.d_chain.release();
   m.mip = MipTable{};
 }
 
@@ -696,7 +652,7 @@ int build_chain(bbr_context *c, Material &m) {
   for (int i = 0; i < kMapCount; ++i) {
     const TexDesc &td = m.desc.maps[i];
     MipSet &ms = m.mip.set[i];
-    ms.levels = m.d_texels[i] ? mip_level_count(td.w, td.h, n) : 1;  // (a defaulted map is 1 x 1)
+    ms.levels = m.d_texels[i].ptr ? mip_level_count(td.w, td.h, n) : 1;  // (a defaulted map is 1 x 1)
     ms.level[0] = td.texels;
     for (int k = 1; k < ms.levels; ++k) {
       offset[i][k] = total;
@@ -711,26 +667,26 @@ int build_chain(bbr_context *c, Material &m) {
     total += aligned(packed_level_bytes(mip_extent(m.desc.pw, k), mip_extent(m.desc.ph, k)));
   }
   if (!total) return BBR_OK;
-  HIP_TRY(c, hipMalloc(&m.d_chain, total));
+  HIP_TRY(c, m.d_chain.ensure(total));
   for (int i = 0; i < kMipSets; ++i)
-    for (int k = 1; k < m.mip.set[i].levels; ++k) m.mip.set[i].level[k] = m.d_chain + offset[i][k];
+    for (int k = 1; k < m.mip.set[i].levels; ++k) m.mip.set[i].level[k] = m.d_chain.ptr + offset[i][k];
   for (int i = 0; i < kMapCount; ++i) {
     const TexDesc &td = m.desc.maps[i];
     const MipSet &ms = m.mip.set[i];
     for (int k = 1; k < ms.levels; ++k) {
       const int w0 = mip_extent(td.w, k - 1), h0 = mip_extent(td.h, k - 1), w1 = mip_extent(td.w, k), h1 = mip_extent(td.h, k);
       hipLaunchKernelGGL(k_mip_reduce, dim3((unsigned)(((size_t)w1 * h1 + kMipThreads - 1) / kMipThreads)), dim3(kMipThreads), 0, nullptr,
-                         (const uint32_t *)ms.level[k - 1], w0, h0, (uint32_t *)(m.d_chain + offset[i][k]), w1, h1);
+                         (const uint32_t *)ms.level[k - 1], w0, h0, (uint32_t *)(m.d_chain.ptr + offset[i][k]), w1, h1);
     }
   }
   for (int k = 1; k < ps.levels; ++k) {
     // (the supplied shaded maps of a packed material have its size, so each has this level)
     MipPackMaps maps;
-    for (int j = 0; j < 5; ++j) maps.map[j] = m.d_texels[j] ? m.mip.set[j].level[k] : nullptr;
+    for (int j = 0; j < 5; ++j) maps.map[j] = m.d_texels[j].ptr ? m.mip.set[j].level[k] : nullptr;
     const int w = mip_extent(m.desc.pw, k), h = mip_extent(m.desc.ph, k);
     const size_t slots = std::max<size_t>((((size_t)w + 3) / 4) * (((size_t)h + 3) / 4) * 16, kPackedTexelPad);
     hipLaunchKernelGGL(k_mip_pack, dim3((unsigned)((slots + kMipThreads - 1) / kMipThreads)), dim3(kMipThreads), 0, nullptr, maps,
-                       (const uint8_t *)c->d_default_texels, w, h, m.d_chain + offset[kMapCount][k]);
+                       (const uint8_t *)c->d_default_texels.ptr, w, h, m.d_chain.ptr + offset[kMapCount][k]);
   }
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(nullptr));
@@ -765,7 +721,7 @@ int upload_material_table(bbr_context *c) {
 
 // `ev`: the frame's five timing events, or nullptr; `final_out`: the W x H fp32 frame (nullptr if the mode has none)
 template <int TW, int TH>
-void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const FrameStreams &st, hipEvent_t *ev, const FrameParams &fp_in,
+void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const FrameStreams &st, const Event *ev, const FrameParams &fp_in,
                   const Mat4 &pv, const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DrawDesc *d_draws, uint32_t n_draws,
                   const FirstPrims &first_prims, float4 *final_out, uint32_t *d_item_head) {
   FrameParams fp = fp_in;
@@ -796,7 +752,7 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   const int64_t heavy_tiles = c->heavy_tiles >= 0 ? c->heavy_tiles : (c->pipelined() ? 0 : 64);
   if (!short_frame && heavy_tiles > 0 && !c->dump_vis) {
     fp.heavy_threshold = (uint32_t)heavy_tiles;
-    const uint32_t seen_heavy = s.h_flags ? s.h_flags[kFlagHeavyTiles] : 0u;
+    const uint32_t seen_heavy = s.h_flags.ptr ? s.h_flags.ptr[kFlagHeavyTiles] : 0u;
     if (seen_heavy) fp.heavy_rows = (int32_t)((seen_heavy + seen_heavy / 8u + 8u + (uint32_t)fp.tiles_x - 1u) / (uint32_t)fp.tiles_x);
   }
   const hipStream_t sg = st.geom, sr = st.raster, ss = st.shade;
@@ -819,7 +775,7 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   hipLaunchKernelGGL((k_raster<TW, TH>), dim3(fp.tiles_x, fp.heavy_rows + grid_y), dim3(kTileThreads), 0, sr, s.d_tile_count.ptr, ctr,
                      s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, out, fp, s.d_tris.ptr, s.d_clip.ptr, s.d_bins.ptr,
                      vis_prim, vis_depth,
-                     fp.deferred ? s.d_background.ptr : nullptr, depth, s.h_flags, out8, (short_frame || merged) ? nullptr : s.d_item_groups.ptr, item_head, s.d_items.ptr, d_lights, sp.num_lights,
+                     fp.deferred ? s.d_background.ptr : nullptr, depth, s.h_flags.ptr, out8, (short_frame || merged) ? nullptr : s.d_item_groups.ptr, item_head, s.d_items.ptr, d_lights, sp.num_lights,
                      s.d_cooked.ptr, s.d_heavy.ptr);
   if (merged)
     with_samples(mode.n, [&](auto n) {
@@ -832,7 +788,7 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   // same launch cooks the frame's light table
   if (!short_frame)
     hipLaunchKernelGGL((k_shade_items<TW, TH>), dim3((unsigned)((fp.tiles_x * grid_y + kItemsThreads - 1) / kItemsThreads)), dim3(kItemsThreads), 0, sr, fp, s.d_frag_count.ptr, s.d_item_groups.ptr, s.d_items.ptr,
-                       fp.tiles_x, grid_y, s.h_flags ? s.h_flags + kFlagItemCount : nullptr, d_lights, sp.num_lights, s.d_cooked.ptr,
+                       fp.tiles_x, grid_y, s.h_flags.ptr ? s.h_flags.ptr + kFlagItemCount : nullptr, d_lights, sp.num_lights, s.d_cooked.ptr,
                        s.d_tile_count.ptr, ctr, s.d_heavy.ptr);
   if (mode.depth_rule && (depth || vis_prim)) {
     // k_resolve_depth, on k_raster's stream behind it and in front of the edge to the shading stream: the slot's ev_done, recorded
@@ -856,7 +812,7 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   // Main launch: one item (64 fragments) per wave, four per workgroup, sized from the item count of the frame this slot
   // rendered last (k_shade_items leaves it in pinned host memory) plus 3 %; tail launch: a small persistent grid for
   // whatever lies behind that (a scene that suddenly grew; normally nothing, and its workgroups exit at once).
-  const uint32_t seen = s.h_flags ? s.h_flags[kFlagItemCount] : 0u;
+  const uint32_t seen = s.h_flags.ptr ? s.h_flags.ptr[kFlagItemCount] : 0u;
   uint32_t est = seen ? seen + seen / 32u + 64u : max_items;
   if (est > max_items) est = max_items;
   // A small frame is launched at full coverage instead: workgroups without an item leave after one scalar load, and a few
@@ -963,8 +919,8 @@ uint32_t fill_draw_descs(const bbr_context *c, DrawDesc *hd, const InstanceBlock
     if (!rd.n_instances || !rd.tris_per_instance) continue;
     const Mesh &m = c->meshes[rd.mesh];
     DrawDesc d;
-    d.vertices = m.d_vertices;
-    d.indices = m.d_indices;
+    d.vertices = m.d_vertices.ptr;
+    d.indices = m.d_indices.ptr;
     d.instances = d_inst_base + rd.first_instance;
     d.n_instances = rd.n_instances;
     d.tris_per_instance = rd.tris_per_instance;
@@ -1000,9 +956,8 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   // Self-healing for hosts that only stream frames: the frame that last used this slot reported an overflow.  Its
   // pixels (and those of the frames queued since) are incomplete and already handed out; from this frame on the
   // capacities fit.  (Synchronising calls do better: they re-render the overflowed frame, sync_and_fix.)
-  if (s.h_flags && s.h_flags[kFlagOverflow]) {
-    const uint32_t overflow = s.h_flags[kFlagOverflow], bin_need = s.h_flags[kFlagBinNeed], broad_need = s.h_flags[kFlagBroadNeed],
-                   clip_need = s.h_flags[kFlagClipNeed];
+  if (const uint32_t *f = s.h_flags.ptr; f && f[kFlagOverflow]) {
+    const uint32_t overflow = f[kFlagOverflow], bin_need = f[kFlagBinNeed], broad_need = f[kFlagBroadNeed], clip_need = f[kFlagClipNeed];
     rc = drain(c);
     if (rc) return rc;
     rc = apply_growth(c, overflow, bin_need, broad_need, clip_need);
@@ -1019,29 +974,26 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   // ... [item head: one zero word, 16-byte slot] -- k_raster's tiles count a short frame's items through it (launch_frame)
   const size_t head_offset = (lights_bytes + draws_bytes + inst_bytes + 15) & ~(size_t)15;
   size_t total = head_offset + 16;
-  if (total > s.staging_cap) {
-    if (s.h_staging) (void)hipHostFree(s.h_staging);
-    s.h_staging = nullptr;
-    size_t cap = std::max<size_t>(total * 2, 1 << 16);
-    HIP_TRY(c, hipHostMalloc(&s.h_staging, cap, hipHostMallocDefault));
-    s.staging_cap = cap;
-    HIP_TRY(c, s.d_staging.ensure(cap));
+  if (total > s.h_staging.cap) {
+    HIP_TRY(c, s.h_staging.ensure(std::max<size_t>(total * 2, 1 << 16)));
+    HIP_TRY(c, s.d_staging.ensure(s.h_staging.cap));
   }
-  std::memcpy(s.h_staging, c->frame_u.lights, lights_bytes);
+  uint8_t *const h_staging = s.h_staging.ptr;
+  std::memcpy(h_staging, c->frame_u.lights, lights_bytes);
   // draw descriptors point into the device copy of the instance data made by the same transfer
   FirstPrims first_prims;  // first_prim of the frame's draws 1 .. 3 (k_geometry)
   const uint32_t n_live_draws =
-      fill_draw_descs(c, reinterpret_cast<DrawDesc *>((uint8_t *)s.h_staging + lights_bytes),
+      fill_draw_descs(c, reinterpret_cast<DrawDesc *>(h_staging + lights_bytes),
                       reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + lights_bytes + draws_bytes), first_prims);
-  if (inst_bytes) std::memcpy((uint8_t *)s.h_staging + lights_bytes + draws_bytes, c->host_instances.data(), inst_bytes);
-  std::memset((uint8_t *)s.h_staging + head_offset, 0, 16);
+  if (inst_bytes) std::memcpy(h_staging + lights_bytes + draws_bytes, c->host_instances.data(), inst_bytes);
+  std::memset(h_staging + head_offset, 0, 16);
   uint32_t *d_item_head = reinterpret_cast<uint32_t *>(s.d_staging.ptr + head_offset);
 
   const int n_lights = std::min(std::max(c->frame_u.num_lights, 0), kMaxNumLights);
   const FrameStreams st = c->frame_streams(slot_index);
   for (hipEvent_t e : c->pending_waits) HIP_TRY(c, hipStreamWaitEvent(st.geom, e, 0));  // bbr_wait_event
   c->pending_waits.clear();
-  hipEvent_t *ev = nullptr;  // this frame's timing events, if it carries any
+  const Event *ev = nullptr;  // this frame's timing events, if it carries any
   if (c->timing && (c->timing_tick++ % (uint64_t)c->timing_stride) == 0) {
     rc = ensure_timing_ring(c, mode.resolve);
     if (rc) return rc;
@@ -1063,7 +1015,7 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   sp.num_lights = n_lights;
   float4 *out = !mode.frame32() ? nullptr : (c->ext_out ? reinterpret_cast<float4 *>(c->ext_out) : s.d_frame.ptr);
 
-  HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, s.h_staging, total, hipMemcpyHostToDevice, st.geom));
+  HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, h_staging, total, hipMemcpyHostToDevice, st.geom));
   if (c->tile_mode == 0) launch_frame<64, 64>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head);
   else launch_frame<32, 32>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head);
   HIP_TRY(c, hipGetLastError());
@@ -1217,13 +1169,11 @@ const void *last_output(const bbr_context *c) {
 namespace {
 
 int upload_internal_mesh(bbr_context *c, Mesh &m, const std::vector<Vertex> &v, const std::vector<uint32_t> &idx) {
-  if (m.d_vertices) (void)hipFree(m.d_vertices);
-  if (m.d_indices) (void)hipFree(m.d_indices);
   m = Mesh();
-  HIP_TRY(c, hipMalloc(&m.d_vertices, v.size() * sizeof(Vertex)));
-  HIP_TRY(c, upload_sync(m.d_vertices, v.data(), v.size() * sizeof(Vertex)));
-  HIP_TRY(c, hipMalloc(&m.d_indices, idx.size() * sizeof(uint32_t)));
-  HIP_TRY(c, upload_sync(m.d_indices, idx.data(), idx.size() * sizeof(uint32_t)));
+  HIP_TRY(c, m.d_vertices.ensure(v.size()));
+  HIP_TRY(c, upload_sync(m.d_vertices.ptr, v.data(), v.size() * sizeof(Vertex)));
+  HIP_TRY(c, m.d_indices.ensure(idx.size()));
+  HIP_TRY(c, upload_sync(m.d_indices.ptr, idx.data(), idx.size() * sizeof(uint32_t)));
   m.n_vertices = (uint32_t)v.size();
   m.n_indices = (uint32_t)idx.size();
   m.alive = true;
@@ -1308,8 +1258,8 @@ int draw_tbn(bbr_context *c, FrameSlot &fs) {
   for (const RecordedDraw &rd : c->draws) {
     const Mesh &m = c->meshes[rd.mesh];
     DrawDesc d = {};
-    d.vertices = m.d_vertices;
-    d.indices = m.d_indices;
+    d.vertices = m.d_vertices.ptr;
+    d.indices = m.d_indices.ptr;
     d.n_instances = rd.n_instances;
     d.tris_per_instance = rd.tris_per_instance;
     d.first_prim = rd.first_prim;
@@ -1358,6 +1308,7 @@ int draw_tbn(bbr_context *c, FrameSlot &fs) {
 extern "C" int bbr_upload_gizmo(bbr_context *c, const void *gizmo_vertices, uint32_t n_vertices, const uint32_t *indices,
                                 uint32_t n_indices) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
   if (!gizmo_vertices || !n_vertices) return fail(c, BBR_ERR_INVALID_ARGUMENT, "upload_gizmo: null/empty input");
   int rc = drain(c);
   if (rc) return rc;
@@ -1445,13 +1396,13 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
   const InstanceBlock *d_inst = reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + draws_bytes);
   if (n_lights) {
     DrawDesc d = {};
-    d.vertices = c->marker_mesh.d_vertices; d.indices = c->marker_mesh.d_indices; d.instances = d_inst;
+    d.vertices = c->marker_mesh.d_vertices.ptr; d.indices = c->marker_mesh.d_indices.ptr; d.instances = d_inst;
     d.n_instances = (uint32_t)n_lights; d.tris_per_instance = marker_tris; d.first_prim = 0; d.material = 1u;  // program: marker
     draws.push_back(d);
   }
   if (gizmo) {
     DrawDesc d = {};
-    d.vertices = c->gizmo_mesh.d_vertices; d.indices = c->gizmo_mesh.d_indices; d.instances = d_inst + n_lights;
+    d.vertices = c->gizmo_mesh.d_vertices.ptr; d.indices = c->gizmo_mesh.d_indices.ptr; d.instances = d_inst + n_lights;
     d.n_instances = 1; d.tris_per_instance = gizmo_tris; d.first_prim = marker_tris * (uint32_t)n_lights; d.material = 2u;  // program: gizmo
     draws.push_back(d);
   }
@@ -1524,20 +1475,17 @@ extern "C" int bbr_upload_ui_texture(bbr_context *c, const uint8_t *rgba8, int32
     return fail(c, BBR_ERR_INVALID_ARGUMENT, "upload_ui_texture: null input or size outside 1..16384");
   bbr_context::UiTexture t;
   const size_t bytes = (size_t)w * h * 4;
-  HIP_TRY(c, hipMalloc(&t.d_texels, bytes));
-  const hipError_t e = upload_sync(t.d_texels, rgba8, bytes);
-  if (e != hipSuccess) {
-    (void)hipFree(t.d_texels);
-    return fail(c, BBR_ERR_HIP, std::string("upload_ui_texture: ") + hipGetErrorString(e));
-  }
+  HIP_TRY(c, t.d_texels.ensure((size_t)w * h));
+  const hipError_t e = upload_sync(t.d_texels.ptr, rgba8, bytes);
+  if (e != hipSuccess) return fail(c, BBR_ERR_HIP, std::string("upload_ui_texture: ") + hipGetErrorString(e));
   t.w = w;
   t.h = h;
   // handles start at 1: 0 is the GUI's null ImTextureID.  The lowest freed handle is handed out again, so a host that
   // rebuilds its atlas again and again does not grow the table.
   size_t at = 0;
-  while (at < c->ui_textures.size() && c->ui_textures[at].d_texels) ++at;
-  if (at == c->ui_textures.size()) c->ui_textures.push_back(t);
-  else c->ui_textures[at] = t;
+  while (at < c->ui_textures.size() && c->ui_textures[at].d_texels.ptr) ++at;
+  if (at == c->ui_textures.size()) c->ui_textures.push_back(std::move(t));
+  else c->ui_textures[at] = std::move(t);
   *out_texture = (int32_t)at + 1;
   return BBR_OK;
 }
@@ -1546,11 +1494,10 @@ extern "C" int bbr_free_ui_texture(bbr_context *c, int32_t texture) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   if (!is_live(c)) return BBR_ERR_BAD_HANDLE;
   BBR_ON_DEVICE(c);
-  if (texture < 1 || texture > (int32_t)c->ui_textures.size() || !c->ui_textures[texture - 1].d_texels)
+  if (texture < 1 || texture > (int32_t)c->ui_textures.size() || !c->ui_textures[texture - 1].d_texels.ptr)
     return fail(c, BBR_ERR_BAD_HANDLE, "free_ui_texture: bad handle");
   int rc = drain(c);  // a queued GUI pass may still sample it
   if (rc) return rc;
-  (void)hipFree(c->ui_textures[texture - 1].d_texels);
   c->ui_textures[texture - 1] = bbr_context::UiTexture();
   return BBR_OK;
 }
@@ -1575,7 +1522,7 @@ extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
     return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_ui: malformed draw data (see bbr_ui_validate)");
   for (uint32_t i = 0; i < draw->n_cmds; ++i) {
     const int32_t t = draw->cmds[i].texture;
-    if (draw->cmds[i].elem_count && (t < 1 || t > (int32_t)c->ui_textures.size() || !c->ui_textures[t - 1].d_texels))
+    if (draw->cmds[i].elem_count && (t < 1 || t > (int32_t)c->ui_textures.size() || !c->ui_textures[t - 1].d_texels.ptr))
       return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_ui: a command names a texture that is not alive");
   }
   if (box[2] <= box[0] || box[3] <= box[1]) return BBR_OK;  // nothing can pass a scissor
@@ -1590,7 +1537,7 @@ extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
     if (!in.elem_count || !ui_scissor(in.clip_rect, *draw, c->width, c->height, sc)) continue;
     const bbr_context::UiTexture &t = c->ui_textures[in.texture - 1];
     UiCmd u = {};
-    u.texels = t.d_texels; u.tw = t.w; u.th = t.h;
+    u.texels = t.d_texels.ptr; u.tw = t.w; u.th = t.h;
     u.vtx_offset = in.vtx_offset; u.idx_offset = in.idx_offset;
     u.first_tri = (uint32_t)n_tris64;
     u.sx0 = sc[0]; u.sy0 = sc[1]; u.sx1 = sc[2]; u.sy1 = sc[3];
@@ -1613,21 +1560,14 @@ extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
     HIP_TRY(c, upload_sync(c->d_ui_dec.ptr, dec, sizeof dec));
   }
   auto &ui = s.ui;
-  if (!ui.ev_copied) HIP_TRY(c, hipEventCreateWithFlags(&ui.ev_copied, hipEventDisableTiming));
+  HIP_TRY(c, ui.ev_copied.ensure(hipEventDisableTiming));
   // Each buffer is tested against its own capacity, so that a call after a failed allocation grows what is still missing.
-  if (total > ui.staging_cap || total > ui.d_staging.cap || n_tris > ui.d_tris.cap || n_tris > ui.d_boxes.cap) {
+  if (total > ui.h_staging.cap || total > ui.d_staging.cap || n_tris > ui.d_tris.cap || n_tris > ui.d_boxes.cap) {
     // growing: everything queued for this slot (an earlier GUI pass included) must have left the buffers first
     HIP_TRY(c, s.wait_idle());
     ui.copy_pending = false;
-    if (total > ui.staging_cap) {
-      if (ui.h_staging) (void)hipHostFree(ui.h_staging);
-      ui.h_staging = nullptr;
-      ui.staging_cap = 0;
-      const size_t cap = std::max<size_t>(total * 2, 1 << 16);
-      HIP_TRY(c, hipHostMalloc(&ui.h_staging, cap, hipHostMallocDefault));
-      ui.staging_cap = cap;  // the pinned block exists; the device block has a capacity of its own
-    }
-    if (total > ui.d_staging.cap) HIP_TRY(c, ui.d_staging.ensure(ui.staging_cap));
+    if (total > ui.h_staging.cap) HIP_TRY(c, ui.h_staging.ensure(std::max<size_t>(total * 2, 1 << 16)));
+    if (total > ui.d_staging.cap) HIP_TRY(c, ui.d_staging.ensure(ui.h_staging.cap));  // (the device block has a capacity of its own)
     const size_t tri_cap = std::max<size_t>((size_t)n_tris * 2, 4096);
     if (n_tris > ui.d_tris.cap) HIP_TRY(c, ui.d_tris.ensure(tri_cap));
     if (n_tris > ui.d_boxes.cap) HIP_TRY(c, ui.d_boxes.ensure(tri_cap));
@@ -1636,7 +1576,7 @@ extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
     HIP_TRY(c, hipEventSynchronize(ui.ev_copied));
     ui.copy_pending = false;
   }
-  uint8_t *h = static_cast<uint8_t *>(ui.h_staging);
+  uint8_t *h = ui.h_staging.ptr;
   std::memcpy(h, cmds.data(), cmds_bytes);
   std::memcpy(h + vtx_at, draw->vertices, vtx_bytes);
   std::memcpy(h + idx_at, draw->indices, idx_bytes);
@@ -1644,7 +1584,7 @@ extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
   // behind the presentation (and whatever was queued on the image since), on the stream the presentation used
   const hipStream_t ps = c->slot_present_stream(s);
   HIP_TRY(c, s.follow(ps));
-  HIP_TRY(c, hipMemcpyAsync(ui.d_staging.ptr, ui.h_staging, total, hipMemcpyHostToDevice, ps));
+  HIP_TRY(c, hipMemcpyAsync(ui.d_staging.ptr, h, total, hipMemcpyHostToDevice, ps));
   HIP_TRY(c, hipEventRecord(ui.ev_copied, ps));
   ui.copy_pending = true;
   const UiTransform t = ui_transform(*draw, c->width, c->height);
@@ -1692,50 +1632,12 @@ int bbr_device_count(void) {
 
 const char *bbr_last_error(const bbr_context *ctx) { return ctx ? ctx->last_error.c_str() : g_create_error.c_str(); }
 
-// Everything a context owns, whatever state its construction reached (bbr_destroy, and bbr_create when a step fails).
+// Everything a context owns, whatever state its construction reached (bbr_destroy, and bbr_create when a step fails): the
+// context's members own themselves, and nothing is freed before the drain.
 static void release_context(bbr_context *c) {
   (void)hipSetDevice(c->device);
   (void)drain(c);
   if (c->comm) (void)g_rccl.comm_destroy(c->comm);
-  for (Mesh &m : c->meshes) {
-    if (m.d_vertices) (void)hipFree(m.d_vertices);
-    if (m.d_indices) (void)hipFree(m.d_indices);
-  }
-  for (Material &m : c->materials) {
-    for (auto &p : m.d_texels)
-      if (p) (void)hipFree(p);
-    if (m.d_packed) (void)hipFree(m.d_packed);
-    free_chain(m);
-  }
-  c->d_mip_tables.release();
-  if (c->d_default_texels) (void)hipFree(c->d_default_texels);
-  for (auto &t : c->ui_textures)
-    if (t.d_texels) (void)hipFree(t.d_texels);
-  c->d_ui_dec.release();
-  c->d_materials.release();
-  c->d_counters.release();
-  c->d_counters_done.release();
-  c->d_vis_prim.release();
-  c->d_vis_depth.release();
-  c->d_vis_fine_prim.release();
-  c->d_vis_fine_depth.release();
-  c->d_gbuffer.release();
-  for (FrameSlot &s : c->slots) s.release_all();
-  for (Mesh *m : {&c->marker_mesh, &c->gizmo_mesh}) {
-    if (m->d_vertices) (void)hipFree(m->d_vertices);
-    if (m->d_indices) (void)hipFree(m->d_indices);
-  }
-  c->ov.release_all();
-  c->tbn_pass.release();
-  for (auto &e : c->ring)
-    if (e) (void)hipEventDestroy(e);
-  c->present_ring.destroy();
-  c->resolve_ring.destroy();
-  c->d_srgb_tables.release();
-  if (c->s_geom) (void)hipStreamDestroy(c->s_geom);
-  if (c->s_raster) (void)hipStreamDestroy(c->s_raster);
-  if (c->s_shade) (void)hipStreamDestroy(c->s_shade);
-  if (c->s_present) (void)hipStreamDestroy(c->s_present);
   delete c;
 }
 
@@ -1773,16 +1675,16 @@ int bbr_create(int32_t width, int32_t height, int32_t device, bbr_context **out_
     int prio_low = 0, prio_high = 0;
     CREATE_TRY(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
     // (measured on C3/C5: swapping or equalising the two priorities changes the pipelined frame time by < 2 %)
-    CREATE_TRY(hipStreamCreateWithPriority(&c->s_geom, hipStreamNonBlocking, prio_high));
+    CREATE_TRY(c->s_geom.create(hipStreamNonBlocking, prio_high));
     // (created here, next to s_geom: a stream made later, once the others are busy, was measured to serialise with them)
-    CREATE_TRY(hipStreamCreateWithPriority(&c->s_raster, hipStreamNonBlocking, prio_high));
-    CREATE_TRY(hipStreamCreateWithPriority(&c->s_shade, hipStreamNonBlocking, prio_low));
-    CREATE_TRY(hipStreamCreateWithPriority(&c->s_present, hipStreamNonBlocking, prio_low));
+    CREATE_TRY(c->s_raster.create(hipStreamNonBlocking, prio_high));
+    CREATE_TRY(c->s_shade.create(hipStreamNonBlocking, prio_low));
+    CREATE_TRY(c->s_present.create(hipStreamNonBlocking, prio_low));
   }
   // `default` material maps (resources/pbr/default/*.png are uniform images): 1x1 RGBA8 each -- the table a packed material
   // broadcasts from (bb_pack.h)
-  CREATE_TRY(hipMalloc(&c->d_default_texels, sizeof kDefaultTexel));
-  CREATE_TRY(upload_sync(c->d_default_texels, kDefaultTexel, sizeof kDefaultTexel));
+  CREATE_TRY(c->d_default_texels.ensure(sizeof kDefaultTexel));
+  CREATE_TRY(upload_sync(c->d_default_texels.ptr, kDefaultTexel, sizeof kDefaultTexel));
 #undef CREATE_TRY
   {
     std::lock_guard<std::mutex> lock(g_live_mutex);
@@ -1817,22 +1719,14 @@ int bbr_upload_mesh(bbr_context *c, const void *vertices, uint32_t n_vertices, c
   m.n_vertices = n_vertices;
   m.n_indices = indices ? n_indices : 0;
   // (a failure half way gives back what the mesh already owns: the handle never comes to exist, so nobody else could)
-  const int rc = [&]() -> int {
-    HIP_TRY(c, hipMalloc(&m.d_vertices, (size_t)n_vertices * sizeof(Vertex)));
-    HIP_TRY(c, upload_sync(m.d_vertices, vertices, (size_t)n_vertices * sizeof(Vertex)));
-    if (m.n_indices) {
-      HIP_TRY(c, hipMalloc(&m.d_indices, (size_t)n_indices * sizeof(uint32_t)));
-      HIP_TRY(c, upload_sync(m.d_indices, indices, (size_t)n_indices * sizeof(uint32_t)));
-    }
-    return BBR_OK;
-  }();
-  if (rc != BBR_OK) {
-    if (m.d_vertices) (void)hipFree(m.d_vertices);
-    if (m.d_indices) (void)hipFree(m.d_indices);
-    return rc;
+  HIP_TRY(c, m.d_vertices.ensure(n_vertices));
+  HIP_TRY(c, upload_sync(m.d_vertices.ptr, vertices, (size_t)n_vertices * sizeof(Vertex)));
+  if (m.n_indices) {
+    HIP_TRY(c, m.d_indices.ensure(n_indices));
+    HIP_TRY(c, upload_sync(m.d_indices.ptr, indices, (size_t)n_indices * sizeof(uint32_t)));
   }
   m.alive = true;
-  c->meshes.push_back(m);
+  c->meshes.push_back(std::move(m));
   *out_mesh = (int32_t)c->meshes.size() - 1;
   return BBR_OK;
 }
@@ -1845,10 +1739,7 @@ int bbr_free_mesh(bbr_context *c, int32_t mesh) {
     return fail(c, BBR_ERR_BAD_HANDLE, "free_mesh: bad handle");
   int rc = drain(c);
   if (rc) return rc;
-  Mesh &m = c->meshes[mesh];
-  if (m.d_vertices) (void)hipFree(m.d_vertices);
-  if (m.d_indices) (void)hipFree(m.d_indices);
-  m = Mesh();
+  c->meshes[mesh] = Mesh();
   c->have_frame = false;
   return BBR_OK;
 }
@@ -1857,28 +1748,18 @@ int bbr_upload_material(bbr_context *c, const bbr_image maps[BBR_MAP_COUNT], int
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!maps || !out_material) return fail(c, BBR_ERR_INVALID_ARGUMENT, "upload_material: null input");
-  Material m;
-  struct Guard {  // frees what a failed upload had already allocated
-    Material *m;
-    ~Guard() {
-      if (!m) return;
-      for (auto &p : m->d_texels)
-        if (p) (void)hipFree(p);
-      if (m->d_packed) (void)hipFree(m->d_packed);
-      free_chain(*m);
-    }
-  } guard{&m};
+  Material m;  // (a failed upload gives back what it had already allocated)
   for (int i = 0; i < kMapCount; ++i) {
     const bbr_image &im = maps[i];
     if (im.rgba && im.width > 0 && im.height > 0) {
       if (im.width > 16384 || im.height > 16384) return fail(c, BBR_ERR_INVALID_ARGUMENT, "upload_material: map too large");
       size_t bytes = (size_t)im.width * im.height * 4;
-      HIP_TRY(c, hipMalloc(&m.d_texels[i], bytes));
-      HIP_TRY(c, upload_sync(m.d_texels[i], im.rgba, bytes));
-      m.desc.maps[i] = TexDesc{m.d_texels[i], im.width, im.height};
+      HIP_TRY(c, m.d_texels[i].ensure(bytes));
+      HIP_TRY(c, upload_sync(m.d_texels[i].ptr, im.rgba, bytes));
+      m.desc.maps[i] = TexDesc{m.d_texels[i].ptr, im.width, im.height};
     } else {
       // missing map => the `default` material's map (src/render.cpp:1328-1336)
-      m.desc.maps[i] = TexDesc{c->d_default_texels + 4 * i, 1, 1};
+      m.desc.maps[i] = TexDesc{c->d_default_texels.ptr + 4 * i, 1, 1};
     }
   }
   // Interleave the five shaded maps when the supplied ones agree on one size (bb_pack.h; missing maps are uniform, so they
@@ -1888,9 +1769,9 @@ int bbr_upload_material(bbr_context *c, const bbr_image maps[BBR_MAP_COUNT], int
     if (plan.packable) {
       std::vector<uint8_t> host(plan.bytes);
       pack_fill(maps, plan, host.data());
-      HIP_TRY(c, hipMalloc(&m.d_packed, host.size()));
-      HIP_TRY(c, upload_sync(m.d_packed, host.data(), host.size()));
-      m.desc.packed = m.d_packed;
+      HIP_TRY(c, m.d_packed.ensure(host.size()));
+      HIP_TRY(c, upload_sync(m.d_packed.ptr, host.data(), host.size()));
+      m.desc.packed = m.d_packed.ptr;
       m.desc.pw = plan.pw;
       m.desc.ph = plan.ph;
     }
@@ -1900,8 +1781,7 @@ int bbr_upload_material(bbr_context *c, const bbr_image maps[BBR_MAP_COUNT], int
     if (rc) return rc;
   }
   m.alive = true;
-  guard.m = nullptr;  // ownership passes to the context
-  c->materials.push_back(m);
+  c->materials.push_back(std::move(m));
   c->materials_dirty = true;
   *out_material = (int32_t)c->materials.size() - 1;
   return BBR_OK;
@@ -1915,12 +1795,7 @@ int bbr_free_material(bbr_context *c, int32_t material) {
     return fail(c, BBR_ERR_BAD_HANDLE, "free_material: bad handle");
   int rc = drain(c);
   if (rc) return rc;
-  Material &m = c->materials[material];
-  for (auto &p : m.d_texels)
-    if (p) (void)hipFree(p);
-  if (m.d_packed) (void)hipFree(m.d_packed);
-  free_chain(m);
-  m = Material();
+  c->materials[material] = Material();
   c->materials_dirty = true;
   c->have_frame = false;
   return BBR_OK;
@@ -1985,7 +1860,7 @@ int bbr_draw(bbr_context *c, int32_t mesh, int32_t material, const void *instanc
     return fail(c, BBR_ERR_BAD_HANDLE, "draw: bad material handle");
   if (n_instances && !instance_blocks) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw: NULL instance data");
   const Mesh &m = c->meshes[mesh];
-  uint32_t tris = (m.d_indices ? m.n_indices : m.n_vertices) / 3;
+  uint32_t tris = (m.d_indices.ptr ? m.n_indices : m.n_vertices) / 3;
   uint64_t total = (uint64_t)c->n_prims + (uint64_t)tris * n_instances;
   if (total >= kMaxPrims) return fail(c, BBR_ERR_TOO_MANY_PRIMITIVES, "draw: more than 2^29 primitives in one frame");
   RecordedDraw rd;
@@ -2203,9 +2078,9 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
 // The render or the output extent changed (bbr_resize, option "supersample"): everything sized by either goes, the flag words
 // are forgotten and there is no current frame.  The context is drained.
 static void drop_extent_buffers(bbr_context *c) {
-  auto drop = [](FrameSlot &s) {
-    s.release_tile_buffers();
-    s.d_frame.release(); s.d_fine.release(); s.d_sample_map.release(); s.d_present.release(); s.d_depth.release(); s.d_fine_depth.release();
+  auto drop_slot = [](FrameSlot &s) {
+    drop<TileSized>(s);
+    drop<ExtentSized>(s);
     s.mode = FrameMode{};
     s.present.active = false;
     s.present.out = nullptr;
@@ -2214,14 +2089,10 @@ static void drop_extent_buffers(bbr_context *c) {
     s.in_flight = false;
     s.forget_extent();
   };
-  for (FrameSlot &s : c->slots) drop(s);
-  drop(c->ov);
-  c->tbn_pass.release();  // (its records were snapped to the old extent)
-  c->d_vis_prim.release();
-  c->d_vis_depth.release();
-  c->d_vis_fine_prim.release();
-  c->d_vis_fine_depth.release();
-  c->d_gbuffer.release();
+  for (FrameSlot &s : c->slots) drop_slot(s);
+  drop_slot(c->ov);
+  drop<bbr_context::TbnRecords>(c->tbn_pass);
+  drop<ExtentDumps>(*c);
   forget_current_frame(c);  // (the whole frame of the last exchange had the old extent, too)
 }
 
@@ -2470,7 +2341,7 @@ int bbr_last_frame_time_ms(bbr_context *c, float *out_frame_ms, float *out_shade
   if (!c->ring_frames) return fail(c, BBR_ERR_NOT_IN_FRAME, "last_frame_time_ms: no timed frame yet");
   int rc = drain(c);
   if (rc) return rc;
-  const hipEvent_t *e = &c->ring[bbr_context::kRingEvents * ((c->ring_frames - 1) % bbr_context::kRingCap)];
+  const Event *e = &c->ring[bbr_context::kRingEvents * ((c->ring_frames - 1) % bbr_context::kRingCap)];
   float a = 0.f, b = 0.f;
   if (c->timing == 1) HIP_TRY(c, hipEventElapsedTime(&a, e[0], frame_end_event(c, c->ring_frames - 1)));
   HIP_TRY(c, hipEventElapsedTime(&b, e[3], e[4]));
@@ -2501,6 +2372,13 @@ int bbr_capacity_growths(const bbr_context *c, uint32_t *out_count) {
   return BBR_OK;
 }
 
+int bbr_debug_live_resources(uint64_t out[5]) {
+  if (!out) return BBR_ERR_INVALID_ARGUMENT;
+  const LiveCounts &n = g_live_counts;
+  for (const std::atomic<uint64_t> *v : {&n.device_allocs, &n.device_bytes, &n.pinned_blocks, &n.events, &n.streams}) *out++ = v->load();
+  return BBR_OK;
+}
+
 int bbr_timing_reset(bbr_context *c) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
@@ -2524,7 +2402,7 @@ int bbr_timing_summary(bbr_context *c, uint32_t *out_frames, float *out_avg_fram
   uint32_t n = std::min(c->ring_frames, bbr_context::kRingCap);
   double f = 0, g = 0, r = 0, t = 0;
   for (uint32_t i = 0; i < n; ++i) {
-    const hipEvent_t *e = &c->ring[bbr_context::kRingEvents * i];
+    const Event *e = &c->ring[bbr_context::kRingEvents * i];
     float a = 0.f, b = 0.f, d = 0.f, h = 0.f;
     if (c->timing == 1) {
       HIP_TRY(c, hipEventElapsedTime(&a, e[0], frame_end_event(c, i)));
@@ -2609,9 +2487,8 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
     if (c->world > 1 && c->band_rows % (value == 0 ? 64 : 32))
       return fail(c, BBR_ERR_INVALID_ARGUMENT, "tile_mode: band_rows not a multiple of the new tile height");
     c->tile_mode = (int)value;
-    // bins and fragment lists are laid out per tile: drop them so that ensure() re-zeroes the counters
-    for (FrameSlot &s : c->slots) s.release_tile_buffers();
-    c->ov.release_tile_buffers();
+    for (FrameSlot &s : c->slots) drop<TileSized>(s);
+    drop<TileSized>(c->ov);
   } else if (n == "bin_cap") {
     if (value < 1 || value > (1 << 20)) return fail(c, BBR_ERR_INVALID_ARGUMENT, "bin_cap out of range");
     c->bin_cap = (uint32_t)value;
@@ -3228,13 +3105,11 @@ int bbr_selftest_rcp(bbr_context *c, uint32_t lo_bits, uint32_t hi_bits, uint64_
   if (!out_mismatches || hi_bits < lo_bits) return fail(c, BBR_ERR_INVALID_ARGUMENT, "selftest_rcp: bad arguments");
   int rc = drain(c);
   if (rc) return rc;
-  unsigned long long *d = nullptr, h = 0;
-  HIP_TRY(c, hipMalloc(&d, sizeof h));
-  HIP_TRY(c, zero_fill_sync(d, sizeof h));
-  hipLaunchKernelGGL(k_selftest_rcp, dim3(4096), dim3(256), 0, c->geom_stream(), d, lo_bits, hi_bits);
-  hipError_t e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  HIP_TRY(c, e);
+  unsigned long long h = 0;
+  DeviceBuffer<unsigned long long> d;
+  HIP_TRY(c, d.ensure(1, true));
+  hipLaunchKernelGGL(k_selftest_rcp, dim3(4096), dim3(256), 0, c->geom_stream(), d.ptr, lo_bits, hi_bits);
+  HIP_TRY(c, hipMemcpy(&h, d.ptr, sizeof h, hipMemcpyDeviceToHost));
   *out_mismatches = h;
   return BBR_OK;
 }
@@ -3277,33 +3152,28 @@ int bbr_selftest_lines(bbr_context *c, const bbr_tbn_segment *segs, uint32_t n, 
   int rc = drain(c);
   if (rc) return rc;
   const size_t px = (size_t)width * height;
-  TbnSeg *d_segs = nullptr;
-  float *d_depth = nullptr;
-  uint32_t *d_keys = nullptr;
-  auto cleanup = [&]() {
-    if (d_segs) (void)hipFree(d_segs);
-    if (d_depth) (void)hipFree(d_depth);
-    if (d_keys) (void)hipFree(d_keys);
-  };
-  hipError_t e = hipMalloc(&d_segs, std::max<size_t>(n, 1) * sizeof(TbnSeg));
-  if (e == hipSuccess) e = hipMalloc(&d_depth, px * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_keys, px * sizeof(uint32_t));
+  DeviceBuffer<TbnSeg> segs_buf;
+  DeviceBuffer<float> depth_buf;
+  DeviceBuffer<uint32_t> keys_buf;
+  hipError_t e = segs_buf.ensure(std::max<size_t>(n, 1));
+  if (e == hipSuccess) e = depth_buf.ensure(px);
+  if (e == hipSuccess) e = keys_buf.ensure(px);
+  TbnSeg *const d_segs = segs_buf.ptr;
+  float *const d_depth = depth_buf.ptr;
+  uint32_t *const d_keys = keys_buf.ptr;
   if (e == hipSuccess && n) e = upload_sync(d_segs, h.data(), (size_t)n * sizeof(TbnSeg));
   if (e == hipSuccess) e = upload_sync(d_depth, depth, px * sizeof(float));
-  if (e != hipSuccess) {
-    cleanup();
-    HIP_TRY(c, e);
-  }
+  HIP_TRY(c, e);
   hipStream_t st = c->geom_stream();
   rc = BBR_ERR_CAPACITY;
   for (int attempt = 0; attempt < 8 && rc == BBR_ERR_CAPACITY; ++attempt) {
     TbnParams tp;
     int r = tbn_launch_params(c, width, height, tp);
-    if (r) { cleanup(); return r; }
+    if (r) return r;
     if (n) hipLaunchKernelGGL(k_tbn_bin, dim3((n + 255) / 256), dim3(256), 0, st, d_segs, n, tp, c->tbn_pass.d_tile_count.ptr,
                               c->tbn_pass.d_bins.ptr, c->tbn_pass.d_ctr.ptr);
     r = tbn_check_bins(c, st);
-    if (r < 0) { cleanup(); return r; }
+    if (r < 0) return r;
     if (r == 1) continue;
     e = hipMemsetAsync(d_keys, 0, px * sizeof(uint32_t), st);
     if (e == hipSuccess)
@@ -3314,7 +3184,6 @@ int bbr_selftest_lines(bbr_context *c, const bbr_tbn_segment *segs, uint32_t n, 
     if (e == hipSuccess) e = hipMemcpy(out_keys, d_keys, px * sizeof(uint32_t), hipMemcpyDeviceToHost);
     rc = BBR_OK;
   }
-  cleanup();
   HIP_TRY(c, e);
   if (rc) return fail(c, rc, "selftest_lines: bins still overflow after 8 growth steps");
   return BBR_OK;

@@ -66,6 +66,17 @@ def ui_validate(draw, fb_width, fb_height):
     return rc, tuple(box)
 
 
+LIVE_RESOURCES = ("device_allocs", "device_bytes", "pinned_blocks", "events", "streams")
+
+
+def live_resources():
+    """bbr_debug_live_resources: what the library holds alive in this process, over all contexts (no GPU call)"""
+    out = (C.c_uint64 * len(LIVE_RESOURCES))()
+    rc = lib().bbr_debug_live_resources(out)
+    assert rc == 0, rc
+    return dict(zip(LIVE_RESOURCES, (int(x) for x in out)))
+
+
 class Renderer:
     def __init__(self, width, height, device=0):
         self._L = lib()

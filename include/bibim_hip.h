@@ -197,6 +197,11 @@ int bbr_capacity_growths(const bbr_context *ctx, uint32_t *out_count);          
 int bbr_host_timing(const bbr_context *ctx, uint64_t *out_frames, uint64_t *out_submit_ns, uint64_t *out_blocked_ns,
                     uint64_t *out_blocked_frames);
 int bbr_host_timing_reset(bbr_context *ctx);
+/* What the library itself holds alive in this process, over all contexts, without touching the GPU: out[0] device allocations
+ * and out[1] their bytes, out[2] pinned host blocks, out[3] events, out[4] streams.  Memory the caller owns (bbr_device_alloc,
+ * the IPC calls) and the RCCL communicator are not counted.  Every count returns to its earlier value when a context is
+ * destroyed: a host, or a test, can tell from it that nothing leaked. */
+int bbr_debug_live_resources(uint64_t out[5]);
 /* winning primitive (global API-order index, 0xFFFFFFFF = none) and depth per pixel; synchronises.
  * Re-runs the frame once with the visibility dump enabled. */
 int bbr_read_visibility(bbr_context *ctx, uint32_t *prim_host, float *depth_host);
