@@ -99,6 +99,9 @@ SIGNATURES = {
     "bbr_selftest_rcp": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "bbr_read_gbuffer": (C.c_int, [_P, C.c_void_p]),
     "bbr_read_surface": (C.c_int, [_P, C.c_void_p]),
+    "bbr_render_shadow_map": (C.c_int, [_P, C.c_int32, C.c_void_p, C.c_float]),
+    "bbr_read_shadow_map": (C.c_int, [_P, C.c_void_p]),
+    "bbr_read_shadow_mask": (C.c_int, [_P, C.c_void_p]),
     "bbr_read_material_level": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32)]),
     "bbr_read_packed_level": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

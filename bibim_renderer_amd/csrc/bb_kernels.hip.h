@@ -17,6 +17,7 @@
 //   k_sample_merge, k_resolve_merged    option "sample_shading" 0: the fragment lists thinned to one fragment per primitive and
 //                output pixel behind k_raster, and the resolve that knows which sample stands for which
 //   k_resolve_depth    option "depth_resolve": the depth (and winner) of one sample of the block for the output pixel
+//   k_shade_shadow     option "shadow_map": k_shade_aniso's fragment stage with a shadow test in front of one light's iteration
 //
 // Arithmetic contract: every floating-point expression below has the same operand order and the same
 // explicit fmaf() placement as the CPU oracle; the file is compiled with -ffp-contract=off, IEEE
@@ -1961,9 +1962,14 @@ struct ConstLights {
   BB_DEV static int type_of(const CookedLight &c) { return c.type; }
 };
 
-template <typename Lights>
+// `skip(li)`: this fragment takes nothing from light li (option "shadow_map": the caster's iteration of a shadowed fragment).
+// The default skips nothing and leaves no trace in the code.
+struct NoSkip {
+  BB_DEV bool operator()(int) const { return false; }
+};
+template <typename Lights, class Skip = NoSkip>
 BB_DEV float4 light_surface(const ShadeParams &sp, const Lights lights, f3 P, f3 normal, f3 albedo, float metallic,
-                            float roughness, float ao) {
+                            float roughness, float ao, const Skip skip = Skip{}) {
   // per-pixel invariants
   const f3 V = normalize3(sub3(mk3(sp.view_pos[0], sp.view_pos[1], sp.view_pos[2]), P));
   const f3 N = normalize3(normal);
@@ -1987,6 +1993,7 @@ BB_DEV float4 light_surface(const ShadeParams &sp, const Lights lights, f3 P, f3
     const float px = cl.px, py = cl.py, pz = cl.pz, cr = cl.cr, cg = cl.cg, cb = cl.cb;
     const int type = Lights::type_of(cl);
     nxt = lights.get(li + 1 < sp.num_lights ? li + 1 : li);
+    if (skip(li)) continue;  // (as an unknown type, below: nothing)
     f3 L;
     float att;
     if (type == 0 || type == 1) {
@@ -2259,17 +2266,77 @@ BB_DEV f3 sample_map_rgb(const TexDesc &td, float u, float v) {
   return mk3(map_channel(r, 0), map_channel(r, 1), map_channel(r, 2));
 }
 
+// ------------------------------------------------------------------------------------------------
+// Shadow mapping (option "shadow_map" = S > 0, bbr_render_shadow_map; k_shade_shadow).  The rule, in binary32 and in this
+// operand order (restated independently in tests/shadow_reference.py):
+//   map     texel (i, j) = the depth k_raster keeps for pixel (i, j) of an S x S frame of the recorded draws under
+//           gl_Position = (L.proj * L.view) * posWorld (the forward order, proj_view(L), whatever "render_pass" is), with the
+//           frame's own clipper, cull, snap, fill rule, depth test and clamp; an uncovered texel holds the clear value
+//   test    on the P the light loop receives (deferred: after bb_half_round).  M = proj_view(L); c = mat4_mul(M, (P, 1));
+//           !(c.w > 0) -> OUTSIDE.  r = bb_rcp(c.w), h = 0.5f * S; xs = fmaf(c.x * r, h, h), ys = fmaf(c.y * r, h, h);
+//           !(xs >= 0 && xs < S && ys >= 0 && ys < S) -> OUTSIDE (NaN lands here).  i = (int)xs, j = (int)ys;
+//           t = c.z * r + bias; SHADOWED iff map[j][i] > t (a NaN t is not shadowed), otherwise LIT
+//   classes 0 not covered, 1 LIT, 2 SHADOWED, 3 OUTSIDE (bbr_read_shadow_mask)
+//   loop    the iteration of light `light` of a SHADOWED fragment contributes nothing: the `continue` of an unknown light
+//           type.  Every other operation, and the operand order, is light_surface's
+// Deviations: a hard compare, one caster, a point light gets the one frustum the caller chose, and the deferred background
+// colour (k_deferred_background) is evaluated without the test.
+// M and the scalars are kernel arguments (scalar registers); the map costs one 4-byte gather per fragment, and only lanes
+// inside the map address it: i and j lie in [0, S - 1].
+// ------------------------------------------------------------------------------------------------
+enum ShadowClass : int { kShadowNone = 0, kShadowLit = 1, kShadowShadowed = 2, kShadowOutside = 3 };
+struct ShadowArgs {
+  Mat4 m;            // proj_view(L)
+  const float *map;  // S x S depths, row-major
+  uint8_t *mask;     // the DUMP form's second output (bbr_read_shadow_mask): a class per pixel, or nullptr
+  int32_t side;      // S
+  int32_t light;     // the caster's index in the frame's light list
+  float half;        // 0.5f * S
+  float bias;
+};
+struct ShadowSkip {
+  int light;
+  bool shadowed;
+  BB_DEV bool operator()(int li) const { return shadowed && li == light; }
+};
+// What surface_colour asks of its `shadow`: on() classifies the fragment and says which iteration the light loop skips.
+struct NoShadow {
+  BB_DEV NoSkip on(const FrameParams &, f3, bool, int, int) const { return NoSkip{}; }
+};
+template <bool DUMP>
+struct ShadowTest {
+  const ShadowArgs &a;
+  BB_DEV int classify(f3 P) const {
+    const f4 c = mat4_mul(a.m, f4{P.x, P.y, P.z, 1.0f});
+    const float r = bb_rcp(c.w);  // (of a w <= 0 too: not used then)
+    const float side = (float)a.side;
+    const float xs = fmaf(c.x * r, a.half, a.half), ys = fmaf(c.y * r, a.half, a.half);
+    const bool inside = c.w > 0.0f && xs >= 0.0f && xs < side && ys >= 0.0f && ys < side;
+    if (!inside) return kShadowOutside;
+    const int i = (int)xs, j = (int)ys;  // 0 .. S - 1
+    const float t = c.z * r + a.bias;
+    return a.map[(size_t)j * (size_t)a.side + (size_t)i] > t ? kShadowShadowed : kShadowLit;
+  }
+  BB_DEV ShadowSkip on(const FrameParams &fp, f3 P, bool valid, int gx, int gy) const {
+    const int cls = classify(P);
+    if (DUMP && a.mask && valid) a.mask[(size_t)gy * (size_t)fp.width + (size_t)gx] = (uint8_t)cls;
+    return ShadowSkip{a.light, cls == kShadowShadowed};
+  }
+};
+
 // From the filtered surface to the pixel's colour.  Forward: brdf.glsl on the surface.  Deferred: gbuffer.frag:24-32 into
 // four RGBA16F attachments (binary16, round to nearest even), then brdf.frag:12-73 on the pixel's own texel -- fused, the
 // texel only goes to memory when somebody asked to see it, and only then is the height map sampled (height(): the
 // filtered, unrounded value); with gbuffer_view, buffer_visualize.frag:8-12 instead of brdf.frag (recordCommand,
 // src/main.cpp:96-121): the rgb of one attachment.
-template <bool DEFERRED, class Lights, class Height>
+// `shadow` (k_shade_shadow: a ShadowTest) is asked once, on the P the light loop receives.
+template <bool DEFERRED, class Lights, class Height, class Shadow = NoShadow>
 BB_DEV float4 surface_colour(const FrameParams &fp, const ShadeParams &sp, const Lights lights, f3 P, f3 normal, f3 albedo,
                              float metallic, float roughness, float ao, uint2 *__restrict__ gbuffer, bool valid, int gx, int gy,
-                             Height height) {
-  if (!DEFERRED) return light_surface(sp, lights, P, normal, albedo, metallic, roughness, ao);
+                             Height height, const Shadow &shadow = Shadow{}) {
+  if (!DEFERRED) return light_surface(sp, lights, P, normal, albedo, metallic, roughness, ao, shadow.on(fp, P, valid, gx, gy));
   P = mk3(bb_half_round(P.x), bb_half_round(P.y), bb_half_round(P.z));
+  const auto skip = shadow.on(fp, P, valid, gx, gy);
   normal = mk3(bb_half_round(normal.x), bb_half_round(normal.y), bb_half_round(normal.z));
   albedo = mk3(bb_half_round(albedo.x), bb_half_round(albedo.y), bb_half_round(albedo.z));
   metallic = bb_half_round(metallic); roughness = bb_half_round(roughness); ao = bb_half_round(ao);
@@ -2290,7 +2357,7 @@ BB_DEV float4 surface_colour(const FrameParams &fp, const ShadeParams &sp, const
     const f3 shown = fp.gbuffer_view == 0 ? P : (fp.gbuffer_view == 1 ? normal : (fp.gbuffer_view == 2 ? albedo : mk3(metallic, roughness, ao)));
     return make_float4(shown.x, shown.y, shown.z, 1.0f);
   }
-  return light_surface(sp, lights, P, normal, albedo, metallic, roughness, ao);
+  return light_surface(sp, lights, P, normal, albedo, metallic, roughness, ao, skip);
 }
 
 // the pixel's colour into the frame, or (PRESENT) through present_pixel into the presented RGBA8 image
@@ -2764,7 +2831,7 @@ struct AnisoFilter {
 
 // The fragment stage with a footprint: what k_shade_aniso and k_shade_mip are, up to the filter.  One launch shades every
 // item (each wave walks the list with the launch's stride) and every lane gathers its own record.
-template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP, class Filter>
+template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP, class Filter, class Shadow = NoShadow>
 BB_DEV void shade_item_list(
     const uint32_t *__restrict__ items, const uint32_t *__restrict__ item_count,
     const unsigned long long *__restrict__ frags, const uint32_t *__restrict__ frag_count,
@@ -2773,7 +2840,7 @@ BB_DEV void shade_item_list(
     const MaterialDesc *__restrict__ materials, float4 *__restrict__ out,
     uint2 *__restrict__ gbuffer, const SrgbTables *__restrict__ tables, uint32_t *__restrict__ out8,
     Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups, const Filter &filter,
-    float *__restrict__ dump) {
+    float *__restrict__ dump, const Shadow &shadow = Shadow{}) {
   constexpr int TILE_PIXELS = TILE_W * TILE_H;
   const ConstLights lights_c{(ConstCooked)cooked};
   retire_counters(ctr, ctr_done, item_groups);
@@ -2880,7 +2947,7 @@ BB_DEV void shade_item_list(
     }
 
     const float4 color = surface_colour<DEFERRED>(fp, sp, lights_c, mk3(a[2], a[3], a[4]), normal, albedo, metallic, roughness, ao, gbuffer,
-                                                  valid, gx, gy, [&] { return height; });
+                                                  valid, gx, gy, [&] { return height; }, shadow);
     store_colour<PRESENT>(valid, color, o, out, out8, tables, sp);
   }
 }
@@ -2897,6 +2964,24 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
     float *__restrict__ dump) {
   shade_item_list<TILE_W, TILE_H, DEFERRED, PRESENT, DUMP>(items, item_count, frags, frag_count, recs, clip_arena, fp, sp, cooked, materials, out,
                                                            gbuffer, tables, out8, ctr, ctr_done, item_groups, AnisoFilter{max_aniso}, dump);
+}
+
+// k_shade_shadow: the fragment stage of k_shade_aniso ("max_anisotropy" 1 .. 16) with the shadow test in front of the caster's
+// iteration of the light loop (the rule: in front of ShadowTest).  The test is evaluated in surface_colour, behind the filter,
+// where the footprint's registers are dead.  DUMP as in k_shade_aniso, plus the class of every pixel where `shadow.mask` is set.
+template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
+__global__ __launch_bounds__(kShadeThreads) void k_shade_shadow(
+    const uint32_t *__restrict__ items, const uint32_t *__restrict__ item_count,
+    const unsigned long long *__restrict__ frags, const uint32_t *__restrict__ frag_count,
+    const ShadeRec *__restrict__ recs, const ClipSlot *__restrict__ clip_arena,
+    FrameParams fp, ShadeParams sp, const CookedLight *__restrict__ cooked,
+    const MaterialDesc *__restrict__ materials, float4 *__restrict__ out,
+    uint2 *__restrict__ gbuffer, const SrgbTables *__restrict__ tables, uint32_t *__restrict__ out8,
+    Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups, int max_aniso,
+    float *__restrict__ dump, ShadowArgs shadow) {
+  shade_item_list<TILE_W, TILE_H, DEFERRED, PRESENT, DUMP>(items, item_count, frags, frag_count, recs, clip_arena, fp, sp, cooked, materials, out,
+                                                           gbuffer, tables, out8, ctr, ctr_done, item_groups, AnisoFilter{max_aniso}, dump,
+                                                           ShadowTest<DUMP>{shadow});
 }
 
 // ------------------------------------------------------------------------------------------------

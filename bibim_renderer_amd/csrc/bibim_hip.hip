@@ -86,6 +86,7 @@ struct FrameMode {
   bool merged = false;   // ... with option "sample_shading" 0: a sample map, k_sample_merge, k_resolve_merged
   bool depth = false;    // option "overlays": the frame keeps its depth for bbr_draw_overlays (whole frame; n >= 2: a rule)
   int depth_rule = 0;    // n >= 2: option "depth_resolve" (0: no depth is kept; else k_resolve_depth's MODE, VkResolveModeFlagBits)
+  bool shadow = false;   // option "shadow_map" > 0 and a map has been rendered (bbr_render_shadow_map): k_shade_shadow shades
   bool fused = false;    // option "present_fused": the frame is written as presented RGBA8 (the slot's d_present) ...
   bool shade_presents() const { return fused && !resolve; }   // ... by k_raster / k_shade
   bool resolve_presents() const { return fused && resolve; }  // ... by k_resolve (a presented byte cannot be averaged): then
@@ -240,6 +241,16 @@ struct ExtentDumps {
   DeviceBuffer<uint32_t> d_vis_fine_prim;  // ... k_raster's dump of the render extent: bbr_read_sample_visibility)
   DeviceBuffer<float> d_vis_fine_depth;
   DeviceBuffer<uint2> d_gbuffer;  // width*height*4 (four RGBA16F texels per pixel), only while bbr_read_gbuffer runs
+  DeviceBuffer<uint8_t> d_shadow_mask;  // width*height classes, only while bbr_read_shadow_mask runs
+};
+
+// Option "shadow_map": everything the feature owns.  Changing the option's value drops the group; at 0 nothing of it exists.
+struct ShadowOwned {
+  FrameSlot pass;                 // the map pass's own little frame (k_geometry -> k_raster at S x S), like the overlay pass's
+  DeviceBuffer<float> d_map;      // the map: S x S depths, row-major (k_raster's depth store)
+  DeviceBuffer<uint32_t> d_sink;  // S x S words k_raster's background stores go to; nothing reads them
+  ShadowArgs args = {};           // what every frame's k_shade_shadow gets: M, the map, S, the caster's index, the bias
+  bool valid = false;             // a map has been rendered since the option was set
 };
 
 struct bbr_context : ExtentDumps {
@@ -320,6 +331,9 @@ struct bbr_context : ExtentDumps {
   int max_anisotropy = 1;         // option "max_anisotropy": 1 = k_shade's bilinear tap, 2..16 = k_shade_aniso
   int mip_levels = 1;             // option "mip_levels": 1 = no chain, the kernels above; 2..15 = chains of up to that many levels, k_shade_mip
   DeviceBuffer<MipTable> d_mip_tables;  // one per material slot, beside d_materials (only while "mip_levels" >= 2)
+  int shadow_map = 0;             // option "shadow_map": 0 = off, 1..8192 = the side S of the map (k_shade_shadow once a map exists)
+  ShadowOwned shadow;
+  bool dump_shadow_mask = false;  // (bbr_read_shadow_mask: together with dump_surface, the DUMP form of k_shade_shadow)
   bool dump_surface = false;
   DeviceBuffer<float> d_surface;  // width*height*32 floats, only while bbr_read_surface runs
   uint32_t ablate = 0;
@@ -438,6 +452,7 @@ FrameMode frame_mode(const bbr_context *c) {
   m.resolve = c->supersample > 1;
   m.merged = m.resolve && c->sample_shading == 0;
   m.fused = c->present_fused;
+  m.shadow = c->shadow_map > 0 && c->shadow.valid;
   m.depth_rule = m.resolve ? c->depth_resolve : 0;
   // (bbr_draw_overlays is refused on a partition, and with n >= 2 unless option "depth_resolve" names a rule)
   m.depth = c->overlays && c->world == 1 && (!m.resolve || m.depth_rule != 0);
@@ -458,8 +473,11 @@ int refuse_without_depth_rule(bbr_context *c, const char *who, const char *why) 
 }
 // the pair of options that is refused, in whichever order it is asked for: a 3 x 3 block straddles the tiles
 bool refused_pair(int64_t supersample, int64_t sample_shading) { return supersample == 3 && sample_shading == 0; }
+// ... and the other one: pairing them would double the instantiations of the largest kernel (k_shade_mip)
+bool refused_shadow_pair(int64_t mip_levels, int64_t shadow_map) { return mip_levels >= 2 && shadow_map > 0; }
 // the render extent n * width x n * height has the limit of the output extent (bbr_create)
 constexpr int32_t kMaxExtent = 32768;
+constexpr int32_t kMaxShadowMap = 8192;  // option "shadow_map": 256 x 256 tiles of 32 x 32, the launch-slot limit of a frame
 int check_render_extent(bbr_context *c, const char *who, int64_t n, int32_t width, int32_t height) {
   if (n * width <= kMaxExtent && n * height <= kMaxExtent) return BBR_OK;
   return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": supersample x width/height exceeds 32768");
@@ -585,6 +603,7 @@ int ensure_slot_buffers(bbr_context *c, FrameSlot &s, const FrameMode &m) {
   }
   if (c->dump_gbuffer) HIP_TRY(c, c->d_gbuffer.ensure((size_t)c->width * c->height * 4, true));
   if (c->dump_surface) HIP_TRY(c, c->d_surface.ensure((size_t)c->width * c->height * kSurfaceFloats, true));
+  if (c->dump_shadow_mask) HIP_TRY(c, c->d_shadow_mask.ensure((size_t)c->width * c->height, true));
   if (!c->ext_out && m.frame32()) HIP_TRY(c, s.d_frame.ensure(m.out_rows * c->width));
   if (c->dump_vis) {  // (n >= 2: k_raster dumps the render extent; the output extent exists where a rule resolves it)
     if (m.resolve) {
@@ -835,14 +854,19 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
       }, first_item);
     };
     uint32_t *groups = short_frame ? nullptr : s.d_item_groups.ptr;
-    if (c->mip_levels > 1 || c->max_anisotropy > 1 || c->dump_surface) {
-      // option "mip_levels": k_shade_mip; option "max_anisotropy" / bbr_read_surface (the kernels' DUMP forms): k_shade_aniso.
-      // Either is one launch whose waves walk the whole item list.
+    if (mode.shadow || c->mip_levels > 1 || c->max_anisotropy > 1 || c->dump_surface) {
+      // a valid shadow map: k_shade_shadow (never together with "mip_levels" >= 2: refused_shadow_pair); option "mip_levels":
+      // k_shade_mip; option "max_anisotropy" / bbr_read_surface (the kernels' DUMP forms): k_shade_aniso.
+      // Each is one launch whose waves walk the whole item list.
       if (ev) (void)hipEventRecord(ev[3], ss);
       float *surface = c->dump_surface ? c->d_surface.ptr : nullptr;
       with_bool(c->mip_levels > 1, [&](auto mip) { with_bool(c->dump_surface, [&](auto dump) {
         constexpr bool DUMP = decltype(dump)::value;
-        if constexpr (decltype(mip)::value) launch(k_shade_mip<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, c->d_mip_tables.ptr, surface);
+        if (mode.shadow) {
+          ShadowArgs sa = c->shadow.args;
+          sa.mask = (DUMP && c->dump_shadow_mask) ? c->d_shadow_mask.ptr : nullptr;
+          launch(k_shade_shadow<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface, sa);
+        } else if constexpr (decltype(mip)::value) launch(k_shade_mip<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, c->d_mip_tables.ptr, surface);
         else launch(k_shade_aniso<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface);
       }); });
       return;
@@ -1458,6 +1482,141 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
     if (s.d_tile_count.ptr) HIP_TRY(c, zero_fill_sync(s.d_tile_count.ptr, s.d_tile_count.cap * sizeof(uint32_t)));
   }
   return fail(c, BBR_ERR_CAPACITY, "draw_overlays: capacity still exceeded after 8 growth steps");
+}
+
+// ================================================================================================
+// shadow map pass (option "shadow_map"): the recorded draws once more, from the light's view, depth only
+// ================================================================================================
+
+// Synchronous, like the overlay pass, and built like it: the context is drained, the pass has a slot of its own
+// (bbr_context::shadow.pass) and the overlay pass's counter block (both passes clear it before they return), and a capacity
+// that overflows is grown and the pass run again.  The kernels are the frame's own k_geometry and k_raster, untouched:
+// k_raster keeps its depth through the pointer the option "overlays" uses (so every tile takes the general path and every
+// texel is stored, the clear value where nothing is drawn), and its colour stores -- the background of uncovered texels --
+// go as presented words into d_sink, which nothing reads; it makes no items.  The map ignores the partition.
+extern "C" int bbr_render_shadow_map(bbr_context *c, int32_t light_index, const void *light_view_block, float bias) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (c->shadow_map <= 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, "render_shadow_map: option shadow_map is 0");
+  if (light_index < 0 || light_index >= kMaxNumLights) return fail(c, BBR_ERR_INVALID_ARGUMENT, "render_shadow_map: light_index outside 0 .. 99");
+  if (!light_view_block) return fail(c, BBR_ERR_INVALID_ARGUMENT, "render_shadow_map: NULL view block");
+  if (bias != bias) return fail(c, BBR_ERR_INVALID_ARGUMENT, "render_shadow_map: bias is NaN");
+  if (!c->in_frame && !c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, "render_shadow_map: no recorded draws (call it after bbr_draw or after bbr_end_frame)");
+  for (const RecordedDraw &rd : c->draws)
+    if (!c->meshes[rd.mesh].alive || !c->materials[rd.material].alive)
+      return fail(c, BBR_ERR_BAD_HANDLE, "render_shadow_map: a recorded draw's mesh or material was freed");
+  int rc = sync_and_fix(c, nullptr);  // the frames in flight leave the GPU (and the last one is complete)
+  if (rc) return rc;
+  rc = upload_material_table(c);
+  if (rc) return rc;
+  ViewUniformBlock lv;
+  std::memcpy(&lv, light_view_block, sizeof lv);
+
+  ShadowOwned &sh = c->shadow;
+  FrameSlot &s = sh.pass;
+  sh.valid = false;
+  const int32_t S = c->shadow_map;
+  const size_t texels = (size_t)S * (size_t)S;
+  HIP_TRY(c, sh.d_map.ensure(texels));
+  HIP_TRY(c, sh.d_sink.ensure(texels));
+
+  // ---- the recorded draws: [draw descriptors | instances], as the frame's staging holds them ----
+  const size_t draws_bytes = (sizeof(DrawDesc) * std::max<size_t>(c->draws.size(), 1) + 127) & ~(size_t)127;
+  const size_t inst_bytes = sizeof(InstanceBlock) * c->host_instances.size();
+  HIP_TRY(c, s.d_staging.ensure(draws_bytes + std::max<size_t>(inst_bytes, 1)));
+  std::vector<DrawDesc> draws(std::max<size_t>(c->draws.size(), 1));
+  FirstPrims first_prims;
+  const uint32_t n_draws = fill_draw_descs(c, draws.data(), reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + draws_bytes), first_prims);
+  if (n_draws) HIP_TRY(c, upload_sync(s.d_staging.ptr, draws.data(), n_draws * sizeof(DrawDesc)));
+  if (inst_bytes) HIP_TRY(c, upload_sync(s.d_staging.ptr + draws_bytes, c->host_instances.data(), inst_bytes));
+  const DrawDesc *d_draws = reinterpret_cast<const DrawDesc *>(s.d_staging.ptr);
+  const uint32_t n_prims = c->n_prims;
+  const Mat4 pv = proj_view(lv);  // gl_Position = (L.proj * L.view) * posWorld: the forward order, whatever "render_pass" is
+
+  for (int attempt = 0; attempt < 8; ++attempt) {
+    FrameParams fp = make_params(c);  // (the capacities; again after a growth)
+    fp.width = fp.height = S;
+    fp.half_w = fp.half_h = 0.5f * (float)S;
+    fp.tiles_x = (S + c->tile_w() - 1) / c->tile_w();
+    fp.tiles_y = (S + c->tile_h() - 1) / c->tile_h();
+    fp.rank = 0;
+    fp.world = 1;  // every rank renders the whole map
+    fp.band_tiles = fp.tiles_y;
+    fp.shard_rows = S;
+    fp.deferred = 0;
+    fp.gbuffer_view = -1;
+    rc = ensure_pass_buffers(c, s, n_prims, (size_t)fp.tiles_x * fp.tiles_y);
+    if (rc) return rc;
+    s.ctr_index = bbr_context::kMaxSlots;
+    Counters *ctr = c->d_counters.ptr + s.ctr_index;
+    hipStream_t st = c->shade_stream();
+    auto launch = [&](auto tw, auto th) {
+      constexpr int TW = decltype(tw)::value, TH = decltype(th)::value;
+      if (n_prims)
+        hipLaunchKernelGGL((k_geometry<TW, TH>), dim3((n_prims + 255) / 256), dim3(256), 0, st, d_draws, n_draws, n_prims, first_prims,
+                           s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv, lv.view, fp, s.d_clip.ptr, s.d_broad.ptr,
+                           c->d_materials.ptr, s.d_block_stats.ptr, (uint32_t *)nullptr);
+      hipLaunchKernelGGL((k_raster<TW, TH>), dim3(fp.tiles_x, fp.tiles_y), dim3(kTileThreads), 0, st, s.d_tile_count.ptr, ctr,
+                         s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, (float4 *)nullptr, fp, s.d_tris.ptr, s.d_clip.ptr,
+                         s.d_bins.ptr, (uint32_t *)nullptr, (float *)nullptr, (const float4 *)nullptr, sh.d_map.ptr,
+                         (uint32_t *)nullptr, sh.d_sink.ptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                         (const Light *)nullptr, 0, (CookedLight *)nullptr, (const uint32_t *)nullptr);
+    };
+    if (c->tile_mode == 0) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{});
+    else launch(std::integral_constant<int, 32>{}, std::integral_constant<int, 32>{});
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    Counters h = {};
+    HIP_TRY(c, hipMemcpy(&h, ctr, sizeof h, hipMemcpyDeviceToHost));
+    HIP_TRY(c, zero_fill_sync(ctr, sizeof(Counters)));  // (the pass is synchronous: cleared here, not by a kernel)
+    if (!h.overflow) {
+      sh.args.m = pv;
+      sh.args.map = sh.d_map.ptr;
+      sh.args.mask = nullptr;
+      sh.args.side = S;
+      sh.args.light = light_index;
+      sh.args.half = 0.5f * (float)S;
+      sh.args.bias = bias;
+      sh.valid = true;
+      return BBR_OK;
+    }
+    // a triangle did not fit: the map is incomplete.  Grow and render all of it again.
+    rc = apply_growth(c, h.overflow, h.bin_need, h.n_broad, h.n_clip_slots);
+    if (rc) return rc;
+    if (s.d_tile_count.ptr) HIP_TRY(c, zero_fill_sync(s.d_tile_count.ptr, s.d_tile_count.cap * sizeof(uint32_t)));
+  }
+  return fail(c, BBR_ERR_CAPACITY, "render_shadow_map: capacity still exceeded after 8 growth steps");
+}
+
+extern "C" int bbr_read_shadow_map(bbr_context *c, float *host) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_map: NULL");
+  if (c->shadow_map <= 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_map: option shadow_map is 0");
+  if (!c->shadow.valid) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_shadow_map: no map rendered (bbr_render_shadow_map)");
+  HIP_TRY(c, hipMemcpy(host, c->shadow.d_map.ptr, (size_t)c->shadow_map * c->shadow_map * sizeof(float), hipMemcpyDeviceToHost));
+  return BBR_OK;
+}
+
+// the class of every pixel of the last frame: the DUMP form of k_shade_shadow (with it the surface dump, which is dropped)
+extern "C" int bbr_read_shadow_mask(bbr_context *c, uint8_t *host) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_mask: NULL");
+  if (int rc = refuse_supersampled(c, "read_shadow_mask")) return rc;
+  if (!frame_mode(c).shadow) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_mask: no shadow map in use (option shadow_map, bbr_render_shadow_map)");
+  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_shadow_mask: nothing rendered");
+  if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_mask: not available on a partitioned context");
+  c->dump_surface = true;
+  int rc = rerender_with(c, &bbr_context::dump_shadow_mask);
+  c->dump_surface = false;
+  if (rc == BBR_OK) {
+    hipError_t e = hipMemcpy(host, c->d_shadow_mask.ptr, (size_t)c->width * c->height, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(c, BBR_ERR_HIP, std::string("read_shadow_mask: ") + hipGetErrorString(e));
+  }
+  c->d_shadow_mask.release();  // (uncovered pixels are the zeros of a fresh buffer)
+  c->d_surface.release();
+  return rc;
 }
 
 // ================================================================================================
@@ -2489,6 +2648,7 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
     c->tile_mode = (int)value;
     for (FrameSlot &s : c->slots) drop<TileSized>(s);
     drop<TileSized>(c->ov);
+    drop<TileSized>(c->shadow.pass);  // (the map itself has no tiles: it stays)
   } else if (n == "bin_cap") {
     if (value < 1 || value > (1 << 20)) return fail(c, BBR_ERR_INVALID_ARGUMENT, "bin_cap out of range");
     c->bin_cap = (uint32_t)value;
@@ -2504,6 +2664,8 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
     c->max_anisotropy = (int)value;
   } else if (n == "mip_levels") {
     if (value < 1 || value > kMaxMipLevels) return fail(c, BBR_ERR_INVALID_ARGUMENT, "mip_levels: 1 (no chain) .. 15");
+    if (refused_shadow_pair(value, c->shadow_map))
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, "mip_levels: >= 2 is not available with option shadow_map > 0 (k_shade_shadow has no trilinear form)");
     // every chain is built for the option's value: drop them all, then build the new ones of every live material
     for (Material &m : c->materials) free_chain(m);
     c->mip_levels = (int)value;
@@ -2554,6 +2716,16 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
         for (FrameSlot &s : c->slots) s.d_fine_depth.release();
         forget_current_frame(c);
       }
+    }
+  } else if (n == "shadow_map") {
+    // the side of the map; a change drops the map and its pass buffers (the context is drained): frames are unshadowed again
+    // until bbr_render_shadow_map has rendered the new one
+    if (value < 0 || value > kMaxShadowMap) return fail(c, BBR_ERR_INVALID_ARGUMENT, "shadow_map: 0 (off) or the side of the map, 1 .. 8192");
+    if (refused_shadow_pair(c->mip_levels, value))
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, "shadow_map: > 0 is not available with option mip_levels >= 2 (k_shade_shadow has no trilinear form)");
+    if ((int)value != c->shadow_map) {
+      c->shadow_map = (int)value;
+      c->shadow = ShadowOwned();
     }
   } else if (n == "present_fused") {
     c->present_fused = value != 0;

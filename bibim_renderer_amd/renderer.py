@@ -86,6 +86,7 @@ class Renderer:
             raise BibimError(rc, (self._L.bbr_last_error(None) or b"").decode())
         self.width, self.height = int(width), int(height)
         self.supersample = 1  # option "supersample": the fine frame is supersample x the output extent
+        self.shadow_map = 0   # option "shadow_map": the side of the map read_shadow_map returns
         self._scenes = weakref.WeakSet()  # host-shim scenes hold meshes of this context: they must go first
 
     # -- plumbing --
@@ -224,6 +225,8 @@ class Renderer:
         self._check(self._L.bbr_set_option(self._ctx, name.encode(), int(value)))
         if name == "supersample":
             self.supersample = int(value)
+        if name == "shadow_map":
+            self.shadow_map = int(value)
 
     def last_frame_time_ms(self):
         a, b = C.c_float(), C.c_float()
@@ -258,6 +261,29 @@ class Renderer:
         "surface read-back"); re-renders the last frame"""
         out = np.empty((self.height, self.width, 32), np.float32)
         self._check(self._L.bbr_read_surface(self._ctx, _ptr(out)))
+        return out
+
+    # -- shadow mapping (option "shadow_map" = S > 0; include/bibim_hip.h, "shadow mapping") --
+    def render_shadow_map(self, light_index, light_view, bias=0.0):
+        """render the S x S depth map of the recorded draws from `light_view` (a 144-byte view block: view and proj are used) and
+        make light `light_index` the caster of every frame submitted from now on; synchronous.  Inside a frame after the draws,
+        or after end_frame()"""
+        b = np.ascontiguousarray(light_view)
+        assert b.nbytes == 144
+        self._check(self._L.bbr_render_shadow_map(self._ctx, int(light_index), _ptr(b), float(bias)))
+
+    def read_shadow_map(self):
+        """the shadow map, [S, S] float32"""
+        s = max(int(self.shadow_map), 0)
+        out = np.empty(max(s * s, 1), np.float32)  # (s = 0: the call refuses)
+        self._check(self._L.bbr_read_shadow_map(self._ctx, _ptr(out)))
+        return out.reshape(s, s)
+
+    def read_shadow_mask(self):
+        """the shadow class of every pixel of the last frame, [h, w] uint8: 0 not covered, 1 lit, 2 shadowed, 3 outside the
+        map; re-renders the last frame"""
+        out = np.empty((self.height, self.width), np.uint8)
+        self._check(self._L.bbr_read_shadow_mask(self._ctx, _ptr(out)))
         return out
 
     def read_material_level(self, material, map_index, level):

@@ -262,7 +262,14 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            (a 16384 x 3 set: half again, not a third).  Frames are then
  *                            shaded by k_shade_mip, whatever "max_anisotropy" is (the rule: "mip chains" below).  The TBN
  *                            overlay's vertex-stage fetch and the GUI sampler have no derivatives and stay on level 0.
- *                            Anything else: INVALID_ARGUMENT
+ *                            Anything else: INVALID_ARGUMENT.  Refused (INVALID_ARGUMENT) at >= 2 while "shadow_map" > 0
+ *   "shadow_map" 0..8192     shadow mapping, one caster per context ("shadow mapping" below).  0 (default): off -- no kernel
+ *                            of the option runs, no buffer of it exists.  S >= 1: the side of a square binary32 depth map
+ *                            that bbr_render_shadow_map renders; until it has, frames are rendered by the unshadowed
+ *                            kernels exactly as with 0, afterwards by k_shade_shadow.  Changing the value drains the
+ *                            context and drops the map and its pass buffers.  Anything else: INVALID_ARGUMENT, the option
+ *                            unchanged.  Refused (INVALID_ARGUMENT) at > 0 while "mip_levels" >= 2, in whichever order the
+ *                            two are set: k_shade_shadow has no trilinear form
  *   "supersample" 1..4       n x n supersampling: rasterizationSamples = n^2 on a regular grid, sampleShadingEnable with
  *                            minSampleShading = 1 and VK_RESOLVE_MODE_AVERAGE (the reference pins 1 sample,
  *                            src/render.cpp:1104-1112).  1 (default): nothing changes, no kernel of the option runs.
@@ -438,6 +445,46 @@ int bbr_read_surface(bbr_context *ctx, float *out);
 int bbr_read_material_level(bbr_context *ctx, int32_t material, int32_t map, int32_t level, uint8_t *out_rgba8, uint64_t capacity,
                             int32_t *out_width, int32_t *out_height);
 int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uint8_t *out, uint64_t capacity, uint64_t *out_bytes);
+
+/* ---- shadow mapping (option "shadow_map" = S > 0) ----
+ * One shadow-casting light per context: a depth map of the recorded draws from a view the caller supplies, and a depth test
+ * in front of that light's iteration of the light loop.  The rule, in binary32, without contraction, in this operand order
+ * (tests/shadow_reference.py):
+ *   map      texel (i, j) is the depth the rasteriser keeps for pixel (i, j) of an S x S frame of the recorded draws under
+ *            gl_Position = (L.proj * L.view) * posWorld -- the forward order, whatever "render_pass" is -- with the frame's
+ *            own fixed-function state (clipper, back-face cull, 1/256 snap, top-left rule, GREATER_OR_EQUAL, depth clamp).
+ *            An uncovered texel holds the clear value 0.  The map ignores the partition: every rank renders all of it.
+ *   test     per fragment, on the position P the light loop receives (deferred: P rounded to binary16).  M = L.proj *
+ *            L.view as the vertex stage evaluates it (column j = proj * view[j], an fma chain); c = M * (P, 1) in the same
+ *            chain.  !(c.w > 0): OUTSIDE.  r = the correctly rounded 1 / c.w, h = 0.5f * S, xs = fmaf(c.x * r, h, h), ys =
+ *            fmaf(c.y * r, h, h).  !(xs >= 0 && xs < S && ys >= 0 && ys < S): OUTSIDE (NaN lands here).  i = (int)xs, j =
+ *            (int)ys, t = c.z * r + bias.  SHADOWED iff map[j][i] > t (a NaN t is not shadowed); otherwise LIT.
+ *   classes  as bbr_read_shadow_mask reports them: 0 not covered, 1 LIT, 2 SHADOWED, 3 OUTSIDE
+ *   loop     the iteration of light `light_index` of a SHADOWED fragment contributes nothing, like a light of unknown type;
+ *            everything else is the light loop's.  A light_index >= NumLights shadows nothing.
+ * Deviations: a hard compare (no filtering of the map), one caster, a point light gets the one frustum the caller chose, and
+ * the deferred background colour is evaluated without the test.
+ *
+ * bbr_render_shadow_map renders the map from `light_view_block` (144 bytes in ViewUniformBlock layout; view and proj are
+ * used, the rest is ignored).  It renders the recorded draws and is valid inside a frame after the bbr_draw calls (the draws
+ * recorded so far) and after bbr_end_frame (the last recorded frame's); otherwise BBR_ERR_NOT_IN_FRAME.  It is synchronous,
+ * like bbr_draw_overlays: it drains the frames in flight, grows a capacity that overflows and renders again, and returns
+ * when the map is complete.  From then on every submitted frame (bbr_end_frame, bbr_replay_frame, the re-renders of the
+ * read-backs) uses the map, the index and the bias, until the next call, a change of the option or bbr_destroy; bbr_resize
+ * keeps them.  BBR_ERR_INVALID_ARGUMENT: the option is 0, light_index outside [0, 100), a NULL block, a NaN bias.
+ * Works with both tile modes, both render passes, "present_fused", "max_anisotropy", "supersample" with either
+ * "sample_shading" (the test runs per fine fragment), a partition, up to four frames in flight and bbr_replay_frame.
+ *
+ * Read-backs, in the family of the other diagnostics:
+ *   bbr_read_shadow_map   the S x S map, row-major.  INVALID_ARGUMENT while the option is 0, BBR_ERR_NOT_IN_FRAME before a
+ *                         map has been rendered
+ *   bbr_read_shadow_mask  width*height bytes: the class of every pixel of the last frame.  Re-renders it like
+ *                         bbr_read_surface, with the same refusals ("supersample" >= 2, a partition), and INVALID_ARGUMENT
+ *                         while no map is in use
+ * bbr_read_surface and bbr_read_gbuffer keep working while a map is in use: the re-rendered frame is the shadowed one. */
+int bbr_render_shadow_map(bbr_context *ctx, int32_t light_index, const void *light_view_block /* 144 B */, float bias);
+int bbr_read_shadow_map(bbr_context *ctx, float *out);
+int bbr_read_shadow_mask(bbr_context *ctx, uint8_t *out);
 
 /* ---- primitive-record read-back ----
  * What the vertex stage (k_geometry: forward_brdf.vert / gbuffer.vert, clip test, viewport, snap, triangle setup) wrote

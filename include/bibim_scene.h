@@ -193,6 +193,13 @@ void fillUniforms(const SceneBase &scene, const FreeLookCamera &cam, const Frame
 int drawFrame(bbr_context *ctx, SceneBase &scene, const FreeLookCamera &cam, const FrameSettings &settings,
               int32_t material, int width, int height, float dt = 0.f);
 
+// Shadow mapping (option "shadow_map" > 0, include/bibim_hip.h): render the map of the last drawn frame's draws from
+// `lightView` (ViewMat and ProjMat are used) and make scene light `light` the caster of the frames that follow.
+// Synchronous; returns a bbr_status.
+inline int renderShadowMap(bbr_context *ctx, int32_t light, const ViewUniformBlock &lightView, float bias) {
+  return bbr_render_shadow_map(ctx, light, &lightView, bias);
+}
+
 }  // namespace bb
 
 extern "C" {
