@@ -132,6 +132,7 @@ SIGNATURES = {
     "bbr_push_shard": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int32), _P]),
     "bbr_push_state": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "bbr_capacity_growths": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "bbr_static_record_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bbr_host_timing": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bbr_host_timing_reset": (C.c_int, [_P]),
     "bbr_debug_live_resources": (C.c_int, [C.POINTER(C.c_uint64)]),

@@ -832,13 +832,17 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
       // triangle, the record's planes and posWorld.  Only two values (rw2, posWorld.z of vertex 2: the first dwords of 16-byte
       // pieces that the attributes complete) and the tile range wait for the loads with the lane. ----
       const bool keep = !BB_ABLATE(64u);
+      // The light path: the host says (kDrawStaticPresent) that the camera-independent part of the draw's records -- uv, the
+      // material binding, the whole body -- is in `recs` already, bit for bit what this block would store (k_record_static).
+      // Such a lane asks for no attributes, computes no N, T, B and stores the planes, rw2 and clip_base only.
+      const bool light = !OVERLAY && (draw.flags & kDrawStaticPresent) != 0u;
       if (keep) {
         if (survives) tris[prim] = t;
         // planes of the unclipped triangle; zero for a primitive that goes through the clipper (its sub-triangles have their
         // own): t is written in the unclipped branch only, so there it still holds the zeros it was initialised with
         rec_store4(rec, kRecPlanes, (uint32_t)t.X0, (uint32_t)t.Y0, __float_as_uint(t.l1dx), __float_as_uint(t.l1dy));
         rec_store4(rec, kRecPlanes + 4, t.l2dx, t.l2dy, t.rw0, t.rw1);
-        if (!OVERLAY) {
+        if (!OVERLAY && !light) {
           // body varyings 0..2 (posWorld), varying-major: vary[j][k] = pw[k][j]
           rec_store4(rec, kRecBody, pw[0][0], pw[1][0], pw[2][0], pw[0][1]);
           rec_store4(rec, kRecBody + 4, pw[1][1], pw[2][1], pw[0][2], pw[1][2]);
@@ -852,71 +856,81 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
         else binned = true;
         cls = raster_class(frame_box(t, fp), tri_span(tri_core(t)));  // (the box again, not kept from the setup: two registers)
       }
-      float nrm[3][3], tng[3][3], uv[3][2], im_[3][3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        uv[k][0] = src.v[k]->uv[0]; uv[k][1] = src.v[k]->uv[1];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { nrm[k][c] = src.v[k]->normal[c]; tng[k][c] = src.v[k]->tangent[c]; }
-      }
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int cc = 0; cc < 3; ++cc) im_[r][cc] = src.ib->inv_model.M[r][cc];
-      asm volatile("" :: "v"(im_[0][0]), "v"(im_[0][1]), "v"(im_[0][2]), "v"(im_[1][0]), "v"(im_[1][1]), "v"(im_[1][2]), "v"(im_[2][0]),
-                   "v"(im_[2][1]), "v"(im_[2][2]), "v"(nrm[0][0]), "v"(nrm[1][0]), "v"(nrm[2][0]), "v"(tng[0][0]), "v"(tng[1][0]),
-                   "v"(tng[2][0]), "v"(uv[0][0]), "v"(uv[1][0]), "v"(uv[2][0]) : "memory");
-      if (OVERLAY) {
-        // ib.inv_model row 0 = the light's colour, or the gizmo's viewMat whose upper 3x3 turns the normals
-        // (gizmo.vert:27).  draw.material is the program: 1 marker, 2 gizmo (not an index into the material table).
-        // Varyings 0, 1 sit in the head, 2..5 in the body.
-        float o[3][6];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-#pragma unroll
-          for (int j = 0; j < 6; ++j) o[k][j] = 0.0f;
-          if (draw.material == 1u) {
-            o[k][0] = im_[0][0]; o[k][1] = im_[0][1]; o[k][2] = im_[0][2];
-          } else {
-            f3 n = ld3(nrm[k]);
-            o[k][0] = tng[k][0]; o[k][1] = tng[k][1]; o[k][2] = tng[k][2];  // the gizmo mesh keeps its colour there
-            o[k][3] = fmaf(im_[2][0], n.z, fmaf(im_[1][0], n.y, im_[0][0] * n.x));
-            o[k][4] = fmaf(im_[2][1], n.z, fmaf(im_[1][1], n.y, im_[0][1] * n.x));
-            o[k][5] = fmaf(im_[2][2], n.z, fmaf(im_[1][2], n.y, im_[0][2] * n.x));
-          }
-        }
+      if (light) {
+        // (clip_base every frame: a primitive the clipper took last frame and leaves alone now is reset; the clipper patches
+        //  it below exactly as on the full path)
         if (keep) {
-          rec_store_head_rest(rec, rw2, o[0], o[1], o[2], 0u, nullptr, draw.material);
-          rec_store4(rec, kRecBody, o[0][2], o[1][2], o[2][2], o[0][3]);
-          rec_store4(rec, kRecBody + 4, o[1][3], o[2][3], o[0][4], o[1][4]);
-          rec_store4(rec, kRecBody + 8, o[2][4], o[0][5], o[1][5], o[2][5]);
-#pragma unroll
-          for (int q = kRecBody + 12; q < kShadeRecDwords; q += 4) rec_store4(rec, q, 0.0f, 0.0f, 0.0f, 0.0f);
+          uint32_t *const dw = reinterpret_cast<uint32_t *>(rec);
+          dw[kRecHeadRest] = __float_as_uint(rw2);
+          dw[kRecHeadRest + 11] = kNotClipped;
         }
       } else {
-        // (the material's packed form travels in the draw descriptor: no load of the material table here)
-        if (keep) rec_store_head_rest(rec, rw2, uv[0], uv[1], uv[2], draw.packed ? draw.packed_dims : 0u, draw.packed, draw.material);
-        // Body varyings 3..11, varying-major like the rest of the body: N of the three vertices, then T, then B, each
-        // 16-byte piece stored when its last value exists (the interleaving holds the kernel at 64 registers).
-        f3 N[3], T[3], B[3];
+        float nrm[3][3], tng[3][3], uv[3][2], im_[3][3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) N[k] = normal_dir(im_, ld3(nrm[k]));
-        if (keep) {
-          rec_store4(rec, kRecBody + 8, pwz2, N[0].x, N[1].x, N[2].x);
-          rec_store4(rec, kRecBody + 12, N[0].y, N[1].y, N[2].y, N[0].z);
+        for (int k = 0; k < 3; ++k) {
+          uv[k][0] = src.v[k]->uv[0]; uv[k][1] = src.v[k]->uv[1];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) { nrm[k][c] = src.v[k]->normal[c]; tng[k][c] = src.v[k]->tangent[c]; }
         }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) T[k] = normal_dir(im_, ld3(tng[k]));
-        if (keep) {
-          rec_store4(rec, kRecBody + 16, N[1].z, N[2].z, T[0].x, T[1].x);
-          rec_store4(rec, kRecBody + 20, T[2].x, T[0].y, T[1].y, T[2].y);
-        }
+        for (int r = 0; r < 3; ++r)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) B[k] = cross3(N[k], T[k]);
-        if (keep) {
-          rec_store4(rec, kRecBody + 24, T[0].z, T[1].z, T[2].z, B[0].x);
-          rec_store4(rec, kRecBody + 28, B[1].x, B[2].x, B[0].y, B[1].y);
-          rec_store4(rec, kRecBody + 32, B[2].y, B[0].z, B[1].z, B[2].z);
+          for (int cc = 0; cc < 3; ++cc) im_[r][cc] = src.ib->inv_model.M[r][cc];
+        asm volatile("" :: "v"(im_[0][0]), "v"(im_[0][1]), "v"(im_[0][2]), "v"(im_[1][0]), "v"(im_[1][1]), "v"(im_[1][2]), "v"(im_[2][0]),
+                     "v"(im_[2][1]), "v"(im_[2][2]), "v"(nrm[0][0]), "v"(nrm[1][0]), "v"(nrm[2][0]), "v"(tng[0][0]), "v"(tng[1][0]),
+                     "v"(tng[2][0]), "v"(uv[0][0]), "v"(uv[1][0]), "v"(uv[2][0]) : "memory");
+        if (OVERLAY) {
+          // ib.inv_model row 0 = the light's colour, or the gizmo's viewMat whose upper 3x3 turns the normals
+          // (gizmo.vert:27).  draw.material is the program: 1 marker, 2 gizmo (not an index into the material table).
+          // Varyings 0, 1 sit in the head, 2..5 in the body.
+          float o[3][6];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) o[k][j] = 0.0f;
+            if (draw.material == 1u) {
+              o[k][0] = im_[0][0]; o[k][1] = im_[0][1]; o[k][2] = im_[0][2];
+            } else {
+              f3 n = ld3(nrm[k]);
+              o[k][0] = tng[k][0]; o[k][1] = tng[k][1]; o[k][2] = tng[k][2];  // the gizmo mesh keeps its colour there
+              o[k][3] = fmaf(im_[2][0], n.z, fmaf(im_[1][0], n.y, im_[0][0] * n.x));
+              o[k][4] = fmaf(im_[2][1], n.z, fmaf(im_[1][1], n.y, im_[0][1] * n.x));
+              o[k][5] = fmaf(im_[2][2], n.z, fmaf(im_[1][2], n.y, im_[0][2] * n.x));
+            }
+          }
+          if (keep) {
+            rec_store_head_rest(rec, rw2, o[0], o[1], o[2], 0u, nullptr, draw.material);
+            rec_store4(rec, kRecBody, o[0][2], o[1][2], o[2][2], o[0][3]);
+            rec_store4(rec, kRecBody + 4, o[1][3], o[2][3], o[0][4], o[1][4]);
+            rec_store4(rec, kRecBody + 8, o[2][4], o[0][5], o[1][5], o[2][5]);
+#pragma unroll
+            for (int q = kRecBody + 12; q < kShadeRecDwords; q += 4) rec_store4(rec, q, 0.0f, 0.0f, 0.0f, 0.0f);
+          }
+        } else {
+          // (the material's packed form travels in the draw descriptor: no load of the material table here)
+          if (keep) rec_store_head_rest(rec, rw2, uv[0], uv[1], uv[2], draw.packed ? draw.packed_dims : 0u, draw.packed, draw.material);
+          // Body varyings 3..11, varying-major like the rest of the body: N of the three vertices, then T, then B, each
+          // 16-byte piece stored when its last value exists (the interleaving holds the kernel at 64 registers).
+          f3 N[3], T[3], B[3];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) N[k] = normal_dir(im_, ld3(nrm[k]));
+          if (keep) {
+            rec_store4(rec, kRecBody + 8, pwz2, N[0].x, N[1].x, N[2].x);
+            rec_store4(rec, kRecBody + 12, N[0].y, N[1].y, N[2].y, N[0].z);
+          }
+#pragma unroll
+          for (int k = 0; k < 3; ++k) T[k] = normal_dir(im_, ld3(tng[k]));
+          if (keep) {
+            rec_store4(rec, kRecBody + 16, N[1].z, N[2].z, T[0].x, T[1].x);
+            rec_store4(rec, kRecBody + 20, T[2].x, T[0].y, T[1].y, T[2].y);
+          }
+#pragma unroll
+          for (int k = 0; k < 3; ++k) B[k] = cross3(N[k], T[k]);
+          if (keep) {
+            rec_store4(rec, kRecBody + 24, T[0].z, T[1].z, T[2].z, B[0].x);
+            rec_store4(rec, kRecBody + 28, B[1].x, B[2].x, B[0].y, B[1].y);
+            rec_store4(rec, kRecBody + 32, B[2].y, B[0].z, B[1].z, B[2].z);
+          }
         }
       }
     }
@@ -983,6 +997,65 @@ __global__ __launch_bounds__(256) void k_geometry(const DrawDesc *__restrict__ d
       block_stats[blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6)] = BlockStats{n_survivors + clipped_raster, n_clipped, refs};
   }
   BB_STAMP(5);
+}
+
+// The camera-independent part of the records of ONE draw of the main pass (draws[d]): uv, the material binding and the body
+// -- dwords 9..18 and 20..55 of ShadeRec; the planes, rw0..2 (0..8) and clip_base (19) are k_geometry's, every frame.  One thread
+// per primitive, culled ones too (a primitive that faces away now may face the camera in the next frame).  The values come
+// from the functions k_geometry's full path calls on the same operands, hence the same bits.  Queued by the host once per
+// frame slot when a draw's key has repeated (bibim_hip.hip, static_records); k_geometry then takes its light path for the draw.
+constexpr int kRecordStaticThreads = 256;
+__global__ __launch_bounds__(kRecordStaticThreads) void k_record_static(const DrawDesc *__restrict__ draws, uint32_t d,
+                                                                        ShadeRec *__restrict__ recs) {
+  const DrawDesc draw = draws[d];
+  const uint32_t local = blockIdx.x * blockDim.x + threadIdx.x;
+  if (local >= draw.n_instances * draw.tris_per_instance) return;
+  const uint32_t prim = draw.first_prim + local;
+  const PrimSource src = prim_source(draw, prim);
+  float pos[3][3];
+  Mat4 model;
+  load_positions(src, pos, model);
+  float im_[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int cc = 0; cc < 3; ++cc) im_[r][cc] = src.ib->inv_model.M[r][cc];
+  ShadeRec *const rec = recs + prim;
+  uint32_t *const dw = reinterpret_cast<uint32_t *>(rec);
+  // the head behind rw2: uv of the three vertices, packed_dims, packed, material (rec_store_head_rest without its two ends)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    dw[kRecHeadRest + 1 + 2 * k] = __float_as_uint(src.v[k]->uv[0]);
+    dw[kRecHeadRest + 2 + 2 * k] = __float_as_uint(src.v[k]->uv[1]);
+  }
+  const unsigned long long packed_bits = (unsigned long long)reinterpret_cast<uintptr_t>(draw.packed);
+  dw[kRecHeadRest + 7] = draw.packed ? draw.packed_dims : 0u;
+  dw[kRecHeadRest + 8] = (uint32_t)packed_bits;
+  dw[kRecHeadRest + 9] = (uint32_t)(packed_bits >> 32);
+  dw[kRecHeadRest + 10] = draw.material;
+  // the body, varying-major: posWorld, N, T, B of the three vertices
+  f3 N[3], T[3], B[3];
+  float pw[3][3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const f4 w = vertex_world(model, pos[k]);
+    pw[k][0] = w.x; pw[k][1] = w.y; pw[k][2] = w.z;
+    float nrm[3], tng[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { nrm[c] = src.v[k]->normal[c]; tng[c] = src.v[k]->tangent[c]; }
+    N[k] = normal_dir(im_, ld3(nrm));
+    T[k] = normal_dir(im_, ld3(tng));
+    B[k] = cross3(N[k], T[k]);
+  }
+  rec_store4(rec, kRecBody, pw[0][0], pw[1][0], pw[2][0], pw[0][1]);
+  rec_store4(rec, kRecBody + 4, pw[1][1], pw[2][1], pw[0][2], pw[1][2]);
+  rec_store4(rec, kRecBody + 8, pw[2][2], N[0].x, N[1].x, N[2].x);
+  rec_store4(rec, kRecBody + 12, N[0].y, N[1].y, N[2].y, N[0].z);
+  rec_store4(rec, kRecBody + 16, N[1].z, N[2].z, T[0].x, T[1].x);
+  rec_store4(rec, kRecBody + 20, T[2].x, T[0].y, T[1].y, T[2].y);
+  rec_store4(rec, kRecBody + 24, T[0].z, T[1].z, T[2].z, B[0].x);
+  rec_store4(rec, kRecBody + 28, B[1].x, B[2].x, B[0].y, B[1].y);
+  rec_store4(rec, kRecBody + 32, B[2].y, B[0].z, B[1].z, B[2].z);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -175,9 +175,12 @@ struct DrawDesc {
   // filled in by the host, so that k_geometry has no dependent load of the material table in front of its record stores
   const uint8_t *packed;
   uint32_t packed_dims;  // width | height << 16
-  uint32_t pad;
+  uint32_t flags;        // kDrawStaticPresent, or 0
 };
 static_assert(sizeof(DrawDesc) == 56, "DrawDesc");
+// The camera-independent part of every record of the draw (uv, the material binding, the body: dwords 9..18 and 20..55 of
+// ShadeRec) is in the slot's record buffer already (k_record_static): k_geometry writes the planes, rw0..2 and clip_base only.
+constexpr uint32_t kDrawStaticPresent = 1u;
 // first_prim of draws 1 .. kInlineFirstPrims travel as kernel arguments (0xFFFFFFFF: no such draw): k_geometry finds its
 // draw without a load for frames of up to kInlineFirstPrims + 1 draws
 constexpr int kInlineFirstPrims = 3;

@@ -156,8 +156,25 @@ struct ExtentSized {
   DeviceBuffer<uint32_t> d_present;   // RGBA8 presented image of this slot's frame (bbr_present)
 };
 
+// Option "static_records": what a slot knows about the camera-independent part of the records in its d_attrs.  One entry
+// per live draw of the frame last submitted to the slot, in draw order: the descriptor k_geometry was given (its instance
+// blocks are still in the slot's pinned staging, where `key.instances` points in the device copy) and whether k_record_static
+// has written the draw's static part since.  Whatever destroys or replaces record bytes forgets the entries.
+struct StaticRecords {
+  struct Draw {
+    DrawDesc key;  // (flags 0)
+    bool filled;
+  };
+  std::vector<Draw> draws;
+  uint64_t epoch = 0;  // bbr_context::resource_epoch the keys were taken under
+  // capacities of d_attrs and of the staging the keys speak of: both buffers only ever grow, and growing loses what they held
+  size_t attrs_cap = 0, staging_cap = 0;
+  void forget() { draws.clear(); }
+};
+
 // Everything one frame in flight owns.  What is in neither group survives an option change and a resize.
 struct FrameSlot : TileSized, ExtentSized {
+  StaticRecords statics;
   PinnedBlock<uint8_t> h_staging;  // pinned: lights, draw descriptors, instances
   PinnedBlock<uint32_t> h_flags;   // pinned, device-visible: the kHostFlagWords words of HostFlagWord (bb_types.h), stored by the kernels
                                    // of the frame last rendered in this slot and read when the slot's next frame is submitted
@@ -336,6 +353,14 @@ struct bbr_context : ExtentDumps {
   bool dump_shadow_mask = false;  // (bbr_read_shadow_mask: together with dump_surface, the DUMP form of k_shade_shadow)
   bool dump_surface = false;
   DeviceBuffer<float> d_surface;  // width*height*32 floats, only while bbr_read_surface runs
+  // option "static_records": 1 = a draw whose key repeats in a slot has the camera-independent part of its records written
+  // once (k_record_static) and k_geometry's light path from then on; 0 = always the full path
+  bool static_records = true;
+  bool dump_records = false;    // (bbr_read_records: its frame shows what k_geometry's full path writes, and what it leaves alone)
+  // Bumped by every call that can change what a mesh or material handle, or a pointer taken from one, means (upload and free
+  // of either, the material table, the mip chains): a freed and reused address never compares equal to its former self.
+  uint64_t resource_epoch = 1;
+  uint64_t static_fills = 0, static_light_draws = 0;  // k_record_static launches; draws submitted on the light path
   uint32_t ablate = 0;
   int n_cus = 256;         // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   int timing = 0;  // 0 off, 1 five events per frame, 2 only the two events around k_shade
@@ -735,6 +760,7 @@ int upload_material_table(bbr_context *c) {
     HIP_TRY(c, upload_sync(c->d_mip_tables.ptr, t.data(), n * sizeof(MipTable)));
   }
   c->materials_dirty = false;
+  ++c->resource_epoch;
   return BBR_OK;
 }
 
@@ -742,7 +768,8 @@ int upload_material_table(bbr_context *c) {
 template <int TW, int TH>
 void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const FrameStreams &st, const Event *ev, const FrameParams &fp_in,
                   const Mat4 &pv, const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DrawDesc *d_draws, uint32_t n_draws,
-                  const FirstPrims &first_prims, float4 *final_out, uint32_t *d_item_head) {
+                  const FirstPrims &first_prims, float4 *final_out, uint32_t *d_item_head, const DrawDesc *h_draws,
+                  const std::vector<uint32_t> &fills) {
   FrameParams fp = fp_in;
   // Where the kernels up to shading write.  With a resolve they render the fine frame and k_resolve (at the end) writes
   // `final_out`; with fused presentation k_raster / k_shade write presented pixels into the slot's RGBA8 image, unless there is a
@@ -776,6 +803,14 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   }
   const hipStream_t sg = st.geom, sr = st.raster, ss = st.shade;
   Counters *ctr = c->d_counters.ptr + s.ctr_index, *ctr_done = c->d_counters_done.ptr + s.ctr_index;
+  // option "static_records": the draws whose key has just repeated in this slot (plan_static_records; `h_draws`: the host's
+  // copy of `d_draws`) get the camera-independent part of their records first, once; k_geometry then stores the rest
+  for (const uint32_t d : fills) {
+    const uint32_t n = h_draws[d].n_instances * h_draws[d].tris_per_instance;
+    hipLaunchKernelGGL(k_record_static, dim3((n + kRecordStaticThreads - 1) / kRecordStaticThreads), dim3(kRecordStaticThreads), 0, sg,
+                       d_draws, d, s.d_attrs.ptr);
+    ++c->static_fills;
+  }
   if (c->n_prims)
     hipLaunchKernelGGL((k_geometry<TW, TH>), dim3((c->n_prims + 255) / 256), dim3(256), 0, sg, d_draws, n_draws,
                        c->n_prims, first_prims, s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv, view, fp, s.d_clip.ptr,
@@ -953,12 +988,50 @@ uint32_t fill_draw_descs(const bbr_context *c, DrawDesc *hd, const InstanceBlock
     const MaterialDesc &md = c->materials[rd.material].desc;
     d.packed = md.packed;
     d.packed_dims = md.packed ? ((uint32_t)md.pw | ((uint32_t)md.ph << 16)) : 0u;
-    d.pad = 0;
+    d.flags = 0;  // (the full path; a main frame's static draws: plan_static_records)
     if (k >= 1 && k <= (uint32_t)kInlineFirstPrims) first_prims.v[k - 1] = d.first_prim;
     hd[k++] = d;
   }
   for (uint32_t q = std::max(k, 1u); q <= (uint32_t)kInlineFirstPrims; ++q) first_prims.v[q - 1] = 0xFFFFFFFFu;
   return k;
+}
+
+// Option "static_records", a main frame's `n_draws` descriptors `hd` (fill_draw_descs) about to go into slot `s`: which of
+// the draws find the camera-independent part of their records in the slot's d_attrs.  A draw's key is its descriptor (mesh
+// pointers, instance count and place, triangle count, first primitive, material binding), its place in the frame and its
+// instance blocks byte for byte, under one resource epoch and one allocation of d_attrs.  Per draw:
+//   key new or changed    the full path; the key is remembered
+//   key repeated          k_record_static is queued for the draw (`fills`), then the light path
+//   key repeated, filled  the light path
+// so a draw whose instances move every frame never causes a fill and pays the comparison only.  `old_staging` is the slot's
+// pinned staging as its previous frame left it, `d_staging` its device copy; the instance blocks of `hd` are still in
+// c->host_instances, `d_inst_base` is where their device copy begins.  Called before the staging is overwritten.
+void plan_static_records(bbr_context *c, FrameSlot &s, DrawDesc *hd, uint32_t n_draws, const uint8_t *old_staging, const uint8_t *d_staging,
+                         const InstanceBlock *d_inst_base, std::vector<uint32_t> &fills) {
+  StaticRecords &sr = s.statics;
+  if (!c->static_records || c->dump_records || c->ablate) return sr.forget();
+  if (sr.epoch != c->resource_epoch || sr.attrs_cap != s.d_attrs.cap || sr.staging_cap != s.h_staging.cap) sr.forget();
+  sr.epoch = c->resource_epoch;
+  sr.attrs_cap = s.d_attrs.cap;
+  sr.staging_cap = s.h_staging.cap;
+  sr.draws.resize(n_draws, StaticRecords::Draw{DrawDesc{}, false});  // (a fresh entry's null pointers equal no live draw's)
+  for (uint32_t k = 0; k < n_draws; ++k) {
+    StaticRecords::Draw &e = sr.draws[k];
+    const size_t inst_bytes = sizeof(InstanceBlock) * hd[k].n_instances;
+    // (equal descriptors point at the same place of the device staging: the previous frame's blocks are at that offset of the pinned one)
+    const bool same = std::memcmp(&e.key, &hd[k], sizeof(DrawDesc)) == 0 &&
+                      std::memcmp(old_staging + (reinterpret_cast<const uint8_t *>(hd[k].instances) - d_staging),
+                                  c->host_instances.data() + (hd[k].instances - d_inst_base), inst_bytes) == 0;
+    if (!same) {
+      e.key = hd[k];
+      e.filled = false;
+      continue;
+    }
+    if (!e.filled) fills.push_back(k);
+    e.filled = true;
+    hd[k].flags = kDrawStaticPresent;
+    ++c->static_light_draws;
+  }
 }
 
 // Queue the recorded frame into slot `slot_index`.  Asynchronous.
@@ -1009,6 +1082,11 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   const uint32_t n_live_draws =
       fill_draw_descs(c, reinterpret_cast<DrawDesc *>(h_staging + lights_bytes),
                       reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + lights_bytes + draws_bytes), first_prims);
+  // (while the staging still holds the instance blocks of the slot's previous frame: a repeated descriptor has left them in place)
+  const DrawDesc *const h_draws = reinterpret_cast<const DrawDesc *>(h_staging + lights_bytes);
+  std::vector<uint32_t> fills;  // draws k_record_static runs for in front of this frame's k_geometry
+  plan_static_records(c, s, reinterpret_cast<DrawDesc *>(h_staging + lights_bytes), n_live_draws, h_staging, s.d_staging.ptr,
+                      reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + lights_bytes + draws_bytes), fills);
   if (inst_bytes) std::memcpy(h_staging + lights_bytes + draws_bytes, c->host_instances.data(), inst_bytes);
   std::memset(h_staging + head_offset, 0, 16);
   uint32_t *d_item_head = reinterpret_cast<uint32_t *>(s.d_staging.ptr + head_offset);
@@ -1040,8 +1118,8 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   float4 *out = !mode.frame32() ? nullptr : (c->ext_out ? reinterpret_cast<float4 *>(c->ext_out) : s.d_frame.ptr);
 
   HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, h_staging, total, hipMemcpyHostToDevice, st.geom));
-  if (c->tile_mode == 0) launch_frame<64, 64>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head);
-  else launch_frame<32, 32>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head);
+  if (c->tile_mode == 0) launch_frame<64, 64>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head, h_draws, fills);
+  else launch_frame<32, 32>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head, h_draws, fills);
   HIP_TRY(c, hipGetLastError());
   s.in_flight = true;
   s.mode = mode;
@@ -1885,6 +1963,7 @@ int bbr_upload_mesh(bbr_context *c, const void *vertices, uint32_t n_vertices, c
     HIP_TRY(c, upload_sync(m.d_indices.ptr, indices, (size_t)n_indices * sizeof(uint32_t)));
   }
   m.alive = true;
+  ++c->resource_epoch;
   c->meshes.push_back(std::move(m));
   *out_mesh = (int32_t)c->meshes.size() - 1;
   return BBR_OK;
@@ -1899,6 +1978,7 @@ int bbr_free_mesh(bbr_context *c, int32_t mesh) {
   int rc = drain(c);
   if (rc) return rc;
   c->meshes[mesh] = Mesh();
+  ++c->resource_epoch;
   c->have_frame = false;
   return BBR_OK;
 }
@@ -1942,6 +2022,7 @@ int bbr_upload_material(bbr_context *c, const bbr_image maps[BBR_MAP_COUNT], int
   m.alive = true;
   c->materials.push_back(std::move(m));
   c->materials_dirty = true;
+  ++c->resource_epoch;
   *out_material = (int32_t)c->materials.size() - 1;
   return BBR_OK;
 }
@@ -1956,6 +2037,7 @@ int bbr_free_material(bbr_context *c, int32_t material) {
   if (rc) return rc;
   c->materials[material] = Material();
   c->materials_dirty = true;
+  ++c->resource_epoch;
   c->have_frame = false;
   return BBR_OK;
 }
@@ -2482,8 +2564,12 @@ int bbr_read_records(bbr_context *c, void *records, void *triangles, uint32_t ca
       HIP_TRY(c, hipStreamSynchronize(nullptr));  // (the context's streams do not order themselves after the NULL stream)
     }
   }
+  // (the full path, whatever option "static_records" says: a culled primitive keeps the fill.  The slot's static parts are gone
+  //  with the fill, and the resubmission forgets them: plan_static_records)
+  c->dump_records = true;
   rc = resubmit_last_frame(c);
   if (rc == BBR_OK) rc = sync_and_fix(c, nullptr);
+  c->dump_records = false;
   if (rc) return rc;
   const FrameSlot &s = c->slots[c->last_slot];
   const size_t m = std::min<size_t>(cap, n);
@@ -2528,6 +2614,13 @@ int bbr_host_timing_reset(bbr_context *c) {
 int bbr_capacity_growths(const bbr_context *c, uint32_t *out_count) {
   if (!c || !out_count) return BBR_ERR_INVALID_ARGUMENT;
   *out_count = (uint32_t)c->retries;
+  return BBR_OK;
+}
+
+int bbr_static_record_counts(const bbr_context *c, uint64_t *out_fills, uint64_t *out_light_draws) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  if (out_fills) *out_fills = c->static_fills;
+  if (out_light_draws) *out_light_draws = c->static_light_draws;
   return BBR_OK;
 }
 
@@ -2670,6 +2763,7 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
     for (Material &m : c->materials) free_chain(m);
     c->mip_levels = (int)value;
     c->materials_dirty = true;
+    ++c->resource_epoch;
     if (value == 1) c->d_mip_tables.release();
     for (Material &m : c->materials)
       if (m.alive && value > 1 && (rc = build_chain(c, m)) != BBR_OK) {
@@ -2727,6 +2821,9 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
       c->shadow_map = (int)value;
       c->shadow = ShadowOwned();
     }
+  } else if (n == "static_records") {
+    if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "static_records: 1 (write a static draw's record part once) or 0 (every frame)");
+    c->static_records = value == 1;
   } else if (n == "present_fused") {
     c->present_fused = value != 0;
   } else if (n == "overlays") {

@@ -500,6 +500,13 @@ class Renderer:
         self._check(self._L.bbr_capacity_growths(self._ctx, C.byref(n)))
         return int(n.value)
 
+    def static_record_counts(self):
+        """option static_records since the context was created (host-side counters: no synchronisation): k_record_static launches,
+        draws submitted on the geometry kernel's light path"""
+        fills, light = C.c_uint64(), C.c_uint64()
+        self._check(self._L.bbr_static_record_counts(self._ctx, C.byref(fills), C.byref(light)))
+        return {"fills": int(fills.value), "light_draws": int(light.value)}
+
     def host_timing(self):
         """host side of the frame loop since host_timing_reset (no GPU call): frames submitted, ns inside the submit calls, ns of
         that spent blocked on a frame slot still in flight, frames in which the host was blocked"""

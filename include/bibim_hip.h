@@ -189,6 +189,10 @@ int bbr_get_stats(bbr_context *ctx, bbr_stats *out);                            
 /* How often a capacity (bins, every-tile list, clip arena) has been grown since bbr_create (= bbr_stats.bin_overflow), without
  * synchronising or touching the GPU: a host that times frames can tell afterwards whether one of them overflowed. */
 int bbr_capacity_growths(const bbr_context *ctx, uint32_t *out_count);          /* host-side counter: does NOT synchronise */
+/* Option "static_records" since bbr_create, without synchronising or touching the GPU: how often the camera-independent part
+ * of a draw's records was written (one k_record_static launch per draw and frame slot), and how many draws were submitted
+ * on the geometry kernel's light path.  Either pointer may be NULL. */
+int bbr_static_record_counts(const bbr_context *ctx, uint64_t *out_fills, uint64_t *out_light_draws);
 /* The host's side of the frame loop since bbr_host_timing_reset, kept without touching the GPU (steady_clock around the
  * submit): frames submitted by bbr_end_frame / bbr_replay_frame, nanoseconds spent inside those calls, and the part of
  * it the host was BLOCKED because the frame slot it wanted to reuse was still on the GPU (and in how many frames).  A
@@ -377,6 +381,16 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            references before the screen-ordered rest.  Same pixels.  0: plain screen order; -1 (default):
  *                            64 while one frame is in flight, 0 otherwise -- it shortens a single frame (C3: k_raster alone
  *                            61.9 -> 51.0 us, frame latency 177 -> 167 us) and costs 1-2 % of the pipelined frame rate
+ *   "static_records" 0|1     1 (default): 184 of the 224 bytes of a primitive's record -- texture coordinates, material binding,
+ *                            world-space position, normal, tangent, bitangent -- do not depend on the camera.  A draw whose
+ *                            mesh, material binding, place in the frame and instance blocks (compared byte for byte) are
+ *                            those of the frame that used the same frame slot before has them written once per slot, for
+ *                            every primitive (k_record_static); from then on the geometry kernel stores only the 40 bytes
+ *                            that follow the camera.  Same records, same pixels.  A draw whose instances change pays the
+ *                            comparison and is processed as with 0; it comes back one frame after its key has repeated.
+ *                            Uploading or freeing a mesh or a material, a change of "mip_levels", bbr_read_records and a
+ *                            growth of the record buffer make every draw start over.  0: every frame writes whole records.
+ *                            The overlay pass and the shadow-map pass always write whole records.
  *   "ablate" bits            diagnostic builds only (make EXTRA=-DBB_ABLATE): skip parts of the pipeline */
 int bbr_set_option(bbr_context *ctx, const char *name, int64_t value);
 /* The stream layout in use (option "stream_layout"; 0 while only one frame is in flight).  *out_decided is always 1 and

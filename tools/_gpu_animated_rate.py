@@ -1,0 +1,83 @@
+"""Diagnostic: pipelined frame period of a workload whose instances MOVE every frame (every instance block of both draws differs
+from the one the frame slot saw last), through the plain C API: bbr_begin_frame / bbr_draw / bbr_end_frame.  Option
+"static_records" never finds a repeated key in such a sequence: the figure shows what an animated scene pays for the comparison.
+--still: the same loop with the instances left alone (the draws go to the light path).  Each case runs in its own process.
+usage: _gpu_animated_rate.py [--root TREE] [--reps 3] [--still] workload[:fif=3][:name=value ...] ..."""
+import argparse, os, subprocess, sys
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CHILD = r'''
+import sys, time, gc
+sys.path.insert(0, %(root)r)
+import numpy as np
+from bibim_renderer_amd import configs, textures, Renderer
+from bibim_renderer_amd import scene as S
+cfg = configs.CONFIGS[%(workload)r]
+r = Renderer(cfg.width, cfg.height)
+r.set_option("frames_in_flight", %(fif)d)
+for k, v in %(opts)r: r.set_option(k, v)
+material = r.upload_material(textures.make_material(cfg.texture_size))
+scene, cam, settings = S.config_scene(None, cfg)
+fb, vb = scene.fill_uniforms(cam, settings, cfg.width, cfg.height)
+balls, ground = scene.instances(0), scene.instances(1)
+plane = np.zeros((4, 11), np.float32)
+plane[:, 0:3] = [(-0.5, 0, -0.5), (-0.5, 0, 0.5), (0.5, 0, 0.5), (0.5, 0, -0.5)]
+plane[:, 3:5] = [(0, 0), (0, 1), (1, 1), (1, 0)]
+plane[:, 5:8], plane[:, 8:11] = (0, 1, 0), (1, 0, 0)
+m_ball = r.upload_mesh(S.load_shaderball_vertices())
+m_plane = r.upload_mesh(plane, np.array([0, 1, 2, 2, 3, 0], np.uint32))
+# eight sets of instance blocks, a hair apart (the translation column of every model matrix): consecutive frames of a slot differ
+sets = []
+for k in range(1 if %(still)r else 8):
+    b, g = balls.copy(), ground.copy()
+    b[:, 0, 3, 1] += 1e-4 * k
+    g[:, 0, 3, 1] -= 1e-4 * k
+    sets.append((np.ascontiguousarray(b).view(np.uint8).reshape(-1), np.ascontiguousarray(g).view(np.uint8).reshape(-1)))
+r.set_frame_uniforms(fb)
+r.set_view_uniforms(vb)
+n = [0]
+def frame():
+    b, g = sets[n[0] %% len(sets)]
+    n[0] += 1
+    r.begin_frame(); r.draw(m_ball, material, b); r.draw(m_plane, material, g); r.end_frame()
+frame(); r.synchronize()
+gc.collect(); gc.disable()
+for _ in range(60): frame()
+r.synchronize()
+out = []
+for rep in range(%(reps)d):
+    for _ in range(10): frame()
+    t0 = time.perf_counter()
+    for _ in range(%(frames)d): frame()
+    r.synchronize()
+    out.append((time.perf_counter() - t0) / %(frames)d * 1e6)
+counts = r.static_record_counts() if hasattr(r, "static_record_counts") else None
+print("%(tag)-40s us/frame " + " ".join("%%7.1f" %% x for x in out) + "   static records: %%s" %% (counts,), flush=True)
+scene.close(); r.close()
+'''
+ap = argparse.ArgumentParser()
+ap.add_argument("--root", default=HERE, help="the tree whose package and library are used (another checkout, for A/B timing)")
+ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--still", action="store_true")
+ap.add_argument("cases", nargs="+")
+a = ap.parse_args()
+rc = 0
+for case in a.cases:
+    parts = case.split(":")
+    workload = parts[0]
+    fif, opts = (4 if workload == "c2" else 3), []
+    for p in parts[1:]:
+        k, v = p.split("=")
+        if k == "fif":
+            fif = int(v)
+        else:
+            opts.append((k, int(v)))
+    frames = {"c2": 600, "c3": 300, "c5": 80}[workload]
+    tag = ("still " if a.still else "moving ") + case + (" [" + os.path.basename(os.path.abspath(a.root)) + "]" if a.root != HERE else "")
+    code = CHILD % dict(root=os.path.abspath(a.root), workload=workload, opts=opts, frames=frames, fif=fif, reps=a.reps, tag=tag, still=a.still)
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    sys.stdout.write(p.stdout)
+    if p.returncode:
+        sys.stdout.write(f"{case}: FAILED rc={p.returncode}\n{p.stderr[-1500:]}\n"); rc = 1
+    sys.stdout.flush()
+sys.exit(rc)
