@@ -102,6 +102,9 @@ SIGNATURES = {
     "bbr_render_shadow_map": (C.c_int, [_P, C.c_int32, C.c_void_p, C.c_float]),
     "bbr_read_shadow_map": (C.c_int, [_P, C.c_void_p]),
     "bbr_read_shadow_mask": (C.c_int, [_P, C.c_void_p]),
+    "bbr_render_shadow_faces": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_void_p, C.c_float]),
+    "bbr_read_shadow_face": (C.c_int, [_P, C.c_int32, C.c_void_p]),
+    "bbr_read_shadow_face_index": (C.c_int, [_P, C.c_void_p]),
     "bbr_read_material_level": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32)]),
     "bbr_read_packed_level": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -159,6 +162,7 @@ SCENE_SIGNATURES = {
     "bbs_mat4_rotate": (None, [C.c_int, _F, _P]),
     "bbs_mat4_look_at": (None, [_P, _P, _P, _P]),
     "bbs_mat4_perspective": (None, [_F, _F, _F, _F, _P]),
+    "bbs_cube_shadow_views": (None, [_P, _F, _F, _F, _P]),
     "bbs_camera_look": (None, [_F, _F, _P]),
     "bbs_camera_view": (None, [_P, _F, _F, _P]),
     "bbs_plane_mesh": (None, [_P, _P]),

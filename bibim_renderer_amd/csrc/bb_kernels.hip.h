@@ -18,6 +18,7 @@
 //                output pixel behind k_raster, and the resolve that knows which sample stands for which
 //   k_resolve_depth    option "depth_resolve": the depth (and winner) of one sample of the block for the output pixel
 //   k_shade_shadow     option "shadow_map": k_shade_aniso's fragment stage with a shadow test in front of one light's iteration
+//   k_shade_shadow_faces    ... with 2 .. 6 faces for that light (bbr_render_shadow_faces): cube maps, cascades
 //
 // Arithmetic contract: every floating-point expression below has the same operand order and the same
 // explicit fmaf() placement as the CPU oracle; the file is compiled with -ffp-contract=off, IEEE
@@ -2352,8 +2353,9 @@ BB_DEV f3 sample_map_rgb(const TexDesc &td, float u, float v) {
 //   classes 0 not covered, 1 LIT, 2 SHADOWED, 3 OUTSIDE (bbr_read_shadow_mask)
 //   loop    the iteration of light `light` of a SHADOWED fragment contributes nothing: the `continue` of an unknown light
 //           type.  Every other operation, and the operand order, is light_surface's
-// Deviations: a hard compare, one caster, a point light gets the one frustum the caller chose, and the deferred background
-// colour (k_deferred_background) is evaluated without the test.
+// Deviations: a hard compare, one caster, and the deferred background colour (k_deferred_background) is evaluated without the
+// test.  A point light gets up to six frusta (ShadowFacesTest, below): a fragment on a seam of exactly-90-degree faces is
+// outside all of them and lit, and where frusta overlap the earlier one decides.
 // M and the scalars are kernel arguments (scalar registers); the map costs one 4-byte gather per fragment, and only lanes
 // inside the map address it: i and j lie in [0, S - 1].
 // ------------------------------------------------------------------------------------------------
@@ -2393,6 +2395,60 @@ struct ShadowTest {
   BB_DEV ShadowSkip on(const FrameParams &fp, f3 P, bool valid, int gx, int gy) const {
     const int cls = classify(P);
     if (DUMP && a.mask && valid) a.mask[(size_t)gy * (size_t)fp.width + (size_t)gx] = (uint8_t)cls;
+    return ShadowSkip{a.light, cls == kShadowShadowed};
+  }
+};
+
+// Up to six faces for the one caster (bbr_render_shadow_faces with 2 .. 6 view blocks; k_shade_shadow_faces): six 90-degree-class
+// frusta at a point light are a cube map, nested orthographic ones are cascades.  The rule (restated
+// independently in tests/shadow_faces_reference.py):
+//   maps    map_f = the map above for L_f, at map + f * S * S
+//   test    for f = 0 .. F - 1 in this order: cls_f = the rule above with M_f = proj_view(L_f) and map_f; the first
+//           cls_f != OUTSIDE is the fragment's class and f its face; none: OUTSIDE, face 255
+// Where frusta overlap the earlier face wins and the later map is not read; a fragment outside every face is lit (with faces
+// of exactly 90 degrees: on the seam planes).
+// The face loop is uniform over the wave: f is a scalar, so M_f arrives through scalar loads from the kernel arguments and
+// every lane runs the same face; a lane that has its class only carries it.  The loop ends when no lane of the wave is
+// undecided (a ballot): most waves of a cube-lit frame see one or two faces.  Only lanes inside face f address its map, with
+// i, j in [0, S - 1] by the comparisons and f < F by the loop bound.
+constexpr int kMaxShadowFaces = 6;
+struct ShadowFacesArgs {
+  Mat4 m[kMaxShadowFaces];  // proj_view(L_f)
+  const float *map;         // F maps of S x S depths, face f at map + f * S * S
+  uint8_t *mask;            // the DUMP form's outputs (bbr_read_shadow_mask, bbr_read_shadow_face_index): a class and ...
+  uint8_t *face;            // ... the deciding face per pixel, or nullptr
+  int32_t side;             // S
+  int32_t light;            // the caster's index in the frame's light list
+  int32_t faces;            // F
+  float half;               // 0.5f * S
+  float bias;
+};
+template <bool DUMP>
+struct ShadowFacesTest {
+  const ShadowFacesArgs &a;
+  BB_DEV ShadowSkip on(const FrameParams &fp, f3 P, bool valid, int gx, int gy) const {
+    const float side = (float)a.side;
+    const size_t texels = (size_t)a.side * (size_t)a.side;
+    int cls = kShadowOutside, face = 255;
+    for (int f = 0; f < a.faces; ++f) {
+      const bool undecided = cls == kShadowOutside;
+      if (__ballot(undecided) == 0ull) break;
+      const f4 c = mat4_mul(a.m[f], f4{P.x, P.y, P.z, 1.0f});
+      const float r = bb_rcp(c.w);  // (of a w <= 0 too: not used then)
+      const float xs = fmaf(c.x * r, a.half, a.half), ys = fmaf(c.y * r, a.half, a.half);
+      const bool inside = c.w > 0.0f && xs >= 0.0f && xs < side && ys >= 0.0f && ys < side;
+      if (undecided && inside) {
+        const int i = (int)xs, j = (int)ys;  // 0 .. S - 1
+        const float t = c.z * r + a.bias;
+        cls = a.map[(size_t)f * texels + (size_t)j * (size_t)a.side + (size_t)i] > t ? kShadowShadowed : kShadowLit;
+        face = f;
+      }
+    }
+    if (DUMP && valid) {
+      const size_t o = (size_t)gy * (size_t)fp.width + (size_t)gx;
+      if (a.mask) a.mask[o] = (uint8_t)cls;
+      if (a.face) a.face[o] = (uint8_t)face;
+    }
     return ShadowSkip{a.light, cls == kShadowShadowed};
   }
 };
@@ -3055,6 +3111,23 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_shadow(
   shade_item_list<TILE_W, TILE_H, DEFERRED, PRESENT, DUMP>(items, item_count, frags, frag_count, recs, clip_arena, fp, sp, cooked, materials, out,
                                                            gbuffer, tables, out8, ctr, ctr_done, item_groups, AnisoFilter{max_aniso}, dump,
                                                            ShadowTest<DUMP>{shadow});
+}
+
+// k_shade_shadow_faces: k_shade_shadow with 2 .. 6 faces for the caster (the rule: in front of ShadowFacesTest).  DUMP as in
+// k_shade_shadow, plus the deciding face of every pixel where `shadow.face` is set.
+template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
+__global__ __launch_bounds__(kShadeThreads) void k_shade_shadow_faces(
+    const uint32_t *__restrict__ items, const uint32_t *__restrict__ item_count,
+    const unsigned long long *__restrict__ frags, const uint32_t *__restrict__ frag_count,
+    const ShadeRec *__restrict__ recs, const ClipSlot *__restrict__ clip_arena,
+    FrameParams fp, ShadeParams sp, const CookedLight *__restrict__ cooked,
+    const MaterialDesc *__restrict__ materials, float4 *__restrict__ out,
+    uint2 *__restrict__ gbuffer, const SrgbTables *__restrict__ tables, uint32_t *__restrict__ out8,
+    Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups, int max_aniso,
+    float *__restrict__ dump, ShadowFacesArgs shadow) {
+  shade_item_list<TILE_W, TILE_H, DEFERRED, PRESENT, DUMP>(items, item_count, frags, frag_count, recs, clip_arena, fp, sp, cooked, materials, out,
+                                                           gbuffer, tables, out8, ctr, ctr_done, item_groups, AnisoFilter{max_aniso}, dump,
+                                                           ShadowFacesTest<DUMP>{shadow});
 }
 
 // ------------------------------------------------------------------------------------------------

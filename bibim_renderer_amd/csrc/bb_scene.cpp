@@ -268,6 +268,18 @@ void fillUniforms(const SceneBase &scene, const FreeLookCamera &cam, const Frame
   vb.EnableNormalMap = s.EnableNormalMap ? 1 : 0;
 }
 
+void cubeShadowViews(const Float3 &pos, float fovDegrees, float nearZ, float farZ, ViewUniformBlock out[6]) {
+  static const Float3 dirs[6] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+  static const Float3 ups[6] = {{0, 1, 0}, {0, 1, 0}, {0, 0, -1}, {0, 0, 1}, {0, 1, 0}, {0, 1, 0}};
+  const Mat4 proj = Mat4::perspective(fovDegrees, 1.f, nearZ, farZ);
+  for (int f = 0; f < 6; ++f) {
+    out[f] = ViewUniformBlock();
+    out[f].ViewMat = Mat4::lookAt(pos, pos + dirs[f], ups[f]);
+    out[f].ProjMat = proj;
+    out[f].ViewPos = pos;
+  }
+}
+
 int drawFrame(bbr_context *ctx, SceneBase &scene, const FreeLookCamera &cam, const FrameSettings &settings,
               int32_t material, int width, int height, float dt) {
   scene.updateScene(dt);
@@ -342,6 +354,11 @@ void bbs_mat4_look_at(const float *eye, const float *target, const float *up, fl
 }
 void bbs_mat4_perspective(float fov, float aspect, float n, float f, float *out) {
   storeMat(bb::Mat4::perspective(fov, aspect, n, f), out);
+}
+void bbs_cube_shadow_views(const float *pos, float fov, float n, float f, void *out_view_blocks6) {
+  bb::ViewUniformBlock blocks[6];
+  bb::cubeShadowViews({pos[0], pos[1], pos[2]}, fov, n, f, blocks);
+  std::memcpy(out_view_blocks6, static_cast<const void *>(blocks), sizeof blocks);
 }
 void bbs_camera_look(float yaw, float pitch, float *out3) {
   float zero[3] = {0, 0, 0};

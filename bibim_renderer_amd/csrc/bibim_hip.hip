@@ -87,6 +87,7 @@ struct FrameMode {
   bool depth = false;    // option "overlays": the frame keeps its depth for bbr_draw_overlays (whole frame; n >= 2: a rule)
   int depth_rule = 0;    // n >= 2: option "depth_resolve" (0: no depth is kept; else k_resolve_depth's MODE, VkResolveModeFlagBits)
   bool shadow = false;   // option "shadow_map" > 0 and a map has been rendered (bbr_render_shadow_map): k_shade_shadow shades
+  bool shadow_faces = false;  // ... two or more of them (bbr_render_shadow_faces): k_shade_shadow_faces
   bool fused = false;    // option "present_fused": the frame is written as presented RGBA8 (the slot's d_present) ...
   bool shade_presents() const { return fused && !resolve; }   // ... by k_raster / k_shade
   bool resolve_presents() const { return fused && resolve; }  // ... by k_resolve (a presented byte cannot be averaged): then
@@ -259,15 +260,23 @@ struct ExtentDumps {
   DeviceBuffer<float> d_vis_fine_depth;
   DeviceBuffer<uint2> d_gbuffer;  // width*height*4 (four RGBA16F texels per pixel), only while bbr_read_gbuffer runs
   DeviceBuffer<uint8_t> d_shadow_mask;  // width*height classes, only while bbr_read_shadow_mask runs
+  DeviceBuffer<uint8_t> d_shadow_face;  // width*height deciding faces, only while bbr_read_shadow_face_index runs (F >= 2)
 };
 
 // Option "shadow_map": everything the feature owns.  Changing the option's value drops the group; at 0 nothing of it exists.
 struct ShadowOwned {
   FrameSlot pass;                 // the map pass's own little frame (k_geometry -> k_raster at S x S), like the overlay pass's
-  DeviceBuffer<float> d_map;      // the map: S x S depths, row-major (k_raster's depth store)
-  DeviceBuffer<uint32_t> d_sink;  // S x S words k_raster's background stores go to; nothing reads them
-  ShadowArgs args = {};           // what every frame's k_shade_shadow gets: M, the map, S, the caster's index, the bias
-  bool valid = false;             // a map has been rendered since the option was set
+  DeviceBuffer<float> d_map;      // the maps: F x S x S depths, face f row-major at f * S * S (k_raster's depth store)
+  DeviceBuffer<uint32_t> d_sink;  // S x S words k_raster's background stores go to; nothing reads them (one for all faces)
+  DeviceBuffer<Counters> d_ctr;   // a counter block per face: the faces run back to back and are read after one wait
+  ShadowFacesArgs args = {};      // what every frame's k_shade_shadow (F = 1: its first matrix) or k_shade_shadow_faces gets:
+                                  // M_f, the maps, S, F, the caster's index, the bias
+  bool valid = false;             // the maps have been rendered since the option was set
+  ShadowArgs one_face() const {   // (F = 1)
+    ShadowArgs a = {};
+    a.m = args.m[0], a.map = args.map, a.side = args.side, a.light = args.light, a.half = args.half, a.bias = args.bias;
+    return a;
+  }
 };
 
 struct bbr_context : ExtentDumps {
@@ -478,6 +487,7 @@ FrameMode frame_mode(const bbr_context *c) {
   m.merged = m.resolve && c->sample_shading == 0;
   m.fused = c->present_fused;
   m.shadow = c->shadow_map > 0 && c->shadow.valid;
+  m.shadow_faces = m.shadow && c->shadow.args.faces > 1;
   m.depth_rule = m.resolve ? c->depth_resolve : 0;
   // (bbr_draw_overlays is refused on a partition, and with n >= 2 unless option "depth_resolve" names a rule)
   m.depth = c->overlays && c->world == 1 && (!m.resolve || m.depth_rule != 0);
@@ -890,15 +900,20 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
     };
     uint32_t *groups = short_frame ? nullptr : s.d_item_groups.ptr;
     if (mode.shadow || c->mip_levels > 1 || c->max_anisotropy > 1 || c->dump_surface) {
-      // a valid shadow map: k_shade_shadow (never together with "mip_levels" >= 2: refused_shadow_pair); option "mip_levels":
+      // a valid shadow map: k_shade_shadow, k_shade_shadow_faces (never together with "mip_levels" >= 2: refused_shadow_pair); option "mip_levels":
       // k_shade_mip; option "max_anisotropy" / bbr_read_surface (the kernels' DUMP forms): k_shade_aniso.
       // Each is one launch whose waves walk the whole item list.
       if (ev) (void)hipEventRecord(ev[3], ss);
       float *surface = c->dump_surface ? c->d_surface.ptr : nullptr;
       with_bool(c->mip_levels > 1, [&](auto mip) { with_bool(c->dump_surface, [&](auto dump) {
         constexpr bool DUMP = decltype(dump)::value;
-        if (mode.shadow) {
-          ShadowArgs sa = c->shadow.args;
+        if (mode.shadow_faces) {
+          ShadowFacesArgs sa = c->shadow.args;
+          sa.mask = (DUMP && c->dump_shadow_mask) ? c->d_shadow_mask.ptr : nullptr;
+          sa.face = (DUMP && c->dump_shadow_mask) ? c->d_shadow_face.ptr : nullptr;
+          launch(k_shade_shadow_faces<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface, sa);
+        } else if (mode.shadow) {
+          ShadowArgs sa = c->shadow.one_face();
           sa.mask = (DUMP && c->dump_shadow_mask) ? c->d_shadow_mask.ptr : nullptr;
           launch(k_shade_shadow<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface, sa);
         } else if constexpr (decltype(mip)::value) launch(k_shade_mip<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, c->d_mip_tables.ptr, surface);
@@ -1567,36 +1582,48 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
 // ================================================================================================
 
 // Synchronous, like the overlay pass, and built like it: the context is drained, the pass has a slot of its own
-// (bbr_context::shadow.pass) and the overlay pass's counter block (both passes clear it before they return), and a capacity
-// that overflows is grown and the pass run again.  The kernels are the frame's own k_geometry and k_raster, untouched:
+// (bbr_context::shadow.pass) and counter blocks of its own (cleared before it returns), and a capacity that overflows is
+// grown and the pass run again.  The kernels are the frame's own k_geometry and k_raster, untouched:
 // k_raster keeps its depth through the pointer the option "overlays" uses (so every tile takes the general path and every
 // texel is stored, the clear value where nothing is drawn), and its colour stores -- the background of uncovered texels --
 // go as presented words into d_sink, which nothing reads; it makes no items.  The map ignores the partition.
-extern "C" int bbr_render_shadow_map(bbr_context *c, int32_t light_index, const void *light_view_block, float bias) {
+//
+// One call renders F = 1 .. 6 faces (bbr_render_shadow_faces; bbr_render_shadow_map is F = 1).  The draws and instances are
+// uploaded once.  The faces run back to back on the stream through the one pass slot: k_raster leaves every tile's bin
+// counts at zero behind it (the general path's clear), the triangle records, bins, clip arena and every-tile list of face f
+// are dead when its k_raster has finished, and the stream orders face f + 1's k_geometry behind that.  Only the counters
+// must not be shared -- the every-tile and clip allocators start at zero for every face -- so each face has a block of its
+// own in ShadowOwned::d_ctr.  One wait, one read of the F blocks, one clear.  If any face overflowed, the capacities grow by
+// the largest need among the faces and ALL faces are rendered again: the faces of a cube see the same draws, so one that
+// overflows is rarely alone, and which texels of the others were complete is not worth tracking.
+static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t light_index, int32_t n_faces, const void *light_view_blocks,
+                               float bias) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
-  if (c->shadow_map <= 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, "render_shadow_map: option shadow_map is 0");
-  if (light_index < 0 || light_index >= kMaxNumLights) return fail(c, BBR_ERR_INVALID_ARGUMENT, "render_shadow_map: light_index outside 0 .. 99");
-  if (!light_view_block) return fail(c, BBR_ERR_INVALID_ARGUMENT, "render_shadow_map: NULL view block");
-  if (bias != bias) return fail(c, BBR_ERR_INVALID_ARGUMENT, "render_shadow_map: bias is NaN");
-  if (!c->in_frame && !c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, "render_shadow_map: no recorded draws (call it after bbr_draw or after bbr_end_frame)");
+  if (c->shadow_map <= 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": option shadow_map is 0");
+  if (n_faces < 1 || n_faces > kMaxShadowFaces) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": n_faces outside 1 .. 6");
+  if (light_index < 0 || light_index >= kMaxNumLights) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": light_index outside 0 .. 99");
+  if (!light_view_blocks) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": NULL view block");
+  if (bias != bias) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": bias is NaN");
+  if (!c->in_frame && !c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, who + ": no recorded draws (call it after bbr_draw or after bbr_end_frame)");
   for (const RecordedDraw &rd : c->draws)
     if (!c->meshes[rd.mesh].alive || !c->materials[rd.material].alive)
-      return fail(c, BBR_ERR_BAD_HANDLE, "render_shadow_map: a recorded draw's mesh or material was freed");
+      return fail(c, BBR_ERR_BAD_HANDLE, who + ": a recorded draw's mesh or material was freed");
   int rc = sync_and_fix(c, nullptr);  // the frames in flight leave the GPU (and the last one is complete)
   if (rc) return rc;
   rc = upload_material_table(c);
   if (rc) return rc;
-  ViewUniformBlock lv;
-  std::memcpy(&lv, light_view_block, sizeof lv);
+  ViewUniformBlock lv[kMaxShadowFaces];
+  std::memcpy(lv, light_view_blocks, sizeof(ViewUniformBlock) * (size_t)n_faces);
 
   ShadowOwned &sh = c->shadow;
   FrameSlot &s = sh.pass;
   sh.valid = false;
   const int32_t S = c->shadow_map;
   const size_t texels = (size_t)S * (size_t)S;
-  HIP_TRY(c, sh.d_map.ensure(texels));
+  HIP_TRY(c, sh.d_map.ensure(texels * (size_t)n_faces));
   HIP_TRY(c, sh.d_sink.ensure(texels));
+  HIP_TRY(c, sh.d_ctr.ensure(kMaxShadowFaces, true));
 
   // ---- the recorded draws: [draw descriptors | instances], as the frame's staging holds them ----
   const size_t draws_bytes = (sizeof(DrawDesc) * std::max<size_t>(c->draws.size(), 1) + 127) & ~(size_t)127;
@@ -1609,7 +1636,8 @@ extern "C" int bbr_render_shadow_map(bbr_context *c, int32_t light_index, const 
   if (inst_bytes) HIP_TRY(c, upload_sync(s.d_staging.ptr + draws_bytes, c->host_instances.data(), inst_bytes));
   const DrawDesc *d_draws = reinterpret_cast<const DrawDesc *>(s.d_staging.ptr);
   const uint32_t n_prims = c->n_prims;
-  const Mat4 pv = proj_view(lv);  // gl_Position = (L.proj * L.view) * posWorld: the forward order, whatever "render_pass" is
+  Mat4 pv[kMaxShadowFaces];  // gl_Position = (L.proj * L.view) * posWorld: the forward order, whatever "render_pass" is
+  for (int f = 0; f < n_faces; ++f) pv[f] = proj_view(lv[f]);
 
   for (int attempt = 0; attempt < 8; ++attempt) {
     FrameParams fp = make_params(c);  // (the capacities; again after a growth)
@@ -1625,76 +1653,121 @@ extern "C" int bbr_render_shadow_map(bbr_context *c, int32_t light_index, const 
     fp.gbuffer_view = -1;
     rc = ensure_pass_buffers(c, s, n_prims, (size_t)fp.tiles_x * fp.tiles_y);
     if (rc) return rc;
-    s.ctr_index = bbr_context::kMaxSlots;
-    Counters *ctr = c->d_counters.ptr + s.ctr_index;
+    s.ctr_index = bbr_context::kMaxSlots;  // (not a frame slot's; the pass counts in sh.d_ctr)
     hipStream_t st = c->shade_stream();
-    auto launch = [&](auto tw, auto th) {
+    auto launch = [&](auto tw, auto th, int f) {
       constexpr int TW = decltype(tw)::value, TH = decltype(th)::value;
+      Counters *ctr = sh.d_ctr.ptr + f;
       if (n_prims)
         hipLaunchKernelGGL((k_geometry<TW, TH>), dim3((n_prims + 255) / 256), dim3(256), 0, st, d_draws, n_draws, n_prims, first_prims,
-                           s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv, lv.view, fp, s.d_clip.ptr, s.d_broad.ptr,
+                           s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv[f], lv[f].view, fp, s.d_clip.ptr, s.d_broad.ptr,
                            c->d_materials.ptr, s.d_block_stats.ptr, (uint32_t *)nullptr);
       hipLaunchKernelGGL((k_raster<TW, TH>), dim3(fp.tiles_x, fp.tiles_y), dim3(kTileThreads), 0, st, s.d_tile_count.ptr, ctr,
                          s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, (float4 *)nullptr, fp, s.d_tris.ptr, s.d_clip.ptr,
-                         s.d_bins.ptr, (uint32_t *)nullptr, (float *)nullptr, (const float4 *)nullptr, sh.d_map.ptr,
+                         s.d_bins.ptr, (uint32_t *)nullptr, (float *)nullptr, (const float4 *)nullptr, sh.d_map.ptr + (size_t)f * texels,
                          (uint32_t *)nullptr, sh.d_sink.ptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
                          (const Light *)nullptr, 0, (CookedLight *)nullptr, (const uint32_t *)nullptr);
     };
-    if (c->tile_mode == 0) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{});
-    else launch(std::integral_constant<int, 32>{}, std::integral_constant<int, 32>{});
+    for (int f = 0; f < n_faces; ++f) {
+      if (c->tile_mode == 0) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{}, f);
+      else launch(std::integral_constant<int, 32>{}, std::integral_constant<int, 32>{}, f);
+    }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(st));
-    Counters h = {};
-    HIP_TRY(c, hipMemcpy(&h, ctr, sizeof h, hipMemcpyDeviceToHost));
-    HIP_TRY(c, zero_fill_sync(ctr, sizeof(Counters)));  // (the pass is synchronous: cleared here, not by a kernel)
-    if (!h.overflow) {
-      sh.args.m = pv;
+    Counters h[kMaxShadowFaces] = {};
+    HIP_TRY(c, hipMemcpy(h, sh.d_ctr.ptr, sizeof(Counters) * (size_t)n_faces, hipMemcpyDeviceToHost));
+    HIP_TRY(c, zero_fill_sync(sh.d_ctr.ptr, sizeof(Counters) * (size_t)n_faces));  // (the pass is synchronous: cleared here, not by a kernel)
+    Counters need = {};
+    for (int f = 0; f < n_faces; ++f) {
+      need.overflow |= h[f].overflow;
+      need.bin_need = std::max(need.bin_need, h[f].bin_need);
+      need.n_broad = std::max(need.n_broad, h[f].n_broad);
+      need.n_clip_slots = std::max(need.n_clip_slots, h[f].n_clip_slots);
+    }
+    if (!need.overflow) {
+      for (int f = 0; f < n_faces; ++f) sh.args.m[f] = pv[f];
+      for (int f = n_faces; f < kMaxShadowFaces; ++f) sh.args.m[f] = Mat4{};
       sh.args.map = sh.d_map.ptr;
       sh.args.mask = nullptr;
+      sh.args.face = nullptr;
       sh.args.side = S;
       sh.args.light = light_index;
+      sh.args.faces = n_faces;
       sh.args.half = 0.5f * (float)S;
       sh.args.bias = bias;
       sh.valid = true;
       return BBR_OK;
     }
-    // a triangle did not fit: the map is incomplete.  Grow and render all of it again.
-    rc = apply_growth(c, h.overflow, h.bin_need, h.n_broad, h.n_clip_slots);
+    // a triangle did not fit: a map is incomplete.  Grow and render all of them again.
+    rc = apply_growth(c, need.overflow, need.bin_need, need.n_broad, need.n_clip_slots);
     if (rc) return rc;
     if (s.d_tile_count.ptr) HIP_TRY(c, zero_fill_sync(s.d_tile_count.ptr, s.d_tile_count.cap * sizeof(uint32_t)));
   }
-  return fail(c, BBR_ERR_CAPACITY, "render_shadow_map: capacity still exceeded after 8 growth steps");
+  return fail(c, BBR_ERR_CAPACITY, who + ": capacity still exceeded after 8 growth steps");
 }
 
-extern "C" int bbr_read_shadow_map(bbr_context *c, float *host) {
+extern "C" int bbr_render_shadow_map(bbr_context *c, int32_t light_index, const void *light_view_block, float bias) {
+  return render_shadow_faces(c, "render_shadow_map", light_index, 1, light_view_block, bias);
+}
+
+extern "C" int bbr_render_shadow_faces(bbr_context *c, int32_t light_index, int32_t n_faces, const void *light_view_blocks, float bias) {
+  return render_shadow_faces(c, "render_shadow_faces", light_index, n_faces, light_view_blocks, bias);
+}
+
+extern "C" int bbr_read_shadow_face(bbr_context *c, int32_t face, float *host) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_map: NULL");
   if (c->shadow_map <= 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_map: option shadow_map is 0");
   if (!c->shadow.valid) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_shadow_map: no map rendered (bbr_render_shadow_map)");
-  HIP_TRY(c, hipMemcpy(host, c->shadow.d_map.ptr, (size_t)c->shadow_map * c->shadow_map * sizeof(float), hipMemcpyDeviceToHost));
+  if (face < 0 || face >= c->shadow.args.faces) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_face: face outside 0 .. F - 1");
+  const size_t texels = (size_t)c->shadow_map * c->shadow_map;
+  HIP_TRY(c, hipMemcpy(host, c->shadow.d_map.ptr + (size_t)face * texels, texels * sizeof(float), hipMemcpyDeviceToHost));
   return BBR_OK;
 }
 
-// the class of every pixel of the last frame: the DUMP form of k_shade_shadow (with it the surface dump, which is dropped)
-extern "C" int bbr_read_shadow_mask(bbr_context *c, uint8_t *host) {
+extern "C" int bbr_read_shadow_map(bbr_context *c, float *host) { return bbr_read_shadow_face(c, 0, host); }
+
+// The class (and, F >= 2, the deciding face) of every pixel of the last frame: the DUMP form of k_shade_shadow /
+// k_shade_shadow_faces (with it the surface dump, which is dropped).  With one face the face index follows from the class.
+static int read_shadow_classes(bbr_context *c, const std::string &who, uint8_t *host, bool want_face) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
-  if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_mask: NULL");
-  if (int rc = refuse_supersampled(c, "read_shadow_mask")) return rc;
-  if (!frame_mode(c).shadow) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_mask: no shadow map in use (option shadow_map, bbr_render_shadow_map)");
-  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_shadow_mask: nothing rendered");
-  if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_mask: not available on a partitioned context");
-  c->dump_surface = true;
-  int rc = rerender_with(c, &bbr_context::dump_shadow_mask);
-  c->dump_surface = false;
+  if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": NULL");
+  if (int rc = refuse_supersampled(c, who.c_str())) return rc;
+  const FrameMode mode = frame_mode(c);
+  if (!mode.shadow) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": no shadow map in use (option shadow_map, bbr_render_shadow_map)");
+  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, who + ": nothing rendered");
+  if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": not available on a partitioned context");
+  const size_t pixels = (size_t)c->width * c->height;
+  int rc = BBR_OK;
+  if (mode.shadow_faces) {  // (an uncovered pixel keeps the fill: face 255)
+    hipError_t e = c->d_shadow_face.ensure(pixels);
+    if (e == hipSuccess) e = hipMemset(c->d_shadow_face.ptr, 0xFF, pixels);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) rc = fail(c, BBR_ERR_HIP, who + ": " + hipGetErrorString(e));
+  }
   if (rc == BBR_OK) {
-    hipError_t e = hipMemcpy(host, c->d_shadow_mask.ptr, (size_t)c->width * c->height, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(c, BBR_ERR_HIP, std::string("read_shadow_mask: ") + hipGetErrorString(e));
+    c->dump_surface = true;
+    rc = rerender_with(c, &bbr_context::dump_shadow_mask);
+    c->dump_surface = false;
+  }
+  if (rc == BBR_OK) {
+    const uint8_t *src = (want_face && mode.shadow_faces) ? c->d_shadow_face.ptr : c->d_shadow_mask.ptr;
+    hipError_t e = hipMemcpy(host, src, pixels, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(c, BBR_ERR_HIP, who + ": " + hipGetErrorString(e));
+    else if (want_face && !mode.shadow_faces)
+      for (size_t i = 0; i < pixels; ++i) host[i] = (host[i] == kShadowLit || host[i] == kShadowShadowed) ? 0 : 255;
   }
   c->d_shadow_mask.release();  // (uncovered pixels are the zeros of a fresh buffer)
+  c->d_shadow_face.release();
   c->d_surface.release();
   return rc;
+}
+
+extern "C" int bbr_read_shadow_mask(bbr_context *c, uint8_t *host) { return read_shadow_classes(c, "read_shadow_mask", host, false); }
+extern "C" int bbr_read_shadow_face_index(bbr_context *c, uint8_t *host) {
+  return read_shadow_classes(c, "read_shadow_face_index", host, true);
 }
 
 // ================================================================================================

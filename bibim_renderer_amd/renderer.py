@@ -279,6 +279,28 @@ class Renderer:
         self._check(self._L.bbr_read_shadow_map(self._ctx, _ptr(out)))
         return out.reshape(s, s)
 
+    def render_shadow_faces(self, light_index, light_views, bias=0.0):
+        """render_shadow_map with F = 1 .. 6 faces: `light_views` holds F consecutive 144-byte view blocks (cube_shadow_views
+        gives the six of a point light).  The first face a fragment is not outside of decides it; one face is
+        render_shadow_map"""
+        b = np.ascontiguousarray(light_views)
+        assert b.nbytes % 144 == 0
+        self._check(self._L.bbr_render_shadow_faces(self._ctx, int(light_index), b.nbytes // 144, _ptr(b), float(bias)))
+
+    def read_shadow_face(self, face):
+        """the shadow map of one face, [S, S] float32"""
+        s = max(int(self.shadow_map), 0)
+        out = np.empty(max(s * s, 1), np.float32)  # (s = 0: the call refuses)
+        self._check(self._L.bbr_read_shadow_face(self._ctx, int(face), _ptr(out)))
+        return out.reshape(s, s)
+
+    def read_shadow_face_index(self):
+        """the face that decided every pixel of the last frame, [h, w] uint8: 255 where the pixel is not covered or outside
+        every face; re-renders the last frame"""
+        out = np.empty((self.height, self.width), np.uint8)
+        self._check(self._L.bbr_read_shadow_face_index(self._ctx, _ptr(out)))
+        return out
+
     def read_shadow_mask(self):
         """the shadow class of every pixel of the last frame, [h, w] uint8: 0 not covered, 1 lit, 2 shadowed, 3 outside the
         map; re-renders the last frame"""

@@ -30,6 +30,14 @@ def load_shaderball_vertices():
     return np.ascontiguousarray(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "shaderball_vertices.npz"))["vertices"])
 
 
+def cube_shadow_views(pos, fov_degrees, near_z, far_z):
+    """bb::cubeShadowViews: the six view blocks (+X, -X, +Y, -Y, +Z, -Z) of a cube shadow map at `pos`, float32 [6, 36],
+    as Renderer.render_shadow_faces takes them"""
+    out = np.zeros((6, 36), np.float32)
+    lib().bbs_cube_shadow_views(_p(np.ascontiguousarray(pos, np.float32)), float(fov_degrees), float(near_z), float(far_z), _p(out))
+    return out
+
+
 @dataclass
 class FreeLookCamera:
     pos: tuple = (0.0, 0.0, 0.0)

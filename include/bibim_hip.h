@@ -476,8 +476,22 @@ int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uin
  *   classes  as bbr_read_shadow_mask reports them: 0 not covered, 1 LIT, 2 SHADOWED, 3 OUTSIDE
  *   loop     the iteration of light `light_index` of a SHADOWED fragment contributes nothing, like a light of unknown type;
  *            everything else is the light loop's.  A light_index >= NumLights shadows nothing.
- * Deviations: a hard compare (no filtering of the map), one caster, a point light gets the one frustum the caller chose, and
- * the deferred background colour is evaluated without the test.
+ * Deviations: a hard compare (no filtering of the map), one caster, and the deferred background colour is evaluated without
+ * the test.
+ *
+ * Faces.  The caster has an ordered list of F = 1 .. 6 frusta (bbr_render_shadow_faces; bbr_render_shadow_map is F = 1), each
+ * with a map of its own, for ONE light_index and ONE bias:
+ *   maps     map_f is the map above for L_f; every rank renders all of them
+ *   test     for f = 0 .. F - 1 in this order: cls_f = the test above with M_f = L_f.proj * L_f.view and map_f.  The first
+ *            cls_f != OUTSIDE is the fragment's class and f its face.  None: OUTSIDE, face 255
+ * Six 90-degree-class frusta at a point light's position are a cube map (bb::cubeShadowViews / bbs_cube_shadow_views,
+ * include/bibim_scene.h: +X, -X, +Y, -Y, +Z, -Z); two or three nested orthographic ones are cascades of a directional light.
+ *   overlap  where frusta overlap, the earlier face wins; the later face's map is not read there
+ *   seams    a fragment OUTSIDE every face is lit.  With faces of exactly 90 degrees that happens ON the seam planes (both
+ *            neighbours reject a coordinate that lands on xs == S or ys == S): give a cube a few degrees over 90 (96 is what
+ *            the tests use; the overlap rule then decides the doubly covered rim)
+ *   memory   F * S * S * 4 bytes of maps; the pass's buffers are shared by the faces.  A later call with fewer faces keeps
+ *            the larger buffer
  *
  * bbr_render_shadow_map renders the map from `light_view_block` (144 bytes in ViewUniformBlock layout; view and proj are
  * used, the rest is ignored).  It renders the recorded draws and is valid inside a frame after the bbr_draw calls (the draws
@@ -486,6 +500,9 @@ int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uin
  * when the map is complete.  From then on every submitted frame (bbr_end_frame, bbr_replay_frame, the re-renders of the
  * read-backs) uses the map, the index and the bias, until the next call, a change of the option or bbr_destroy; bbr_resize
  * keeps them.  BBR_ERR_INVALID_ARGUMENT: the option is 0, light_index outside [0, 100), a NULL block, a NaN bias.
+ * bbr_render_shadow_faces is the same call with `n_faces` consecutive view blocks (n_faces outside 1 .. 6:
+ * BBR_ERR_INVALID_ARGUMENT): one drain, one upload of the draws, the faces back to back, one wait; if a capacity overflows
+ * in any face, it grows and all faces are rendered again.  With n_faces = 1 it is bbr_render_shadow_map, bit for bit.
  * Works with both tile modes, both render passes, "present_fused", "max_anisotropy", "supersample" with either
  * "sample_shading" (the test runs per fine fragment), a partition, up to four frames in flight and bbr_replay_frame.
  *
@@ -494,11 +511,19 @@ int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uin
  *                         map has been rendered
  *   bbr_read_shadow_mask  width*height bytes: the class of every pixel of the last frame.  Re-renders it like
  *                         bbr_read_surface, with the same refusals ("supersample" >= 2, a partition), and INVALID_ARGUMENT
- *                         while no map is in use
+ *                         while no map is in use.  With F >= 2: the class of the deciding face
+ *   bbr_read_shadow_face  the S x S map of face `face`; as bbr_read_shadow_map (which reads face 0), and INVALID_ARGUMENT
+ *                         for a face outside 0 .. F - 1
+ *   bbr_read_shadow_face_index  width*height bytes: the deciding face of every pixel of the last frame, 255 where the class
+ *                         is 0 or OUTSIDE.  The same re-render and the same refusals as bbr_read_shadow_mask
  * bbr_read_surface and bbr_read_gbuffer keep working while a map is in use: the re-rendered frame is the shadowed one. */
 int bbr_render_shadow_map(bbr_context *ctx, int32_t light_index, const void *light_view_block /* 144 B */, float bias);
 int bbr_read_shadow_map(bbr_context *ctx, float *out);
 int bbr_read_shadow_mask(bbr_context *ctx, uint8_t *out);
+int bbr_render_shadow_faces(bbr_context *ctx, int32_t light_index, int32_t n_faces, const void *light_view_blocks /* n_faces x 144 B */,
+                            float bias);
+int bbr_read_shadow_face(bbr_context *ctx, int32_t face, float *out);
+int bbr_read_shadow_face_index(bbr_context *ctx, uint8_t *out);
 
 /* ---- primitive-record read-back ----
  * What the vertex stage (k_geometry: forward_brdf.vert / gbuffer.vert, clip test, viewport, snap, triangle setup) wrote

@@ -200,6 +200,16 @@ inline int renderShadowMap(bbr_context *ctx, int32_t light, const ViewUniformBlo
   return bbr_render_shadow_map(ctx, light, &lightView, bias);
 }
 
+// The six faces of a cube map at a point light's position, in the order +X, -X, +Y, -Y, +Z, -Z: ViewMat = lookAt(pos, pos +
+// dir, up) with up (0,1,0) for the X and Z faces, (0,0,-1) for +Y and (0,0,1) for -Y; ProjMat = perspective(fovDegrees, 1,
+// nearZ, farZ).  At exactly 90 degrees fragments ON a seam plane are outside every face and therefore lit: take a few
+// degrees more (96), and the earlier face decides the overlap (include/bibim_hip.h, "Faces").
+void cubeShadowViews(const Float3 &pos, float fovDegrees, float nearZ, float farZ, ViewUniformBlock out[6]);
+// ... and the call that renders them (nFaces = 1 .. 6 consecutive blocks) for scene light `light`.
+inline int renderShadowFaces(bbr_context *ctx, int32_t light, const ViewUniformBlock *faces, int32_t nFaces, float bias) {
+  return bbr_render_shadow_faces(ctx, light, nFaces, faces, bias);
+}
+
 }  // namespace bb
 
 extern "C" {
@@ -218,6 +228,7 @@ void bbs_mat4_scale(float x, float y, float z, float *out);
 void bbs_mat4_rotate(int axis, float degrees, float *out); /* 0 x, 1 y, 2 z */
 void bbs_mat4_look_at(const float *eye, const float *target, const float *up, float *out);
 void bbs_mat4_perspective(float fov_degrees, float aspect, float near_z, float far_z, float *out);
+void bbs_cube_shadow_views(const float *pos3, float fov_degrees, float near_z, float far_z, void *out_view_blocks6 /* 6 x 144 B */);
 void bbs_camera_look(float yaw, float pitch, float *out3);
 void bbs_camera_view(const float *pos, float yaw, float pitch, float *out);
 void bbs_plane_mesh(void *out_vertices4, uint32_t *out_indices6);

@@ -1,0 +1,30 @@
+"""Register, scratch and LDS footprint of k_shade_shadow_faces (bbr_render_shadow_faces with two or more faces), from the
+compiler's own device listing, built the way tests/test_kernel_resources.py builds it (its fixture, compiled once more for this
+module).  No GPU is needed.
+
+k_shade_shadow_faces is k_shade_shadow with a wave-uniform loop over the faces in place of the one test.  Every instantiation --
+both tile shapes, forward and deferred, fp32 and presented output, the shipped form and the dumping one -- owns no scratch and no
+LDS.  The eight shipped forms stay at or under 128 vector registers, the allocation step of the four waves per SIMD
+k_shade_aniso runs at (ANISO_VGPR_MAX).  The dumping forms are diagnostics (the read-backs' re-render) and never on a frame's
+path: their count is printed, not bounded."""
+import pytest
+
+from test_kernel_resources import ANISO_VGPR_MAX, _one, kernels  # noqa: F401  (the fixture)
+
+
+@pytest.mark.parametrize("dump", [0, 1])
+@pytest.mark.parametrize("present", [0, 1])
+@pytest.mark.parametrize("deferred", [0, 1])
+@pytest.mark.parametrize("tile", [32, 64])
+def test_k_shade_shadow_faces_footprint(kernels, tile, deferred, present, dump):  # noqa: F811
+    k = _one(kernels, f"_ZN3bbr20k_shade_shadow_facesILi{tile}ELi{tile}ELb{deferred}ELb{present}ELb{dump}EEE")
+    print(f"k_shade_shadow_faces<{tile},{tile},{deferred},{present},{dump}>: {k}")
+    assert k["private_segment_fixed_size"] == 0, "k_shade_shadow_faces owns scratch"
+    assert k["group_segment_fixed_size"] == 0, "k_shade_shadow_faces owns LDS"
+    if not dump:
+        assert k["vgpr_count"] + k["agpr_count"] <= ANISO_VGPR_MAX
+
+
+def test_every_instantiation_is_there(kernels):  # noqa: F811
+    names = [n for n in kernels if n.startswith("_ZN3bbr20k_shade_shadow_facesILi")]
+    assert len(names) == 16, names
