@@ -19,6 +19,7 @@
 //   k_resolve_depth    option "depth_resolve": the depth (and winner) of one sample of the block for the output pixel
 //   k_shade_shadow     option "shadow_map": k_shade_aniso's fragment stage with a shadow test in front of one light's iteration
 //   k_shade_shadow_faces    ... with 2 .. 6 faces for that light (bbr_render_shadow_faces): cube maps, cascades
+//   k_shade_shadow_pcf      option "shadow_filter" 1 .. 2: ... with a 3 x 3 or 5 x 5 box of compares, 1 .. 6 faces
 //
 // Arithmetic contract: every floating-point expression below has the same operand order and the same
 // explicit fmaf() placement as the CPU oracle; the file is compiled with -ffp-contract=off, IEEE
@@ -2037,9 +2038,11 @@ struct ConstLights {
 };
 
 // `skip(li)`: this fragment takes nothing from light li (option "shadow_map": the caster's iteration of a shadowed fragment).
-// The default skips nothing and leaves no trace in the code.
+// `skip.colour(li, cr, cg, cb)`: the cooked colour iteration li runs with (option "shadow_filter": the caster's, scaled, for a
+// fragment whose taps are partly lit).  The default skips nothing, changes nothing and leaves no trace in the code.
 struct NoSkip {
   BB_DEV bool operator()(int) const { return false; }
+  BB_DEV void colour(int, float &, float &, float &) const {}
 };
 template <typename Lights, class Skip = NoSkip>
 BB_DEV float4 light_surface(const ShadeParams &sp, const Lights lights, f3 P, f3 normal, f3 albedo, float metallic,
@@ -2064,10 +2067,12 @@ BB_DEV float4 light_surface(const ShadeParams &sp, const Lights lights, f3 P, f3
   if (sp.num_lights > 0) nxt = lights.get(0);
   for (int li = 0; li < sp.num_lights; ++li) {
     const CookedLight cl = nxt;
-    const float px = cl.px, py = cl.py, pz = cl.pz, cr = cl.cr, cg = cl.cg, cb = cl.cb;
+    const float px = cl.px, py = cl.py, pz = cl.pz;
+    float cr = cl.cr, cg = cl.cg, cb = cl.cb;
     const int type = Lights::type_of(cl);
     nxt = lights.get(li + 1 < sp.num_lights ? li + 1 : li);
     if (skip(li)) continue;  // (as an unknown type, below: nothing)
+    skip.colour(li, cr, cg, cb);
     f3 L;
     float att;
     if (type == 0 || type == 1) {
@@ -2353,13 +2358,13 @@ BB_DEV f3 sample_map_rgb(const TexDesc &td, float u, float v) {
 //   classes 0 not covered, 1 LIT, 2 SHADOWED, 3 OUTSIDE (bbr_read_shadow_mask)
 //   loop    the iteration of light `light` of a SHADOWED fragment contributes nothing: the `continue` of an unknown light
 //           type.  Every other operation, and the operand order, is light_surface's
-// Deviations: a hard compare, one caster, and the deferred background colour (k_deferred_background) is evaluated without the
+// Deviations: a hard compare (option "shadow_filter": a box of them, ShadowPcfTest below), one caster, and the deferred background colour (k_deferred_background) is evaluated without the
 // test.  A point light gets up to six frusta (ShadowFacesTest, below): a fragment on a seam of exactly-90-degree faces is
 // outside all of them and lit, and where frusta overlap the earlier one decides.
 // M and the scalars are kernel arguments (scalar registers); the map costs one 4-byte gather per fragment, and only lanes
 // inside the map address it: i and j lie in [0, S - 1].
 // ------------------------------------------------------------------------------------------------
-enum ShadowClass : int { kShadowNone = 0, kShadowLit = 1, kShadowShadowed = 2, kShadowOutside = 3 };
+enum ShadowClass : int { kShadowNone = 0, kShadowLit = 1, kShadowShadowed = 2, kShadowOutside = 3, kShadowPartial = 4 /* "shadow_filter" */ };
 struct ShadowArgs {
   Mat4 m;            // proj_view(L)
   const float *map;  // S x S depths, row-major
@@ -2373,6 +2378,7 @@ struct ShadowSkip {
   int light;
   bool shadowed;
   BB_DEV bool operator()(int li) const { return shadowed && li == light; }
+  BB_DEV void colour(int, float &, float &, float &) const {}
 };
 // What surface_colour asks of its `shadow`: on() classifies the fragment and says which iteration the light loop skips.
 struct NoShadow {
@@ -2450,6 +2456,99 @@ struct ShadowFacesTest {
       if (a.face) a.face[o] = (uint8_t)face;
     }
     return ShadowSkip{a.light, cls == kShadowShadowed};
+  }
+};
+
+// Percentage-closer filtering (option "shadow_filter" = R in 1 .. 2; k_shade_shadow_pcf): a (2R+1) x (2R+1) box of the hard
+// rule's compares, K = 9 or 25 taps.  The rule (restated independently in tests/shadow_filter_reference.py):
+//   face, i, j, t   the rules above, unchanged: the deciding face f is the first the fragment is not OUTSIDE of, and OUTSIDE
+//           and "not covered" are decided before any tap is read
+//   taps    for dj = -R .. R, di = -R .. R: texel = map_f[clamp(j + dj, 0, S - 1)][clamp(i + di, 0, S - 1)]; the tap is lit
+//           iff !(texel > t) (a NaN t: every tap is lit).  k = the number of lit taps, an integer: the order has no meaning
+//   classes 1 LIT (k = K), 2 SHADOWED (k = 0), 4 PARTIAL (0 < k < K); 0 and 3 as above
+//   loop    k = K: untouched.  k = 0: the caster's iteration contributes nothing.  Otherwise it runs with the cooked colour
+//           color[c] * (intensity * v), v = (float)k * RK, RK[9], RK[25] = the binary32 nearest 1/9, 1/25: the caster's
+//           intensity replaced by the binary32 product intensity * v, everything else light_surface's
+// Deviations: a box, not bilinear weights; one t for all taps (no receiver-plane bias); taps never leave the deciding face's
+// map (on a cube they clamp at the face's edge); the deferred background stays untested.
+// R is a kernel argument, a scalar: one kernel serves both radii.  A tap is one 4-byte gather; a window's rows are walked one
+// after the other and a row's 2R + 1 gathers are issued together (lit_taps; the plain double loop paid K dependent round
+// trips: profiles/shadow_filter.txt).  Only lanes inside face f address its map, and a clamped address lies in [0, S - 1] by
+// construction.  The caster's raw colour and intensity are read from the
+// frame's light block through the scalar cache (wave-uniform), guarded by light < num_lights.
+struct ShadowPcfArgs {
+  ShadowFacesArgs f;    // F = 1 .. 6 faces; `mask`, `face`: the DUMP form's outputs, as above
+  const Light *lights;  // the frame's light block
+  uint8_t *taps;        // the DUMP form's third output (bbr_read_shadow_taps): k per pixel, 255 where OUTSIDE, or nullptr
+  int32_t num_lights;
+  int32_t radius;       // R
+};
+typedef const Light __attribute__((address_space(4))) *ConstLight;
+struct ShadowScale {
+  int light;
+  bool shadowed, partial;
+  float iv;          // intensity * v
+  float r, g, b;     // the caster's raw colour (scalars)
+  BB_DEV bool operator()(int li) const { return shadowed && li == light; }
+  BB_DEV void colour(int li, float &cr, float &cg, float &cb) const {
+    if (partial && li == light) { cr = r * iv; cg = g * iv; cb = b * iv; }
+  }
+};
+template <bool DUMP>
+struct ShadowPcfTest {
+  const ShadowPcfArgs &a;
+  // k of the window round texel (i, j): the rows one after the other, a row's 2R + 1 gathers issued together
+  template <int RADIUS>
+  BB_DEV int lit_taps(const float *face_map, int i, int j, float t) const {
+    const int last = a.f.side - 1;
+    int n = 0;
+#pragma unroll 1
+    for (int dj = -RADIUS; dj <= RADIUS; ++dj) {
+      const float *row = face_map + (size_t)min(max(j + dj, 0), last) * (size_t)a.f.side;
+      float texel[2 * RADIUS + 1];
+#pragma unroll
+      for (int di = -RADIUS; di <= RADIUS; ++di) texel[di + RADIUS] = row[min(max(i + di, 0), last)];
+#pragma unroll
+      for (int q = 0; q <= 2 * RADIUS; ++q) n += texel[q] > t ? 0 : 1;
+    }
+    return n;
+  }
+  BB_DEV ShadowScale on(const FrameParams &fp, f3 P, bool valid, int gx, int gy) const {
+    const ShadowFacesArgs &s = a.f;
+    const float side = (float)s.side;
+    const size_t texels = (size_t)s.side * (size_t)s.side;
+    const int R = a.radius, K = (2 * R + 1) * (2 * R + 1);
+    int cls = kShadowOutside, face = 255, k = 255;
+    for (int f = 0; f < s.faces; ++f) {
+      const bool undecided = cls == kShadowOutside;
+      if (__ballot(undecided) == 0ull) break;
+      const f4 c = mat4_mul(s.m[f], f4{P.x, P.y, P.z, 1.0f});
+      const float r = bb_rcp(c.w);  // (of a w <= 0 too: not used then)
+      const float xs = fmaf(c.x * r, s.half, s.half), ys = fmaf(c.y * r, s.half, s.half);
+      const bool inside = c.w > 0.0f && xs >= 0.0f && xs < side && ys >= 0.0f && ys < side;
+      if (undecided && inside) {
+        const int i = (int)xs, j = (int)ys;  // 0 .. S - 1
+        const float t = c.z * r + s.bias;
+        const float *face_map = s.map + (size_t)f * texels;
+        const int n = R == 1 ? lit_taps<1>(face_map, i, j, t) : lit_taps<2>(face_map, i, j, t);
+        k = n;
+        cls = n == K ? kShadowLit : (n == 0 ? kShadowShadowed : kShadowPartial);
+        face = f;
+      }
+    }
+    if (DUMP && valid) {
+      const size_t o = (size_t)gy * (size_t)fp.width + (size_t)gx;
+      if (s.mask) s.mask[o] = (uint8_t)cls;
+      if (s.face) s.face[o] = (uint8_t)face;
+      if (a.taps) a.taps[o] = (uint8_t)k;
+    }
+    float intensity = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+    if (s.light < a.num_lights) {
+      ConstLight l = (ConstLight)a.lights + s.light;
+      intensity = l->intensity; cr = l->color[0]; cg = l->color[1]; cb = l->color[2];
+    }
+    const float rk = R == 1 ? 1.0f / 9.0f : 1.0f / 25.0f;
+    return ShadowScale{s.light, cls == kShadowShadowed, cls == kShadowPartial, intensity * ((float)k * rk), cr, cg, cb};
   }
 };
 
@@ -3128,6 +3227,23 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_shadow_faces(
   shade_item_list<TILE_W, TILE_H, DEFERRED, PRESENT, DUMP>(items, item_count, frags, frag_count, recs, clip_arena, fp, sp, cooked, materials, out,
                                                            gbuffer, tables, out8, ctr, ctr_done, item_groups, AnisoFilter{max_aniso}, dump,
                                                            ShadowFacesTest<DUMP>{shadow});
+}
+
+// k_shade_shadow_pcf: k_shade_shadow / k_shade_shadow_faces with option "shadow_filter" (the rule: in front of ShadowPcfTest), one
+// kernel for 1 .. 6 faces and both radii.  DUMP as in k_shade_shadow_faces, plus k of every pixel where `shadow.taps` is set.
+template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
+__global__ __launch_bounds__(kShadeThreads) void k_shade_shadow_pcf(
+    const uint32_t *__restrict__ items, const uint32_t *__restrict__ item_count,
+    const unsigned long long *__restrict__ frags, const uint32_t *__restrict__ frag_count,
+    const ShadeRec *__restrict__ recs, const ClipSlot *__restrict__ clip_arena,
+    FrameParams fp, ShadeParams sp, const CookedLight *__restrict__ cooked,
+    const MaterialDesc *__restrict__ materials, float4 *__restrict__ out,
+    uint2 *__restrict__ gbuffer, const SrgbTables *__restrict__ tables, uint32_t *__restrict__ out8,
+    Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups, int max_aniso,
+    float *__restrict__ dump, ShadowPcfArgs shadow) {
+  shade_item_list<TILE_W, TILE_H, DEFERRED, PRESENT, DUMP>(items, item_count, frags, frag_count, recs, clip_arena, fp, sp, cooked, materials, out,
+                                                           gbuffer, tables, out8, ctr, ctr_done, item_groups, AnisoFilter{max_aniso}, dump,
+                                                           ShadowPcfTest<DUMP>{shadow});
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -88,6 +88,7 @@ struct FrameMode {
   int depth_rule = 0;    // n >= 2: option "depth_resolve" (0: no depth is kept; else k_resolve_depth's MODE, VkResolveModeFlagBits)
   bool shadow = false;   // option "shadow_map" > 0 and a map has been rendered (bbr_render_shadow_map): k_shade_shadow shades
   bool shadow_faces = false;  // ... two or more of them (bbr_render_shadow_faces): k_shade_shadow_faces
+  int shadow_filter = 0;      // ... and option "shadow_filter" R >= 1: k_shade_shadow_pcf, whatever the number of faces
   bool fused = false;    // option "present_fused": the frame is written as presented RGBA8 (the slot's d_present) ...
   bool shade_presents() const { return fused && !resolve; }   // ... by k_raster / k_shade
   bool resolve_presents() const { return fused && resolve; }  // ... by k_resolve (a presented byte cannot be averaged): then
@@ -261,6 +262,7 @@ struct ExtentDumps {
   DeviceBuffer<uint2> d_gbuffer;  // width*height*4 (four RGBA16F texels per pixel), only while bbr_read_gbuffer runs
   DeviceBuffer<uint8_t> d_shadow_mask;  // width*height classes, only while bbr_read_shadow_mask runs
   DeviceBuffer<uint8_t> d_shadow_face;  // width*height deciding faces, only while bbr_read_shadow_face_index runs (F >= 2)
+  DeviceBuffer<uint8_t> d_shadow_taps;  // width*height lit-tap counts, only while bbr_read_shadow_taps runs ("shadow_filter" >= 1)
 };
 
 // Option "shadow_map": everything the feature owns.  Changing the option's value drops the group; at 0 nothing of it exists.
@@ -359,6 +361,7 @@ struct bbr_context : ExtentDumps {
   DeviceBuffer<MipTable> d_mip_tables;  // one per material slot, beside d_materials (only while "mip_levels" >= 2)
   int shadow_map = 0;             // option "shadow_map": 0 = off, 1..8192 = the side S of the map (k_shade_shadow once a map exists)
   ShadowOwned shadow;
+  int shadow_filter = 0;          // option "shadow_filter": 0 = the hard compare, 1..2 = the radius R of the box (k_shade_shadow_pcf)
   bool dump_shadow_mask = false;  // (bbr_read_shadow_mask: together with dump_surface, the DUMP form of k_shade_shadow)
   bool dump_surface = false;
   DeviceBuffer<float> d_surface;  // width*height*32 floats, only while bbr_read_surface runs
@@ -488,6 +491,7 @@ FrameMode frame_mode(const bbr_context *c) {
   m.fused = c->present_fused;
   m.shadow = c->shadow_map > 0 && c->shadow.valid;
   m.shadow_faces = m.shadow && c->shadow.args.faces > 1;
+  m.shadow_filter = m.shadow ? c->shadow_filter : 0;
   m.depth_rule = m.resolve ? c->depth_resolve : 0;
   // (bbr_draw_overlays is refused on a partition, and with n >= 2 unless option "depth_resolve" names a rule)
   m.depth = c->overlays && c->world == 1 && (!m.resolve || m.depth_rule != 0);
@@ -900,14 +904,18 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
     };
     uint32_t *groups = short_frame ? nullptr : s.d_item_groups.ptr;
     if (mode.shadow || c->mip_levels > 1 || c->max_anisotropy > 1 || c->dump_surface) {
-      // a valid shadow map: k_shade_shadow, k_shade_shadow_faces (never together with "mip_levels" >= 2: refused_shadow_pair); option "mip_levels":
+      // a valid shadow map: k_shade_shadow, k_shade_shadow_faces, k_shade_shadow_pcf (never together with "mip_levels" >= 2: refused_shadow_pair); option "mip_levels":
       // k_shade_mip; option "max_anisotropy" / bbr_read_surface (the kernels' DUMP forms): k_shade_aniso.
       // Each is one launch whose waves walk the whole item list.
       if (ev) (void)hipEventRecord(ev[3], ss);
       float *surface = c->dump_surface ? c->d_surface.ptr : nullptr;
       with_bool(c->mip_levels > 1, [&](auto mip) { with_bool(c->dump_surface, [&](auto dump) {
         constexpr bool DUMP = decltype(dump)::value;
-        if (mode.shadow_faces) {
+        if (mode.shadow_filter) {
+          ShadowPcfArgs sa = {c->shadow.args, d_lights, nullptr, sp.num_lights, mode.shadow_filter};
+          if (DUMP && c->dump_shadow_mask) sa.f.mask = c->d_shadow_mask.ptr, sa.f.face = c->d_shadow_face.ptr, sa.taps = c->d_shadow_taps.ptr;
+          launch(k_shade_shadow_pcf<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface, sa);
+        } else if (mode.shadow_faces) {
           ShadowFacesArgs sa = c->shadow.args;
           sa.mask = (DUMP && c->dump_shadow_mask) ? c->d_shadow_mask.ptr : nullptr;
           sa.face = (DUMP && c->dump_shadow_mask) ? c->d_shadow_face.ptr : nullptr;
@@ -1730,7 +1738,9 @@ extern "C" int bbr_read_shadow_map(bbr_context *c, float *host) { return bbr_rea
 
 // The class (and, F >= 2, the deciding face) of every pixel of the last frame: the DUMP form of k_shade_shadow /
 // k_shade_shadow_faces (with it the surface dump, which is dropped).  With one face the face index follows from the class.
-static int read_shadow_classes(bbr_context *c, const std::string &who, uint8_t *host, bool want_face) {
+enum class ShadowDump { kMask, kFace, kTaps };
+static int read_shadow_classes(bbr_context *c, const std::string &who, uint8_t *host, ShadowDump want) {
+  const bool want_face = want == ShadowDump::kFace;
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": NULL");
@@ -1741,9 +1751,11 @@ static int read_shadow_classes(bbr_context *c, const std::string &who, uint8_t *
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": not available on a partitioned context");
   const size_t pixels = (size_t)c->width * c->height;
   int rc = BBR_OK;
-  if (mode.shadow_faces) {  // (an uncovered pixel keeps the fill: face 255)
-    hipError_t e = c->d_shadow_face.ensure(pixels);
-    if (e == hipSuccess) e = hipMemset(c->d_shadow_face.ptr, 0xFF, pixels);
+  const bool want_taps = want == ShadowDump::kTaps && mode.shadow_filter;  // (R = 0: K = 1, k follows from the class)
+  for (DeviceBuffer<uint8_t> *b : {mode.shadow_faces ? &c->d_shadow_face : nullptr, want_taps ? &c->d_shadow_taps : nullptr}) {
+    if (!b || rc != BBR_OK) continue;  // (an uncovered pixel keeps the fill: face 255, k 255)
+    hipError_t e = b->ensure(pixels);
+    if (e == hipSuccess) e = hipMemset(b->ptr, 0xFF, pixels);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) rc = fail(c, BBR_ERR_HIP, who + ": " + hipGetErrorString(e));
   }
@@ -1753,21 +1765,30 @@ static int read_shadow_classes(bbr_context *c, const std::string &who, uint8_t *
     c->dump_surface = false;
   }
   if (rc == BBR_OK) {
-    const uint8_t *src = (want_face && mode.shadow_faces) ? c->d_shadow_face.ptr : c->d_shadow_mask.ptr;
+    const uint8_t *src = (want_face && mode.shadow_faces) ? c->d_shadow_face.ptr : (want_taps ? c->d_shadow_taps.ptr : c->d_shadow_mask.ptr);
     hipError_t e = hipMemcpy(host, src, pixels, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(c, BBR_ERR_HIP, who + ": " + hipGetErrorString(e));
     else if (want_face && !mode.shadow_faces)
-      for (size_t i = 0; i < pixels; ++i) host[i] = (host[i] == kShadowLit || host[i] == kShadowShadowed) ? 0 : 255;
+      for (size_t i = 0; i < pixels; ++i) host[i] = (host[i] == kShadowLit || host[i] == kShadowShadowed || host[i] == kShadowPartial) ? 0 : 255;
+    else if (want == ShadowDump::kTaps && !want_taps)
+      for (size_t i = 0; i < pixels; ++i) host[i] = host[i] == kShadowLit ? 1 : (host[i] == kShadowShadowed ? 0 : 255);
   }
   c->d_shadow_mask.release();  // (uncovered pixels are the zeros of a fresh buffer)
   c->d_shadow_face.release();
+  c->d_shadow_taps.release();
   c->d_surface.release();
   return rc;
 }
 
-extern "C" int bbr_read_shadow_mask(bbr_context *c, uint8_t *host) { return read_shadow_classes(c, "read_shadow_mask", host, false); }
+extern "C" int bbr_read_shadow_mask(bbr_context *c, uint8_t *host) {
+  return read_shadow_classes(c, "read_shadow_mask", host, ShadowDump::kMask);
+}
 extern "C" int bbr_read_shadow_face_index(bbr_context *c, uint8_t *host) {
-  return read_shadow_classes(c, "read_shadow_face_index", host, true);
+  return read_shadow_classes(c, "read_shadow_face_index", host, ShadowDump::kFace);
+}
+// k, the number of lit taps, of every pixel of the last frame (option "shadow_filter"; 255 where the class is 0 or OUTSIDE)
+extern "C" int bbr_read_shadow_taps(bbr_context *c, uint8_t *host) {
+  return read_shadow_classes(c, "read_shadow_taps", host, ShadowDump::kTaps);
 }
 
 // ================================================================================================
@@ -2893,6 +2914,14 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
     if ((int)value != c->shadow_map) {
       c->shadow_map = (int)value;
       c->shadow = ShadowOwned();
+    }
+  } else if (n == "shadow_filter") {
+    // the radius of the box of compares; stored at any "shadow_map", and the map stays.  The current frame was shaded under the
+    // other rule: there is none any more
+    if (value < 0 || value > 2) return fail(c, BBR_ERR_INVALID_ARGUMENT, "shadow_filter: 0 (the hard compare), 1 (3 x 3 taps) or 2 (5 x 5 taps)");
+    if ((int)value != c->shadow_filter) {
+      c->shadow_filter = (int)value;
+      forget_current_frame(c);
     }
   } else if (n == "static_records") {
     if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "static_records: 1 (write a static draw's record part once) or 0 (every frame)");

@@ -303,9 +303,16 @@ class Renderer:
 
     def read_shadow_mask(self):
         """the shadow class of every pixel of the last frame, [h, w] uint8: 0 not covered, 1 lit, 2 shadowed, 3 outside the
-        map; re-renders the last frame"""
+        map, 4 partly lit (option "shadow_filter" >= 1); re-renders the last frame"""
         out = np.empty((self.height, self.width), np.uint8)
         self._check(self._L.bbr_read_shadow_mask(self._ctx, _ptr(out)))
+        return out
+
+    def read_shadow_taps(self):
+        """k, the number of lit taps of every pixel of the last frame, [h, w] uint8: 0 .. (2R + 1)^2 under option "shadow_filter"
+        = R (R = 0: 1 lit, 0 shadowed), 255 where the pixel is not covered or outside the map; re-renders the last frame"""
+        out = np.empty((self.height, self.width), np.uint8)
+        self._check(self._L.bbr_read_shadow_taps(self._ctx, _ptr(out)))
         return out
 
     def read_material_level(self, material, map_index, level):

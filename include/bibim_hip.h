@@ -274,6 +274,12 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            context and drops the map and its pass buffers.  Anything else: INVALID_ARGUMENT, the option
  *                            unchanged.  Refused (INVALID_ARGUMENT) at > 0 while "mip_levels" >= 2, in whichever order the
  *                            two are set: k_shade_shadow has no trilinear form
+ *   "shadow_filter" 0..2     percentage-closer filtering of the shadow test ("shadow mapping" below, "Filtering").  0
+ *                            (default): the hard compare -- the kernels, launches and bits of "shadow_map" alone.  R >= 1: a
+ *                            (2R+1) x (2R+1) box of compares, 9 or 25 taps; frames under a map are shaded by
+ *                            k_shade_shadow_pcf, whatever the number of faces.  Stored at any "shadow_map" (in effect once a
+ *                            map exists); setting it drains the context, leaves no current frame and keeps the map.
+ *                            Anything else: INVALID_ARGUMENT, the option unchanged.  "mip_levels" >= 2 stays refused
  *   "supersample" 1..4       n x n supersampling: rasterizationSamples = n^2 on a regular grid, sampleShadingEnable with
  *                            minSampleShading = 1 and VK_RESOLVE_MODE_AVERAGE (the reference pins 1 sample,
  *                            src/render.cpp:1104-1112).  1 (default): nothing changes, no kernel of the option runs.
@@ -473,11 +479,11 @@ int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uin
  *            chain.  !(c.w > 0): OUTSIDE.  r = the correctly rounded 1 / c.w, h = 0.5f * S, xs = fmaf(c.x * r, h, h), ys =
  *            fmaf(c.y * r, h, h).  !(xs >= 0 && xs < S && ys >= 0 && ys < S): OUTSIDE (NaN lands here).  i = (int)xs, j =
  *            (int)ys, t = c.z * r + bias.  SHADOWED iff map[j][i] > t (a NaN t is not shadowed); otherwise LIT.
- *   classes  as bbr_read_shadow_mask reports them: 0 not covered, 1 LIT, 2 SHADOWED, 3 OUTSIDE
+ *   classes  as bbr_read_shadow_mask reports them: 0 not covered, 1 LIT, 2 SHADOWED, 3 OUTSIDE (4 PARTIAL: "Filtering")
  *   loop     the iteration of light `light_index` of a SHADOWED fragment contributes nothing, like a light of unknown type;
  *            everything else is the light loop's.  A light_index >= NumLights shadows nothing.
- * Deviations: a hard compare (no filtering of the map), one caster, and the deferred background colour is evaluated without
- * the test.
+ * Deviations: a hard compare unless option "shadow_filter" is set ("Filtering" below), one caster, and the deferred
+ * background colour is evaluated without the test.
  *
  * Faces.  The caster has an ordered list of F = 1 .. 6 frusta (bbr_render_shadow_faces; bbr_render_shadow_map is F = 1), each
  * with a map of its own, for ONE light_index and ONE bias:
@@ -492,6 +498,25 @@ int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uin
  *            the tests use; the overlap rule then decides the doubly covered rim)
  *   memory   F * S * S * 4 bytes of maps; the pass's buffers are shared by the faces.  A later call with fewer faces keeps
  *            the larger buffer
+ *
+ * Filtering (option "shadow_filter" = R in 1 .. 2; tests/shadow_filter_reference.py).  K = (2R+1)^2 compares instead of one:
+ *   face, texel, t   exactly the rules above: the deciding face f is the first face the fragment is not OUTSIDE of (with one
+ *            face, that face); i, j and t = c.z * r + bias are taken on the P the light loop receives (deferred: after the
+ *            binary16 rounding).  OUTSIDE and "not covered" are unchanged and decided before any tap is read
+ *   taps     for dj = -R .. R and di = -R .. R, tap (di, dj) reads map_f[clamp(j + dj, 0, S - 1)][clamp(i + di, 0, S - 1)].
+ *            A tap is lit iff !(texel > t) -- the hard rule's compare, so a NaN t makes every tap lit.  k is the number of
+ *            lit taps, 0 .. K: an integer count, the tap order has no meaning.  Taps never leave the deciding face's map; on a
+ *            cube they clamp at the face's edge
+ *   classes  0, 1 LIT (k = K), 2 SHADOWED (k = 0) and 3 OUTSIDE as above; 4 PARTIAL (0 < k < K)
+ *   loop     k = K: the caster's iteration is untouched.  k = 0: it contributes nothing.  0 < k < K: it runs with the caster's
+ *            cooked colour replaced, per channel, by color[c] * (intensity * v), v = (float)k * RK, RK[9] and RK[25] the
+ *            binary32 values nearest 1/9 and 1/25 (the device of R[3] in the resolve rule): the light loop with the caster's
+ *            intensity replaced by the binary32 product intensity * v, everything else unchanged.  A light_index >=
+ *            NumLights shadows and scales nothing
+ *   hence    with S = 1 every tap is texel (0, 0), k is 0 or K and the frame is the hard rule's, bit for bit; the same holds
+ *            wherever all K taps agree
+ * Deviations: a box, not bilinear weights; one t for all taps (no receiver-plane bias); no fetch across cube faces; the
+ * deferred background stays untested.
  *
  * bbr_render_shadow_map renders the map from `light_view_block` (144 bytes in ViewUniformBlock layout; view and proj are
  * used, the rest is ignored).  It renders the recorded draws and is valid inside a frame after the bbr_draw calls (the draws
@@ -516,6 +541,9 @@ int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uin
  *                         for a face outside 0 .. F - 1
  *   bbr_read_shadow_face_index  width*height bytes: the deciding face of every pixel of the last frame, 255 where the class
  *                         is 0 or OUTSIDE.  The same re-render and the same refusals as bbr_read_shadow_mask
+ *   bbr_read_shadow_taps  width*height bytes: k of every pixel of the last frame, 255 where the class is 0 or OUTSIDE.  With
+ *                         "shadow_filter" 0 it is K = 1: 1 where LIT, 0 where SHADOWED.  The same re-render and the same
+ *                         refusals as bbr_read_shadow_mask
  * bbr_read_surface and bbr_read_gbuffer keep working while a map is in use: the re-rendered frame is the shadowed one. */
 int bbr_render_shadow_map(bbr_context *ctx, int32_t light_index, const void *light_view_block /* 144 B */, float bias);
 int bbr_read_shadow_map(bbr_context *ctx, float *out);
@@ -524,6 +552,7 @@ int bbr_render_shadow_faces(bbr_context *ctx, int32_t light_index, int32_t n_fac
                             float bias);
 int bbr_read_shadow_face(bbr_context *ctx, int32_t face, float *out);
 int bbr_read_shadow_face_index(bbr_context *ctx, uint8_t *out);
+int bbr_read_shadow_taps(bbr_context *ctx, uint8_t *out);
 
 /* ---- primitive-record read-back ----
  * What the vertex stage (k_geometry: forward_brdf.vert / gbuffer.vert, clip test, viewport, snap, triangle setup) wrote
