@@ -106,6 +106,13 @@ SIGNATURES = {
     "bbr_read_shadow_face": (C.c_int, [_P, C.c_int32, C.c_void_p]),
     "bbr_read_shadow_face_index": (C.c_int, [_P, C.c_void_p]),
     "bbr_read_shadow_taps": (C.c_int, [_P, C.c_void_p]),
+    "bbr_render_shadow_caster": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float]),
+    "bbr_drop_shadow_caster": (C.c_int, [_P, C.c_int32]),
+    "bbr_get_shadow_casters": (C.c_int, [_P, C.c_void_p, C.c_void_p]),
+    "bbr_read_shadow_caster_face": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_void_p]),
+    "bbr_read_shadow_caster_mask": (C.c_int, [_P, C.c_int32, C.c_void_p]),
+    "bbr_read_shadow_caster_face_index": (C.c_int, [_P, C.c_int32, C.c_void_p]),
+    "bbr_read_shadow_caster_taps": (C.c_int, [_P, C.c_int32, C.c_void_p]),
     "bbr_read_material_level": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32)]),
     "bbr_read_packed_level": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

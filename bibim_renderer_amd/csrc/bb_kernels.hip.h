@@ -20,6 +20,7 @@
 //   k_shade_shadow     option "shadow_map": k_shade_aniso's fragment stage with a shadow test in front of one light's iteration
 //   k_shade_shadow_faces    ... with 2 .. 6 faces for that light (bbr_render_shadow_faces): cube maps, cascades
 //   k_shade_shadow_pcf      option "shadow_filter" 1 .. 2: ... with a 3 x 3 or 5 x 5 box of compares, 1 .. 6 faces
+//   k_shade_shadow_casters  bbr_render_shadow_caster: ... with up to eight casters, each in front of its own light's iteration
 //
 // Arithmetic contract: every floating-point expression below has the same operand order and the same
 // explicit fmaf() placement as the CPU oracle; the file is compiled with -ffp-contract=off, IEEE
@@ -2358,7 +2359,7 @@ BB_DEV f3 sample_map_rgb(const TexDesc &td, float u, float v) {
 //   classes 0 not covered, 1 LIT, 2 SHADOWED, 3 OUTSIDE (bbr_read_shadow_mask)
 //   loop    the iteration of light `light` of a SHADOWED fragment contributes nothing: the `continue` of an unknown light
 //           type.  Every other operation, and the operand order, is light_surface's
-// Deviations: a hard compare (option "shadow_filter": a box of them, ShadowPcfTest below), one caster, and the deferred background colour (k_deferred_background) is evaluated without the
+// Deviations: a hard compare (option "shadow_filter": a box of them, ShadowPcfTest below), one caster per light (up to eight lights: ShadowCastersTest below), and the deferred background colour (k_deferred_background) is evaluated without the
 // test.  A point light gets up to six frusta (ShadowFacesTest, below): a fragment on a seam of exactly-90-degree faces is
 // outside all of them and lit, and where frusta overlap the earlier one decides.
 // M and the scalars are kernel arguments (scalar registers); the map costs one 4-byte gather per fragment, and only lanes
@@ -2549,6 +2550,154 @@ struct ShadowPcfTest {
     }
     const float rk = R == 1 ? 1.0f / 9.0f : 1.0f / 25.0f;
     return ShadowScale{s.light, cls == kShadowShadowed, cls == kShadowPartial, intensity * ((float)k * rk), cr, cg, cb};
+  }
+};
+
+// Casters (bbr_render_shadow_caster; k_shade_shadow_casters): up to kMaxShadowCasters = 8 caster SLOTS per context, 0 .. 7.  A slot
+// in use holds a light index, F = 1 .. 6 view blocks, their F maps of S x S and a bias; S ("shadow_map") and R ("shadow_filter")
+// are the context's.  The caster of bbr_render_shadow_map / bbr_render_shadow_faces is slot 0.  The rule (DESIGN.md section 3,
+// "Casters"; restated independently in tests/shadow_casters_reference.py):
+//   maps    slot s, face f: the map rule above for that view block.  Every rank renders all of them
+//   test    for every slot in use, independently of the others: (class_s, face_s, k_s) = the rules above with that slot's
+//           matrices, maps and bias, on the P the light loop receives.  R = 0: the first face not OUTSIDE and the hard compare,
+//           K = 1, k = 0 or 1.  R >= 1: the box of K = 9 or 25 compares clamped inside the deciding face.  Slots do not see
+//           each other
+//   loop    iteration li looks for the slot in use whose light index is li (there is at most one).  None, or class OUTSIDE, or
+//           k = K: untouched.  k = 0: the iteration contributes nothing (the `continue` of an unknown type).  0 < k < K: it runs
+//           with the cooked colour color[c] * (intensity * ((float)k * RK)).  The lights' order, every other operation and the
+//           accumulation order are light_surface's.  A slot whose light index is >= NumLights changes nothing
+// Hence: one slot in use, whichever, gives the frame of that caster in slot 0; permuting casters over slots changes no bit; a
+// caster at bias 2, or on a light beyond the frame's, leaves the frame of the others alone.
+// Deviations kept: the deferred background stays untested; a box, one t per window, no fetch across faces.  New: one slot per
+// light -- two slots naming one light are refused, not combined.
+// The casters do not fit kernel arguments (8 x 6 Mat4 = 3 KB): the kernel gets a pointer to a table the host owns and writes
+// only while no frame is in flight, and reads it wave-uniformly through the scalar cache (constant address space, like
+// ConstLight): the slot index s and the face index f are scalars.  A lane carries k_s out of on() -- one byte per slot, OUTSIDE
+// stored as K, two registers for the eight -- and nothing else; the light loop finds the slot of li in the table's host-built
+// light -> slot lookup, extracts that byte and forms the scale from the light's scalars there.  Only lanes inside face f of slot
+// s address that map: i, j in [0, S - 1] by the comparisons (and the clamps), f < F_s and s < 8 by the loop bounds.
+constexpr int kMaxShadowCasters = 8;
+struct ShadowCasterEntry {
+  Mat4 m[kMaxShadowFaces];  // proj_view(L_f)
+  const float *map;         // F maps of S x S depths, face f at map + f * S * S
+  int32_t light;            // the caster's index in the frame's light list
+  int32_t faces;            // F; 0: the slot is not in use
+  float bias;
+  int32_t pad_;
+};
+struct ShadowCasterTable {
+  ShadowCasterEntry slot[kMaxShadowCasters];
+  int32_t slot_of_light[kMaxNumLights];  // the slot in use whose light index this is, or -1
+};
+struct ShadowCastersArgs {
+  const ShadowCasterTable *table;
+  const Light *lights;  // the frame's light block
+  uint8_t *mask;        // the DUMP form's outputs for slot `dump_slot`: class, deciding face and k per pixel, or nullptr
+  uint8_t *face;
+  uint8_t *taps;
+  int32_t num_lights;
+  int32_t radius;       // R = 0 .. 2
+  int32_t side;         // S
+  int32_t dump_slot;
+  float half;           // 0.5f * S
+};
+typedef const ShadowCasterTable __attribute__((address_space(4))) *ConstCasters;
+struct ShadowCastersSkip {
+  ConstCasters table;
+  ConstLight lights;
+  int K;           // (scalars)
+  float rk;
+  uint32_t k[2];   // per lane: byte s & 3 of word s >> 2 = k_s, K where slot s is OUTSIDE, not in use or not evaluated
+  BB_DEV int count(int li) const {
+    const int s = table->slot_of_light[li];
+    if (s < 0) return K;
+    return (int)(((s < 4 ? k[0] : k[1]) >> (8 * (s & 3))) & 0xFFu);
+  }
+  BB_DEV bool operator()(int li) const { return count(li) == 0; }
+  BB_DEV void colour(int li, float &cr, float &cg, float &cb) const {
+    const int s = table->slot_of_light[li];
+    if (s < 0) return;
+    ConstLight l = lights + li;
+    const float intensity = l->intensity, r = l->color[0], g = l->color[1], b = l->color[2];
+    const int n = (int)(((s < 4 ? k[0] : k[1]) >> (8 * (s & 3))) & 0xFFu);
+    if (n > 0 && n < K) {
+      const float iv = intensity * ((float)n * rk);
+      cr = r * iv; cg = g * iv; cb = b * iv;
+    }
+  }
+};
+template <bool DUMP>
+struct ShadowCastersTest {
+  const ShadowCastersArgs &a;
+  // k of the window round texel (i, j), as ShadowPcfTest::lit_taps
+  template <int RADIUS>
+  BB_DEV int lit_taps(const float *face_map, int i, int j, float t) const {
+    const int last = a.side - 1;
+    int n = 0;
+#pragma unroll 1
+    for (int dj = -RADIUS; dj <= RADIUS; ++dj) {
+      const float *row = face_map + (size_t)min(max(j + dj, 0), last) * (size_t)a.side;
+      float texel[2 * RADIUS + 1];
+#pragma unroll
+      for (int di = -RADIUS; di <= RADIUS; ++di) texel[di + RADIUS] = row[min(max(i + di, 0), last)];
+#pragma unroll
+      for (int q = 0; q <= 2 * RADIUS; ++q) n += texel[q] > t ? 0 : 1;
+    }
+    return n;
+  }
+  BB_DEV ShadowCastersSkip on(const FrameParams &fp, f3 P, bool valid, int gx, int gy) const {
+    const ConstCasters table = (ConstCasters)a.table;
+    const float side = (float)a.side;
+    const size_t texels = (size_t)a.side * (size_t)a.side;
+    const int R = a.radius, K = (2 * R + 1) * (2 * R + 1);
+    const uint32_t all_k = (uint32_t)K * 0x01010101u;
+    uint32_t packed[2] = {all_k, all_k};
+#pragma unroll 1
+    for (int s = 0; s < kMaxShadowCasters; ++s) {
+      const int faces = table->slot[s].faces;
+      if (faces == 0) continue;
+      // (nothing observable depends on a caster beyond the frame's lights -- but its mask is observable)
+      if (!DUMP && table->slot[s].light >= a.num_lights) continue;
+      const float bias = table->slot[s].bias;
+      const float *map = table->slot[s].map;
+      int cls = kShadowOutside, face = 255, k = 255;
+#pragma unroll 1
+      for (int f = 0; f < faces; ++f) {
+        const bool undecided = cls == kShadowOutside;
+        if (__ballot(undecided) == 0ull) break;
+        Mat4 m;
+#pragma unroll
+        for (int col = 0; col < 4; ++col)
+#pragma unroll
+          for (int row = 0; row < 4; ++row) m.M[col][row] = table->slot[s].m[f].M[col][row];
+        const f4 c = mat4_mul(m, f4{P.x, P.y, P.z, 1.0f});
+        const float r = bb_rcp(c.w);  // (of a w <= 0 too: not used then)
+        const float xs = fmaf(c.x * r, a.half, a.half), ys = fmaf(c.y * r, a.half, a.half);
+        const bool inside = c.w > 0.0f && xs >= 0.0f && xs < side && ys >= 0.0f && ys < side;
+        if (undecided && inside) {
+          const int i = (int)xs, j = (int)ys;  // 0 .. S - 1
+          const float t = c.z * r + bias;
+          const float *face_map = map + (size_t)f * texels;
+          int n;
+          if (R == 0) n = face_map[(size_t)j * (size_t)a.side + (size_t)i] > t ? 0 : 1;
+          else n = R == 1 ? lit_taps<1>(face_map, i, j, t) : lit_taps<2>(face_map, i, j, t);
+          k = n;
+          cls = n == K ? kShadowLit : (n == 0 ? kShadowShadowed : kShadowPartial);
+          face = f;
+        }
+      }
+      const uint32_t byte = cls == kShadowOutside ? (uint32_t)K : (uint32_t)k;
+      const uint32_t shift = 8u * (uint32_t)(s & 3);
+      uint32_t &word = s < 4 ? packed[0] : packed[1];
+      word = (word & ~(0xFFu << shift)) | (byte << shift);
+      if (DUMP && valid && s == a.dump_slot) {
+        const size_t o = (size_t)gy * (size_t)fp.width + (size_t)gx;
+        if (a.mask) a.mask[o] = (uint8_t)cls;
+        if (a.face) a.face[o] = (uint8_t)face;
+        if (a.taps) a.taps[o] = (uint8_t)k;
+      }
+    }
+    return ShadowCastersSkip{table, (ConstLight)a.lights, K, R == 0 ? 1.0f : (R == 1 ? 1.0f / 9.0f : 1.0f / 25.0f), {packed[0], packed[1]}};
   }
 };
 
@@ -3244,6 +3393,24 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_shadow_pcf(
   shade_item_list<TILE_W, TILE_H, DEFERRED, PRESENT, DUMP>(items, item_count, frags, frag_count, recs, clip_arena, fp, sp, cooked, materials, out,
                                                            gbuffer, tables, out8, ctr, ctr_done, item_groups, AnisoFilter{max_aniso}, dump,
                                                            ShadowPcfTest<DUMP>{shadow});
+}
+
+// k_shade_shadow_casters: the kernel of a context with a caster slot other than 0 in use (the rule: in front of
+// ShadowCastersTest), one kernel for every number of casters, 1 .. 6 faces each and R = 0 .. 2.  DUMP as in k_shade_shadow_pcf,
+// for the slot `shadow.dump_slot`.
+template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
+__global__ __launch_bounds__(kShadeThreads) void k_shade_shadow_casters(
+    const uint32_t *__restrict__ items, const uint32_t *__restrict__ item_count,
+    const unsigned long long *__restrict__ frags, const uint32_t *__restrict__ frag_count,
+    const ShadeRec *__restrict__ recs, const ClipSlot *__restrict__ clip_arena,
+    FrameParams fp, ShadeParams sp, const CookedLight *__restrict__ cooked,
+    const MaterialDesc *__restrict__ materials, float4 *__restrict__ out,
+    uint2 *__restrict__ gbuffer, const SrgbTables *__restrict__ tables, uint32_t *__restrict__ out8,
+    Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups, int max_aniso,
+    float *__restrict__ dump, ShadowCastersArgs shadow) {
+  shade_item_list<TILE_W, TILE_H, DEFERRED, PRESENT, DUMP>(items, item_count, frags, frag_count, recs, clip_arena, fp, sp, cooked, materials, out,
+                                                           gbuffer, tables, out8, ctr, ctr_done, item_groups, AnisoFilter{max_aniso}, dump,
+                                                           ShadowCastersTest<DUMP>{shadow});
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -89,6 +89,7 @@ struct FrameMode {
   bool shadow = false;   // option "shadow_map" > 0 and a map has been rendered (bbr_render_shadow_map): k_shade_shadow shades
   bool shadow_faces = false;  // ... two or more of them (bbr_render_shadow_faces): k_shade_shadow_faces
   int shadow_filter = 0;      // ... and option "shadow_filter" R >= 1: k_shade_shadow_pcf, whatever the number of faces
+  bool shadow_casters = false;  // ... a caster slot other than 0 is in use (bbr_render_shadow_caster): k_shade_shadow_casters, whatever F and R
   bool fused = false;    // option "present_fused": the frame is written as presented RGBA8 (the slot's d_present) ...
   bool shade_presents() const { return fused && !resolve; }   // ... by k_raster / k_shade
   bool resolve_presents() const { return fused && resolve; }  // ... by k_resolve (a presented byte cannot be averaged): then
@@ -266,15 +267,31 @@ struct ExtentDumps {
 };
 
 // Option "shadow_map": everything the feature owns.  Changing the option's value drops the group; at 0 nothing of it exists.
-struct ShadowOwned {
-  FrameSlot pass;                 // the map pass's own little frame (k_geometry -> k_raster at S x S), like the overlay pass's
+// One caster slot (bbr_render_shadow_caster): its maps and what the shading kernels get of it.
+struct ShadowSlot {
   DeviceBuffer<float> d_map;      // the maps: F x S x S depths, face f row-major at f * S * S (k_raster's depth store)
-  DeviceBuffer<uint32_t> d_sink;  // S x S words k_raster's background stores go to; nothing reads them (one for all faces)
-  DeviceBuffer<Counters> d_ctr;   // a counter block per face: the faces run back to back and are read after one wait
   ShadowFacesArgs args = {};      // what every frame's k_shade_shadow (F = 1: its first matrix) or k_shade_shadow_faces gets:
                                   // M_f, the maps, S, F, the caster's index, the bias
-  bool valid = false;             // the maps have been rendered since the option was set
-  ShadowArgs one_face() const {   // (F = 1)
+  bool valid = false;             // in use: the maps have been rendered since the option was set, and not dropped
+};
+struct ShadowOwned {
+  FrameSlot pass;                 // the map pass's own little frame (k_geometry -> k_raster at S x S), like the overlay pass's
+  ShadowSlot slot[kMaxShadowCasters];  // slot 0: the caster of bbr_render_shadow_map / bbr_render_shadow_faces
+  DeviceBuffer<uint32_t> d_sink;  // S x S words k_raster's background stores go to; nothing reads them (one for all faces)
+  DeviceBuffer<Counters> d_ctr;   // a counter block per face: the faces run back to back and are read after one wait
+  // what k_shade_shadow_casters reads: every slot's entry and the light -> slot lookup.  It exists from the first use of a slot
+  // other than 0, and is written by the synchronous render / drop calls only, while no frame is in flight.
+  DeviceBuffer<ShadowCasterTable> d_table;
+  bool any() const {
+    for (const ShadowSlot &s : slot) if (s.valid) return true;
+    return false;
+  }
+  bool beyond_first() const {     // a slot other than 0 is in use: k_shade_shadow_casters
+    for (int s = 1; s < kMaxShadowCasters; ++s) if (slot[s].valid) return true;
+    return false;
+  }
+  ShadowArgs one_face() const {   // (slot 0 alone, F = 1)
+    const ShadowFacesArgs &args = slot[0].args;
     ShadowArgs a = {};
     a.m = args.m[0], a.map = args.map, a.side = args.side, a.light = args.light, a.half = args.half, a.bias = args.bias;
     return a;
@@ -363,6 +380,7 @@ struct bbr_context : ExtentDumps {
   ShadowOwned shadow;
   int shadow_filter = 0;          // option "shadow_filter": 0 = the hard compare, 1..2 = the radius R of the box (k_shade_shadow_pcf)
   bool dump_shadow_mask = false;  // (bbr_read_shadow_mask: together with dump_surface, the DUMP form of k_shade_shadow)
+  int dump_shadow_slot = 0;       // (... the caster slot k_shade_shadow_casters' DUMP form dumps)
   bool dump_surface = false;
   DeviceBuffer<float> d_surface;  // width*height*32 floats, only while bbr_read_surface runs
   // option "static_records": 1 = a draw whose key repeats in a slot has the camera-independent part of its records written
@@ -489,8 +507,9 @@ FrameMode frame_mode(const bbr_context *c) {
   m.resolve = c->supersample > 1;
   m.merged = m.resolve && c->sample_shading == 0;
   m.fused = c->present_fused;
-  m.shadow = c->shadow_map > 0 && c->shadow.valid;
-  m.shadow_faces = m.shadow && c->shadow.args.faces > 1;
+  m.shadow = c->shadow_map > 0 && c->shadow.any();
+  m.shadow_casters = m.shadow && c->shadow.beyond_first();
+  m.shadow_faces = m.shadow && !m.shadow_casters && c->shadow.slot[0].args.faces > 1;
   m.shadow_filter = m.shadow ? c->shadow_filter : 0;
   m.depth_rule = m.resolve ? c->depth_resolve : 0;
   // (bbr_draw_overlays is refused on a partition, and with n >= 2 unless option "depth_resolve" names a rule)
@@ -904,19 +923,25 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
     };
     uint32_t *groups = short_frame ? nullptr : s.d_item_groups.ptr;
     if (mode.shadow || c->mip_levels > 1 || c->max_anisotropy > 1 || c->dump_surface) {
-      // a valid shadow map: k_shade_shadow, k_shade_shadow_faces, k_shade_shadow_pcf (never together with "mip_levels" >= 2: refused_shadow_pair); option "mip_levels":
+      // a valid shadow map: k_shade_shadow_casters, or k_shade_shadow, k_shade_shadow_faces, k_shade_shadow_pcf (never together with "mip_levels" >= 2: refused_shadow_pair); option "mip_levels":
       // k_shade_mip; option "max_anisotropy" / bbr_read_surface (the kernels' DUMP forms): k_shade_aniso.
       // Each is one launch whose waves walk the whole item list.
       if (ev) (void)hipEventRecord(ev[3], ss);
       float *surface = c->dump_surface ? c->d_surface.ptr : nullptr;
       with_bool(c->mip_levels > 1, [&](auto mip) { with_bool(c->dump_surface, [&](auto dump) {
         constexpr bool DUMP = decltype(dump)::value;
-        if (mode.shadow_filter) {
-          ShadowPcfArgs sa = {c->shadow.args, d_lights, nullptr, sp.num_lights, mode.shadow_filter};
+        if (mode.shadow_casters) {
+          ShadowCastersArgs sa = {};
+          sa.table = c->shadow.d_table.ptr, sa.lights = d_lights, sa.num_lights = sp.num_lights, sa.radius = mode.shadow_filter;
+          sa.side = c->shadow_map, sa.half = 0.5f * (float)c->shadow_map, sa.dump_slot = c->dump_shadow_slot;
+          if (DUMP && c->dump_shadow_mask) sa.mask = c->d_shadow_mask.ptr, sa.face = c->d_shadow_face.ptr, sa.taps = c->d_shadow_taps.ptr;
+          launch(k_shade_shadow_casters<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface, sa);
+        } else if (mode.shadow_filter) {
+          ShadowPcfArgs sa = {c->shadow.slot[0].args, d_lights, nullptr, sp.num_lights, mode.shadow_filter};
           if (DUMP && c->dump_shadow_mask) sa.f.mask = c->d_shadow_mask.ptr, sa.f.face = c->d_shadow_face.ptr, sa.taps = c->d_shadow_taps.ptr;
           launch(k_shade_shadow_pcf<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface, sa);
         } else if (mode.shadow_faces) {
-          ShadowFacesArgs sa = c->shadow.args;
+          ShadowFacesArgs sa = c->shadow.slot[0].args;
           sa.mask = (DUMP && c->dump_shadow_mask) ? c->d_shadow_mask.ptr : nullptr;
           sa.face = (DUMP && c->dump_shadow_mask) ? c->d_shadow_face.ptr : nullptr;
           launch(k_shade_shadow_faces<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface, sa);
@@ -1604,15 +1629,46 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
 // own in ShadowOwned::d_ctr.  One wait, one read of the F blocks, one clear.  If any face overflowed, the capacities grow by
 // the largest need among the faces and ALL faces are rendered again: the faces of a cube see the same draws, so one that
 // overflows is rarely alone, and which texels of the others were complete is not worth tracking.
-static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t light_index, int32_t n_faces, const void *light_view_blocks,
-                               float bias) {
+//
+// A call renders ONE caster slot (bbr_render_shadow_caster; bbr_render_shadow_map and _faces are slot 0).  The pass slot, the sink and the
+// counter blocks are shared by the slots; the maps are the slot's own.  Every argument is judged before anything is
+// invalidated: a refused call leaves every slot as it was.
+
+// The table k_shade_shadow_casters reads, rebuilt from the slots.  The caller has drained the context.  It is made at the
+// first use of a slot other than 0: a context that only ever uses slot 0 owns what it owned before there were slots.
+static int upload_caster_table(bbr_context *c) {
+  ShadowOwned &sh = c->shadow;
+  if (!sh.d_table.ptr && !sh.beyond_first()) return BBR_OK;
+  HIP_TRY(c, sh.d_table.ensure(1));
+  std::vector<ShadowCasterTable> host(1);  // (3.6 KB)
+  ShadowCasterTable &t = host[0];
+  std::memset(&t, 0, sizeof t);
+  for (int32_t &s : t.slot_of_light) s = -1;
+  for (int s = 0; s < kMaxShadowCasters; ++s) {
+    if (!sh.slot[s].valid) continue;
+    const ShadowFacesArgs &a = sh.slot[s].args;
+    ShadowCasterEntry &e = t.slot[s];
+    for (int f = 0; f < kMaxShadowFaces; ++f) e.m[f] = a.m[f];
+    e.map = a.map, e.light = a.light, e.faces = a.faces, e.bias = a.bias;
+    t.slot_of_light[a.light] = s;  // (0 .. 99, and no other slot in use names it: render_shadow_faces)
+  }
+  HIP_TRY(c, upload_sync(sh.d_table.ptr, &t, sizeof t));
+  return BBR_OK;
+}
+
+static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t caster, int32_t light_index, int32_t n_faces,
+                               const void *light_view_blocks, float bias) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (c->shadow_map <= 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": option shadow_map is 0");
+  if (caster < 0 || caster >= kMaxShadowCasters) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": caster outside 0 .. 7");
   if (n_faces < 1 || n_faces > kMaxShadowFaces) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": n_faces outside 1 .. 6");
   if (light_index < 0 || light_index >= kMaxNumLights) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": light_index outside 0 .. 99");
   if (!light_view_blocks) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": NULL view block");
   if (bias != bias) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": bias is NaN");
+  for (int s = 0; s < kMaxShadowCasters; ++s)
+    if (s != caster && c->shadow.slot[s].valid && c->shadow.slot[s].args.light == light_index)
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": another caster slot in use holds this light_index (one slot per light)");
   if (!c->in_frame && !c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, who + ": no recorded draws (call it after bbr_draw or after bbr_end_frame)");
   for (const RecordedDraw &rd : c->draws)
     if (!c->meshes[rd.mesh].alive || !c->materials[rd.material].alive)
@@ -1625,11 +1681,16 @@ static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t l
   std::memcpy(lv, light_view_blocks, sizeof(ViewUniformBlock) * (size_t)n_faces);
 
   ShadowOwned &sh = c->shadow;
+  ShadowSlot &cs = sh.slot[caster];
   FrameSlot &s = sh.pass;
-  sh.valid = false;
+  if (cs.valid) {  // (the slot's maps are about to be overwritten: until they are whole again no frame may use them)
+    cs.valid = false;
+    rc = upload_caster_table(c);
+    if (rc) return rc;
+  }
   const int32_t S = c->shadow_map;
   const size_t texels = (size_t)S * (size_t)S;
-  HIP_TRY(c, sh.d_map.ensure(texels * (size_t)n_faces));
+  HIP_TRY(c, cs.d_map.ensure(texels * (size_t)n_faces));
   HIP_TRY(c, sh.d_sink.ensure(texels));
   HIP_TRY(c, sh.d_ctr.ensure(kMaxShadowFaces, true));
 
@@ -1672,7 +1733,7 @@ static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t l
                            c->d_materials.ptr, s.d_block_stats.ptr, (uint32_t *)nullptr);
       hipLaunchKernelGGL((k_raster<TW, TH>), dim3(fp.tiles_x, fp.tiles_y), dim3(kTileThreads), 0, st, s.d_tile_count.ptr, ctr,
                          s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, (float4 *)nullptr, fp, s.d_tris.ptr, s.d_clip.ptr,
-                         s.d_bins.ptr, (uint32_t *)nullptr, (float *)nullptr, (const float4 *)nullptr, sh.d_map.ptr + (size_t)f * texels,
+                         s.d_bins.ptr, (uint32_t *)nullptr, (float *)nullptr, (const float4 *)nullptr, cs.d_map.ptr + (size_t)f * texels,
                          (uint32_t *)nullptr, sh.d_sink.ptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
                          (const Light *)nullptr, 0, (CookedLight *)nullptr, (const uint32_t *)nullptr);
     };
@@ -1693,18 +1754,20 @@ static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t l
       need.n_clip_slots = std::max(need.n_clip_slots, h[f].n_clip_slots);
     }
     if (!need.overflow) {
-      for (int f = 0; f < n_faces; ++f) sh.args.m[f] = pv[f];
-      for (int f = n_faces; f < kMaxShadowFaces; ++f) sh.args.m[f] = Mat4{};
-      sh.args.map = sh.d_map.ptr;
-      sh.args.mask = nullptr;
-      sh.args.face = nullptr;
-      sh.args.side = S;
-      sh.args.light = light_index;
-      sh.args.faces = n_faces;
-      sh.args.half = 0.5f * (float)S;
-      sh.args.bias = bias;
-      sh.valid = true;
-      return BBR_OK;
+      for (int f = 0; f < n_faces; ++f) cs.args.m[f] = pv[f];
+      for (int f = n_faces; f < kMaxShadowFaces; ++f) cs.args.m[f] = Mat4{};
+      cs.args.map = cs.d_map.ptr;
+      cs.args.mask = nullptr;
+      cs.args.face = nullptr;
+      cs.args.side = S;
+      cs.args.light = light_index;
+      cs.args.faces = n_faces;
+      cs.args.half = 0.5f * (float)S;
+      cs.args.bias = bias;
+      cs.valid = true;
+      rc = upload_caster_table(c);
+      if (rc) cs.valid = false;  // (the table still says so)
+      return rc;
     }
     // a triangle did not fit: a map is incomplete.  Grow and render all of them again.
     rc = apply_growth(c, need.overflow, need.bin_need, need.n_broad, need.n_clip_slots);
@@ -1715,23 +1778,64 @@ static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t l
 }
 
 extern "C" int bbr_render_shadow_map(bbr_context *c, int32_t light_index, const void *light_view_block, float bias) {
-  return render_shadow_faces(c, "render_shadow_map", light_index, 1, light_view_block, bias);
+  return render_shadow_faces(c, "render_shadow_map", 0, light_index, 1, light_view_block, bias);
 }
 
 extern "C" int bbr_render_shadow_faces(bbr_context *c, int32_t light_index, int32_t n_faces, const void *light_view_blocks, float bias) {
-  return render_shadow_faces(c, "render_shadow_faces", light_index, n_faces, light_view_blocks, bias);
+  return render_shadow_faces(c, "render_shadow_faces", 0, light_index, n_faces, light_view_blocks, bias);
 }
 
-extern "C" int bbr_read_shadow_face(bbr_context *c, int32_t face, float *host) {
+extern "C" int bbr_render_shadow_caster(bbr_context *c, int32_t caster, int32_t light_index, int32_t n_faces, const void *light_view_blocks,
+                                        float bias) {
+  return render_shadow_faces(c, "render_shadow_caster", caster, light_index, n_faces, light_view_blocks, bias);
+}
+
+extern "C" int bbr_drop_shadow_caster(bbr_context *c, int32_t caster) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (caster < 0 || caster >= kMaxShadowCasters) return fail(c, BBR_ERR_INVALID_ARGUMENT, "drop_shadow_caster: caster outside 0 .. 7");
+  ShadowSlot &cs = c->shadow.slot[caster];
+  if (!cs.valid) return BBR_OK;
+  int rc = sync_and_fix(c, nullptr);  // the frames in flight read the table and the maps
+  if (rc) return rc;
+  cs.valid = false;
+  rc = upload_caster_table(c);
+  cs = ShadowSlot();
+  return rc;
+}
+
+extern "C" int bbr_get_shadow_casters(bbr_context *c, int32_t *out_light_index, int32_t *out_faces) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  if (!out_light_index || !out_faces) return fail(c, BBR_ERR_INVALID_ARGUMENT, "get_shadow_casters: NULL");
+  for (int s = 0; s < kMaxShadowCasters; ++s) {
+    const ShadowSlot &cs = c->shadow.slot[s];
+    const bool used = c->shadow_map > 0 && cs.valid;
+    out_light_index[s] = used ? cs.args.light : -1;
+    out_faces[s] = used ? cs.args.faces : 0;
+  }
+  return BBR_OK;
+}
+
+// `unused`: what a slot not in use is answered with (the calls of slot 0 from before there were slots: BBR_ERR_NOT_IN_FRAME)
+static int read_shadow_caster_face(bbr_context *c, int32_t caster, int32_t face, float *host, int unused) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_map: NULL");
   if (c->shadow_map <= 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_map: option shadow_map is 0");
-  if (!c->shadow.valid) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_shadow_map: no map rendered (bbr_render_shadow_map)");
-  if (face < 0 || face >= c->shadow.args.faces) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_face: face outside 0 .. F - 1");
+  if (caster < 0 || caster >= kMaxShadowCasters) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_caster_face: caster outside 0 .. 7");
+  const ShadowSlot &cs = c->shadow.slot[caster];
+  if (!cs.valid) return fail(c, unused, "read_shadow_map: no map rendered (bbr_render_shadow_map, bbr_render_shadow_caster)");
+  if (face < 0 || face >= cs.args.faces) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_face: face outside 0 .. F - 1");
   const size_t texels = (size_t)c->shadow_map * c->shadow_map;
-  HIP_TRY(c, hipMemcpy(host, c->shadow.d_map.ptr + (size_t)face * texels, texels * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(host, cs.d_map.ptr + (size_t)face * texels, texels * sizeof(float), hipMemcpyDeviceToHost));
   return BBR_OK;
+}
+
+extern "C" int bbr_read_shadow_face(bbr_context *c, int32_t face, float *host) {
+  return read_shadow_caster_face(c, 0, face, host, BBR_ERR_NOT_IN_FRAME);
+}
+extern "C" int bbr_read_shadow_caster_face(bbr_context *c, int32_t caster, int32_t face, float *host) {
+  return read_shadow_caster_face(c, caster, face, host, BBR_ERR_INVALID_ARGUMENT);
 }
 
 extern "C" int bbr_read_shadow_map(bbr_context *c, float *host) { return bbr_read_shadow_face(c, 0, host); }
@@ -1739,20 +1843,26 @@ extern "C" int bbr_read_shadow_map(bbr_context *c, float *host) { return bbr_rea
 // The class (and, F >= 2, the deciding face) of every pixel of the last frame: the DUMP form of k_shade_shadow /
 // k_shade_shadow_faces (with it the surface dump, which is dropped).  With one face the face index follows from the class.
 enum class ShadowDump { kMask, kFace, kTaps };
-static int read_shadow_classes(bbr_context *c, const std::string &who, uint8_t *host, ShadowDump want) {
+// One re-render dumps one caster slot.  With a slot other than 0 in use the kernel is k_shade_shadow_casters, whose DUMP form
+// writes all three outputs itself, whatever F and R.
+static int read_shadow_classes(bbr_context *c, const std::string &who, uint8_t *host, ShadowDump want, int32_t caster = 0) {
   const bool want_face = want == ShadowDump::kFace;
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!host) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": NULL");
+  if (caster < 0 || caster >= kMaxShadowCasters) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": caster outside 0 .. 7");
   if (int rc = refuse_supersampled(c, who.c_str())) return rc;
-  const FrameMode mode = frame_mode(c);
-  if (!mode.shadow) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": no shadow map in use (option shadow_map, bbr_render_shadow_map)");
+  FrameMode mode = frame_mode(c);
+  if (!mode.shadow || !c->shadow.slot[caster].valid)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": no shadow map in use (option shadow_map, bbr_render_shadow_map, bbr_render_shadow_caster)");
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, who + ": nothing rendered");
   if (c->world > 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": not available on a partitioned context");
   const size_t pixels = (size_t)c->width * c->height;
   int rc = BBR_OK;
-  const bool want_taps = want == ShadowDump::kTaps && mode.shadow_filter;  // (R = 0: K = 1, k follows from the class)
-  for (DeviceBuffer<uint8_t> *b : {mode.shadow_faces ? &c->d_shadow_face : nullptr, want_taps ? &c->d_shadow_taps : nullptr}) {
+  if (mode.shadow_casters) mode.shadow_faces = true;  // (below: the kernel writes the face index and k itself)
+  const bool want_taps = want == ShadowDump::kTaps && (mode.shadow_filter || mode.shadow_casters);  // (R = 0: K = 1, k follows from the class)
+  c->dump_shadow_slot = caster;
+  for (DeviceBuffer<uint8_t> *b : {mode.shadow_faces ? &c->d_shadow_face : nullptr, (want_taps || mode.shadow_casters) ? &c->d_shadow_taps : nullptr}) {
     if (!b || rc != BBR_OK) continue;  // (an uncovered pixel keeps the fill: face 255, k 255)
     hipError_t e = b->ensure(pixels);
     if (e == hipSuccess) e = hipMemset(b->ptr, 0xFF, pixels);
@@ -1777,6 +1887,7 @@ static int read_shadow_classes(bbr_context *c, const std::string &who, uint8_t *
   c->d_shadow_face.release();
   c->d_shadow_taps.release();
   c->d_surface.release();
+  c->dump_shadow_slot = 0;
   return rc;
 }
 
@@ -1789,6 +1900,16 @@ extern "C" int bbr_read_shadow_face_index(bbr_context *c, uint8_t *host) {
 // k, the number of lit taps, of every pixel of the last frame (option "shadow_filter"; 255 where the class is 0 or OUTSIDE)
 extern "C" int bbr_read_shadow_taps(bbr_context *c, uint8_t *host) {
   return read_shadow_classes(c, "read_shadow_taps", host, ShadowDump::kTaps);
+}
+// ... and of one caster slot each
+extern "C" int bbr_read_shadow_caster_mask(bbr_context *c, int32_t caster, uint8_t *host) {
+  return read_shadow_classes(c, "read_shadow_caster_mask", host, ShadowDump::kMask, caster);
+}
+extern "C" int bbr_read_shadow_caster_face_index(bbr_context *c, int32_t caster, uint8_t *host) {
+  return read_shadow_classes(c, "read_shadow_caster_face_index", host, ShadowDump::kFace, caster);
+}
+extern "C" int bbr_read_shadow_caster_taps(bbr_context *c, int32_t caster, uint8_t *host) {
+  return read_shadow_classes(c, "read_shadow_caster_taps", host, ShadowDump::kTaps, caster);
 }
 
 // ================================================================================================

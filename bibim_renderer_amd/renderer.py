@@ -315,6 +315,48 @@ class Renderer:
         self._check(self._L.bbr_read_shadow_taps(self._ctx, _ptr(out)))
         return out
 
+    # -- up to eight casters (include/bibim_hip.h, "Casters"): slot 0 is the caster of the calls above --
+    def render_shadow_caster(self, caster, light_index, light_views, bias=0.0):
+        """render_shadow_faces for caster slot `caster` (0 .. 7): light `light_index` is shadowed through the F = 1 .. 6 view
+        blocks of `light_views`.  One slot per light"""
+        b = np.ascontiguousarray(light_views)
+        assert b.nbytes % 144 == 0
+        self._check(self._L.bbr_render_shadow_caster(self._ctx, int(caster), int(light_index), b.nbytes // 144, _ptr(b), float(bias)))
+
+    def drop_shadow_caster(self, caster):
+        """release the slot's maps and mark it not in use"""
+        self._check(self._L.bbr_drop_shadow_caster(self._ctx, int(caster)))
+
+    def shadow_casters(self):
+        """(light index of every slot, -1 where it is not in use; number of faces of every slot), two int32 [8]"""
+        light, faces = np.empty(8, np.int32), np.empty(8, np.int32)
+        self._check(self._L.bbr_get_shadow_casters(self._ctx, _ptr(light), _ptr(faces)))
+        return light, faces
+
+    def read_shadow_caster_face(self, caster, face):
+        """read_shadow_face for one slot"""
+        s = max(int(self.shadow_map), 0)
+        out = np.empty(max(s * s, 1), np.float32)  # (s = 0: the call refuses)
+        self._check(self._L.bbr_read_shadow_caster_face(self._ctx, int(caster), int(face), _ptr(out)))
+        return out.reshape(s, s)
+
+    def _read_shadow_caster(self, call, caster):
+        out = np.empty((self.height, self.width), np.uint8)
+        self._check(call(self._ctx, int(caster), _ptr(out)))
+        return out
+
+    def read_shadow_caster_mask(self, caster):
+        """read_shadow_mask for one slot; re-renders the last frame"""
+        return self._read_shadow_caster(self._L.bbr_read_shadow_caster_mask, caster)
+
+    def read_shadow_caster_face_index(self, caster):
+        """read_shadow_face_index for one slot; re-renders the last frame"""
+        return self._read_shadow_caster(self._L.bbr_read_shadow_caster_face_index, caster)
+
+    def read_shadow_caster_taps(self, caster):
+        """read_shadow_taps for one slot; re-renders the last frame"""
+        return self._read_shadow_caster(self._L.bbr_read_shadow_caster_taps, caster)
+
     def read_material_level(self, material, map_index, level):
         """level `level` of one of a material's six maps (PBRMapType order), uint8 [h, w, 4] (option "mip_levels")"""
         w, h = C.c_int32(), C.c_int32()

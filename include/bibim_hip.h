@@ -267,7 +267,7 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            shaded by k_shade_mip, whatever "max_anisotropy" is (the rule: "mip chains" below).  The TBN
  *                            overlay's vertex-stage fetch and the GUI sampler have no derivatives and stay on level 0.
  *                            Anything else: INVALID_ARGUMENT.  Refused (INVALID_ARGUMENT) at >= 2 while "shadow_map" > 0
- *   "shadow_map" 0..8192     shadow mapping, one caster per context ("shadow mapping" below).  0 (default): off -- no kernel
+ *   "shadow_map" 0..8192     shadow mapping, up to eight casters per context ("shadow mapping" below).  0 (default): off -- no kernel
  *                            of the option runs, no buffer of it exists.  S >= 1: the side of a square binary32 depth map
  *                            that bbr_render_shadow_map renders; until it has, frames are rendered by the unshadowed
  *                            kernels exactly as with 0, afterwards by k_shade_shadow.  Changing the value drains the
@@ -467,8 +467,9 @@ int bbr_read_material_level(bbr_context *ctx, int32_t material, int32_t map, int
 int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uint8_t *out, uint64_t capacity, uint64_t *out_bytes);
 
 /* ---- shadow mapping (option "shadow_map" = S > 0) ----
- * One shadow-casting light per context: a depth map of the recorded draws from a view the caller supplies, and a depth test
- * in front of that light's iteration of the light loop.  The rule, in binary32, without contraction, in this operand order
+ * Up to eight shadow-casting lights per context ("Casters" below; what follows states the rule for one, the caster of slot
+ * 0): a depth map of the recorded draws from a view the caller supplies, and a depth test in front of that light's
+ * iteration of the light loop.  The rule, in binary32, without contraction, in this operand order
  * (tests/shadow_reference.py):
  *   map      texel (i, j) is the depth the rasteriser keeps for pixel (i, j) of an S x S frame of the recorded draws under
  *            gl_Position = (L.proj * L.view) * posWorld -- the forward order, whatever "render_pass" is -- with the frame's
@@ -482,8 +483,8 @@ int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uin
  *   classes  as bbr_read_shadow_mask reports them: 0 not covered, 1 LIT, 2 SHADOWED, 3 OUTSIDE (4 PARTIAL: "Filtering")
  *   loop     the iteration of light `light_index` of a SHADOWED fragment contributes nothing, like a light of unknown type;
  *            everything else is the light loop's.  A light_index >= NumLights shadows nothing.
- * Deviations: a hard compare unless option "shadow_filter" is set ("Filtering" below), one caster, and the deferred
- * background colour is evaluated without the test.
+ * Deviations: a hard compare unless option "shadow_filter" is set ("Filtering" below), one caster per light ("Casters"
+ * below), and the deferred background colour is evaluated without the test.
  *
  * Faces.  The caster has an ordered list of F = 1 .. 6 frusta (bbr_render_shadow_faces; bbr_render_shadow_map is F = 1), each
  * with a map of its own, for ONE light_index and ONE bias:
@@ -518,6 +519,29 @@ int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uin
  * Deviations: a box, not bilinear weights; one t for all taps (no receiver-plane bias); no fetch across cube faces; the
  * deferred background stays untested.
  *
+ * Casters (bbr_render_shadow_caster; tests/shadow_casters_reference.py).  A context has kMaxShadowCasters = 8 caster SLOTS,
+ * 0 .. 7.  A slot in use holds a light index, F = 1 .. 6 view blocks, their F maps of S x S and a bias; S ("shadow_map") and R
+ * ("shadow_filter") stay context-wide.  The caster of bbr_render_shadow_map / bbr_render_shadow_faces is slot 0.
+ *   maps     slot s, face f: exactly the map rule above for that view block.  Every rank renders all of them
+ *   test     for every slot in use, independently of the others: (class_s, face_s, k_s) is the rule above evaluated with that
+ *            slot's matrices, maps and bias.  R = 0: the first face not OUTSIDE and the hard compare, K = 1 and k is 0 or 1.
+ *            R >= 1: the box of K = 9 or 25 compares clamped inside the deciding face.  It runs on the P the light loop
+ *            receives (deferred: after the binary16 rounding); no operation of it changes.  Slots do not see each other
+ *   loop     iteration li looks for the slot in use whose light index is li; there is at most one.  No such slot, or class
+ *            OUTSIDE, or k = K: the iteration is untouched.  k = 0: it contributes nothing, the `continue` of an unknown type.
+ *            0 < k < K: it runs with the cooked colour color[c] * (intensity * ((float)k * RK)), RK as above.  The lights'
+ *            order, every other operation and the accumulation order are the light loop's.  A slot whose light index is >=
+ *            NumLights changes nothing
+ *   hence    a frame with one slot in use, whichever slot it is, is bit for bit the frame of that caster in slot 0; which slot
+ *            a caster sits in has no meaning: permuting the casters over the slots changes no bit; a caster at bias 2
+ *            (nothing shadowed), or on a light beyond the frame's lights, leaves the frame of the other casters alone
+ *   kernels  with only slot 0 in use a frame runs the kernels, launches and bits described above; with any other slot in use,
+ *            k_shade_shadow_casters, one kernel for every number of casters, every F and R = 0 .. 2
+ *   memory   per slot its F * S * S * 4 bytes of maps, allocated when the slot is first rendered; the pass's buffers are
+ *            shared by the slots; a 3.6 KB table from the first use of a slot other than 0
+ * Deviations kept: the deferred background stays untested; a box, one t per window, no fetch across faces.  New: one slot per
+ * light -- two slots naming the same light are refused, not combined.
+ *
  * bbr_render_shadow_map renders the map from `light_view_block` (144 bytes in ViewUniformBlock layout; view and proj are
  * used, the rest is ignored).  It renders the recorded draws and is valid inside a frame after the bbr_draw calls (the draws
  * recorded so far) and after bbr_end_frame (the last recorded frame's); otherwise BBR_ERR_NOT_IN_FRAME.  It is synchronous,
@@ -528,6 +552,13 @@ int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uin
  * bbr_render_shadow_faces is the same call with `n_faces` consecutive view blocks (n_faces outside 1 .. 6:
  * BBR_ERR_INVALID_ARGUMENT): one drain, one upload of the draws, the faces back to back, one wait; if a capacity overflows
  * in any face, it grows and all faces are rendered again.  With n_faces = 1 it is bbr_render_shadow_map, bit for bit.
+ * bbr_render_shadow_caster is bbr_render_shadow_faces for one slot: the same validity, the same synchronous pass and growth,
+ * the same refusals; also BBR_ERR_INVALID_ARGUMENT for `caster` outside 0 .. 7 and for a light_index that another slot in use
+ * already holds.  A refused call leaves every slot as it was, the slot named included.  bbr_render_shadow_map / _faces are
+ * this call with caster 0, bit for bit (the duplicate-light refusal included).  bbr_drop_shadow_caster drains, releases the
+ * slot's maps and marks it not in use; on a slot not in use it is BBR_OK.  With no slot left in use, frames are rendered by
+ * the unshadowed kernels, as before a map exists.  bbr_get_shadow_casters fills eight light indices (-1: not in use) and
+ * eight face counts (0: not in use).  Changing "shadow_map" drops every slot; "shadow_filter" applies to every slot.
  * Works with both tile modes, both render passes, "present_fused", "max_anisotropy", "supersample" with either
  * "sample_shading" (the test runs per fine fragment), a partition, up to four frames in flight and bbr_replay_frame.
  *
@@ -544,7 +575,11 @@ int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uin
  *   bbr_read_shadow_taps  width*height bytes: k of every pixel of the last frame, 255 where the class is 0 or OUTSIDE.  With
  *                         "shadow_filter" 0 it is K = 1: 1 where LIT, 0 where SHADOWED.  The same re-render and the same
  *                         refusals as bbr_read_shadow_mask
+ *   bbr_read_shadow_caster_face / _mask / _face_index / _taps  what the namesake above does, for one slot (the calls above
+ *                         are slot 0): the same re-render -- one re-render dumps one slot --, the same refusals, the same
+ *                         fill values; INVALID_ARGUMENT for a slot outside 0 .. 7 or not in use
  * bbr_read_surface and bbr_read_gbuffer keep working while a map is in use: the re-rendered frame is the shadowed one. */
+#define BBR_MAX_SHADOW_CASTERS 8
 int bbr_render_shadow_map(bbr_context *ctx, int32_t light_index, const void *light_view_block /* 144 B */, float bias);
 int bbr_read_shadow_map(bbr_context *ctx, float *out);
 int bbr_read_shadow_mask(bbr_context *ctx, uint8_t *out);
@@ -553,6 +588,14 @@ int bbr_render_shadow_faces(bbr_context *ctx, int32_t light_index, int32_t n_fac
 int bbr_read_shadow_face(bbr_context *ctx, int32_t face, float *out);
 int bbr_read_shadow_face_index(bbr_context *ctx, uint8_t *out);
 int bbr_read_shadow_taps(bbr_context *ctx, uint8_t *out);
+int bbr_render_shadow_caster(bbr_context *ctx, int32_t caster, int32_t light_index, int32_t n_faces,
+                             const void *light_view_blocks /* n_faces x 144 B */, float bias);
+int bbr_drop_shadow_caster(bbr_context *ctx, int32_t caster);
+int bbr_get_shadow_casters(bbr_context *ctx, int32_t *out_light_index /* 8, -1 = not in use */, int32_t *out_faces /* 8 */);
+int bbr_read_shadow_caster_face(bbr_context *ctx, int32_t caster, int32_t face, float *out);
+int bbr_read_shadow_caster_mask(bbr_context *ctx, int32_t caster, uint8_t *out);
+int bbr_read_shadow_caster_face_index(bbr_context *ctx, int32_t caster, uint8_t *out);
+int bbr_read_shadow_caster_taps(bbr_context *ctx, int32_t caster, uint8_t *out);
 
 /* ---- primitive-record read-back ----
  * What the vertex stage (k_geometry: forward_brdf.vert / gbuffer.vert, clip test, viewport, snap, triangle setup) wrote
