@@ -2385,26 +2385,19 @@ struct ShadowSkip {
 struct NoShadow {
   BB_DEV NoSkip on(const FrameParams &, f3, bool, int, int) const { return NoSkip{}; }
 };
-template <bool DUMP>
-struct ShadowTest {
-  const ShadowArgs &a;
-  BB_DEV int classify(f3 P) const {
-    const f4 c = mat4_mul(a.m, f4{P.x, P.y, P.z, 1.0f});
-    const float r = bb_rcp(c.w);  // (of a w <= 0 too: not used then)
-    const float side = (float)a.side;
-    const float xs = fmaf(c.x * r, a.half, a.half), ys = fmaf(c.y * r, a.half, a.half);
-    const bool inside = c.w > 0.0f && xs >= 0.0f && xs < side && ys >= 0.0f && ys < side;
-    if (!inside) return kShadowOutside;
-    const int i = (int)xs, j = (int)ys;  // 0 .. S - 1
-    const float t = c.z * r + a.bias;
-    return a.map[(size_t)j * (size_t)a.side + (size_t)i] > t ? kShadowShadowed : kShadowLit;
-  }
-  BB_DEV ShadowSkip on(const FrameParams &fp, f3 P, bool valid, int gx, int gy) const {
-    const int cls = classify(P);
-    if (DUMP && a.mask && valid) a.mask[(size_t)gy * (size_t)fp.width + (size_t)gx] = (uint8_t)cls;
-    return ShadowSkip{a.light, cls == kShadowShadowed};
-  }
+// The rule's `test` for one face up to the map read, stated once for the four kernels: where P lands in the map of M and the
+// depth t it is compared at.  i = (int)xs and j = (int)ys (0 .. S - 1) are formed at the use, behind `inside`.
+struct ShadowTexel {
+  bool inside;
+  float xs, ys, t;
 };
+template <typename M4>  // (Mat4 in any address space)
+BB_DEV ShadowTexel shadow_texel(const M4 &m, f3 P, float side, float half, float bias) {
+  const f4 c = mat4_mul(m, f4{P.x, P.y, P.z, 1.0f});
+  const float r = bb_rcp(c.w);  // (of a w <= 0 too: not used then)
+  const float xs = fmaf(c.x * r, half, half), ys = fmaf(c.y * r, half, half);
+  return ShadowTexel{c.w > 0.0f && xs >= 0.0f && xs < side && ys >= 0.0f && ys < side, xs, ys, c.z * r + bias};
+}
 
 // Up to six faces for the one caster (bbr_render_shadow_faces with 2 .. 6 view blocks; k_shade_shadow_faces): six 90-degree-class
 // frusta at a point light are a cube map, nested orthographic ones are cascades.  The rule (restated
@@ -2413,11 +2406,7 @@ struct ShadowTest {
 //   test    for f = 0 .. F - 1 in this order: cls_f = the rule above with M_f = proj_view(L_f) and map_f; the first
 //           cls_f != OUTSIDE is the fragment's class and f its face; none: OUTSIDE, face 255
 // Where frusta overlap the earlier face wins and the later map is not read; a fragment outside every face is lit (with faces
-// of exactly 90 degrees: on the seam planes).
-// The face loop is uniform over the wave: f is a scalar, so M_f arrives through scalar loads from the kernel arguments and
-// every lane runs the same face; a lane that has its class only carries it.  The loop ends when no lane of the wave is
-// undecided (a ballot): most waves of a cube-lit frame see one or two faces.  Only lanes inside face f address its map, with
-// i, j in [0, S - 1] by the comparisons and f < F by the loop bound.
+// of exactly 90 degrees: on the seam planes).  The walk itself: shadow_verdict, below.
 constexpr int kMaxShadowFaces = 6;
 struct ShadowFacesArgs {
   Mat4 m[kMaxShadowFaces];  // proj_view(L_f)
@@ -2429,35 +2418,6 @@ struct ShadowFacesArgs {
   int32_t faces;            // F
   float half;               // 0.5f * S
   float bias;
-};
-template <bool DUMP>
-struct ShadowFacesTest {
-  const ShadowFacesArgs &a;
-  BB_DEV ShadowSkip on(const FrameParams &fp, f3 P, bool valid, int gx, int gy) const {
-    const float side = (float)a.side;
-    const size_t texels = (size_t)a.side * (size_t)a.side;
-    int cls = kShadowOutside, face = 255;
-    for (int f = 0; f < a.faces; ++f) {
-      const bool undecided = cls == kShadowOutside;
-      if (__ballot(undecided) == 0ull) break;
-      const f4 c = mat4_mul(a.m[f], f4{P.x, P.y, P.z, 1.0f});
-      const float r = bb_rcp(c.w);  // (of a w <= 0 too: not used then)
-      const float xs = fmaf(c.x * r, a.half, a.half), ys = fmaf(c.y * r, a.half, a.half);
-      const bool inside = c.w > 0.0f && xs >= 0.0f && xs < side && ys >= 0.0f && ys < side;
-      if (undecided && inside) {
-        const int i = (int)xs, j = (int)ys;  // 0 .. S - 1
-        const float t = c.z * r + a.bias;
-        cls = a.map[(size_t)f * texels + (size_t)j * (size_t)a.side + (size_t)i] > t ? kShadowShadowed : kShadowLit;
-        face = f;
-      }
-    }
-    if (DUMP && valid) {
-      const size_t o = (size_t)gy * (size_t)fp.width + (size_t)gx;
-      if (a.mask) a.mask[o] = (uint8_t)cls;
-      if (a.face) a.face[o] = (uint8_t)face;
-    }
-    return ShadowSkip{a.light, cls == kShadowShadowed};
-  }
 };
 
 // Percentage-closer filtering (option "shadow_filter" = R in 1 .. 2; k_shade_shadow_pcf): a (2R+1) x (2R+1) box of the hard
@@ -2495,61 +2455,103 @@ struct ShadowScale {
     if (partial && li == light) { cr = r * iv; cg = g * iv; cb = b * iv; }
   }
 };
+// k of the window round texel (i, j) of one face's S x S map: the rows one after the other, a row's 2R + 1 gathers issued together
+template <int RADIUS>
+BB_DEV int lit_taps(const float *face_map, int side, int i, int j, float t) {
+  const int last = side - 1;
+  int n = 0;
+#pragma unroll 1
+  for (int dj = -RADIUS; dj <= RADIUS; ++dj) {
+    const float *row = face_map + (size_t)min(max(j + dj, 0), last) * (size_t)side;
+    float texel[2 * RADIUS + 1];
+#pragma unroll
+    for (int di = -RADIUS; di <= RADIUS; ++di) texel[di + RADIUS] = row[min(max(i + di, 0), last)];
+#pragma unroll
+    for (int q = 0; q <= 2 * RADIUS; ++q) n += texel[q] > t ? 0 : 1;
+  }
+  return n;
+}
+// k for R = 0 .. 2: the hard compare is the window of one tap
+BB_DEV int lit_count(const float *face_map, int side, int R, int i, int j, float t) {
+  if (R == 0) return face_map[(size_t)j * (size_t)side + (size_t)i] > t ? 0 : 1;
+  return R == 1 ? lit_taps<1>(face_map, side, i, j, t) : lit_taps<2>(face_map, side, i, j, t);
+}
+BB_DEV int shadow_taps(int R) { return (2 * R + 1) * (2 * R + 1); }                                   // K
+BB_DEV float shadow_rk(int R) { return R == 0 ? 1.0f : (R == 1 ? 1.0f / 9.0f : 1.0f / 25.0f); }  // RK
+BB_DEV int shadow_class(int k, int K) { return k == K ? kShadowLit : (k == 0 ? kShadowShadowed : kShadowPartial); }
+// the caster's intensity under a PARTIAL verdict: intensity * v
+BB_DEV float partial_intensity(float intensity, int k, float rk) { return intensity * ((float)k * rk); }
+
+// What the test says of a fragment under one caster; the DUMP forms store it per pixel (bbr_read_shadow_mask,
+// bbr_read_shadow_face_index, bbr_read_shadow_taps), each output only where its pointer is set.
+struct ShadowVerdict {
+  int cls, face, k;  // OUTSIDE: face 255, k 255
+  BB_DEV void dump(const FrameParams &fp, int gx, int gy, uint8_t *mask, uint8_t *face_out, uint8_t *taps) const {
+    const size_t o = (size_t)gy * (size_t)fp.width + (size_t)gx;
+    if (mask) mask[o] = (uint8_t)cls;
+    if (face_out) face_out[o] = (uint8_t)face;
+    if (taps) taps[o] = (uint8_t)k;
+  }
+};
+// of a fragment inside face f, at texel ((int)x.xs, (int)x.ys) of its map
+BB_DEV ShadowVerdict face_verdict(const ShadowTexel &x, const float *face_map, int side, int R, int f) {
+  const int k = lit_count(face_map, side, R, (int)x.xs, (int)x.ys, x.t);
+  return ShadowVerdict{shadow_class(k, shadow_taps(R)), f, k};
+}
+// The face walk of the faces rule, with M_f = matrix_of(f): kernel arguments (faces_verdict) or the caster table
+// (ShadowCastersTest).  The loop is uniform over the wave: f is a scalar, so M_f arrives through scalar loads and every lane
+// runs the same face; a lane that has its class only carries it.  The loop ends when no lane of the wave is undecided (a
+// ballot): most waves of a cube-lit frame see one or two faces.  Only lanes inside face f address its map, with i, j in
+// [0, S - 1] by the comparisons (and the clamps of lit_taps) and f < F by the loop bound.
+template <class MatrixOf>
+BB_DEV ShadowVerdict shadow_verdict(MatrixOf matrix_of, const float *map, int faces, int side, float half, float bias, int R, f3 P) {
+  const size_t texels = (size_t)side * (size_t)side;
+  ShadowVerdict v{kShadowOutside, 255, 255};
+  for (int f = 0; f < faces; ++f) {
+    const bool undecided = v.cls == kShadowOutside;
+    if (__ballot(undecided) == 0ull) break;
+    const ShadowTexel x = shadow_texel(matrix_of(f), P, (float)side, half, bias);
+    if (undecided && x.inside) v = face_verdict(x, map + (size_t)f * texels, side, R, f);
+  }
+  return v;
+}
+BB_DEV ShadowVerdict faces_verdict(const ShadowFacesArgs &a, int R, f3 P) {
+  return shadow_verdict([&](int f) -> const Mat4 & { return a.m[f]; }, a.map, a.faces, a.side, a.half, a.bias, R, P);
+}
+
+template <bool DUMP>
+struct ShadowTest {  // one face, R = 0: no loop and no ballot
+  const ShadowArgs &a;
+  BB_DEV ShadowSkip on(const FrameParams &fp, f3 P, bool valid, int gx, int gy) const {
+    const ShadowTexel x = shadow_texel(a.m, P, (float)a.side, a.half, a.bias);
+    ShadowVerdict v{kShadowOutside, 255, 255};
+    if (x.inside) v = face_verdict(x, a.map, a.side, 0, 0);
+    if (DUMP && valid) v.dump(fp, gx, gy, a.mask, nullptr, nullptr);
+    return ShadowSkip{a.light, v.cls == kShadowShadowed};
+  }
+};
+template <bool DUMP>
+struct ShadowFacesTest {
+  const ShadowFacesArgs &a;
+  BB_DEV ShadowSkip on(const FrameParams &fp, f3 P, bool valid, int gx, int gy) const {
+    const ShadowVerdict v = faces_verdict(a, 0, P);
+    if (DUMP && valid) v.dump(fp, gx, gy, a.mask, a.face, nullptr);
+    return ShadowSkip{a.light, v.cls == kShadowShadowed};
+  }
+};
 template <bool DUMP>
 struct ShadowPcfTest {
   const ShadowPcfArgs &a;
-  // k of the window round texel (i, j): the rows one after the other, a row's 2R + 1 gathers issued together
-  template <int RADIUS>
-  BB_DEV int lit_taps(const float *face_map, int i, int j, float t) const {
-    const int last = a.f.side - 1;
-    int n = 0;
-#pragma unroll 1
-    for (int dj = -RADIUS; dj <= RADIUS; ++dj) {
-      const float *row = face_map + (size_t)min(max(j + dj, 0), last) * (size_t)a.f.side;
-      float texel[2 * RADIUS + 1];
-#pragma unroll
-      for (int di = -RADIUS; di <= RADIUS; ++di) texel[di + RADIUS] = row[min(max(i + di, 0), last)];
-#pragma unroll
-      for (int q = 0; q <= 2 * RADIUS; ++q) n += texel[q] > t ? 0 : 1;
-    }
-    return n;
-  }
   BB_DEV ShadowScale on(const FrameParams &fp, f3 P, bool valid, int gx, int gy) const {
     const ShadowFacesArgs &s = a.f;
-    const float side = (float)s.side;
-    const size_t texels = (size_t)s.side * (size_t)s.side;
-    const int R = a.radius, K = (2 * R + 1) * (2 * R + 1);
-    int cls = kShadowOutside, face = 255, k = 255;
-    for (int f = 0; f < s.faces; ++f) {
-      const bool undecided = cls == kShadowOutside;
-      if (__ballot(undecided) == 0ull) break;
-      const f4 c = mat4_mul(s.m[f], f4{P.x, P.y, P.z, 1.0f});
-      const float r = bb_rcp(c.w);  // (of a w <= 0 too: not used then)
-      const float xs = fmaf(c.x * r, s.half, s.half), ys = fmaf(c.y * r, s.half, s.half);
-      const bool inside = c.w > 0.0f && xs >= 0.0f && xs < side && ys >= 0.0f && ys < side;
-      if (undecided && inside) {
-        const int i = (int)xs, j = (int)ys;  // 0 .. S - 1
-        const float t = c.z * r + s.bias;
-        const float *face_map = s.map + (size_t)f * texels;
-        const int n = R == 1 ? lit_taps<1>(face_map, i, j, t) : lit_taps<2>(face_map, i, j, t);
-        k = n;
-        cls = n == K ? kShadowLit : (n == 0 ? kShadowShadowed : kShadowPartial);
-        face = f;
-      }
-    }
-    if (DUMP && valid) {
-      const size_t o = (size_t)gy * (size_t)fp.width + (size_t)gx;
-      if (s.mask) s.mask[o] = (uint8_t)cls;
-      if (s.face) s.face[o] = (uint8_t)face;
-      if (a.taps) a.taps[o] = (uint8_t)k;
-    }
+    const ShadowVerdict v = faces_verdict(s, a.radius, P);
+    if (DUMP && valid) v.dump(fp, gx, gy, s.mask, s.face, a.taps);
     float intensity = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
     if (s.light < a.num_lights) {
       ConstLight l = (ConstLight)a.lights + s.light;
       intensity = l->intensity; cr = l->color[0]; cg = l->color[1]; cb = l->color[2];
     }
-    const float rk = R == 1 ? 1.0f / 9.0f : 1.0f / 25.0f;
-    return ShadowScale{s.light, cls == kShadowShadowed, cls == kShadowPartial, intensity * ((float)k * rk), cr, cg, cb};
+    return ShadowScale{s.light, v.cls == kShadowShadowed, v.cls == kShadowPartial, partial_intensity(intensity, v.k, shadow_rk(a.radius)), cr, cg, cb};
   }
 };
 
@@ -2621,7 +2623,7 @@ struct ShadowCastersSkip {
     const float intensity = l->intensity, r = l->color[0], g = l->color[1], b = l->color[2];
     const int n = (int)(((s < 4 ? k[0] : k[1]) >> (8 * (s & 3))) & 0xFFu);
     if (n > 0 && n < K) {
-      const float iv = intensity * ((float)n * rk);
+      const float iv = partial_intensity(intensity, n, rk);
       cr = r * iv; cg = g * iv; cb = b * iv;
     }
   }
@@ -2629,27 +2631,9 @@ struct ShadowCastersSkip {
 template <bool DUMP>
 struct ShadowCastersTest {
   const ShadowCastersArgs &a;
-  // k of the window round texel (i, j), as ShadowPcfTest::lit_taps
-  template <int RADIUS>
-  BB_DEV int lit_taps(const float *face_map, int i, int j, float t) const {
-    const int last = a.side - 1;
-    int n = 0;
-#pragma unroll 1
-    for (int dj = -RADIUS; dj <= RADIUS; ++dj) {
-      const float *row = face_map + (size_t)min(max(j + dj, 0), last) * (size_t)a.side;
-      float texel[2 * RADIUS + 1];
-#pragma unroll
-      for (int di = -RADIUS; di <= RADIUS; ++di) texel[di + RADIUS] = row[min(max(i + di, 0), last)];
-#pragma unroll
-      for (int q = 0; q <= 2 * RADIUS; ++q) n += texel[q] > t ? 0 : 1;
-    }
-    return n;
-  }
   BB_DEV ShadowCastersSkip on(const FrameParams &fp, f3 P, bool valid, int gx, int gy) const {
     const ConstCasters table = (ConstCasters)a.table;
-    const float side = (float)a.side;
-    const size_t texels = (size_t)a.side * (size_t)a.side;
-    const int R = a.radius, K = (2 * R + 1) * (2 * R + 1);
+    const int R = a.radius, K = shadow_taps(R);
     const uint32_t all_k = (uint32_t)K * 0x01010101u;
     uint32_t packed[2] = {all_k, all_k};
 #pragma unroll 1
@@ -2658,46 +2642,22 @@ struct ShadowCastersTest {
       if (faces == 0) continue;
       // (nothing observable depends on a caster beyond the frame's lights -- but its mask is observable)
       if (!DUMP && table->slot[s].light >= a.num_lights) continue;
-      const float bias = table->slot[s].bias;
-      const float *map = table->slot[s].map;
-      int cls = kShadowOutside, face = 255, k = 255;
-#pragma unroll 1
-      for (int f = 0; f < faces; ++f) {
-        const bool undecided = cls == kShadowOutside;
-        if (__ballot(undecided) == 0ull) break;
+      const auto matrix_of = [&](int f) {  // a Mat4 in scalar registers
         Mat4 m;
 #pragma unroll
         for (int col = 0; col < 4; ++col)
 #pragma unroll
           for (int row = 0; row < 4; ++row) m.M[col][row] = table->slot[s].m[f].M[col][row];
-        const f4 c = mat4_mul(m, f4{P.x, P.y, P.z, 1.0f});
-        const float r = bb_rcp(c.w);  // (of a w <= 0 too: not used then)
-        const float xs = fmaf(c.x * r, a.half, a.half), ys = fmaf(c.y * r, a.half, a.half);
-        const bool inside = c.w > 0.0f && xs >= 0.0f && xs < side && ys >= 0.0f && ys < side;
-        if (undecided && inside) {
-          const int i = (int)xs, j = (int)ys;  // 0 .. S - 1
-          const float t = c.z * r + bias;
-          const float *face_map = map + (size_t)f * texels;
-          int n;
-          if (R == 0) n = face_map[(size_t)j * (size_t)a.side + (size_t)i] > t ? 0 : 1;
-          else n = R == 1 ? lit_taps<1>(face_map, i, j, t) : lit_taps<2>(face_map, i, j, t);
-          k = n;
-          cls = n == K ? kShadowLit : (n == 0 ? kShadowShadowed : kShadowPartial);
-          face = f;
-        }
-      }
-      const uint32_t byte = cls == kShadowOutside ? (uint32_t)K : (uint32_t)k;
+        return m;
+      };
+      const ShadowVerdict v = shadow_verdict(matrix_of, table->slot[s].map, faces, a.side, a.half, table->slot[s].bias, R, P);
+      const uint32_t byte = v.cls == kShadowOutside ? (uint32_t)K : (uint32_t)v.k;
       const uint32_t shift = 8u * (uint32_t)(s & 3);
       uint32_t &word = s < 4 ? packed[0] : packed[1];
       word = (word & ~(0xFFu << shift)) | (byte << shift);
-      if (DUMP && valid && s == a.dump_slot) {
-        const size_t o = (size_t)gy * (size_t)fp.width + (size_t)gx;
-        if (a.mask) a.mask[o] = (uint8_t)cls;
-        if (a.face) a.face[o] = (uint8_t)face;
-        if (a.taps) a.taps[o] = (uint8_t)k;
-      }
+      if (DUMP && valid && s == a.dump_slot) v.dump(fp, gx, gy, a.mask, a.face, a.taps);
     }
-    return ShadowCastersSkip{table, (ConstLight)a.lights, K, R == 0 ? 1.0f : (R == 1 ? 1.0f / 9.0f : 1.0f / 25.0f), {packed[0], packed[1]}};
+    return ShadowCastersSkip{table, (ConstLight)a.lights, K, shadow_rk(R), {packed[0], packed[1]}};
   }
 };
 
@@ -3344,7 +3304,7 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_aniso(
 }
 
 // k_shade_shadow: the fragment stage of k_shade_aniso ("max_anisotropy" 1 .. 16) with the shadow test in front of the caster's
-// iteration of the light loop (the rule: in front of ShadowTest).  The test is evaluated in surface_colour, behind the filter,
+// iteration of the light loop (the rule: at the head of "Shadow mapping").  The test is evaluated in surface_colour, behind the filter,
 // where the footprint's registers are dead.  DUMP as in k_shade_aniso, plus the class of every pixel where `shadow.mask` is set.
 template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
 __global__ __launch_bounds__(kShadeThreads) void k_shade_shadow(
@@ -3361,7 +3321,7 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_shadow(
                                                            ShadowTest<DUMP>{shadow});
 }
 
-// k_shade_shadow_faces: k_shade_shadow with 2 .. 6 faces for the caster (the rule: in front of ShadowFacesTest).  DUMP as in
+// k_shade_shadow_faces: k_shade_shadow with 2 .. 6 faces for the caster (the rule: in front of ShadowFacesArgs).  DUMP as in
 // k_shade_shadow, plus the deciding face of every pixel where `shadow.face` is set.
 template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
 __global__ __launch_bounds__(kShadeThreads) void k_shade_shadow_faces(
@@ -3378,7 +3338,7 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_shadow_faces(
                                                            ShadowFacesTest<DUMP>{shadow});
 }
 
-// k_shade_shadow_pcf: k_shade_shadow / k_shade_shadow_faces with option "shadow_filter" (the rule: in front of ShadowPcfTest), one
+// k_shade_shadow_pcf: k_shade_shadow / k_shade_shadow_faces with option "shadow_filter" (the rule: in front of ShadowPcfArgs), one
 // kernel for 1 .. 6 faces and both radii.  DUMP as in k_shade_shadow_faces, plus k of every pixel where `shadow.taps` is set.
 template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
 __global__ __launch_bounds__(kShadeThreads) void k_shade_shadow_pcf(
@@ -3396,7 +3356,7 @@ __global__ __launch_bounds__(kShadeThreads) void k_shade_shadow_pcf(
 }
 
 // k_shade_shadow_casters: the kernel of a context with a caster slot other than 0 in use (the rule: in front of
-// ShadowCastersTest), one kernel for every number of casters, 1 .. 6 faces each and R = 0 .. 2.  DUMP as in k_shade_shadow_pcf,
+// ShadowCasterEntry), one kernel for every number of casters, 1 .. 6 faces each and R = 0 .. 2.  DUMP as in k_shade_shadow_pcf,
 // for the slot `shadow.dump_slot`.
 template <int TILE_W, int TILE_H, bool DEFERRED, bool PRESENT, bool DUMP = false>
 __global__ __launch_bounds__(kShadeThreads) void k_shade_shadow_casters(

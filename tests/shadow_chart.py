@@ -1,5 +1,5 @@
-"""Shadow chart: 128 x 128 frames whose pixels are a CHOSEN population of positions for the shadow test (ShadowTest::classify
-and its three copies in csrc/bb_kernels.hip.h; DESIGN.md section 3, "Shadow chart").  TEST INFRASTRUCTURE ONLY; no test lives
+"""Shadow chart: 128 x 128 frames whose pixels are a CHOSEN population of positions for the shadow test (shadow_texel and
+the pieces the four shadow kernels share in csrc/bb_kernels.hip.h; DESIGN.md section 3, "Shadow chart").  TEST INFRASTRUCTURE ONLY; no test lives
 here.
 
 The scenes of tests/shadow_scenes.py and its descendants put every receiver on ONE plane perpendicular to the caster's axis: the

@@ -2,22 +2,27 @@
 period over 200 timed frames after the steady warm-up.  A caster is tools/shadow_faces_cost.py's cube: six faces of 96 degrees
 at the light's position, S = 1024.
 
-  (a)  the default frame (k_shade) and the frame with light 0 a cube caster in slot 0 (k_shade_shadow_faces), on this tree and,
-       with --parent ROOT (the parent commit's tree, built), on that tree: the unchanged paths, alternated in the same call
+  (a)  the default frame (k_shade) and the frame with light 0 a caster in slot 0: the cube's first face alone (k_shade_shadow),
+       the cube (k_shade_shadow_faces), the cube at R = 1 (k_shade_shadow_pcf)
   (b)  the same caster in slot 1 (k_shade_shadow_casters) against slot 0: the price of the general kernel
   (c)  all four lights of C3 as cube casters, at R = 0 and R = 1
   (d)  the wall time of the four bbr_render_shadow_caster calls of (c)
 
+With --parent ROOT (the parent commit's tree, built) every case runs on both trees, alternated in the same call: each of the four
+shadow kernels against its parent.  Per case the difference of the two medians is set against the parent's own spread (max - min
+over its repetitions).
 Every case runs in a process of its own under a time limit, behind bench.py's steady warm-up rule; the first case that fails
 ends the run.
 usage: shadow_casters_cost.py [--reps 3] [--frames 200] [--rounds 2] [--parent ROOT] [--out FILE]"""
 import argparse
 import json
 import os
+import statistics
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PARENT = "parent: "
 
 CHILD = r'''
 import sys, time, gc, json
@@ -25,7 +30,7 @@ import numpy as np
 sys.path.insert(0, %(root)r)
 from bibim_renderer_amd import configs, textures, Renderer
 from bibim_renderer_amd import scene as S
-SLOTS, RADIUS, REPS, FRAMES = %(slots)r, %(radius)d, %(reps)d, %(frames)d
+SLOTS, FACES, RADIUS, REPS, FRAMES = %(slots)r, %(faces)d, %(radius)d, %(reps)d, %(frames)d
 cfg = configs.C3
 r = Renderer(cfg.width, cfg.height)
 r.set_option("frames_in_flight", 3)
@@ -38,10 +43,10 @@ frame = S.frame_call(r, scene, cam, settings, material)
 frame(); r.synchronize()                      # the first frame sizes the capacities
 out = dict(shadowed=[], cast_ms=[])
 for slot, light in SLOTS:
-    views = S.cube_shadow_views(cfg.lights[light].pos, 96.0, 0.1, 1000.0)
+    views = S.cube_shadow_views(cfg.lights[light].pos, 96.0, 0.1, 1000.0)[:FACES]
     t0 = time.perf_counter()
     if slot is None:
-        r.render_shadow_faces(light, views, 2.0 ** -10)        # (the call both trees have: slot 0)
+        r.render_shadow_faces(light, views, 2.0 ** -10)        # (slot 0)
     else:
         r.render_shadow_caster(slot, light, views, 2.0 ** -10)
     out["cast_ms"].append((time.perf_counter() - t0) * 1e3)
@@ -75,7 +80,7 @@ scene.close(); r.close()
 
 
 def run(tag, **kw):
-    args = dict(root=ROOT, slots=[], radius=0)
+    args = dict(root=ROOT, slots=[], faces=6, radius=0)
     args.update(kw)
     p = subprocess.run([sys.executable, "-c", CHILD % args], capture_output=True, text=True, timeout=240)
     if p.returncode:
@@ -93,7 +98,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=2)
-    ap.add_argument("--parent", default=None, help="root of the parent commit's tree, built: its default and slot-0 frames are timed too")
+    ap.add_argument("--parent", default=None, help="root of the parent commit's tree, built: every case is timed on it too")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     common = dict(reps=a.reps, frames=a.frames)
@@ -104,15 +109,18 @@ def main():
         lines.append(s)
 
     four = [(s, s) for s in range(4)]
-    cases = [("(a) default (k_shade)", dict()),
-             ("(a) cube caster in slot 0 (k_shade_shadow_faces)", dict(slots=[(None, 0)])),
-             ("(b) the same caster in slot 1 (k_shade_shadow_casters)", dict(slots=[(1, 0)])),
-             ("(c) four cube casters, R = 0 (k_shade_shadow_casters)", dict(slots=four)),
-             ("(c) four cube casters, R = 1 (k_shade_shadow_casters)", dict(slots=four, radius=1))]
-    if a.parent:
-        parent = os.path.abspath(a.parent)
-        cases[1:1] = [("(a) the parent's default", dict(root=parent))]
-        cases[3:3] = [("(a) the parent's cube caster", dict(root=parent, slots=[(None, 0)]))]
+    own = [("(a) default (k_shade)", dict()),
+           ("(a) first face in slot 0 (k_shade_shadow)", dict(slots=[(None, 0)], faces=1)),
+           ("(a) cube caster in slot 0 (k_shade_shadow_faces)", dict(slots=[(None, 0)])),
+           ("(a) cube caster in slot 0, R = 1 (k_shade_shadow_pcf)", dict(slots=[(None, 0)], radius=1)),
+           ("(b) the same caster in slot 1 (k_shade_shadow_casters)", dict(slots=[(1, 0)])),
+           ("(c) four cube casters, R = 0 (k_shade_shadow_casters)", dict(slots=four)),
+           ("(c) four cube casters, R = 1 (k_shade_shadow_casters)", dict(slots=four, radius=1))]
+    cases = []
+    for name, kw in own:
+        cases.append((name, kw))
+        if a.parent:
+            cases.append((PARENT + name, dict(kw, root=os.path.abspath(a.parent))))
     say(f"# C3 scene (3840 x 2160), three frames in flight: frame period, us per frame ({a.frames} frames between two synchronisations, "
         f"{a.reps} runs per process), the cases alternated, {a.rounds} rounds: {a.reps * a.rounds} repetitions each")
     seen = {name: [] for name, _ in cases}
@@ -122,22 +130,29 @@ def main():
         for name, kw in cases:
             last[name] = run(name, **kw, **common)
             seen[name] += last[name]["period_us"]
-            say(f"{name:58s} {fmt(last[name]['period_us'])}")
+            say(f"{name:66s} {fmt(last[name]['period_us'])}")
             if len(kw.get("slots", [])) == 4:
                 cast.append((name, last[name]["cast_ms"]))
     say()
     say("# range over all repetitions, us per frame")
     for name, _ in cases:
-        say(f"{name:58s} {min(seen[name]):8.1f} .. {max(seen[name]):8.1f}")
+        say(f"{name:66s} {min(seen[name]):8.1f} .. {max(seen[name]):8.1f}")
     say()
+    if a.parent:
+        say("# median of this tree, of the parent, their difference, the parent's spread (max - min); inside: |difference| <= spread")
+        for name, _ in own:
+            new, old = statistics.median(seen[name]), statistics.median(seen[PARENT + name])
+            spread = max(seen[PARENT + name]) - min(seen[PARENT + name])
+            say(f"{name:66s} {new:8.1f} {old:8.1f} {new - old:+8.1f} {spread:8.1f}   {'inside' if abs(new - old) <= spread else 'OUTSIDE'}")
+        say()
     say("# (d) wall time of the four bbr_render_shadow_caster calls (six faces of S = 1024 each; the first also makes the pass's buffers), ms")
     for name, ms in cast:
-        say(f"{name:58s} {fmt(ms, '%8.2f')}   sum {sum(ms):8.2f}")
+        say(f"{name:66s} {fmt(ms, '%8.2f')}   sum {sum(ms):8.2f}")
     say()
     say("# share of the frame's pixels SHADOWED or PARTIAL, per caster (the last round)")
     for name, _ in cases:
         if last[name]["shadowed"]:
-            say(f"{name:58s} {fmt(last[name]['shadowed'], '%.4f')}")
+            say(f"{name:66s} {fmt(last[name]['shadowed'], '%.4f')}")
     if a.out:
         with open(a.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
