@@ -1436,6 +1436,7 @@ BB_DEV unsigned long long fetch_fragment(uint32_t item, const ItemPlace &p, int 
 // ------------------------------------------------------------------------------------------------
 constexpr int kStage = kTileThreads;  // staged entries per chunk (one per thread)
 constexpr uint32_t kBroadSpec = 16;    // every-tile-list entries a light tile fetches before it knows the count
+constexpr uint32_t kSkyKept = 1u;      // option "sky_keep": bit 0 of a tile's word = the tile's fill was skipped (stamps are even)
 
 struct StagedTri {  // struct-of-arrays in LDS: thread j owns column j when filling
   int X0[kStage], Y0[kStage], X1[kStage], Y1[kStage], X2[kStage], Y2[kStage];
@@ -1588,7 +1589,9 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
     const float4 *__restrict__ background, float *__restrict__ depth_io, uint32_t *__restrict__ host_flags,
     uint32_t *__restrict__ out8, uint32_t *__restrict__ item_groups, uint32_t *__restrict__ item_head,
     uint32_t *__restrict__ items, const Light *__restrict__ lights, int num_lights, CookedLight *__restrict__ cooked,
-    const uint32_t *__restrict__ heavy) {
+    const uint32_t *__restrict__ heavy,
+    // option "sky_keep" (the light-tile path): the slot's word per tile and this frame's stamp, or nullptr / 0: never keep
+    uint32_t *__restrict__ sky_state, uint32_t sky_stamp) {
   constexpr int TILE_PIXELS = TILE_W * TILE_H;
   // ---- the workgroup's LDS ----
   __shared__ unsigned long long keys[TILE_PIXELS];  // depth bits << 32 | reference + 1; 0: nothing drawn
@@ -1689,6 +1692,18 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
   //  counts above, in front of the tile's first decision.  As `overflow & 2 ? 0 : n_broad` the compiler made the second
   //  load wait for the first.)
   const uint32_t ctr_overflow = ctr->overflow, ctr_n_broad = ctr->n_broad, ctr_n_heavy = ctr->n_heavy;
+  // SKY KEEP (option "sky_keep"; main passes into the slot's own fp32 frame only, the host decides: bibim_hip.hip, sky_stamp_for).
+  // One word per tile, the slot's: sky_stamp (+ kSkyKept) says that every in-frame pixel of the tile, in the buffer this slot's
+  // frames go to, holds the clear colour -- the light path below left it so in an earlier frame under the same stamp, and
+  // nothing has written the buffer since (whatever does makes the host hand out a fresh stamp: no word can equal it).  Such
+  // a tile's 16 KB of background stores are not issued again.  Every other way a tile is finished leaves 0, which no stamp
+  // is.  The word travels with the counts above (the same round trip); it is stored by one thread, and only where it changes.
+  uint32_t sky = 0u;
+  const bool sky_on = !OVERLAY && sky_state != nullptr && sky_stamp != 0u;
+  if (sky_on) sky = sky_state[tg.tile];
+  auto sky_word = [&](uint32_t want) {  // (thread 0)
+    if (sky_on && sky != want) sky_state[tg.tile] = want;
+  };
   const uint32_t n_broad = BB_ABLATE(5u) ? 0u : (min(ctr_n_broad, fp.broad_cap) & (((ctr_overflow >> 1) & 1u) - 1u));
   if (!OVERLAY && fp.heavy_rows) {
     if (heavy_slot) {   // (the list is in use, or this workgroup had left above)
@@ -1757,6 +1772,12 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
     }
     const unsigned long long m_ok = __ballot(ok);
     if (m_ok == 0ull) {
+      const bool keep = sky_on && (sky & ~kSkyKept) == sky_stamp;
+      if (tid == 0) {
+        frag_count[tg.tile] = 0u;
+        sky_word(keep ? sky_stamp | kSkyKept : sky_stamp);
+      }
+      if (keep) return;   // (diagnostic build: no stamps for a kept tile)
       // the same pixels in the same order as `for (p = tid; p < TILE_PIXELS; p += kTileThreads) tile_pixel(p)` would visit them,
       // without that function's arithmetic per pixel: pass k of thread tid is pixel (x, y + k * STEP) of the tile
       // (kTileThreads = 256 pixels = 4 blocks of 8 x 8 = a strip TILE_W wide or, for 64-pixel tiles, half of one)
@@ -1769,7 +1790,6 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
         const int x = (block % BX) * 8 + (tid & 7), y = (block / BX) * 8 + ((tid >> 3) & 7);
         if (tg.x0 + x < fp.width && tg.y0 + y < fp.height) store_background(x, y);
       }
-      if (tid == 0) frag_count[tg.tile] = 0u;
       BB_RSTAMP(1); BB_RSTAMP(2); BB_RSTAMP(3); BB_RSTAMP(4);   // (diagnostic build: a light tile's phases all end here)
       return;
     }
@@ -1780,6 +1800,7 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
         frags[(size_t)tg.tile * TILE_PIXELS] = fragment_word((uint32_t)__builtin_amdgcn_readlane((int)clip_slot1, src), 0u,
                                                           (uint32_t)__builtin_amdgcn_readlane((int)ref, src));
         frag_count[tg.tile] = (uint32_t)TILE_PIXELS | kFullTile;
+        sky_word(0u);
         if (item_groups) atomicAdd(&item_groups[(slot / kItemGroupSlots) * kItemGroupStride], (uint32_t)(TILE_PIXELS / 64));
       }
       if (item_head && wave == 0) append_items(item_head, items, lane, (uint32_t)(TILE_PIXELS / 64), kFullTile);
@@ -1791,6 +1812,7 @@ __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(TI
   // ---- clear.  Out: keys, s_count, s_n_clip_refs; behind the barrier the tile's bin counts ----
   clear_keys<TILE_W, TILE_H, OVERLAY>(keys, tg, fp, depth_io, tid);
   if (tid == 0) {
+    sky_word(0u);  // (the general path, a heavy slot's tile included: its pixels are no longer all background)
     s_count = 0;
     s_n_clip_refs = 0;
   }

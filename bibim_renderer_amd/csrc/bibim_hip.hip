@@ -142,11 +142,22 @@ struct TileSized {
   DeviceBuffer<uint32_t> d_tile_count;
   DeviceBuffer<uint32_t> d_bins;
   DeviceBuffer<unsigned long long> d_frags;  // per tile: compacted (pixel << 32 | primitive ref) of covered pixels
-  DeviceBuffer<uint32_t> d_frag_count;
+  DeviceBuffer<uint32_t> d_frag_count;       // per tile; behind the counts, option "sky_keep": k_raster's word per tile (sky_words)
   DeviceBuffer<uint32_t> d_items;       // k_shade's work list: [0] = count, then slot << 6 | chunk of 64 fragments
   DeviceBuffer<CookedLight> d_cooked;   // the frame's light table as the light loop consumes it (k_shade_items -> k_shade)
   DeviceBuffer<uint32_t> d_heavy;       // the frame's heavy-tile list (k_geometry -> k_raster; option "heavy_tiles")
   DeviceBuffer<uint32_t> d_item_groups; // 64-fragment chunks per group of 256 launch slots (k_raster -> k_shade_items)
+};
+
+// Option "sky_keep": what a slot remembers about the background in its d_frame.  While `stamp` is non-zero, a tile whose word
+// behind the slot's fragment counts carries it holds the clear colour in every pixel of the buffer described by the other members (k_raster's
+// light-tile path establishes that, and nothing else).  The stamp is kept from frame to frame only while the next frame goes
+// into that same buffer in a mode that may keep (sky_stamp_for); forgetting is asking for a fresh one, which no word holds.
+struct SkyKeep {
+  uint32_t stamp = 0;        // 0: nothing is remembered
+  uint32_t used = 0;         // the stamp the slot's last frame ran under (0: it kept nothing and marked nothing): bbr_read_sky_tiles
+  const void *out = nullptr, *state = nullptr;  // the frame and the state buffer the stamp speaks of
+  int32_t width = 0, height = 0, tiles_x = 0, tiles_y = 0, tile_mode = -1;
 };
 // ... by the render or the output extent: bbr_resize and option "supersample" drop it (drop_extent_buffers)
 struct ExtentSized {
@@ -233,6 +244,12 @@ struct FrameSlot : TileSized, ExtentSized {
   void forget_extent() {
     if (uint32_t *f = h_flags.ptr) f[kFlagOverflow] = f[kFlagBinNeed] = f[kFlagItemCount] = 0u;
   }
+  // Option "sky_keep": something other than this slot's own k_raster / k_shade may have written its frame, or the frame or
+  // the state words are not the ones the stamp speaks of.  The rule for every entry point that touches a slot's image or its
+  // buffers outside launch_frame: call this (forget_sky(c) does it for every slot).  Touches no memory: the slot's next
+  // frame runs under a fresh stamp, fills every sky tile and keeps again from the frame after.
+  SkyKeep sky;
+  void forget_sky() { sky.stamp = 0; }
   // native exchange (bbr_allgather_frame / bbr_push_shard) with library-owned buffers: every rank's block, the whole frame
   DeviceBuffer<uint8_t> d_gathered, d_whole;
 };
@@ -386,6 +403,9 @@ struct bbr_context : ExtentDumps {
   // option "static_records": 1 = a draw whose key repeats in a slot has the camera-independent part of its records written
   // once (k_record_static) and k_geometry's light path from then on; 0 = always the full path
   bool static_records = true;
+  // option "sky_keep": 1 = a tile that was background when its frame slot rendered last, and is background again, is not
+  // filled again (k_raster's light-tile path, SkyKeep); 0 = every frame stores every background pixel
+  bool sky_keep = true;
   bool dump_records = false;    // (bbr_read_records: its frame shows what k_geometry's full path writes, and what it leaves alone)
   // Bumped by every call that can change what a mesh or material handle, or a pointer taken from one, means (upload and free
   // of either, the material table, the mip chains): a freed and reused address never compares equal to its former self.
@@ -547,6 +567,48 @@ void forget_current_frame(bbr_context *c) {
   c->have_frame = false;
 }
 
+// Option "sky_keep": the slot's word per tile stands behind the `tiles` fragment counts in d_frag_count, zeroed with them when
+// the buffer is made (0 is no stamp) and dropped with them (the tile group: no allocation of its own)
+#ifdef BB_STAMPS
+constexpr size_t kFragCountWords = 18;  // diagnostic build: counts, 8 x u64 raster stamps per tile, the sky words
+#else
+constexpr size_t kFragCountWords = 2;   // counts, sky words
+#endif
+uint32_t *sky_words(const FrameSlot &s, size_t tiles) {
+  return s.d_frag_count.cap >= tiles * kFragCountWords ? s.d_frag_count.ptr + tiles * (kFragCountWords - 1) : nullptr;
+}
+// Option "sky_keep": every slot forgets (FrameSlot::forget_sky has the rule)
+void forget_sky(bbr_context *c) {
+  for (FrameSlot &s : c->slots) s.forget_sky();
+}
+// The stamp a main frame about to be launched into slot `s` runs under (0: it keeps nothing and marks nothing; k_raster then
+// gets no state words at all).  A frame may keep while it is a forward frame of the whole image, one sample per pixel, into
+// the slot's own fp32 frame, and k_raster's light-tile path is in use (no depth or visibility store); the slot's stamp lives
+// on while such a frame follows such a frame into the same buffer under the same tile grid with the same state words.
+// Everything else gets, or leaves behind, a fresh stamp from a process-wide counter: bit 30 set, bit 0 (kSkyKept) and bit 31
+// clear, so it is never 0, k_raster's words of earlier stamps cannot equal it, and neither can the zeros of a new buffer
+// or a fragment count (at most a tile's pixels, with or without kFullTile = bit 31).
+uint32_t sky_stamp_for(const bbr_context *c, FrameSlot &s, const FrameMode &mode, const float4 *out) {
+  const uint32_t *state = sky_words(s, (size_t)c->tiles_x() * c->tiles_y());
+  const bool may_keep = c->sky_keep && !c->ablate && !c->deferred && !c->ext_out && c->world == 1 && !c->dump_vis && !mode.fused &&
+                        !mode.resolve && !mode.depth && out && out == s.d_frame.ptr && state;
+  const SkyKeep now = {s.sky.stamp, 0u, out, state, c->width, c->height, c->tiles_x(), c->tiles_y(), c->tile_mode};
+  const SkyKeep &was = s.sky;
+  if (!may_keep || was.out != now.out || was.state != now.state || was.width != now.width || was.height != now.height ||
+      was.tiles_x != now.tiles_x || was.tiles_y != now.tiles_y || was.tile_mode != now.tile_mode)
+    s.forget_sky();
+  const uint32_t kept_stamp = s.sky.stamp;
+  s.sky = now;
+  s.sky.stamp = kept_stamp;
+  if (may_keep && !s.sky.stamp) {
+    static std::atomic<uint32_t> counter{0};
+    s.sky.stamp = 0x40000000u | ((counter.fetch_add(1u) << 1) & 0x3FFFFFFEu);
+  }
+  if (!may_keep) s.sky.stamp = 0;
+  s.sky.used = s.sky.stamp;
+  return s.sky.stamp;
+}
+
 // P*V exactly as the vertex stage's contract evaluates it (column j = P * V[j], fmaf chain)
 Mat4 proj_view(const ViewUniformBlock &v) {
   Mat4 r;
@@ -627,11 +689,7 @@ int ensure_pass_buffers(bbr_context *c, FrameSlot &s, uint32_t n_prims, size_t t
   // (at least kBroadSpec entries: k_raster's light-tile path reads that many before it knows how many the frame wrote)
   HIP_TRY(c, s.d_broad.ensure(std::max<size_t>(c->broad_cap, kBroadSpec), true));
   HIP_TRY(c, s.d_frags.ensure(tiles * (size_t)(c->tile_w() * c->tile_h())));
-#ifdef BB_STAMPS
-  HIP_TRY(c, s.d_frag_count.ensure(tiles * 17, true));  // diagnostic build: 8 x u64 raster stamps per tile behind the counts
-#else
-  HIP_TRY(c, s.d_frag_count.ensure(tiles, true));
-#endif
+  HIP_TRY(c, s.d_frag_count.ensure(tiles * kFragCountWords, true));  // (the counts and what stands behind them: sky_words)
   return BBR_OK;
 }
 
@@ -859,11 +917,13 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   if (fp.deferred)
     hipLaunchKernelGGL(k_deferred_background, dim3(1), dim3(kBackgroundThreads), 0, sr, sp, d_lights, s.d_background.ptr, tables, fp.gbuffer_view);
   uint32_t *item_head = short_frame ? d_item_head : nullptr;
+  // option "sky_keep": the stamp this frame's light tiles keep and mark under, if the frame may (k_raster writes `final_out` then)
+  const uint32_t sky_stamp = sky_stamp_for(c, s, mode, final_out);
   hipLaunchKernelGGL((k_raster<TW, TH>), dim3(fp.tiles_x, fp.heavy_rows + grid_y), dim3(kTileThreads), 0, sr, s.d_tile_count.ptr, ctr,
                      s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, out, fp, s.d_tris.ptr, s.d_clip.ptr, s.d_bins.ptr,
                      vis_prim, vis_depth,
                      fp.deferred ? s.d_background.ptr : nullptr, depth, s.h_flags.ptr, out8, (short_frame || merged) ? nullptr : s.d_item_groups.ptr, item_head, s.d_items.ptr, d_lights, sp.num_lights,
-                     s.d_cooked.ptr, s.d_heavy.ptr);
+                     s.d_cooked.ptr, s.d_heavy.ptr, sky_stamp ? sky_words(s, (size_t)fp.tiles_x * fp.tiles_y) : nullptr, sky_stamp);
   if (merged)
     with_samples(mode.n, [&](auto n) {
       constexpr int N = decltype(n)::value;
@@ -1300,6 +1360,7 @@ int sync_and_fix(bbr_context *c, Counters *out_counters) {
 int rerender_with(bbr_context *c, bool bbr_context::*dump) {
   int rc = sync_and_fix(c, nullptr);
   if (rc) return rc;
+  forget_sky(c);  // (a diagnostic frame: rendered in full)
   c->*dump = true;
   rc = resubmit_last_frame(c);
   if (rc == BBR_OK) rc = sync_and_fix(c, nullptr);
@@ -1493,6 +1554,7 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
   if (int rc = refuse_without_depth_rule(c, "draw_overlays", "no depth resolve rule: option depth_resolve is 0")) return rc;
   int rc = sync_and_fix(c, nullptr);  // the overlay pass is synchronous: it is a debugging aid, not part of the hot path
   if (rc) return rc;
+  forget_sky(c);
   FrameSlot &fs = c->slots[c->last_slot];
   if (!fs.mode.depth) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_overlays: the frame was rendered without option \"overlays\"");
   if (!fs.present.active) return fail(c, BBR_ERR_NOT_IN_FRAME, "draw_overlays: call bbr_present first (overlays go into the presented image)");
@@ -1588,7 +1650,7 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
                          s.d_bins.ptr, (uint32_t *)nullptr, (float *)nullptr,
                          (const float4 *)nullptr, fs.d_depth.ptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
                          (uint32_t *)nullptr, (uint32_t *)nullptr, (const Light *)nullptr, 0, (CookedLight *)nullptr,
-                         (const uint32_t *)nullptr);
+                         (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u);
       constexpr int kChunks = TW * TH / kShadeThreads;
       hipLaunchKernelGGL((k_shade_overlay<TW, TH>), dim3(fp.tiles_x * kChunks, fp.tiles_y), dim3(kShadeThreads), 0, st, fp,
                          s.d_attrs.ptr, s.d_clip.ptr, s.d_frags.ptr, s.d_frag_count.ptr, c->d_srgb_tables.ptr, fs.present.out);
@@ -1735,7 +1797,7 @@ static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t c
                          s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, (float4 *)nullptr, fp, s.d_tris.ptr, s.d_clip.ptr,
                          s.d_bins.ptr, (uint32_t *)nullptr, (float *)nullptr, (const float4 *)nullptr, cs.d_map.ptr + (size_t)f * texels,
                          (uint32_t *)nullptr, sh.d_sink.ptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                         (const Light *)nullptr, 0, (CookedLight *)nullptr, (const uint32_t *)nullptr);
+                         (const Light *)nullptr, 0, (CookedLight *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u);
     };
     for (int f = 0; f < n_faces; ++f) {
       if (c->tile_mode == 0) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{}, f);
@@ -1963,6 +2025,7 @@ extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
   FrameSlot &s = c->slots[c->last_slot];
   if (!s.present.active || !s.present.out)
     return fail(c, BBR_ERR_NOT_IN_FRAME, "draw_ui: call bbr_present first (the GUI goes into the presented image)");
+  forget_sky(c);
   // int fb_width = (int)(DisplaySize.x * FramebufferScale.x), as the back end computes it
   for (int k = 0; k < 2; ++k) {
     const float f = draw->display_size[k] * draw->framebuffer_scale[k];
@@ -2451,6 +2514,7 @@ int bbr_framebuffer_device_ptr(bbr_context *c, void **out_ptr, uint64_t *out_byt
   BBR_ON_DEVICE(c);
   if (!out_ptr) return fail(c, BBR_ERR_INVALID_ARGUMENT, "framebuffer_device_ptr: NULL");
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "framebuffer_device_ptr: nothing rendered");
+  forget_sky(c);  // (the caller may write through the pointer before the next frame)
   *out_ptr = (void *)c->slots[c->last_slot].out_used;
   if (out_bytes)
     *out_bytes = c->ext_out ? c->ext_out_bytes : (uint64_t)c->width * std::max(c->height, c->shard_rows()) * 16;
@@ -2467,6 +2531,7 @@ int bbr_set_output_device_ptr(bbr_context *c, void *device_ptr, uint64_t bytes) 
   }
   c->ext_out = device_ptr;
   c->ext_out_bytes = device_ptr ? bytes : 0;
+  forget_sky(c);
   return BBR_OK;
 }
 
@@ -2514,6 +2579,7 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
   c->rank = rank;
   c->world = world;
   c->band_rows = band_rows;
+  forget_sky(c);
   for (FrameSlot &s : c->slots) {  // (a fine shard's padding rows, and their map words, are the zeros of a fresh buffer)
     s.d_fine.release();
     s.d_fine_depth.release();
@@ -2563,6 +2629,7 @@ int bbr_resize(bbr_context *c, int32_t width, int32_t height) {
   if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "resize: between begin_frame and end_frame");
   int rc = drain(c);
   if (rc) return rc;
+  forget_sky(c);
   if (width == c->width && height == c->height) return BBR_OK;
   c->width = width;
   c->height = height;
@@ -2839,6 +2906,28 @@ int bbr_static_record_counts(const bbr_context *c, uint64_t *out_fills, uint64_t
   return BBR_OK;
 }
 
+int bbr_read_sky_tiles(bbr_context *c, uint8_t *out, uint32_t cap, uint32_t *out_count) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_sky_tiles: nothing rendered");
+  int rc = sync_and_fix(c, nullptr);
+  if (rc) return rc;
+  const FrameSlot &s = c->slots[c->last_slot];
+  const uint32_t tiles = (uint32_t)c->tiles_x() * (uint32_t)c->tiles_y();
+  if (out_count) *out_count = tiles;
+  if (!out) return BBR_OK;
+  if (cap < tiles) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_sky_tiles: cap is smaller than the tile count");
+  std::fill(out, out + tiles, (uint8_t)BBR_SKY_TILE_NONE);
+  const uint32_t stamp = s.sky.used;  // (the frame, or its re-render after a capacity growth, ran under it)
+  const uint32_t *state = sky_words(s, tiles);
+  if (!stamp || !state || state != s.sky.state) return BBR_OK;
+  std::vector<uint32_t> words(tiles);
+  HIP_TRY(c, hipMemcpy(words.data(), state, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (uint32_t t = 0; t < tiles; ++t)
+    if ((words[t] & ~kSkyKept) == stamp) out[t] = (words[t] & kSkyKept) ? BBR_SKY_TILE_KEPT : BBR_SKY_TILE_FILLED;
+  return BBR_OK;
+}
+
 int bbr_debug_live_resources(uint64_t out[5]) {
   if (!out) return BBR_ERR_INVALID_ARGUMENT;
   const LiveCounts &n = g_live_counts;
@@ -2932,6 +3021,7 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   }
   int rc = drain(c);
   if (rc) return rc;
+  forget_sky(c);  // (whatever the option is: options are not set between the frames of a steady run)
   if (n == "timing") {
     if (value < 0 || value > 2) return fail(c, BBR_ERR_INVALID_ARGUMENT, "timing: 0, 1 or 2");
     c->timing = (int)value;
@@ -3047,6 +3137,9 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   } else if (n == "static_records") {
     if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "static_records: 1 (write a static draw's record part once) or 0 (every frame)");
     c->static_records = value == 1;
+  } else if (n == "sky_keep") {
+    if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "sky_keep: 1 (a tile that stays background is filled once per frame slot) or 0 (every frame)");
+    c->sky_keep = value == 1;
   } else if (n == "present_fused") {
     c->present_fused = value != 0;
   } else if (n == "overlays") {
@@ -3282,6 +3375,7 @@ int check_exchange(bbr_context *c, int form, const char *who) {
 }
 
 int unpack_whole(bbr_context *c, int form, const void *gathered, void *whole, hipStream_t st) {
+  forget_sky(c);  // (`whole` may be a slot's frame: the caller's pointer)
   kWireForms[form].unpack(c, gathered, whole, st);
   HIP_TRY(c, hipGetLastError());
   return BBR_OK;
@@ -3688,6 +3782,7 @@ int bbr_tone_map(bbr_context *c, int32_t enable, float exposure) {
   if (c->slots[c->last_slot].mode.fused) return fail(c, BBR_ERR_INVALID_ARGUMENT, "tone_map: no fp32 frame with option present_fused");
   float4 *frame = c->slots[c->last_slot].out_used;
   size_t n = c->shard_pixels();
+  forget_sky(c);  // (in place)
   // same stream as the frame's shade kernel: ordered after it
   hipLaunchKernelGGL(k_tone_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->slots[c->last_slot].stream_used, frame, n, enable, exposure);
   HIP_TRY(c, hipGetLastError());

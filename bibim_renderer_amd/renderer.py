@@ -578,6 +578,15 @@ class Renderer:
         self._check(self._L.bbr_static_record_counts(self._ctx, C.byref(fills), C.byref(light)))
         return {"fills": int(fills.value), "light_draws": int(light.value)}
 
+    def read_sky_tiles(self):
+        """option sky_keep, the most recently submitted frame: a uint8 per tile, (tiles_y * tiles_x,) row-major -- 0 not a
+        background tile (or a frame that could not keep), 1 background and filled, 2 background and kept.  Synchronises."""
+        n = C.c_uint32()
+        self._check(self._L.bbr_read_sky_tiles(self._ctx, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), dtype=np.uint8)
+        self._check(self._L.bbr_read_sky_tiles(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size, C.byref(n)))
+        return out
+
     def host_timing(self):
         """host side of the frame loop since host_timing_reset (no GPU call): frames submitted, ns inside the submit calls, ns of
         that spent blocked on a frame slot still in flight, frames in which the host was blocked"""

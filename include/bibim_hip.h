@@ -193,6 +193,13 @@ int bbr_capacity_growths(const bbr_context *ctx, uint32_t *out_count);          
  * of a draw's records was written (one k_record_static launch per draw and frame slot), and how many draws were submitted
  * on the geometry kernel's light path.  Either pointer may be NULL. */
 int bbr_static_record_counts(const bbr_context *ctx, uint64_t *out_fills, uint64_t *out_light_draws);
+/* Option "sky_keep", the most recently submitted frame: one byte per tile, row-major over the tile grid (*out_count tiles;
+ * `out` may be NULL to ask for the count, else `cap` must cover it).  BBR_SKY_TILE_FILLED: a background tile whose pixels
+ * this frame stored; BBR_SKY_TILE_KEPT: a background tile whose pixels the frame found in place and did not store;
+ * BBR_SKY_TILE_NONE: every other tile, and every tile of a frame that could not keep (see the option).  Synchronises; a frame
+ * that is rendered again here after a capacity growth reports the second rendering. */
+enum { BBR_SKY_TILE_NONE = 0, BBR_SKY_TILE_FILLED = 1, BBR_SKY_TILE_KEPT = 2 };
+int bbr_read_sky_tiles(bbr_context *ctx, uint8_t *out, uint32_t cap, uint32_t *out_count);
 /* The host's side of the frame loop since bbr_host_timing_reset, kept without touching the GPU (steady_clock around the
  * submit): frames submitted by bbr_end_frame / bbr_replay_frame, nanoseconds spent inside those calls, and the part of
  * it the host was BLOCKED because the frame slot it wanted to reuse was still on the GPU (and in how many frames).  A
@@ -397,7 +404,22 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            Uploading or freeing a mesh or a material, a change of "mip_levels", bbr_read_records and a
  *                            growth of the record buffer make every draw start over.  0: every frame writes whole records.
  *                            The overlay pass and the shadow-map pass always write whole records.
- *   "ablate" bits            diagnostic builds only (make EXTRA=-DBB_ABLATE): skip parts of the pipeline */
+ *   "sky_keep" 0|1           1 (default): a 32 x 32 (64 x 64) tile that no triangle touches gets the clear colour in every pixel,
+ *                            and the frame goes into the frame slot's own buffer -- so a tile that was background when the
+ *                            slot rendered last, and is background again, already holds those bytes and is not stored
+ *                            again (C3: 61.9 of the 86.4 MB the raster kernel writes per frame).  Same pixels.  The library
+ *                            keeps one word per tile and slot; a tile that turns background is filled once and kept from the
+ *                            slot's next frame on.  Only forward frames of the whole image with one sample per pixel into the
+ *                            library's fp32 frame keep: not "render_pass" 1, "present_fused", "supersample" >= 2,
+ *                            "overlays", a partition or a caller's output buffer.  Every slot starts over (one frame that
+ *                            fills every background tile) after bbr_tone_map, bbr_draw_overlays, bbr_draw_ui, bbr_resize,
+ *                            bbr_set_partition, bbr_set_output_device_ptr, bbr_framebuffer_device_ptr, the bbr_unpack_*
+ *                            calls, any bbr_set_option that waits for the GPU, and a read-back that renders the frame again
+ *                            (visibility, G-buffer, surface, shadow mask).  The pointer of bbr_framebuffer_device_ptr is
+ *                            good for what the call has always promised, the most recently submitted frame: a caller who
+ *                            writes through it later, behind frames the library has rendered since, must set 0.
+ *                            0: every frame stores every background pixel.  bbr_read_sky_tiles says what happened.
+ *   "ablate" bits           diagnostic builds only (make EXTRA=-DBB_ABLATE): skip parts of the pipeline */
 int bbr_set_option(bbr_context *ctx, const char *name, int64_t value);
 /* The stream layout in use (option "stream_layout"; 0 while only one frame is in flight).  *out_decided is always 1 and
  * out_ms[3] all zero: the layout is a plain option, nothing is timed at run time (round 1 did). */

@@ -2,12 +2,17 @@
 from the one the frame slot saw last), through the plain C API: bbr_begin_frame / bbr_draw / bbr_end_frame.  Option
 "static_records" never finds a repeated key in such a sequence: the figure shows what an animated scene pays for the comparison.
 --still: the same loop with the instances left alone (the draws go to the light path).  Each case runs in its own process.
-usage: _gpu_animated_rate.py [--root TREE] [--reps 3] [--still] workload[:fif=3][:name=value ...] ..."""
+--camera: the CAMERA moves instead (implies --still): sixteen views, a quarter of a degree of yaw and an eighth of pitch apart, one
+per frame in turn, so every frame's view differs from the one its slot saw last.  What option "sky_keep" keeps of such a
+sequence is printed as the share of background tiles kept, summed over the last frame of every slot.
+--forget: bbr_framebuffer_device_ptr in front of every frame: every frame slot forgets what option "sky_keep" remembers and no
+tile is ever kept (the call waits for nothing; on a tree without the option it only returns the pointer).
+usage: _gpu_animated_rate.py [--root TREE] [--reps 3] [--still] [--camera] [--forget] workload[:fif=3][:name=value ...] ..."""
 import argparse, os, subprocess, sys
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = r'''
-import sys, time, gc
+import sys, time, gc, dataclasses
 sys.path.insert(0, %(root)r)
 import numpy as np
 from bibim_renderer_amd import configs, textures, Renderer
@@ -35,9 +40,17 @@ for k in range(1 if %(still)r else 8):
     sets.append((np.ascontiguousarray(b).view(np.uint8).reshape(-1), np.ascontiguousarray(g).view(np.uint8).reshape(-1)))
 r.set_frame_uniforms(fb)
 r.set_view_uniforms(vb)
+views = []
+if %(camera)r:
+    for k in range(16):
+        step = min(k, 16 - k)   # there and back
+        views.append(scene.fill_uniforms(dataclasses.replace(cam, yaw=cam.yaw + 0.25 * step, pitch=cam.pitch + 0.125 * step), settings,
+                                         cfg.width, cfg.height)[1])
 n = [0]
 def frame():
     b, g = sets[n[0] %% len(sets)]
+    if views: r.set_view_uniforms(views[n[0] %% len(views)])
+    if %(forget)r and n[0]: r.framebuffer_device_ptr()   # (there is no frame in front of the first)
     n[0] += 1
     r.begin_frame(); r.draw(m_ball, material, b); r.draw(m_plane, material, g); r.end_frame()
 frame(); r.synchronize()
@@ -52,13 +65,23 @@ for rep in range(%(reps)d):
     r.synchronize()
     out.append((time.perf_counter() - t0) / %(frames)d * 1e6)
 counts = r.static_record_counts() if hasattr(r, "static_record_counts") else None
-print("%(tag)-40s us/frame " + " ".join("%%7.1f" %% x for x in out) + "   static records: %%s" %% (counts,), flush=True)
+sky = ""
+if hasattr(r, "read_sky_tiles"):
+    kept = filled = 0
+    for _ in range(%(fif)d):   # (one frame at a time: the report is the last frame's)
+        frame()
+        t = r.read_sky_tiles()
+        kept, filled = kept + int((t == 2).sum()), filled + int((t == 1).sum())
+    sky = "   background tiles kept: %%d of %%d" %% (kept, kept + filled)
+print("%(tag)-40s us/frame " + " ".join("%%7.1f" %% x for x in out) + "   static records: %%s" %% (counts,) + sky, flush=True)
 scene.close(); r.close()
 '''
 ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=HERE, help="the tree whose package and library are used (another checkout, for A/B timing)")
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--still", action="store_true")
+ap.add_argument("--camera", action="store_true")
+ap.add_argument("--forget", action="store_true")
 ap.add_argument("cases", nargs="+")
 a = ap.parse_args()
 rc = 0
@@ -73,8 +96,9 @@ for case in a.cases:
         else:
             opts.append((k, int(v)))
     frames = {"c2": 600, "c3": 300, "c5": 80}[workload]
-    tag = ("still " if a.still else "moving ") + case + (" [" + os.path.basename(os.path.abspath(a.root)) + "]" if a.root != HERE else "")
-    code = CHILD % dict(root=os.path.abspath(a.root), workload=workload, opts=opts, frames=frames, fif=fif, reps=a.reps, tag=tag, still=a.still)
+    tag = ("camera " if a.camera else "still " if a.still else "moving ") + ("forget " if a.forget else "") + case + (" [" + os.path.basename(os.path.abspath(a.root)) + "]" if a.root != HERE else "")
+    code = CHILD % dict(root=os.path.abspath(a.root), workload=workload, opts=opts, frames=frames, fif=fif, reps=a.reps, tag=tag, still=a.still or a.camera,
+                        camera=a.camera, forget=a.forget)
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     sys.stdout.write(p.stdout)
     if p.returncode:
