@@ -107,6 +107,8 @@ SIGNATURES = {
     "bbr_read_shadow_face_index": (C.c_int, [_P, C.c_void_p]),
     "bbr_read_shadow_taps": (C.c_int, [_P, C.c_void_p]),
     "bbr_render_shadow_caster": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float]),
+    "bbr_queue_shadow_caster": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float]),
+    "bbr_shadow_queue_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bbr_drop_shadow_caster": (C.c_int, [_P, C.c_int32]),
     "bbr_get_shadow_casters": (C.c_int, [_P, C.c_void_p, C.c_void_p]),
     "bbr_read_shadow_caster_face": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_void_p]),

@@ -4398,4 +4398,46 @@ __global__ __launch_bounds__(256) void k_tbn_colour(const uint32_t *__restrict__
   present[o] = c == 0u ? 0xFF0000FFu : (c == 1u ? 0xFF00FF00u : 0xFFFF0000u);
 }
 
+// A queued shadow pass (bbr_queue_shadow_caster) has rendered its faces in front of its frame, each counting in a block of
+// its own (`face_ctr`, `n_blocks` <= kShadowPassBlocks of them, zero before the pass).  What the synchronous pass does on
+// the host after a wait happens here, one wave behind the last face and in front of the frame's k_geometry: the blocks are
+// folded into the frame's own words and cleared for the next pass.
+//   overflow, bin_need   or / max into the frame's block `frame_ctr` (zero since the slot's last frame retired it, and only
+//                        ever or-ed and max-ed by k_geometry): the frame's k_raster publishes them in the pinned flag words,
+//                        its shading retires them (retire_counters) -- an overflow in the pass is the frame's
+//   n_broad, n_clip_slots   are allocators in the frame's block, so the largest among the faces goes beside them
+//                        (Counters::pass_broad / pass_clip, which travel with the block) and into the pinned words of their own
+// (A frame whose pass overflowed the every-tile list then ignores its own list, k_raster: it is rendered again anyway.)
+constexpr int kShadowPassBlocks = kMaxShadowCasters * kMaxShadowFaces;
+constexpr int kPassRetireThreads = 64;
+static_assert(kShadowPassBlocks <= kPassRetireThreads, "one lane per block");
+__global__ __launch_bounds__(kPassRetireThreads) void k_shadow_pass_retire(Counters *__restrict__ face_ctr, uint32_t n_blocks,
+                                                                          Counters *__restrict__ frame_ctr,
+                                                                          uint32_t *__restrict__ host_flags) {
+  const uint32_t lane = threadIdx.x;
+  uint32_t overflow = 0u, bin_need = 0u, broad = 0u, clip = 0u;
+  if (lane < n_blocks) {
+    const Counters &b = face_ctr[lane];
+    overflow = b.overflow, bin_need = b.bin_need, broad = b.n_broad, clip = b.n_clip_slots;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {  // (butterfly: every lane ends with the wave's value)
+    overflow |= (uint32_t)__shfl_xor((int)overflow, d);
+    bin_need = max(bin_need, (uint32_t)__shfl_xor((int)bin_need, d));
+    broad = max(broad, (uint32_t)__shfl_xor((int)broad, d));
+    clip = max(clip, (uint32_t)__shfl_xor((int)clip, d));
+  }
+  __syncthreads();  // (every block has been read)
+  for (uint32_t i = lane; i < n_blocks * (uint32_t)(sizeof(Counters) / 4); i += kPassRetireThreads)
+    reinterpret_cast<uint32_t *>(face_ctr)[i] = 0u;
+  if (lane == 0) {
+    if (overflow) atomicOr(&frame_ctr->overflow, overflow);
+    if (bin_need) atomicMax(&frame_ctr->bin_need, bin_need);
+    frame_ctr->pass_broad = broad;
+    frame_ctr->pass_clip = clip;
+    host_flags[kFlagPassBroadNeed] = broad;
+    host_flags[kFlagPassClipNeed] = clip;
+  }
+}
+
 }  // namespace bbr

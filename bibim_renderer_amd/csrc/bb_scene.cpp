@@ -300,6 +300,10 @@ int drawFrame(bbr_context *ctx, SceneBase &scene, const FreeLookCamera &cam, con
   frame.Material = material;
   rc = scene.drawScene(frame);
   if (rc != BBR_OK) return rc;
+  for (const SceneBase::QueuedShadowCaster &q : scene.QueuedShadowCasters) {
+    rc = bbr_queue_shadow_caster(ctx, q.Caster, q.Light, (int32_t)q.Faces.size(), q.Faces.data(), q.Bias);
+    if (rc != BBR_OK) return rc;
+  }
   return bbr_end_frame(ctx);
 }
 

@@ -207,7 +207,10 @@ struct Counters {
   uint32_t overflow;  // bit0 bins, bit1 broad list, bit2 clip arena
   uint32_t bin_need;  // largest per-tile reference count seen when a bin overflowed
   uint32_t n_heavy;   // entries of the frame's heavy-tile list (k_geometry appends, k_raster starts those tiles first)
-  uint32_t pad[27];
+  // a frame block only, and only behind a queued shadow pass (k_shadow_pass_retire): the largest n_broad / n_clip_slots among
+  // the pass's faces.  No kernel of the frame touches them; they travel to the host with the block (retire_counters)
+  uint32_t pass_broad, pass_clip;
+  uint32_t pad[25];
 };
 static_assert(sizeof(Counters) == 128, "Counters");
 
@@ -220,9 +223,13 @@ static_assert(sizeof(Counters) == 128, "Counters");
 //   kFlagBroadNeed   k_raster, Counters::n_broad           submit_frame_into, for that growth
 //   kFlagClipNeed    k_raster, Counters::n_clip_slots      submit_frame_into, for that growth
 //   kFlagHeavyTiles  k_raster, Counters::n_heavy           launch_frame: sizes k_raster's heavy rows
+//   kFlagPassBroadNeed, kFlagPassClipNeed   k_shadow_pass_retire (a frame with a queued shadow pass; the host zeroes them for
+//                    every other frame), Counters::pass_broad / pass_clip      submit_frame_into, for that growth
 // The host zeroes them at allocation and clears some when they go stale (FrameSlot::forget_capacities / forget_extent).
-enum HostFlagWord : int { kFlagOverflow = 0, kFlagBinNeed, kFlagItemCount, kFlagBroadNeed, kFlagClipNeed, kFlagHeavyTiles };
-constexpr int kHostFlagWords = 8;  // allocated (the words behind kFlagHeavyTiles are spare)
+enum HostFlagWord : int {
+  kFlagOverflow = 0, kFlagBinNeed, kFlagItemCount, kFlagBroadNeed, kFlagClipNeed, kFlagHeavyTiles, kFlagPassBroadNeed, kFlagPassClipNeed
+};
+constexpr int kHostFlagWords = 8;  // allocated
 
 // k_geometry statistics of one workgroup
 struct BlockStats {

@@ -186,6 +186,23 @@ struct StaticRecords {
   void forget() { draws.clear(); }
 };
 
+// bbr_queue_shadow_caster: what the recorded frame asked for in one caster slot.  It belongs to the recorded frame like its
+// draws: bbr_begin_frame forgets it, every submission of the frame (bbr_end_frame, a replay, a re-render) renders it again.
+struct QueuedCaster {
+  bool on = false;
+  int32_t light = 0, faces = 0;
+  float bias = 0.f;
+  ViewUniformBlock view[kMaxShadowFaces];
+};
+// A queued pass as the frame in a slot carried it: which caster slot, the request, and the stamp the slot got from it (the
+// slot still holds this request while its stamp is this one).  Kept so that the pass can be rendered again from the frame's
+// draws, which stay in the slot's device staging until its next frame (settle_queued_passes).
+struct CarriedPass {
+  int caster = 0;
+  uint32_t stamp = 0;
+  QueuedCaster q;
+};
+
 // Everything one frame in flight owns.  What is in neither group survives an option change and a resize.
 struct FrameSlot : TileSized, ExtentSized {
   StaticRecords statics;
@@ -232,6 +249,15 @@ struct FrameSlot : TileSized, ExtentSized {
     bool copy_pending = false;
   } ui;
   bool in_flight = false;
+  // per caster slot, the map generation the frame in this slot reads (ShadowSlot::cur at its submission), -1: none.  While
+  // the frame is on the GPU no queued pass writes that generation (pick_generation).
+  int8_t shadow_gen[kMaxShadowCasters] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  bool had_pass = false;       // the frame in this slot carried a queued shadow pass (its overflow words include the pass's)
+  std::vector<CarriedPass> carried;  // ... these; and where the frame's draws are in d_staging, for rendering them again
+  size_t draws_offset = 0;
+  uint32_t n_draws = 0;
+  FirstPrims first_prims = {};
+  uint64_t serial = 0;         // the order of submission among the context's frames
   float4 *out_used = nullptr;  // where the frame in this slot wrote its pixels
   hipStream_t stream_used = nullptr;  // the stream its k_shade ran on
   uint32_t n_prims = 0;
@@ -239,7 +265,8 @@ struct FrameSlot : TileSized, ExtentSized {
   // The flag words describe frames rendered with the old capacities (apply_growth) / the old extent (bbr_resize).  Two sets,
   // kept apart as they were; the heavy-tile count survives both (a list that does not fit its rows is merely not used).
   void forget_capacities() {
-    if (uint32_t *f = h_flags.ptr) f[kFlagOverflow] = f[kFlagBinNeed] = f[kFlagItemCount] = f[kFlagBroadNeed] = f[kFlagClipNeed] = 0u;
+    if (uint32_t *f = h_flags.ptr)
+      f[kFlagOverflow] = f[kFlagBinNeed] = f[kFlagItemCount] = f[kFlagBroadNeed] = f[kFlagClipNeed] = f[kFlagPassBroadNeed] = f[kFlagPassClipNeed] = 0u;
   }
   void forget_extent() {
     if (uint32_t *f = h_flags.ptr) f[kFlagOverflow] = f[kFlagBinNeed] = f[kFlagItemCount] = 0u;
@@ -287,6 +314,14 @@ struct ExtentDumps {
 // One caster slot (bbr_render_shadow_caster): its maps and what the shading kernels get of it.
 struct ShadowSlot {
   DeviceBuffer<float> d_map;      // the maps: F x S x S depths, face f row-major at f * S * S (k_raster's depth store)
+  // Queued passes (bbr_queue_shadow_caster): further GENERATIONS of the maps, d_map being generation 0.  A frame reads the
+  // generation that was current when it was submitted (FrameSlot::shadow_gen); a queued pass writes one no frame on the GPU
+  // reads (pick_generation), which then is the current one.  The synchronous pass writes generation 0: nothing is in flight.
+  static constexpr int kGenerations = 4;  // the frame slots: of n frames in flight, n - 1 can hold a generation against the n-th
+  DeviceBuffer<float> d_more[kGenerations - 1];
+  int cur = 0;                    // the generation args.map points to
+  uint32_t stamp = 0;             // a new value with every request that makes the slot valid (bbr_context::caster_stamp): CarriedPass
+  DeviceBuffer<float> &generation(int g) { return g == 0 ? d_map : d_more[g - 1]; }
   ShadowFacesArgs args = {};      // what every frame's k_shade_shadow (F = 1: its first matrix) or k_shade_shadow_faces gets:
                                   // M_f, the maps, S, F, the caster's index, the bias
   bool valid = false;             // in use: the maps have been rendered since the option was set, and not dropped
@@ -294,8 +329,16 @@ struct ShadowSlot {
 struct ShadowOwned {
   FrameSlot pass;                 // the map pass's own little frame (k_geometry -> k_raster at S x S), like the overlay pass's
   ShadowSlot slot[kMaxShadowCasters];  // slot 0: the caster of bbr_render_shadow_map / bbr_render_shadow_faces
+  QueuedCaster queued[kMaxShadowCasters];
+  // The queued passes of all frames share `pass`, the sink and the counter blocks: ev_pass is recorded behind each (its
+  // k_shadow_pass_retire), the next one waits for it on its stream, and so does the shading of every frame from then on -- a
+  // frame that queues nothing may read maps that the pass of the frame before it, on another stream, is still writing.
+  Event ev_pass;
+  bool pass_queued = false;       // a queued pass has been submitted since the group was made: ev_pass is recorded
+  bool table_stale = false;       // ... and has changed a slot since d_table was written: frames carry the table in their staging
+  struct { uint32_t n_prims = 0, bin_cap = 0, broad_cap = 0, clip_cap = 0; int tile_mode = -1; } pass_sized;  // what `pass` was last sized for
   DeviceBuffer<uint32_t> d_sink;  // S x S words k_raster's background stores go to; nothing reads them (one for all faces)
-  DeviceBuffer<Counters> d_ctr;   // a counter block per face: the faces run back to back and are read after one wait
+  DeviceBuffer<Counters> d_ctr;   // a counter block per face (of every queued slot: kShadowPassBlocks): the faces run back to back and are read after one wait
   // what k_shade_shadow_casters reads: every slot's entry and the light -> slot lookup.  It exists from the first use of a slot
   // other than 0, and is written by the synchronous render / drop calls only, while no frame is in flight.
   DeviceBuffer<ShadowCasterTable> d_table;
@@ -411,6 +454,11 @@ struct bbr_context : ExtentDumps {
   // of either, the material table, the mip chains): a freed and reused address never compares equal to its former self.
   uint64_t resource_epoch = 1;
   uint64_t static_fills = 0, static_light_draws = 0;  // k_record_static launches; draws submitted on the light path
+  // bbr_shadow_queue_counts: queued passes submitted (one per queued slot and submission of its frame), and how often a
+  // frame had to drain the context because of one (an overflowed pass seen in a slot's pinned words).  They outlive `shadow`.
+  uint64_t shadow_queue_passes = 0, shadow_queue_drains = 0;
+  uint32_t caster_stamp = 0;   // ShadowSlot::stamp's source
+  uint64_t frame_serial = 0;   // FrameSlot::serial's source
   uint32_t ablate = 0;
   int n_cus = 256;         // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   int timing = 0;  // 0 off, 1 five events per frame, 2 only the two events around k_shade
@@ -860,7 +908,7 @@ template <int TW, int TH>
 void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const FrameStreams &st, const Event *ev, const FrameParams &fp_in,
                   const Mat4 &pv, const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DrawDesc *d_draws, uint32_t n_draws,
                   const FirstPrims &first_prims, float4 *final_out, uint32_t *d_item_head, const DrawDesc *h_draws,
-                  const std::vector<uint32_t> &fills) {
+                  const std::vector<uint32_t> &fills, const ShadowCasterTable *frame_table) {
   FrameParams fp = fp_in;
   // Where the kernels up to shading write.  With a resolve they render the fine frame and k_resolve (at the end) writes
   // `final_out`; with fused presentation k_raster / k_shade write presented pixels into the slot's RGBA8 image, unless there is a
@@ -955,6 +1003,8 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   stream_edge(sr, ss, s.ev_raster_done);
   // (ev[3], the start of the shading interval, is recorded in front of the MAIN launch below -- behind the tail launch when
   //  both are on one stream: the interval is then the dominant kernel's own, which the kernel trace can be held against)
+  // the maps a shadowed frame reads may come from a queued pass on another frame's stream (ShadowOwned::ev_pass)
+  if (mode.shadow && c->shadow.pass_queued) (void)hipStreamWaitEvent(ss, c->shadow.ev_pass, 0);
   uint2 *gbuf = (fp.deferred && c->dump_gbuffer) ? c->d_gbuffer.ptr : nullptr;
   // Main launch: one item (64 fragments) per wave, four per workgroup, sized from the item count of the frame this slot
   // rendered last (k_shade_items leaves it in pinned host memory) plus 3 %; tail launch: a small persistent grid for
@@ -992,7 +1042,7 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
         constexpr bool DUMP = decltype(dump)::value;
         if (mode.shadow_casters) {
           ShadowCastersArgs sa = {};
-          sa.table = c->shadow.d_table.ptr, sa.lights = d_lights, sa.num_lights = sp.num_lights, sa.radius = mode.shadow_filter;
+          sa.table = frame_table ? frame_table : c->shadow.d_table.ptr, sa.lights = d_lights, sa.num_lights = sp.num_lights, sa.radius = mode.shadow_filter;
           sa.side = c->shadow_map, sa.half = 0.5f * (float)c->shadow_map, sa.dump_slot = c->dump_shadow_slot;
           if (DUMP && c->dump_shadow_mask) sa.mask = c->d_shadow_mask.ptr, sa.face = c->d_shadow_face.ptr, sa.taps = c->d_shadow_taps.ptr;
           launch(k_shade_shadow_casters<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface, sa);
@@ -1075,6 +1125,8 @@ int apply_growth(bbr_context *c, uint32_t overflow, uint32_t bin_need, uint32_t 
     // tile counters may hold residue of references that did not fit
     if (s.d_tile_count.ptr) HIP_TRY(c, zero_fill_sync(s.d_tile_count.ptr, s.d_tile_count.cap * sizeof(uint32_t)));
   }
+  // (a queued shadow pass overflows as part of its frame, and leaves the same residue in the pass slot)
+  if (FrameSlot &p = c->shadow.pass; p.d_tile_count.ptr) HIP_TRY(c, zero_fill_sync(p.d_tile_count.ptr, p.d_tile_count.cap * sizeof(uint32_t)));
   return BBR_OK;
 }
 
@@ -1142,8 +1194,278 @@ void plan_static_records(bbr_context *c, FrameSlot &s, DrawDesc *hd, uint32_t n_
   }
 }
 
-// Queue the recorded frame into slot `slot_index`.  Asynchronous.
+// ---- shadow map passes: what the synchronous call (render_shadow_faces) and a frame's queued pass share ----
+
+// The pass's frame: S x S whatever "supersample" is, the whole map on every rank, the forward order whatever "render_pass" is,
+// the context's capacities as they are now.
+FrameParams shadow_pass_params(const bbr_context *c) {
+  const int32_t S = c->shadow_map;
+  FrameParams fp = make_params(c);
+  fp.width = fp.height = S;
+  fp.half_w = fp.half_h = 0.5f * (float)S;
+  fp.tiles_x = (S + c->tile_w() - 1) / c->tile_w();
+  fp.tiles_y = (S + c->tile_h() - 1) / c->tile_h();
+  fp.rank = 0;
+  fp.world = 1;  // every rank renders the whole map
+  fp.band_tiles = fp.tiles_y;
+  fp.shard_rows = S;
+  fp.deferred = 0;
+  fp.gbuffer_view = -1;
+  return fp;
+}
+
+// One face on `st`, through the pass slot: the frame's own k_geometry and k_raster, counting in `ctr` (zero before), the depth
+// of every texel into `map`.
+void launch_shadow_face(bbr_context *c, hipStream_t st, const FrameParams &fp, const DrawDesc *d_draws, uint32_t n_draws,
+                        const FirstPrims &first_prims, uint32_t n_prims, const Mat4 &pv, const Mat4 &view, Counters *ctr, float *map) {
+  ShadowOwned &sh = c->shadow;
+  FrameSlot &s = sh.pass;
+  auto launch = [&](auto tw, auto th) {
+    constexpr int TW = decltype(tw)::value, TH = decltype(th)::value;
+    if (n_prims)
+      hipLaunchKernelGGL((k_geometry<TW, TH>), dim3((n_prims + 255) / 256), dim3(256), 0, st, d_draws, n_draws, n_prims, first_prims,
+                         s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv, view, fp, s.d_clip.ptr, s.d_broad.ptr,
+                         c->d_materials.ptr, s.d_block_stats.ptr, (uint32_t *)nullptr);
+    hipLaunchKernelGGL((k_raster<TW, TH>), dim3(fp.tiles_x, fp.tiles_y), dim3(kTileThreads), 0, st, s.d_tile_count.ptr, ctr,
+                       s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, (float4 *)nullptr, fp, s.d_tris.ptr, s.d_clip.ptr,
+                       s.d_bins.ptr, (uint32_t *)nullptr, (float *)nullptr, (const float4 *)nullptr, map,
+                       (uint32_t *)nullptr, sh.d_sink.ptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                       (const Light *)nullptr, 0, (CookedLight *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u);
+  };
+  if (c->tile_mode == 0) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{});
+  else launch(std::integral_constant<int, 32>{}, std::integral_constant<int, 32>{});
+}
+
+// What the shading kernels get of caster slot `cs` once its maps are (being) rendered from `view`: into generation `cs.cur`
+void set_caster_args(const bbr_context *c, ShadowSlot &cs, int32_t light_index, int32_t n_faces, const ViewUniformBlock *view, float bias) {
+  const int32_t S = c->shadow_map;
+  for (int f = 0; f < kMaxShadowFaces; ++f) cs.args.m[f] = f < n_faces ? proj_view(view[f]) : Mat4{};
+  cs.args.map = cs.generation(cs.cur).ptr;
+  cs.args.mask = nullptr;
+  cs.args.face = nullptr;
+  cs.args.side = S;
+  cs.args.light = light_index;
+  cs.args.faces = n_faces;
+  cs.args.half = 0.5f * (float)S;
+  cs.args.bias = bias;
+}
+
+// The table k_shade_shadow_casters reads, from the slots in use
+void fill_caster_table(const ShadowOwned &sh, ShadowCasterTable &t) {
+  std::memset(&t, 0, sizeof t);
+  for (int32_t &s : t.slot_of_light) s = -1;
+  for (int s = 0; s < kMaxShadowCasters; ++s) {
+    if (!sh.slot[s].valid) continue;
+    const ShadowFacesArgs &a = sh.slot[s].args;
+    ShadowCasterEntry &e = t.slot[s];
+    for (int f = 0; f < kMaxShadowFaces; ++f) e.m[f] = a.m[f];
+    e.map = a.map, e.light = a.light, e.faces = a.faces, e.bias = a.bias;
+    t.slot_of_light[a.light] = s;  // (0 .. 99, and no other slot in use names it: render_shadow_faces, bbr_queue_shadow_caster)
+  }
+}
+
+// ---- the queued pass (bbr_queue_shadow_caster) ----
+// The rule: a frame that queued casters is the frame with bbr_render_shadow_caster called for each of them, in slot order,
+// directly in front of its bbr_end_frame.  So the queued slots become the context's casters when the frame is submitted
+// (apply_queued_casters, in front of frame_mode: the frame is shaded with them), and their maps are rendered from the frame's own
+// draws on the frame's own stream in front of its k_geometry (launch_queued_passes).  Nothing waits and nothing is drained.
+
+// The generation of slot `caster`'s maps a pass in front of the frame going into `into` may write: one that no frame on the
+// GPU reads.  The frames in flight beside `into` are at most kMaxSlots - 1 and read one generation each, so there is one
+// and nothing ever waits; finding none is an error.
+static_assert(ShadowSlot::kGenerations >= bbr_context::kMaxSlots, "a free generation for every frame in flight");
+int pick_generation(bbr_context *c, int caster, const FrameSlot &into, int *out) {
+  auto read_on_gpu = [&](int g) {
+    for (const FrameSlot &o : c->slots)
+      if (&o != &into && o.in_flight && o.shadow_gen[caster] == g && !o.idle()) return true;
+    return false;
+  };
+  for (int g = 0; g < ShadowSlot::kGenerations; ++g)
+    if (!read_on_gpu(g)) return *out = g, BBR_OK;
+  return fail(c, BBR_ERR_HIP, "queued shadow pass: every generation of the slot's maps is read by a frame in flight");
+}
+
+// The recorded frame's queued casters become the context's, each on a generation of its own.  Returns through `n_queued` how many.
+int apply_queued_casters(bbr_context *c, const FrameSlot &into, int *n_queued) {
+  ShadowOwned &sh = c->shadow;
+  *n_queued = 0;
+  if (c->shadow_map <= 0) return BBR_OK;
+  const size_t texels = (size_t)c->shadow_map * (size_t)c->shadow_map;
+  for (int k = 0; k < kMaxShadowCasters; ++k) {
+    QueuedCaster &q = sh.queued[k];
+    if (!q.on) continue;
+    // (a synchronous call since has put the light into another slot: the call in front of bbr_end_frame would be refused)
+    for (int o = 0; o < kMaxShadowCasters; ++o)
+      if (o != k && sh.slot[o].valid && sh.slot[o].args.light == q.light) q.on = false;
+    if (!q.on) continue;
+    ShadowSlot &cs = sh.slot[k];
+    int g = 0;
+    if (int rc = pick_generation(c, k, into, &g)) return rc;
+    HIP_TRY(c, cs.generation(g).ensure(texels * (size_t)q.faces));  // (growing frees a buffer nothing on the GPU reads)
+    cs.cur = g;
+    set_caster_args(c, cs, q.light, q.faces, q.view, q.bias);
+    cs.stamp = ++c->caster_stamp;
+    cs.valid = true;
+    sh.table_stale = true;
+    ++*n_queued;
+  }
+  return BBR_OK;
+}
+
+// The queued casters' faces on `st` -- the frame's geometry stream, behind its staging transfer, whose descriptors and instance
+// blocks the pass reads (`d_draws`: a static draw's light path stores less of a record the pass never reads, and the same
+// triangle) -- then k_shadow_pass_retire, which folds the faces' counters into the frame's (`frame_ctr`, `into.h_flags`).
+// The pass slot is the context's one (ShadowOwned::pass), shared by all frames behind ev_pass.  It never holds records a later
+// frame relies on, unlike the frame slot's own buffers under "static_records".
+int launch_queued_passes(bbr_context *c, FrameSlot &into, hipStream_t st, const DrawDesc *d_draws, uint32_t n_draws,
+                         const FirstPrims &first_prims, Counters *frame_ctr) {
+  ShadowOwned &sh = c->shadow;
+  FrameSlot &p = sh.pass;
+  const FrameParams fp = shadow_pass_params(c);
+  const size_t texels = (size_t)c->shadow_map * (size_t)c->shadow_map;
+  auto &z = sh.pass_sized;
+  const bool fits = p.d_tile_count.ptr && p.d_bins.ptr && p.d_broad.ptr && p.d_clip.ptr && sh.d_sink.cap >= texels &&
+                    sh.d_ctr.cap >= (size_t)kShadowPassBlocks && c->n_prims <= z.n_prims && c->bin_cap == z.bin_cap &&
+                    c->broad_cap == z.broad_cap && c->clip_cap == z.clip_cap && c->tile_mode == z.tile_mode;
+  if (!fits) {
+    // the pass slot may be reallocated: the pass on the GPU leaves it first (the host waits for that one event)
+    if (sh.pass_queued) HIP_TRY(c, hipEventSynchronize(sh.ev_pass));
+    HIP_TRY(c, sh.d_sink.ensure(texels));
+    HIP_TRY(c, sh.d_ctr.ensure(kShadowPassBlocks, true));
+    if (int rc = ensure_pass_buffers(c, p, c->n_prims, (size_t)fp.tiles_x * fp.tiles_y)) return rc;
+    z.n_prims = std::max(z.n_prims, c->n_prims), z.bin_cap = c->bin_cap, z.broad_cap = c->broad_cap, z.clip_cap = c->clip_cap;
+    z.tile_mode = c->tile_mode;
+  }
+  HIP_TRY(c, sh.ev_pass.ensure(hipEventDisableTiming));
+  if (sh.pass_queued) HIP_TRY(c, hipStreamWaitEvent(st, sh.ev_pass, 0));  // behind the pass of the frame before
+  uint32_t block = 0;
+  for (int k = 0; k < kMaxShadowCasters; ++k) {
+    const QueuedCaster &q = sh.queued[k];
+    if (!q.on) continue;
+    ShadowSlot &cs = sh.slot[k];
+    for (int f = 0; f < q.faces; ++f)
+      launch_shadow_face(c, st, fp, d_draws, n_draws, first_prims, c->n_prims, cs.args.m[f], q.view[f].view, sh.d_ctr.ptr + block++,
+                         cs.generation(cs.cur).ptr + (size_t)f * texels);
+    ++c->shadow_queue_passes;
+  }
+  hipLaunchKernelGGL(k_shadow_pass_retire, dim3(1), dim3(kPassRetireThreads), 0, st, sh.d_ctr.ptr, block, frame_ctr, into.h_flags.ptr);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(sh.ev_pass, st));
+  sh.pass_queued = true;
+  return BBR_OK;
+}
+
+// The faces of one caster, synchronously, through the pass slot on the context's shading stream: `n_faces` maps of S x S at `map`
+// from the `n_prims` primitives of `d_draws`.  Nothing of the context is on the GPU.  One wait, one read of the faces' counter
+// blocks, one clear; a capacity that overflowed in any face is grown and ALL faces are rendered again.  Shared by the
+// synchronous call (render_shadow_faces) and by the repair of a queued pass that overflowed (settle_queued_passes).
+int render_faces_sync(bbr_context *c, const std::string &who, float *map, int32_t n_faces, const Mat4 *pv, const ViewUniformBlock *lv,
+                      const DrawDesc *d_draws, uint32_t n_draws, const FirstPrims &first_prims, uint32_t n_prims) {
+  ShadowOwned &sh = c->shadow;
+  FrameSlot &s = sh.pass;
+  const size_t texels = (size_t)c->shadow_map * (size_t)c->shadow_map;
+  HIP_TRY(c, sh.d_sink.ensure(texels));
+  HIP_TRY(c, sh.d_ctr.ensure(kMaxShadowFaces, true));
+  for (int attempt = 0; attempt < 8; ++attempt) {
+    const FrameParams fp = shadow_pass_params(c);  // (the capacities; again after a growth)
+    int rc = ensure_pass_buffers(c, s, n_prims, (size_t)fp.tiles_x * fp.tiles_y);
+    if (rc) return rc;
+    s.ctr_index = bbr_context::kMaxSlots;  // (not a frame slot's; the pass counts in sh.d_ctr)
+    hipStream_t st = c->shade_stream();
+    for (int f = 0; f < n_faces; ++f)
+      launch_shadow_face(c, st, fp, d_draws, n_draws, first_prims, n_prims, pv[f], lv[f].view, sh.d_ctr.ptr + f, map + (size_t)f * texels);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    Counters h[kMaxShadowFaces] = {};
+    HIP_TRY(c, hipMemcpy(h, sh.d_ctr.ptr, sizeof(Counters) * (size_t)n_faces, hipMemcpyDeviceToHost));
+    HIP_TRY(c, zero_fill_sync(sh.d_ctr.ptr, sizeof(Counters) * (size_t)n_faces));  // (the pass is synchronous: cleared here, not by a kernel)
+    Counters need = {};
+    for (int f = 0; f < n_faces; ++f) {
+      need.overflow |= h[f].overflow;
+      need.bin_need = std::max(need.bin_need, h[f].bin_need);
+      need.n_broad = std::max(need.n_broad, h[f].n_broad);
+      need.n_clip_slots = std::max(need.n_clip_slots, h[f].n_clip_slots);
+    }
+    if (!need.overflow) return BBR_OK;
+    // a triangle did not fit: a map is incomplete.  Grow and render all of them again.
+    rc = apply_growth(c, need.overflow, need.bin_need, need.n_broad, need.n_clip_slots);
+    if (rc) return rc;
+    if (s.d_tile_count.ptr) HIP_TRY(c, zero_fill_sync(s.d_tile_count.ptr, s.d_tile_count.cap * sizeof(uint32_t)));
+  }
+  return fail(c, BBR_ERR_CAPACITY, who + ": capacity still exceeded after 8 growth steps");
+}
+
+// A queued pass that overflowed is the frame's overflow (k_shadow_pass_retire), and the frame's repair -- growing, rendering the
+// frame again -- reaches the pass only while that frame is still the recorded one.  This settles the rest.  The context is
+// drained.  If the frame in any slot carried a pass and reported an overflow in its pinned words, the capacities grow by what
+// those frames asked for, and every pass carried by a frame submitted since the first of them is rendered again, synchronously,
+// oldest first, from that frame's own draws -- they are still in its slot's device staging, which only the slot's next frame
+// overwrites, and a slot's words are looked at before that (submit_frame_into) -- into the generation the caster slot has now,
+// unless a later request has replaced the slot's (CarriedPass::stamp).  The passes BEHIND the overflowed one are included because
+// they ran on the pass slot's residue.  The frames shaded with the incomplete maps in between keep their pixels, as frames do
+// that were queued behind an overflowed frame; `repaired` says that the last frame is among them.
+int settle_queued_passes(bbr_context *c, bool *repaired) {
+  *repaired = false;
+  uint64_t first = ~0ull;
+  uint32_t overflow = 0, bin_need = 0, broad_need = 0, clip_need = 0;
+  for (const FrameSlot &o : c->slots) {
+    const uint32_t *f = o.h_flags.ptr;
+    if (!o.had_pass || !f || !f[kFlagOverflow]) continue;
+    first = std::min(first, o.serial);
+    overflow |= f[kFlagOverflow];
+    bin_need = std::max(bin_need, f[kFlagBinNeed]);
+    broad_need = std::max({broad_need, f[kFlagBroadNeed], f[kFlagPassBroadNeed]});
+    clip_need = std::max({clip_need, f[kFlagClipNeed], f[kFlagPassClipNeed]});
+  }
+  if (!overflow || c->shadow_map <= 0) return BBR_OK;
+  int rc = apply_growth(c, overflow, bin_need, broad_need, clip_need);  // (clears every slot's words)
+  if (rc) return rc;
+  *repaired = true;
+  FrameSlot *order[bbr_context::kMaxSlots];
+  int n = 0;
+  for (FrameSlot &o : c->slots)
+    if (o.had_pass && o.serial >= first) order[n++] = &o;
+  std::sort(order, order + n, [](const FrameSlot *a, const FrameSlot *b) { return a->serial < b->serial; });
+  for (int i = 0; i < n; ++i) {
+    FrameSlot &o = *order[i];
+    for (const CarriedPass &cp : o.carried) {
+      ShadowSlot &cs = c->shadow.slot[cp.caster];
+      if (!cs.valid || cs.stamp != cp.stamp || !o.d_staging.ptr) continue;  // (replaced or dropped since)
+      rc = render_faces_sync(c, "queued shadow pass", cs.generation(cs.cur).ptr, cp.q.faces, cs.args.m, cp.q.view,
+                             reinterpret_cast<const DrawDesc *>(o.d_staging.ptr + o.draws_offset), o.n_draws, o.first_prims, o.n_prims);
+      if (rc) return rc;
+    }
+  }
+  return BBR_OK;
+}
+
+int submit_frame_body(bbr_context *c, int slot_index);
+
+// Queue the recorded frame into slot `slot_index`.  Asynchronous.  A submission that fails leaves the caster slots, and the
+// recorded frame's queued entries, as they were: the queued casters become the context's in front of steps that can fail
+// (apply_queued_casters), and a caster whose maps were never rendered must not stay in use.
 int submit_frame_into(bbr_context *c, int slot_index) {
+  struct Kept {
+    bool valid, queued;
+    int cur;
+    uint32_t stamp;
+    ShadowFacesArgs args;
+  } kept[kMaxShadowCasters];
+  ShadowOwned &sh = c->shadow;
+  const bool table_stale = sh.table_stale;
+  for (int k = 0; k < kMaxShadowCasters; ++k) kept[k] = {sh.slot[k].valid, sh.queued[k].on, sh.slot[k].cur, sh.slot[k].stamp, sh.slot[k].args};
+  const int rc = submit_frame_body(c, slot_index);
+  if (rc != BBR_OK) {
+    for (int k = 0; k < kMaxShadowCasters; ++k) {
+      sh.slot[k].valid = kept[k].valid, sh.slot[k].cur = kept[k].cur, sh.slot[k].stamp = kept[k].stamp, sh.slot[k].args = kept[k].args;
+      sh.queued[k].on = kept[k].queued;
+    }
+    sh.table_stale = table_stale;
+  }
+  return rc;
+}
+
+int submit_frame_body(bbr_context *c, int slot_index) {
   if (!c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, "no recorded frame");
   int rc = upload_material_table(c);
   if (rc) return rc;
@@ -1162,15 +1484,27 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   // pixels (and those of the frames queued since) are incomplete and already handed out; from this frame on the
   // capacities fit.  (Synchronising calls do better: they re-render the overflowed frame, sync_and_fix.)
   if (const uint32_t *f = s.h_flags.ptr; f && f[kFlagOverflow]) {
-    const uint32_t overflow = f[kFlagOverflow], bin_need = f[kFlagBinNeed], broad_need = f[kFlagBroadNeed], clip_need = f[kFlagClipNeed];
     rc = drain(c);
     if (rc) return rc;
-    rc = apply_growth(c, overflow, bin_need, broad_need, clip_need);
+    // the frame carried a queued shadow pass: its overflow bits are in the frame's.  The capacities grow and the pass, and those
+    // behind it, are rendered again before this frame's staging replaces its draws (settle_queued_passes, which clears the words)
+    if (s.had_pass) ++c->shadow_queue_drains;
+    bool repaired = false;
+    rc = settle_queued_passes(c, &repaired);
     if (rc) return rc;
+    if (f[kFlagOverflow]) {  // (a frame without a pass)
+      rc = apply_growth(c, f[kFlagOverflow], f[kFlagBinNeed], f[kFlagBroadNeed], f[kFlagClipNeed]);
+      if (rc) return rc;
+    }
   }
+  // bbr_queue_shadow_caster: the frame's queued casters are the context's from here on, this frame's mode included
+  int n_queued = 0;
+  rc = apply_queued_casters(c, s, &n_queued);
+  if (rc) return rc;
   const FrameMode mode = frame_mode(c);  // decided once for the frame: the buffers, the launches, what the slot remembers
   rc = ensure_slot_buffers(c, s, mode);
   if (rc) return rc;
+  if (!n_queued) s.h_flags.ptr[kFlagPassBroadNeed] = s.h_flags.ptr[kFlagPassClipNeed] = 0u;  // (k_shadow_pass_retire's words)
 
   // staging layout: [lights (100 * 64 B)] [draw descriptors] [instances]
   size_t lights_bytes = sizeof(Light) * kMaxNumLights;
@@ -1179,6 +1513,11 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   // ... [item head: one zero word, 16-byte slot] -- k_raster's tiles count a short frame's items through it (launch_frame)
   const size_t head_offset = (lights_bytes + draws_bytes + inst_bytes + 15) & ~(size_t)15;
   size_t total = head_offset + 16;
+  // ... [the caster table] -- k_shade_shadow_casters' own copy, once a queued pass has changed a slot: the context's table is
+  // written only while nothing is in flight, and the frames in flight differ in the generations they read
+  const bool carries_table = mode.shadow_casters && c->shadow.table_stale;
+  const size_t table_offset = (total + 255) & ~(size_t)255;
+  if (carries_table) total = table_offset + sizeof(ShadowCasterTable);
   if (total > s.h_staging.cap) {
     HIP_TRY(c, s.h_staging.ensure(std::max<size_t>(total * 2, 1 << 16)));
     HIP_TRY(c, s.d_staging.ensure(s.h_staging.cap));
@@ -1198,6 +1537,8 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   if (inst_bytes) std::memcpy(h_staging + lights_bytes + draws_bytes, c->host_instances.data(), inst_bytes);
   std::memset(h_staging + head_offset, 0, 16);
   uint32_t *d_item_head = reinterpret_cast<uint32_t *>(s.d_staging.ptr + head_offset);
+  if (carries_table) fill_caster_table(c->shadow, *reinterpret_cast<ShadowCasterTable *>(h_staging + table_offset));
+  const ShadowCasterTable *d_table = carries_table ? reinterpret_cast<const ShadowCasterTable *>(s.d_staging.ptr + table_offset) : nullptr;
 
   const int n_lights = std::min(std::max(c->frame_u.num_lights, 0), kMaxNumLights);
   const FrameStreams st = c->frame_streams(slot_index);
@@ -1226,10 +1567,23 @@ int submit_frame_into(bbr_context *c, int slot_index) {
   float4 *out = !mode.frame32() ? nullptr : (c->ext_out ? reinterpret_cast<float4 *>(c->ext_out) : s.d_frame.ptr);
 
   HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, h_staging, total, hipMemcpyHostToDevice, st.geom));
-  if (c->tile_mode == 0) launch_frame<64, 64>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head, h_draws, fills);
-  else launch_frame<32, 32>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head, h_draws, fills);
+  if (n_queued) {
+    rc = launch_queued_passes(c, s, st.geom, d_draws, n_live_draws, first_prims, c->d_counters.ptr + s.ctr_index);
+    if (rc) return rc;
+  }
+  if (c->tile_mode == 0) launch_frame<64, 64>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head, h_draws, fills, d_table);
+  else launch_frame<32, 32>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head, h_draws, fills, d_table);
   HIP_TRY(c, hipGetLastError());
   s.in_flight = true;
+  for (int k = 0; k < kMaxShadowCasters; ++k) s.shadow_gen[k] = (mode.shadow && c->shadow.slot[k].valid) ? (int8_t)c->shadow.slot[k].cur : (int8_t)-1;
+  s.had_pass = n_queued != 0;
+  s.carried.clear();
+  for (int k = 0; n_queued && k < kMaxShadowCasters; ++k)
+    if (c->shadow.queued[k].on) s.carried.push_back({k, c->shadow.slot[k].stamp, c->shadow.queued[k]});
+  s.draws_offset = lights_bytes;
+  s.n_draws = n_live_draws;
+  s.first_prims = first_prims;
+  s.serial = ++c->frame_serial;
   s.mode = mode;
   s.present.active = mode.fused;  // fused presentation: the frame IS the presented image
   s.present.out = mode.fused ? s.d_present.ptr : nullptr;
@@ -1342,12 +1696,25 @@ int sync_and_fix(bbr_context *c, Counters *out_counters) {
   for (int attempt = 0; attempt < 8; ++attempt) {
     int rc = drain(c);
     if (rc) return rc;
+    // queued shadow passes that overflowed, in whichever frame: grown and rendered again; the last frame was shaded with their
+    // incomplete maps (or is itself one of those frames) and is rendered again, too -- its counters are read after that
+    bool repaired = false;
+    rc = settle_queued_passes(c, &repaired);
+    if (rc) return rc;
+    if (repaired) {
+      if (out_counters) *out_counters = Counters{};
+      if (!c->have_frame || c->last_slot < 0) return BBR_OK;
+      rc = resubmit_last_frame(c);
+      if (rc) return rc;
+      continue;
+    }
     Counters h = {};
     if (c->have_frame && c->last_slot >= 0 && c->d_counters.ptr)
       HIP_TRY(c, hipMemcpy(&h, c->d_counters_done.ptr + c->slots[c->last_slot].ctr_index, sizeof h, hipMemcpyDeviceToHost));
     if (out_counters) *out_counters = h;
     if (!h.overflow) return BBR_OK;
-    rc = apply_growth(c, h.overflow, h.bin_need, h.n_broad, h.n_clip_slots);
+    // (a queued shadow pass overflows as part of its frame: k_shadow_pass_retire; the frame is rendered again with its pass)
+    rc = apply_growth(c, h.overflow, h.bin_need, std::max(h.n_broad, h.pass_broad), std::max(h.n_clip_slots, h.pass_clip));
     if (rc) return rc;
     rc = resubmit_last_frame(c);
     if (rc) return rc;
@@ -1704,17 +2071,9 @@ static int upload_caster_table(bbr_context *c) {
   HIP_TRY(c, sh.d_table.ensure(1));
   std::vector<ShadowCasterTable> host(1);  // (3.6 KB)
   ShadowCasterTable &t = host[0];
-  std::memset(&t, 0, sizeof t);
-  for (int32_t &s : t.slot_of_light) s = -1;
-  for (int s = 0; s < kMaxShadowCasters; ++s) {
-    if (!sh.slot[s].valid) continue;
-    const ShadowFacesArgs &a = sh.slot[s].args;
-    ShadowCasterEntry &e = t.slot[s];
-    for (int f = 0; f < kMaxShadowFaces; ++f) e.m[f] = a.m[f];
-    e.map = a.map, e.light = a.light, e.faces = a.faces, e.bias = a.bias;
-    t.slot_of_light[a.light] = s;  // (0 .. 99, and no other slot in use names it: render_shadow_faces)
-  }
+  fill_caster_table(sh, t);
   HIP_TRY(c, upload_sync(sh.d_table.ptr, &t, sizeof t));
+  sh.table_stale = false;  // (frames read this table again, not a copy of their own)
   return BBR_OK;
 }
 
@@ -1745,6 +2104,9 @@ static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t c
   ShadowOwned &sh = c->shadow;
   ShadowSlot &cs = sh.slot[caster];
   FrameSlot &s = sh.pass;
+  // (outside a frame the recorded frame's queued pass for this slot is replaced too: a replay shows this call's maps.  Inside
+  //  one it is not: the queued pass stands in front of bbr_end_frame, behind this call)
+  if (!c->in_frame) sh.queued[caster].on = false;
   if (cs.valid) {  // (the slot's maps are about to be overwritten: until they are whole again no frame may use them)
     cs.valid = false;
     rc = upload_caster_table(c);
@@ -1770,73 +2132,16 @@ static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t c
   Mat4 pv[kMaxShadowFaces];  // gl_Position = (L.proj * L.view) * posWorld: the forward order, whatever "render_pass" is
   for (int f = 0; f < n_faces; ++f) pv[f] = proj_view(lv[f]);
 
-  for (int attempt = 0; attempt < 8; ++attempt) {
-    FrameParams fp = make_params(c);  // (the capacities; again after a growth)
-    fp.width = fp.height = S;
-    fp.half_w = fp.half_h = 0.5f * (float)S;
-    fp.tiles_x = (S + c->tile_w() - 1) / c->tile_w();
-    fp.tiles_y = (S + c->tile_h() - 1) / c->tile_h();
-    fp.rank = 0;
-    fp.world = 1;  // every rank renders the whole map
-    fp.band_tiles = fp.tiles_y;
-    fp.shard_rows = S;
-    fp.deferred = 0;
-    fp.gbuffer_view = -1;
-    rc = ensure_pass_buffers(c, s, n_prims, (size_t)fp.tiles_x * fp.tiles_y);
-    if (rc) return rc;
-    s.ctr_index = bbr_context::kMaxSlots;  // (not a frame slot's; the pass counts in sh.d_ctr)
-    hipStream_t st = c->shade_stream();
-    auto launch = [&](auto tw, auto th, int f) {
-      constexpr int TW = decltype(tw)::value, TH = decltype(th)::value;
-      Counters *ctr = sh.d_ctr.ptr + f;
-      if (n_prims)
-        hipLaunchKernelGGL((k_geometry<TW, TH>), dim3((n_prims + 255) / 256), dim3(256), 0, st, d_draws, n_draws, n_prims, first_prims,
-                           s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv[f], lv[f].view, fp, s.d_clip.ptr, s.d_broad.ptr,
-                           c->d_materials.ptr, s.d_block_stats.ptr, (uint32_t *)nullptr);
-      hipLaunchKernelGGL((k_raster<TW, TH>), dim3(fp.tiles_x, fp.tiles_y), dim3(kTileThreads), 0, st, s.d_tile_count.ptr, ctr,
-                         s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, (float4 *)nullptr, fp, s.d_tris.ptr, s.d_clip.ptr,
-                         s.d_bins.ptr, (uint32_t *)nullptr, (float *)nullptr, (const float4 *)nullptr, cs.d_map.ptr + (size_t)f * texels,
-                         (uint32_t *)nullptr, sh.d_sink.ptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                         (const Light *)nullptr, 0, (CookedLight *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u);
-    };
-    for (int f = 0; f < n_faces; ++f) {
-      if (c->tile_mode == 0) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{}, f);
-      else launch(std::integral_constant<int, 32>{}, std::integral_constant<int, 32>{}, f);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(st));
-    Counters h[kMaxShadowFaces] = {};
-    HIP_TRY(c, hipMemcpy(h, sh.d_ctr.ptr, sizeof(Counters) * (size_t)n_faces, hipMemcpyDeviceToHost));
-    HIP_TRY(c, zero_fill_sync(sh.d_ctr.ptr, sizeof(Counters) * (size_t)n_faces));  // (the pass is synchronous: cleared here, not by a kernel)
-    Counters need = {};
-    for (int f = 0; f < n_faces; ++f) {
-      need.overflow |= h[f].overflow;
-      need.bin_need = std::max(need.bin_need, h[f].bin_need);
-      need.n_broad = std::max(need.n_broad, h[f].n_broad);
-      need.n_clip_slots = std::max(need.n_clip_slots, h[f].n_clip_slots);
-    }
-    if (!need.overflow) {
-      for (int f = 0; f < n_faces; ++f) cs.args.m[f] = pv[f];
-      for (int f = n_faces; f < kMaxShadowFaces; ++f) cs.args.m[f] = Mat4{};
-      cs.args.map = cs.d_map.ptr;
-      cs.args.mask = nullptr;
-      cs.args.face = nullptr;
-      cs.args.side = S;
-      cs.args.light = light_index;
-      cs.args.faces = n_faces;
-      cs.args.half = 0.5f * (float)S;
-      cs.args.bias = bias;
-      cs.valid = true;
-      rc = upload_caster_table(c);
-      if (rc) cs.valid = false;  // (the table still says so)
-      return rc;
-    }
-    // a triangle did not fit: a map is incomplete.  Grow and render all of them again.
-    rc = apply_growth(c, need.overflow, need.bin_need, need.n_broad, need.n_clip_slots);
-    if (rc) return rc;
-    if (s.d_tile_count.ptr) HIP_TRY(c, zero_fill_sync(s.d_tile_count.ptr, s.d_tile_count.cap * sizeof(uint32_t)));
-  }
-  return fail(c, BBR_ERR_CAPACITY, who + ": capacity still exceeded after 8 growth steps");
+  rc = render_faces_sync(c, who, cs.d_map.ptr, n_faces, pv, lv, d_draws, n_draws, first_prims, n_prims);
+  if (rc) return rc;
+  for (DeviceBuffer<float> &g : cs.d_more) g.release();  // (nothing is in flight: the generations of earlier queued passes go)
+  cs.cur = 0;  // (the synchronous pass writes generation 0)
+  set_caster_args(c, cs, light_index, n_faces, lv, bias);
+  cs.stamp = ++c->caster_stamp;
+  cs.valid = true;
+  rc = upload_caster_table(c);
+  if (rc) cs.valid = false;  // (the table still says so)
+  return rc;
 }
 
 extern "C" int bbr_render_shadow_map(bbr_context *c, int32_t light_index, const void *light_view_block, float bias) {
@@ -1852,6 +2157,42 @@ extern "C" int bbr_render_shadow_caster(bbr_context *c, int32_t caster, int32_t 
   return render_shadow_faces(c, "render_shadow_caster", caster, light_index, n_faces, light_view_blocks, bias);
 }
 
+// The queued form of bbr_render_shadow_caster: judged like it, recorded with the frame, rendered when the frame is submitted
+// (apply_queued_casters, launch_queued_passes).  Copies the view blocks; launches nothing, waits for nothing.
+extern "C" int bbr_queue_shadow_caster(bbr_context *c, int32_t caster, int32_t light_index, int32_t n_faces, const void *light_view_blocks,
+                                       float bias) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  const std::string who = "queue_shadow_caster";
+  if (c->shadow_map <= 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": option shadow_map is 0");
+  if (caster < 0 || caster >= kMaxShadowCasters) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": caster outside 0 .. 7");
+  if (n_faces < 1 || n_faces > kMaxShadowFaces) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": n_faces outside 1 .. 6");
+  if (light_index < 0 || light_index >= kMaxNumLights) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": light_index outside 0 .. 99");
+  if (!light_view_blocks) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": NULL view block");
+  if (bias != bias) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": bias is NaN");
+  ShadowOwned &sh = c->shadow;
+  for (int s = 0; s < kMaxShadowCasters; ++s)
+    if (s != caster && ((sh.slot[s].valid && sh.slot[s].args.light == light_index) || (sh.queued[s].on && sh.queued[s].light == light_index)))
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": another caster slot, in use or queued in this frame, holds this light_index (one slot per light)");
+  if (!c->in_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, who + ": outside begin_frame/end_frame");
+  for (const RecordedDraw &rd : c->draws)
+    if (!c->meshes[rd.mesh].alive || !c->materials[rd.material].alive)
+      return fail(c, BBR_ERR_BAD_HANDLE, who + ": a recorded draw's mesh or material was freed");
+  QueuedCaster &q = sh.queued[caster];  // (a second call for the slot in one frame: the last one stands)
+  q.on = true;
+  q.light = light_index;
+  q.faces = n_faces;
+  q.bias = bias;
+  std::memcpy(q.view, light_view_blocks, sizeof(ViewUniformBlock) * (size_t)n_faces);
+  return BBR_OK;
+}
+
+extern "C" int bbr_shadow_queue_counts(const bbr_context *c, uint64_t *out_queued_passes, uint64_t *out_drains) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  if (out_queued_passes) *out_queued_passes = c->shadow_queue_passes;
+  if (out_drains) *out_drains = c->shadow_queue_drains;
+  return BBR_OK;
+}
+
 extern "C" int bbr_drop_shadow_caster(bbr_context *c, int32_t caster) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
@@ -1861,6 +2202,7 @@ extern "C" int bbr_drop_shadow_caster(bbr_context *c, int32_t caster) {
   int rc = sync_and_fix(c, nullptr);  // the frames in flight read the table and the maps
   if (rc) return rc;
   cs.valid = false;
+  if (!c->in_frame) c->shadow.queued[caster].on = false;  // (as in render_shadow_faces)
   rc = upload_caster_table(c);
   cs = ShadowSlot();
   return rc;
@@ -1889,7 +2231,10 @@ static int read_shadow_caster_face(bbr_context *c, int32_t caster, int32_t face,
   if (!cs.valid) return fail(c, unused, "read_shadow_map: no map rendered (bbr_render_shadow_map, bbr_render_shadow_caster)");
   if (face < 0 || face >= cs.args.faces) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_shadow_face: face outside 0 .. F - 1");
   const size_t texels = (size_t)c->shadow_map * c->shadow_map;
-  HIP_TRY(c, hipMemcpy(host, cs.d_map.ptr + (size_t)face * texels, texels * sizeof(float), hipMemcpyDeviceToHost));
+  // (a queued pass may still be on the GPU, or have overflowed with its frame: the read-back drains, like the others)
+  if (c->shadow.pass_queued)
+    if (int rc = sync_and_fix(c, nullptr)) return rc;
+  HIP_TRY(c, hipMemcpy(host, c->shadow.slot[caster].args.map + (size_t)face * texels, texels * sizeof(float), hipMemcpyDeviceToHost));
   return BBR_OK;
 }
 
@@ -2255,6 +2600,8 @@ int bbr_free_mesh(bbr_context *c, int32_t mesh) {
     return fail(c, BBR_ERR_BAD_HANDLE, "free_mesh: bad handle");
   int rc = drain(c);
   if (rc) return rc;
+  bool repaired = false;  // (a queued shadow pass that overflowed is rendered again while its frame's draws can still be read)
+  if ((rc = settle_queued_passes(c, &repaired)) != BBR_OK) return rc;
   c->meshes[mesh] = Mesh();
   ++c->resource_epoch;
   c->have_frame = false;
@@ -2313,6 +2660,8 @@ int bbr_free_material(bbr_context *c, int32_t material) {
     return fail(c, BBR_ERR_BAD_HANDLE, "free_material: bad handle");
   int rc = drain(c);
   if (rc) return rc;
+  bool repaired = false;  // (as in bbr_free_mesh)
+  if ((rc = settle_queued_passes(c, &repaired)) != BBR_OK) return rc;
   c->materials[material] = Material();
   c->materials_dirty = true;
   ++c->resource_epoch;
@@ -2366,6 +2715,7 @@ int bbr_begin_frame(bbr_context *c) {
   c->n_prims = 0;
   c->in_frame = true;
   c->have_frame = false;
+  for (QueuedCaster &q : c->shadow.queued) q.on = false;  // (bbr_queue_shadow_caster: they belonged to the frame before)
   return BBR_OK;
 }
 

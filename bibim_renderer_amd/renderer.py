@@ -323,6 +323,19 @@ class Renderer:
         assert b.nbytes % 144 == 0
         self._check(self._L.bbr_render_shadow_caster(self._ctx, int(caster), int(light_index), b.nbytes // 144, _ptr(b), float(bias)))
 
+    def queue_shadow_caster(self, caster, light_index, light_views, bias=0.0):
+        """render_shadow_caster queued with the frame being recorded (between begin_frame and end_frame): the frame is the one
+        with render_shadow_caster called in front of its end_frame, but nothing waits and no frame in flight is drained"""
+        b = np.ascontiguousarray(light_views)
+        assert b.nbytes % 144 == 0
+        self._check(self._L.bbr_queue_shadow_caster(self._ctx, int(caster), int(light_index), b.nbytes // 144, _ptr(b), float(bias)))
+
+    def shadow_queue_counts(self):
+        """(queued passes submitted, drains of the context they caused) since the context was created; does not synchronise"""
+        passes, drains = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.bbr_shadow_queue_counts(self._ctx, C.byref(passes), C.byref(drains)))
+        return passes.value, drains.value
+
     def drop_shadow_caster(self, caster):
         """release the slot's maps and mark it not in use"""
         self._check(self._L.bbr_drop_shadow_caster(self._ctx, int(caster)))

@@ -600,7 +600,29 @@ int bbr_read_packed_level(bbr_context *ctx, int32_t material, int32_t level, uin
  *   bbr_read_shadow_caster_face / _mask / _face_index / _taps  what the namesake above does, for one slot (the calls above
  *                         are slot 0): the same re-render -- one re-render dumps one slot --, the same refusals, the same
  *                         fill values; INVALID_ARGUMENT for a slot outside 0 .. 7 or not in use
- * bbr_read_surface and bbr_read_gbuffer keep working while a map is in use: the re-rendered frame is the shadowed one. */
+ * bbr_read_surface and bbr_read_gbuffer keep working while a map is in use: the re-rendered frame is the shadowed one.
+ *
+ * The queued pass (bbr_queue_shadow_caster): for a caster that moves every frame.  Valid between bbr_begin_frame and
+ * bbr_end_frame only (BBR_ERR_NOT_IN_FRAME elsewhere); it judges its arguments as bbr_render_shadow_caster does, with the same
+ * codes, and also refuses a light_index that another slot queued in this frame holds.  It copies the view blocks and returns:
+ * nothing is launched, nothing waits, the frames in flight stay in flight.  A second call for a slot in one frame replaces the first.
+ * The rule: any sequence of calls with bbr_queue_shadow_caster(args) inside a frame gives, bit for bit in every output, what the
+ * same sequence gives with bbr_render_shadow_caster(args) directly in front of that frame's bbr_end_frame, once per queued slot
+ * in slot order.  So the maps show every draw the frame has recorded by bbr_end_frame, wherever in the frame the call stood; the
+ * caster stays the context's for later frames; a later synchronous call or bbr_drop_shadow_caster replaces or drops it; the
+ * read-backs work afterwards (they drain).  The maps are rendered on the frame's own stream in front of its geometry, into a
+ * generation of the slot's maps that no frame on the GPU reads.  A capacity that overflows in the pass overflows the frame and
+ * is found where a frame's overflow is found: by a synchronising call (any of them, also when later frames have been recorded
+ * since), by the next frame that goes into the frame's slot, and by bbr_free_mesh / bbr_free_material.  There the capacities
+ * grow and the pass -- and every queued pass submitted behind it -- is rendered again, synchronously, from its own frame's
+ * draws, unless a later call has replaced the slot's caster; a synchronising call also renders the last frame again.  Frames
+ * shaded in between with the incomplete maps keep their pixels, as frames queued behind an overflowed frame do.
+ * A slot keeps up to one copy of its maps (F x S x S floats) per frame in flight once it has been queued; a synchronous call
+ * for the slot, a drop or a change of "shadow_map" releases the extra ones.
+ * bbr_replay_frame renders the recorded frame's queued passes again.
+ * bbr_shadow_queue_counts: host-side counters, does NOT synchronise -- queued passes submitted since bbr_create (one per queued
+ * slot and submission of its frame), and how often a frame had to drain the whole context because of one (an overflowed pass
+ * found by a host that only streams frames).  Waiting for one frame slot to become idle is not a drain. */
 #define BBR_MAX_SHADOW_CASTERS 8
 int bbr_render_shadow_map(bbr_context *ctx, int32_t light_index, const void *light_view_block /* 144 B */, float bias);
 int bbr_read_shadow_map(bbr_context *ctx, float *out);
@@ -612,6 +634,9 @@ int bbr_read_shadow_face_index(bbr_context *ctx, uint8_t *out);
 int bbr_read_shadow_taps(bbr_context *ctx, uint8_t *out);
 int bbr_render_shadow_caster(bbr_context *ctx, int32_t caster, int32_t light_index, int32_t n_faces,
                              const void *light_view_blocks /* n_faces x 144 B */, float bias);
+int bbr_queue_shadow_caster(bbr_context *ctx, int32_t caster, int32_t light_index, int32_t n_faces,
+                            const void *light_view_blocks /* n_faces x 144 B */, float bias);
+int bbr_shadow_queue_counts(const bbr_context *ctx, uint64_t *out_queued_passes, uint64_t *out_drains);
 int bbr_drop_shadow_caster(bbr_context *ctx, int32_t caster);
 int bbr_get_shadow_casters(bbr_context *ctx, int32_t *out_light_index /* 8, -1 = not in use */, int32_t *out_faces /* 8 */);
 int bbr_read_shadow_caster_face(bbr_context *ctx, int32_t caster, int32_t face, float *out);

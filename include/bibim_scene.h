@@ -138,6 +138,14 @@ struct SceneBase {
   // (src/main.cpp:89-112).
   RenderPassType SceneRenderPassType = RenderPassType::Forward;
   std::vector<Light> Lights;
+  // Shadow casters drawFrame queues with every frame (bbr_queue_shadow_caster: the maps are rendered with the frame, from
+  // its own draws, and nothing waits).  Empty by default: the scene casts no queued shadow.  updateScene may move them.
+  struct QueuedShadowCaster {
+    int32_t Caster = 0, Light = 0;          // the caster slot 0 .. 7 and the scene light it shadows
+    std::vector<ViewUniformBlock> Faces;    // 1 .. 6 view blocks (cubeShadowViews)
+    float Bias = 0.f;
+  };
+  std::vector<QueuedShadowCaster> QueuedShadowCasters;
   virtual ~SceneBase() = default;
   virtual void updateScene(float dt) = 0;
   virtual int drawScene(const Frame &frame) = 0;  // records bbr_draw calls in API order
