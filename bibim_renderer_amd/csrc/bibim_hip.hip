@@ -69,6 +69,12 @@ struct RecordedDraw {
   int32_t mesh, material;
   uint32_t n_instances, first_instance, first_prim, tris_per_instance;
 };
+// A draw list on the device as k_geometry takes it: the descriptors (fill_draw_descs), how many, and first_prim of draws 1 .. 3
+struct DeviceDraws {
+  const DrawDesc *d = nullptr;
+  uint32_t n = 0;
+  FirstPrims first_prims = {};
+};
 
 // Host -> device copies that kernels on the (non-blocking) context streams read right afterwards: completed on the
 // NULL stream before returning, for the reason given at zero_fill_sync (bb_own.h).
@@ -123,6 +129,9 @@ struct PairRing {
 template <class F> void with_bool(bool b, F &&f) { b ? f(std::true_type{}) : f(std::false_type{}); }
 template <class F> void with_samples(int n, F &&f) {  // n = 2, 3 or 4
   n == 2 ? f(std::integral_constant<int, 2>{}) : n == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 4>{});
+}
+template <class F> void with_tile(int tile_mode, F &&f) {  // option "tile_mode": the side of the square tiles, 64 or 32
+  tile_mode == 0 ? f(std::integral_constant<int, 64>{}) : f(std::integral_constant<int, 32>{});
 }
 
 template <class F> void with_depth_rule(int rule, F &&f) {  // option "depth_resolve": 1, 4 or 8
@@ -186,10 +195,11 @@ struct StaticRecords {
   void forget() { draws.clear(); }
 };
 
-// bbr_queue_shadow_caster: what the recorded frame asked for in one caster slot.  It belongs to the recorded frame like its
-// draws: bbr_begin_frame forgets it, every submission of the frame (bbr_end_frame, a replay, a re-render) renders it again.
-struct QueuedCaster {
-  bool on = false;
+// What a call asks for in one caster slot (check_caster_request): the synchronous calls render it at once.
+// bbr_queue_shadow_caster keeps it as what the recorded frame asked for (ShadowOwned::queued): it belongs to the recorded frame like
+// its draws: bbr_begin_frame forgets it, every submission of the frame (bbr_end_frame, a replay, a re-render) renders it again.
+struct CasterRequest {
+  bool on = false;  // (queued)
   int32_t light = 0, faces = 0;
   float bias = 0.f;
   ViewUniformBlock view[kMaxShadowFaces];
@@ -200,7 +210,7 @@ struct QueuedCaster {
 struct CarriedPass {
   int caster = 0;
   uint32_t stamp = 0;
-  QueuedCaster q;
+  CasterRequest q;
 };
 
 // Everything one frame in flight owns.  What is in neither group survives an option change and a resize.
@@ -312,24 +322,29 @@ struct ExtentDumps {
 
 // Option "shadow_map": everything the feature owns.  Changing the option's value drops the group; at 0 nothing of it exists.
 // One caster slot (bbr_render_shadow_caster): its maps and what the shading kernels get of it.
-struct ShadowSlot {
+// What a slot publishes to the frames: everything a submission may change of it (publish), and what a failed one puts back
+// by assignment (submit_frame_into).  A member that a submission changes belongs here.
+struct CasterPublished {
+  bool valid = false;             // in use: the maps have been rendered since the option was set, and not dropped
+  int cur = 0;                    // the generation args.map points to
+  uint32_t stamp = 0;             // a new value with every request that makes the slot valid (bbr_context::caster_stamp): CarriedPass
+  ShadowFacesArgs args = {};      // what every frame's k_shade_shadow (F = 1: its first matrix) or k_shade_shadow_faces gets:
+                                  // M_f, the maps, S, F, the caster's index, the bias
+};
+struct ShadowSlot : CasterPublished {
+  CasterPublished &published() { return *this; }
   DeviceBuffer<float> d_map;      // the maps: F x S x S depths, face f row-major at f * S * S (k_raster's depth store)
   // Queued passes (bbr_queue_shadow_caster): further GENERATIONS of the maps, d_map being generation 0.  A frame reads the
   // generation that was current when it was submitted (FrameSlot::shadow_gen); a queued pass writes one no frame on the GPU
   // reads (pick_generation), which then is the current one.  The synchronous pass writes generation 0: nothing is in flight.
   static constexpr int kGenerations = 4;  // the frame slots: of n frames in flight, n - 1 can hold a generation against the n-th
   DeviceBuffer<float> d_more[kGenerations - 1];
-  int cur = 0;                    // the generation args.map points to
-  uint32_t stamp = 0;             // a new value with every request that makes the slot valid (bbr_context::caster_stamp): CarriedPass
   DeviceBuffer<float> &generation(int g) { return g == 0 ? d_map : d_more[g - 1]; }
-  ShadowFacesArgs args = {};      // what every frame's k_shade_shadow (F = 1: its first matrix) or k_shade_shadow_faces gets:
-                                  // M_f, the maps, S, F, the caster's index, the bias
-  bool valid = false;             // in use: the maps have been rendered since the option was set, and not dropped
 };
 struct ShadowOwned {
   FrameSlot pass;                 // the map pass's own little frame (k_geometry -> k_raster at S x S), like the overlay pass's
   ShadowSlot slot[kMaxShadowCasters];  // slot 0: the caster of bbr_render_shadow_map / bbr_render_shadow_faces
-  QueuedCaster queued[kMaxShadowCasters];
+  CasterRequest queued[kMaxShadowCasters];
   // The queued passes of all frames share `pass`, the sink and the counter blocks: ev_pass is recorded behind each (its
   // k_shadow_pass_retire), the next one waits for it on its stream, and so does the shading of every frame from then on -- a
   // frame that queues nothing may read maps that the pass of the frame before it, on another stream, is still writing.
@@ -903,12 +918,48 @@ int upload_material_table(bbr_context *c) {
   return BBR_OK;
 }
 
+// ---- the bin pass: k_geometry -> k_raster through a slot's pass buffers (ensure_pass_buffers), counting in `ctr` ----
+// The frame, a shadow face and the overlay pass (OVERLAY) each launch the pair through these two, which hold the only launch
+// of their kernel.
+template <int TW, int TH, bool OVERLAY = false>
+void launch_geometry(const bbr_context *c, FrameSlot &s, hipStream_t st, Counters *ctr, const FrameParams &fp, const DeviceDraws &draws,
+                     uint32_t n_prims, const Mat4 &pv, const Mat4 &view, uint32_t *heavy = nullptr) {
+  if (!n_prims) return;
+  hipLaunchKernelGGL((k_geometry<TW, TH, OVERLAY>), dim3((n_prims + 255) / 256), dim3(256), 0, st, draws.d, draws.n, n_prims, draws.first_prims,
+                     s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv, view, fp, s.d_clip.ptr, s.d_broad.ptr,
+                     c->d_materials.ptr, s.d_block_stats.ptr, heavy);
+}
+
+// What a pass asks of k_raster beside the slot's own buffers: its optional inputs and outputs, null / 0 where the pass names none
+struct RasterIO {
+  int rows = 0;                   // of the grid: heavy_rows + grid_y for a frame, tiles_y for a pass
+  float4 *out = nullptr;          // the background pixels' colour, or (out8) their presented words
+  uint32_t *out8 = nullptr;
+  uint32_t *vis_prim = nullptr;   // bbr_read_visibility's dump
+  float *vis_depth = nullptr;
+  const float4 *background = nullptr;
+  float *depth_io = nullptr;      // a frame or a shadow face stores its depth here; the overlay pass tests against it
+  uint32_t *host_flags = nullptr, *item_groups = nullptr, *item_head = nullptr, *items = nullptr;
+  const Light *lights = nullptr;  // what a short frame's first workgroup cooks
+  int num_lights = 0;
+  CookedLight *cooked = nullptr;
+  const uint32_t *heavy = nullptr;
+  uint32_t *sky_state = nullptr;  // option "sky_keep": the slot's word per tile and the frame's stamp (sky_stamp_for)
+  uint32_t sky_stamp = 0;
+};
+template <int TW, int TH, bool OVERLAY = false>
+void launch_raster(FrameSlot &s, hipStream_t st, Counters *ctr, const FrameParams &fp, const RasterIO &io) {
+  hipLaunchKernelGGL((k_raster<TW, TH, OVERLAY>), dim3(fp.tiles_x, io.rows), dim3(kTileThreads), 0, st, s.d_tile_count.ptr, ctr, s.d_broad.ptr,
+                     s.d_frag_count.ptr, s.d_frags.ptr, io.out, fp, s.d_tris.ptr, s.d_clip.ptr, s.d_bins.ptr, io.vis_prim, io.vis_depth,
+                     io.background, io.depth_io, io.host_flags, io.out8, io.item_groups, io.item_head, io.items, io.lights, io.num_lights,
+                     io.cooked, io.heavy, io.sky_state, io.sky_stamp);
+}
+
 // `ev`: the frame's five timing events, or nullptr; `final_out`: the W x H fp32 frame (nullptr if the mode has none)
 template <int TW, int TH>
 void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const FrameStreams &st, const Event *ev, const FrameParams &fp_in,
-                  const Mat4 &pv, const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DrawDesc *d_draws, uint32_t n_draws,
-                  const FirstPrims &first_prims, float4 *final_out, uint32_t *d_item_head, const DrawDesc *h_draws,
-                  const std::vector<uint32_t> &fills, const ShadowCasterTable *frame_table) {
+                  const Mat4 &pv, const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DeviceDraws &draws, float4 *final_out,
+                  uint32_t *d_item_head, const DrawDesc *h_draws, const std::vector<uint32_t> &fills, const ShadowCasterTable *frame_table) {
   FrameParams fp = fp_in;
   // Where the kernels up to shading write.  With a resolve they render the fine frame and k_resolve (at the end) writes
   // `final_out`; with fused presentation k_raster / k_shade write presented pixels into the slot's RGBA8 image, unless there is a
@@ -943,17 +994,14 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   const hipStream_t sg = st.geom, sr = st.raster, ss = st.shade;
   Counters *ctr = c->d_counters.ptr + s.ctr_index, *ctr_done = c->d_counters_done.ptr + s.ctr_index;
   // option "static_records": the draws whose key has just repeated in this slot (plan_static_records; `h_draws`: the host's
-  // copy of `d_draws`) get the camera-independent part of their records first, once; k_geometry then stores the rest
+  // copy of `draws.d`) get the camera-independent part of their records first, once; k_geometry then stores the rest
   for (const uint32_t d : fills) {
     const uint32_t n = h_draws[d].n_instances * h_draws[d].tris_per_instance;
     hipLaunchKernelGGL(k_record_static, dim3((n + kRecordStaticThreads - 1) / kRecordStaticThreads), dim3(kRecordStaticThreads), 0, sg,
-                       d_draws, d, s.d_attrs.ptr);
+                       draws.d, d, s.d_attrs.ptr);
     ++c->static_fills;
   }
-  if (c->n_prims)
-    hipLaunchKernelGGL((k_geometry<TW, TH>), dim3((c->n_prims + 255) / 256), dim3(256), 0, sg, d_draws, n_draws,
-                       c->n_prims, first_prims, s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv, view, fp, s.d_clip.ptr,
-                       s.d_broad.ptr, c->d_materials.ptr, s.d_block_stats.ptr, s.d_heavy.ptr);
+  launch_geometry<TW, TH>(c, s, sg, ctr, fp, draws, c->n_prims, pv, view, s.d_heavy.ptr);
   if (ev && c->timing == 1) (void)hipEventRecord(ev[1], sg);
   stream_edge(sg, sr, s.ev_geom_done);
   // k_raster writes the background pixels of `out`: if the frame still shading on the other stream writes the
@@ -965,13 +1013,16 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   if (fp.deferred)
     hipLaunchKernelGGL(k_deferred_background, dim3(1), dim3(kBackgroundThreads), 0, sr, sp, d_lights, s.d_background.ptr, tables, fp.gbuffer_view);
   uint32_t *item_head = short_frame ? d_item_head : nullptr;
+  RasterIO io;
+  io.rows = fp.heavy_rows + grid_y;
+  io.out = out, io.out8 = out8, io.vis_prim = vis_prim, io.vis_depth = vis_depth, io.depth_io = depth, io.host_flags = s.h_flags.ptr;
+  io.background = fp.deferred ? s.d_background.ptr : nullptr;
+  io.item_groups = (short_frame || merged) ? nullptr : s.d_item_groups.ptr, io.item_head = item_head, io.items = s.d_items.ptr;
+  io.lights = d_lights, io.num_lights = sp.num_lights, io.cooked = s.d_cooked.ptr, io.heavy = s.d_heavy.ptr;
   // option "sky_keep": the stamp this frame's light tiles keep and mark under, if the frame may (k_raster writes `final_out` then)
-  const uint32_t sky_stamp = sky_stamp_for(c, s, mode, final_out);
-  hipLaunchKernelGGL((k_raster<TW, TH>), dim3(fp.tiles_x, fp.heavy_rows + grid_y), dim3(kTileThreads), 0, sr, s.d_tile_count.ptr, ctr,
-                     s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, out, fp, s.d_tris.ptr, s.d_clip.ptr, s.d_bins.ptr,
-                     vis_prim, vis_depth,
-                     fp.deferred ? s.d_background.ptr : nullptr, depth, s.h_flags.ptr, out8, (short_frame || merged) ? nullptr : s.d_item_groups.ptr, item_head, s.d_items.ptr, d_lights, sp.num_lights,
-                     s.d_cooked.ptr, s.d_heavy.ptr, sky_stamp ? sky_words(s, (size_t)fp.tiles_x * fp.tiles_y) : nullptr, sky_stamp);
+  io.sky_stamp = sky_stamp_for(c, s, mode, final_out);
+  io.sky_state = io.sky_stamp ? sky_words(s, (size_t)fp.tiles_x * fp.tiles_y) : nullptr;
+  launch_raster<TW, TH>(s, sr, ctr, fp, io);
   if (merged)
     with_samples(mode.n, [&](auto n) {
       constexpr int N = decltype(n)::value;
@@ -1103,6 +1154,8 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   }
 }
 
+// what a growth loop reports when its eighth growth was not enough (sync_and_fix, run_pass_sync)
+constexpr char kStillExceeded[] = "capacity still exceeded after 8 growth steps";
 // A capacity overflowed (bit0 bins, bit1 every-tile list, bit2 clip arena): grow it.  Everything must have left the GPU.
 int apply_growth(bbr_context *c, uint32_t overflow, uint32_t bin_need, uint32_t broad_need, uint32_t clip_need) {
   if (getenv("BBR_DEBUG"))
@@ -1154,6 +1207,20 @@ uint32_t fill_draw_descs(const bbr_context *c, DrawDesc *hd, const InstanceBlock
   }
   for (uint32_t q = std::max(k, 1u); q <= (uint32_t)kInlineFirstPrims; ++q) first_prims.v[q - 1] = 0xFFFFFFFFu;
   return k;
+}
+
+// The recorded draws for a synchronous pass: [draw descriptors | instances] in `staging`, as the frame's staging holds them,
+// uploaded at once.  (A frame's own transfer is another job: pinned, asynchronous, one copy with its lights, head and table.)
+int upload_recorded_draws(bbr_context *c, DeviceBuffer<uint8_t> &staging, DeviceDraws &up) {
+  const size_t draws_bytes = (sizeof(DrawDesc) * std::max<size_t>(c->draws.size(), 1) + 127) & ~(size_t)127;
+  const size_t inst_bytes = sizeof(InstanceBlock) * c->host_instances.size();
+  HIP_TRY(c, staging.ensure(draws_bytes + std::max<size_t>(inst_bytes, 1)));
+  std::vector<DrawDesc> draws(std::max<size_t>(c->draws.size(), 1));
+  up.d = reinterpret_cast<const DrawDesc *>(staging.ptr);
+  up.n = fill_draw_descs(c, draws.data(), reinterpret_cast<const InstanceBlock *>(staging.ptr + draws_bytes), up.first_prims);
+  if (up.n) HIP_TRY(c, upload_sync(staging.ptr, draws.data(), up.n * sizeof(DrawDesc)));
+  if (inst_bytes) HIP_TRY(c, upload_sync(staging.ptr + draws_bytes, c->host_instances.data(), inst_bytes));
+  return BBR_OK;
 }
 
 // Option "static_records", a main frame's `n_draws` descriptors `hd` (fill_draw_descs) about to go into slot `s`: which of
@@ -1214,40 +1281,44 @@ FrameParams shadow_pass_params(const bbr_context *c) {
   return fp;
 }
 
-// One face on `st`, through the pass slot: the frame's own k_geometry and k_raster, counting in `ctr` (zero before), the depth
-// of every texel into `map`.
-void launch_shadow_face(bbr_context *c, hipStream_t st, const FrameParams &fp, const DrawDesc *d_draws, uint32_t n_draws,
-                        const FirstPrims &first_prims, uint32_t n_prims, const Mat4 &pv, const Mat4 &view, Counters *ctr, float *map) {
-  ShadowOwned &sh = c->shadow;
-  FrameSlot &s = sh.pass;
-  auto launch = [&](auto tw, auto th) {
-    constexpr int TW = decltype(tw)::value, TH = decltype(th)::value;
-    if (n_prims)
-      hipLaunchKernelGGL((k_geometry<TW, TH>), dim3((n_prims + 255) / 256), dim3(256), 0, st, d_draws, n_draws, n_prims, first_prims,
-                         s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv, view, fp, s.d_clip.ptr, s.d_broad.ptr,
-                         c->d_materials.ptr, s.d_block_stats.ptr, (uint32_t *)nullptr);
-    hipLaunchKernelGGL((k_raster<TW, TH>), dim3(fp.tiles_x, fp.tiles_y), dim3(kTileThreads), 0, st, s.d_tile_count.ptr, ctr,
-                       s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, (float4 *)nullptr, fp, s.d_tris.ptr, s.d_clip.ptr,
-                       s.d_bins.ptr, (uint32_t *)nullptr, (float *)nullptr, (const float4 *)nullptr, map,
-                       (uint32_t *)nullptr, sh.d_sink.ptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                       (const Light *)nullptr, 0, (CookedLight *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u);
-  };
-  if (c->tile_mode == 0) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{});
-  else launch(std::integral_constant<int, 32>{}, std::integral_constant<int, 32>{});
+// The faces of `q` on `st`, back to back through the pass slot: the frame's own k_geometry and k_raster, face f counting in
+// `ctr[f]` (zero before), the depth of every texel into the f-th S x S map at `map`.
+void launch_shadow_faces(bbr_context *c, hipStream_t st, const FrameParams &fp, const DeviceDraws &draws, uint32_t n_prims,
+                         const CasterRequest &q, Counters *ctr, float *map) {
+  FrameSlot &s = c->shadow.pass;
+  const size_t texels = (size_t)c->shadow_map * (size_t)c->shadow_map;
+  with_tile(c->tile_mode, [&](auto tile) {
+    constexpr int T = decltype(tile)::value;
+    for (int f = 0; f < q.faces; ++f) {
+      RasterIO io;  // the depth into the map; the background's presented words into the sink
+      io.rows = fp.tiles_y, io.depth_io = map + (size_t)f * texels, io.out8 = c->shadow.d_sink.ptr;
+      // gl_Position = (L.proj * L.view) * posWorld: the forward order, whatever "render_pass" is
+      launch_geometry<T, T>(c, s, st, ctr + f, fp, draws, n_prims, proj_view(q.view[f]), q.view[f].view);
+      launch_raster<T, T>(s, st, ctr + f, fp, io);
+    }
+  });
 }
 
-// What the shading kernels get of caster slot `cs` once its maps are (being) rendered from `view`: into generation `cs.cur`
-void set_caster_args(const bbr_context *c, ShadowSlot &cs, int32_t light_index, int32_t n_faces, const ViewUniformBlock *view, float bias) {
+// What the shading kernels get of caster slot `cs` once its maps are (being) rendered as `q` asks: into generation `cs.cur`
+void set_caster_args(const bbr_context *c, ShadowSlot &cs, const CasterRequest &q) {
   const int32_t S = c->shadow_map;
-  for (int f = 0; f < kMaxShadowFaces; ++f) cs.args.m[f] = f < n_faces ? proj_view(view[f]) : Mat4{};
+  for (int f = 0; f < kMaxShadowFaces; ++f) cs.args.m[f] = f < q.faces ? proj_view(q.view[f]) : Mat4{};
   cs.args.map = cs.generation(cs.cur).ptr;
   cs.args.mask = nullptr;
   cs.args.face = nullptr;
   cs.args.side = S;
-  cs.args.light = light_index;
-  cs.args.faces = n_faces;
+  cs.args.light = q.light;
+  cs.args.faces = q.faces;
   cs.args.half = 0.5f * (float)S;
-  cs.args.bias = bias;
+  cs.args.bias = q.bias;
+}
+// The slot becomes valid: the frames from here on are shaded with `q`'s maps in `generation` (rendered, or about to be on the
+// frame's own stream), under a stamp of its own
+void publish(bbr_context *c, ShadowSlot &cs, int generation, const CasterRequest &q) {
+  cs.cur = generation;
+  set_caster_args(c, cs, q);
+  cs.stamp = ++c->caster_stamp;
+  cs.valid = true;
 }
 
 // The table k_shade_shadow_casters reads, from the slots in use
@@ -1292,7 +1363,7 @@ int apply_queued_casters(bbr_context *c, const FrameSlot &into, int *n_queued) {
   if (c->shadow_map <= 0) return BBR_OK;
   const size_t texels = (size_t)c->shadow_map * (size_t)c->shadow_map;
   for (int k = 0; k < kMaxShadowCasters; ++k) {
-    QueuedCaster &q = sh.queued[k];
+    CasterRequest &q = sh.queued[k];
     if (!q.on) continue;
     // (a synchronous call since has put the light into another slot: the call in front of bbr_end_frame would be refused)
     for (int o = 0; o < kMaxShadowCasters; ++o)
@@ -1302,10 +1373,7 @@ int apply_queued_casters(bbr_context *c, const FrameSlot &into, int *n_queued) {
     int g = 0;
     if (int rc = pick_generation(c, k, into, &g)) return rc;
     HIP_TRY(c, cs.generation(g).ensure(texels * (size_t)q.faces));  // (growing frees a buffer nothing on the GPU reads)
-    cs.cur = g;
-    set_caster_args(c, cs, q.light, q.faces, q.view, q.bias);
-    cs.stamp = ++c->caster_stamp;
-    cs.valid = true;
+    publish(c, cs, g, q);
     sh.table_stale = true;
     ++*n_queued;
   }
@@ -1313,12 +1381,11 @@ int apply_queued_casters(bbr_context *c, const FrameSlot &into, int *n_queued) {
 }
 
 // The queued casters' faces on `st` -- the frame's geometry stream, behind its staging transfer, whose descriptors and instance
-// blocks the pass reads (`d_draws`: a static draw's light path stores less of a record the pass never reads, and the same
+// blocks the pass reads (`draws`: a static draw's light path stores less of a record the pass never reads, and the same
 // triangle) -- then k_shadow_pass_retire, which folds the faces' counters into the frame's (`frame_ctr`, `into.h_flags`).
 // The pass slot is the context's one (ShadowOwned::pass), shared by all frames behind ev_pass.  It never holds records a later
 // frame relies on, unlike the frame slot's own buffers under "static_records".
-int launch_queued_passes(bbr_context *c, FrameSlot &into, hipStream_t st, const DrawDesc *d_draws, uint32_t n_draws,
-                         const FirstPrims &first_prims, Counters *frame_ctr) {
+int launch_queued_passes(bbr_context *c, FrameSlot &into, hipStream_t st, const DeviceDraws &draws, Counters *frame_ctr) {
   ShadowOwned &sh = c->shadow;
   FrameSlot &p = sh.pass;
   const FrameParams fp = shadow_pass_params(c);
@@ -1340,12 +1407,11 @@ int launch_queued_passes(bbr_context *c, FrameSlot &into, hipStream_t st, const 
   if (sh.pass_queued) HIP_TRY(c, hipStreamWaitEvent(st, sh.ev_pass, 0));  // behind the pass of the frame before
   uint32_t block = 0;
   for (int k = 0; k < kMaxShadowCasters; ++k) {
-    const QueuedCaster &q = sh.queued[k];
+    const CasterRequest &q = sh.queued[k];
     if (!q.on) continue;
     ShadowSlot &cs = sh.slot[k];
-    for (int f = 0; f < q.faces; ++f)
-      launch_shadow_face(c, st, fp, d_draws, n_draws, first_prims, c->n_prims, cs.args.m[f], q.view[f].view, sh.d_ctr.ptr + block++,
-                         cs.generation(cs.cur).ptr + (size_t)f * texels);
+    launch_shadow_faces(c, st, fp, draws, c->n_prims, q, sh.d_ctr.ptr + block, cs.generation(cs.cur).ptr);
+    block += (uint32_t)q.faces;
     ++c->shadow_queue_passes;
   }
   hipLaunchKernelGGL(k_shadow_pass_retire, dim3(1), dim3(kPassRetireThreads), 0, st, sh.d_ctr.ptr, block, frame_ctr, into.h_flags.ptr);
@@ -1355,44 +1421,51 @@ int launch_queued_passes(bbr_context *c, FrameSlot &into, hipStream_t st, const 
   return BBR_OK;
 }
 
-// The faces of one caster, synchronously, through the pass slot on the context's shading stream: `n_faces` maps of S x S at `map`
-// from the `n_prims` primitives of `d_draws`.  Nothing of the context is on the GPU.  One wait, one read of the faces' counter
-// blocks, one clear; a capacity that overflowed in any face is grown and ALL faces are rendered again.  Shared by the
-// synchronous call (render_shadow_faces) and by the repair of a queued pass that overflowed (settle_queued_passes).
-int render_faces_sync(bbr_context *c, const std::string &who, float *map, int32_t n_faces, const Mat4 *pv, const ViewUniformBlock *lv,
-                      const DrawDesc *d_draws, uint32_t n_draws, const FirstPrims &first_prims, uint32_t n_prims) {
-  ShadowOwned &sh = c->shadow;
-  FrameSlot &s = sh.pass;
-  const size_t texels = (size_t)c->shadow_map * (size_t)c->shadow_map;
-  HIP_TRY(c, sh.d_sink.ensure(texels));
-  HIP_TRY(c, sh.d_ctr.ensure(kMaxShadowFaces, true));
+// A synchronous bin pass over `n_prims` primitives through the pass slot `s`, on the context's shading stream, until it fits.
+// Nothing of the context is on the GPU.  An attempt takes its parameters from `params()` (the capacities: again after a growth),
+// sizes the slot's pass buffers for them, and `launch(fp, stream)` queues it; it counts in the `n_blocks` counter blocks at
+// `d_blocks` (zero before, not a frame slot's: the pass is synchronous, so they are cleared here and not by a kernel).  One
+// wait, one read of the blocks, one clear; a capacity that overflowed in any block is grown by the largest need among them and
+// the whole attempt runs again.
+template <class Params, class Launch>
+int run_pass_sync(bbr_context *c, FrameSlot &s, uint32_t n_prims, Params &&params, Counters *d_blocks, int n_blocks, const std::string &who,
+                  Launch &&launch) {
   for (int attempt = 0; attempt < 8; ++attempt) {
-    const FrameParams fp = shadow_pass_params(c);  // (the capacities; again after a growth)
+    const FrameParams fp = params();
     int rc = ensure_pass_buffers(c, s, n_prims, (size_t)fp.tiles_x * fp.tiles_y);
     if (rc) return rc;
-    s.ctr_index = bbr_context::kMaxSlots;  // (not a frame slot's; the pass counts in sh.d_ctr)
+    s.ctr_index = bbr_context::kMaxSlots;
     hipStream_t st = c->shade_stream();
-    for (int f = 0; f < n_faces; ++f)
-      launch_shadow_face(c, st, fp, d_draws, n_draws, first_prims, n_prims, pv[f], lv[f].view, sh.d_ctr.ptr + f, map + (size_t)f * texels);
+    launch(fp, st);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(st));
     Counters h[kMaxShadowFaces] = {};
-    HIP_TRY(c, hipMemcpy(h, sh.d_ctr.ptr, sizeof(Counters) * (size_t)n_faces, hipMemcpyDeviceToHost));
-    HIP_TRY(c, zero_fill_sync(sh.d_ctr.ptr, sizeof(Counters) * (size_t)n_faces));  // (the pass is synchronous: cleared here, not by a kernel)
+    HIP_TRY(c, hipMemcpy(h, d_blocks, sizeof(Counters) * (size_t)n_blocks, hipMemcpyDeviceToHost));
+    HIP_TRY(c, zero_fill_sync(d_blocks, sizeof(Counters) * (size_t)n_blocks));
     Counters need = {};
-    for (int f = 0; f < n_faces; ++f) {
-      need.overflow |= h[f].overflow;
-      need.bin_need = std::max(need.bin_need, h[f].bin_need);
-      need.n_broad = std::max(need.n_broad, h[f].n_broad);
-      need.n_clip_slots = std::max(need.n_clip_slots, h[f].n_clip_slots);
+    for (int b = 0; b < n_blocks; ++b) {
+      need.overflow |= h[b].overflow;
+      need.bin_need = std::max(need.bin_need, h[b].bin_need);
+      need.n_broad = std::max(need.n_broad, h[b].n_broad);
+      need.n_clip_slots = std::max(need.n_clip_slots, h[b].n_clip_slots);
     }
     if (!need.overflow) return BBR_OK;
-    // a triangle did not fit: a map is incomplete.  Grow and render all of them again.
     rc = apply_growth(c, need.overflow, need.bin_need, need.n_broad, need.n_clip_slots);
     if (rc) return rc;
     if (s.d_tile_count.ptr) HIP_TRY(c, zero_fill_sync(s.d_tile_count.ptr, s.d_tile_count.cap * sizeof(uint32_t)));
   }
-  return fail(c, BBR_ERR_CAPACITY, who + ": capacity still exceeded after 8 growth steps");
+  return fail(c, BBR_ERR_CAPACITY, who + ": " + kStillExceeded);
+}
+
+// The faces of one caster, synchronously, through the pass slot: `q.faces` maps of S x S at `map` from the `n_prims` primitives
+// of `draws`, a counter block per face (run_pass_sync: an overflow in any face renders ALL faces again).  Shared by the
+// synchronous call (render_shadow_faces) and by the repair of a queued pass that overflowed (settle_queued_passes).
+int render_faces_sync(bbr_context *c, const std::string &who, float *map, const CasterRequest &q, const DeviceDraws &draws, uint32_t n_prims) {
+  ShadowOwned &sh = c->shadow;
+  HIP_TRY(c, sh.d_sink.ensure((size_t)c->shadow_map * (size_t)c->shadow_map));
+  HIP_TRY(c, sh.d_ctr.ensure(kMaxShadowFaces, true));
+  return run_pass_sync(c, sh.pass, n_prims, [&] { return shadow_pass_params(c); }, sh.d_ctr.ptr, q.faces, who,
+                       [&](const FrameParams &fp, hipStream_t st) { launch_shadow_faces(c, st, fp, draws, n_prims, q, sh.d_ctr.ptr, map); });
 }
 
 // A queued pass that overflowed is the frame's overflow (k_shadow_pass_retire), and the frame's repair -- growing, rendering the
@@ -1431,8 +1504,8 @@ int settle_queued_passes(bbr_context *c, bool *repaired) {
     for (const CarriedPass &cp : o.carried) {
       ShadowSlot &cs = c->shadow.slot[cp.caster];
       if (!cs.valid || cs.stamp != cp.stamp || !o.d_staging.ptr) continue;  // (replaced or dropped since)
-      rc = render_faces_sync(c, "queued shadow pass", cs.generation(cs.cur).ptr, cp.q.faces, cs.args.m, cp.q.view,
-                             reinterpret_cast<const DrawDesc *>(o.d_staging.ptr + o.draws_offset), o.n_draws, o.first_prims, o.n_prims);
+      const DeviceDraws draws = {reinterpret_cast<const DrawDesc *>(o.d_staging.ptr + o.draws_offset), o.n_draws, o.first_prims};
+      rc = render_faces_sync(c, "queued shadow pass", cs.generation(cs.cur).ptr, cp.q, draws, o.n_prims);
       if (rc) return rc;
     }
   }
@@ -1445,21 +1518,16 @@ int submit_frame_body(bbr_context *c, int slot_index);
 // recorded frame's queued entries, as they were: the queued casters become the context's in front of steps that can fail
 // (apply_queued_casters), and a caster whose maps were never rendered must not stay in use.
 int submit_frame_into(bbr_context *c, int slot_index) {
-  struct Kept {
-    bool valid, queued;
-    int cur;
-    uint32_t stamp;
-    ShadowFacesArgs args;
+  struct {
+    CasterPublished slot;
+    bool queued;
   } kept[kMaxShadowCasters];
   ShadowOwned &sh = c->shadow;
   const bool table_stale = sh.table_stale;
-  for (int k = 0; k < kMaxShadowCasters; ++k) kept[k] = {sh.slot[k].valid, sh.queued[k].on, sh.slot[k].cur, sh.slot[k].stamp, sh.slot[k].args};
+  for (int k = 0; k < kMaxShadowCasters; ++k) kept[k] = {sh.slot[k].published(), sh.queued[k].on};
   const int rc = submit_frame_body(c, slot_index);
   if (rc != BBR_OK) {
-    for (int k = 0; k < kMaxShadowCasters; ++k) {
-      sh.slot[k].valid = kept[k].valid, sh.slot[k].cur = kept[k].cur, sh.slot[k].stamp = kept[k].stamp, sh.slot[k].args = kept[k].args;
-      sh.queued[k].on = kept[k].queued;
-    }
+    for (int k = 0; k < kMaxShadowCasters; ++k) sh.slot[k].published() = kept[k].slot, sh.queued[k].on = kept[k].queued;
     sh.table_stale = table_stale;
   }
   return rc;
@@ -1525,14 +1593,14 @@ int submit_frame_body(bbr_context *c, int slot_index) {
   uint8_t *const h_staging = s.h_staging.ptr;
   std::memcpy(h_staging, c->frame_u.lights, lights_bytes);
   // draw descriptors point into the device copy of the instance data made by the same transfer
-  FirstPrims first_prims;  // first_prim of the frame's draws 1 .. 3 (k_geometry)
-  const uint32_t n_live_draws =
-      fill_draw_descs(c, reinterpret_cast<DrawDesc *>(h_staging + lights_bytes),
-                      reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + lights_bytes + draws_bytes), first_prims);
+  DeviceDraws draws;
+  draws.d = reinterpret_cast<const DrawDesc *>(s.d_staging.ptr + lights_bytes);
+  draws.n = fill_draw_descs(c, reinterpret_cast<DrawDesc *>(h_staging + lights_bytes),
+                            reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + lights_bytes + draws_bytes), draws.first_prims);
   // (while the staging still holds the instance blocks of the slot's previous frame: a repeated descriptor has left them in place)
   const DrawDesc *const h_draws = reinterpret_cast<const DrawDesc *>(h_staging + lights_bytes);
   std::vector<uint32_t> fills;  // draws k_record_static runs for in front of this frame's k_geometry
-  plan_static_records(c, s, reinterpret_cast<DrawDesc *>(h_staging + lights_bytes), n_live_draws, h_staging, s.d_staging.ptr,
+  plan_static_records(c, s, reinterpret_cast<DrawDesc *>(h_staging + lights_bytes), draws.n, h_staging, s.d_staging.ptr,
                       reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + lights_bytes + draws_bytes), fills);
   if (inst_bytes) std::memcpy(h_staging + lights_bytes + draws_bytes, c->host_instances.data(), inst_bytes);
   std::memset(h_staging + head_offset, 0, 16);
@@ -1553,7 +1621,6 @@ int submit_frame_body(bbr_context *c, int slot_index) {
   }
   s.ctr_index = slot_index;
   const Light *d_lights = reinterpret_cast<const Light *>(s.d_staging.ptr);
-  const DrawDesc *d_draws = reinterpret_cast<const DrawDesc *>(s.d_staging.ptr + lights_bytes);
   FrameParams fp = make_params(c);
   // forward: gl_Position = (P*V) * posWorld; deferred: P * (V * posWorld) -- the kernel gets P and V separately
   Mat4 pv = c->deferred ? c->view_u.proj : proj_view(c->view_u);
@@ -1568,11 +1635,13 @@ int submit_frame_body(bbr_context *c, int slot_index) {
 
   HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, h_staging, total, hipMemcpyHostToDevice, st.geom));
   if (n_queued) {
-    rc = launch_queued_passes(c, s, st.geom, d_draws, n_live_draws, first_prims, c->d_counters.ptr + s.ctr_index);
+    rc = launch_queued_passes(c, s, st.geom, draws, c->d_counters.ptr + s.ctr_index);
     if (rc) return rc;
   }
-  if (c->tile_mode == 0) launch_frame<64, 64>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head, h_draws, fills, d_table);
-  else launch_frame<32, 32>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, d_draws, n_live_draws, first_prims, out, d_item_head, h_draws, fills, d_table);
+  with_tile(c->tile_mode, [&](auto tile) {
+    constexpr int T = decltype(tile)::value;
+    launch_frame<T, T>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, draws, out, d_item_head, h_draws, fills, d_table);
+  });
   HIP_TRY(c, hipGetLastError());
   s.in_flight = true;
   for (int k = 0; k < kMaxShadowCasters; ++k) s.shadow_gen[k] = (mode.shadow && c->shadow.slot[k].valid) ? (int8_t)c->shadow.slot[k].cur : (int8_t)-1;
@@ -1581,8 +1650,8 @@ int submit_frame_body(bbr_context *c, int slot_index) {
   for (int k = 0; n_queued && k < kMaxShadowCasters; ++k)
     if (c->shadow.queued[k].on) s.carried.push_back({k, c->shadow.slot[k].stamp, c->shadow.queued[k]});
   s.draws_offset = lights_bytes;
-  s.n_draws = n_live_draws;
-  s.first_prims = first_prims;
+  s.n_draws = draws.n;
+  s.first_prims = draws.first_prims;
   s.serial = ++c->frame_serial;
   s.mode = mode;
   s.present.active = mode.fused;  // fused presentation: the frame IS the presented image
@@ -1719,7 +1788,7 @@ int sync_and_fix(bbr_context *c, Counters *out_counters) {
     rc = resubmit_last_frame(c);
     if (rc) return rc;
   }
-  return fail(c, BBR_ERR_CAPACITY, "bin capacity still exceeded after 8 growth steps");
+  return fail(c, BBR_ERR_CAPACITY, std::string("bin ") + kStillExceeded);
 }
 
 // Render the last frame again with a dump switched on (bbr_context::dump_vis / dump_gbuffer / dump_surface): nothing of
@@ -1832,25 +1901,8 @@ int draw_tbn(bbr_context *c, FrameSlot &fs) {
   auto &t = c->tbn_pass;
   t.valid = false;
   const uint32_t n_prims = c->n_prims;
-  std::vector<DrawDesc> draws;
-  for (const RecordedDraw &rd : c->draws) {
-    const Mesh &m = c->meshes[rd.mesh];
-    DrawDesc d = {};
-    d.vertices = m.d_vertices.ptr;
-    d.indices = m.d_indices.ptr;
-    d.n_instances = rd.n_instances;
-    d.tris_per_instance = rd.tris_per_instance;
-    d.first_prim = rd.first_prim;
-    d.material = (uint32_t)rd.material;
-    draws.push_back(d);
-  }
-  const size_t draws_bytes = (draws.size() * sizeof(DrawDesc) + 255) / 256 * 256;
-  const size_t inst_bytes = c->host_instances.size() * sizeof(InstanceBlock);
-  HIP_TRY(c, t.d_staging.ensure(std::max<size_t>(draws_bytes + inst_bytes, 1)));
-  const InstanceBlock *d_inst = reinterpret_cast<const InstanceBlock *>(t.d_staging.ptr + draws_bytes);
-  for (size_t i = 0; i < draws.size(); ++i) draws[i].instances = d_inst + c->draws[i].first_instance;
-  if (!draws.empty()) HIP_TRY(c, upload_sync(t.d_staging.ptr, draws.data(), draws.size() * sizeof(DrawDesc)));
-  if (inst_bytes) HIP_TRY(c, upload_sync(t.d_staging.ptr + draws_bytes, c->host_instances.data(), inst_bytes));
+  DeviceDraws up;
+  if (int rc = upload_recorded_draws(c, t.d_staging, up)) return rc;
   HIP_TRY(c, t.d_segs.ensure(std::max<size_t>((size_t)n_prims * 8, 1)));
   t.n_slots = n_prims * 8;
   const Mat4 pv = proj_view(fs.view_u);  // vCombined = uProjMat * uViewMat (tbn.vert:21), both render passes
@@ -1860,8 +1912,7 @@ int draw_tbn(bbr_context *c, FrameSlot &fs) {
     int rc = tbn_launch_params(c, c->width, c->height, tp);
     if (rc) return rc;
     if (n_prims)
-      hipLaunchKernelGGL(k_tbn_segments, dim3((n_prims + 255) / 256), dim3(256), 0, st,
-                         reinterpret_cast<const DrawDesc *>(t.d_staging.ptr), (uint32_t)draws.size(), n_prims, pv,
+      hipLaunchKernelGGL(k_tbn_segments, dim3((n_prims + 255) / 256), dim3(256), 0, st, up.d, up.n, n_prims, pv,
                          fs.view_u.enable_normal_map, c->d_materials.ptr, tp, t.d_segs.ptr, t.d_tile_count.ptr, t.d_bins.ptr,
                          t.d_ctr.ptr);
     rc = tbn_check_bins(c, st);
@@ -1987,14 +2038,11 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
   }
   HIP_TRY(c, upload_sync(s.d_staging.ptr, draws.data(), draws.size() * sizeof(DrawDesc)));
   HIP_TRY(c, upload_sync(s.d_staging.ptr + draws_bytes, inst.data(), inst_bytes));
-  const DrawDesc *d_draws = reinterpret_cast<const DrawDesc *>(s.d_staging.ptr);
-  FirstPrims ov_first = {{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}};
-  for (size_t q = 1; q < draws.size() && q <= (size_t)kInlineFirstPrims; ++q) ov_first.v[q - 1] = draws[q].first_prim;
+  DeviceDraws ov = {reinterpret_cast<const DrawDesc *>(s.d_staging.ptr), (uint32_t)draws.size(), {{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}}};
+  for (size_t q = 1; q < draws.size() && q <= (size_t)kInlineFirstPrims; ++q) ov.first_prims.v[q - 1] = draws[q].first_prim;
 
-  for (int attempt = 0; attempt < 8; ++attempt) {
+  auto params = [&] {
     FrameParams fp = make_output_params(c);
-    rc = ensure_pass_buffers(c, s, n_prims, (size_t)fp.tiles_x * fp.tiles_y);  // (again after a growth)
-    if (rc) return rc;
     fp.deferred = 0;
     fp.gbuffer_view = -1;
     fp.ov_first_gizmo_prim = gizmo ? marker_tris * (uint32_t)n_lights : 0xFFFFFFFFu;
@@ -2003,40 +2051,24 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
     fp.ov_cx = (float)x0 + fp.ov_half;
     fp.ov_cy = fp.ov_half;
     fp.ov_x0 = std::max(x0, 0); fp.ov_y0 = 0; fp.ov_x1 = c->width; fp.ov_y1 = std::min(gizmo_extent, c->height);
-    s.ctr_index = bbr_context::kMaxSlots;
-    Counters *ctr = c->d_counters.ptr + s.ctr_index;
-    hipStream_t st = c->shade_stream();
+    return fp;
+  };
+  Counters *ctr = c->d_counters.ptr + bbr_context::kMaxSlots;  // (the overlay pass's block: the frame rendered has made them)
+  // When an overlay triangle did not fit, the presented pixels the attempt already wrote are a subset of the right ones (same
+  // colours), so growing and drawing again on top is correct
+  return run_pass_sync(c, s, n_prims, params, ctr, 1, "draw_overlays", [&](const FrameParams &fp, hipStream_t st) {
     const Mat4 ident = {};
-    auto launch = [&](auto tw, auto th) {
-      constexpr int TW = decltype(tw)::value, TH = decltype(th)::value;
-      hipLaunchKernelGGL((k_geometry<TW, TH, true>), dim3((n_prims + 255) / 256), dim3(256), 0, st, d_draws, (uint32_t)draws.size(),
-                         n_prims, ov_first, s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, ident, ident, fp, s.d_clip.ptr,
-                         s.d_broad.ptr, c->d_materials.ptr, s.d_block_stats.ptr, (uint32_t *)nullptr);
-      hipLaunchKernelGGL((k_raster<TW, TH, true>), dim3(fp.tiles_x, fp.tiles_y), dim3(kTileThreads), 0, st, s.d_tile_count.ptr, ctr,
-                         s.d_broad.ptr, s.d_frag_count.ptr, s.d_frags.ptr, (float4 *)nullptr, fp, s.d_tris.ptr, s.d_clip.ptr,
-                         s.d_bins.ptr, (uint32_t *)nullptr, (float *)nullptr,
-                         (const float4 *)nullptr, fs.d_depth.ptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                         (uint32_t *)nullptr, (uint32_t *)nullptr, (const Light *)nullptr, 0, (CookedLight *)nullptr,
-                         (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u);
-      constexpr int kChunks = TW * TH / kShadeThreads;
-      hipLaunchKernelGGL((k_shade_overlay<TW, TH>), dim3(fp.tiles_x * kChunks, fp.tiles_y), dim3(kShadeThreads), 0, st, fp,
+    RasterIO io;  // tested against the frame's depth; the colour is k_shade_overlay's
+    io.rows = fp.tiles_y, io.depth_io = fs.d_depth.ptr;
+    with_tile(c->tile_mode, [&](auto tile) {
+      constexpr int T = decltype(tile)::value;
+      launch_geometry<T, T, true>(c, s, st, ctr, fp, ov, n_prims, ident, ident);
+      launch_raster<T, T, true>(s, st, ctr, fp, io);
+      constexpr int kChunks = T * T / kShadeThreads;
+      hipLaunchKernelGGL((k_shade_overlay<T, T>), dim3(fp.tiles_x * kChunks, fp.tiles_y), dim3(kShadeThreads), 0, st, fp,
                          s.d_attrs.ptr, s.d_clip.ptr, s.d_frags.ptr, s.d_frag_count.ptr, c->d_srgb_tables.ptr, fs.present.out);
-    };
-    if (c->tile_mode == 0) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{});
-    else launch(std::integral_constant<int, 32>{}, std::integral_constant<int, 32>{});
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(st));
-    Counters h = {};
-    HIP_TRY(c, hipMemcpy(&h, ctr, sizeof h, hipMemcpyDeviceToHost));
-    HIP_TRY(c, zero_fill_sync(ctr, sizeof(Counters)));  // (the pass is synchronous: cleared here, not by a kernel)
-    if (!h.overflow) return BBR_OK;
-    // an overlay triangle did not fit: the presented pixels it already wrote are a subset of the right ones (same
-    // colours), so growing and drawing again on top is correct
-    rc = apply_growth(c, h.overflow, h.bin_need, h.n_broad, h.n_clip_slots);
-    if (rc) return rc;
-    if (s.d_tile_count.ptr) HIP_TRY(c, zero_fill_sync(s.d_tile_count.ptr, s.d_tile_count.cap * sizeof(uint32_t)));
-  }
-  return fail(c, BBR_ERR_CAPACITY, "draw_overlays: capacity still exceeded after 8 growth steps");
+    });
+  });
 }
 
 // ================================================================================================
@@ -2077,33 +2109,51 @@ static int upload_caster_table(bbr_context *c) {
   return BBR_OK;
 }
 
-static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t caster, int32_t light_index, int32_t n_faces,
-                               const void *light_view_blocks, float bias) {
-  if (!c) return BBR_ERR_INVALID_ARGUMENT;
-  BBR_ON_DEVICE(c);
+// A call's arguments judged, for the synchronous calls and (`queued`) for bbr_queue_shadow_caster.  The order of the checks
+// decides which refusal a call with two faults gets.  The queued form differs in two places: a light is also taken by a slot the
+// recorded frame has queued, and the call has to stand inside the frame.
+static int check_caster_request(bbr_context *c, const std::string &who, int32_t caster, int32_t light_index, int32_t n_faces,
+                                const void *light_view_blocks, float bias, bool queued) {
   if (c->shadow_map <= 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": option shadow_map is 0");
   if (caster < 0 || caster >= kMaxShadowCasters) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": caster outside 0 .. 7");
   if (n_faces < 1 || n_faces > kMaxShadowFaces) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": n_faces outside 1 .. 6");
   if (light_index < 0 || light_index >= kMaxNumLights) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": light_index outside 0 .. 99");
   if (!light_view_blocks) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": NULL view block");
   if (bias != bias) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": bias is NaN");
+  const ShadowOwned &sh = c->shadow;
   for (int s = 0; s < kMaxShadowCasters; ++s)
-    if (s != caster && c->shadow.slot[s].valid && c->shadow.slot[s].args.light == light_index)
-      return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": another caster slot in use holds this light_index (one slot per light)");
+    if (s != caster && ((sh.slot[s].valid && sh.slot[s].args.light == light_index) || (queued && sh.queued[s].on && sh.queued[s].light == light_index)))
+      return fail(c, BBR_ERR_INVALID_ARGUMENT, who + (queued ? ": another caster slot, in use or queued in this frame, holds this light_index (one slot per light)"
+                                                              : ": another caster slot in use holds this light_index (one slot per light)"));
+  if (queued && !c->in_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, who + ": outside begin_frame/end_frame");
   if (!c->in_frame && !c->have_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, who + ": no recorded draws (call it after bbr_draw or after bbr_end_frame)");
   for (const RecordedDraw &rd : c->draws)
     if (!c->meshes[rd.mesh].alive || !c->materials[rd.material].alive)
       return fail(c, BBR_ERR_BAD_HANDLE, who + ": a recorded draw's mesh or material was freed");
+  return BBR_OK;
+}
+// ... and made into the request (the view blocks are copied)
+static CasterRequest caster_request(int32_t light_index, int32_t n_faces, const void *light_view_blocks, float bias, bool queued) {
+  CasterRequest q = {};
+  q.on = queued;
+  q.light = light_index, q.faces = n_faces, q.bias = bias;
+  std::memcpy(q.view, light_view_blocks, sizeof(ViewUniformBlock) * (size_t)n_faces);
+  return q;
+}
+
+static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t caster, int32_t light_index, int32_t n_faces,
+                               const void *light_view_blocks, float bias) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (int rc = check_caster_request(c, who, caster, light_index, n_faces, light_view_blocks, bias, false)) return rc;
+  const CasterRequest q = caster_request(light_index, n_faces, light_view_blocks, bias, false);
   int rc = sync_and_fix(c, nullptr);  // the frames in flight leave the GPU (and the last one is complete)
   if (rc) return rc;
   rc = upload_material_table(c);
   if (rc) return rc;
-  ViewUniformBlock lv[kMaxShadowFaces];
-  std::memcpy(lv, light_view_blocks, sizeof(ViewUniformBlock) * (size_t)n_faces);
 
   ShadowOwned &sh = c->shadow;
   ShadowSlot &cs = sh.slot[caster];
-  FrameSlot &s = sh.pass;
   // (outside a frame the recorded frame's queued pass for this slot is replaced too: a replay shows this call's maps.  Inside
   //  one it is not: the queued pass stands in front of bbr_end_frame, behind this call)
   if (!c->in_frame) sh.queued[caster].on = false;
@@ -2112,33 +2162,14 @@ static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t c
     rc = upload_caster_table(c);
     if (rc) return rc;
   }
-  const int32_t S = c->shadow_map;
-  const size_t texels = (size_t)S * (size_t)S;
-  HIP_TRY(c, cs.d_map.ensure(texels * (size_t)n_faces));
-  HIP_TRY(c, sh.d_sink.ensure(texels));
-  HIP_TRY(c, sh.d_ctr.ensure(kMaxShadowFaces, true));
-
-  // ---- the recorded draws: [draw descriptors | instances], as the frame's staging holds them ----
-  const size_t draws_bytes = (sizeof(DrawDesc) * std::max<size_t>(c->draws.size(), 1) + 127) & ~(size_t)127;
-  const size_t inst_bytes = sizeof(InstanceBlock) * c->host_instances.size();
-  HIP_TRY(c, s.d_staging.ensure(draws_bytes + std::max<size_t>(inst_bytes, 1)));
-  std::vector<DrawDesc> draws(std::max<size_t>(c->draws.size(), 1));
-  FirstPrims first_prims;
-  const uint32_t n_draws = fill_draw_descs(c, draws.data(), reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + draws_bytes), first_prims);
-  if (n_draws) HIP_TRY(c, upload_sync(s.d_staging.ptr, draws.data(), n_draws * sizeof(DrawDesc)));
-  if (inst_bytes) HIP_TRY(c, upload_sync(s.d_staging.ptr + draws_bytes, c->host_instances.data(), inst_bytes));
-  const DrawDesc *d_draws = reinterpret_cast<const DrawDesc *>(s.d_staging.ptr);
-  const uint32_t n_prims = c->n_prims;
-  Mat4 pv[kMaxShadowFaces];  // gl_Position = (L.proj * L.view) * posWorld: the forward order, whatever "render_pass" is
-  for (int f = 0; f < n_faces; ++f) pv[f] = proj_view(lv[f]);
-
-  rc = render_faces_sync(c, who, cs.d_map.ptr, n_faces, pv, lv, d_draws, n_draws, first_prims, n_prims);
+  HIP_TRY(c, cs.d_map.ensure((size_t)c->shadow_map * (size_t)c->shadow_map * (size_t)n_faces));
+  DeviceDraws draws;
+  rc = upload_recorded_draws(c, sh.pass.d_staging, draws);
+  if (rc) return rc;
+  rc = render_faces_sync(c, who, cs.d_map.ptr, q, draws, c->n_prims);
   if (rc) return rc;
   for (DeviceBuffer<float> &g : cs.d_more) g.release();  // (nothing is in flight: the generations of earlier queued passes go)
-  cs.cur = 0;  // (the synchronous pass writes generation 0)
-  set_caster_args(c, cs, light_index, n_faces, lv, bias);
-  cs.stamp = ++c->caster_stamp;
-  cs.valid = true;
+  publish(c, cs, 0, q);  // (the synchronous pass writes generation 0)
   rc = upload_caster_table(c);
   if (rc) cs.valid = false;  // (the table still says so)
   return rc;
@@ -2162,27 +2193,9 @@ extern "C" int bbr_render_shadow_caster(bbr_context *c, int32_t caster, int32_t 
 extern "C" int bbr_queue_shadow_caster(bbr_context *c, int32_t caster, int32_t light_index, int32_t n_faces, const void *light_view_blocks,
                                        float bias) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
-  const std::string who = "queue_shadow_caster";
-  if (c->shadow_map <= 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": option shadow_map is 0");
-  if (caster < 0 || caster >= kMaxShadowCasters) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": caster outside 0 .. 7");
-  if (n_faces < 1 || n_faces > kMaxShadowFaces) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": n_faces outside 1 .. 6");
-  if (light_index < 0 || light_index >= kMaxNumLights) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": light_index outside 0 .. 99");
-  if (!light_view_blocks) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": NULL view block");
-  if (bias != bias) return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": bias is NaN");
-  ShadowOwned &sh = c->shadow;
-  for (int s = 0; s < kMaxShadowCasters; ++s)
-    if (s != caster && ((sh.slot[s].valid && sh.slot[s].args.light == light_index) || (sh.queued[s].on && sh.queued[s].light == light_index)))
-      return fail(c, BBR_ERR_INVALID_ARGUMENT, who + ": another caster slot, in use or queued in this frame, holds this light_index (one slot per light)");
-  if (!c->in_frame) return fail(c, BBR_ERR_NOT_IN_FRAME, who + ": outside begin_frame/end_frame");
-  for (const RecordedDraw &rd : c->draws)
-    if (!c->meshes[rd.mesh].alive || !c->materials[rd.material].alive)
-      return fail(c, BBR_ERR_BAD_HANDLE, who + ": a recorded draw's mesh or material was freed");
-  QueuedCaster &q = sh.queued[caster];  // (a second call for the slot in one frame: the last one stands)
-  q.on = true;
-  q.light = light_index;
-  q.faces = n_faces;
-  q.bias = bias;
-  std::memcpy(q.view, light_view_blocks, sizeof(ViewUniformBlock) * (size_t)n_faces);
+  if (int rc = check_caster_request(c, "queue_shadow_caster", caster, light_index, n_faces, light_view_blocks, bias, true)) return rc;
+  // (a second call for the slot in one frame: the last one stands)
+  c->shadow.queued[caster] = caster_request(light_index, n_faces, light_view_blocks, bias, true);
   return BBR_OK;
 }
 
@@ -2715,7 +2728,7 @@ int bbr_begin_frame(bbr_context *c) {
   c->n_prims = 0;
   c->in_frame = true;
   c->have_frame = false;
-  for (QueuedCaster &q : c->shadow.queued) q.on = false;  // (bbr_queue_shadow_caster: they belonged to the frame before)
+  for (CasterRequest &q : c->shadow.queued) q.on = false;  // (bbr_queue_shadow_caster: they belonged to the frame before)
   return BBR_OK;
 }
 

@@ -16,7 +16,8 @@ tests/shadow_casters_scenes.py.  Every test calls a new symbol.
   3  persistence   the caster stays for frames that queue nothing; a synchronous call replaces it; a drop drops it
   4  overflow      a first queued pass that exceeds its first capacities: after bbr_get_stats frame and maps are right; also with
                    a plain frame behind it, and for a host that never synchronises (the slot's reuse finds it)
-  5  state         every refusal leaves slots, counters and the next frame alone; outside a frame; one slot twice; one light twice
+  5  state         every refusal leaves slots, counters and the next frame alone, and is the synchronous call's refusal (code and
+                   text); outside a frame; one slot twice; one light twice
   6  around        a partition of three, supersample 2 in both sample modes, both tile modes, static_records with repeated
                    draws, replay, resize, live_resources()"""
 import ctypes as C
@@ -365,6 +366,34 @@ def test_refusals_leave_everything_as_it_was():
     r.end_frame()
     assert state(r) == want_state and r.shadow_queue_counts() == want_counts
     assert equal(r.read_framebuffer(), want_frame), "a frame of refused calls is not the frame without them"
+    rig.close()
+
+    # The queued and the synchronous form judge a request alike: the same code, and the same text behind the call's name -- but
+    # for the one-slot-per-light refusal, where the queued form also looks at what the frame has queued and says so.
+    rig = Rig("queue", size=(32, 32), side=16)
+    r = rig.r
+    rig.frame([held])
+    want_state, want_counts = state(r), r.shadow_queue_counts()
+
+    def refusal(name, caster, light, n_faces, blocks, bias):
+        rc = getattr(r._L, "bbr_" + name)(r._ctx, caster, light, n_faces, blocks.ctypes.data_as(C.c_void_p), bias)
+        text = r._L.bbr_last_error(r._ctx).decode()
+        assert text.startswith(name + ": "), text
+        return rc, text[len(name) + 2:]
+
+    one_slot_per_light = ("another caster slot, in use or queued in this frame, holds this light_index (one slot per light)",
+                          "another caster slot in use holds this light_index (one slot per light)")
+    faults = {"caster 8": (8, 0, 1, SPOT, CS.BIAS), "no face": (0, 0, 0, SPOT, CS.BIAS), "seven faces": (0, 0, 7, views(7), CS.BIAS),
+              "light 100": (0, 100, 1, SPOT, CS.BIAS), "NaN bias": (0, 0, 1, SPOT, float("nan")), "light held by slot 0": (1, 0, 1, SPOT, CS.BIAS)}
+    r.begin_frame()
+    for mesh, mat, inst in rig.draws:
+        r.draw(mesh, mat, inst)
+    for what, args in faults.items():
+        (q_rc, q_text), (s_rc, s_text) = refusal("queue_shadow_caster", *args), refusal("render_shadow_caster", *args)
+        assert q_rc == s_rc == INVALID, (what, q_rc, s_rc)
+        assert (q_text, s_text) == one_slot_per_light if what == "light held by slot 0" else q_text == s_text, (what, q_text, s_text)
+    r.end_frame()
+    assert state(r) == want_state and r.shadow_queue_counts() == want_counts
     rig.close()
 
 
