@@ -147,6 +147,7 @@ SIGNATURES = {
     "bbr_capacity_growths": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "bbr_static_record_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bbr_read_sky_tiles": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "bbr_view_keep_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bbr_host_timing": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bbr_host_timing_reset": (C.c_int, [_P]),
     "bbr_debug_live_resources": (C.c_int, [C.POINTER(C.c_uint64)]),

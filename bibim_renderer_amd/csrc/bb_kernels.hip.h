@@ -2245,6 +2245,13 @@ __global__ __launch_bounds__(kItemsThreads) void k_shade_items(FrameParams fp, c
   }
 }
 
+// The frame's cooked light table alone, one workgroup: a kept frame (option "view_keep") runs neither of the kernels that
+// cook it on the way (k_raster's first workgroup, k_shade_items' last), and its lights may be new.
+__global__ __launch_bounds__(kItemsThreads) void k_cook_lights(const Light *__restrict__ lights, int num_lights,
+                                                               CookedLight *__restrict__ cooked) {
+  cook_lights<kItemsThreads>(lights, num_lights, cooked);
+}
+
 // ------------------------------------------------------------------------------------------------
 // k_shade: forward_brdf.frag + brdf.glsl once per visible pixel.
 //

@@ -168,6 +168,26 @@ struct SkyKeep {
   const void *out = nullptr, *state = nullptr;  // the frame and the state buffer the stamp speaks of
   int32_t width = 0, height = 0, tiles_x = 0, tiles_y = 0, tile_mode = -1;
 };
+// Option "view_keep": what a slot remembers about the visibility in its buffers.  While `valid`, the slot's geometry-side
+// buffers (tris, records, bins, every-tile list, clip slots, fragment lists and counts, items, item count) and the background
+// pixels of its d_frame are those of a complete frame rendered from exactly the inputs below: a frame with the same inputs
+// launches its shading only (launch_frame's kept branch).  Set by every full frame that may be kept behind (submit_frame_body),
+// left alone by a kept one; whatever touches the image or the lists outside launch_frame forgets (FrameSlot::forget_visibility).
+struct VisKeep {
+  bool valid = false;
+  bool kept_last = false;  // the slot's last frame was a kept one (bbr_read_sky_tiles: it stored into no background tile)
+  // the inputs k_geometry, k_raster and k_shade_items had beside the draws (those: plan_static_records' keys)
+  Mat4 pv = {}, view = {};
+  FrameParams fp = {};  // the final ones (capacities, heavy rows)
+  FirstPrims first_prims = {};
+  uint32_t n_draws = 0, n_prims = 0;
+  int tile_mode = -1, grid_y = 0;
+  bool short_frame = false;
+  size_t head_offset = 0;  // of the item head in the staging
+  // the buffers that hold it
+  const void *buffers[15] = {};
+};
+
 // ... by the render or the output extent: bbr_resize and option "supersample" drop it (drop_extent_buffers)
 struct ExtentSized {
   DeviceBuffer<float4> d_frame;
@@ -283,10 +303,16 @@ struct FrameSlot : TileSized, ExtentSized {
   }
   // Option "sky_keep": something other than this slot's own k_raster / k_shade may have written its frame, or the frame or
   // the state words are not the ones the stamp speaks of.  The rule for every entry point that touches a slot's image or its
-  // buffers outside launch_frame: call this (forget_sky(c) does it for every slot).  Touches no memory: the slot's next
+  // buffers outside launch_frame: call this (forget_image(c) does it for every slot, with what stands below).  Touches no memory: the slot's next
   // frame runs under a fresh stamp, fills every sky tile and keeps again from the frame after.
   SkyKeep sky;
   void forget_sky() { sky.stamp = 0; }
+  // Option "view_keep": the same rule, and besides for whatever touches, frees or re-reads under other inputs the slot's
+  // geometry-side buffers (a capacity growth, a diagnostic re-render, a dropped buffer group): the slot's next frame is
+  // rendered in full.  An entry point that touches the image forgets both (forget_image).
+  VisKeep vis;
+  void forget_visibility() { vis.valid = false; }
+  void forget_image() { forget_sky(), forget_visibility(); }
   // native exchange (bbr_allgather_frame / bbr_push_shard) with library-owned buffers: every rank's block, the whole frame
   DeviceBuffer<uint8_t> d_gathered, d_whole;
 };
@@ -407,7 +433,10 @@ struct bbr_context : ExtentDumps {
   uint32_t n_prims = 0;
 
   static constexpr int kMaxSlots = 4;
-  static constexpr int kCounterBlocks = kMaxSlots + 1;  // one per frame slot + one for the overlay pass
+  // one per frame slot + one for the overlay pass + a spare one: what the shading of a kept frame (option "view_keep") retires
+  // in place of its slot's block, whose retired copy stays the full frame's
+  static constexpr int kCounterBlocks = kMaxSlots + 2;
+  static constexpr int kSpareCounterBlock = kMaxSlots + 1;
   FrameSlot slots[kMaxSlots];
   DeviceBuffer<Counters> d_counters;       // zero between frames: a frame's k_shade clears its slot's block ...
   DeviceBuffer<Counters> d_counters_done;  // ... after copying it here (statistics, overflow check)
@@ -464,6 +493,10 @@ struct bbr_context : ExtentDumps {
   // option "sky_keep": 1 = a tile that was background when its frame slot rendered last, and is background again, is not
   // filled again (k_raster's light-tile path, SkyKeep); 0 = every frame stores every background pixel
   bool sky_keep = true;
+  // option "view_keep": 1 = a frame whose view, draws and geometry parameters are those its frame slot rendered last launches
+  // its shading only (VisKeep, launch_frame's kept branch); 0 = every frame runs every stage
+  bool view_keep = true;
+  uint64_t view_kept_frames = 0, view_full_frames = 0;  // bbr_view_keep_counts: main frames submitted either way
   bool dump_records = false;    // (bbr_read_records: its frame shows what k_geometry's full path writes, and what it leaves alone)
   // Bumped by every call that can change what a mesh or material handle, or a pointer taken from one, means (upload and free
   // of either, the material table, the mip chains): a freed and reused address never compares equal to its former self.
@@ -640,9 +673,9 @@ constexpr size_t kFragCountWords = 2;   // counts, sky words
 uint32_t *sky_words(const FrameSlot &s, size_t tiles) {
   return s.d_frag_count.cap >= tiles * kFragCountWords ? s.d_frag_count.ptr + tiles * (kFragCountWords - 1) : nullptr;
 }
-// Option "sky_keep": every slot forgets (FrameSlot::forget_sky has the rule)
-void forget_sky(bbr_context *c) {
-  for (FrameSlot &s : c->slots) s.forget_sky();
+// Options "sky_keep" and "view_keep": every slot forgets what it holds (FrameSlot::forget_sky has the rule)
+void forget_image(bbr_context *c) {
+  for (FrameSlot &s : c->slots) s.forget_image();
 }
 // The stamp a main frame about to be launched into slot `s` runs under (0: it keeps nothing and marks nothing; k_raster then
 // gets no state words at all).  A frame may keep while it is a forward frame of the whole image, one sample per pixel, into
@@ -651,10 +684,25 @@ void forget_sky(bbr_context *c) {
 // Everything else gets, or leaves behind, a fresh stamp from a process-wide counter: bit 30 set, bit 0 (kSkyKept) and bit 31
 // clear, so it is never 0, k_raster's words of earlier stamps cannot equal it, and neither can the zeros of a new buffer
 // or a fragment count (at most a tile's pixels, with or without kFullTile = bit 31).
+// What options "sky_keep" and "view_keep" both rest on: the frame about to go into slot `s` is a forward frame of the whole
+// image, one sample per pixel, into the slot's own fp32 frame, and k_raster's light-tile path is in use (no depth or
+// visibility store).  Only such a frame leaves pixels behind that the slot's next frame may rely on, and only such a frame may.
+bool keeps_own_image(const bbr_context *c, const FrameSlot &s, const FrameMode &mode, const float4 *out) {
+  return !c->ablate && !c->deferred && !c->ext_out && c->world == 1 && !c->dump_vis && !mode.fused && !mode.resolve && !mode.depth &&
+         out && out == s.d_frame.ptr;
+}
+// Option "view_keep": the two frames' visibility is a function of the same inputs and lies in the same buffers (byte for byte:
+// the members compared have no padding)
+bool same_inputs(const VisKeep &a, const VisKeep &b) {
+  static_assert(sizeof(FrameParams) == 27 * 4 && sizeof(Mat4) == 64 && sizeof(FirstPrims) == 4 * kInlineFirstPrims, "no padding");
+  return std::memcmp(&a.pv, &b.pv, sizeof a.pv) == 0 && std::memcmp(&a.view, &b.view, sizeof a.view) == 0 &&
+         std::memcmp(&a.fp, &b.fp, sizeof a.fp) == 0 && std::memcmp(&a.first_prims, &b.first_prims, sizeof a.first_prims) == 0 &&
+         a.n_draws == b.n_draws && a.n_prims == b.n_prims && a.tile_mode == b.tile_mode && a.grid_y == b.grid_y &&
+         a.short_frame == b.short_frame && a.head_offset == b.head_offset && std::memcmp(a.buffers, b.buffers, sizeof a.buffers) == 0;
+}
 uint32_t sky_stamp_for(const bbr_context *c, FrameSlot &s, const FrameMode &mode, const float4 *out) {
   const uint32_t *state = sky_words(s, (size_t)c->tiles_x() * c->tiles_y());
-  const bool may_keep = c->sky_keep && !c->ablate && !c->deferred && !c->ext_out && c->world == 1 && !c->dump_vis && !mode.fused &&
-                        !mode.resolve && !mode.depth && out && out == s.d_frame.ptr && state;
+  const bool may_keep = c->sky_keep && keeps_own_image(c, s, mode, out) && state;
   const SkyKeep now = {s.sky.stamp, 0u, out, state, c->width, c->height, c->tiles_x(), c->tiles_y(), c->tile_mode};
   const SkyKeep &was = s.sky;
   if (!may_keep || was.out != now.out || was.state != now.state || was.width != now.width || was.height != now.height ||
@@ -955,12 +1003,48 @@ void launch_raster(FrameSlot &s, hipStream_t st, Counters *ctr, const FrameParam
                      io.cooked, io.heavy, io.sky_state, io.sky_stamp);
 }
 
-// `ev`: the frame's five timing events, or nullptr; `final_out`: the W x H fp32 frame (nullptr if the mode has none)
+// What a main frame's launches are sized by, decided once in front of them (frame_shape): the final parameters, the rows of
+// k_raster's screen-ordered grid, the item slots of the frame and whether it is a short one.
+struct FrameShape {
+  FrameParams fp;
+  int grid_y;
+  uint32_t max_items;
+  bool short_frame;
+};
+FrameShape frame_shape(const bbr_context *c, const FrameSlot &s, const FrameMode &mode, const FrameParams &fp_in) {
+  FrameShape z = {fp_in, 0, 0u, false};
+  FrameParams &fp = z.fp;
+  // a rank without bands (more ranks than bands) still launches one row: its blocks fall off tiles_y and exit
+  z.grid_y = std::max(1, c->world > 1 ? c->local_bands() * fp.band_tiles : fp.tiles_y);
+  // A SHORT frame (at most option "no_tail_items" item slots: 1080p has 32 640) has no k_shade_items launch: k_raster's tiles
+  // append their items themselves through the head word the staging copy has just zeroed, and its first workgroup cooks
+  // the lights.  One kernel and one kernel boundary less on the frame's chain of dependent kernels; such a frame is also
+  // shaded at full coverage, without the tail launch (launch_frame).
+  z.max_items = (uint32_t)(fp.tiles_x * z.grid_y) * (uint32_t)(c->tile_w() * c->tile_h() / 64);
+  // option "sample_shading" 0 (n >= 2): always the long route -- k_sample_merge thins the lists behind k_raster and does the
+  // accounting of the items, which k_raster therefore leaves alone (both of its pointers are guarded)
+  z.short_frame = !mode.merged && z.max_items <= (uint32_t)c->no_tail_items;
+  // Heavy tiles first (long frames; k_raster): the heavy rows in front of the launch are sized from the length of the list
+  // the slot's previous frame produced (pinned word kFlagHeavyTiles) + 1/8 + 8.  A list that does not fit them is not
+  // used by that frame at all (plain screen order), so the first frame of a slot, or one after a jump, is merely slower.
+  const int64_t heavy_tiles = c->heavy_tiles >= 0 ? c->heavy_tiles : (c->pipelined() ? 0 : 64);
+  if (!z.short_frame && heavy_tiles > 0 && !c->dump_vis) {
+    fp.heavy_threshold = (uint32_t)heavy_tiles;
+    const uint32_t seen_heavy = s.h_flags.ptr ? s.h_flags.ptr[kFlagHeavyTiles] : 0u;
+    if (seen_heavy) fp.heavy_rows = (int32_t)((seen_heavy + seen_heavy / 8u + 8u + (uint32_t)fp.tiles_x - 1u) / (uint32_t)fp.tiles_x);
+  }
+  return z;
+}
+
+// `ev`: the frame's five timing events, or nullptr; `final_out`: the W x H fp32 frame (nullptr if the mode has none).
+// `kept` (option "view_keep", submit_frame_body decides): the slot's buffers hold this frame's visibility already: nothing is
+// launched in front of the shading but, where `cook` says the lights are not the ones the slot's table was cooked from, k_cook_lights.
 template <int TW, int TH>
-void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const FrameStreams &st, const Event *ev, const FrameParams &fp_in,
+void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const FrameStreams &st, const Event *ev, const FrameShape &shape,
                   const Mat4 &pv, const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DeviceDraws &draws, float4 *final_out,
-                  uint32_t *d_item_head, const DrawDesc *h_draws, const std::vector<uint32_t> &fills, const ShadowCasterTable *frame_table) {
-  FrameParams fp = fp_in;
+                  uint32_t *d_item_head, const DrawDesc *h_draws, const std::vector<uint32_t> &fills, const ShadowCasterTable *frame_table,
+                  bool kept, bool cook) {
+  const FrameParams &fp = shape.fp;
   // Where the kernels up to shading write.  With a resolve they render the fine frame and k_resolve (at the end) writes
   // `final_out`; with fused presentation k_raster / k_shade write presented pixels into the slot's RGBA8 image, unless there is a
   // resolve (a fine frame is fp32: a presented byte cannot be averaged, k_resolve presents)
@@ -972,82 +1056,79 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
   float *depth = !mode.depth ? nullptr : (resolve ? s.d_fine_depth.ptr : s.d_depth.ptr);
   uint32_t *vis_prim = !c->dump_vis ? nullptr : (resolve ? c->d_vis_fine_prim.ptr : c->d_vis_prim.ptr);
   float *vis_depth = !c->dump_vis ? nullptr : (resolve ? c->d_vis_fine_depth.ptr : c->d_vis_depth.ptr);
-  // a rank without bands (more ranks than bands) still launches one row: its blocks fall off tiles_y and exit
-  const int grid_y = std::max(1, c->world > 1 ? c->local_bands() * fp.band_tiles : fp.tiles_y);
-  // A SHORT frame (at most option "no_tail_items" item slots: 1080p has 32 640) has no k_shade_items launch: k_raster's tiles
-  // append their items themselves through the head word the staging copy has just zeroed, and its first workgroup cooks
-  // the lights.  One kernel and one kernel boundary less on the frame's chain of dependent kernels; such a frame is also
-  // shaded at full coverage, without the tail launch (below).
-  const uint32_t max_items = (uint32_t)(fp.tiles_x * grid_y) * (uint32_t)(TW * TH / 64);
-  // option "sample_shading" 0 (n >= 2): always the long route -- k_sample_merge thins the lists behind k_raster and does the
-  // accounting of the items, which k_raster therefore leaves alone (both of its pointers are guarded)
-  const bool short_frame = !merged && max_items <= (uint32_t)c->no_tail_items;
-  // Heavy tiles first (long frames; k_raster): the heavy rows in front of the launch are sized from the length of the list
-  // the slot's previous frame produced (pinned word kFlagHeavyTiles) + 1/8 + 8.  A list that does not fit them is not
-  // used by that frame at all (plain screen order), so the first frame of a slot, or one after a jump, is merely slower.
-  const int64_t heavy_tiles = c->heavy_tiles >= 0 ? c->heavy_tiles : (c->pipelined() ? 0 : 64);
-  if (!short_frame && heavy_tiles > 0 && !c->dump_vis) {
-    fp.heavy_threshold = (uint32_t)heavy_tiles;
-    const uint32_t seen_heavy = s.h_flags.ptr ? s.h_flags.ptr[kFlagHeavyTiles] : 0u;
-    if (seen_heavy) fp.heavy_rows = (int32_t)((seen_heavy + seen_heavy / 8u + 8u + (uint32_t)fp.tiles_x - 1u) / (uint32_t)fp.tiles_x);
-  }
+  const int grid_y = shape.grid_y;
+  const uint32_t max_items = shape.max_items;
+  const bool short_frame = shape.short_frame;
   const hipStream_t sg = st.geom, sr = st.raster, ss = st.shade;
-  Counters *ctr = c->d_counters.ptr + s.ctr_index, *ctr_done = c->d_counters_done.ptr + s.ctr_index;
-  // option "static_records": the draws whose key has just repeated in this slot (plan_static_records; `h_draws`: the host's
-  // copy of `draws.d`) get the camera-independent part of their records first, once; k_geometry then stores the rest
-  for (const uint32_t d : fills) {
-    const uint32_t n = h_draws[d].n_instances * h_draws[d].tris_per_instance;
-    hipLaunchKernelGGL(k_record_static, dim3((n + kRecordStaticThreads - 1) / kRecordStaticThreads), dim3(kRecordStaticThreads), 0, sg,
-                       draws.d, d, s.d_attrs.ptr);
-    ++c->static_fills;
-  }
-  launch_geometry<TW, TH>(c, s, sg, ctr, fp, draws, c->n_prims, pv, view, s.d_heavy.ptr);
-  if (ev && c->timing == 1) (void)hipEventRecord(ev[1], sg);
-  stream_edge(sg, sr, s.ev_geom_done);
-  // k_raster writes the background pixels of `out`: if the frame still shading on the other stream writes the
-  // same buffer (single external output), raster has to wait for it; geometry above still overlapped
-  // (every frame still in flight, not just the previous one: with one stream per slot, or while the layout is being
-  //  switched, "after the previous frame" no longer implies "after the one before")
-  for (const FrameSlot &o : c->slots)
-    if (&o != &s && o.in_flight && final_out && o.out_used == final_out && o.stream_used != sr) (void)o.follow(sr);
-  if (fp.deferred)
-    hipLaunchKernelGGL(k_deferred_background, dim3(1), dim3(kBackgroundThreads), 0, sr, sp, d_lights, s.d_background.ptr, tables, fp.gbuffer_view);
+  // (a kept frame: the slot's block is zero already and its retired copy holds the full frame's statistics, which stay: the
+  //  frame's shading retires the spare block, and finds the chunk totals cleared)
+  const int ctr_block = kept ? bbr_context::kSpareCounterBlock : s.ctr_index;
+  Counters *ctr = c->d_counters.ptr + ctr_block, *ctr_done = c->d_counters_done.ptr + ctr_block;
   uint32_t *item_head = short_frame ? d_item_head : nullptr;
-  RasterIO io;
-  io.rows = fp.heavy_rows + grid_y;
-  io.out = out, io.out8 = out8, io.vis_prim = vis_prim, io.vis_depth = vis_depth, io.depth_io = depth, io.host_flags = s.h_flags.ptr;
-  io.background = fp.deferred ? s.d_background.ptr : nullptr;
-  io.item_groups = (short_frame || merged) ? nullptr : s.d_item_groups.ptr, io.item_head = item_head, io.items = s.d_items.ptr;
-  io.lights = d_lights, io.num_lights = sp.num_lights, io.cooked = s.d_cooked.ptr, io.heavy = s.d_heavy.ptr;
-  // option "sky_keep": the stamp this frame's light tiles keep and mark under, if the frame may (k_raster writes `final_out` then)
-  io.sky_stamp = sky_stamp_for(c, s, mode, final_out);
-  io.sky_state = io.sky_stamp ? sky_words(s, (size_t)fp.tiles_x * fp.tiles_y) : nullptr;
-  launch_raster<TW, TH>(s, sr, ctr, fp, io);
-  if (merged)
-    with_samples(mode.n, [&](auto n) {
-      constexpr int N = decltype(n)::value;
-      if constexpr (N != 3)  // (refused_pair)
-        hipLaunchKernelGGL((k_sample_merge<TW, TH, N>), dim3((unsigned)fp.tiles_x, (unsigned)grid_y), dim3(kMergeThreads), 0, sr, fp, s.d_frag_count.ptr,
-                           s.d_frags.ptr, reinterpret_cast<typename SampleMap<N>::Word *>(s.d_sample_map.ptr), s.d_item_groups.ptr);
-    });
-  // k_shade's work list (64 fragments per item), built from the per-tile fragment counts as soon as k_raster is done; the
-  // same launch cooks the frame's light table
-  if (!short_frame)
-    hipLaunchKernelGGL((k_shade_items<TW, TH>), dim3((unsigned)((fp.tiles_x * grid_y + kItemsThreads - 1) / kItemsThreads)), dim3(kItemsThreads), 0, sr, fp, s.d_frag_count.ptr, s.d_item_groups.ptr, s.d_items.ptr,
-                       fp.tiles_x, grid_y, s.h_flags.ptr ? s.h_flags.ptr + kFlagItemCount : nullptr, d_lights, sp.num_lights, s.d_cooked.ptr,
-                       s.d_tile_count.ptr, ctr, s.d_heavy.ptr);
-  if (mode.depth_rule && (depth || vis_prim)) {
-    // k_resolve_depth, on k_raster's stream behind it and in front of the edge to the shading stream: the slot's ev_done, recorded
-    // behind shading, covers it in every stream layout.  The plain form for the overlay pass's depth, the PRIM form for the dump.
-    const dim3 grid((unsigned)((c->width + kResolveThreads - 1) / kResolveThreads), (unsigned)c->height);
-    auto launch = [&](auto n, auto rule, auto prim, const float *fine_depth, const uint32_t *fine_prim, float *to_depth, uint32_t *to_prim) {
-      hipLaunchKernelGGL((k_resolve_depth<decltype(n)::value, decltype(rule)::value, decltype(prim)::value>), grid, dim3(kResolveThreads), 0, sr,
-                         reinterpret_cast<const uint32_t *>(fine_depth), fine_prim, reinterpret_cast<uint32_t *>(to_depth), to_prim, c->width);
-    };
-    with_samples(mode.n, [&](auto n) { with_depth_rule(mode.depth_rule, [&](auto rule) {
-      if (depth) launch(n, rule, std::false_type{}, depth, nullptr, s.d_depth.ptr, nullptr);
-      if (vis_prim) launch(n, rule, std::true_type{}, vis_depth, vis_prim, c->d_vis_depth.ptr, c->d_vis_prim.ptr);
-    }); });
+  // Everything in front of the shading: the frame's visibility, into the slot's buffers
+  auto visibility = [&] {
+    // option "static_records": the draws whose key has just repeated in this slot (plan_static_records; `h_draws`: the host's
+    // copy of `draws.d`) get the camera-independent part of their records first, once; k_geometry then stores the rest
+    for (const uint32_t d : fills) {
+      const uint32_t n = h_draws[d].n_instances * h_draws[d].tris_per_instance;
+      hipLaunchKernelGGL(k_record_static, dim3((n + kRecordStaticThreads - 1) / kRecordStaticThreads), dim3(kRecordStaticThreads), 0, sg,
+                         draws.d, d, s.d_attrs.ptr);
+      ++c->static_fills;
+    }
+    launch_geometry<TW, TH>(c, s, sg, ctr, fp, draws, c->n_prims, pv, view, s.d_heavy.ptr);
+    if (ev && c->timing == 1) (void)hipEventRecord(ev[1], sg);
+    stream_edge(sg, sr, s.ev_geom_done);
+    // k_raster writes the background pixels of `out`: if the frame still shading on the other stream writes the
+    // same buffer (single external output), raster has to wait for it; geometry above still overlapped
+    // (every frame still in flight, not just the previous one: with one stream per slot, or while the layout is being
+    //  switched, "after the previous frame" no longer implies "after the one before")
+    for (const FrameSlot &o : c->slots)
+      if (&o != &s && o.in_flight && final_out && o.out_used == final_out && o.stream_used != sr) (void)o.follow(sr);
+    if (fp.deferred)
+      hipLaunchKernelGGL(k_deferred_background, dim3(1), dim3(kBackgroundThreads), 0, sr, sp, d_lights, s.d_background.ptr, tables, fp.gbuffer_view);
+    RasterIO io;
+    io.rows = fp.heavy_rows + grid_y;
+    io.out = out, io.out8 = out8, io.vis_prim = vis_prim, io.vis_depth = vis_depth, io.depth_io = depth, io.host_flags = s.h_flags.ptr;
+    io.background = fp.deferred ? s.d_background.ptr : nullptr;
+    io.item_groups = (short_frame || merged) ? nullptr : s.d_item_groups.ptr, io.item_head = item_head, io.items = s.d_items.ptr;
+    io.lights = d_lights, io.num_lights = sp.num_lights, io.cooked = s.d_cooked.ptr, io.heavy = s.d_heavy.ptr;
+    // option "sky_keep": the stamp this frame's light tiles keep and mark under, if the frame may (k_raster writes `final_out` then)
+    io.sky_stamp = sky_stamp_for(c, s, mode, final_out);
+    io.sky_state = io.sky_stamp ? sky_words(s, (size_t)fp.tiles_x * fp.tiles_y) : nullptr;
+    launch_raster<TW, TH>(s, sr, ctr, fp, io);
+    if (merged)
+      with_samples(mode.n, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        if constexpr (N != 3)  // (refused_pair)
+          hipLaunchKernelGGL((k_sample_merge<TW, TH, N>), dim3((unsigned)fp.tiles_x, (unsigned)grid_y), dim3(kMergeThreads), 0, sr, fp, s.d_frag_count.ptr,
+                             s.d_frags.ptr, reinterpret_cast<typename SampleMap<N>::Word *>(s.d_sample_map.ptr), s.d_item_groups.ptr);
+      });
+    // k_shade's work list (64 fragments per item), built from the per-tile fragment counts as soon as k_raster is done; the
+    // same launch cooks the frame's light table
+    if (!short_frame)
+      hipLaunchKernelGGL((k_shade_items<TW, TH>), dim3((unsigned)((fp.tiles_x * grid_y + kItemsThreads - 1) / kItemsThreads)), dim3(kItemsThreads), 0, sr, fp, s.d_frag_count.ptr, s.d_item_groups.ptr, s.d_items.ptr,
+                         fp.tiles_x, grid_y, s.h_flags.ptr ? s.h_flags.ptr + kFlagItemCount : nullptr, d_lights, sp.num_lights, s.d_cooked.ptr,
+                         s.d_tile_count.ptr, ctr, s.d_heavy.ptr);
+    if (mode.depth_rule && (depth || vis_prim)) {
+      // k_resolve_depth, on k_raster's stream behind it and in front of the edge to the shading stream: the slot's ev_done, recorded
+      // behind shading, covers it in every stream layout.  The plain form for the overlay pass's depth, the PRIM form for the dump.
+      const dim3 grid((unsigned)((c->width + kResolveThreads - 1) / kResolveThreads), (unsigned)c->height);
+      auto launch = [&](auto n, auto rule, auto prim, const float *fine_depth, const uint32_t *fine_prim, float *to_depth, uint32_t *to_prim) {
+        hipLaunchKernelGGL((k_resolve_depth<decltype(n)::value, decltype(rule)::value, decltype(prim)::value>), grid, dim3(kResolveThreads), 0, sr,
+                           reinterpret_cast<const uint32_t *>(fine_depth), fine_prim, reinterpret_cast<uint32_t *>(to_depth), to_prim, c->width);
+      };
+      with_samples(mode.n, [&](auto n) { with_depth_rule(mode.depth_rule, [&](auto rule) {
+        if (depth) launch(n, rule, std::false_type{}, depth, nullptr, s.d_depth.ptr, nullptr);
+        if (vis_prim) launch(n, rule, std::true_type{}, vis_depth, vis_prim, c->d_vis_depth.ptr, c->d_vis_prim.ptr);
+      }); });
+    }
+  };
+  if (kept) {
+    // on the stream the slot's table was cooked on, in front of the edge to the shading stream, like the kernels it stands for
+    stream_edge(sg, sr, s.ev_geom_done);
+    if (cook) hipLaunchKernelGGL(k_cook_lights, dim3(1), dim3(kItemsThreads), 0, sr, d_lights, sp.num_lights, s.d_cooked.ptr);
+  } else {
+    visibility();
   }
   const uint32_t *item_count = short_frame ? item_head : s.d_items.ptr;   // where k_shade finds the number of items
   if (ev && c->timing == 1) (void)hipEventRecord(ev[2], sr);
@@ -1082,7 +1163,7 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
                            out8, ctr, ctr_done, item_groups, trailing...);
       }, first_item);
     };
-    uint32_t *groups = short_frame ? nullptr : s.d_item_groups.ptr;
+    uint32_t *groups = (short_frame || kept) ? nullptr : s.d_item_groups.ptr;
     if (mode.shadow || c->mip_levels > 1 || c->max_anisotropy > 1 || c->dump_surface) {
       // a valid shadow map: k_shade_shadow_casters, or k_shade_shadow, k_shade_shadow_faces, k_shade_shadow_pcf (never together with "mip_levels" >= 2: refused_shadow_pair); option "mip_levels":
       // k_shade_mip; option "max_anisotropy" / bbr_read_surface (the kernels' DUMP forms): k_shade_aniso.
@@ -1175,6 +1256,7 @@ int apply_growth(bbr_context *c, uint32_t overflow, uint32_t bin_need, uint32_t 
   ++c->retries;
   for (FrameSlot &s : c->slots) {
     s.forget_capacities();
+    s.forget_visibility();  // (option "view_keep": the lists were cut short, and are laid out for the old capacities)
     // tile counters may hold residue of references that did not fit
     if (s.d_tile_count.ptr) HIP_TRY(c, zero_fill_sync(s.d_tile_count.ptr, s.d_tile_count.cap * sizeof(uint32_t)));
   }
@@ -1589,8 +1671,13 @@ int submit_frame_body(bbr_context *c, int slot_index) {
   if (total > s.h_staging.cap) {
     HIP_TRY(c, s.h_staging.ensure(std::max<size_t>(total * 2, 1 << 16)));
     HIP_TRY(c, s.d_staging.ensure(s.h_staging.cap));
+    s.forget_visibility();  // (the item head of a short frame lived in the old one)
   }
   uint8_t *const h_staging = s.h_staging.ptr;
+  const int n_lights = std::min(std::max(c->frame_u.num_lights, 0), kMaxNumLights);
+  // option "view_keep": the slot's light table was cooked from the lights its last frame brought, which are still in the staging
+  const bool lights_cooked = s.vis.valid && n_lights <= std::min(std::max(s.frame_u.num_lights, 0), kMaxNumLights) &&
+                             std::memcmp(h_staging, c->frame_u.lights, sizeof(Light) * (size_t)n_lights) == 0;
   std::memcpy(h_staging, c->frame_u.lights, lights_bytes);
   // draw descriptors point into the device copy of the instance data made by the same transfer
   DeviceDraws draws;
@@ -1608,7 +1695,6 @@ int submit_frame_body(bbr_context *c, int slot_index) {
   if (carries_table) fill_caster_table(c->shadow, *reinterpret_cast<ShadowCasterTable *>(h_staging + table_offset));
   const ShadowCasterTable *d_table = carries_table ? reinterpret_cast<const ShadowCasterTable *>(s.d_staging.ptr + table_offset) : nullptr;
 
-  const int n_lights = std::min(std::max(c->frame_u.num_lights, 0), kMaxNumLights);
   const FrameStreams st = c->frame_streams(slot_index);
   for (hipEvent_t e : c->pending_waits) HIP_TRY(c, hipStreamWaitEvent(st.geom, e, 0));  // bbr_wait_event
   c->pending_waits.clear();
@@ -1632,15 +1718,47 @@ int submit_frame_body(bbr_context *c, int slot_index) {
   sp.exposure = c->frame_u.exposure;
   sp.num_lights = n_lights;
   float4 *out = !mode.frame32() ? nullptr : (c->ext_out ? reinterpret_cast<float4 *>(c->ext_out) : s.d_frame.ptr);
+  const FrameShape shape = frame_shape(c, s, mode, fp);
 
-  HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, h_staging, total, hipMemcpyHostToDevice, st.geom));
+  // Option "view_keep": is this frame's visibility what the slot's buffers hold?  `now`: everything k_geometry, k_raster and
+  // k_shade_items make theirs from beside the draws, and where they put it.  The draws are plan_static_records' business: every
+  // one found its key repeated and its static part written, so descriptors, places, instance blocks and resources are the
+  // last frame's.  The frame before must have been complete, and one that a frame may be kept behind (`keepable`); the
+  // five-event breakdown (option "timing" 1) asks for every stage.  Nothing here looks at the device.
+  VisKeep now;
+  now.pv = pv, now.view = view, now.fp = shape.fp, now.first_prims = draws.first_prims, now.n_draws = draws.n, now.n_prims = c->n_prims;
+  now.tile_mode = c->tile_mode, now.grid_y = shape.grid_y, now.short_frame = shape.short_frame, now.head_offset = head_offset;
+  const void *const buffers[] = {s.d_staging.ptr, s.d_tris.ptr, s.d_attrs.ptr, s.d_clip.ptr, s.d_broad.ptr, s.d_tile_count.ptr, s.d_bins.ptr,
+                                 s.d_frags.ptr, s.d_frag_count.ptr, s.d_items.ptr, s.d_cooked.ptr, s.d_heavy.ptr, s.d_item_groups.ptr,
+                                 s.d_block_stats.ptr, out};
+  static_assert(sizeof buffers == sizeof now.buffers, "VisKeep::buffers");
+  std::memcpy(now.buffers, buffers, sizeof buffers);
+  const bool keepable = keeps_own_image(c, s, mode, out) && !n_queued && !c->dump_records;
+  bool all_light = c->static_records && fills.empty();
+  for (uint32_t k = 0; all_light && k < draws.n; ++k) all_light = h_draws[k].flags == kDrawStaticPresent;
+  const bool kept = c->view_keep && keepable && all_light && c->timing != 1 && s.vis.valid && same_inputs(s.vis, now) &&
+                    !s.h_flags.ptr[kFlagOverflow];
+  if (kept) {
+    ++c->view_kept_frames;
+    s.vis.kept_last = true;
+  } else {
+    ++c->view_full_frames;
+    s.vis = now;
+    s.vis.valid = keepable;
+  }
+
+  // (a kept frame: up to the item head, which a short frame's shading counts its items by and the full frame's k_raster left)
+  HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, h_staging, kept ? head_offset : total, hipMemcpyHostToDevice, st.geom));
+  if (kept && carries_table)
+    HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr + table_offset, h_staging + table_offset, sizeof(ShadowCasterTable), hipMemcpyHostToDevice, st.geom));
   if (n_queued) {
     rc = launch_queued_passes(c, s, st.geom, draws, c->d_counters.ptr + s.ctr_index);
     if (rc) return rc;
   }
   with_tile(c->tile_mode, [&](auto tile) {
     constexpr int T = decltype(tile)::value;
-    launch_frame<T, T>(c, s, mode, st, ev, fp, pv, view, sp, d_lights, draws, out, d_item_head, h_draws, fills, d_table);
+    launch_frame<T, T>(c, s, mode, st, ev, shape, pv, view, sp, d_lights, draws, out, d_item_head, h_draws, fills, d_table, kept,
+                       kept && !lights_cooked && n_lights > 0);
   });
   HIP_TRY(c, hipGetLastError());
   s.in_flight = true;
@@ -1796,7 +1914,7 @@ int sync_and_fix(bbr_context *c, Counters *out_counters) {
 int rerender_with(bbr_context *c, bool bbr_context::*dump) {
   int rc = sync_and_fix(c, nullptr);
   if (rc) return rc;
-  forget_sky(c);  // (a diagnostic frame: rendered in full)
+  forget_image(c);  // (a diagnostic frame: rendered in full)
   c->*dump = true;
   rc = resubmit_last_frame(c);
   if (rc == BBR_OK) rc = sync_and_fix(c, nullptr);
@@ -1972,7 +2090,7 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
   if (int rc = refuse_without_depth_rule(c, "draw_overlays", "no depth resolve rule: option depth_resolve is 0")) return rc;
   int rc = sync_and_fix(c, nullptr);  // the overlay pass is synchronous: it is a debugging aid, not part of the hot path
   if (rc) return rc;
-  forget_sky(c);
+  forget_image(c);
   FrameSlot &fs = c->slots[c->last_slot];
   if (!fs.mode.depth) return fail(c, BBR_ERR_INVALID_ARGUMENT, "draw_overlays: the frame was rendered without option \"overlays\"");
   if (!fs.present.active) return fail(c, BBR_ERR_NOT_IN_FRAME, "draw_overlays: call bbr_present first (overlays go into the presented image)");
@@ -2383,7 +2501,7 @@ extern "C" int bbr_draw_ui(bbr_context *c, const bbr_ui_draw *draw) {
   FrameSlot &s = c->slots[c->last_slot];
   if (!s.present.active || !s.present.out)
     return fail(c, BBR_ERR_NOT_IN_FRAME, "draw_ui: call bbr_present first (the GUI goes into the presented image)");
-  forget_sky(c);
+  forget_image(c);
   // int fb_width = (int)(DisplaySize.x * FramebufferScale.x), as the back end computes it
   for (int k = 0; k < 2; ++k) {
     const float f = draw->display_size[k] * draw->framebuffer_scale[k];
@@ -2877,7 +2995,7 @@ int bbr_framebuffer_device_ptr(bbr_context *c, void **out_ptr, uint64_t *out_byt
   BBR_ON_DEVICE(c);
   if (!out_ptr) return fail(c, BBR_ERR_INVALID_ARGUMENT, "framebuffer_device_ptr: NULL");
   if (!c->have_frame || c->last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "framebuffer_device_ptr: nothing rendered");
-  forget_sky(c);  // (the caller may write through the pointer before the next frame)
+  forget_image(c);  // (the caller may write through the pointer before the next frame)
   *out_ptr = (void *)c->slots[c->last_slot].out_used;
   if (out_bytes)
     *out_bytes = c->ext_out ? c->ext_out_bytes : (uint64_t)c->width * std::max(c->height, c->shard_rows()) * 16;
@@ -2894,7 +3012,7 @@ int bbr_set_output_device_ptr(bbr_context *c, void *device_ptr, uint64_t bytes) 
   }
   c->ext_out = device_ptr;
   c->ext_out_bytes = device_ptr ? bytes : 0;
-  forget_sky(c);
+  forget_image(c);
   return BBR_OK;
 }
 
@@ -2942,7 +3060,7 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
   c->rank = rank;
   c->world = world;
   c->band_rows = band_rows;
-  forget_sky(c);
+  forget_image(c);
   for (FrameSlot &s : c->slots) {  // (a fine shard's padding rows, and their map words, are the zeros of a fresh buffer)
     s.d_fine.release();
     s.d_fine_depth.release();
@@ -2973,6 +3091,7 @@ static void drop_extent_buffers(bbr_context *c) {
     s.out_used = nullptr;
     s.in_flight = false;
     s.forget_extent();
+    s.forget_image();
   };
   for (FrameSlot &s : c->slots) drop_slot(s);
   drop_slot(c->ov);
@@ -2992,7 +3111,7 @@ int bbr_resize(bbr_context *c, int32_t width, int32_t height) {
   if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "resize: between begin_frame and end_frame");
   int rc = drain(c);
   if (rc) return rc;
-  forget_sky(c);
+  forget_image(c);
   if (width == c->width && height == c->height) return BBR_OK;
   c->width = width;
   c->height = height;
@@ -3269,6 +3388,13 @@ int bbr_static_record_counts(const bbr_context *c, uint64_t *out_fills, uint64_t
   return BBR_OK;
 }
 
+int bbr_view_keep_counts(const bbr_context *c, uint64_t *out_kept, uint64_t *out_full) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  if (out_kept) *out_kept = c->view_kept_frames;
+  if (out_full) *out_full = c->view_full_frames;
+  return BBR_OK;
+}
+
 int bbr_read_sky_tiles(bbr_context *c, uint8_t *out, uint32_t cap, uint32_t *out_count) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
@@ -3286,8 +3412,10 @@ int bbr_read_sky_tiles(bbr_context *c, uint8_t *out, uint32_t cap, uint32_t *out
   if (!stamp || !state || state != s.sky.state) return BBR_OK;
   std::vector<uint32_t> words(tiles);
   HIP_TRY(c, hipMemcpy(words.data(), state, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  // (a kept frame, option "view_keep": k_raster did not run, the words are the previous frame's, and nothing was stored into
+  //  any tile they call background)
   for (uint32_t t = 0; t < tiles; ++t)
-    if ((words[t] & ~kSkyKept) == stamp) out[t] = (words[t] & kSkyKept) ? BBR_SKY_TILE_KEPT : BBR_SKY_TILE_FILLED;
+    if ((words[t] & ~kSkyKept) == stamp) out[t] = ((words[t] & kSkyKept) || s.vis.kept_last) ? BBR_SKY_TILE_KEPT : BBR_SKY_TILE_FILLED;
   return BBR_OK;
 }
 
@@ -3384,7 +3512,16 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   }
   int rc = drain(c);
   if (rc) return rc;
-  forget_sky(c);  // (whatever the option is: options are not set between the frames of a steady run)
+  // "sky_keep": whatever the option is (options are not set between the frames of a steady run).  "view_keep": unless the option
+  // is one of those that change shading alone, or what a frame's submission decides by itself -- the GUI of the application
+  // restated here sets such between frames of one view.  Every other one may change the parameters, the mode or a buffer.
+  static const char *const kLeavesVisibility[] = {"timing", "timing_stride", "max_anisotropy", "mip_levels", "shadow_map", "shadow_filter",
+                                                  "static_records", "sky_keep", "view_keep", "push_mode"};
+  const bool leaves_visibility = std::find(std::begin(kLeavesVisibility), std::end(kLeavesVisibility), n) != std::end(kLeavesVisibility);
+  for (FrameSlot &s : c->slots) {
+    s.forget_sky();
+    if (!leaves_visibility) s.forget_visibility();
+  }
   if (n == "timing") {
     if (value < 0 || value > 2) return fail(c, BBR_ERR_INVALID_ARGUMENT, "timing: 0, 1 or 2");
     c->timing = (int)value;
@@ -3503,6 +3640,9 @@ int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   } else if (n == "sky_keep") {
     if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "sky_keep: 1 (a tile that stays background is filled once per frame slot) or 0 (every frame)");
     c->sky_keep = value == 1;
+  } else if (n == "view_keep") {
+    if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "view_keep: 1 (a frame whose view and draws repeat in its frame slot launches its shading only) or 0 (every frame runs every stage)");
+    c->view_keep = value == 1;
   } else if (n == "present_fused") {
     c->present_fused = value != 0;
   } else if (n == "overlays") {
@@ -3738,7 +3878,7 @@ int check_exchange(bbr_context *c, int form, const char *who) {
 }
 
 int unpack_whole(bbr_context *c, int form, const void *gathered, void *whole, hipStream_t st) {
-  forget_sky(c);  // (`whole` may be a slot's frame: the caller's pointer)
+  forget_image(c);  // (`whole` may be a slot's frame: the caller's pointer)
   kWireForms[form].unpack(c, gathered, whole, st);
   HIP_TRY(c, hipGetLastError());
   return BBR_OK;
@@ -4145,7 +4285,7 @@ int bbr_tone_map(bbr_context *c, int32_t enable, float exposure) {
   if (c->slots[c->last_slot].mode.fused) return fail(c, BBR_ERR_INVALID_ARGUMENT, "tone_map: no fp32 frame with option present_fused");
   float4 *frame = c->slots[c->last_slot].out_used;
   size_t n = c->shard_pixels();
-  forget_sky(c);  // (in place)
+  forget_image(c);  // (in place)
   // same stream as the frame's shade kernel: ordered after it
   hipLaunchKernelGGL(k_tone_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->slots[c->last_slot].stream_used, frame, n, enable, exposure);
   HIP_TRY(c, hipGetLastError());

@@ -591,6 +591,13 @@ class Renderer:
         self._check(self._L.bbr_static_record_counts(self._ctx, C.byref(fills), C.byref(light)))
         return {"fills": int(fills.value), "light_draws": int(light.value)}
 
+    def view_keep_counts(self):
+        """option view_keep since the context was created (host-side counters: no synchronisation): main frames kept (shading
+        only), main frames rendered in full"""
+        kept, full = C.c_uint64(), C.c_uint64()
+        self._check(self._L.bbr_view_keep_counts(self._ctx, C.byref(kept), C.byref(full)))
+        return {"kept": int(kept.value), "full": int(full.value)}
+
     def read_sky_tiles(self):
         """option sky_keep, the most recently submitted frame: a uint8 per tile, (tiles_y * tiles_x,) row-major -- 0 not a
         background tile (or a frame that could not keep), 1 background and filled, 2 background and kept.  Synchronises."""

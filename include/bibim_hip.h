@@ -200,6 +200,10 @@ int bbr_static_record_counts(const bbr_context *ctx, uint64_t *out_fills, uint64
  * that is rendered again here after a capacity growth reports the second rendering. */
 enum { BBR_SKY_TILE_NONE = 0, BBR_SKY_TILE_FILLED = 1, BBR_SKY_TILE_KEPT = 2 };
 int bbr_read_sky_tiles(bbr_context *ctx, uint8_t *out, uint32_t cap, uint32_t *out_count);
+/* Option "view_keep" since bbr_create, without synchronising or touching the GPU: main frames submitted that were kept (their
+ * visibility was in the frame slot: shading only) and main frames rendered in full (re-renders included).  Either pointer
+ * may be NULL. */
+int bbr_view_keep_counts(const bbr_context *ctx, uint64_t *out_kept, uint64_t *out_full);
 /* The host's side of the frame loop since bbr_host_timing_reset, kept without touching the GPU (steady_clock around the
  * submit): frames submitted by bbr_end_frame / bbr_replay_frame, nanoseconds spent inside those calls, and the part of
  * it the host was BLOCKED because the frame slot it wanted to reuse was still on the GPU (and in how many frames).  A
@@ -419,6 +423,22 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            good for what the call has always promised, the most recently submitted frame: a caller who
  *                            writes through it later, behind frames the library has rendered since, must set 0.
  *                            0: every frame stores every background pixel.  bbr_read_sky_tiles says what happened.
+ *   "view_keep" 0|1          1 (default): what the geometry and raster kernels produce -- triangles, records, bins, fragment
+ *                            lists, the shading work list, the background pixels -- depends on the view, the draws and the
+ *                            frame's geometry parameters only, not on lights, tone mapping, the normal-map switch, the
+ *                            filtering options or a shadow map.  A frame whose view matrices, draws (as "static_records"
+ *                            compares them: every draw on the light path, nothing to fill), capacities, parameters and
+ *                            buffers are those its frame slot rendered last finds all of that in the slot and launches
+ *                            its staging copy and its shading only (and a one-workgroup kernel for the light table when
+ *                            the lights changed).  Shading itself is never kept.  Same pixels, same read-backs, same
+ *                            bbr_get_stats.  Kept from the slot's third frame of a kind on; the conditions of "sky_keep" apply,
+ *                            and so does its list of calls that make every slot start over -- except that of the options only
+ *                            those that can change the parameters, the mode or a buffer do (not "max_anisotropy",
+ *                            "mip_levels", "shadow_map", "shadow_filter", "timing", "static_records", "sky_keep").  Not kept:
+ *                            a frame under "timing" 1 (every stage is timed), "static_records" 0, a frame that carries a
+ *                            queued shadow caster or follows one, a frame behind a capacity growth or an overflowed frame.
+ *                            bbr_read_sky_tiles reports a kept frame's background tiles as kept.  0: every frame runs every
+ *                            stage.  bbr_view_keep_counts counts both kinds.
  *   "ablate" bits           diagnostic builds only (make EXTRA=-DBB_ABLATE): skip parts of the pipeline */
 int bbr_set_option(bbr_context *ctx, const char *name, int64_t value);
 /* The stream layout in use (option "stream_layout"; 0 while only one frame is in flight).  *out_decided is always 1 and

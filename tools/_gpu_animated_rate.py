@@ -5,9 +5,13 @@ from the one the frame slot saw last), through the plain C API: bbr_begin_frame 
 --camera: the CAMERA moves instead (implies --still): sixteen views, a quarter of a degree of yaw and an eighth of pitch apart, one
 per frame in turn, so every frame's view differs from the one its slot saw last.  What option "sky_keep" keeps of such a
 sequence is printed as the share of background tiles kept, summed over the last frame of every slot.
+--every N (with --camera): the view changes with every N-th frame only, the frames between repeat it.
+--lights: the camera stands still and LIGHT 0 moves instead (implies --still): eight positions a millimetre apart, one per frame in
+turn -- what the application does between two inputs.  Every frame has its slot's view and draws and new shading inputs: what
+option "view_keep" keeps of a sequence is printed as the share of frames kept (bbr_view_keep_counts, the whole run).
 --forget: bbr_framebuffer_device_ptr in front of every frame: every frame slot forgets what option "sky_keep" remembers and no
 tile is ever kept (the call waits for nothing; on a tree without the option it only returns the pointer).
-usage: _gpu_animated_rate.py [--root TREE] [--reps 3] [--still] [--camera] [--forget] workload[:fif=3][:name=value ...] ..."""
+usage: _gpu_animated_rate.py [--root TREE] [--reps 3] [--still] [--camera [--every N]] [--lights] [--forget] workload[:fif=3][:name=value ...] ..."""
 import argparse, os, subprocess, sys
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,10 +50,17 @@ if %(camera)r:
         step = min(k, 16 - k)   # there and back
         views.append(scene.fill_uniforms(dataclasses.replace(cam, yaw=cam.yaw + 0.25 * step, pitch=cam.pitch + 0.125 * step), settings,
                                          cfg.width, cfg.height)[1])
+frame_blocks = []
+if %(lights)r:
+    for k in range(8):
+        f = fb.copy()
+        f[16:20].view(np.float32)[0] += 1e-3 * k   # lights[0].pos.x
+        frame_blocks.append(f)
 n = [0]
 def frame():
     b, g = sets[n[0] %% len(sets)]
-    if views: r.set_view_uniforms(views[n[0] %% len(views)])
+    if views: r.set_view_uniforms(views[(n[0] // %(every)d) %% len(views)])
+    if frame_blocks: r.set_frame_uniforms(frame_blocks[n[0] %% len(frame_blocks)])
     if %(forget)r and n[0]: r.framebuffer_device_ptr()   # (there is no frame in front of the first)
     n[0] += 1
     r.begin_frame(); r.draw(m_ball, material, b); r.draw(m_plane, material, g); r.end_frame()
@@ -73,6 +84,9 @@ if hasattr(r, "read_sky_tiles"):
         t = r.read_sky_tiles()
         kept, filled = kept + int((t == 2).sum()), filled + int((t == 1).sum())
     sky = "   background tiles kept: %%d of %%d" %% (kept, kept + filled)
+if hasattr(r, "view_keep_counts"):
+    c = r.view_keep_counts()
+    sky += "   frames kept: %%d of %%d" %% (c["kept"], c["kept"] + c["full"])
 print("%(tag)-40s us/frame " + " ".join("%%7.1f" %% x for x in out) + "   static records: %%s" %% (counts,) + sky, flush=True)
 scene.close(); r.close()
 '''
@@ -81,6 +95,8 @@ ap.add_argument("--root", default=HERE, help="the tree whose package and library
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--still", action="store_true")
 ap.add_argument("--camera", action="store_true")
+ap.add_argument("--every", type=int, default=1)
+ap.add_argument("--lights", action="store_true")
 ap.add_argument("--forget", action="store_true")
 ap.add_argument("cases", nargs="+")
 a = ap.parse_args()
@@ -96,9 +112,9 @@ for case in a.cases:
         else:
             opts.append((k, int(v)))
     frames = {"c2": 600, "c3": 300, "c5": 80}[workload]
-    tag = ("camera " if a.camera else "still " if a.still else "moving ") + ("forget " if a.forget else "") + case + (" [" + os.path.basename(os.path.abspath(a.root)) + "]" if a.root != HERE else "")
-    code = CHILD % dict(root=os.path.abspath(a.root), workload=workload, opts=opts, frames=frames, fif=fif, reps=a.reps, tag=tag, still=a.still or a.camera,
-                        camera=a.camera, forget=a.forget)
+    tag = ("lights " if a.lights else (f"camera/{a.every} " if a.every > 1 else "camera ") if a.camera else "still " if a.still else "moving ") + ("forget " if a.forget else "") + case + (" [" + os.path.basename(os.path.abspath(a.root)) + "]" if a.root != HERE else "")
+    code = CHILD % dict(root=os.path.abspath(a.root), workload=workload, opts=opts, frames=frames, fif=fif, reps=a.reps, tag=tag, still=a.still or a.camera or a.lights,
+                        camera=a.camera, forget=a.forget, lights=a.lights, every=max(a.every, 1))
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     sys.stdout.write(p.stdout)
     if p.returncode:
