@@ -10,6 +10,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <limits>
@@ -23,6 +24,11 @@
 #include <vector>
 
 #include "../../include/bibim_hip.h"
+#ifdef BB_ABLATE  // a diagnostic build (make EXTRA=-DBB_ABLATE)?  Asked here: bb_kernels.hip.h defines the macro's function form in every build
+constexpr bool kAblateBuild = true;
+#else
+constexpr bool kAblateBuild = false;
+#endif
 #include "bb_kernels.hip.h"
 #include "bb_own.h"
 #include "bb_pack.h"
@@ -69,11 +75,34 @@ struct RecordedDraw {
   int32_t mesh, material;
   uint32_t n_instances, first_instance, first_prim, tris_per_instance;
 };
-// A draw list on the device as k_geometry takes it: the descriptors (fill_draw_descs), how many, and first_prim of draws 1 .. 3
+// A draw list on the device as k_geometry takes it: the descriptors (fill_draw_descs), how many, first_prim of draws 1 .. 3, the primitives of all
 struct DeviceDraws {
   const DrawDesc *d = nullptr;
   uint32_t n = 0;
   FirstPrims first_prims = {};
+  uint32_t n_prims = 0;
+};
+
+// Where a transfer of draws keeps its parts, computed once from the counts: [lights | draw descriptors | instances | item head |
+// caster table] in a frame's staging (`frame`), [descriptors | instances] alone in a synchronous pass's.  The accessors give the
+// typed view of one part of a block laid out so: the pinned staging or its device copy.
+struct StagingLayout {
+  size_t draws_offset, inst_offset, inst_bytes, head_offset, table_offset, total;
+  // [item head: one zero word, 16-byte slot]: k_raster's tiles count a short frame's items through it.  [caster table]: once a queued pass has
+  // changed a slot: the context's table is written only while nothing is in flight, and the frames in flight differ in the generations they read
+  StagingLayout(size_t n_descs, size_t n_instances, bool frame = false, bool carries_table = false) {
+    draws_offset = frame ? sizeof(Light) * kMaxNumLights : 0;
+    inst_offset = draws_offset + ((sizeof(DrawDesc) * n_descs + 127) & ~(size_t)127);
+    inst_bytes = sizeof(InstanceBlock) * n_instances;
+    head_offset = (inst_offset + inst_bytes + 15) & ~(size_t)15;
+    table_offset = (head_offset + 16 + 255) & ~(size_t)255;
+    total = carries_table ? table_offset + sizeof(ShadowCasterTable) : frame ? head_offset + 16 : inst_offset + inst_bytes;
+  }
+  Light *lights(uint8_t *block) const { return reinterpret_cast<Light *>(block); }
+  DrawDesc *descs(uint8_t *block) const { return reinterpret_cast<DrawDesc *>(block + draws_offset); }
+  InstanceBlock *instances(uint8_t *block) const { return reinterpret_cast<InstanceBlock *>(block + inst_offset); }
+  uint32_t *item_head(uint8_t *block) const { return reinterpret_cast<uint32_t *>(block + head_offset); }
+  ShadowCasterTable *caster_table(uint8_t *block) const { return reinterpret_cast<ShadowCasterTable *>(block + table_offset); }
 };
 
 // Host -> device copies that kernels on the (non-blocking) context streams read right afterwards: completed on the
@@ -168,6 +197,18 @@ struct SkyKeep {
   const void *out = nullptr, *state = nullptr;  // the frame and the state buffer the stamp speaks of
   int32_t width = 0, height = 0, tiles_x = 0, tiles_y = 0, tile_mode = -1;
 };
+// What k_record_static, k_geometry, k_raster, k_sample_merge and k_shade_items make a main frame's visibility from, beside the
+// slot's buffers: stated here and nowhere else.  submit_frame_body builds one per frame (frame_shape), launch_visibility takes every
+// geometry-side value from it, and option "view_keep" compares it with the slot's (same_inputs): a new input is a new member.
+struct FrameInputs {
+  Mat4 pv = {}, view = {};
+  FrameParams fp = {};  // the final ones (capacities, heavy rows)
+  DeviceDraws draws;    // (their contents: plan_static_records' keys)
+  int tile_mode = -1, grid_y = 0;  // (the rows of k_raster's screen-ordered grid)
+  uint32_t max_items = 0;     // the item slots of the frame
+  bool short_frame = false;   // no k_shade_items launch: k_raster's tiles append their items through the head word
+  uint32_t *item_head = nullptr;  // that word, in the slot's device staging
+};
 // Option "view_keep": what a slot remembers about the visibility in its buffers.  While `valid`, the slot's geometry-side
 // buffers (tris, records, bins, every-tile list, clip slots, fragment lists and counts, items, item count) and the background
 // pixels of its d_frame are those of a complete frame rendered from exactly the inputs below: a frame with the same inputs
@@ -176,16 +217,8 @@ struct SkyKeep {
 struct VisKeep {
   bool valid = false;
   bool kept_last = false;  // the slot's last frame was a kept one (bbr_read_sky_tiles: it stored into no background tile)
-  // the inputs k_geometry, k_raster and k_shade_items had beside the draws (those: plan_static_records' keys)
-  Mat4 pv = {}, view = {};
-  FrameParams fp = {};  // the final ones (capacities, heavy rows)
-  FirstPrims first_prims = {};
-  uint32_t n_draws = 0, n_prims = 0;
-  int tile_mode = -1, grid_y = 0;
-  bool short_frame = false;
-  size_t head_offset = 0;  // of the item head in the staging
-  // the buffers that hold it
-  const void *buffers[15] = {};
+  FrameInputs in;          // what the visibility was made from beside the draws' contents (those: plan_static_records' keys)
+  std::array<const void *, 15> buffers = {};  // the buffers that hold it
 };
 
 // ... by the render or the output extent: bbr_resize and option "supersample" drop it (drop_extent_buffers)
@@ -283,14 +316,13 @@ struct FrameSlot : TileSized, ExtentSized {
   // the frame is on the GPU no queued pass writes that generation (pick_generation).
   int8_t shadow_gen[kMaxShadowCasters] = {-1, -1, -1, -1, -1, -1, -1, -1};
   bool had_pass = false;       // the frame in this slot carried a queued shadow pass (its overflow words include the pass's)
-  std::vector<CarriedPass> carried;  // ... these; and where the frame's draws are in d_staging, for rendering them again
-  size_t draws_offset = 0;
-  uint32_t n_draws = 0;
-  FirstPrims first_prims = {};
+  std::vector<CarriedPass> carried;  // ... these
+  // The draw list of the frame in this slot, in d_staging: valid only until the slot's next submission replaces the staging (until
+  // then the carried passes can be rendered again from it, settle_queued_passes; `d` is null once that staging was reallocated)
+  DeviceDraws draws;
   uint64_t serial = 0;         // the order of submission among the context's frames
   float4 *out_used = nullptr;  // where the frame in this slot wrote its pixels
   hipStream_t stream_used = nullptr;  // the stream its k_shade ran on
-  uint32_t n_prims = 0;
 
   // The flag words describe frames rendered with the old capacities (apply_growth) / the old extent (bbr_resize).  Two sets,
   // kept apart as they were; the heavy-tile count survives both (a list that does not fit its rows is merely not used).
@@ -691,14 +723,14 @@ bool keeps_own_image(const bbr_context *c, const FrameSlot &s, const FrameMode &
   return !c->ablate && !c->deferred && !c->ext_out && c->world == 1 && !c->dump_vis && !mode.fused && !mode.resolve && !mode.depth &&
          out && out == s.d_frame.ptr;
 }
-// Option "view_keep": the two frames' visibility is a function of the same inputs and lies in the same buffers (byte for byte:
-// the members compared have no padding)
-bool same_inputs(const VisKeep &a, const VisKeep &b) {
+// Option "view_keep": the same inputs, member by member (the structs have padding; those compared byte for byte have none)
+bool same_inputs(const FrameInputs &a, const FrameInputs &b) {
   static_assert(sizeof(FrameParams) == 27 * 4 && sizeof(Mat4) == 64 && sizeof(FirstPrims) == 4 * kInlineFirstPrims, "no padding");
-  return std::memcmp(&a.pv, &b.pv, sizeof a.pv) == 0 && std::memcmp(&a.view, &b.view, sizeof a.view) == 0 &&
-         std::memcmp(&a.fp, &b.fp, sizeof a.fp) == 0 && std::memcmp(&a.first_prims, &b.first_prims, sizeof a.first_prims) == 0 &&
-         a.n_draws == b.n_draws && a.n_prims == b.n_prims && a.tile_mode == b.tile_mode && a.grid_y == b.grid_y &&
-         a.short_frame == b.short_frame && a.head_offset == b.head_offset && std::memcmp(a.buffers, b.buffers, sizeof a.buffers) == 0;
+  auto same_bytes = [](const auto &x, const auto &y) { return std::memcmp(&x, &y, sizeof x) == 0; };
+  return same_bytes(a.pv, b.pv) && same_bytes(a.view, b.view) && same_bytes(a.fp, b.fp) && a.draws.d == b.draws.d &&
+         a.draws.n == b.draws.n && same_bytes(a.draws.first_prims, b.draws.first_prims) && a.draws.n_prims == b.draws.n_prims &&
+         a.tile_mode == b.tile_mode && a.grid_y == b.grid_y && a.max_items == b.max_items && a.short_frame == b.short_frame &&
+         a.item_head == b.item_head;
 }
 uint32_t sky_stamp_for(const bbr_context *c, FrameSlot &s, const FrameMode &mode, const float4 *out) {
   const uint32_t *state = sky_words(s, (size_t)c->tiles_x() * c->tiles_y());
@@ -971,9 +1003,9 @@ int upload_material_table(bbr_context *c) {
 // of their kernel.
 template <int TW, int TH, bool OVERLAY = false>
 void launch_geometry(const bbr_context *c, FrameSlot &s, hipStream_t st, Counters *ctr, const FrameParams &fp, const DeviceDraws &draws,
-                     uint32_t n_prims, const Mat4 &pv, const Mat4 &view, uint32_t *heavy = nullptr) {
-  if (!n_prims) return;
-  hipLaunchKernelGGL((k_geometry<TW, TH, OVERLAY>), dim3((n_prims + 255) / 256), dim3(256), 0, st, draws.d, draws.n, n_prims, draws.first_prims,
+                     const Mat4 &pv, const Mat4 &view, uint32_t *heavy = nullptr) {
+  if (!draws.n_prims) return;
+  hipLaunchKernelGGL((k_geometry<TW, TH, OVERLAY>), dim3((draws.n_prims + 255) / 256), dim3(256), 0, st, draws.d, draws.n, draws.n_prims, draws.first_prims,
                      s.d_tris.ptr, s.d_attrs.ptr, s.d_tile_count.ptr, s.d_bins.ptr, ctr, pv, view, fp, s.d_clip.ptr, s.d_broad.ptr,
                      c->d_materials.ptr, s.d_block_stats.ptr, heavy);
 }
@@ -1003,17 +1035,12 @@ void launch_raster(FrameSlot &s, hipStream_t st, Counters *ctr, const FrameParam
                      io.cooked, io.heavy, io.sky_state, io.sky_stamp);
 }
 
-// What a main frame's launches are sized by, decided once in front of them (frame_shape): the final parameters, the rows of
-// k_raster's screen-ordered grid, the item slots of the frame and whether it is a short one.
-struct FrameShape {
-  FrameParams fp;
-  int grid_y;
-  uint32_t max_items;
-  bool short_frame;
-};
-FrameShape frame_shape(const bbr_context *c, const FrameSlot &s, const FrameMode &mode, const FrameParams &fp_in) {
-  FrameShape z = {fp_in, 0, 0u, false};
-  FrameParams &fp = z.fp;
+// What a main frame's launches are sized by, decided once in front of them: the final parameters, the rows of k_raster's
+// screen-ordered grid, the item slots and whether it is a short frame.  The caller adds the view, the draws and the item head.
+FrameInputs frame_shape(const bbr_context *c, const FrameSlot &s, const FrameMode &mode, const FrameParams &fp_in) {
+  FrameInputs z;
+  z.tile_mode = c->tile_mode;
+  FrameParams &fp = z.fp = fp_in;
   // a rank without bands (more ranks than bands) still launches one row: its blocks fall off tiles_y and exit
   z.grid_y = std::max(1, c->world > 1 ? c->local_bands() * fp.band_tiles : fp.tiles_y);
   // A SHORT frame (at most option "no_tail_items" item slots: 1080p has 32 640) has no k_shade_items launch: k_raster's tiles
@@ -1036,99 +1063,113 @@ FrameShape frame_shape(const bbr_context *c, const FrameSlot &s, const FrameMode
   return z;
 }
 
-// `ev`: the frame's five timing events, or nullptr; `final_out`: the W x H fp32 frame (nullptr if the mode has none).
-// `kept` (option "view_keep", submit_frame_body decides): the slot's buffers hold this frame's visibility already: nothing is
-// launched in front of the shading but, where `cook` says the lights are not the ones the slot's table was cooked from, k_cook_lights.
+// What shading alone needs of a main frame beside the slot's buffers (k_raster stores the background through the same pointers)
+struct ShadeInputs {
+  ShadeParams sp = {};
+  const Light *lights = nullptr;             // the frame's, in the slot's device staging
+  const ShadowCasterTable *table = nullptr;  // the frame's own caster table in its staging, or nullptr: the context's
+  // Where the kernels write.  With a resolve `out` is the fine frame and k_resolve (at the end) writes `final_out`, the W x H fp32
+  // frame (nullptr if the mode has none); with fused presentation k_raster / k_shade write presented pixels into the slot's RGBA8
+  // image (`out8`), unless there is a resolve (a fine frame is fp32: a presented byte cannot be averaged, k_resolve presents)
+  float4 *final_out = nullptr, *out = nullptr;
+  uint32_t *out8 = nullptr;
+  const SrgbTables *tables = nullptr;
+  // option "view_keep" (submit_frame_body decides).  `kept`: the slot's buffers hold this frame's visibility already: nothing is
+  // launched in front of the shading but, where `cook` says the lights are not the ones the slot's table was cooked from, k_cook_lights.
+  bool kept = false, cook = false;
+};
+
+// Everything in front of the shading: the frame's visibility, from `in`, into the slot's buffers.  `ev`: as for launch_frame.
 template <int TW, int TH>
-void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const FrameStreams &st, const Event *ev, const FrameShape &shape,
-                  const Mat4 &pv, const Mat4 &view, const ShadeParams &sp, const Light *d_lights, const DeviceDraws &draws, float4 *final_out,
-                  uint32_t *d_item_head, const DrawDesc *h_draws, const std::vector<uint32_t> &fills, const ShadowCasterTable *frame_table,
-                  bool kept, bool cook) {
-  const FrameParams &fp = shape.fp;
-  // Where the kernels up to shading write.  With a resolve they render the fine frame and k_resolve (at the end) writes
-  // `final_out`; with fused presentation k_raster / k_shade write presented pixels into the slot's RGBA8 image, unless there is a
-  // resolve (a fine frame is fp32: a presented byte cannot be averaged, k_resolve presents)
-  const bool resolve = mode.resolve, merged = mode.merged;
-  float4 *out = resolve ? s.d_fine.ptr : final_out;
-  uint32_t *out8 = mode.shade_presents() ? s.d_present.ptr : nullptr;
-  const SrgbTables *tables = mode.shade_presents() ? c->d_srgb_tables.ptr : nullptr;
+void launch_visibility(bbr_context *c, FrameSlot &s, const FrameMode &mode, const FrameStreams &st, const Event *ev, const FrameInputs &in,
+                       const ShadeInputs &sh, const DrawDesc *h_draws, const std::vector<uint32_t> &fills) {
+  const FrameParams &fp = in.fp;
+  const bool resolve = mode.resolve, merged = mode.merged, short_frame = in.short_frame;
+  const int grid_y = in.grid_y;
+  const hipStream_t sg = st.geom, sr = st.raster;
+  Counters *const ctr = c->d_counters.ptr + s.ctr_index;
   // (with a resolve k_raster stores the depth, and dumps, at the render extent; k_resolve_depth, behind it, the output's)
   float *depth = !mode.depth ? nullptr : (resolve ? s.d_fine_depth.ptr : s.d_depth.ptr);
   uint32_t *vis_prim = !c->dump_vis ? nullptr : (resolve ? c->d_vis_fine_prim.ptr : c->d_vis_prim.ptr);
   float *vis_depth = !c->dump_vis ? nullptr : (resolve ? c->d_vis_fine_depth.ptr : c->d_vis_depth.ptr);
-  const int grid_y = shape.grid_y;
-  const uint32_t max_items = shape.max_items;
-  const bool short_frame = shape.short_frame;
+  // option "static_records": the draws whose key has just repeated in this slot (plan_static_records; `h_draws`: the host's
+  // copy of the descriptors) get the camera-independent part of their records first, once; k_geometry then stores the rest
+  for (const uint32_t d : fills) {
+    const uint32_t n = h_draws[d].n_instances * h_draws[d].tris_per_instance;
+    hipLaunchKernelGGL(k_record_static, dim3((n + kRecordStaticThreads - 1) / kRecordStaticThreads), dim3(kRecordStaticThreads), 0, sg,
+                       in.draws.d, d, s.d_attrs.ptr);
+    ++c->static_fills;
+  }
+  launch_geometry<TW, TH>(c, s, sg, ctr, fp, in.draws, in.pv, in.view, s.d_heavy.ptr);
+  if (ev && c->timing == 1) (void)hipEventRecord(ev[1], sg);
+  stream_edge(sg, sr, s.ev_geom_done);
+  // k_raster writes the background pixels of `out`: if the frame still shading on the other stream writes the
+  // same buffer (single external output), raster has to wait for it; geometry above still overlapped
+  // (every frame still in flight, not just the previous one: with one stream per slot, or while the layout is being
+  //  switched, "after the previous frame" no longer implies "after the one before")
+  for (const FrameSlot &o : c->slots)
+    if (&o != &s && o.in_flight && sh.final_out && o.out_used == sh.final_out && o.stream_used != sr) (void)o.follow(sr);
+  if (fp.deferred)
+    hipLaunchKernelGGL(k_deferred_background, dim3(1), dim3(kBackgroundThreads), 0, sr, sh.sp, sh.lights, s.d_background.ptr, sh.tables, fp.gbuffer_view);
+  RasterIO io;
+  io.rows = fp.heavy_rows + grid_y;
+  io.out = sh.out, io.out8 = sh.out8, io.vis_prim = vis_prim, io.vis_depth = vis_depth, io.depth_io = depth, io.host_flags = s.h_flags.ptr;
+  io.background = fp.deferred ? s.d_background.ptr : nullptr;
+  io.item_groups = (short_frame || merged) ? nullptr : s.d_item_groups.ptr, io.item_head = short_frame ? in.item_head : nullptr, io.items = s.d_items.ptr;
+  io.lights = sh.lights, io.num_lights = sh.sp.num_lights, io.cooked = s.d_cooked.ptr, io.heavy = s.d_heavy.ptr;
+  // option "sky_keep": the stamp this frame's light tiles keep and mark under, if the frame may (k_raster writes the fp32 frame then)
+  io.sky_stamp = sky_stamp_for(c, s, mode, sh.final_out);
+  io.sky_state = io.sky_stamp ? sky_words(s, (size_t)fp.tiles_x * fp.tiles_y) : nullptr;
+  launch_raster<TW, TH>(s, sr, ctr, fp, io);
+  if (merged)
+    with_samples(mode.n, [&](auto n) {
+      constexpr int N = decltype(n)::value;
+      if constexpr (N != 3)  // (refused_pair)
+        hipLaunchKernelGGL((k_sample_merge<TW, TH, N>), dim3((unsigned)fp.tiles_x, (unsigned)grid_y), dim3(kMergeThreads), 0, sr, fp, s.d_frag_count.ptr,
+                           s.d_frags.ptr, reinterpret_cast<typename SampleMap<N>::Word *>(s.d_sample_map.ptr), s.d_item_groups.ptr);
+    });
+  // k_shade's work list (64 fragments per item), built from the per-tile fragment counts as soon as k_raster is done; the
+  // same launch cooks the frame's light table
+  if (!short_frame)
+    hipLaunchKernelGGL((k_shade_items<TW, TH>), dim3((unsigned)((fp.tiles_x * grid_y + kItemsThreads - 1) / kItemsThreads)), dim3(kItemsThreads), 0, sr, fp, s.d_frag_count.ptr, s.d_item_groups.ptr, s.d_items.ptr,
+                       fp.tiles_x, grid_y, s.h_flags.ptr ? s.h_flags.ptr + kFlagItemCount : nullptr, sh.lights, sh.sp.num_lights, s.d_cooked.ptr,
+                       s.d_tile_count.ptr, ctr, s.d_heavy.ptr);
+  if (mode.depth_rule && (depth || vis_prim)) {
+    // k_resolve_depth, on k_raster's stream behind it and in front of the edge to the shading stream: the slot's ev_done, recorded
+    // behind shading, covers it in every stream layout.  The plain form for the overlay pass's depth, the PRIM form for the dump.
+    const dim3 grid((unsigned)((c->width + kResolveThreads - 1) / kResolveThreads), (unsigned)c->height);
+    auto launch = [&](auto n, auto rule, auto prim, const float *fine_depth, const uint32_t *fine_prim, float *to_depth, uint32_t *to_prim) {
+      hipLaunchKernelGGL((k_resolve_depth<decltype(n)::value, decltype(rule)::value, decltype(prim)::value>), grid, dim3(kResolveThreads), 0, sr,
+                         reinterpret_cast<const uint32_t *>(fine_depth), fine_prim, reinterpret_cast<uint32_t *>(to_depth), to_prim, c->width);
+    };
+    with_samples(mode.n, [&](auto n) { with_depth_rule(mode.depth_rule, [&](auto rule) {
+      if (depth) launch(n, rule, std::false_type{}, depth, nullptr, s.d_depth.ptr, nullptr);
+      if (vis_prim) launch(n, rule, std::true_type{}, vis_depth, vis_prim, c->d_vis_depth.ptr, c->d_vis_prim.ptr);
+    }); });
+  }
+}
+
+// The launches of a main frame.  `ev`: the frame's five timing events, or nullptr.
+template <int TW, int TH>
+void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const FrameStreams &st, const Event *ev, const FrameInputs &in,
+                  const ShadeInputs &sh, const DrawDesc *h_draws, const std::vector<uint32_t> &fills) {
+  const FrameParams &fp = in.fp;
+  const ShadeParams &sp = sh.sp;
+  const Light *d_lights = sh.lights;
+  const bool resolve = mode.resolve, merged = mode.merged, kept = sh.kept, short_frame = in.short_frame;
+  const uint32_t max_items = in.max_items;
   const hipStream_t sg = st.geom, sr = st.raster, ss = st.shade;
   // (a kept frame: the slot's block is zero already and its retired copy holds the full frame's statistics, which stay: the
   //  frame's shading retires the spare block, and finds the chunk totals cleared)
   const int ctr_block = kept ? bbr_context::kSpareCounterBlock : s.ctr_index;
   Counters *ctr = c->d_counters.ptr + ctr_block, *ctr_done = c->d_counters_done.ptr + ctr_block;
-  uint32_t *item_head = short_frame ? d_item_head : nullptr;
-  // Everything in front of the shading: the frame's visibility, into the slot's buffers
-  auto visibility = [&] {
-    // option "static_records": the draws whose key has just repeated in this slot (plan_static_records; `h_draws`: the host's
-    // copy of `draws.d`) get the camera-independent part of their records first, once; k_geometry then stores the rest
-    for (const uint32_t d : fills) {
-      const uint32_t n = h_draws[d].n_instances * h_draws[d].tris_per_instance;
-      hipLaunchKernelGGL(k_record_static, dim3((n + kRecordStaticThreads - 1) / kRecordStaticThreads), dim3(kRecordStaticThreads), 0, sg,
-                         draws.d, d, s.d_attrs.ptr);
-      ++c->static_fills;
-    }
-    launch_geometry<TW, TH>(c, s, sg, ctr, fp, draws, c->n_prims, pv, view, s.d_heavy.ptr);
-    if (ev && c->timing == 1) (void)hipEventRecord(ev[1], sg);
-    stream_edge(sg, sr, s.ev_geom_done);
-    // k_raster writes the background pixels of `out`: if the frame still shading on the other stream writes the
-    // same buffer (single external output), raster has to wait for it; geometry above still overlapped
-    // (every frame still in flight, not just the previous one: with one stream per slot, or while the layout is being
-    //  switched, "after the previous frame" no longer implies "after the one before")
-    for (const FrameSlot &o : c->slots)
-      if (&o != &s && o.in_flight && final_out && o.out_used == final_out && o.stream_used != sr) (void)o.follow(sr);
-    if (fp.deferred)
-      hipLaunchKernelGGL(k_deferred_background, dim3(1), dim3(kBackgroundThreads), 0, sr, sp, d_lights, s.d_background.ptr, tables, fp.gbuffer_view);
-    RasterIO io;
-    io.rows = fp.heavy_rows + grid_y;
-    io.out = out, io.out8 = out8, io.vis_prim = vis_prim, io.vis_depth = vis_depth, io.depth_io = depth, io.host_flags = s.h_flags.ptr;
-    io.background = fp.deferred ? s.d_background.ptr : nullptr;
-    io.item_groups = (short_frame || merged) ? nullptr : s.d_item_groups.ptr, io.item_head = item_head, io.items = s.d_items.ptr;
-    io.lights = d_lights, io.num_lights = sp.num_lights, io.cooked = s.d_cooked.ptr, io.heavy = s.d_heavy.ptr;
-    // option "sky_keep": the stamp this frame's light tiles keep and mark under, if the frame may (k_raster writes `final_out` then)
-    io.sky_stamp = sky_stamp_for(c, s, mode, final_out);
-    io.sky_state = io.sky_stamp ? sky_words(s, (size_t)fp.tiles_x * fp.tiles_y) : nullptr;
-    launch_raster<TW, TH>(s, sr, ctr, fp, io);
-    if (merged)
-      with_samples(mode.n, [&](auto n) {
-        constexpr int N = decltype(n)::value;
-        if constexpr (N != 3)  // (refused_pair)
-          hipLaunchKernelGGL((k_sample_merge<TW, TH, N>), dim3((unsigned)fp.tiles_x, (unsigned)grid_y), dim3(kMergeThreads), 0, sr, fp, s.d_frag_count.ptr,
-                             s.d_frags.ptr, reinterpret_cast<typename SampleMap<N>::Word *>(s.d_sample_map.ptr), s.d_item_groups.ptr);
-      });
-    // k_shade's work list (64 fragments per item), built from the per-tile fragment counts as soon as k_raster is done; the
-    // same launch cooks the frame's light table
-    if (!short_frame)
-      hipLaunchKernelGGL((k_shade_items<TW, TH>), dim3((unsigned)((fp.tiles_x * grid_y + kItemsThreads - 1) / kItemsThreads)), dim3(kItemsThreads), 0, sr, fp, s.d_frag_count.ptr, s.d_item_groups.ptr, s.d_items.ptr,
-                         fp.tiles_x, grid_y, s.h_flags.ptr ? s.h_flags.ptr + kFlagItemCount : nullptr, d_lights, sp.num_lights, s.d_cooked.ptr,
-                         s.d_tile_count.ptr, ctr, s.d_heavy.ptr);
-    if (mode.depth_rule && (depth || vis_prim)) {
-      // k_resolve_depth, on k_raster's stream behind it and in front of the edge to the shading stream: the slot's ev_done, recorded
-      // behind shading, covers it in every stream layout.  The plain form for the overlay pass's depth, the PRIM form for the dump.
-      const dim3 grid((unsigned)((c->width + kResolveThreads - 1) / kResolveThreads), (unsigned)c->height);
-      auto launch = [&](auto n, auto rule, auto prim, const float *fine_depth, const uint32_t *fine_prim, float *to_depth, uint32_t *to_prim) {
-        hipLaunchKernelGGL((k_resolve_depth<decltype(n)::value, decltype(rule)::value, decltype(prim)::value>), grid, dim3(kResolveThreads), 0, sr,
-                           reinterpret_cast<const uint32_t *>(fine_depth), fine_prim, reinterpret_cast<uint32_t *>(to_depth), to_prim, c->width);
-      };
-      with_samples(mode.n, [&](auto n) { with_depth_rule(mode.depth_rule, [&](auto rule) {
-        if (depth) launch(n, rule, std::false_type{}, depth, nullptr, s.d_depth.ptr, nullptr);
-        if (vis_prim) launch(n, rule, std::true_type{}, vis_depth, vis_prim, c->d_vis_depth.ptr, c->d_vis_prim.ptr);
-      }); });
-    }
-  };
+  uint32_t *item_head = short_frame ? in.item_head : nullptr;
   if (kept) {
     // on the stream the slot's table was cooked on, in front of the edge to the shading stream, like the kernels it stands for
     stream_edge(sg, sr, s.ev_geom_done);
-    if (cook) hipLaunchKernelGGL(k_cook_lights, dim3(1), dim3(kItemsThreads), 0, sr, d_lights, sp.num_lights, s.d_cooked.ptr);
+    if (sh.cook) hipLaunchKernelGGL(k_cook_lights, dim3(1), dim3(kItemsThreads), 0, sr, d_lights, sp.num_lights, s.d_cooked.ptr);
   } else {
-    visibility();
+    launch_visibility<TW, TH>(c, s, mode, st, ev, in, sh, h_draws, fills);
   }
   const uint32_t *item_count = short_frame ? item_head : s.d_items.ptr;   // where k_shade finds the number of items
   if (ev && c->timing == 1) (void)hipEventRecord(ev[2], sr);
@@ -1159,8 +1200,8 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
     auto launch = [&](auto kernel, uint32_t wgs, hipStream_t stream, auto first_item, uint32_t *item_groups, auto... trailing) {
       std::apply([&](auto... first) {
         hipLaunchKernelGGL(kernel, dim3(wgs), dim3(kShadeThreads), 0, stream, s.d_items.ptr, item_count, first..., s.d_frags.ptr,
-                           s.d_frag_count.ptr, s.d_attrs.ptr, s.d_clip.ptr, fp, sp, s.d_cooked.ptr, c->d_materials.ptr, out, gbuf, tables,
-                           out8, ctr, ctr_done, item_groups, trailing...);
+                           s.d_frag_count.ptr, s.d_attrs.ptr, s.d_clip.ptr, fp, sp, s.d_cooked.ptr, c->d_materials.ptr, sh.out, gbuf, sh.tables,
+                           sh.out8, ctr, ctr_done, item_groups, trailing...);
       }, first_item);
     };
     uint32_t *groups = (short_frame || kept) ? nullptr : s.d_item_groups.ptr;
@@ -1174,7 +1215,7 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
         constexpr bool DUMP = decltype(dump)::value;
         if (mode.shadow_casters) {
           ShadowCastersArgs sa = {};
-          sa.table = frame_table ? frame_table : c->shadow.d_table.ptr, sa.lights = d_lights, sa.num_lights = sp.num_lights, sa.radius = mode.shadow_filter;
+          sa.table = sh.table ? sh.table : c->shadow.d_table.ptr, sa.lights = d_lights, sa.num_lights = sp.num_lights, sa.radius = mode.shadow_filter;
           sa.side = c->shadow_map, sa.half = 0.5f * (float)c->shadow_map, sa.dump_slot = c->dump_shadow_slot;
           if (DUMP && c->dump_shadow_mask) sa.mask = c->d_shadow_mask.ptr, sa.face = c->d_shadow_face.ptr, sa.taps = c->d_shadow_taps.ptr;
           launch(k_shade_shadow_casters<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface, sa);
@@ -1202,7 +1243,7 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
     with_bool(c->all_packed, [&](auto packed) { launch(k_shade<TW, TH, DEFERRED, PRESENT, false, !decltype(packed)::value>, main_wgs, ss, std::make_tuple(0u), groups); });
     if (tail) stream_edge(sr, ss, s.ev_tail_done);  // (nothing else went onto sr since the tail launch)
   };
-  with_bool(fp.deferred, [&](auto deferred) { with_bool(out8 != nullptr, [&](auto present) { shade(deferred, present); }); });
+  with_bool(fp.deferred, [&](auto deferred) { with_bool(sh.out8 != nullptr, [&](auto present) { shade(deferred, present); }); });
   if (resolve) {
     // k_resolve, right behind k_shade (and the tail launch, whose edge `ss` already follows) on the frame's own stream.  The
     // shading interval ends in front of it, the frame's interval behind it (the stop event of its own pair).
@@ -1218,11 +1259,11 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
       constexpr int N = decltype(n)::value;
       constexpr bool PRESENT = decltype(present)::value;
       if constexpr (!decltype(merged_c)::value)
-        hipLaunchKernelGGL((k_resolve<N, PRESENT>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out, final_out, present_to, c->width,
+        hipLaunchKernelGGL((k_resolve<N, PRESENT>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)sh.out, sh.final_out, present_to, c->width,
                            present_tables, sp.tone_enable, sp.exposure);
       else if constexpr (N != 3)  // (refused_pair)
-        hipLaunchKernelGGL((k_resolve_merged<N, PRESENT>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)out,
-                           reinterpret_cast<const typename SampleMap<N>::Word *>(s.d_sample_map.ptr), final_out, present_to, c->width,
+        hipLaunchKernelGGL((k_resolve_merged<N, PRESENT>), grid, dim3(kResolveThreads), 0, ss, (const float4 *)sh.out,
+                           reinterpret_cast<const typename SampleMap<N>::Word *>(s.d_sample_map.ptr), sh.final_out, present_to, c->width,
                            present_tables, sp.tone_enable, sp.exposure);
     }); }); });
     if (ev) (void)c->resolve_ring.end(ss);
@@ -1265,9 +1306,12 @@ int apply_growth(bbr_context *c, uint32_t overflow, uint32_t bin_need, uint32_t 
   return BBR_OK;
 }
 
-// The recorded frame's draw descriptors as k_geometry reads them, into `hd`; `d_inst_base` is where the device copy of the
-// instance data will be.  Returns how many there are: empty draws would break the first_prim search and get none.
-uint32_t fill_draw_descs(const bbr_context *c, DrawDesc *hd, const InstanceBlock *d_inst_base, FirstPrims &first_prims) {
+// The recorded frame's draw descriptors as k_geometry reads them, into the host block `host` laid out as `lay`, for its device copy
+// `device` (where the instance data will be too).  Returns the list: empty draws would break the first_prim search and get none.
+DeviceDraws fill_draw_descs(const bbr_context *c, const StagingLayout &lay, uint8_t *host, uint8_t *device) {
+  DrawDesc *const hd = lay.descs(host);
+  const InstanceBlock *const d_inst_base = lay.instances(device);
+  FirstPrims first_prims = {};
   uint32_t k = 0;
   for (const RecordedDraw &rd : c->draws) {
     if (!rd.n_instances || !rd.tris_per_instance) continue;
@@ -1288,20 +1332,18 @@ uint32_t fill_draw_descs(const bbr_context *c, DrawDesc *hd, const InstanceBlock
     hd[k++] = d;
   }
   for (uint32_t q = std::max(k, 1u); q <= (uint32_t)kInlineFirstPrims; ++q) first_prims.v[q - 1] = 0xFFFFFFFFu;
-  return k;
+  return {lay.descs(device), k, first_prims, c->n_prims};
 }
 
 // The recorded draws for a synchronous pass: [draw descriptors | instances] in `staging`, as the frame's staging holds them,
 // uploaded at once.  (A frame's own transfer is another job: pinned, asynchronous, one copy with its lights, head and table.)
 int upload_recorded_draws(bbr_context *c, DeviceBuffer<uint8_t> &staging, DeviceDraws &up) {
-  const size_t draws_bytes = (sizeof(DrawDesc) * std::max<size_t>(c->draws.size(), 1) + 127) & ~(size_t)127;
-  const size_t inst_bytes = sizeof(InstanceBlock) * c->host_instances.size();
-  HIP_TRY(c, staging.ensure(draws_bytes + std::max<size_t>(inst_bytes, 1)));
-  std::vector<DrawDesc> draws(std::max<size_t>(c->draws.size(), 1));
-  up.d = reinterpret_cast<const DrawDesc *>(staging.ptr);
-  up.n = fill_draw_descs(c, draws.data(), reinterpret_cast<const InstanceBlock *>(staging.ptr + draws_bytes), up.first_prims);
-  if (up.n) HIP_TRY(c, upload_sync(staging.ptr, draws.data(), up.n * sizeof(DrawDesc)));
-  if (inst_bytes) HIP_TRY(c, upload_sync(staging.ptr + draws_bytes, c->host_instances.data(), inst_bytes));
+  const StagingLayout lay(std::max<size_t>(c->draws.size(), 1), c->host_instances.size());
+  HIP_TRY(c, staging.ensure(std::max<size_t>(lay.total, lay.inst_offset + 1)));
+  std::vector<uint8_t> descs(lay.inst_offset);
+  up = fill_draw_descs(c, lay, descs.data(), staging.ptr);
+  if (up.n) HIP_TRY(c, upload_sync(lay.descs(staging.ptr), descs.data(), up.n * sizeof(DrawDesc)));
+  if (lay.inst_bytes) HIP_TRY(c, upload_sync(lay.instances(staging.ptr), c->host_instances.data(), lay.inst_bytes));
   return BBR_OK;
 }
 
@@ -1312,11 +1354,12 @@ int upload_recorded_draws(bbr_context *c, DeviceBuffer<uint8_t> &staging, Device
 //   key new or changed    the full path; the key is remembered
 //   key repeated          k_record_static is queued for the draw (`fills`), then the light path
 //   key repeated, filled  the light path
-// so a draw whose instances move every frame never causes a fill and pays the comparison only.  `old_staging` is the slot's
-// pinned staging as its previous frame left it, `d_staging` its device copy; the instance blocks of `hd` are still in
-// c->host_instances, `d_inst_base` is where their device copy begins.  Called before the staging is overwritten.
-void plan_static_records(bbr_context *c, FrameSlot &s, DrawDesc *hd, uint32_t n_draws, const uint8_t *old_staging, const uint8_t *d_staging,
-                         const InstanceBlock *d_inst_base, std::vector<uint32_t> &fills) {
+// so a draw whose instances move every frame never causes a fill and pays the comparison only.  The descriptors are in the slot's
+// pinned staging, laid out as `lay`, whose instance part is still as the slot's previous frame left it; the instance blocks of
+// this frame are still in c->host_instances.  Called before that part is overwritten.
+void plan_static_records(bbr_context *c, FrameSlot &s, const StagingLayout &lay, uint32_t n_draws, std::vector<uint32_t> &fills) {
+  DrawDesc *const hd = lay.descs(s.h_staging.ptr);
+  const InstanceBlock *const old_inst = lay.instances(s.h_staging.ptr), *const d_inst_base = lay.instances(s.d_staging.ptr);
   StaticRecords &sr = s.statics;
   if (!c->static_records || c->dump_records || c->ablate) return sr.forget();
   if (sr.epoch != c->resource_epoch || sr.attrs_cap != s.d_attrs.cap || sr.staging_cap != s.h_staging.cap) sr.forget();
@@ -1327,10 +1370,9 @@ void plan_static_records(bbr_context *c, FrameSlot &s, DrawDesc *hd, uint32_t n_
   for (uint32_t k = 0; k < n_draws; ++k) {
     StaticRecords::Draw &e = sr.draws[k];
     const size_t inst_bytes = sizeof(InstanceBlock) * hd[k].n_instances;
-    // (equal descriptors point at the same place of the device staging: the previous frame's blocks are at that offset of the pinned one)
+    // (equal descriptors point at the same place of the device staging: the previous frame's blocks are at that place of the pinned one)
     const bool same = std::memcmp(&e.key, &hd[k], sizeof(DrawDesc)) == 0 &&
-                      std::memcmp(old_staging + (reinterpret_cast<const uint8_t *>(hd[k].instances) - d_staging),
-                                  c->host_instances.data() + (hd[k].instances - d_inst_base), inst_bytes) == 0;
+                      std::memcmp(old_inst + (hd[k].instances - d_inst_base), c->host_instances.data() + (hd[k].instances - d_inst_base), inst_bytes) == 0;
     if (!same) {
       e.key = hd[k];
       e.filled = false;
@@ -1365,8 +1407,8 @@ FrameParams shadow_pass_params(const bbr_context *c) {
 
 // The faces of `q` on `st`, back to back through the pass slot: the frame's own k_geometry and k_raster, face f counting in
 // `ctr[f]` (zero before), the depth of every texel into the f-th S x S map at `map`.
-void launch_shadow_faces(bbr_context *c, hipStream_t st, const FrameParams &fp, const DeviceDraws &draws, uint32_t n_prims,
-                         const CasterRequest &q, Counters *ctr, float *map) {
+void launch_shadow_faces(bbr_context *c, hipStream_t st, const FrameParams &fp, const DeviceDraws &draws, const CasterRequest &q,
+                         Counters *ctr, float *map) {
   FrameSlot &s = c->shadow.pass;
   const size_t texels = (size_t)c->shadow_map * (size_t)c->shadow_map;
   with_tile(c->tile_mode, [&](auto tile) {
@@ -1375,7 +1417,7 @@ void launch_shadow_faces(bbr_context *c, hipStream_t st, const FrameParams &fp, 
       RasterIO io;  // the depth into the map; the background's presented words into the sink
       io.rows = fp.tiles_y, io.depth_io = map + (size_t)f * texels, io.out8 = c->shadow.d_sink.ptr;
       // gl_Position = (L.proj * L.view) * posWorld: the forward order, whatever "render_pass" is
-      launch_geometry<T, T>(c, s, st, ctr + f, fp, draws, n_prims, proj_view(q.view[f]), q.view[f].view);
+      launch_geometry<T, T>(c, s, st, ctr + f, fp, draws, proj_view(q.view[f]), q.view[f].view);
       launch_raster<T, T>(s, st, ctr + f, fp, io);
     }
   });
@@ -1474,15 +1516,15 @@ int launch_queued_passes(bbr_context *c, FrameSlot &into, hipStream_t st, const 
   const size_t texels = (size_t)c->shadow_map * (size_t)c->shadow_map;
   auto &z = sh.pass_sized;
   const bool fits = p.d_tile_count.ptr && p.d_bins.ptr && p.d_broad.ptr && p.d_clip.ptr && sh.d_sink.cap >= texels &&
-                    sh.d_ctr.cap >= (size_t)kShadowPassBlocks && c->n_prims <= z.n_prims && c->bin_cap == z.bin_cap &&
+                    sh.d_ctr.cap >= (size_t)kShadowPassBlocks && draws.n_prims <= z.n_prims && c->bin_cap == z.bin_cap &&
                     c->broad_cap == z.broad_cap && c->clip_cap == z.clip_cap && c->tile_mode == z.tile_mode;
   if (!fits) {
     // the pass slot may be reallocated: the pass on the GPU leaves it first (the host waits for that one event)
     if (sh.pass_queued) HIP_TRY(c, hipEventSynchronize(sh.ev_pass));
     HIP_TRY(c, sh.d_sink.ensure(texels));
     HIP_TRY(c, sh.d_ctr.ensure(kShadowPassBlocks, true));
-    if (int rc = ensure_pass_buffers(c, p, c->n_prims, (size_t)fp.tiles_x * fp.tiles_y)) return rc;
-    z.n_prims = std::max(z.n_prims, c->n_prims), z.bin_cap = c->bin_cap, z.broad_cap = c->broad_cap, z.clip_cap = c->clip_cap;
+    if (int rc = ensure_pass_buffers(c, p, draws.n_prims, (size_t)fp.tiles_x * fp.tiles_y)) return rc;
+    z.n_prims = std::max(z.n_prims, draws.n_prims), z.bin_cap = c->bin_cap, z.broad_cap = c->broad_cap, z.clip_cap = c->clip_cap;
     z.tile_mode = c->tile_mode;
   }
   HIP_TRY(c, sh.ev_pass.ensure(hipEventDisableTiming));
@@ -1492,7 +1534,7 @@ int launch_queued_passes(bbr_context *c, FrameSlot &into, hipStream_t st, const 
     const CasterRequest &q = sh.queued[k];
     if (!q.on) continue;
     ShadowSlot &cs = sh.slot[k];
-    launch_shadow_faces(c, st, fp, draws, c->n_prims, q, sh.d_ctr.ptr + block, cs.generation(cs.cur).ptr);
+    launch_shadow_faces(c, st, fp, draws, q, sh.d_ctr.ptr + block, cs.generation(cs.cur).ptr);
     block += (uint32_t)q.faces;
     ++c->shadow_queue_passes;
   }
@@ -1539,15 +1581,15 @@ int run_pass_sync(bbr_context *c, FrameSlot &s, uint32_t n_prims, Params &&param
   return fail(c, BBR_ERR_CAPACITY, who + ": " + kStillExceeded);
 }
 
-// The faces of one caster, synchronously, through the pass slot: `q.faces` maps of S x S at `map` from the `n_prims` primitives
-// of `draws`, a counter block per face (run_pass_sync: an overflow in any face renders ALL faces again).  Shared by the
+// The faces of one caster, synchronously, through the pass slot: `q.faces` maps of S x S at `map` from the primitives of
+// `draws`, a counter block per face (run_pass_sync: an overflow in any face renders ALL faces again).  Shared by the
 // synchronous call (render_shadow_faces) and by the repair of a queued pass that overflowed (settle_queued_passes).
-int render_faces_sync(bbr_context *c, const std::string &who, float *map, const CasterRequest &q, const DeviceDraws &draws, uint32_t n_prims) {
+int render_faces_sync(bbr_context *c, const std::string &who, float *map, const CasterRequest &q, const DeviceDraws &draws) {
   ShadowOwned &sh = c->shadow;
   HIP_TRY(c, sh.d_sink.ensure((size_t)c->shadow_map * (size_t)c->shadow_map));
   HIP_TRY(c, sh.d_ctr.ensure(kMaxShadowFaces, true));
-  return run_pass_sync(c, sh.pass, n_prims, [&] { return shadow_pass_params(c); }, sh.d_ctr.ptr, q.faces, who,
-                       [&](const FrameParams &fp, hipStream_t st) { launch_shadow_faces(c, st, fp, draws, n_prims, q, sh.d_ctr.ptr, map); });
+  return run_pass_sync(c, sh.pass, draws.n_prims, [&] { return shadow_pass_params(c); }, sh.d_ctr.ptr, q.faces, who,
+                       [&](const FrameParams &fp, hipStream_t st) { launch_shadow_faces(c, st, fp, draws, q, sh.d_ctr.ptr, map); });
 }
 
 // A queued pass that overflowed is the frame's overflow (k_shadow_pass_retire), and the frame's repair -- growing, rendering the
@@ -1585,34 +1627,12 @@ int settle_queued_passes(bbr_context *c, bool *repaired) {
     FrameSlot &o = *order[i];
     for (const CarriedPass &cp : o.carried) {
       ShadowSlot &cs = c->shadow.slot[cp.caster];
-      if (!cs.valid || cs.stamp != cp.stamp || !o.d_staging.ptr) continue;  // (replaced or dropped since)
-      const DeviceDraws draws = {reinterpret_cast<const DrawDesc *>(o.d_staging.ptr + o.draws_offset), o.n_draws, o.first_prims};
-      rc = render_faces_sync(c, "queued shadow pass", cs.generation(cs.cur).ptr, cp.q, draws, o.n_prims);
+      if (!cs.valid || cs.stamp != cp.stamp || !o.d_staging.ptr || !o.draws.d) continue;  // (replaced or dropped since; no staging)
+      rc = render_faces_sync(c, "queued shadow pass", cs.generation(cs.cur).ptr, cp.q, o.draws);
       if (rc) return rc;
     }
   }
   return BBR_OK;
-}
-
-int submit_frame_body(bbr_context *c, int slot_index);
-
-// Queue the recorded frame into slot `slot_index`.  Asynchronous.  A submission that fails leaves the caster slots, and the
-// recorded frame's queued entries, as they were: the queued casters become the context's in front of steps that can fail
-// (apply_queued_casters), and a caster whose maps were never rendered must not stay in use.
-int submit_frame_into(bbr_context *c, int slot_index) {
-  struct {
-    CasterPublished slot;
-    bool queued;
-  } kept[kMaxShadowCasters];
-  ShadowOwned &sh = c->shadow;
-  const bool table_stale = sh.table_stale;
-  for (int k = 0; k < kMaxShadowCasters; ++k) kept[k] = {sh.slot[k].published(), sh.queued[k].on};
-  const int rc = submit_frame_body(c, slot_index);
-  if (rc != BBR_OK) {
-    for (int k = 0; k < kMaxShadowCasters; ++k) sh.slot[k].published() = kept[k].slot, sh.queued[k].on = kept[k].queued;
-    sh.table_stale = table_stale;
-  }
-  return rc;
 }
 
 int submit_frame_body(bbr_context *c, int slot_index) {
@@ -1656,44 +1676,29 @@ int submit_frame_body(bbr_context *c, int slot_index) {
   if (rc) return rc;
   if (!n_queued) s.h_flags.ptr[kFlagPassBroadNeed] = s.h_flags.ptr[kFlagPassClipNeed] = 0u;  // (k_shadow_pass_retire's words)
 
-  // staging layout: [lights (100 * 64 B)] [draw descriptors] [instances]
-  size_t lights_bytes = sizeof(Light) * kMaxNumLights;
-  size_t draws_bytes = (sizeof(DrawDesc) * c->draws.size() + 127) & ~(size_t)127;
-  size_t inst_bytes = sizeof(InstanceBlock) * c->host_instances.size();
-  // ... [item head: one zero word, 16-byte slot] -- k_raster's tiles count a short frame's items through it (launch_frame)
-  const size_t head_offset = (lights_bytes + draws_bytes + inst_bytes + 15) & ~(size_t)15;
-  size_t total = head_offset + 16;
-  // ... [the caster table] -- k_shade_shadow_casters' own copy, once a queued pass has changed a slot: the context's table is
-  // written only while nothing is in flight, and the frames in flight differ in the generations they read
+  // the staging: [lights (100 * 64 B)] [draw descriptors] [instances] [item head] [caster table] (StagingLayout)
   const bool carries_table = mode.shadow_casters && c->shadow.table_stale;
-  const size_t table_offset = (total + 255) & ~(size_t)255;
-  if (carries_table) total = table_offset + sizeof(ShadowCasterTable);
-  if (total > s.h_staging.cap) {
-    HIP_TRY(c, s.h_staging.ensure(std::max<size_t>(total * 2, 1 << 16)));
+  const StagingLayout lay(c->draws.size(), c->host_instances.size(), true, carries_table);
+  if (lay.total > s.h_staging.cap) {
+    HIP_TRY(c, s.h_staging.ensure(std::max<size_t>(lay.total * 2, 1 << 16)));
     HIP_TRY(c, s.d_staging.ensure(s.h_staging.cap));
     s.forget_visibility();  // (the item head of a short frame lived in the old one)
+    s.draws.d = nullptr;    // (... and the descriptors of the slot's last frame)
   }
-  uint8_t *const h_staging = s.h_staging.ptr;
+  uint8_t *const h_staging = s.h_staging.ptr, *const d_staging = s.d_staging.ptr;
   const int n_lights = std::min(std::max(c->frame_u.num_lights, 0), kMaxNumLights);
   // option "view_keep": the slot's light table was cooked from the lights its last frame brought, which are still in the staging
   const bool lights_cooked = s.vis.valid && n_lights <= std::min(std::max(s.frame_u.num_lights, 0), kMaxNumLights) &&
-                             std::memcmp(h_staging, c->frame_u.lights, sizeof(Light) * (size_t)n_lights) == 0;
-  std::memcpy(h_staging, c->frame_u.lights, lights_bytes);
+                             std::memcmp(lay.lights(h_staging), c->frame_u.lights, sizeof(Light) * (size_t)n_lights) == 0;
+  std::memcpy(lay.lights(h_staging), c->frame_u.lights, sizeof(Light) * kMaxNumLights);
   // draw descriptors point into the device copy of the instance data made by the same transfer
-  DeviceDraws draws;
-  draws.d = reinterpret_cast<const DrawDesc *>(s.d_staging.ptr + lights_bytes);
-  draws.n = fill_draw_descs(c, reinterpret_cast<DrawDesc *>(h_staging + lights_bytes),
-                            reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + lights_bytes + draws_bytes), draws.first_prims);
+  const DeviceDraws draws = fill_draw_descs(c, lay, h_staging, d_staging);
   // (while the staging still holds the instance blocks of the slot's previous frame: a repeated descriptor has left them in place)
-  const DrawDesc *const h_draws = reinterpret_cast<const DrawDesc *>(h_staging + lights_bytes);
   std::vector<uint32_t> fills;  // draws k_record_static runs for in front of this frame's k_geometry
-  plan_static_records(c, s, reinterpret_cast<DrawDesc *>(h_staging + lights_bytes), draws.n, h_staging, s.d_staging.ptr,
-                      reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + lights_bytes + draws_bytes), fills);
-  if (inst_bytes) std::memcpy(h_staging + lights_bytes + draws_bytes, c->host_instances.data(), inst_bytes);
-  std::memset(h_staging + head_offset, 0, 16);
-  uint32_t *d_item_head = reinterpret_cast<uint32_t *>(s.d_staging.ptr + head_offset);
-  if (carries_table) fill_caster_table(c->shadow, *reinterpret_cast<ShadowCasterTable *>(h_staging + table_offset));
-  const ShadowCasterTable *d_table = carries_table ? reinterpret_cast<const ShadowCasterTable *>(s.d_staging.ptr + table_offset) : nullptr;
+  plan_static_records(c, s, lay, draws.n, fills);
+  if (lay.inst_bytes) std::memcpy(lay.instances(h_staging), c->host_instances.data(), lay.inst_bytes);
+  std::memset(lay.item_head(h_staging), 0, 16);
+  if (carries_table) fill_caster_table(c->shadow, *lay.caster_table(h_staging));
 
   const FrameStreams st = c->frame_streams(slot_index);
   for (hipEvent_t e : c->pending_waits) HIP_TRY(c, hipStreamWaitEvent(st.geom, e, 0));  // bbr_wait_event
@@ -1706,59 +1711,52 @@ int submit_frame_body(bbr_context *c, int slot_index) {
     if (c->timing == 1) HIP_TRY(c, hipEventRecord(ev[0], st.geom));
   }
   s.ctr_index = slot_index;
-  const Light *d_lights = reinterpret_cast<const Light *>(s.d_staging.ptr);
-  FrameParams fp = make_params(c);
+  FrameInputs in = frame_shape(c, s, mode, make_params(c));
   // forward: gl_Position = (P*V) * posWorld; deferred: P * (V * posWorld) -- the kernel gets P and V separately
-  Mat4 pv = c->deferred ? c->view_u.proj : proj_view(c->view_u);
-  const Mat4 view = c->view_u.view;
-  ShadeParams sp = {};
-  std::memcpy(sp.view_pos, c->view_u.view_pos, sizeof sp.view_pos);
-  sp.enable_normal_map = c->view_u.enable_normal_map;
-  sp.tone_enable = c->frame_u.enable_tone_mapping;
-  sp.exposure = c->frame_u.exposure;
-  sp.num_lights = n_lights;
-  float4 *out = !mode.frame32() ? nullptr : (c->ext_out ? reinterpret_cast<float4 *>(c->ext_out) : s.d_frame.ptr);
-  const FrameShape shape = frame_shape(c, s, mode, fp);
+  in.pv = c->deferred ? c->view_u.proj : proj_view(c->view_u);
+  in.view = c->view_u.view, in.draws = draws, in.item_head = lay.item_head(d_staging);
+  ShadeInputs sh;
+  std::memcpy(sh.sp.view_pos, c->view_u.view_pos, sizeof sh.sp.view_pos);
+  sh.sp.enable_normal_map = c->view_u.enable_normal_map;
+  sh.sp.tone_enable = c->frame_u.enable_tone_mapping, sh.sp.exposure = c->frame_u.exposure;
+  sh.sp.num_lights = n_lights, sh.lights = lay.lights(d_staging);
+  float4 *const out = sh.final_out = !mode.frame32() ? nullptr : (c->ext_out ? static_cast<float4 *>(c->ext_out) : s.d_frame.ptr);
+  sh.out = mode.resolve ? s.d_fine.ptr : out;
+  sh.out8 = mode.shade_presents() ? s.d_present.ptr : nullptr, sh.tables = mode.shade_presents() ? c->d_srgb_tables.ptr : nullptr;
+  sh.table = carries_table ? lay.caster_table(d_staging) : nullptr;
 
-  // Option "view_keep": is this frame's visibility what the slot's buffers hold?  `now`: everything k_geometry, k_raster and
-  // k_shade_items make theirs from beside the draws, and where they put it.  The draws are plan_static_records' business: every
-  // one found its key repeated and its static part written, so descriptors, places, instance blocks and resources are the
-  // last frame's.  The frame before must have been complete, and one that a frame may be kept behind (`keepable`); the
-  // five-event breakdown (option "timing" 1) asks for every stage.  Nothing here looks at the device.
-  VisKeep now;
-  now.pv = pv, now.view = view, now.fp = shape.fp, now.first_prims = draws.first_prims, now.n_draws = draws.n, now.n_prims = c->n_prims;
-  now.tile_mode = c->tile_mode, now.grid_y = shape.grid_y, now.short_frame = shape.short_frame, now.head_offset = head_offset;
-  const void *const buffers[] = {s.d_staging.ptr, s.d_tris.ptr, s.d_attrs.ptr, s.d_clip.ptr, s.d_broad.ptr, s.d_tile_count.ptr, s.d_bins.ptr,
+  // Option "view_keep": is this frame's visibility what the slot's buffers hold?  `in`: what the kernels make it from beside the draws'
+  // contents; `buffers`: where they put it.  The contents are plan_static_records' business: every draw found its key repeated and its
+  // static part written, so descriptors, places, instance blocks and resources are the last frame's.  The frame before must have been complete, and one
+  // that a frame may be kept behind (`keepable`); the five-event breakdown (option "timing" 1) asks for every stage.  Nothing here looks at the device.
+  const decltype(s.vis.buffers) buffers = {d_staging, s.d_tris.ptr, s.d_attrs.ptr, s.d_clip.ptr, s.d_broad.ptr, s.d_tile_count.ptr, s.d_bins.ptr,
                                  s.d_frags.ptr, s.d_frag_count.ptr, s.d_items.ptr, s.d_cooked.ptr, s.d_heavy.ptr, s.d_item_groups.ptr,
                                  s.d_block_stats.ptr, out};
-  static_assert(sizeof buffers == sizeof now.buffers, "VisKeep::buffers");
-  std::memcpy(now.buffers, buffers, sizeof buffers);
   const bool keepable = keeps_own_image(c, s, mode, out) && !n_queued && !c->dump_records;
   bool all_light = c->static_records && fills.empty();
-  for (uint32_t k = 0; all_light && k < draws.n; ++k) all_light = h_draws[k].flags == kDrawStaticPresent;
-  const bool kept = c->view_keep && keepable && all_light && c->timing != 1 && s.vis.valid && same_inputs(s.vis, now) &&
-                    !s.h_flags.ptr[kFlagOverflow];
+  for (uint32_t k = 0; all_light && k < draws.n; ++k) all_light = lay.descs(h_staging)[k].flags == kDrawStaticPresent;
+  const bool kept = sh.kept = c->view_keep && keepable && all_light && c->timing != 1 && s.vis.valid && same_inputs(s.vis.in, in) &&
+                              buffers == s.vis.buffers && !s.h_flags.ptr[kFlagOverflow];
+  sh.cook = kept && !lights_cooked && n_lights > 0;
   if (kept) {
     ++c->view_kept_frames;
     s.vis.kept_last = true;
   } else {
     ++c->view_full_frames;
-    s.vis = now;
-    s.vis.valid = keepable;
+    s.vis = {keepable, false, in, buffers};
   }
 
   // (a kept frame: up to the item head, which a short frame's shading counts its items by and the full frame's k_raster left)
-  HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr, h_staging, kept ? head_offset : total, hipMemcpyHostToDevice, st.geom));
+  HIP_TRY(c, hipMemcpyAsync(d_staging, h_staging, kept ? lay.head_offset : lay.total, hipMemcpyHostToDevice, st.geom));
   if (kept && carries_table)
-    HIP_TRY(c, hipMemcpyAsync(s.d_staging.ptr + table_offset, h_staging + table_offset, sizeof(ShadowCasterTable), hipMemcpyHostToDevice, st.geom));
+    HIP_TRY(c, hipMemcpyAsync(lay.caster_table(d_staging), lay.caster_table(h_staging), sizeof(ShadowCasterTable), hipMemcpyHostToDevice, st.geom));
   if (n_queued) {
     rc = launch_queued_passes(c, s, st.geom, draws, c->d_counters.ptr + s.ctr_index);
     if (rc) return rc;
   }
-  with_tile(c->tile_mode, [&](auto tile) {
+  with_tile(in.tile_mode, [&](auto tile) {
     constexpr int T = decltype(tile)::value;
-    launch_frame<T, T>(c, s, mode, st, ev, shape, pv, view, sp, d_lights, draws, out, d_item_head, h_draws, fills, d_table, kept,
-                       kept && !lights_cooked && n_lights > 0);
+    launch_frame<T, T>(c, s, mode, st, ev, in, sh, lay.descs(h_staging), fills);
   });
   HIP_TRY(c, hipGetLastError());
   s.in_flight = true;
@@ -1767,9 +1765,7 @@ int submit_frame_body(bbr_context *c, int slot_index) {
   s.carried.clear();
   for (int k = 0; n_queued && k < kMaxShadowCasters; ++k)
     if (c->shadow.queued[k].on) s.carried.push_back({k, c->shadow.slot[k].stamp, c->shadow.queued[k]});
-  s.draws_offset = lights_bytes;
-  s.n_draws = draws.n;
-  s.first_prims = draws.first_prims;
+  s.draws = draws;
   s.serial = ++c->frame_serial;
   s.mode = mode;
   s.present.active = mode.fused;  // fused presentation: the frame IS the presented image
@@ -1781,9 +1777,27 @@ int submit_frame_body(bbr_context *c, int slot_index) {
   s.frame_u = c->frame_u;
   s.view_u = c->view_u;
   s.out_used = out;
-  s.n_prims = c->n_prims;
   c->last_slot = slot_index;
   return BBR_OK;
+}
+
+// Queue the recorded frame into slot `slot_index`.  Asynchronous.  A submission that fails leaves the caster slots, and the
+// recorded frame's queued entries, as they were: the queued casters become the context's in front of steps that can fail
+// (apply_queued_casters), and a caster whose maps were never rendered must not stay in use.
+int submit_frame_into(bbr_context *c, int slot_index) {
+  struct {
+    CasterPublished slot;
+    bool queued;
+  } kept[kMaxShadowCasters];
+  ShadowOwned &sh = c->shadow;
+  const bool table_stale = sh.table_stale;
+  for (int k = 0; k < kMaxShadowCasters; ++k) kept[k] = {sh.slot[k].published(), sh.queued[k].on};
+  const int rc = submit_frame_body(c, slot_index);
+  if (rc != BBR_OK) {
+    for (int k = 0; k < kMaxShadowCasters; ++k) sh.slot[k].published() = kept[k].slot, sh.queued[k].on = kept[k].queued;
+    sh.table_stale = table_stale;
+  }
+  return rc;
 }
 
 int ensure_srgb_tables(bbr_context *c) {
@@ -2139,9 +2153,9 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
   if (!n_prims) return BBR_OK;
   std::vector<DrawDesc> draws;
   FrameSlot &s = c->ov;
-  const size_t draws_bytes = 2 * sizeof(DrawDesc), inst_bytes = inst.size() * sizeof(InstanceBlock);
-  HIP_TRY(c, s.d_staging.ensure(draws_bytes + inst_bytes));
-  const InstanceBlock *d_inst = reinterpret_cast<const InstanceBlock *>(s.d_staging.ptr + draws_bytes);
+  const StagingLayout lay(2, inst.size());  // (as a synchronous pass keeps the recorded draws)
+  HIP_TRY(c, s.d_staging.ensure(lay.total));
+  const InstanceBlock *d_inst = lay.instances(s.d_staging.ptr);
   if (n_lights) {
     DrawDesc d = {};
     d.vertices = c->marker_mesh.d_vertices.ptr; d.indices = c->marker_mesh.d_indices.ptr; d.instances = d_inst;
@@ -2154,9 +2168,9 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
     d.n_instances = 1; d.tris_per_instance = gizmo_tris; d.first_prim = marker_tris * (uint32_t)n_lights; d.material = 2u;  // program: gizmo
     draws.push_back(d);
   }
-  HIP_TRY(c, upload_sync(s.d_staging.ptr, draws.data(), draws.size() * sizeof(DrawDesc)));
-  HIP_TRY(c, upload_sync(s.d_staging.ptr + draws_bytes, inst.data(), inst_bytes));
-  DeviceDraws ov = {reinterpret_cast<const DrawDesc *>(s.d_staging.ptr), (uint32_t)draws.size(), {{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}}};
+  HIP_TRY(c, upload_sync(lay.descs(s.d_staging.ptr), draws.data(), draws.size() * sizeof(DrawDesc)));
+  HIP_TRY(c, upload_sync(lay.instances(s.d_staging.ptr), inst.data(), lay.inst_bytes));
+  DeviceDraws ov = {lay.descs(s.d_staging.ptr), (uint32_t)draws.size(), {{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}}, n_prims};
   for (size_t q = 1; q < draws.size() && q <= (size_t)kInlineFirstPrims; ++q) ov.first_prims.v[q - 1] = draws[q].first_prim;
 
   auto params = [&] {
@@ -2180,7 +2194,7 @@ extern "C" int bbr_draw_overlays(bbr_context *c, int32_t gizmo_extent) {
     io.rows = fp.tiles_y, io.depth_io = fs.d_depth.ptr;
     with_tile(c->tile_mode, [&](auto tile) {
       constexpr int T = decltype(tile)::value;
-      launch_geometry<T, T, true>(c, s, st, ctr, fp, ov, n_prims, ident, ident);
+      launch_geometry<T, T, true>(c, s, st, ctr, fp, ov, ident, ident);
       launch_raster<T, T, true>(s, st, ctr, fp, io);
       constexpr int kChunks = T * T / kShadeThreads;
       hipLaunchKernelGGL((k_shade_overlay<T, T>), dim3(fp.tiles_x * kChunks, fp.tiles_y), dim3(kShadeThreads), 0, st, fp,
@@ -2284,7 +2298,7 @@ static int render_shadow_faces(bbr_context *c, const std::string &who, int32_t c
   DeviceDraws draws;
   rc = upload_recorded_draws(c, sh.pass.d_staging, draws);
   if (rc) return rc;
-  rc = render_faces_sync(c, who, cs.d_map.ptr, q, draws, c->n_prims);
+  rc = render_faces_sync(c, who, cs.d_map.ptr, q, draws);
   if (rc) return rc;
   for (DeviceBuffer<float> &g : cs.d_more) g.release();  // (nothing is in flight: the generations of earlier queued passes go)
   publish(c, cs, 0, q);  // (the synchronous pass writes generation 0)
@@ -3495,189 +3509,174 @@ int bbr_resolve_timing(bbr_context *c, uint32_t *out_launches, float *out_avg_ms
   return pair_ring_timing(c, &bbr_context::resolve_ring, "resolve_timing", out_launches, out_avg_ms);
 }
 
+}  // extern "C" (the option rows name their members through templates)
+
+// ---- bbr_set_option: one row per name (kOptions), which states everything the call does with it ----
+namespace {
+// A plain option: the checked value goes into a member
+template <auto MEMBER> int store(bbr_context *c, int64_t value) {
+  c->*MEMBER = static_cast<std::decay_t<decltype(c->*MEMBER)>>(value);
+  return BBR_OK;
+}
+int set_timing(bbr_context *c, int64_t value) {
+  c->timing = (int)value;
+  if (int rc = value ? ensure_timing_ring(c, frame_mode(c).resolve) : BBR_OK) return rc;
+  c->ring_frames = 0;  // (see bbr_timing_reset on what each of the three reset sites resets)
+  c->present_ring.reset();
+  c->resolve_ring.reset();
+  c->timing_tick = 0;
+  return BBR_OK;
+}
+int set_tile_mode(bbr_context *c, int64_t value) {
+  if (c->world > 1 && c->band_rows % (value == 0 ? 64 : 32))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "tile_mode: band_rows not a multiple of the new tile height");
+  c->tile_mode = (int)value;
+  for (FrameSlot &s : c->slots) drop<TileSized>(s);
+  drop<TileSized>(c->ov);
+  drop<TileSized>(c->shadow.pass);  // (the map itself has no tiles: it stays)
+  return BBR_OK;
+}
+// a capacity and the buffer it sizes, which goes: of every frame slot and (`OVERLAY_TOO`) of the overlay pass
+template <auto CAP, auto BUFFER, bool OVERLAY_TOO> int set_capacity(bbr_context *c, int64_t value) {
+  c->*CAP = (uint32_t)value;
+  for (FrameSlot &s : c->slots) (s.*BUFFER).release();
+  if (OVERLAY_TOO) (c->ov.*BUFFER).release();
+  return BBR_OK;
+}
+int set_mip_levels(bbr_context *c, int64_t value) {
+  if (refused_shadow_pair(value, c->shadow_map))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "mip_levels: >= 2 is not available with option shadow_map > 0 (k_shade_shadow has no trilinear form)");
+  // every chain is built for the option's value: drop them all, then build the new ones of every live material
+  for (Material &m : c->materials) free_chain(m);
+  c->mip_levels = (int)value;
+  c->materials_dirty = true;
+  ++c->resource_epoch;
+  if (value == 1) c->d_mip_tables.release();
+  for (Material &m : c->materials)
+    if (int rc = (m.alive && value > 1) ? build_chain(c, m) : BBR_OK) {
+      for (Material &q : c->materials) free_chain(q);
+      c->mip_levels = 1;
+      return rc;
+    }
+  return BBR_OK;
+}
+// like a resize of the render extent; the output extent, and with it a caller's output buffer, stay
+int set_supersample(bbr_context *c, int64_t value) {
+  if (int rc = check_render_extent(c, "supersample", value, c->width, c->height)) return rc;
+  if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: between begin_frame and end_frame");
+  if (refused_pair(value, c->sample_shading))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: 3 is not available with option sample_shading 0 (a 3 x 3 block straddles the tiles)");
+  if ((int)value == c->supersample) return BBR_OK;
+  // (the one step that can fail comes first: a refused call leaves the context as it was)
+  if (int rc = c->timing ? ensure_timing_ring(c, value > 1) : BBR_OK) return rc;
+  c->supersample = (int)value;
+  drop_extent_buffers(c);
+  c->ring_frames = 0;  // (a frame's interval ends behind its k_resolve: the ring holds frames of one kind)
+  c->resolve_ring.reset();
+  c->timing_tick = 0;
+  return BBR_OK;
+}
+// no extent changes: only the sample maps go, and there is no current frame (its samples were of the other kind)
+int set_sample_shading(bbr_context *c, int64_t value) {
+  if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "sample_shading: between begin_frame and end_frame");
+  if (refused_pair(c->supersample, value))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "sample_shading: 0 is not available with option supersample 3 (a 3 x 3 block straddles the tiles)");
+  if ((int)value == c->sample_shading) return BBR_OK;
+  for (FrameSlot &s : c->slots) s.d_sample_map.release();
+  forget_current_frame(c);
+  return store<&bbr_context::sample_shading>(c, value);
+}
+// VkResolveModeFlagBits; AVERAGE (2) has no winner.  At n = 1 the value is only stored; with n >= 2 the current frame was
+// rendered under the other rule (or kept no depth at all): there is none any more, and the fine depth goes
+int set_depth_resolve(bbr_context *c, int64_t value) {
+  if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "depth_resolve: between begin_frame and end_frame");
+  if ((int)value != c->depth_resolve && c->supersample > 1) {
+    for (FrameSlot &s : c->slots) s.d_fine_depth.release();
+    forget_current_frame(c);
+  }
+  return store<&bbr_context::depth_resolve>(c, value);
+}
+// the side of the map; a change drops the map and its pass buffers (the context is drained): frames are unshadowed again
+// until bbr_render_shadow_map has rendered the new one
+int set_shadow_map(bbr_context *c, int64_t value) {
+  if (refused_shadow_pair(c->mip_levels, value))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "shadow_map: > 0 is not available with option mip_levels >= 2 (k_shade_shadow has no trilinear form)");
+  if ((int)value != c->shadow_map) c->shadow = ShadowOwned();
+  return store<&bbr_context::shadow_map>(c, value);
+}
+// the radius of the box of compares; stored at any "shadow_map", and the map stays.  The current frame was shaded under the
+// other rule: there is none any more
+int set_shadow_filter(bbr_context *c, int64_t value) {
+  if ((int)value != c->shadow_filter) forget_current_frame(c);
+  return store<&bbr_context::shadow_filter>(c, value);
+}
+
+// What bbr_set_option does with a name.  Its checks in order: NULL name; a row that does not wait is checked and applied at once; every
+// other call (an unknown name too) waits for the GPU and makes the slots forget; then the row's range; then `apply`, which holds the refusals that
+// depend on another option or on the recorded frame.  (So a value refused behind the wait has made the slots forget: one full frame, no pixel.)
+struct OptionRow {
+  const char *name;
+  int64_t lo, hi;       // the accepted values ...
+  uint32_t only;        // ... non-zero: of lo .. hi only those whose bit is set (lo = 0)
+  const char *accepts;  // what the refusal says behind the name
+  bool waits;           // the call drains the context (the others take effect with the next submitted frame)
+  // "view_keep": the call leaves the slots' visibility alone ("sky_keep" forgets whatever the option is: options are not set
+  // between the frames of a steady run).  Such change shading alone, or what a submission decides by itself: the GUI of the
+  // application restated here sets them between frames of one view.  Every other one may change the parameters, the mode or a buffer.
+  bool leaves_visibility;
+  int (*apply)(bbr_context *, int64_t);
+};
+constexpr int64_t kAny = std::numeric_limits<int64_t>::max();
+constexpr bool kWaits = true, kLeaves = true, kForgets = false;  // (OptionRow::waits, ::leaves_visibility)
+using Ctx = bbr_context;
+const OptionRow kOptions[] = {
+    {"gbuffer_view", -1, 3, 0, ": -1 (the lit scene) or 0..3 (position, normal, albedo, MRAH)", !kWaits, kLeaves, store<&Ctx::gbuffer_view>},
+    {"render_pass", 0, 1, 0, ": 0 (forward) or 1 (deferred)", !kWaits, kLeaves, store<&Ctx::deferred>},
+    {"timing", 0, 2, 0, ": 0, 1 or 2", kWaits, kLeaves, set_timing},
+    {"timing_stride", 1, 1024, 0, ": 1 .. 1024", kWaits, kLeaves, [](Ctx *c, int64_t v) { return c->timing_tick = 0, store<&Ctx::timing_stride>(c, v); }},
+    {"frames_in_flight", 1, Ctx::kMaxSlots, 0, ": 1 .. 4", kWaits, kForgets, [](Ctx *c, int64_t v) { return c->frame_counter = 0, store<&Ctx::frames_in_flight>(c, v); }},
+    {"tile_mode", 0, 1, 0, ": 0 (64x64) or 1 (32x32)", kWaits, kForgets, set_tile_mode},
+    {"bin_cap", 1, 1 << 20, 0, " out of range", kWaits, kForgets, set_capacity<&Ctx::bin_cap, &FrameSlot::d_bins, false>},
+    {"ablate", kAblateBuild ? -kAny - 1 : 0, kAblateBuild ? kAny : 0, 0, ": diagnostic builds only (make EXTRA=-DBB_ABLATE)", kWaits, kForgets, store<&Ctx::ablate>},
+    {"max_anisotropy", 1, kMaxAnisotropy, 0, ": 1 (bilinear) .. 16", kWaits, kLeaves, store<&Ctx::max_anisotropy>},
+    {"mip_levels", 1, kMaxMipLevels, 0, ": 1 (no chain) .. 15", kWaits, kLeaves, set_mip_levels},
+    {"supersample", 1, 4, 0, ": 1 (off) .. 4", kWaits, kForgets, set_supersample},
+    {"sample_shading", 0, 1, 0, ": 1 (every sample) or 0 (one fragment per primitive and pixel)", kWaits, kForgets, set_sample_shading},
+    {"depth_resolve", 0, kDepthMax, 1u | 1u << kDepthZero | 1u << kDepthMin | 1u << kDepthMax, ": 0 (none), 1 (SAMPLE_ZERO), 4 (MIN) or 8 (MAX)", kWaits, kForgets, set_depth_resolve},
+    {"shadow_map", 0, kMaxShadowMap, 0, ": 0 (off) or the side of the map, 1 .. 8192", kWaits, kLeaves, set_shadow_map},
+    {"shadow_filter", 0, 2, 0, ": 0 (the hard compare), 1 (3 x 3 taps) or 2 (5 x 5 taps)", kWaits, kLeaves, set_shadow_filter},
+    {"static_records", 0, 1, 0, ": 1 (write a static draw's record part once) or 0 (every frame)", kWaits, kLeaves, store<&Ctx::static_records>},
+    {"sky_keep", 0, 1, 0, ": 1 (a tile that stays background is filled once per frame slot) or 0 (every frame)", kWaits, kLeaves, store<&Ctx::sky_keep>},
+    {"view_keep", 0, 1, 0, ": 1 (a frame whose view and draws repeat in its frame slot launches its shading only) or 0 (every frame runs every stage)", kWaits, kLeaves, store<&Ctx::view_keep>},
+    {"present_fused", -kAny - 1, kAny, 0, "", kWaits, kForgets, store<&Ctx::present_fused>},  // (any value: non-zero is on)
+    {"overlays", -kAny - 1, kAny, 0, "", kWaits, kForgets, store<&Ctx::overlays>},
+    {"tbn", -kAny - 1, kAny, 0, "", kWaits, kForgets, store<&Ctx::tbn>},
+    {"stream_layout", 0, Ctx::kLayouts - 1, 0, ": 0, 1 or 2", kWaits, kForgets, store<&Ctx::layout_mode>},
+    {"push_mode", 0, 1, 0, ": 0 (copies) or 1 (one kernel, all peers)", kWaits, kLeaves, store<&Ctx::push_mode>},
+    {"no_tail_items", 0, kAny, 0, " must be >= 0", kWaits, kForgets, store<&Ctx::no_tail_items>},
+    {"heavy_tiles", -1, 1 << 24, 0, ": -1 (automatic), 0 (off) or a reference count", kWaits, kForgets, store<&Ctx::heavy_tiles>},
+    // starting capacity of the every-tile list / the clip arena (entries); both double when a frame overflows them
+    {"broad_cap", 1, 1 << 24, 0, " out of range (1 .. 2^24)", kWaits, kForgets, set_capacity<&Ctx::broad_cap, &FrameSlot::d_broad, true>},
+    {"clip_cap", 1, 1 << 24, 0, " out of range (1 .. 2^24)", kWaits, kForgets, set_capacity<&Ctx::clip_cap, &FrameSlot::d_clip, true>},
+    {"broad_threshold", 1, kAny, 0, " must be >= 1", kWaits, kForgets, store<&Ctx::broad_threshold>},
+};
+}  // namespace
+
+extern "C" {
 int bbr_set_option(bbr_context *c, const char *name, int64_t value) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
   if (!name) return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_option: NULL name");
-  std::string n(name);
-  if (n == "gbuffer_view") {  // like render_pass: takes effect with the next submitted frame
-    if (value < -1 || value > 3) return fail(c, BBR_ERR_INVALID_ARGUMENT, "gbuffer_view: -1 (the lit scene) or 0..3 (position, normal, albedo, MRAH)");
-    c->gbuffer_view = (int)value;
-    return BBR_OK;
+  const OptionRow *row = std::find_if(std::begin(kOptions), std::end(kOptions), [&](const OptionRow &r) { return std::strcmp(r.name, name) == 0; });
+  if (row == std::end(kOptions)) row = nullptr;  // (an unknown name)
+  if (!row || row->waits) {
+    if (int rc = drain(c)) return rc;
+    for (FrameSlot &s : c->slots) (row && row->leaves_visibility) ? s.forget_sky() : s.forget_image();
   }
-  if (n == "render_pass") {  // takes effect with the next submitted frame; no need to wait for the ones in flight
-    if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "render_pass: 0 (forward) or 1 (deferred)");
-    c->deferred = value == 1;
-    return BBR_OK;
-  }
-  int rc = drain(c);
-  if (rc) return rc;
-  // "sky_keep": whatever the option is (options are not set between the frames of a steady run).  "view_keep": unless the option
-  // is one of those that change shading alone, or what a frame's submission decides by itself -- the GUI of the application
-  // restated here sets such between frames of one view.  Every other one may change the parameters, the mode or a buffer.
-  static const char *const kLeavesVisibility[] = {"timing", "timing_stride", "max_anisotropy", "mip_levels", "shadow_map", "shadow_filter",
-                                                  "static_records", "sky_keep", "view_keep", "push_mode"};
-  const bool leaves_visibility = std::find(std::begin(kLeavesVisibility), std::end(kLeavesVisibility), n) != std::end(kLeavesVisibility);
-  for (FrameSlot &s : c->slots) {
-    s.forget_sky();
-    if (!leaves_visibility) s.forget_visibility();
-  }
-  if (n == "timing") {
-    if (value < 0 || value > 2) return fail(c, BBR_ERR_INVALID_ARGUMENT, "timing: 0, 1 or 2");
-    c->timing = (int)value;
-    if (value && (rc = ensure_timing_ring(c, frame_mode(c).resolve)) != BBR_OK) return rc;
-    c->ring_frames = 0;  // (see bbr_timing_reset on what each of the three reset sites resets)
-    c->present_ring.reset();
-    c->resolve_ring.reset();
-    c->timing_tick = 0;
-  } else if (n == "timing_stride") {
-    if (value < 1 || value > 1024) return fail(c, BBR_ERR_INVALID_ARGUMENT, "timing_stride: 1 .. 1024");
-    c->timing_stride = (int)value;
-    c->timing_tick = 0;
-  }
-  else if (n == "frames_in_flight") {
-    if (value < 1 || value > bbr_context::kMaxSlots) return fail(c, BBR_ERR_INVALID_ARGUMENT, "frames_in_flight: 1 .. 4");
-    c->frames_in_flight = (int)value;
-    c->frame_counter = 0;
-  } else if (n == "tile_mode") {
-    if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "tile_mode: 0 (64x64) or 1 (32x32)");
-    if (c->world > 1 && c->band_rows % (value == 0 ? 64 : 32))
-      return fail(c, BBR_ERR_INVALID_ARGUMENT, "tile_mode: band_rows not a multiple of the new tile height");
-    c->tile_mode = (int)value;
-    for (FrameSlot &s : c->slots) drop<TileSized>(s);
-    drop<TileSized>(c->ov);
-    drop<TileSized>(c->shadow.pass);  // (the map itself has no tiles: it stays)
-  } else if (n == "bin_cap") {
-    if (value < 1 || value > (1 << 20)) return fail(c, BBR_ERR_INVALID_ARGUMENT, "bin_cap out of range");
-    c->bin_cap = (uint32_t)value;
-    for (FrameSlot &s : c->slots) s.d_bins.release();
-  } else if (n == "ablate") {
-#ifdef BB_ABLATE
-    c->ablate = (uint32_t)value;
-#else
-    if (value != 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, "ablate: diagnostic builds only (make EXTRA=-DBB_ABLATE)");
-#endif
-  } else if (n == "max_anisotropy") {
-    if (value < 1 || value > kMaxAnisotropy) return fail(c, BBR_ERR_INVALID_ARGUMENT, "max_anisotropy: 1 (bilinear) .. 16");
-    c->max_anisotropy = (int)value;
-  } else if (n == "mip_levels") {
-    if (value < 1 || value > kMaxMipLevels) return fail(c, BBR_ERR_INVALID_ARGUMENT, "mip_levels: 1 (no chain) .. 15");
-    if (refused_shadow_pair(value, c->shadow_map))
-      return fail(c, BBR_ERR_INVALID_ARGUMENT, "mip_levels: >= 2 is not available with option shadow_map > 0 (k_shade_shadow has no trilinear form)");
-    // every chain is built for the option's value: drop them all, then build the new ones of every live material
-    for (Material &m : c->materials) free_chain(m);
-    c->mip_levels = (int)value;
-    c->materials_dirty = true;
-    ++c->resource_epoch;
-    if (value == 1) c->d_mip_tables.release();
-    for (Material &m : c->materials)
-      if (m.alive && value > 1 && (rc = build_chain(c, m)) != BBR_OK) {
-        for (Material &q : c->materials) free_chain(q);
-        c->mip_levels = 1;
-        return rc;
-      }
-  } else if (n == "supersample") {
-    // like a resize of the render extent; the output extent, and with it a caller's output buffer, stay
-    if (value < 1 || value > 4) return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: 1 (off) .. 4");
-    if ((rc = check_render_extent(c, "supersample", value, c->width, c->height)) != BBR_OK) return rc;
-    if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: between begin_frame and end_frame");
-    if (refused_pair(value, c->sample_shading))
-      return fail(c, BBR_ERR_INVALID_ARGUMENT, "supersample: 3 is not available with option sample_shading 0 (a 3 x 3 block straddles the tiles)");
-    if ((int)value != c->supersample) {
-      // (the one step that can fail comes first: a refused call leaves the context as it was)
-      if (c->timing && (rc = ensure_timing_ring(c, value > 1)) != BBR_OK) return rc;
-      c->supersample = (int)value;
-      drop_extent_buffers(c);
-      c->ring_frames = 0;  // (a frame's interval ends behind its k_resolve: the ring holds frames of one kind)
-      c->resolve_ring.reset();
-      c->timing_tick = 0;
-    }
-  } else if (n == "sample_shading") {
-    // no extent changes: only the sample maps go, and there is no current frame (its samples were of the other kind)
-    if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "sample_shading: 1 (every sample) or 0 (one fragment per primitive and pixel)");
-    if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "sample_shading: between begin_frame and end_frame");
-    if (refused_pair(c->supersample, value))
-      return fail(c, BBR_ERR_INVALID_ARGUMENT, "sample_shading: 0 is not available with option supersample 3 (a 3 x 3 block straddles the tiles)");
-    if ((int)value != c->sample_shading) {
-      c->sample_shading = (int)value;
-      for (FrameSlot &s : c->slots) s.d_sample_map.release();
-      forget_current_frame(c);
-    }
-  } else if (n == "depth_resolve") {
-    // VkResolveModeFlagBits; AVERAGE (2) has no winner.  At n = 1 the value is only stored; with n >= 2 the current frame was
-    // rendered under the other rule (or kept no depth at all): there is none any more, and the fine depth goes
-    if (value != 0 && value != kDepthZero && value != kDepthMin && value != kDepthMax)
-      return fail(c, BBR_ERR_INVALID_ARGUMENT, "depth_resolve: 0 (none), 1 (SAMPLE_ZERO), 4 (MIN) or 8 (MAX)");
-    if (c->in_frame) return fail(c, BBR_ERR_INVALID_ARGUMENT, "depth_resolve: between begin_frame and end_frame");
-    if ((int)value != c->depth_resolve) {
-      c->depth_resolve = (int)value;
-      if (c->supersample > 1) {
-        for (FrameSlot &s : c->slots) s.d_fine_depth.release();
-        forget_current_frame(c);
-      }
-    }
-  } else if (n == "shadow_map") {
-    // the side of the map; a change drops the map and its pass buffers (the context is drained): frames are unshadowed again
-    // until bbr_render_shadow_map has rendered the new one
-    if (value < 0 || value > kMaxShadowMap) return fail(c, BBR_ERR_INVALID_ARGUMENT, "shadow_map: 0 (off) or the side of the map, 1 .. 8192");
-    if (refused_shadow_pair(c->mip_levels, value))
-      return fail(c, BBR_ERR_INVALID_ARGUMENT, "shadow_map: > 0 is not available with option mip_levels >= 2 (k_shade_shadow has no trilinear form)");
-    if ((int)value != c->shadow_map) {
-      c->shadow_map = (int)value;
-      c->shadow = ShadowOwned();
-    }
-  } else if (n == "shadow_filter") {
-    // the radius of the box of compares; stored at any "shadow_map", and the map stays.  The current frame was shaded under the
-    // other rule: there is none any more
-    if (value < 0 || value > 2) return fail(c, BBR_ERR_INVALID_ARGUMENT, "shadow_filter: 0 (the hard compare), 1 (3 x 3 taps) or 2 (5 x 5 taps)");
-    if ((int)value != c->shadow_filter) {
-      c->shadow_filter = (int)value;
-      forget_current_frame(c);
-    }
-  } else if (n == "static_records") {
-    if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "static_records: 1 (write a static draw's record part once) or 0 (every frame)");
-    c->static_records = value == 1;
-  } else if (n == "sky_keep") {
-    if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "sky_keep: 1 (a tile that stays background is filled once per frame slot) or 0 (every frame)");
-    c->sky_keep = value == 1;
-  } else if (n == "view_keep") {
-    if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "view_keep: 1 (a frame whose view and draws repeat in its frame slot launches its shading only) or 0 (every frame runs every stage)");
-    c->view_keep = value == 1;
-  } else if (n == "present_fused") {
-    c->present_fused = value != 0;
-  } else if (n == "overlays") {
-    c->overlays = value != 0;
-  } else if (n == "tbn") {
-    c->tbn = value != 0;
-  } else if (n == "stream_layout") {
-    if (value < 0 || value >= bbr_context::kLayouts) return fail(c, BBR_ERR_INVALID_ARGUMENT, "stream_layout: 0, 1 or 2");
-    c->layout_mode = (int)value;
-  } else if (n == "push_mode") {
-    if (value != 0 && value != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "push_mode: 0 (copies) or 1 (one kernel, all peers)");
-    c->push_mode = (int)value;
-  } else if (n == "no_tail_items") {
-    if (value < 0) return fail(c, BBR_ERR_INVALID_ARGUMENT, "no_tail_items must be >= 0");
-    c->no_tail_items = value;
-  } else if (n == "heavy_tiles") {
-    if (value < -1 || value > (1 << 24)) return fail(c, BBR_ERR_INVALID_ARGUMENT, "heavy_tiles: -1 (automatic), 0 (off) or a reference count");
-    c->heavy_tiles = value;
-  } else if (n == "broad_cap" || n == "clip_cap") {
-    // starting capacity of the every-tile list / the clip arena (entries); both double when a frame overflows them
-    if (value < 1 || value > (1 << 24)) return fail(c, BBR_ERR_INVALID_ARGUMENT, n + " out of range (1 .. 2^24)");
-    (n == "broad_cap" ? c->broad_cap : c->clip_cap) = (uint32_t)value;
-    for (FrameSlot &s : c->slots) {
-      if (n == "broad_cap") s.d_broad.release();
-      else s.d_clip.release();
-    }
-    if (n == "broad_cap") c->ov.d_broad.release();
-    else c->ov.d_clip.release();
-  } else if (n == "broad_threshold") {
-    if (value < 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "broad_threshold must be >= 1");
-    c->broad_threshold = (uint32_t)value;
-  } else {
-    return fail(c, BBR_ERR_INVALID_ARGUMENT, "unknown option: " + n);
-  }
-  return BBR_OK;
+  if (!row) return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string("unknown option: ") + name);
+  if (value < row->lo || value > row->hi || (row->only && !(row->only >> value & 1u)))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(row->name) + row->accepts);
+  return row->apply(c, value);
 }
 
 #ifdef BB_STAMPS
