@@ -17,6 +17,8 @@
 //   k_sample_merge, k_resolve_merged    option "sample_shading" 0: the fragment lists thinned to one fragment per primitive and
 //                output pixel behind k_raster, and the resolve that knows which sample stands for which
 //   k_resolve_depth    option "depth_resolve": the depth (and winner) of one sample of the block for the output pixel
+//   k_bloom_first, k_bloom_down, k_bloom_up, k_present_bloom    option "bloom": a pyramid of what passes a threshold, added to
+//                the pixel in front of present_pixel (behind k_resolve, whose shape they share)
 //   k_shade_shadow     option "shadow_map": k_shade_aniso's fragment stage with a shadow test in front of one light's iteration
 //   k_shade_shadow_faces    ... with 2 .. 6 faces for that light (bbr_render_shadow_faces): cube maps, cascades
 //   k_shade_shadow_pcf      option "shadow_filter" 1 .. 2: ... with a 3 x 3 or 5 x 5 box of compares, 1 .. 6 faces
@@ -3676,6 +3678,106 @@ __global__ __launch_bounds__(kResolveThreads) void k_resolve(const float4 *__res
     if (x >= width) return;
     store_pixel(&out[o], resolve_pixel<N>(fine, width, x, y));
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// bloom (option "bloom", L = 1..8; the rule: include/bibim_hip.h "bloom").  Between the fp32 frame and the
+// presented image: a bright pass, L box-filtered levels down (w_k = (w_{k-1} + 1) >> 1), a tent filter back up that adds
+// level to level, and k_present_bloom, which is k_present with I * up(U_1) added in front of present_pixel.  The frame itself
+// is only read.  Every + - * is one IEEE operation (__fadd_rn / __fsub_rn / __fmul_rn): nothing may contract into an fma.
+// A level is w_k x h_k float4 texels (r, g, b, 0): 16-byte accesses like the frame's; the levels of one pyramid lie one
+// behind the other in one allocation, each starting on a 16-byte boundary by construction.
+// All four are streaming kernels shaped like k_resolve: one lane per texel of the grid they write, blockIdx.y its row (no
+// lane divides), size_t addresses (a 32768-wide frame passes 2^32 bytes).  The levels are read again by the next launch,
+// so their accesses are ordinary ones, and so is k_bloom_first's read of the frame (k_present_bloom reads it again); that
+// second read and the image's store are non-temporal as in k_present.
+//   k_bloom_first    F -> D_1: per D_1 texel the two contiguous float4 of each of its two source rows (k_resolve<2>'s access
+//                    shape), the bright pass on each, the box.  Odd W / H: the last column / row is read twice (the clamp).
+//   k_bloom_down     D_k -> D_{k+1}: the box alone.
+//   k_bloom_up       U_k = D_k + up(U_{k+1}), in place over D_k: a lane reads and writes its own texel of level k only.
+//   k_present_bloom  LDS: the sRGB tables (sizeof(SrgbTables)) and nothing else; the four U_1 taps come from the L2.
+// ------------------------------------------------------------------------------------------------
+constexpr int kMaxBloomLevels = 8;
+constexpr int kBloomThreads = 256;
+constexpr float kBloomMax = 65504.0f;  // the bright pass's ceiling: the largest binary16 (every level stays finite)
+BB_DEV v4f bloom_bright(v4f f, float threshold) {
+  // max0: NaN -> +0, -0 -> +0, -inf -> 0; the min: +inf -> 65504
+  return v4f{__builtin_fminf(max0(__fsub_rn(f.x, threshold)), kBloomMax), __builtin_fminf(max0(__fsub_rn(f.y, threshold)), kBloomMax),
+             __builtin_fminf(max0(__fsub_rn(f.z, threshold)), kBloomMax), 0.0f};
+}
+// ((a + b) + (c + d)) * 0.25, per channel
+BB_DEV v4f bloom_box(v4f a, v4f b, v4f c, v4f d) {
+  const v4f s = resolve_add(resolve_add(a, b), resolve_add(c, d));
+  return v4f{__fmul_rn(s.x, 0.25f), __fmul_rn(s.y, 0.25f), __fmul_rn(s.z, 0.25f), 0.0f};
+}
+BB_DEV float bloom_lerp4(float a, float b) { return __fadd_rn(a, __fmul_rn(__fsub_rn(b, a), 0.25f)); }
+BB_DEV v4f bloom_lerp4(v4f a, v4f b) { return v4f{bloom_lerp4(a.x, b.x), bloom_lerp4(a.y, b.y), bloom_lerp4(a.z, b.z), 0.0f}; }
+// up(G, w, h)(x, y), (x, y) a texel of the next finer grid: the near texel and its neighbour towards (x, y), 9 3 3 1 / 16
+BB_DEV v4f bloom_up(const float4 *__restrict__ g, int32_t w, int32_t h, int32_t x, int32_t y) {
+  const int32_t px = x >> 1, py = y >> 1;
+  const int32_t qx = min(max(px + ((x & 1) ? 1 : -1), 0), w - 1), qy = min(max(py + ((y & 1) ? 1 : -1), 0), h - 1);
+  const v4f *rp = reinterpret_cast<const v4f *>(g) + (size_t)py * (size_t)w, *rq = reinterpret_cast<const v4f *>(g) + (size_t)qy * (size_t)w;
+  const v4f r0 = bloom_lerp4(rp[px], rp[qx]), r1 = bloom_lerp4(rq[px], rq[qx]);
+  return bloom_lerp4(r0, r1);
+}
+
+template <bool FIRST>  // FIRST: the source is the frame (the bright pass in front of the box); else a level
+BB_DEV void bloom_down(const float4 *__restrict__ src, int32_t w, int32_t h, float4 *__restrict__ dst, int32_t wd, float threshold) {
+  const int32_t x = (int32_t)(blockIdx.x * kBloomThreads + threadIdx.x);
+  if (x >= wd) return;
+  const size_t y = blockIdx.y;
+  const int32_t x0 = 2 * x, x1 = min(2 * x + 1, w - 1);  // (2x <= w - 1 for every x < wd = (w + 1) >> 1)
+  const size_t y0 = 2 * y, y1 = 2 * y + 1 < (size_t)h ? 2 * y + 1 : (size_t)h - 1;
+  const v4f *r0 = reinterpret_cast<const v4f *>(src) + y0 * (size_t)w, *r1 = reinterpret_cast<const v4f *>(src) + y1 * (size_t)w;
+  v4f a, b, c, d;
+  if constexpr (FIRST) {
+    // The frame is read again by k_present_bloom a few launches later: an ORDINARY load here leaves it where that second read
+    // finds part of it (k_present_bloom 69 -> 55 us, the chain 34 -> 29 us at 3840 x 2160, profiles/bloom.txt section 3).
+#ifdef BB_BLOOM_NT_READ  // diagnostic build (make EXTRA=-DBB_BLOOM_NT_READ): the other side of that A/B
+    a = bloom_bright(__builtin_nontemporal_load(r0 + x0), threshold), b = bloom_bright(__builtin_nontemporal_load(r0 + x1), threshold);
+    c = bloom_bright(__builtin_nontemporal_load(r1 + x0), threshold), d = bloom_bright(__builtin_nontemporal_load(r1 + x1), threshold);
+#else
+    a = bloom_bright(r0[x0], threshold), b = bloom_bright(r0[x1], threshold), c = bloom_bright(r1[x0], threshold), d = bloom_bright(r1[x1], threshold);
+#endif
+  } else {
+    a = r0[x0], b = r0[x1], c = r1[x0], d = r1[x1];
+  }
+  reinterpret_cast<v4f *>(dst)[y * (size_t)wd + (size_t)x] = bloom_box(a, b, c, d);
+}
+__global__ __launch_bounds__(kBloomThreads) void k_bloom_first(const float4 *__restrict__ frame, int32_t w, int32_t h,
+                                                                float4 *__restrict__ d1, int32_t w1, float threshold) {
+  bloom_down<true>(frame, w, h, d1, w1, threshold);
+}
+__global__ __launch_bounds__(kBloomThreads) void k_bloom_down(const float4 *__restrict__ src, int32_t w, int32_t h,
+                                                               float4 *__restrict__ dst, int32_t wd) {
+  bloom_down<false>(src, w, h, dst, wd, 0.0f);
+}
+// level: D_k on entry, U_k on return (w x its rows); coarse: U_{k+1}, wc x hc
+__global__ __launch_bounds__(kBloomThreads) void k_bloom_up(const float4 *__restrict__ coarse, int32_t wc, int32_t hc,
+                                                             float4 *level, int32_t w) {
+  const int32_t x = (int32_t)(blockIdx.x * kBloomThreads + threadIdx.x);
+  if (x >= w) return;
+  v4f *t = reinterpret_cast<v4f *>(level) + (size_t)blockIdx.y * (size_t)w + (size_t)x;
+  const v4f u = bloom_up(coarse, wc, hc, x, (int32_t)blockIdx.y);
+  const v4f d = *t;
+  *t = v4f{__fadd_rn(d.x, u.x), __fadd_rn(d.y, u.y), __fadd_rn(d.z, u.z), 0.0f};
+}
+// v = F + I * up(U_1), then present_pixel as k_present (tables staged in LDS as k_resolve's PRESENT form stages them)
+__global__ __launch_bounds__(kBloomThreads) void k_present_bloom(const float4 *__restrict__ frame, const float4 *__restrict__ u1,
+                                                                  int32_t w1, int32_t h1, uint32_t *__restrict__ out_rgba8,
+                                                                  int32_t width, const SrgbTables *__restrict__ tables, int enable,
+                                                                  float exposure, int hdr16, float intensity) {
+  static_assert(kBloomThreads == kResolveThreads, "resolve_stage_tables strides by kResolveThreads");
+  __shared__ SrgbTables t;
+  resolve_stage_tables(t, tables);
+  const int32_t x = (int32_t)(blockIdx.x * kBloomThreads + threadIdx.x);
+  if (x >= width) return;
+  const size_t o = (size_t)blockIdx.y * (size_t)width + (size_t)x;
+  const v4f f = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(frame) + o);
+  const v4f b = bloom_up(u1, w1, h1, x, (int32_t)blockIdx.y);
+  const float r = __fadd_rn(f.x, __fmul_rn(intensity, b.x)), g = __fadd_rn(f.y, __fmul_rn(intensity, b.y)),
+              bl = __fadd_rn(f.z, __fmul_rn(intensity, b.z));
+  store_pixel(&out_rgba8[o], present_pixel(r, g, bl, t, enable, exposure, hdr16));
 }
 
 // ------------------------------------------------------------------------------------------------

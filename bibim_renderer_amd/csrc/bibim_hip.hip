@@ -230,6 +230,7 @@ struct ExtentSized {
   DeviceBuffer<float> d_depth;        // option "overlays": the frame's resolved depth, for bbr_draw_overlays
   DeviceBuffer<float> d_fine_depth;   // ... with n >= 2 and a rule: k_raster's depth of the render extent (k_resolve_depth -> d_depth)
   DeviceBuffer<uint32_t> d_present;   // RGBA8 presented image of this slot's frame (bbr_present)
+  DeviceBuffer<float4> d_bloom;       // option "bloom" >= 1: the slot's pyramid, levels 1 .. L one behind the other (from its first bloomed present)
 };
 
 // Option "static_records": what a slot knows about the camera-independent part of the records in its d_attrs.  One entry
@@ -290,6 +291,7 @@ struct FrameSlot : TileSized, ExtentSized {
     int32_t enable = 0, hdr16 = 1;
     float exposure = 1.f;
   } present;
+  int bloom_ran = 0;  // the levels of the chain that last ran on d_bloom for the frame in this slot (0: none; bbr_read_bloom_level)
   Event ev_geom_done, ev_raster_done, ev_tail_done;  // edges between the streams of a frame
   // Everything queued on this slot's image so far: the frame's k_shade, then whatever was put behind it (presentation, the
   // GUI pass, a copy to the caller's buffer, the exchange).  Work on the image goes between follow() and busy_until().
@@ -547,7 +549,20 @@ struct bbr_context : ExtentDumps {
   // timing ring: (frame start, geometry done, raster done, shade start, shade done) per frame since the last reset
   std::vector<Event> ring;
   uint32_t ring_frames = 0;
-  PairRing present_ring;  // around each k_present while timing is on
+  PairRing present_ring;  // around each k_present (k_present_bloom) while timing is on
+  // option "bloom": 0 = k_present; 1..8 = the levels of the pyramid in front of k_present_bloom (the rule: bibim_hip.h "bloom")
+  int bloom = 0;
+  float bloom_threshold = 1.0f, bloom_intensity = 0.05f;  // bbr_set_bloom: stored at any "bloom"
+  // bbr_present_buffer_bloom's pyramid: one for the context, so its calls are ordered one behind the other through ev_used
+  // whatever their streams.  Dropped with the option's return to 0 and with the extent buffers.
+  struct BloomBuffer {
+    DeviceBuffer<float4> d_levels;
+    Event ev_used;     // behind the last call's k_present_bloom
+    bool used = false; // ... recorded
+    int32_t w = 0, h = 0;
+    int ran = 0;       // extent and levels of the last call's chain (0: none; bbr_read_bloom_level source 1)
+  } bloom_buffer;
+  PairRing bloom_ring;  // around each chain (k_bloom_first .. the last k_bloom_up) while timing is on
   PairRing resolve_ring;  // around the k_resolve of each timed frame: pair i is ring frame i's (the two counts are reset together)
   static constexpr uint32_t kRingCap = ::kRingCap;
   static constexpr uint32_t kRingEvents = 5;
@@ -681,6 +696,9 @@ int refuse_without_depth_rule(bbr_context *c, const char *who, const char *why) 
 bool refused_pair(int64_t supersample, int64_t sample_shading) { return supersample == 3 && sample_shading == 0; }
 // ... and the other one: pairing them would double the instantiations of the largest kernel (k_shade_mip)
 bool refused_shadow_pair(int64_t mip_levels, int64_t shadow_map) { return mip_levels >= 2 && shadow_map > 0; }
+// ... and option "bloom"'s two: a rank's shard lacks the rows its neighbours own, and a fused frame is no fp32 frame
+bool refused_bloom_partition(int64_t bloom, int64_t world) { return bloom >= 1 && world > 1; }
+bool refused_bloom_fused(int64_t bloom, int64_t present_fused) { return bloom >= 1 && present_fused != 0; }
 // the render extent n * width x n * height has the limit of the output extent (bbr_create)
 constexpr int32_t kMaxExtent = 32768;
 constexpr int32_t kMaxShadowMap = 8192;  // option "shadow_map": 256 x 256 tiles of 32 x 32, the launch-slot limit of a frame
@@ -1833,12 +1851,69 @@ int ensure_srgb_tables(bbr_context *c) {
   return BBR_OK;
 }
 
-// k_present for the frame in slot `s`, on the shade stream (ordered after the frame's k_shade)
+// Option "bloom": the sizes of a pyramid over a W x H frame (w_k = (w_{k-1} + 1) >> 1, never below 1) and where each level
+// starts in its allocation, in texels; levels 1 .. L (index 0 is the frame's own extent)
+struct BloomShape {
+  int levels = 0;
+  int32_t w[kMaxBloomLevels + 1] = {}, h[kMaxBloomLevels + 1] = {};
+  size_t at[kMaxBloomLevels + 1] = {}, texels = 0;
+  BloomShape(int32_t width, int32_t height, int l) : levels(l) {
+    w[0] = width, h[0] = height;
+    for (int k = 1; k <= l; ++k) {
+      w[k] = (w[k - 1] + 1) >> 1, h[k] = (h[k - 1] + 1) >> 1;
+      at[k] = texels;
+      texels += (size_t)w[k] * (size_t)h[k];
+    }
+  }
+};
+// The chain over `frame` into `levels` (afterwards U_1 .. U_L), then k_present_bloom into `out`: everything on `ps`.
+// bloom_ring holds the chain's interval, present_ring k_present_bloom's, as it holds k_present's.
+int queue_bloom_present(bbr_context *c, hipStream_t ps, const float4 *frame, uint32_t *out, const BloomShape &sh, float4 *levels,
+                        int enable, float exposure, int hdr16) {
+  auto grid = [](int32_t w, int32_t h) { return dim3((unsigned)((w + kBloomThreads - 1) / kBloomThreads), (unsigned)h); };
+  auto level = [&](int k) { return levels + sh.at[k]; };
+  if (c->timing) {
+    HIP_TRY(c, c->bloom_ring.ensure());
+    HIP_TRY(c, c->present_ring.ensure());
+    HIP_TRY(c, c->bloom_ring.begin(ps));
+  }
+  hipLaunchKernelGGL(k_bloom_first, grid(sh.w[1], sh.h[1]), dim3(kBloomThreads), 0, ps, frame, sh.w[0], sh.h[0], level(1), sh.w[1],
+                     c->bloom_threshold);
+  for (int k = 1; k < sh.levels; ++k)
+    hipLaunchKernelGGL(k_bloom_down, grid(sh.w[k + 1], sh.h[k + 1]), dim3(kBloomThreads), 0, ps, (const float4 *)level(k), sh.w[k], sh.h[k],
+                       level(k + 1), sh.w[k + 1]);
+  for (int k = sh.levels - 1; k >= 1; --k)
+    hipLaunchKernelGGL(k_bloom_up, grid(sh.w[k], sh.h[k]), dim3(kBloomThreads), 0, ps, (const float4 *)level(k + 1), sh.w[k + 1], sh.h[k + 1],
+                       level(k), sh.w[k]);
+  HIP_TRY(c, hipGetLastError());
+  if (c->timing) {
+    HIP_TRY(c, c->bloom_ring.end(ps));
+    HIP_TRY(c, c->present_ring.begin(ps));
+  }
+  hipLaunchKernelGGL(k_present_bloom, grid(sh.w[0], sh.h[0]), dim3(kBloomThreads), 0, ps, frame, (const float4 *)level(1), sh.w[1], sh.h[1],
+                     out, sh.w[0], c->d_srgb_tables.ptr, enable, exposure, hdr16, c->bloom_intensity);
+  HIP_TRY(c, hipGetLastError());
+  if (c->timing) HIP_TRY(c, c->present_ring.end(ps));
+  return BBR_OK;
+}
+
+// k_present for the frame in slot `s`, on the shade stream (ordered after the frame's k_shade); option "bloom" >= 1: the
+// chain on the slot's own pyramid and k_present_bloom in its place (no partition then: the shard is the W x H frame)
 int queue_present(bbr_context *c, FrameSlot &s) {
   int rc_tables = ensure_srgb_tables(c);
   if (rc_tables) return rc_tables;
   const size_t n = c->shard_pixels();
   const hipStream_t ps = c->slot_present_stream(s);
+  if (c->bloom) {
+    const BloomShape sh(c->width, c->height, c->bloom);
+    HIP_TRY(c, s.d_bloom.ensure(sh.texels));  // (grows only behind a drain: at the slot's first bloomed present)
+    if (ps != s.stream_used) HIP_TRY(c, s.follow(ps));
+    if (int rc = queue_bloom_present(c, ps, s.out_used, s.present.out, sh, s.d_bloom.ptr, s.present.enable, s.present.exposure, s.present.hdr16))
+      return rc;
+    s.bloom_ran = sh.levels;
+    HIP_TRY(c, s.busy_until(ps));
+    return BBR_OK;
+  }
   if (ps != s.stream_used) HIP_TRY(c, s.follow(ps));  // behind the frame's k_shade
   if (c->timing) {
     HIP_TRY(c, c->present_ring.ensure());
@@ -3069,6 +3144,8 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
   if (world < 1 || rank < 0 || rank >= world) return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_partition: bad rank/world");
   if (band_rows <= 0) band_rows = c->tile_h();
   if (band_rows % c->tile_h()) return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_partition: band_rows must be a multiple of the tile height");
+  if (refused_bloom_partition(c->bloom, world))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_partition: world > 1 is not available with option bloom >= 1 (the chain needs its neighbours' rows)");
   int rc = drain(c);
   if (rc) return rc;
   c->rank = rank;
@@ -3102,6 +3179,7 @@ static void drop_extent_buffers(bbr_context *c) {
     s.present.active = false;
     s.present.out = nullptr;
     s.present.copy_to = nullptr;
+    s.bloom_ran = 0;
     s.out_used = nullptr;
     s.in_flight = false;
     s.forget_extent();
@@ -3111,6 +3189,7 @@ static void drop_extent_buffers(bbr_context *c) {
   drop_slot(c->ov);
   drop<bbr_context::TbnRecords>(c->tbn_pass);
   drop<ExtentDumps>(*c);
+  c->bloom_buffer = bbr_context::BloomBuffer();
   forget_current_frame(c);  // (the whole frame of the last exchange had the old extent, too)
 }
 
@@ -3449,6 +3528,7 @@ int bbr_timing_reset(bbr_context *c) {
   //  option "timing" those and the stride's tick; option "supersample" the ring, resolve and the tick, not present)
   c->ring_frames = 0;
   c->present_ring.reset();
+  c->bloom_ring.reset();
   c->resolve_ring.reset();
   return BBR_OK;
 }
@@ -3523,6 +3603,7 @@ int set_timing(bbr_context *c, int64_t value) {
   if (int rc = value ? ensure_timing_ring(c, frame_mode(c).resolve) : BBR_OK) return rc;
   c->ring_frames = 0;  // (see bbr_timing_reset on what each of the three reset sites resets)
   c->present_ring.reset();
+  c->bloom_ring.reset();
   c->resolve_ring.reset();
   c->timing_tick = 0;
   return BBR_OK;
@@ -3604,6 +3685,29 @@ int set_shadow_map(bbr_context *c, int64_t value) {
   if ((int)value != c->shadow_map) c->shadow = ShadowOwned();
   return store<&bbr_context::shadow_map>(c, value);
 }
+// the levels of the pyramid.  The frames and the images already presented stay; the pyramids hold the levels of the other
+// value (bbr_read_bloom_level: none until the next present), and at 0 nothing of the option exists
+int set_bloom(bbr_context *c, int64_t value) {
+  if (refused_bloom_partition(value, c->world))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "bloom: >= 1 is not available on a partition of world > 1 (the chain needs its neighbours' rows)");
+  if (refused_bloom_fused(value, c->present_fused))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "bloom: >= 1 is not available with option present_fused (there is no fp32 frame)");
+  if ((int)value != c->bloom) {
+    for (FrameSlot &s : c->slots) s.bloom_ran = 0;
+    c->bloom_buffer.ran = 0;
+  }
+  if (value == 0) {
+    for (FrameSlot &s : c->slots) s.d_bloom.release();
+    c->bloom_buffer = bbr_context::BloomBuffer();
+    c->bloom_ring = PairRing();
+  }
+  return store<&bbr_context::bloom>(c, value);
+}
+int set_present_fused(bbr_context *c, int64_t value) {
+  if (refused_bloom_fused(c->bloom, value))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_fused: not available with option bloom >= 1 (there is no fp32 frame)");
+  return store<&bbr_context::present_fused>(c, value);
+}
 // the radius of the box of compares; stored at any "shadow_map", and the map stays.  The current frame was shaded under the
 // other rule: there is none any more
 int set_shadow_filter(bbr_context *c, int64_t value) {
@@ -3648,7 +3752,8 @@ const OptionRow kOptions[] = {
     {"static_records", 0, 1, 0, ": 1 (write a static draw's record part once) or 0 (every frame)", kWaits, kLeaves, store<&Ctx::static_records>},
     {"sky_keep", 0, 1, 0, ": 1 (a tile that stays background is filled once per frame slot) or 0 (every frame)", kWaits, kLeaves, store<&Ctx::sky_keep>},
     {"view_keep", 0, 1, 0, ": 1 (a frame whose view and draws repeat in its frame slot launches its shading only) or 0 (every frame runs every stage)", kWaits, kLeaves, store<&Ctx::view_keep>},
-    {"present_fused", -kAny - 1, kAny, 0, "", kWaits, kForgets, store<&Ctx::present_fused>},  // (any value: non-zero is on)
+    {"present_fused", -kAny - 1, kAny, 0, "", kWaits, kForgets, set_present_fused},  // (any value: non-zero is on)
+    {"bloom", 0, kMaxBloomLevels, 0, ": 0 (off) or the levels of the pyramid, 1 .. 8", kWaits, kLeaves, set_bloom},
     {"overlays", -kAny - 1, kAny, 0, "", kWaits, kForgets, store<&Ctx::overlays>},
     {"tbn", -kAny - 1, kAny, 0, "", kWaits, kForgets, store<&Ctx::tbn>},
     {"stream_layout", 0, Ctx::kLayouts - 1, 0, ": 0, 1 or 2", kWaits, kForgets, store<&Ctx::layout_mode>},
@@ -3732,6 +3837,90 @@ int bbr_present_buffer(bbr_context *c, const void *rgba32f_device, void *rgba8_d
                      (uint32_t *)rgba8_device, (size_t)n_pixels, c->d_srgb_tables.ptr, enable, exposure, hdr16 != 0);
   HIP_TRY(c, hipGetLastError());
   return BBR_OK;
+}
+
+int bbr_set_bloom(bbr_context *c, float threshold, float intensity) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!std::isfinite(threshold) || !std::isfinite(intensity) || threshold < 0.f || intensity < 0.f)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_bloom: threshold and intensity must be finite and >= 0");
+  if (int rc = drain(c)) return rc;  // like option "bloom": the slots keep their visibility
+  for (FrameSlot &s : c->slots) s.forget_sky();
+  c->bloom_threshold = threshold;
+  c->bloom_intensity = intensity;
+  return BBR_OK;
+}
+
+int bbr_get_bloom(bbr_context *c, int32_t *out_levels, float *out_threshold, float *out_intensity) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  if (out_levels) *out_levels = c->bloom;
+  if (out_threshold) *out_threshold = c->bloom_threshold;
+  if (out_intensity) *out_intensity = c->bloom_intensity;
+  return BBR_OK;
+}
+
+int bbr_present_buffer_bloom(bbr_context *c, const void *rgba32f_device, void *rgba8_device, int32_t width, int32_t height,
+                             int32_t enable, float exposure, int32_t hdr16, void *stream) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!rgba32f_device || !rgba8_device) return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_buffer_bloom: NULL");
+  if ((uintptr_t)rgba32f_device % 16 || (uintptr_t)rgba8_device % 4)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_buffer_bloom: the source must be 16-byte aligned, the output 4-byte aligned");
+  if (width < 1 || height < 1 || width > kMaxExtent || height > kMaxExtent)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_buffer_bloom: width/height out of range (1 .. 32768)");
+  if (!c->bloom)
+    return bbr_present_buffer(c, rgba32f_device, rgba8_device, (uint64_t)width * (uint64_t)height, enable, exposure, hdr16, stream);
+  if (int rc = ensure_srgb_tables(c)) return rc;
+  bbr_context::BloomBuffer &b = c->bloom_buffer;
+  const BloomShape sh(width, height, c->bloom);
+  HIP_TRY(c, b.ev_used.ensure(hipEventDisableTiming));
+  // the one pyramid is never used twice at once: this call's stream waits for the call before it; a pyramid that has to grow
+  // is freed only once that call has left the GPU
+  const hipStream_t ps = stream ? (hipStream_t)stream : c->shade_stream();
+  if (b.used && sh.texels > b.d_levels.cap) HIP_TRY(c, hipEventSynchronize(b.ev_used));
+  HIP_TRY(c, b.d_levels.ensure(sh.texels));
+  if (b.used) HIP_TRY(c, hipStreamWaitEvent(ps, b.ev_used, 0));
+  b.ran = 0;
+  if (int rc = queue_bloom_present(c, ps, (const float4 *)rgba32f_device, (uint32_t *)rgba8_device, sh, b.d_levels.ptr, enable, exposure, hdr16 != 0))
+    return rc;
+  HIP_TRY(c, hipEventRecord(b.ev_used, ps));
+  b.used = true;
+  b.w = width, b.h = height, b.ran = sh.levels;
+  return BBR_OK;
+}
+
+int bbr_read_bloom_level(bbr_context *c, int32_t source, int32_t level, float *out_rgb, uint64_t capacity, int32_t *out_w, int32_t *out_h) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (source != 0 && source != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_bloom_level: source is 0 (the last frame's slot) or 1 (the buffer call)");
+  if (level < 1 || level > c->bloom) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_bloom_level: option bloom has no such level");
+  const float4 *levels = nullptr;
+  int32_t w0 = 0, h0 = 0;
+  if (source == 0) {
+    if (!c->have_frame || c->last_slot < 0 || !c->slots[c->last_slot].present.active || c->slots[c->last_slot].bloom_ran != c->bloom)
+      return fail(c, BBR_ERR_NOT_IN_FRAME, "read_bloom_level: bbr_present with option bloom >= 1 was not called for the last frame");
+    if (int rc = sync_and_fix(c, nullptr)) return rc;  // (a frame rendered again has its chain run again: resubmit_last_frame)
+    levels = c->slots[c->last_slot].d_bloom.ptr, w0 = c->width, h0 = c->height;
+  } else {
+    const bbr_context::BloomBuffer &b = c->bloom_buffer;
+    if (b.ran != c->bloom || !b.used) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_bloom_level: bbr_present_buffer_bloom has not run with option bloom >= 1");
+    HIP_TRY(c, hipEventSynchronize(b.ev_used));
+    levels = b.d_levels.ptr, w0 = b.w, h0 = b.h;
+  }
+  const BloomShape sh(w0, h0, c->bloom);
+  const size_t texels = (size_t)sh.w[level] * (size_t)sh.h[level];
+  if (out_w) *out_w = sh.w[level];
+  if (out_h) *out_h = sh.h[level];
+  if (!out_rgb) return BBR_OK;
+  if (capacity < (uint64_t)texels * 3 * sizeof(float)) return fail(c, BBR_ERR_CAPACITY, "read_bloom_level: capacity (bytes) too small for w * h * 3 floats");
+  std::vector<float4> host(texels);
+  HIP_TRY(c, hipMemcpy(host.data(), levels + sh.at[level], texels * sizeof(float4), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < texels; ++i) out_rgb[3 * i] = host[i].x, out_rgb[3 * i + 1] = host[i].y, out_rgb[3 * i + 2] = host[i].z;
+  return BBR_OK;
+}
+
+int bbr_bloom_timing(bbr_context *c, uint32_t *out_launches, float *out_avg_ms) {
+  return pair_ring_timing(c, &bbr_context::bloom_ring, "bloom_timing", out_launches, out_avg_ms);
 }
 
 int bbr_read_presented(bbr_context *c, uint8_t *host) {

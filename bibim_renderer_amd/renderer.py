@@ -472,6 +472,36 @@ class Renderer:
         self._check(self._L.bbr_resolve_timing(self._ctx, C.byref(n), C.byref(t)))
         return n.value, t.value
 
+    # -- bloom (option "bloom" = L >= 1: a pyramid in front of k_present_bloom; the rule: bibim_hip.h "bloom") --
+    def set_bloom(self, threshold, intensity):
+        self._check(self._L.bbr_set_bloom(self._ctx, float(threshold), float(intensity)))
+
+    def get_bloom(self):
+        """(levels, threshold, intensity) as stored"""
+        n, t, i = C.c_int32(), C.c_float(), C.c_float()
+        self._check(self._L.bbr_get_bloom(self._ctx, C.byref(n), C.byref(t), C.byref(i)))
+        return n.value, t.value, i.value
+
+    def present_buffer_bloom(self, rgba32f_ptr, rgba8_ptr, width, height, enable, exposure, hdr16=True, stream=None):
+        """the bloom rule + presentation on any width x height RGBA32F device frame (asynchronous)"""
+        self._check(self._L.bbr_present_buffer_bloom(self._ctx, C.c_void_p(rgba32f_ptr), C.c_void_p(rgba8_ptr), int(width),
+                                                     int(height), int(enable), float(exposure), int(bool(hdr16)),
+                                                     C.c_void_p(stream) if stream else None))
+
+    def read_bloom_level(self, level, source=0):
+        """U_level, float32 [h_k, w_k, 3], of the last frame's presentation (source 0) or the last buffer call (source 1)"""
+        w, h = C.c_int32(), C.c_int32()
+        self._check(self._L.bbr_read_bloom_level(self._ctx, int(source), int(level), None, 0, C.byref(w), C.byref(h)))
+        out = np.empty((h.value, w.value, 3), np.float32)
+        self._check(self._L.bbr_read_bloom_level(self._ctx, int(source), int(level), _ptr(out), out.nbytes, C.byref(w), C.byref(h)))
+        return out
+
+    def bloom_timing(self):
+        """(chains, average ms of one) since timing_reset(), option "timing" on"""
+        n, t = C.c_uint32(), C.c_float()
+        self._check(self._L.bbr_bloom_timing(self._ctx, C.byref(n), C.byref(t)))
+        return n.value, t.value
+
     def presented_device_ptr(self):
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self._L.bbr_presented_device_ptr(self._ctx, C.byref(p), C.byref(n)))

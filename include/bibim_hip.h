@@ -439,6 +439,11 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            queued shadow caster or follows one, a frame behind a capacity growth or an overflowed frame.
  *                            bbr_read_sky_tiles reports a kept frame's background tiles as kept.  0: every frame runs every
  *                            stage.  bbr_view_keep_counts counts both kinds.
+ *   "bloom" 0..8             0 (default): bbr_present launches k_present; no kernel or buffer of the option exists.  L = 1..8:
+ *                            a bloom pyramid of L levels in front of k_present_bloom (the rule and the calls: "bloom" below).
+ *                            Setting it waits for the GPU like "max_anisotropy": the slots keep their visibility, the last
+ *                            frame stays current, an image already presented is not redone.  Refused with a partition of
+ *                            world > 1 and with "present_fused" non-zero, in either order.
  *   "ablate" bits           diagnostic builds only (make EXTRA=-DBB_ABLATE): skip parts of the pipeline */
 int bbr_set_option(bbr_context *ctx, const char *name, int64_t value);
 /* The stream layout in use (option "stream_layout"; 0 while only one frame is in flight).  *out_decided is always 1 and
@@ -825,6 +830,62 @@ int bbr_present_timing(bbr_context *ctx, uint32_t *out_launches, float *out_avg_
 int bbr_resolve_timing(bbr_context *ctx, uint32_t *out_launches, float *out_avg_ms);
 /* hdr_tone_mapping.frag:9-18 alone on the fp32 frame, in place (no quantisation) */
 int bbr_tone_map(bbr_context *ctx, int32_t enable_tone_mapping, float exposure);
+
+/* ---- bloom (option "bloom" = L in 1..8; no reference counterpart: the reference clips a bright light to a white disc) ----
+ * Between the linear HDR frame and the presented image: what exceeds a threshold is filtered down L levels and back up,
+ * and the sum is added to the frame's value in front of the conversion of bbr_present.  The fp32 frame is only read.
+ * The rule.  All operations are binary32, round to nearest even, denormals kept, no contraction: every + - * below is one
+ * IEEE operation, there is no fma.  Inputs: L; the threshold T and the intensity I of bbr_set_bloom; the source F, the
+ * W x H RGBA32F frame bbr_present reads (the slot's output, the resolved frame under "supersample" >= 2, a caller's output
+ * buffer).  Only r, g and b take part.
+ *   sizes    w_0 = W, h_0 = H;  w_k = (w_{k-1} + 1) >> 1, h_k likewise, k = 1 .. L   (never below 1: all L levels always exist)
+ *   bright   e(x,y)[c] = min(max0(F(x,y)[c] - T), 65504.0f)    max0(d) = d > 0 ? d : 0  (NaN -> +0, -0 -> +0, -inf -> 0, +inf -> 65504)
+ *   box      box(G,w,h)(x,y) = ((G(x0,y0) + G(x1,y0)) + (G(x0,y1) + G(x1,y1))) * 0.25f
+ *            x0 = min(2x, w-1), x1 = min(2x+1, w-1), y0, y1 likewise
+ *   down     D_1 = box(e, W, H);   D_{k+1} = box(D_k, w_k, h_k)
+ *   lerp4    lerp4(a,b) = a + (b - a) * 0.25f
+ *   up       up(G,w',h')(x,y), (x,y) a texel of the next finer grid:  px = x >> 1, py = y >> 1,
+ *            qx = clamp(px + ((x & 1) ? 1 : -1), 0, w'-1), qy likewise,
+ *            r0 = lerp4(G(px,py), G(qx,py)), r1 = lerp4(G(px,qy), G(qx,qy)), up = lerp4(r0, r1)     (weights 9 3 3 1 / 16)
+ *   sum      U_L = D_L;   U_k = D_k + up(U_{k+1}, w_{k+1}, h_{k+1}),  k = L-1 .. 1
+ *   pixel    B(x,y) = up(U_1, w_1, h_1)(x,y);   v[c] = F(x,y)[c] + I * B(x,y)[c]    (the product, then the sum)
+ *   image    the byte triple of bbr_present's conversion of v (binary16 stage if hdr16, tone map, sRGB byte); alpha 255
+ * So every D, U and B is finite and >= +0 whatever F holds; a NaN or inf of F reaches only its own pixel, as without bloom;
+ * with I = 0, or T >= every finite channel of F, the bytes are those of "bloom" 0; and a constant bright-pass value e gives
+ * U_1 = L * e: the levels add and nothing is normalised -- I is the user's scale.
+ * Deviations from the usual effect, on purpose: a hard per-channel threshold (no soft knee, no luminance weighting), a box
+ * down-filter and a tent up-filter, an fp32 pyramid.
+ *   bbr_set_option(ctx, "bloom", L)   see the option list.  With L >= 1 bbr_present queues the chain (k_bloom_first,
+ *             k_bloom_down, k_bloom_up) and k_present_bloom in k_present's place, on the same stream; whatever presents a frame
+ *             again (a capacity growth, the read-backs that render again) runs the chain again.  hdr16 0 and 1, a caller's
+ *             rgba8_device or output buffer, "supersample" 2..4 with either "sample_shading", both render passes, up to four
+ *             frames in flight (a pyramid per frame slot); bbr_draw_overlays and bbr_draw_ui act on the bloomed image.
+ *   bbr_set_bloom     T and I: both finite and >= 0, else BBR_ERR_INVALID_ARGUMENT and nothing changes.  Defaults 1.0f and 0.05f.
+ *             Stored at any L.  Waits for the GPU like the option; in effect from the next presentation.
+ *   bbr_get_bloom     the stored L, T and I (any pointer may be NULL).
+ *   bbr_present_buffer_bloom   the rule on any W x H device frame, with a pyramid owned by the context: how a host blooms the
+ *             all-gathered whole frame of a partition.  With L = 0 it is bbr_present_buffer(n = width * height), bit for bit.
+ *             BBR_ERR_INVALID_ARGUMENT, and nothing launched, for a NULL pointer, a source not 16-byte or an output not 4-byte
+ *             aligned, an extent outside 1..32768.  Asynchronous on `hip_stream` (NULL = the context's shading stream); calls on
+ *             different streams are ordered one behind the other by the library (an event), since they share the pyramid.
+ *   bbr_read_bloom_level   U_level, w_k * h_k * 3 floats (r, g, b; row-major), of the last frame's presentation (source 0)
+ *             or of the last bbr_present_buffer_bloom (source 1).  Synchronises.  `out_rgb` may be NULL to ask for the size;
+ *             `capacity` is in bytes, BBR_ERR_CAPACITY when too small.  BBR_ERR_NOT_IN_FRAME before such a run under the
+ *             option's current value and after bbr_resize; BBR_ERR_INVALID_ARGUMENT for a level outside 1..L (every level at L = 0).
+ *   bbr_bloom_timing  sibling of bbr_present_timing: with option "timing" on, the chains since bbr_timing_reset and the
+ *             average duration of one (first launch to last, in front of k_present_bloom, which bbr_present_timing times).
+ * Refused, by whichever call would complete the pair, with the context unchanged: "bloom" >= 1 on a partition of world > 1
+ * (bbr_set_option / bbr_set_partition: the chain needs the rows the neighbours own) and with "present_fused" non-zero (there
+ * is no fp32 frame).
+ * Memory: per frame slot the sum of w_k * h_k texels of 16 bytes (about a third of W * H), from the slot's first bloomed
+ * presentation until the option returns to 0, bbr_resize or bbr_destroy; counted by bbr_debug_live_resources. */
+int bbr_set_bloom(bbr_context *ctx, float threshold, float intensity);
+int bbr_get_bloom(bbr_context *ctx, int32_t *out_levels, float *out_threshold, float *out_intensity);
+int bbr_present_buffer_bloom(bbr_context *ctx, const void *rgba32f_device, void *rgba8_device, int32_t width, int32_t height,
+                             int32_t enable_tone_mapping, float exposure, int32_t hdr16, void *hip_stream);
+int bbr_read_bloom_level(bbr_context *ctx, int32_t source, int32_t level, float *out_rgb, uint64_t capacity, int32_t *out_w,
+                         int32_t *out_h);
+int bbr_bloom_timing(bbr_context *ctx, uint32_t *out_launches, float *out_avg_ms);
 
 /* ---- native exchange: every rank gets the whole frame (BASELINE config #4) ----
  * The reference renders on one GPU; with a partition (bbr_set_partition) each rank holds a compact shard and the frame
