@@ -155,6 +155,8 @@ SIGNATURES = {
     "bbr_static_record_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bbr_read_sky_tiles": (C.c_int, [_P, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]),
     "bbr_view_keep_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "bbr_surface_keep_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "bbr_read_surface_keep": (C.c_int, [_P, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
     "bbr_host_timing": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bbr_host_timing_reset": (C.c_int, [_P]),
     "bbr_debug_live_resources": (C.c_int, [C.POINTER(C.c_uint64)]),

@@ -4549,4 +4549,142 @@ __global__ __launch_bounds__(kPassRetireThreads) void k_shadow_pass_retire(Count
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Option "surface_keep": a slot's shaded SURFACE, kept under a kept view (option "view_keep").
+//
+// What light_surface receives of a fragment -- P, the normal as surface_normal<false> returns it, albedo, metallic, roughness,
+// ao -- depends on the slot's visibility, the draws' contents, the materials and enable_normal_map; not on the lights, the
+// exposure or tone mapping.  k_surface_store writes it once per stop of the camera and slot, k_shade_lit reads it back in
+// every frame behind: no item word, no fragment list, no record, no texel, one round trip of four coalesced loads per wave.
+//
+// The layout: three float4 planes and one uint32 plane of `plane` = 64 x (item capacity) entries each, one behind the other,
+// entry [item * 64 + lane] the fragment slot k_shade's wave `item` shades in lane `lane`:
+//   plane 0  P.x  P.y  P.z  n.x      plane 1  n.y  n.z  albedo.r  albedo.g      plane 2  albedo.b  metallic  roughness  ao
+//   plane 3  the pixel's index in the output as k_shade forms it, or kSurfaceNoPixel for a lane that is not `valid`
+// Every access is one full-width vector instruction: 1 KB (256 B) contiguous per wave.
+// Both kernels stand HERE, behind every kernel above, for the reason given at k_sample_merge.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t kSurfaceNoPixel = 0xFFFFFFFFu;  // (a frame has at most 2^30 pixels)
+constexpr int kSurfacePlanes = 3;
+// float4 entries of a surface of `items` items: the three planes, and the index plane (four words per entry)
+constexpr size_t surface_keep_entries(size_t items) { return items * 64 * kSurfacePlanes + items * 64 / 4; }
+
+// The fragment stage of k_shade up to the light loop, through the functions the fragment kernels share -- the bits are k_shade's
+// by construction -- in shade_item_list's shape: every lane gathers its own record, each wave walks the list with the launch's
+// stride.  One tap at (u, v): the filter of "max_anisotropy" 1, "mip_levels" 1.  Packed and mixed materials, per lane.
+// `n_cap`: the item capacity of `surface` (the host sized it from the slot's exact item count: never exceeded, and checked here).
+template <int TILE_W, int TILE_H>
+__global__ __launch_bounds__(kShadeThreads) void k_surface_store(
+    const uint32_t *__restrict__ items, const uint32_t *__restrict__ item_count, uint32_t n_cap,
+    const unsigned long long *__restrict__ frags, const uint32_t *__restrict__ frag_count,
+    const ShadeRec *__restrict__ recs, const ClipSlot *__restrict__ clip_arena, FrameParams fp, int enable_normal_map,
+    const MaterialDesc *__restrict__ materials, float4 *__restrict__ surface) {
+  constexpr int TILE_PIXELS = TILE_W * TILE_H;
+  const int lane = (int)(threadIdx.x & 63u);
+  const uint32_t n_items = min(*item_count, n_cap);
+  const size_t plane = (size_t)n_cap * 64;
+  uint32_t *const index = reinterpret_cast<uint32_t *>(surface + kSurfacePlanes * plane);
+  for (uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (uint32_t)kShadeWaves + (threadIdx.x >> 6)));
+       j < n_items; j += gridDim.x * (uint32_t)kShadeWaves) {
+    const uint32_t item = items[1u + j];
+    const ItemPlace at = decode_item(fp, item);
+    bool valid;
+    const unsigned long long frag = fetch_fragment<TILE_PIXELS, false>(item, at, lane, frags, frag_count, valid);
+    const uint32_t ref = (uint32_t)frag;
+    int x, y;
+    tile_pixel<TILE_W>(fragment_pixel<TILE_PIXELS>(frag), x, y);
+    const int gx = at.tx * TILE_W + x, gy = at.ty * TILE_H + y;
+    const uint32_t opix = (uint32_t)(at.out_tile_row * TILE_H + y) * (uint32_t)fp.width + (uint32_t)gx;
+
+    // the head of the primitive record and, for a clipped fragment, its sub-triangle's clip slot
+    const ShadeRec *rp = recs + (ref >> 3);
+    const uint32_t clip1 = (uint32_t)(frag >> (32 + kFragPixBits));  // clip-arena slot + 1 of a clipped sub-triangle, 0: none / unknown
+    bool clipped = clip1 != 0u;
+    const ClipSlot *cp = clip_arena + (clipped ? clip1 - 1u : 0u);
+    PlaneHead h = clipped ? cp->h : rp->h;
+    float uv[3][2], cb[3][3] = {};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { uv[k][0] = rp->uv[k][0]; uv[k][1] = rp->uv[k][1]; }
+    const uint32_t packed_dims = rp->packed_dims, material = rp->material, clip_base = rp->clip_base;
+    const GlobalBytes packed_texels = (GlobalBytes)rp->packed;
+    if (late_clip_slot(clipped, clip_base)) {
+      cp = clip_arena + record_clip_slot(clip_base, ref);
+      h = cp->h;
+      clipped = true;
+    }
+    if (clipped) {
+#pragma unroll
+      for (int jj = 0; jj < 3; ++jj)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cb[jj][k] = cp->bary[jj][k];
+    }
+    const PlaneUV here = plane_uv(h, clipped, cb, uv, gx, gy);
+    float a[kNumVary];
+    a[0] = here.u; a[1] = here.v;
+#pragma unroll
+    for (int jj = 0; jj < kNumBodyVary; ++jj) a[2 + jj] = interp3(here.b0, here.b1, here.b2, rp->vary[jj][0], rp->vary[jj][1], rp->vary[jj][2]);
+
+    // texture filtering, forward_brdf.frag:16-22: k_shade's statements
+    f3 albedo, normal;
+    float metallic, roughness, ao;
+    if (packed_dims != 0u) {
+      const PackedFetch fetch{packed_texels, (int)(packed_dims & 0xFFFFu), (int)(packed_dims >> 16)};
+      const PackedFetch::Raw r = fetch.load(here.u, here.v);
+      albedo.x = filter_channel(r.q00.x, r.q10.x, r.q01.x, r.q11.x, 0, r.fx, r.fy);
+      albedo.y = filter_channel(r.q00.x, r.q10.x, r.q01.x, r.q11.x, 8, r.fx, r.fy);
+      albedo.z = filter_channel(r.q00.x, r.q10.x, r.q01.x, r.q11.x, 16, r.fx, r.fy);
+      metallic = filter_channel(r.q00.x, r.q10.x, r.q01.x, r.q11.x, 24, r.fx, r.fy);
+      roughness = filter_channel(r.q00.y, r.q10.y, r.q01.y, r.q11.y, 24, r.fx, r.fy);
+      ao = filter_channel(r.q00.z, r.q10.z, r.q01.z, r.q11.z, 0, r.fx, r.fy);
+      normal = surface_normal<false>(a, enable_normal_map, [&] {
+        return mk3(normal_map_axis(filter_channel(r.q00.y, r.q10.y, r.q01.y, r.q11.y, 0, r.fx, r.fy)),
+                   normal_map_axis(filter_channel(r.q00.y, r.q10.y, r.q01.y, r.q11.y, 8, r.fx, r.fy)),
+                   normal_map_axis(filter_channel(r.q00.y, r.q10.y, r.q01.y, r.q11.y, 16, r.fx, r.fy)));
+      });
+    } else {
+      // maps of different sizes: one set of taps per map
+      const MaterialDesc &md = materials[material];
+      albedo = sample_map_rgb(md.maps[kMapAlbedo], here.u, here.v);
+      metallic = sample_map_r(md.maps[kMapMetallic], here.u, here.v);
+      roughness = sample_map_r(md.maps[kMapRoughness], here.u, here.v);
+      ao = sample_map_r(md.maps[kMapAO], here.u, here.v);
+      normal = surface_normal<false>(a, enable_normal_map, [&] {
+        const f3 t = sample_map_rgb(md.maps[kMapNormal], here.u, here.v);
+        return mk3(normal_map_axis(t.x), normal_map_axis(t.y), normal_map_axis(t.z));
+      });
+    }
+    const size_t e = (size_t)j * 64 + (size_t)lane;
+    surface[e] = make_float4(a[2], a[3], a[4], normal.x);
+    surface[plane + e] = make_float4(normal.y, normal.z, albedo.x, albedo.y);
+    surface[2 * plane + e] = make_float4(albedo.z, metallic, roughness, ao);
+    index[e] = valid ? opix : kSurfaceNoPixel;
+  }
+}
+
+// One item per wave, four waves per workgroup, the grid sized by the host from the exact item count (the pinned word the slot's
+// last full frame left): no tail launch and no TAIL form.  A wave's four loads depend on nothing but its own index; then the
+// light loop on the slot's cooked table, as surface_colour<false> runs it without a shadow, and the store.  No LDS, no barrier.
+// The surface is read with non-temporal loads: a slot reads its surface again three frames later, three slots' surfaces exceed
+// the Infinity Cache, and what they would push out of the L2 are the pixels and light tables of the frames in flight.  Alone the
+// two policies measure the same; with three frames in flight plain loads cost 1.9 us per frame (profiles/r18_surface_keep.txt).
+template <bool PRESENT = false>
+__global__ __launch_bounds__(kShadeThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_shade_lit(
+    const float4 *__restrict__ surface, const uint32_t *__restrict__ item_count, uint32_t n_cap, ShadeParams sp,
+    const CookedLight *__restrict__ cooked, float4 *__restrict__ out, const SrgbTables *__restrict__ tables,
+    uint32_t *__restrict__ out8, Counters *__restrict__ ctr, Counters *__restrict__ ctr_done, uint32_t *__restrict__ item_groups) {
+  const ConstLights lights_c{(ConstCooked)cooked};
+  retire_counters(ctr, ctr_done, item_groups);
+  const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (uint32_t)kShadeWaves + (threadIdx.x >> 6)));
+  if (j >= n_cap) return;  // (never: the host's grid; what keeps the loads below inside the buffer)
+  const size_t plane = (size_t)n_cap * 64, e = (size_t)j * 64 + (size_t)(threadIdx.x & 63u);
+  const uint32_t *const index = reinterpret_cast<const uint32_t *>(surface + kSurfacePlanes * plane);
+  const v4f *const sv = reinterpret_cast<const v4f *>(surface);
+  const v4f q0 = __builtin_nontemporal_load(sv + e), q1 = __builtin_nontemporal_load(sv + plane + e),
+            q2 = __builtin_nontemporal_load(sv + 2 * plane + e);
+  const uint32_t opix = __builtin_nontemporal_load(index + e);
+  if (j >= *item_count) return;  // a wave without an item (the grid is rounded up to whole workgroups)
+  const float4 color = light_surface(sp, lights_c, mk3(q0.x, q0.y, q0.z), mk3(q0.w, q1.x, q1.y), mk3(q1.z, q1.w, q2.x), q2.y, q2.z, q2.w);
+  store_colour<PRESENT>(opix != kSurfaceNoPixel, color, (size_t)opix, out, out8, tables, sp);
+}
+
 }  // namespace bbr

@@ -185,6 +185,7 @@ struct TileSized {
   DeviceBuffer<CookedLight> d_cooked;   // the frame's light table as the light loop consumes it (k_shade_items -> k_shade)
   DeviceBuffer<uint32_t> d_heavy;       // the frame's heavy-tile list (k_geometry -> k_raster; option "heavy_tiles")
   DeviceBuffer<uint32_t> d_item_groups; // 64-fragment chunks per group of 256 launch slots (k_raster -> k_shade_items)
+  DeviceBuffer<float4> d_surface_keep;  // option "surface_keep": the slot's kept surface (k_surface_store -> k_shade_lit), from its first storing frame
 };
 
 // Option "sky_keep": what a slot remembers about the background in its d_frame.  While `stamp` is non-zero, a tile whose word
@@ -219,6 +220,24 @@ struct VisKeep {
   bool kept_last = false;  // the slot's last frame was a kept one (bbr_read_sky_tiles: it stored into no background tile)
   FrameInputs in;          // what the visibility was made from beside the draws' contents (those: plan_static_records' keys)
   std::array<const void *, 15> buffers = {};  // the buffers that hold it
+};
+
+// Option "surface_keep": what a slot remembers about the surface in its d_surface_keep (TileSized: dropped with the lists it
+// mirrors).  While `valid`, entry [item * 64 + lane] of the buffer holds what light_surface receives for the fragment slot
+// k_shade's wave `item` shades in lane `lane`, for all `items` items of the visibility in the slot's buffers (VisKeep), filtered
+// under `normal_map` and `all_packed`: a kept frame under the same two launches k_shade_lit on it in place of k_shade.  `run`:
+// the kept frames in a row that could have been lit, under one `normal_map`: the n-th of them is the storing frame
+// (submit_frame_body).  Whatever forgets the visibility forgets the surface (FrameSlot::forget_visibility); so does a kept frame
+// that takes another shading kernel, and a full frame.
+constexpr int kSurfaceKeepDefault = 64;
+struct SurfaceKeep {
+  bool valid = false;
+  uint32_t run = 0;
+  int32_t normal_map = 0;   // enable_normal_map of the slot's last frame: what the run counts under, and the surface was made with
+  bool all_packed = true;   // ... and bbr_context::all_packed
+  const void *buffer = nullptr;  // where it lives (d_surface_keep.ptr when it was stored)
+  uint32_t items = 0;       // the exact item count it was stored for, and the buffer's item capacity
+  void forget() { valid = false, run = 0; }
 };
 
 // ... by the render or the output extent: bbr_resize and option "supersample" drop it (drop_extent_buffers)
@@ -345,7 +364,8 @@ struct FrameSlot : TileSized, ExtentSized {
   // geometry-side buffers (a capacity growth, a diagnostic re-render, a dropped buffer group): the slot's next frame is
   // rendered in full.  An entry point that touches the image forgets both (forget_image).
   VisKeep vis;
-  void forget_visibility() { vis.valid = false; }
+  SurfaceKeep surf;  // option "surface_keep": rests on `vis`
+  void forget_visibility() { vis.valid = false, surf.forget(); }
   void forget_image() { forget_sky(), forget_visibility(); }
   // native exchange (bbr_allgather_frame / bbr_push_shard) with library-owned buffers: every rank's block, the whole frame
   DeviceBuffer<uint8_t> d_gathered, d_whole;
@@ -531,6 +551,11 @@ struct bbr_context : ExtentDumps {
   // its shading only (VisKeep, launch_frame's kept branch); 0 = every frame runs every stage
   bool view_keep = true;
   uint64_t view_kept_frames = 0, view_full_frames = 0;  // bbr_view_keep_counts: main frames submitted either way
+  // option "surface_keep": 0 = off; n >= 1 = a slot's n-th kept frame in a row that takes the plain k_shade stores the slot's
+  // surface (k_surface_store), and it and every such frame behind it are shaded from it (k_shade_lit; SurfaceKeep).  The default
+  // is the smallest power of two for which a stop of the camera that ends right behind its stores loses at most 5 %: DESIGN.md section 5
+  int surface_keep = kSurfaceKeepDefault;
+  uint64_t surface_stored_frames = 0, surface_lit_frames = 0;  // bbr_surface_keep_counts: storing frames; frames k_shade_lit shaded (those included)
   bool dump_records = false;    // (bbr_read_records: its frame shows what k_geometry's full path writes, and what it leaves alone)
   // Bumped by every call that can change what a mesh or material handle, or a pointer taken from one, means (upload and free
   // of either, the material table, the mip chains): a freed and reused address never compares equal to its former self.
@@ -1095,6 +1120,11 @@ struct ShadeInputs {
   // option "view_keep" (submit_frame_body decides).  `kept`: the slot's buffers hold this frame's visibility already: nothing is
   // launched in front of the shading but, where `cook` says the lights are not the ones the slot's table was cooked from, k_cook_lights.
   bool kept = false, cook = false;
+  // option "surface_keep" (submit_frame_body decides): `lit`: k_shade_lit on `surface` (`surface_items` items) in place of k_shade
+  // and its tail; `store`: k_surface_store in front of it
+  bool lit = false, store = false;
+  float4 *surface = nullptr;
+  uint32_t surface_items = 0;
 };
 
 // Everything in front of the shading: the frame's visibility, from `in`, into the slot's buffers.  `ev`: as for launch_frame.
@@ -1254,6 +1284,20 @@ void launch_frame(bbr_context *c, FrameSlot &s, const FrameMode &mode, const Fra
         else launch(k_shade_aniso<TW, TH, DEFERRED, PRESENT, DUMP>, main_wgs, ss, std::tuple<>{}, groups, c->max_anisotropy, surface);
       }); });
       return;
+    }
+    if constexpr (!DEFERRED && !PRESENT) {
+      if (sh.lit) {
+        // option "surface_keep": the grid from the exact item count; the storing frame fills the surface first, on the same stream
+        const uint32_t wgs = (sh.surface_items + kShadeWaves - 1) / kShadeWaves;
+        if (sh.store)
+          hipLaunchKernelGGL((k_surface_store<TW, TH>), dim3(std::min(wgs, 8u * (uint32_t)c->n_cus)), dim3(kShadeThreads), 0, ss, s.d_items.ptr, item_count,
+                             sh.surface_items, s.d_frags.ptr, s.d_frag_count.ptr, s.d_attrs.ptr, s.d_clip.ptr, fp, sp.enable_normal_map,
+                             c->d_materials.ptr, sh.surface);
+        if (ev) (void)hipEventRecord(ev[3], ss);
+        hipLaunchKernelGGL(k_shade_lit<false>, dim3(wgs), dim3(kShadeThreads), 0, ss, (const float4 *)sh.surface, item_count, sh.surface_items, sp,
+                           s.d_cooked.ptr, sh.out, sh.tables, sh.out8, ctr, ctr_done, groups);
+        return;
+      }
     }
     if (tail) launch(k_shade<TW, TH, DEFERRED, PRESENT, true, true>, 32u, sr, std::make_tuple(main_wgs * (uint32_t)kShadeWaves), nullptr);
     if (ev) (void)hipEventRecord(ev[3], ss);
@@ -1762,6 +1806,34 @@ int submit_frame_body(bbr_context *c, int slot_index) {
   } else {
     ++c->view_full_frames;
     s.vis = {keepable, false, in, buffers};
+  }
+  // Option "surface_keep": is this kept frame shaded from the slot's surface?  It could be if it takes the plain k_shade on the
+  // long route (a kept frame is forward, of the whole image, into the slot's own fp32 frame, without a resolve: keeps_own_image)
+  // and the slot's pinned word holds the item count its last full frame left.  Such a frame under the normal-map switch of the
+  // slot's last frame is one more of the run: lit if the surface is valid, the storing frame if it is the n-th.  A full frame, a
+  // kept frame that could not be lit and one under another switch start the run again, and the surface is stale.
+  {
+    SurfaceKeep &k = s.surf;
+    const uint32_t n_items = s.h_flags.ptr[kFlagItemCount];
+    const bool could = kept && c->surface_keep > 0 && !in.short_frame && !mode.shadow && c->mip_levels == 1 && c->max_anisotropy == 1 &&
+                       !c->dump_surface && n_items > 0 && n_items <= in.max_items;
+    if (!could || k.normal_map != sh.sp.enable_normal_map || k.all_packed != c->all_packed) {
+      k.forget();
+    } else if (k.valid && k.buffer == s.d_surface_keep.ptr && k.items == n_items) {
+      sh.lit = true;
+    } else if (++k.run >= (uint32_t)c->surface_keep) {
+      // (the slot's frames have left the GPU: growing frees nothing that is in use)
+      HIP_TRY(c, s.d_surface_keep.ensure(surface_keep_entries((n_items + kShadeWaves - 1) / kShadeWaves * kShadeWaves)));
+      k.valid = true, k.buffer = s.d_surface_keep.ptr, k.items = n_items;
+      sh.lit = sh.store = true;
+      ++c->surface_stored_frames;
+    }
+    k.normal_map = sh.sp.enable_normal_map, k.all_packed = c->all_packed;
+    if (sh.lit) {
+      // the capacity the kernels index the planes by: what the buffer was sized for
+      sh.surface = s.d_surface_keep.ptr, sh.surface_items = (n_items + kShadeWaves - 1) / kShadeWaves * kShadeWaves;
+      ++c->surface_lit_frames;
+    }
   }
 
   // (a kept frame: up to the item head, which a short frame's shading counts its items by and the full frame's k_raster left)
@@ -3488,6 +3560,39 @@ int bbr_view_keep_counts(const bbr_context *c, uint64_t *out_kept, uint64_t *out
   return BBR_OK;
 }
 
+int bbr_surface_keep_counts(const bbr_context *c, uint64_t *out_stored, uint64_t *out_lit) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  if (out_stored) *out_stored = c->surface_stored_frames;
+  if (out_lit) *out_lit = c->surface_lit_frames;
+  return BBR_OK;
+}
+
+int bbr_read_surface_keep(bbr_context *c, int32_t slot, float *out_values, uint32_t *out_index, uint64_t capacity, uint32_t *out_items) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (slot < 0 || slot >= c->n_slots()) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface_keep: no such frame slot");
+  int rc = drain(c);
+  if (rc) return rc;
+  const FrameSlot &s = c->slots[slot];
+  const SurfaceKeep &k = s.surf;
+  if (!s.vis.valid || !k.valid || !k.buffer || k.buffer != s.d_surface_keep.ptr)
+    return fail(c, BBR_ERR_NOT_IN_FRAME, "read_surface_keep: the slot holds no valid surface");
+  if (out_items) *out_items = k.items;
+  if (!out_values && !out_index) return BBR_OK;
+  const size_t n = (size_t)k.items * 64;
+  if (capacity < n) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_surface_keep: capacity is smaller than 64 x the item count");
+  const size_t plane = (size_t)((k.items + kShadeWaves - 1) / kShadeWaves * kShadeWaves) * 64;  // (the capacity the planes are indexed by)
+  if (out_values) {
+    std::vector<float4> planes(n);
+    for (int p = 0; p < kSurfacePlanes; ++p) {
+      HIP_TRY(c, hipMemcpy(planes.data(), s.d_surface_keep.ptr + p * plane, n * sizeof(float4), hipMemcpyDeviceToHost));
+      for (size_t e = 0; e < n; ++e) std::memcpy(out_values + e * 4 * kSurfacePlanes + 4 * p, &planes[e], sizeof(float4));
+    }
+  }
+  if (out_index) HIP_TRY(c, hipMemcpy(out_index, s.d_surface_keep.ptr + kSurfacePlanes * plane, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return BBR_OK;
+}
+
 int bbr_read_sky_tiles(bbr_context *c, uint8_t *out, uint32_t cap, uint32_t *out_count) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
@@ -3703,6 +3808,14 @@ int set_bloom(bbr_context *c, int64_t value) {
   }
   return store<&bbr_context::bloom>(c, value);
 }
+// the slots keep their visibility and forget their surfaces: the run starts again under the new n; at 0 nothing of the option exists
+int set_surface_keep(bbr_context *c, int64_t value) {
+  for (FrameSlot &s : c->slots) {
+    s.surf.forget();
+    if (value == 0) s.d_surface_keep.release();
+  }
+  return store<&bbr_context::surface_keep>(c, value);
+}
 int set_present_fused(bbr_context *c, int64_t value) {
   if (refused_bloom_fused(c->bloom, value))
     return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_fused: not available with option bloom >= 1 (there is no fp32 frame)");
@@ -3752,6 +3865,7 @@ const OptionRow kOptions[] = {
     {"static_records", 0, 1, 0, ": 1 (write a static draw's record part once) or 0 (every frame)", kWaits, kLeaves, store<&Ctx::static_records>},
     {"sky_keep", 0, 1, 0, ": 1 (a tile that stays background is filled once per frame slot) or 0 (every frame)", kWaits, kLeaves, store<&Ctx::sky_keep>},
     {"view_keep", 0, 1, 0, ": 1 (a frame whose view and draws repeat in its frame slot launches its shading only) or 0 (every frame runs every stage)", kWaits, kLeaves, store<&Ctx::view_keep>},
+    {"surface_keep", 0, 1 << 20, 0, ": 0 (off) or n >= 1 (a slot's n-th kept frame in a row stores its shaded surface; it and those behind it are lit from it)", kWaits, kLeaves, set_surface_keep},
     {"present_fused", -kAny - 1, kAny, 0, "", kWaits, kForgets, set_present_fused},  // (any value: non-zero is on)
     {"bloom", 0, kMaxBloomLevels, 0, ": 0 (off) or the levels of the pyramid, 1 .. 8", kWaits, kLeaves, set_bloom},
     {"overlays", -kAny - 1, kAny, 0, "", kWaits, kForgets, store<&Ctx::overlays>},

@@ -628,6 +628,23 @@ class Renderer:
         self._check(self._L.bbr_view_keep_counts(self._ctx, C.byref(kept), C.byref(full)))
         return {"kept": int(kept.value), "full": int(full.value)}
 
+    def surface_keep_counts(self):
+        """option surface_keep since the context was created (host-side counters: no synchronisation): storing frames, frames
+        shaded from a kept surface (the storing ones included)"""
+        stored, lit = C.c_uint64(), C.c_uint64()
+        self._check(self._L.bbr_surface_keep_counts(self._ctx, C.byref(stored), C.byref(lit)))
+        return {"stored": int(stored.value), "lit": int(lit.value)}
+
+    def read_surface_keep(self, slot):
+        """option surface_keep, frame slot `slot`: (values float32 [items * 64, 12], index uint32 [items * 64]) of its kept surface
+        (include/bibim_hip.h); raises BibimError when the slot holds none.  Synchronises, renders nothing."""
+        n = C.c_uint32()
+        self._check(self._L.bbr_read_surface_keep(self._ctx, int(slot), None, None, 0, C.byref(n)))
+        values = np.empty((int(n.value) * 64, 12), np.float32)
+        index = np.empty(int(n.value) * 64, np.uint32)
+        self._check(self._L.bbr_read_surface_keep(self._ctx, int(slot), _ptr(values), _ptr(index), index.size, C.byref(n)))
+        return values, index
+
     def read_sky_tiles(self):
         """option sky_keep, the most recently submitted frame: a uint8 per tile, (tiles_y * tiles_x,) row-major -- 0 not a
         background tile (or a frame that could not keep), 1 background and filled, 2 background and kept.  Synchronises."""

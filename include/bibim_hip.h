@@ -204,6 +204,16 @@ int bbr_read_sky_tiles(bbr_context *ctx, uint8_t *out, uint32_t cap, uint32_t *o
  * visibility was in the frame slot: shading only) and main frames rendered in full (re-renders included).  Either pointer
  * may be NULL. */
 int bbr_view_keep_counts(const bbr_context *ctx, uint64_t *out_kept, uint64_t *out_full);
+/* Option "surface_keep" since bbr_create, without synchronising or touching the GPU: storing frames (k_surface_store ran), and
+ * frames shaded from a slot's kept surface (k_shade_lit; the storing frames are among them).  Every such frame is a kept frame
+ * of bbr_view_keep_counts.  Either pointer may be NULL. */
+int bbr_surface_keep_counts(const bbr_context *ctx, uint64_t *out_stored, uint64_t *out_lit);
+/* For tests: the kept surface of frame slot `slot` (0 .. frames in flight - 1) and its item count.  Fragment slot e = item * 64 +
+ * lane, e < 64 * *out_items, gets out_values[12 e ..] = P.xyz, the shading normal, albedo.rgb, metallic, roughness, ao (what
+ * bbr_read_surface reports as floats 6..17 of the pixel's record) and out_index[e] = the pixel's index y * width + x, or
+ * 0xFFFFFFFF for a lane without a fragment.  `capacity`: the fragment slots both arrays have room for; both may be NULL to ask
+ * for the count.  Synchronises; renders nothing and forgets nothing.  BBR_ERR_NOT_IN_FRAME if the slot holds no valid surface. */
+int bbr_read_surface_keep(bbr_context *ctx, int32_t slot, float *out_values, uint32_t *out_index, uint64_t capacity, uint32_t *out_items);
 /* The host's side of the frame loop since bbr_host_timing_reset, kept without touching the GPU (steady_clock around the
  * submit): frames submitted by bbr_end_frame / bbr_replay_frame, nanoseconds spent inside those calls, and the part of
  * it the host was BLOCKED because the frame slot it wanted to reuse was still on the GPU (and in how many frames).  A
@@ -439,6 +449,18 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            queued shadow caster or follows one, a frame behind a capacity growth or an overflowed frame.
  *                            bbr_read_sky_tiles reports a kept frame's background tiles as kept.  0: every frame runs every
  *                            stage.  bbr_view_keep_counts counts both kinds.
+ *   "surface_keep" 0|n       n (default 64): under a kept view the part of shading in front of the light loop -- barycentrics,
+ *                            varyings, texel taps, the filter, the TBN product -- does not change either: it depends on the
+ *                            slot's visibility, the draws, the materials and the normal-map switch, not on lights, exposure
+ *                            or tone mapping.  A slot's n-th kept frame in a row that takes the plain shading kernel on the
+ *                            long route (no shadow map, "mip_levels" 1, "max_anisotropy" 1, "timing" 0 or 2, more item slots
+ *                            than "no_tail_items") stores that surface (k_surface_store: 52 bytes per fragment slot, allocated
+ *                            then); it and every such frame behind it run the light loop alone on it (k_shade_lit).  Same
+ *                            pixels, same read-backs, same bbr_get_stats, same bbr_view_keep_counts.  A full frame, a kept frame
+ *                            that cannot be lit, a change of the normal-map switch and whatever makes the slots forget their
+ *                            visibility start the run again; setting the option itself forgets the surfaces only.  0: off,
+ *                            nothing is allocated.  n follows from what a storing frame costs: DESIGN.md section 5.
+ *                            bbr_surface_keep_counts counts storing and lit frames.
  *   "bloom" 0..8             0 (default): bbr_present launches k_present; no kernel or buffer of the option exists.  L = 1..8:
  *                            a bloom pyramid of L levels in front of k_present_bloom (the rule and the calls: "bloom" below).
  *                            Setting it waits for the GPU like "max_anisotropy": the slots keep their visibility, the last
