@@ -139,6 +139,14 @@ SIGNATURES = {
     "bbr_read_bloom_level": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int32)]),
     "bbr_bloom_timing": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "bbr_set_auto_exposure": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32]),
+    "bbr_get_auto_exposure": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "bbr_reset_exposure": (C.c_int, [_P]),
+    "bbr_present_buffer_auto": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                          C.c_void_p]),
+    "bbr_read_exposure": (C.c_int, [_P, C.c_int32, C.c_void_p]),
+    "bbr_luminance_timing": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "bbr_presented_device_ptr": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "bbr_unpack_gathered_rgba8": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bbr_comm_unique_id": (C.c_int, [_P, _P]),

@@ -19,6 +19,8 @@
 //   k_resolve_depth    option "depth_resolve": the depth (and winner) of one sample of the block for the output pixel
 //   k_bloom_first, k_bloom_down, k_bloom_up, k_present_bloom    option "bloom": a pyramid of what passes a threshold, added to
 //                the pixel in front of present_pixel (behind k_resolve, whose shape they share)
+//   k_luminance, k_exposure, k_present_auto, k_present_bloom_auto    option "auto_exposure": a histogram of the frame's log2
+//                luminance, the exposure it asks for adapted against a history, and the two present kernels reading it
 //   k_shade_shadow     option "shadow_map": k_shade_aniso's fragment stage with a shadow test in front of one light's iteration
 //   k_shade_shadow_faces    ... with 2 .. 6 faces for that light (bbr_render_shadow_faces): cube maps, cascades
 //   k_shade_shadow_pcf      option "shadow_filter" 1 .. 2: ... with a 3 x 3 or 5 x 5 box of compares, 1 .. 6 faces
@@ -3584,9 +3586,10 @@ __global__ void k_tone_map(float4 *__restrict__ frame, size_t n, int enable, flo
 // of tables once and converts 2048 pixels (eight coalesced rounds of 256).
 constexpr int kPresentThreads = 256;
 constexpr int kPresentPerThread = 8;
-__global__ __launch_bounds__(kPresentThreads) void k_present(const float4 *__restrict__ frame, uint32_t *__restrict__ out_rgba8,
-                                                              size_t n, const SrgbTables *__restrict__ tables, int enable,
-                                                              float exposure, int hdr16) {
+// k_present's whole body, stated once: k_present takes the exposure as a kernel argument, k_present_auto (option
+// "auto_exposure") loads it from device memory and calls the same text
+BB_DEV void present_body(const float4 *__restrict__ frame, uint32_t *__restrict__ out_rgba8, size_t n,
+                         const SrgbTables *__restrict__ tables, int enable, float exposure, int hdr16) {
   __shared__ SrgbTables t;
   {
     const uint32_t *src = reinterpret_cast<const uint32_t *>(tables);
@@ -3604,6 +3607,11 @@ __global__ __launch_bounds__(kPresentThreads) void k_present(const float4 *__res
     const uint32_t px = present_pixel(c.x, c.y, c.z, t, enable, exposure, hdr16);
     store_pixel(&out_rgba8[i], px);
   }
+}
+__global__ __launch_bounds__(kPresentThreads) void k_present(const float4 *__restrict__ frame, uint32_t *__restrict__ out_rgba8,
+                                                              size_t n, const SrgbTables *__restrict__ tables, int enable,
+                                                              float exposure, int hdr16) {
+  present_body(frame, out_rgba8, n, tables, enable, exposure, hdr16);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3762,11 +3770,11 @@ __global__ __launch_bounds__(kBloomThreads) void k_bloom_up(const float4 *__rest
   const v4f d = *t;
   *t = v4f{__fadd_rn(d.x, u.x), __fadd_rn(d.y, u.y), __fadd_rn(d.z, u.z), 0.0f};
 }
-// v = F + I * up(U_1), then present_pixel as k_present (tables staged in LDS as k_resolve's PRESENT form stages them)
-__global__ __launch_bounds__(kBloomThreads) void k_present_bloom(const float4 *__restrict__ frame, const float4 *__restrict__ u1,
-                                                                  int32_t w1, int32_t h1, uint32_t *__restrict__ out_rgba8,
-                                                                  int32_t width, const SrgbTables *__restrict__ tables, int enable,
-                                                                  float exposure, int hdr16, float intensity) {
+// v = F + I * up(U_1), then present_pixel as k_present (tables staged in LDS as k_resolve's PRESENT form stages them).
+// The body is stated once for k_present_bloom and k_present_bloom_auto, as present_body is for k_present.
+BB_DEV void present_bloom_body(const float4 *__restrict__ frame, const float4 *__restrict__ u1, int32_t w1, int32_t h1,
+                               uint32_t *__restrict__ out_rgba8, int32_t width, const SrgbTables *__restrict__ tables, int enable,
+                               float exposure, int hdr16, float intensity) {
   static_assert(kBloomThreads == kResolveThreads, "resolve_stage_tables strides by kResolveThreads");
   __shared__ SrgbTables t;
   resolve_stage_tables(t, tables);
@@ -3779,7 +3787,192 @@ __global__ __launch_bounds__(kBloomThreads) void k_present_bloom(const float4 *_
               bl = __fadd_rn(f.z, __fmul_rn(intensity, b.z));
   store_pixel(&out_rgba8[o], present_pixel(r, g, bl, t, enable, exposure, hdr16));
 }
+__global__ __launch_bounds__(kBloomThreads) void k_present_bloom(const float4 *__restrict__ frame, const float4 *__restrict__ u1,
+                                                                  int32_t w1, int32_t h1, uint32_t *__restrict__ out_rgba8,
+                                                                  int32_t width, const SrgbTables *__restrict__ tables, int enable,
+                                                                  float exposure, int hdr16, float intensity) {
+  present_bloom_body(frame, u1, w1, h1, out_rgba8, width, tables, enable, exposure, hdr16, intensity);
+}
 
+// ------------------------------------------------------------------------------------------------
+// auto exposure (option "auto_exposure"; the rule: include/bibim_hip.h "auto exposure").  In front of the
+// conversion: k_luminance counts the frame's pixels into 256 bins of log2 luminance, k_exposure turns the histogram into the
+// exposure E of this presentation and adapts it against the history of its source, k_present_auto / k_present_bloom_auto are
+// k_present / k_present_bloom with E loaded from device memory.  The histogram is integer arithmetic: the order in which
+// pixels are counted does not matter, the result is exact.  The floating-point steps are single IEEE operations
+// (__fadd_rn / __fsub_rn / __fmul_rn: nothing may contract).
+//   k_luminance   streaming: 16 B read per pixel and nothing else, ordinary loads (k_bloom_first and the present kernel read
+//                 the same bytes a few launches later).  A workgroup converts kLumaThreads * kLumaPerThread pixels, in
+//                 coalesced rounds like k_present.  LDS: kLumaWords = 257 words (the 256 bins and `ignored`), 1028 bytes.
+//                 Neighbouring pixels mostly share a bin, so equal bins are combined in front of the LDS add: a lane adds a
+//                 run of equal bins among its own pixels once, and a wave whose lanes all hold the same (bin, count) adds it
+//                 once for all of them (luma_add).  At the end the non-zero words go to the presentation's device histogram,
+//                 one global atomic each.
+//   k_exposure    one workgroup of 256: lane k owns bin k.  Prefix sums, trim, S, the 64-bit division, the reciprocal, the
+//                 clamp, the adapt step against the history word; writes the record, the history, and leaves the device
+//                 histogram zeroed for its next use.
+// ------------------------------------------------------------------------------------------------
+constexpr int kLumaThreads = 256;
+constexpr int kLumaPerThread = 8;
+constexpr int kLumaBins = 256;
+constexpr int kLumaWords = kLumaBins + 1;      // [256]: the ignored pixels
+constexpr uint32_t kLumaSkip = 0xFFFFFFFFu;    // no pixel (behind the frame's end)
+constexpr int kLumaFirstBin = (127 - 16) * 8;  // 888: bits >> 20 of 2^-16
+// bbr_exposure_record (include/bibim_hip.h), as the kernels write it; the host asserts that the two agree
+struct ExposureRecord {
+  uint32_t hist[kLumaBins];
+  uint32_t ignored, counted, kept, mean_bits;
+  unsigned long long sum;
+  float target, clamped, previous, applied;
+  uint32_t flags, reserved;
+};
+struct ExposureHistory {  // one per source
+  float value;
+  uint32_t valid;
+};
+struct ExposureParams {  // bbr_set_auto_exposure
+  float key, e_min, e_max, rate;
+  int32_t lo, hi;
+};
+
+// the word of the histogram a pixel is counted in
+BB_DEV uint32_t luma_word(v4f p) {
+  const float y = __fadd_rn(__fadd_rn(__fmul_rn(0.2126f, p.x), __fmul_rn(0.7152f, p.y)), __fmul_rn(0.0722f, p.z));
+  if (!(y > 0.0f)) return (uint32_t)kLumaBins;  // NaN, +-0, negative, -inf: ignored
+  const int32_t k = (int32_t)(__float_as_uint(y) >> 20) - kLumaFirstBin;
+  return (uint32_t)min(max(k, 0), kLumaBins - 1);
+}
+// BB_LUMA_FORM: the one diagnostic switch of these kernels (make EXTRA=-DBB_LUMA_FORM=n), the A/B of
+// profiles/auto_exposure.txt on how equal bins are combined in front of the LDS add.  0 = one LDS add per pixel, 1 = a lane adds a run of equal
+// bins among its own pixels once, 2 (what ships) = that, and a wave whose lanes all hold the same (bin, count) adds it once.
+#ifndef BB_LUMA_FORM
+#define BB_LUMA_FORM 2
+#endif
+// `cnt` pixels of word `w` into the workgroup's histogram; called by any subset of a wave's lanes
+BB_DEV void luma_add(uint32_t *h, uint32_t w, uint32_t cnt) {
+#if BB_LUMA_FORM == 2
+  const unsigned long long here = __ballot(1);
+  const uint32_t w0 = __builtin_amdgcn_readfirstlane(w), c0 = __builtin_amdgcn_readfirstlane(cnt);
+  if (__ballot(w == w0 && cnt == c0) == here) {  // the expected case: one add for the wave
+    if ((uint32_t)__lane_id() == (uint32_t)__ffsll((long long)here) - 1u) atomicAdd(&h[w0], c0 * (uint32_t)__popcll(here));
+    return;
+  }
+#endif
+  atomicAdd(&h[w], cnt);
+}
+// a lane's kLumaPerThread words (kLumaSkip: no pixel) into the workgroup's histogram
+BB_DEV void luma_count(uint32_t *h, const uint32_t (&w)[kLumaPerThread]) {
+#if BB_LUMA_FORM == 0
+#pragma unroll
+  for (int j = 0; j < kLumaPerThread; ++j)
+    if (w[j] != kLumaSkip) atomicAdd(&h[w[j]], 1u);
+#else
+  uint32_t run = kLumaSkip, cnt = 0u;
+#pragma unroll
+  for (int j = 0; j < kLumaPerThread; ++j) {
+    if (w[j] == run) {
+      ++cnt;
+    } else {
+      if (run != kLumaSkip) luma_add(h, run, cnt);
+      run = w[j], cnt = 1u;
+    }
+  }
+  if (run != kLumaSkip) luma_add(h, run, cnt);
+#endif
+}
+__global__ __launch_bounds__(kLumaThreads) void k_luminance(const float4 *__restrict__ frame, size_t n, uint32_t *__restrict__ hist) {
+  __shared__ uint32_t h[kLumaWords];
+  for (uint32_t w = threadIdx.x; w < (uint32_t)kLumaWords; w += kLumaThreads) h[w] = 0u;
+  __syncthreads();
+  const size_t base = (size_t)blockIdx.x * (kLumaThreads * kLumaPerThread) + threadIdx.x;
+  v4f px[kLumaPerThread];
+#pragma unroll
+  for (int j = 0; j < kLumaPerThread; ++j) {
+    const size_t i = base + (size_t)j * kLumaThreads;
+    px[j] = i < n ? reinterpret_cast<const v4f *>(frame)[i] : v4f{0.f, 0.f, 0.f, 0.f};
+  }
+  uint32_t w[kLumaPerThread];
+#pragma unroll
+  for (int j = 0; j < kLumaPerThread; ++j) w[j] = base + (size_t)j * kLumaThreads < n ? luma_word(px[j]) : kLumaSkip;
+  luma_count(h, w);
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < (uint32_t)kLumaWords; k += kLumaThreads)
+    if (const uint32_t v = h[k]) atomicAdd(&hist[k], v);
+}
+
+constexpr int kExposureThreads = kLumaBins;
+// the sum of v over the workgroup, in every lane (two barriers; `s` holds kExposureThreads words)
+BB_DEV unsigned long long exposure_sum(unsigned long long v, unsigned long long *s) {
+  __syncthreads();
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int d = kExposureThreads / 2; d > 0; d >>= 1) {
+    if ((int)threadIdx.x < d) s[threadIdx.x] += s[threadIdx.x + d];
+    __syncthreads();
+  }
+  return s[0];
+}
+// hist: the presentation's kLumaWords words; fallback: the frame's own Exposure, applied when nothing was counted and there is no history
+__global__ __launch_bounds__(kExposureThreads) void k_exposure(uint32_t *__restrict__ hist, ExposureRecord *__restrict__ rec,
+                                                                ExposureHistory *__restrict__ history, ExposureParams p, float fallback) {
+  __shared__ unsigned long long s[kExposureThreads];
+  __shared__ uint32_t scan[kExposureThreads];
+  const int k = (int)threadIdx.x;
+  const uint32_t mine = hist[k];
+  // P_k + hist[k]: an inclusive scan (the counts sum to at most 2^30 pixels: 32 bits hold every partial sum)
+  scan[k] = mine;
+  __syncthreads();
+  for (int d = 1; d < kExposureThreads; d <<= 1) {
+    const uint32_t below = k >= d ? scan[k - d] : 0u;
+    __syncthreads();
+    scan[k] += below;
+    __syncthreads();
+  }
+  const long long above = (long long)scan[k], below = above - (long long)mine;
+  const long long n = (long long)scan[kExposureThreads - 1];
+  const long long skip_lo = n * p.lo / 1000, skip_hi = n * (1000 - p.hi) / 1000;
+  const long long c = max(0ll, min(above, n - skip_hi) - max(below, skip_lo));
+  const unsigned long long kept = exposure_sum((unsigned long long)c, s);
+  const unsigned long long sum = exposure_sum((unsigned long long)c * (unsigned long long)k, s);
+  rec->hist[k] = mine;
+  hist[k] = 0u;
+  if (k != 0) return;
+  const uint32_t ignored = hist[kLumaBins];
+  hist[kLumaBins] = 0u;
+  const ExposureHistory past = *history;
+  uint32_t mean_bits = 0u;
+  float target = 0.f, clamped = 0.f, applied;
+  if (n > 0) {
+    mean_bits = ((uint32_t)kLumaFirstBin << 20) + (uint32_t)((sum << 20) / kept) + (1u << 19);
+    // the centre of a bin of [2^-16, 2^16): a normal number with a normal reciprocal, bb_rcp_normal's correctly rounded range
+    const float r = bb_rcp_normal(__uint_as_float(mean_bits));
+    target = __fmul_rn(p.key, r);
+    clamped = __builtin_fminf(__builtin_fmaxf(target, p.e_min), p.e_max);
+    applied = (past.valid && p.rate != 1.0f) ? __fadd_rn(past.value, __fmul_rn(__fsub_rn(clamped, past.value), p.rate)) : clamped;
+    *history = ExposureHistory{applied, 1u};
+  } else {
+    applied = past.valid ? past.value : fallback;
+  }
+  rec->ignored = ignored, rec->counted = (uint32_t)n, rec->kept = (uint32_t)kept, rec->mean_bits = mean_bits;
+  rec->sum = sum;
+  rec->target = target, rec->clamped = clamped, rec->previous = past.valid ? past.value : 0.f, rec->applied = applied;
+  rec->flags = (past.valid ? 1u : 0u) | (n > 0 ? 0u : 2u);
+  rec->reserved = 0u;
+}
+
+// k_present / k_present_bloom with the exposure of the presentation's record in the argument's place: one uniform load per workgroup
+__global__ __launch_bounds__(kPresentThreads) void k_present_auto(const float4 *__restrict__ frame, uint32_t *__restrict__ out_rgba8,
+                                                                   size_t n, const SrgbTables *__restrict__ tables, int enable,
+                                                                   const float *__restrict__ exposure, int hdr16) {
+  present_body(frame, out_rgba8, n, tables, enable, *exposure, hdr16);
+}
+__global__ __launch_bounds__(kBloomThreads) void k_present_bloom_auto(const float4 *__restrict__ frame, const float4 *__restrict__ u1,
+                                                                       int32_t w1, int32_t h1, uint32_t *__restrict__ out_rgba8,
+                                                                       int32_t width, const SrgbTables *__restrict__ tables,
+                                                                       int enable, const float *__restrict__ exposure, int hdr16,
+                                                                       float intensity) {
+  present_bloom_body(frame, u1, w1, h1, out_rgba8, width, tables, enable, *exposure, hdr16, intensity);
+}
 // ------------------------------------------------------------------------------------------------
 // multisampling (option "sample_shading" 0 with "supersample" n = 2 or 4): one fragment is shaded per primitive and output
 // pixel.  The block of output pixel (x, y) is the fine pixels (nx + i, ny + j), indexed k = j * n + i; P(s) is the primitive

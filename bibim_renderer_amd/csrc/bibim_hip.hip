@@ -309,6 +309,9 @@ struct FrameSlot : TileSized, ExtentSized {
     void *copy_to = nullptr;  // fused presentation: the caller's buffer the image was copied to
     int32_t enable = 0, hdr16 = 1;
     float exposure = 1.f;
+    // option "auto_exposure": the presentation was queued under it (the image is made with the exposure in the slot's record),
+    // and the frame has been metered (a presentation the library repeats converts with that exposure again and meters nothing)
+    bool auto_e = false, metered = false;
   } present;
   int bloom_ran = 0;  // the levels of the chain that last ran on d_bloom for the frame in this slot (0: none; bbr_read_bloom_level)
   Event ev_geom_done, ev_raster_done, ev_tail_done;  // edges between the streams of a frame
@@ -588,6 +591,28 @@ struct bbr_context : ExtentDumps {
     int ran = 0;       // extent and levels of the last call's chain (0: none; bbr_read_bloom_level source 1)
   } bloom_buffer;
   PairRing bloom_ring;  // around each chain (k_bloom_first .. the last k_bloom_up) while timing is on
+  // option "auto_exposure" (the rule: bibim_hip.h "auto exposure"): 1 = bbr_present meters the frame (k_luminance, k_exposure)
+  // and converts it with the exposure that leaves on the device (k_present_auto / k_present_bloom_auto)
+  int auto_exposure = 0;
+  ExposureParams exposure_params = {0.18f, 0.0009765625f, 1024.0f, 1.0f, 500, 950};  // bbr_set_auto_exposure: stored at either value
+  // Everything of the option on the device, alive while it is 1.  A "unit" is what one presentation in flight owns: a
+  // histogram (zero between uses: k_exposure leaves it so) and a record; one per frame slot, and one (kBufferUnit) for
+  // bbr_present_buffer_auto.  The two histories are shared by the presentations of a source, so their k_exposure are
+  // ordered one behind the other on the device through an event, whatever their streams.
+  struct ExposureOwned {
+    static constexpr int kBufferUnit = kMaxSlots, kUnits = kMaxSlots + 1;
+    DeviceBuffer<uint32_t> d_hist;            // kUnits x kLumaWords
+    DeviceBuffer<ExposureRecord> d_records;   // kUnits
+    DeviceBuffer<ExposureHistory> d_history;  // source 0 (bbr_present), source 1 (bbr_present_buffer_auto)
+    Event ev_adapted;       // behind the k_exposure of source 0's last presentation
+    bool adapted = false;   // ... recorded
+    Event ev_buffer;        // behind the present kernel of the last bbr_present_buffer_auto (its unit is free again)
+    bool buffer_used = false;
+    int last_slot = -1;     // the slot of source 0's last presentation (bbr_read_exposure), -1: none
+    uint32_t *hist(int unit) const { return d_hist.ptr + (size_t)unit * kLumaWords; }
+    ExposureRecord *record(int unit) const { return d_records.ptr + unit; }
+  } exposure;
+  PairRing luminance_ring;  // around each k_luminance while timing is on (k_exposure falls into present_ring's interval)
   PairRing resolve_ring;  // around the k_resolve of each timed frame: pair i is ring frame i's (the two counts are reset together)
   static constexpr uint32_t kRingCap = ::kRingCap;
   static constexpr uint32_t kRingEvents = 5;
@@ -724,6 +749,9 @@ bool refused_shadow_pair(int64_t mip_levels, int64_t shadow_map) { return mip_le
 // ... and option "bloom"'s two: a rank's shard lacks the rows its neighbours own, and a fused frame is no fp32 frame
 bool refused_bloom_partition(int64_t bloom, int64_t world) { return bloom >= 1 && world > 1; }
 bool refused_bloom_fused(int64_t bloom, int64_t present_fused) { return bloom >= 1 && present_fused != 0; }
+// ... and option "auto_exposure"'s two: metering needs the whole frame, and a fused frame needs its exposure before it exists
+bool refused_auto_partition(int64_t auto_exposure, int64_t world) { return auto_exposure != 0 && world > 1; }
+bool refused_auto_fused(int64_t auto_exposure, int64_t present_fused) { return auto_exposure != 0 && present_fused != 0; }
 // the render extent n * width x n * height has the limit of the output extent (bbr_create)
 constexpr int32_t kMaxExtent = 32768;
 constexpr int32_t kMaxShadowMap = 8192;  // option "shadow_map": 256 x 256 tiles of 32 x 32, the launch-slot limit of a frame
@@ -1864,6 +1892,7 @@ int submit_frame_body(bbr_context *c, int slot_index) {
   s.present.exposure = c->frame_u.exposure;
   s.present.hdr16 = 1;
   s.present.copy_to = nullptr;
+  s.present.auto_e = s.present.metered = false;
   s.frame_u = c->frame_u;
   s.view_u = c->view_u;
   s.out_used = out;
@@ -1938,10 +1967,69 @@ struct BloomShape {
     }
   }
 };
+// Option "auto_exposure", the two launches in front of a presentation's conversion, on its stream `ps`.  A unit is a frame
+// slot's index or ExposureOwned::kBufferUnit.
+// k_luminance: the n pixels of `frame` into the unit's histogram (zero on entry).  luminance_ring holds its interval.
+int queue_luminance(bbr_context *c, hipStream_t ps, int unit, const float4 *frame, size_t n) {
+  if (c->timing) {
+    HIP_TRY(c, c->luminance_ring.ensure());
+    HIP_TRY(c, c->luminance_ring.begin(ps));
+  }
+  const size_t per_block = (size_t)kLumaThreads * kLumaPerThread;
+  hipLaunchKernelGGL(k_luminance, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(kLumaThreads), 0, ps, frame, n, c->exposure.hist(unit));
+  HIP_TRY(c, hipGetLastError());
+  if (c->timing) HIP_TRY(c, c->luminance_ring.end(ps));
+  return BBR_OK;
+}
+// k_exposure: the unit's histogram into its record and into the history of `source`.  Source 0's presentations run on the
+// streams of their slots: each adapt step waits on the device for the one before it (the host never does).  Source 1's calls
+// are ordered as a whole (bbr_present_buffer_auto).  `fallback`: the exposure of a frame with nothing to count and no history.
+int queue_exposure(bbr_context *c, hipStream_t ps, int unit, int source, float fallback) {
+  bbr_context::ExposureOwned &x = c->exposure;
+  if (source == 0) {
+    HIP_TRY(c, x.ev_adapted.ensure(hipEventDisableTiming));
+    if (x.adapted) HIP_TRY(c, hipStreamWaitEvent(ps, x.ev_adapted, 0));
+  }
+  hipLaunchKernelGGL(k_exposure, dim3(1), dim3(kExposureThreads), 0, ps, x.hist(unit), x.record(unit), x.d_history.ptr + source,
+                     c->exposure_params, fallback);
+  HIP_TRY(c, hipGetLastError());
+  if (source == 0) {
+    HIP_TRY(c, hipEventRecord(x.ev_adapted, ps));
+    x.adapted = true;
+  }
+  return BBR_OK;
+}
+// A presentation failed between its k_luminance and its k_exposure: the unit's histogram goes back to zero behind whatever
+// was queued, so the unit's next presentation counts its own pixels only (best effort: the failure is what gets reported)
+void abandon_metering(bbr_context *c, hipStream_t ps, int unit) {
+  (void)hipMemsetAsync(c->exposure.hist(unit), 0, kLumaWords * sizeof(uint32_t), ps);
+}
+// k_present (k_present_auto with `d_exposure`) over n pixels on `ps`; `adapt` as in queue_bloom_present
+template <class Adapt>
+int queue_plain_present(bbr_context *c, hipStream_t ps, const float4 *frame, uint32_t *out, size_t n, int enable, float exposure, int hdr16,
+                        const float *d_exposure, Adapt &&adapt) {
+  if (c->timing) {
+    HIP_TRY(c, c->present_ring.ensure());
+    HIP_TRY(c, c->present_ring.begin(ps));
+  }
+  if (int rc = adapt()) return rc;
+  const dim3 grid((unsigned)((n + (size_t)kPresentThreads * kPresentPerThread - 1) / ((size_t)kPresentThreads * kPresentPerThread)));
+  if (d_exposure)
+    hipLaunchKernelGGL(k_present_auto, grid, dim3(kPresentThreads), 0, ps, frame, out, n, c->d_srgb_tables.ptr, enable, d_exposure, hdr16);
+  else
+    hipLaunchKernelGGL(k_present, grid, dim3(kPresentThreads), 0, ps, frame, out, n, c->d_srgb_tables.ptr, enable, exposure, hdr16);
+  HIP_TRY(c, hipGetLastError());
+  if (c->timing) HIP_TRY(c, c->present_ring.end(ps));
+  return BBR_OK;
+}
+
 // The chain over `frame` into `levels` (afterwards U_1 .. U_L), then k_present_bloom into `out`: everything on `ps`.
 // bloom_ring holds the chain's interval, present_ring k_present_bloom's, as it holds k_present's.
+// `d_exposure` (option "auto_exposure"): the exposure is read there by k_present_bloom_auto, and k_exposure is queued between
+// the chain and that kernel (`meter`), inside present_ring's interval.
+template <class Meter>
 int queue_bloom_present(bbr_context *c, hipStream_t ps, const float4 *frame, uint32_t *out, const BloomShape &sh, float4 *levels,
-                        int enable, float exposure, int hdr16) {
+                        int enable, float exposure, int hdr16, const float *d_exposure, Meter &&adapt) {
   auto grid = [](int32_t w, int32_t h) { return dim3((unsigned)((w + kBloomThreads - 1) / kBloomThreads), (unsigned)h); };
   auto level = [&](int k) { return levels + sh.at[k]; };
   if (c->timing) {
@@ -1962,42 +2050,88 @@ int queue_bloom_present(bbr_context *c, hipStream_t ps, const float4 *frame, uin
     HIP_TRY(c, c->bloom_ring.end(ps));
     HIP_TRY(c, c->present_ring.begin(ps));
   }
-  hipLaunchKernelGGL(k_present_bloom, grid(sh.w[0], sh.h[0]), dim3(kBloomThreads), 0, ps, frame, (const float4 *)level(1), sh.w[1], sh.h[1],
-                     out, sh.w[0], c->d_srgb_tables.ptr, enable, exposure, hdr16, c->bloom_intensity);
+  if (int rc = adapt()) return rc;
+  if (d_exposure)
+    hipLaunchKernelGGL(k_present_bloom_auto, grid(sh.w[0], sh.h[0]), dim3(kBloomThreads), 0, ps, frame, (const float4 *)level(1), sh.w[1],
+                       sh.h[1], out, sh.w[0], c->d_srgb_tables.ptr, enable, d_exposure, hdr16, c->bloom_intensity);
+  else
+    hipLaunchKernelGGL(k_present_bloom, grid(sh.w[0], sh.h[0]), dim3(kBloomThreads), 0, ps, frame, (const float4 *)level(1), sh.w[1], sh.h[1],
+                       out, sh.w[0], c->d_srgb_tables.ptr, enable, exposure, hdr16, c->bloom_intensity);
   HIP_TRY(c, hipGetLastError());
   if (c->timing) HIP_TRY(c, c->present_ring.end(ps));
   return BBR_OK;
 }
 
 // k_present for the frame in slot `s`, on the shade stream (ordered after the frame's k_shade); option "bloom" >= 1: the
-// chain on the slot's own pyramid and k_present_bloom in its place (no partition then: the shard is the W x H frame)
+// chain on the slot's own pyramid and k_present_bloom in its place (no partition then: the shard is the W x H frame).
+// Option "auto_exposure": a presentation queued under it converts with the exposure in the slot's record; the first one of
+// the frame in the slot meters it in front (k_luminance, then the chain, then k_exposure: the chain does not need the
+// exposure and runs while the adapt step of the presentation before may still be awaited).
 int queue_present(bbr_context *c, FrameSlot &s) {
   int rc_tables = ensure_srgb_tables(c);
   if (rc_tables) return rc_tables;
   const size_t n = c->shard_pixels();
   const hipStream_t ps = c->slot_present_stream(s);
-  if (c->bloom) {
-    const BloomShape sh(c->width, c->height, c->bloom);
-    HIP_TRY(c, s.d_bloom.ensure(sh.texels));  // (grows only behind a drain: at the slot's first bloomed present)
-    if (ps != s.stream_used) HIP_TRY(c, s.follow(ps));
-    if (int rc = queue_bloom_present(c, ps, s.out_used, s.present.out, sh, s.d_bloom.ptr, s.present.enable, s.present.exposure, s.present.hdr16))
-      return rc;
-    s.bloom_ran = sh.levels;
-    HIP_TRY(c, s.busy_until(ps));
-    return BBR_OK;
-  }
+  const int unit = (int)(&s - c->slots);
+  const bool meter = s.present.auto_e && !s.present.metered;
+  const float *d_exposure = s.present.auto_e ? &c->exposure.record(unit)->applied : nullptr;
+  if (c->bloom) HIP_TRY(c, s.d_bloom.ensure(BloomShape(c->width, c->height, c->bloom).texels));  // (grows only behind a drain: at the slot's first bloomed present)
   if (ps != s.stream_used) HIP_TRY(c, s.follow(ps));  // behind the frame's k_shade
-  if (c->timing) {
-    HIP_TRY(c, c->present_ring.ensure());
-    HIP_TRY(c, c->present_ring.begin(ps));
+  bool adapted = false;  // k_exposure is queued: it leaves the histogram zeroed
+  auto adapt = [&]() -> int {
+    const int rc = meter ? queue_exposure(c, ps, unit, 0, s.present.exposure) : (int)BBR_OK;
+    adapted = rc == BBR_OK;
+    return rc;
+  };
+  int rc = meter ? queue_luminance(c, ps, unit, s.out_used, n) : (int)BBR_OK;
+  if (rc == BBR_OK && c->bloom) {
+    const BloomShape sh(c->width, c->height, c->bloom);
+    rc = queue_bloom_present(c, ps, s.out_used, s.present.out, sh, s.d_bloom.ptr, s.present.enable, s.present.exposure, s.present.hdr16, d_exposure, adapt);
+    if (rc == BBR_OK) s.bloom_ran = sh.levels;
+  } else if (rc == BBR_OK) {
+    rc = queue_plain_present(c, ps, s.out_used, s.present.out, n, s.present.enable, s.present.exposure, s.present.hdr16, d_exposure, adapt);
   }
-  const size_t per_block = (size_t)kPresentThreads * kPresentPerThread;
-  hipLaunchKernelGGL(k_present, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(kPresentThreads), 0,
-                     ps, s.out_used, s.present.out, n, c->d_srgb_tables.ptr, s.present.enable,
-                     s.present.exposure, s.present.hdr16);
-  HIP_TRY(c, hipGetLastError());
-  if (c->timing) HIP_TRY(c, c->present_ring.end(ps));
+  if (rc != BBR_OK) {
+    if (meter && !adapted) abandon_metering(c, ps, unit);
+    return rc;
+  }
+  if (meter) {
+    s.present.metered = true;
+    c->exposure.last_slot = unit;
+  }
   HIP_TRY(c, s.busy_until(ps));  // ... until the presented image exists
+  return BBR_OK;
+}
+
+// The checks the buffer calls with an extent share
+int check_present_buffer(bbr_context *c, const char *who, const void *rgba32f_device, const void *rgba8_device, int32_t width, int32_t height) {
+  if (!rgba32f_device || !rgba8_device) return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL");
+  if ((uintptr_t)rgba32f_device % 16 || (uintptr_t)rgba8_device % 4)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": the source must be 16-byte aligned, the output 4-byte aligned");
+  if (width < 1 || height < 1 || width > kMaxExtent || height > kMaxExtent)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, std::string(who) + ": width/height out of range (1 .. 32768)");
+  return BBR_OK;
+}
+// The chain and the bloomed conversion of a caller's frame on the context's one pyramid (option "bloom" >= 1); `d_exposure`
+// and `adapt` as in queue_bloom_present
+template <class Adapt>
+int queue_buffer_bloom(bbr_context *c, hipStream_t ps, const void *rgba32f_device, void *rgba8_device, int32_t width, int32_t height,
+                              int32_t enable, float exposure, int32_t hdr16, const float *d_exposure, Adapt &&adapt) {
+  bbr_context::BloomBuffer &b = c->bloom_buffer;
+  const BloomShape sh(width, height, c->bloom);
+  HIP_TRY(c, b.ev_used.ensure(hipEventDisableTiming));
+  // the one pyramid is never used twice at once: this call's stream waits for the call before it; a pyramid that has to grow
+  // is freed only once that call has left the GPU
+  if (b.used && sh.texels > b.d_levels.cap) HIP_TRY(c, hipEventSynchronize(b.ev_used));
+  HIP_TRY(c, b.d_levels.ensure(sh.texels));
+  if (b.used) HIP_TRY(c, hipStreamWaitEvent(ps, b.ev_used, 0));
+  b.ran = 0;
+  if (int rc = queue_bloom_present(c, ps, (const float4 *)rgba32f_device, (uint32_t *)rgba8_device, sh, b.d_levels.ptr, enable, exposure, hdr16 != 0,
+                                   d_exposure, adapt))
+    return rc;
+  HIP_TRY(c, hipEventRecord(b.ev_used, ps));
+  b.used = true;
+  b.w = width, b.h = height, b.ran = sh.levels;
   return BBR_OK;
 }
 
@@ -3218,6 +3352,8 @@ int bbr_set_partition(bbr_context *c, int32_t rank, int32_t world, int32_t band_
   if (band_rows % c->tile_h()) return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_partition: band_rows must be a multiple of the tile height");
   if (refused_bloom_partition(c->bloom, world))
     return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_partition: world > 1 is not available with option bloom >= 1 (the chain needs its neighbours' rows)");
+  if (refused_auto_partition(c->auto_exposure, world))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_partition: world > 1 is not available with option auto_exposure 1 (metering needs the whole frame: bbr_present_buffer_auto on the gathered one)");
   int rc = drain(c);
   if (rc) return rc;
   c->rank = rank;
@@ -3251,6 +3387,7 @@ static void drop_extent_buffers(bbr_context *c) {
     s.present.active = false;
     s.present.out = nullptr;
     s.present.copy_to = nullptr;
+    s.present.auto_e = s.present.metered = false;
     s.bloom_ran = 0;
     s.out_used = nullptr;
     s.in_flight = false;
@@ -3262,6 +3399,7 @@ static void drop_extent_buffers(bbr_context *c) {
   drop<bbr_context::TbnRecords>(c->tbn_pass);
   drop<ExtentDumps>(*c);
   c->bloom_buffer = bbr_context::BloomBuffer();
+  c->exposure.last_slot = -1;  // (the histories are no extent's: they stay)
   forget_current_frame(c);  // (the whole frame of the last exchange had the old extent, too)
 }
 
@@ -3277,6 +3415,7 @@ int bbr_resize(bbr_context *c, int32_t width, int32_t height) {
   int rc = drain(c);
   if (rc) return rc;
   forget_image(c);
+  c->exposure.last_slot = -1;
   if (width == c->width && height == c->height) return BBR_OK;
   c->width = width;
   c->height = height;
@@ -3634,6 +3773,7 @@ int bbr_timing_reset(bbr_context *c) {
   c->ring_frames = 0;
   c->present_ring.reset();
   c->bloom_ring.reset();
+  c->luminance_ring.reset();
   c->resolve_ring.reset();
   return BBR_OK;
 }
@@ -3709,6 +3849,7 @@ int set_timing(bbr_context *c, int64_t value) {
   c->ring_frames = 0;  // (see bbr_timing_reset on what each of the three reset sites resets)
   c->present_ring.reset();
   c->bloom_ring.reset();
+  c->luminance_ring.reset();
   c->resolve_ring.reset();
   c->timing_tick = 0;
   return BBR_OK;
@@ -3816,7 +3957,37 @@ int set_surface_keep(bbr_context *c, int64_t value) {
   }
   return store<&bbr_context::surface_keep>(c, value);
 }
+// 1: the device buffers of the option come (zeroed: no history, empty histograms).  0: nothing of it stays -- a slot whose
+// image was made under it keeps the exposure it was made with as a plain number, so whatever presents its frame again makes
+// the same image.  The context is drained.
+int set_auto_exposure(bbr_context *c, int64_t value) {
+  if (refused_auto_partition(value, c->world))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "auto_exposure: not available on a partition of world > 1 (metering needs the whole frame: bbr_present_buffer_auto on the gathered one)");
+  if (refused_auto_fused(value, c->present_fused))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "auto_exposure: not available with option present_fused (the exposure would be needed before the frame exists)");
+  using X = bbr_context::ExposureOwned;
+  X &x = c->exposure;
+  if (value && !c->auto_exposure) {
+    X fresh;
+    HIP_TRY(c, fresh.d_hist.ensure((size_t)X::kUnits * kLumaWords, true));
+    HIP_TRY(c, fresh.d_records.ensure(X::kUnits, true));
+    HIP_TRY(c, fresh.d_history.ensure(2, true));
+    x = std::move(fresh);
+  } else if (!value && c->auto_exposure) {
+    for (int k = 0; k < bbr_context::kMaxSlots; ++k) {
+      FrameSlot &s = c->slots[k];
+      if (s.present.auto_e && s.present.metered)
+        HIP_TRY(c, hipMemcpy(&s.present.exposure, &x.record(k)->applied, sizeof(float), hipMemcpyDeviceToHost));
+      s.present.auto_e = s.present.metered = false;
+    }
+    x = X();
+    c->luminance_ring = PairRing();
+  }
+  return store<&bbr_context::auto_exposure>(c, value);
+}
 int set_present_fused(bbr_context *c, int64_t value) {
+  if (refused_auto_fused(c->auto_exposure, value))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_fused: not available with option auto_exposure 1 (the exposure would be needed before the frame exists)");
   if (refused_bloom_fused(c->bloom, value))
     return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_fused: not available with option bloom >= 1 (there is no fp32 frame)");
   return store<&bbr_context::present_fused>(c, value);
@@ -3868,6 +4039,7 @@ const OptionRow kOptions[] = {
     {"surface_keep", 0, 1 << 20, 0, ": 0 (off) or n >= 1 (a slot's n-th kept frame in a row stores its shaded surface; it and those behind it are lit from it)", kWaits, kLeaves, set_surface_keep},
     {"present_fused", -kAny - 1, kAny, 0, "", kWaits, kForgets, set_present_fused},  // (any value: non-zero is on)
     {"bloom", 0, kMaxBloomLevels, 0, ": 0 (off) or the levels of the pyramid, 1 .. 8", kWaits, kLeaves, set_bloom},
+    {"auto_exposure", 0, 1, 0, ": 0 (the frame's own Exposure) or 1 (metered on the device)", kWaits, kLeaves, set_auto_exposure},
     {"overlays", -kAny - 1, kAny, 0, "", kWaits, kForgets, store<&Ctx::overlays>},
     {"tbn", -kAny - 1, kAny, 0, "", kWaits, kForgets, store<&Ctx::tbn>},
     {"stream_layout", 0, Ctx::kLayouts - 1, 0, ": 0, 1 or 2", kWaits, kForgets, store<&Ctx::layout_mode>},
@@ -3934,6 +4106,8 @@ int bbr_present(bbr_context *c, void *rgba8_device, int32_t hdr16) {
   s.present.enable = s.frame_u.enable_tone_mapping;  // of the frame in the slot, not the uniforms set since
   s.present.exposure = s.frame_u.exposure;
   s.present.hdr16 = hdr16 != 0;
+  s.present.auto_e = c->auto_exposure != 0;  // every call of the host is one presentation: it meters and adapts
+  s.present.metered = false;
   return queue_present(c, s);
 }
 
@@ -3977,30 +4151,12 @@ int bbr_present_buffer_bloom(bbr_context *c, const void *rgba32f_device, void *r
                              int32_t enable, float exposure, int32_t hdr16, void *stream) {
   if (!c) return BBR_ERR_INVALID_ARGUMENT;
   BBR_ON_DEVICE(c);
-  if (!rgba32f_device || !rgba8_device) return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_buffer_bloom: NULL");
-  if ((uintptr_t)rgba32f_device % 16 || (uintptr_t)rgba8_device % 4)
-    return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_buffer_bloom: the source must be 16-byte aligned, the output 4-byte aligned");
-  if (width < 1 || height < 1 || width > kMaxExtent || height > kMaxExtent)
-    return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_buffer_bloom: width/height out of range (1 .. 32768)");
+  if (int rc = check_present_buffer(c, "present_buffer_bloom", rgba32f_device, rgba8_device, width, height)) return rc;
   if (!c->bloom)
     return bbr_present_buffer(c, rgba32f_device, rgba8_device, (uint64_t)width * (uint64_t)height, enable, exposure, hdr16, stream);
   if (int rc = ensure_srgb_tables(c)) return rc;
-  bbr_context::BloomBuffer &b = c->bloom_buffer;
-  const BloomShape sh(width, height, c->bloom);
-  HIP_TRY(c, b.ev_used.ensure(hipEventDisableTiming));
-  // the one pyramid is never used twice at once: this call's stream waits for the call before it; a pyramid that has to grow
-  // is freed only once that call has left the GPU
   const hipStream_t ps = stream ? (hipStream_t)stream : c->shade_stream();
-  if (b.used && sh.texels > b.d_levels.cap) HIP_TRY(c, hipEventSynchronize(b.ev_used));
-  HIP_TRY(c, b.d_levels.ensure(sh.texels));
-  if (b.used) HIP_TRY(c, hipStreamWaitEvent(ps, b.ev_used, 0));
-  b.ran = 0;
-  if (int rc = queue_bloom_present(c, ps, (const float4 *)rgba32f_device, (uint32_t *)rgba8_device, sh, b.d_levels.ptr, enable, exposure, hdr16 != 0))
-    return rc;
-  HIP_TRY(c, hipEventRecord(b.ev_used, ps));
-  b.used = true;
-  b.w = width, b.h = height, b.ran = sh.levels;
-  return BBR_OK;
+  return queue_buffer_bloom(c, ps, rgba32f_device, rgba8_device, width, height, enable, exposure, hdr16, nullptr, [] { return (int)BBR_OK; });
 }
 
 int bbr_read_bloom_level(bbr_context *c, int32_t source, int32_t level, float *out_rgb, uint64_t capacity, int32_t *out_w, int32_t *out_h) {
@@ -4035,6 +4191,106 @@ int bbr_read_bloom_level(bbr_context *c, int32_t source, int32_t level, float *o
 
 int bbr_bloom_timing(bbr_context *c, uint32_t *out_launches, float *out_avg_ms) {
   return pair_ring_timing(c, &bbr_context::bloom_ring, "bloom_timing", out_launches, out_avg_ms);
+}
+
+int bbr_set_auto_exposure(bbr_context *c, float key, float e_min, float e_max, float rate, int32_t lo_permille, int32_t hi_permille) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (!std::isfinite(key) || !std::isfinite(e_min) || !std::isfinite(e_max) || !std::isfinite(rate) || !(key > 0.f) || !(e_min > 0.f) ||
+      !(e_min <= e_max) || !(rate >= 0.f && rate <= 1.f))
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_auto_exposure: every float finite, key > 0, 0 < e_min <= e_max, 0 <= rate <= 1");
+  if (lo_permille < 0 || lo_permille >= hi_permille || hi_permille > 1000)
+    return fail(c, BBR_ERR_INVALID_ARGUMENT, "set_auto_exposure: 0 <= lo_permille < hi_permille <= 1000");
+  // No wait: k_exposure takes the parameters by value at its launch, so the presentations already queued keep theirs and the
+  // next one has these (a host sets `rate` from its clock every frame)
+  c->exposure_params = ExposureParams{key, e_min, e_max, rate, lo_permille, hi_permille};
+  return BBR_OK;
+}
+
+int bbr_get_auto_exposure(bbr_context *c, float *out_key, float *out_e_min, float *out_e_max, float *out_rate,
+                          int32_t *out_lo_permille, int32_t *out_hi_permille) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  const ExposureParams &p = c->exposure_params;
+  if (out_key) *out_key = p.key;
+  if (out_e_min) *out_e_min = p.e_min;
+  if (out_e_max) *out_e_max = p.e_max;
+  if (out_rate) *out_rate = p.rate;
+  if (out_lo_permille) *out_lo_permille = p.lo;
+  if (out_hi_permille) *out_hi_permille = p.hi;
+  return BBR_OK;
+}
+
+int bbr_reset_exposure(bbr_context *c) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (int rc = drain(c)) return rc;
+  for (FrameSlot &s : c->slots) s.forget_sky();
+  if (c->auto_exposure) HIP_TRY(c, zero_fill_sync(c->exposure.d_history.ptr, 2 * sizeof(ExposureHistory)));
+  return BBR_OK;
+}
+
+int bbr_present_buffer_auto(bbr_context *c, const void *rgba32f_device, void *rgba8_device, int32_t width, int32_t height,
+                            int32_t enable, float exposure, int32_t hdr16, void *stream) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (int rc = check_present_buffer(c, "present_buffer_auto", rgba32f_device, rgba8_device, width, height)) return rc;
+  if (!c->auto_exposure) return fail(c, BBR_ERR_INVALID_ARGUMENT, "present_buffer_auto: option auto_exposure is 0");
+  if (int rc = ensure_srgb_tables(c)) return rc;
+  using X = bbr_context::ExposureOwned;
+  X &x = c->exposure;
+  const hipStream_t ps = stream ? (hipStream_t)stream : c->shade_stream();
+  // the calls share one unit and history 1: each is ordered behind the one before it, whatever their streams
+  HIP_TRY(c, x.ev_buffer.ensure(hipEventDisableTiming));
+  if (x.buffer_used) HIP_TRY(c, hipStreamWaitEvent(ps, x.ev_buffer, 0));
+  const size_t n = (size_t)width * (size_t)height;
+  const float *d_exposure = &x.record(X::kBufferUnit)->applied;
+  bool adapted = false;  // k_exposure is queued: it leaves the histogram zeroed
+  auto adapt = [&] {
+    const int rc = queue_exposure(c, ps, X::kBufferUnit, 1, exposure);
+    adapted = rc == BBR_OK;
+    return rc;
+  };
+  int rc = queue_luminance(c, ps, X::kBufferUnit, (const float4 *)rgba32f_device, n);
+  if (rc == BBR_OK)
+    rc = c->bloom ? queue_buffer_bloom(c, ps, rgba32f_device, rgba8_device, width, height, enable, exposure, hdr16, d_exposure, adapt)
+                  : queue_plain_present(c, ps, (const float4 *)rgba32f_device, (uint32_t *)rgba8_device, n, enable, exposure, hdr16 != 0,
+                                        d_exposure, adapt);
+  if (rc != BBR_OK && !adapted) abandon_metering(c, ps, X::kBufferUnit);
+  // (recorded after a failure too: the next call is ordered behind whatever this one did queue)
+  const hipError_t recorded = hipEventRecord(x.ev_buffer, ps);
+  if (recorded == hipSuccess) x.buffer_used = true;
+  if (rc != BBR_OK) return rc;
+  HIP_TRY(c, recorded);
+  return BBR_OK;
+}
+
+int bbr_read_exposure(bbr_context *c, int32_t source, bbr_exposure_record *out) {
+  if (!c) return BBR_ERR_INVALID_ARGUMENT;
+  BBR_ON_DEVICE(c);
+  if (source != 0 && source != 1) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_exposure: source is 0 (bbr_present) or 1 (bbr_present_buffer_auto)");
+  if (!c->auto_exposure) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_exposure: option auto_exposure is 0");
+  if (!out) return fail(c, BBR_ERR_INVALID_ARGUMENT, "read_exposure: NULL");
+  using X = bbr_context::ExposureOwned;
+  const X &x = c->exposure;
+  int unit = X::kBufferUnit;
+  if (source == 0) {
+    if (x.last_slot < 0) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_exposure: bbr_present has not run under option auto_exposure");
+    if (int rc = sync_and_fix(c, nullptr)) return rc;  // (a frame rendered again is presented with its record's exposure: the record stays)
+    unit = x.last_slot;
+  } else {
+    if (!x.buffer_used) return fail(c, BBR_ERR_NOT_IN_FRAME, "read_exposure: bbr_present_buffer_auto has not run under option auto_exposure");
+    HIP_TRY(c, hipEventSynchronize(x.ev_buffer));
+  }
+  static_assert(sizeof(bbr_exposure_record) == sizeof(ExposureRecord) && offsetof(bbr_exposure_record, sum) == offsetof(ExposureRecord, sum) &&
+                    offsetof(bbr_exposure_record, applied) == offsetof(ExposureRecord, applied) &&
+                    offsetof(bbr_exposure_record, flags) == offsetof(ExposureRecord, flags),
+                "the record of the header is the record the kernels write");
+  HIP_TRY(c, hipMemcpy(out, x.record(unit), sizeof(ExposureRecord), hipMemcpyDeviceToHost));
+  return BBR_OK;
+}
+
+int bbr_luminance_timing(bbr_context *c, uint32_t *out_launches, float *out_avg_ms) {
+  return pair_ring_timing(c, &bbr_context::luminance_ring, "luminance_timing", out_launches, out_avg_ms);
 }
 
 int bbr_read_presented(bbr_context *c, uint8_t *host) {

@@ -502,6 +502,43 @@ class Renderer:
         self._check(self._L.bbr_bloom_timing(self._ctx, C.byref(n), C.byref(t)))
         return n.value, t.value
 
+    # -- auto exposure (option "auto_exposure" = 1: the exposure is metered on the device; the rule: bibim_hip.h "auto exposure") --
+    # bbr_exposure_record, field for field
+    EXPOSURE_RECORD = np.dtype([("hist", np.uint32, 256), ("ignored", np.uint32), ("counted", np.uint32), ("kept", np.uint32),
+                                ("mean_bits", np.uint32), ("sum", np.uint64), ("target", np.float32), ("clamped", np.float32),
+                                ("previous", np.float32), ("applied", np.float32), ("flags", np.uint32), ("reserved", np.uint32)])
+
+    def set_auto_exposure(self, key=0.18, e_min=2.0 ** -10, e_max=2.0 ** 10, rate=1.0, lo_permille=500, hi_permille=950):
+        self._check(self._L.bbr_set_auto_exposure(self._ctx, float(key), float(e_min), float(e_max), float(rate), int(lo_permille),
+                                                  int(hi_permille)))
+
+    def get_auto_exposure(self):
+        """(key, e_min, e_max, rate, lo_permille, hi_permille) as stored"""
+        k, a, b, r, lo, hi = C.c_float(), C.c_float(), C.c_float(), C.c_float(), C.c_int32(), C.c_int32()
+        self._check(self._L.bbr_get_auto_exposure(self._ctx, C.byref(k), C.byref(a), C.byref(b), C.byref(r), C.byref(lo), C.byref(hi)))
+        return k.value, a.value, b.value, r.value, lo.value, hi.value
+
+    def reset_exposure(self):
+        self._check(self._L.bbr_reset_exposure(self._ctx))
+
+    def present_buffer_auto(self, rgba32f_ptr, rgba8_ptr, width, height, enable, exposure, hdr16=True, stream=None):
+        """the auto exposure rule (and option "bloom") + presentation on any width x height RGBA32F device frame (asynchronous)"""
+        self._check(self._L.bbr_present_buffer_auto(self._ctx, C.c_void_p(rgba32f_ptr), C.c_void_p(rgba8_ptr), int(width),
+                                                    int(height), int(enable), float(exposure), int(bool(hdr16)),
+                                                    C.c_void_p(stream) if stream else None))
+
+    def read_exposure(self, source=0):
+        """the record of the last presentation of bbr_present (source 0) or bbr_present_buffer_auto (source 1): a dict of numpy values"""
+        rec = np.zeros(1, self.EXPOSURE_RECORD)
+        self._check(self._L.bbr_read_exposure(self._ctx, int(source), _ptr(rec)))
+        return {name: rec[name][0] for name in self.EXPOSURE_RECORD.names if name != "reserved"}
+
+    def luminance_timing(self):
+        """(k_luminance launches, average ms of one) since timing_reset(), option "timing" on"""
+        n, t = C.c_uint32(), C.c_float()
+        self._check(self._L.bbr_luminance_timing(self._ctx, C.byref(n), C.byref(t)))
+        return n.value, t.value
+
     def presented_device_ptr(self):
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self._L.bbr_presented_device_ptr(self._ctx, C.byref(p), C.byref(n)))

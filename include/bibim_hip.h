@@ -466,7 +466,13 @@ int bbr_timing_summary(bbr_context *ctx, uint32_t *out_frames, float *out_avg_fr
  *                            Setting it waits for the GPU like "max_anisotropy": the slots keep their visibility, the last
  *                            frame stays current, an image already presented is not redone.  Refused with a partition of
  *                            world > 1 and with "present_fused" non-zero, in either order.
- *   "ablate" bits           diagnostic builds only (make EXTRA=-DBB_ABLATE): skip parts of the pipeline */
+ *   "auto_exposure" 0|1      0 (default): presentation uses the frame's own Exposure; no kernel or buffer of the option exists.
+ *                            1: bbr_present meters the frame on the device and converts it with the exposure that follows (the
+ *                            rule and the calls: "auto exposure" below).  Setting it waits for the GPU like "bloom": the slots
+ *                            keep their visibility and their kept surfaces, the last frame stays current, an image already
+ *                            presented is not redone.  Setting 0 forgets the histories and frees the buffers.  Refused with a
+ *                            partition of world > 1 and with "present_fused" non-zero, in either order.
+ *   "ablate" bits          diagnostic builds only (make EXTRA=-DBB_ABLATE): skip parts of the pipeline */
 int bbr_set_option(bbr_context *ctx, const char *name, int64_t value);
 /* The stream layout in use (option "stream_layout"; 0 while only one frame is in flight).  *out_decided is always 1 and
  * out_ms[3] all zero: the layout is a plain option, nothing is timed at run time (round 1 did). */
@@ -908,6 +914,87 @@ int bbr_present_buffer_bloom(bbr_context *ctx, const void *rgba32f_device, void 
 int bbr_read_bloom_level(bbr_context *ctx, int32_t source, int32_t level, float *out_rgb, uint64_t capacity, int32_t *out_w,
                          int32_t *out_h);
 int bbr_bloom_timing(bbr_context *ctx, uint32_t *out_launches, float *out_avg_ms);
+
+/* ---- auto exposure (option "auto_exposure" = 1; no reference counterpart: the reference's Exposure is a slider) ----
+ * The exposure of a presentation follows from the pixels of the frame it presents, on the device: nothing is read back and
+ * the frames in flight stay in flight.  The fp32 frame is only read.
+ * The rule.  Every floating-point operation is one binary32 IEEE operation: round to nearest even, denormals kept, no
+ * contraction, no fma.  Everything about the histogram is integer arithmetic, so the result does not depend on the order in
+ * which pixels are counted and can be checked with no tolerance.  Source: F, the W x H RGBA32F frame bbr_present reads (the
+ * slot's output, the resolved frame under "supersample" >= 2, a caller's output buffer): the fp32 values in front of the
+ * binary16 stage and before bloom is added.  Alpha takes no part.
+ *   luma     Y = (0.2126f * r + 0.7152f * g) + 0.0722f * b
+ *   count    !(Y > 0)  (NaN, +-0, negative, -inf): the pixel is IGNORED.  Otherwise, u the bits of Y:
+ *            bin = clamp((int)(u >> 20) - 888, 0, 255)      8 bins per octave over [2^-16, 2^16);  888 = (127 - 16) * 8
+ *            denormals and everything below 2^-16 go to bin 0, everything >= 2^16, +inf included, to bin 255
+ *            hist[k] = the pixels in bin k;  N = sum hist[k];  ignored = W * H - N
+ *   trim     lo, hi in permille, 0 <= lo < hi <= 1000
+ *            skip_lo = floor(N * lo / 1000), skip_hi = floor(N * (1000 - hi) / 1000), in 64 bits
+ *            P_k = sum_{j<k} hist[j];   c_k = max(0, min(P_k + hist[k], N - skip_hi) - max(P_k, skip_lo))
+ *            N' = sum c_k  (= N - skip_lo - skip_hi, > 0 whenever N > 0);   S = sum k * c_k
+ *   mean     mean_bits = (888 << 20) + floor((S << 20) / N') + (1 << 19), in 64 bits: the centre of a bin, the fraction
+ *            carried into the mantissa.  Ybar = the binary32 with those bits: always normal, in [2^-16, 2^16).  This is the
+ *            log-average with log2(1 + t) taken as t, the device "mip_levels" already uses for lambda.
+ *   target   E* = key * r, r the correctly rounded 1 / Ybar;   E_c = min(max(E*, e_min), e_max)
+ *   adapt    with a history E_prev:  E = (rate == 1.0f) ? E_c : E_prev + (E_c - E_prev) * rate;   without one: E = E_c
+ *            The history becomes E.
+ *            N == 0: the history is left as it is, and E = the history if there is one, else the frame's own Exposure
+ *            (the caller's `exposure` in the buffer call); the record's mean_bits, target and clamped are 0 then.
+ *   image    the bytes of bbr_present's conversion with E in Exposure's place; under "bloom" L >= 1 of v = F + I * B as
+ *            without the option.  EnableToneMapping and hdr16 are as without it; with tone mapping off E is computed and unused.
+ * Histories and presentations.  A context has two histories, as bloom has two pyramids: source 0 is the frames bbr_present
+ * presents, source 1 is bbr_present_buffer_auto.  Every bbr_present call the host makes is one presentation, in call order:
+ * it meters, adapts and advances history 0.  Presentations of frames in different slots run on different streams; the adapt
+ * step of each is ordered behind that of the one before it on the device (an event; the host never waits).  A presentation the
+ * library repeats -- the re-render behind a capacity growth, the read-backs that render the frame again -- does not meter
+ * again: it converts with the E the slot's frame was first presented with and leaves the history alone.  Deviation, on
+ * purpose: a frame that overflowed a capacity was metered incomplete, and that E stays.
+ *   bbr_set_option(ctx, "auto_exposure", 0|1)   see the option list.  Both render passes, "supersample" 2..4 with either
+ *             "sample_shading", "bloom" 0..8, a caller's rgba8_device or output buffer, hdr16 0 and 1, one to four frames in
+ *             flight, every "stream_layout", bbr_set_stream and bbr_replay_frame; bbr_draw_overlays and bbr_draw_ui act on the
+ *             image as before.
+ *   bbr_set_auto_exposure   key, e_min, e_max, rate, lo and hi (permille).  Defaults 0.18f, 2^-10, 2^10, 1.0f, 500, 950.  Every
+ *             float finite, key > 0, 0 < e_min <= e_max, 0 <= rate <= 1, 0 <= lo < hi <= 1000; else BBR_ERR_INVALID_ARGUMENT
+ *             and nothing changes.  Stored at either value of the option.  Does not wait for the GPU and touches no slot: a
+ *             presentation takes the values stored when it is queued, so presentations in flight keep theirs and the next
+ *             call of bbr_present / bbr_present_buffer_auto has the new ones -- cheap enough to call every frame.
+ *             `rate` is per presentation: the host owns the clock and passes 1 - exp(-dt * speed).
+ *   bbr_get_auto_exposure   the six stored values (any pointer may be NULL).
+ *   bbr_reset_exposure      forgets both histories (the next presentation of each source applies its E_c).  Waits for the
+ *             GPU like the option.
+ *   bbr_present_buffer_auto   the rule on any W x H device frame, with history 1: how a host exposes the all-gathered whole
+ *             frame of a partition.  Honours option "bloom" exactly as bbr_present_buffer_bloom does, with the same
+ *             alignment and extent refusals; asynchronous on `hip_stream` (NULL = the context's shading stream), calls on
+ *             different streams ordered one behind the other by the library (an event).  `exposure` is used only when nothing
+ *             is counted and there is no history.  BBR_ERR_INVALID_ARGUMENT while the option is 0.
+ *   bbr_read_exposure   synchronises and returns the record of that source's last presentation.  BBR_ERR_NOT_IN_FRAME before
+ *             such a presentation under the option, and after bbr_resize for source 0; BBR_ERR_INVALID_ARGUMENT for a source
+ *             outside 0..1 or while the option is 0.
+ *   bbr_luminance_timing   sibling of bbr_present_timing.  With option "timing" on, k_luminance has a ring of its own: the
+ *             launches since bbr_timing_reset and the average duration of one.  k_exposure (and its wait for the adapt step of
+ *             the presentation before) falls into the interval bbr_present_timing reports.
+ * Refused, by whichever call would complete the pair, with the context unchanged: "auto_exposure" 1 with "present_fused"
+ * non-zero (the exposure would be needed before the frame exists) and on a partition of world > 1 (bbr_set_option /
+ * bbr_set_partition: metering needs the whole frame; the host meters the gathered frame with the buffer call).
+ * Memory: five histograms of 257 words, five records and two history words, from the option's set to 1 until it returns to 0
+ * or bbr_destroy; counted by bbr_debug_live_resources. */
+typedef struct bbr_exposure_record {
+  uint32_t hist[256];                       /* the pixels counted per bin */
+  uint32_t ignored, counted, kept;          /* W * H - N, N, N' */
+  uint32_t mean_bits;                       /* the bits of Ybar */
+  uint64_t sum;                             /* S */
+  float target, clamped, previous, applied; /* E*, E_c, E_prev (0 without a history), E */
+  uint32_t flags;                           /* bit 0: a history existed; bit 1: N == 0 */
+  uint32_t reserved;
+} bbr_exposure_record;
+int bbr_set_auto_exposure(bbr_context *ctx, float key, float e_min, float e_max, float rate, int32_t lo_permille, int32_t hi_permille);
+int bbr_get_auto_exposure(bbr_context *ctx, float *out_key, float *out_e_min, float *out_e_max, float *out_rate,
+                          int32_t *out_lo_permille, int32_t *out_hi_permille);
+int bbr_reset_exposure(bbr_context *ctx);
+int bbr_present_buffer_auto(bbr_context *ctx, const void *rgba32f_device, void *rgba8_device, int32_t width, int32_t height,
+                            int32_t enable_tone_mapping, float exposure, int32_t hdr16, void *hip_stream);
+int bbr_read_exposure(bbr_context *ctx, int32_t source, bbr_exposure_record *out);
+int bbr_luminance_timing(bbr_context *ctx, uint32_t *out_launches, float *out_avg_ms);
 
 /* ---- native exchange: every rank gets the whole frame (BASELINE config #4) ----
  * The reference renders on one GPU; with a partition (bbr_set_partition) each rank holds a compact shard and the frame
